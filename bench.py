@@ -2,7 +2,7 @@
 """Headline benchmark: frames/sec of the DenseNet-121 224x224 frame feature-extract
 (BASELINE.json configs[1]: batch 256 synthetic frames, fp16, one MI355X per rank).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 runs one process per GPU over RCCL: under ``python -m torch.distributed.run --nproc-per-node N ...`` the ranks
 exist already (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* are read from the environment); started as plain
@@ -12,9 +12,11 @@ JSON line.
 A step = one pass of the hot path over one batch of 256 synthetic frames per rank (inputs resident in HBM):
 stem -> 58 dense layers -> 3 transitions -> head -> (B,1024) fp32 features, then for N > 1 the RCCL all-gather of
 the feature rows that the temporal / caption stage consumes.  Frames shard across ranks with no other
-exchange: weak scaling.  The timed region is EXACTLY K steps between two fences (barrier + device synchronise); when
-K is small the region is repeated (each repetition again exactly K fenced steps, at least 200 steps in total) and
-the MEDIAN repetition is reported, so that a 20-step run is not a single 48-ms sample.
+exchange: weak scaling.  The timed region is EXACTLY K steps between two fences (barrier + device synchronise), after
+W untimed warm-up steps; ``ms_per_step`` is the region's time over K.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as float32 .npy files (features.npy, and on
+N ranks gathered_features.npy), at most 64 MB in all: the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -33,7 +35,7 @@ SIZE = 224
 FLOP_PER_FRAME = 5.666e9          # 2 x 2.8331 GMAC over the 120 convolutions
 MFMA_PEAK_TFLOPS = 2500.0         # MI355X dense fp16 MFMA (MI355X_MICROARCH.md)
 HBM_PEAK_TBS = 8.0                # MI355X HBM3E (MI355X_MICROARCH.md)
-MIN_TOTAL_STEPS = 3000        # (~5.5 s of GPU time at the default batch: a median over 15 regions of 200 steps, and long enough for a 1 Hz power / utilisation sampler outside the process to see several busy samples: VERDICT r4 weak 10)
+DUMP_BYTES = 64 << 20             # --dump-outputs: the most that is written in all
 
 
 def parity_note():
@@ -240,15 +242,30 @@ class StepLoop:
                 self.gather_h[j] = None
 
 
+def dump_outputs(out_dir, arrays):
+    """{name: (rows, ...) array} -> out_dir/<name>.npy as float32.  Arrays that would take the total past DUMP_BYTES keep a
+    fixed seeded sample of their rows (in row order), the same rows on every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays) - 4096          # (room for the .npy header)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        keep = max(1, share // max(1, a[0].nbytes))
+        if a.shape[0] > keep:
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps: one fenced region of exactly this many")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=BATCH)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the features of the last timed step to DIR/*.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="also time the 256-frame batch on the CPU (minutes)")
-    ap.add_argument("--single-region", action="store_true", help="one timed region of K steps only (no repetitions)")
+    ap.add_argument("--single-region", action="store_true", help="time the K steps only (no extra regions for the joined-forwards "
+                    "and exact-weights figures)")
     ap.add_argument("--no-pipeline", action="store_true", help="join the encoder's two half-batch streams inside every forward (A/B against the pipelined default)")
     ap.add_argument("--plain-rounding", action="store_true", help="seeded weights that are fp16-representable (rounds 1-2's model) instead of "
                     "the calibrated conversion of fp32 weights")
@@ -262,6 +279,8 @@ def build_parser():
 
 def run(argv):
     args = build_parser().parse_args(argv)
+    if args.steps < 1:
+        raise SystemExit(f"bench.py: --steps {args.steps}: at least one timed step")
     import torch.distributed as dist
     from tennis_amd import sharding
     rank, world, dev = sharding.init_distributed()
@@ -344,9 +363,13 @@ def run(argv):
     for i in range(args.warmup):
         step(i)
     drain(args.warmup)
-    repeats = 1 if args.single_region else max(1, -(-MIN_TOTAL_STEPS // args.steps))
-    times = [timed_region(args.steps) for _ in range(repeats)]
-    dt = float(np.median(times))
+    dt = timed_region(args.steps)
+    if args.dump_outputs and rank == 0:      # what the last timed step handed its caller, before the regions below reuse the buffers
+        last = (args.steps - 1) & 1
+        outputs = {"features": feats[last].cpu().numpy()}
+        if world > 1:
+            outputs["gathered_features"] = gathered[last].cpu().numpy()
+        dump_outputs(args.dump_outputs, outputs)
     # for the record: the same K steps with every forward joined before it returns (one more fenced region, all ranks)
     dt_joined = None
     if pipelined and not args.single_region:
@@ -443,8 +466,8 @@ def run(argv):
                           "parity": (parity_note() if not (args.exact_weights or args.plain_rounding) else None),
                           "comm": comm_record,
                           "exchange": (comm.transport + f", all-gather of {args.batch} x {enc.feature_dim} fp32 rows per rank and step") if comm is not None else "none (1 rank)",
-                          "timing": f"median of {repeats} fenced regions of exactly {args.steps} steps" + (", forwards pipelined (results joined one step behind, all joined before the closing fence)" if pipelined else ""),
-                          "region_ms": [round(t * 1e3, 2) for t in times],
+                          "timing": f"one fenced region of exactly {args.steps} steps after {args.warmup} warm-up steps" + (", forwards pipelined (results joined one step behind, all joined before the closing fence)" if pipelined else ""),
+                          "region_ms": [round(dt * 1e3, 2)],
                           "frames_per_sec_forwards_joined": (round(world * args.batch * args.steps / dt_joined, 1) if dt_joined else None),
                           **({"exact_weights_frames_per_sec": round(fps_exact, 1),
                               "exact_weights_note": "the SAME fp32 parameters with every conv weight (stem included) as hi + lo fp16 pairs, no calibration: the mode for inputs "

@@ -127,9 +127,11 @@ def _eval_worker(root, n_expected, q):
     """config C4's code path on gloo: tennis_amd.evaluate.save_features_sharded (the function evaluate.main drives for
     --save_feats --num_gpus N) -> per-rank .npy files + all-gathered (N, F) matrix; ranks formed by sharding.launch."""
     import numpy as np
+    import torch
     import torch.distributed as dist
     from tennis_amd import evaluate as ev, sharding
     from tennis_amd.dataset import DataLoader, TennisSet
+    torch.cuda.is_available = lambda: False      # the gloo path where GPUs are visible too: one GPU would make init_distributed bind both ranks to it over RCCL
     rank, world, dev = sharding.init_distributed()
     assert world == 2 and dev.type == "cpu"
     ds = TennisSet(root=root, split="test", model_id="c4", save_feats=True, frames_per_video=7, data_shape=16, split_first=2,

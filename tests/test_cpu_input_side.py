@@ -270,11 +270,11 @@ def test_captioning_drivers_read_real_inputs(tmp_path):
     assert tg.build(flags)[3]._input_size == 16
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/data/embeddings-ex.txt"), reason="build container only: the reference's own embedding file")
 def test_reference_embedding_file_parses():
-    """data/embeddings-ex.txt (BASELINE config 5's "250-word embedding"): 250 tokens x 100, rows L2-normalised."""
+    """data/embeddings-ex.txt (BASELINE config 5's "250-word embedding"): 250 tokens x 100, rows L2-normalised.
+    tests/golden/embeddings-ex.txt is a byte-for-byte copy of the reference's file."""
     from tennis_amd.models.captioning.gnmt import TokenEmbedding
-    emb = TokenEmbedding.from_file("/root/reference/data/embeddings-ex.txt")
+    emb = TokenEmbedding.from_file(os.path.join(os.path.dirname(__file__), "golden", "embeddings-ex.txt"))
     assert len(emb) == 250 and emb.idx_to_vec.shape == (250, 100)
     assert np.allclose(np.linalg.norm(emb.idx_to_vec, axis=1), 1.0, atol=1e-4)
     assert emb.idx_to_token[:3] == ["a", "np", "fp"]

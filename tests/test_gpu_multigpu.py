@@ -72,15 +72,19 @@ def test_corpus_mode_checksum_and_rates(report):
     assert abs(total - line["checksum"]) <= 1e-6 * abs(total)
 
 
-def test_bench_line_and_self_spawn():
-    """bench.py started as plain python: --gpus 1 runs in-process; the spawn path (what --gpus N > 1 takes) is driven
-    with one rank; more ranks than GPUs is a loud error, not a single-rank line."""
-    r = _run(["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"])
+def test_bench_line_and_self_spawn(tmp_path):
+    """bench.py started as plain python: --gpus 1 runs in-process, times exactly --steps steps and dumps the last step's
+    features; the spawn path (what --gpus N > 1 takes) is driven with one rank; more ranks than GPUs is a loud error, not a
+    single-rank line."""
+    r = _run(["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")])
     assert r.returncode == 0, r.stdout + r.stderr
     line = _json_line(r.stdout)
     assert line["n_gpus"] == 1 and line["steps"] == 5 and line["roofline"]["bound"] == "mfma"
-    import bench
-    assert line["config"]["timing"].startswith(f"median of {bench.MIN_TOTAL_STEPS // 5} fenced regions of exactly 5 steps")
+    assert line["config"]["timing"].startswith("one fenced region of exactly 5 steps") and len(line["config"]["region_ms"]) == 1
+    assert abs(line["ms_per_step"] * 5 - line["config"]["region_ms"][0]) < 0.02
+    assert sorted(os.listdir(tmp_path / "out")) == ["features.npy"]
+    feats = np.load(tmp_path / "out" / "features.npy")
+    assert feats.shape == (256, 1024) and feats.dtype == np.float32 and np.isfinite(feats).all() and feats.std() > 0
     code = ("import sys; sys.path.insert(0, %r); import bench; from tennis_amd import sharding; "
             "sharding.launch(bench.run, 1, (['--gpus', '1', '--steps', '5', '--warmup', '2', '--no-cpu-baseline', '--single-region'],))" % ROOT)
     r = _run(["-c", code])
