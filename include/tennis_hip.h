@@ -111,7 +111,8 @@ int tn_densenet121_join(tn_encoder *enc, int lag);
  * `batch` frames go through the layer-wise kernels, and for each of the 119 convolutions behind the stem, in execution order
  * (per dense layer the 1x1's K input channels, then the 3x3's 128; a transition's inputs after its block), the mean over all
  * pixels of the OPERAND that convolution's folded weights multiply is written to means_host (fp32, *numel values): for a dense
- * layer's 1x1 the clamped stored activation clamp(x, lo, hi) (tn_bn_relu_clamp_fold; relu(bn(x)) = sw * that + tc), for its 3x3
+ * layer's 1x1 the clamped stored activation clamp(x, lo, hi) (tn_bn_relu_clamp_fold; relu(bn(x)) = sw * that + tc; exactly 0 in a
+ * channel the fold made a constant, lo == hi), for its 3x3
  * the ReLU'd bottleneck, for a transition relu(bn(x)).  (The stem's operand mean, x - 255 mean_c, is a property of the frame and
  * is computed by the caller.) */
 int tn_densenet121_input_means(tn_encoder *enc, const void *x, tn_layout layout, int batch, float *means_host,

@@ -57,6 +57,11 @@ int tn_dbg_dense_layer_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K, const flo
                            int H, int W, unsigned long long *ts /* NULL or stamps */, int variant /* 0 auto, 1 big, 2 small */);
 int tn_dbg_linear(tn_ctx *ctx, const float *x, const float *w, const float *bias, float *y, int M, int N,
                   int K);
+/* The reduction behind tn_densenet121_input_means on its own: out[c] (device fp32, K values) = mean over `rows` rows of the device
+ * fp16 matrix x (rows, ld) of relu(scale[c] x + shift[c]), or with `clamp` of clamp(x, lo = scale[c], hi = shift[c]); scale / shift
+ * device fp32, scratch a device buffer of scratch_bytes >= 32 K doubles.  Synchronous. */
+int tn_dbg_channel_mean(tn_ctx *ctx, const void *x_f16, int ld, int K, const float *scale, const float *shift, int64_t rows,
+                        void *scratch, size_t scratch_bytes, float *out, int clamp);
 /* The strip-streaming fused dense layer (csrc/dense_strip.hip; 56x56 / 28x28 blocks, K <= 320): fp32 (128,K) 1x1 weights
  * with the folded scale / shift (128 each) of the BatchNorm behind them, and (32,128,3,3) 3x3 weights -> the MFMA
  * A-fragment images the kernel keeps resident in LDS ((K+16)*128 and 36864 halves; either output may be NULL), and one

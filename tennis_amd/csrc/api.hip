@@ -247,6 +247,7 @@ struct tn_encoder {
   float *stem_scale, *stem_shift, *stem_shift_u8;
   float *stem_floor = nullptr;                               // centred stem output (round 6): the ReLU's floor -m_c on the device
   std::vector<float> stem_centre;                            // m_c on the host (read_tap / input_means add it back)
+  std::vector<float> calib_centre;                           // per block-1 dense layer, 64 each: m_c, or 0 where the layer's clamp is a constant (lo == hi)
   struct DenseLayer { float *s1, *t1; f16 *w1; float *s2, *t2; f16 *w3p; int cin; f16 *w1s = nullptr, *w3s = nullptr; };   // w1s / w3s: fragment images of the strip kernel
   std::vector<DenseLayer> layers[4];
   struct Trans { float *s, *t; f16 *w; int cin, cout; f16 *wfrag = nullptr; } trans[3];      // wfrag: w in MFMA operand order (trans_ws.hip)
@@ -440,6 +441,11 @@ extern "C" int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int
       std::vector<float> sw1(L.cin), tc1(L.cin);
       bn_relu_clamp_fold(std::vector<float>(s).data(), std::vector<float>(t).data(), L.cin, s.data(), t.data(), sw1.data(), tc1.data());
       L.s1 = e->pool.upload(s); L.t1 = e->pool.upload(t);
+      // input_means hands out block 1's 1x1 operand means in the reference graph's units, clamp(x_centred, lo, hi) + m_c - except in
+      // a channel the fold made a constant (scale 0 / not finite, or a threshold past the fp16 range on the clipped side): its operand
+      // is 0 whatever the centring
+      if (b == 0)
+        for (int c = 0; c < 64; ++c) e->calib_centre.push_back(s[c] != t[c] ? e->stem_centre[c] : 0.f);
       // x0[k] = clamp(0, lo, hi): the operand's value on the CLIPPED side of a channel whose ReLU is off at x = 0 (round 6, below)
       std::vector<float> x0(L.cin);
       for (int k = 0; k < L.cin; ++k) x0[k] = std::fmin(std::fmax(0.f, s[k]), t[k]);
@@ -920,14 +926,15 @@ extern "C" int tn_densenet121_input_means(tn_encoder *e, const void *x, tn_layou
   if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = TN_ERR_HIP;
   if (!rc) {      // block 1's 1x1 operands are clamps of the CENTRED stem channels: hand out the means in the reference graph's units
     int64_t o = 0;
-    for (auto &L : e->layers[0]) {
-      for (int c = 0; c < 64; ++c) means_host[o + c] += e->stem_centre[c];
-      o += L.cin + 128;
+    for (size_t l = 0; l < e->layers[0].size(); ++l) {
+      for (int c = 0; c < 64; ++c) means_host[o + c] += e->calib_centre[l * 64 + c];
+      o += e->layers[0][l].cin + 128;
     }
   }
   release();
   if (rc == TN_ERR_HIP) tn_set_error("tn_densenet121_input_means: HIP error");
   e->last_batch = batch;
+  e->last_ws0 = 0;      // (the pass ran in workspace set 0: read_tap reads its frames, not those of a pipelined forward in set 1)
   return rc;
 }
 

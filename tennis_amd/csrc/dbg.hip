@@ -115,6 +115,21 @@ extern "C" int tn_dbg_dense_layer_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K
   return launch_dense_layer(a, ctx->stream);
 }
 
+// The calibration statistic of tn_densenet121_input_means on its own: per-channel mean over `rows` rows of x (rows, ld) fp16 of
+// relu(scale x + shift), or of clamp(x, lo = scale, hi = shift) with `clamp`; one synchronous launch_channel_mean, all operands
+// on the device, the scratch the caller's (scratch_bytes: at least 32 K doubles)
+extern "C" int tn_dbg_channel_mean(tn_ctx *ctx, const void *x_f16, int ld, int K, const float *scale, const float *shift, int64_t rows,
+                                   void *scratch, size_t scratch_bytes, float *out, int clamp) {
+  TN_REQUIRE(ctx && x_f16 && scale && shift && scratch && out, "tn_dbg_channel_mean: null argument");
+  TN_REQUIRE(K > 0 && ld >= K && rows > 0, "tn_dbg_channel_mean: bad shape");
+  TN_REQUIRE(scratch_bytes >= (size_t)32 * K * sizeof(double), "tn_dbg_channel_mean: scratch smaller than 32 K doubles");
+  TN_ON_DEVICE(ctx->device);
+  const int rc = launch_channel_mean((const f16 *)x_f16, ld, K, scale, shift, (long)rows, (double *)scratch, out, ctx->stream, clamp != 0);
+  if (rc) return rc;
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+
 // fp32 linear: y = x W^T + b
 extern "C" int tn_dbg_linear(tn_ctx *ctx, const float *x, const float *w, const float *bias, float *y, int M, int N,
                              int K) {

@@ -811,3 +811,48 @@ def test_conversion_keeps_the_weights_of_near_dead_channels():
     live = ~dead
     rel = np.abs(conv[:, live] - w[:, live]) / np.abs(w[:, live])
     assert rel.max() < 2.0 ** -10 and (conv[:, live] != w[:, live]).mean() > 0.9        # rounded once, to a neighbour
+
+
+def test_operand_means_oracle_units_hold_together():
+    """tests/tools/operand_means.py, the fp64 oracle of tn_densenet121_input_means, at 224x224 on one frame: the 119 keys are exactly
+    the non-stem convolutions of densenet121_layout() in execution order, their lengths add up to the library's numel (per dense layer
+    K + 128, per transition its K), and the two units of a dense layer's 1x1 hold together - sw * mean(clamp(x, lo, hi)) + tc is the
+    mean of relu(bn(x)) from the same graph, up to |s| times the fp16 rounding of the ReLU threshold.  On the parameter set with
+    planted degenerate channels, whose clamp operand is exactly 0."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from tools import operand_means as OM
+    pre = "densenet0_"
+    p = OM.with_degenerate_channels(W.make_densenet121_weights(0))
+    relu = {}
+    m = OM.operand_means(p, W.synthetic_frames_u8(1, 224), relu_means=relu)
+    convs, _, _ = W.densenet121_layout()
+    assert list(m) == [pre + c["name"] + "_weight" for c in convs if c["kind"] != "stem"]
+    assert all(m[pre + c["name"] + "_weight"].shape == (1, c["cin"]) for c in convs if c["kind"] != "stem")
+    numel, c = 0, W.INIT_FEATURES                     # csrc/api.hip tn_densenet121_input_means
+    for b, nl in enumerate(W.BLOCK_CONFIG):
+        numel += sum(c + W.GROWTH * l + 128 for l in range(nl))
+        c += W.GROWTH * nl
+        if b < 3:
+            numel += c
+            c //= 2
+    assert sum(v.size for v in m.values()) == numel == 40736
+    assert set(relu) == {pre + c["name"] + "_weight" for c in convs if c["kind"] == "dense1x1"}
+    n_off = 0
+    for c in (c for c in convs if c["kind"] == "dense1x1"):
+        k, bn = pre + c["name"] + "_weight", pre + c["bn"]
+        lo, hi, sw, tc = W.bn_relu_clamp_fold(p, bn)
+        s = (p[bn + "_gamma"] / np.sqrt(p[bn + "_running_var"] + np.float32(W.BN_EPS))).astype(np.float32).astype(np.float64)
+        t = (p[bn + "_beta"] - p[bn + "_running_mean"] * s.astype(np.float32)).astype(np.float32).astype(np.float64)
+        thr = np.where(s > 0, lo, hi).astype(np.float64)
+        off = lo == hi
+        slack = np.where(off, 0.0, np.abs(s) * np.abs(thr + t / np.where(s != 0, s, 1.0)))
+        got = sw.astype(np.float64) * m[k][0] + tc
+        want = relu[k][0]
+        assert (np.abs(got - want) <= slack + 1e-6 * (np.abs(want) + np.abs(tc) + np.abs(sw) * np.abs(m[k][0])) + 1e-9).all(), k
+        assert (m[k][0][off] == 0).all()
+        n_off += int(off.sum())
+    assert n_off == 3                                 # the three planted degenerate channels of stage1_conv4's operand
+    bn = pre + "stage1_batchnorm4"
+    assert list(np.flatnonzero(W.bn_relu_clamp_fold(p, bn)[0] == W.bn_relu_clamp_fold(p, bn)[1])) == [3, 17, 58]
+    assert W.bn_relu_clamp_fold(p, bn)[2][40] < 0 and m[pre + "stage1_conv4_weight"][0][40] > 0
