@@ -88,6 +88,15 @@ int tn_densenet121_create(tn_ctx *ctx, const tn_param *params, int n_params, con
  * fp16 once (the served fp16 model).  Any input size since round 6 (maps no fused kernel tiles run their layers un-fused with the
  * same hi + lo pass; flat frames at 448 x 448 / 512 x 512 keep a tail of 1.2e-3 that is the fp16 activation path's: DESIGN.md section 4). */
 #define TN_ENC_EXACT_WEIGHTS 1
+/* TN_ENC_FP32: the reference's own evaluation - fp32 parameters evaluated in fp32 (models/vision/definitions.py:27-33) - for
+ * any checkpoint.  Every activation is stored in fp32 and every product is formed in fp32 on the f32-input MFMA (exact f32,
+ * a k-ordered fma chain); the weights are the raw fp32 parameters (no fp16 conversion, no hi + lo split), the BatchNorms are
+ * folded in double and rounded to fp32 once.  Features within 1e-3 of the fp32 reference on every frame family, seeded and
+ * trained-looking parameters, every input size, at the f32 matrix rate (1/16 of fp16).  Its own kernels
+ * (csrc/dense_fp32.hip) and its own fp32 workspace; every input layout, any batch up to max_batch, pipelined forwards and
+ * the per-family profile (families "fp32_*").  tn_densenet121_input_means and tn_densenet121_read_tap refuse such an encoder.
+ * TN_ENC_FP32 | TN_ENC_EXACT_WEIGHTS selects this mode as well. */
+#define TN_ENC_FP32 4
 int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int n_params, const char *prefix, int height, int width,
                              int max_batch, int flags, tn_encoder **out);
 int tn_densenet121_feature_dim(const tn_encoder *enc);

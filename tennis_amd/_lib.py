@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("TENNIS_HIP_LIB") or os.path.join(_HERE, "lib", "libte
 
 LAYOUT_NCHW_F32, LAYOUT_NHWC_F16, LAYOUT_NHWC_U8 = 0, 1, 2
 ENC_EXACT_WEIGHTS = 1
+ENC_FP32 = 4
 RNN_GRU, RNN_LSTM = 0, 1
 POOL_MAX, POOL_MEAN = 0, 1
 

@@ -336,3 +336,25 @@ int launch_channel_mean(const f16 *x, int ld, int K, const float *scale, const f
                         float *out, hipStream_t s, int clamp = 0 /* scale / shift are lo / hi of the clamp form */);
 int launch_head(const f16 *x, int B, int H, int W, int C, const float *scale, const float *shift,
                 float *feat, int PH, int PW, hipStream_t s, const float *x32 = nullptr /* the same map un-rounded: read instead of x */);
+
+// ---- the fp32 encoder mode (TN_ENC_FP32, dense_fp32.hip): fp32 activations, fp32 weights, f32-input MFMA ----
+enum { FP32_STEM = 0, FP32_1X1 = 1, FP32_3X3 = 2, FP32_TRANS = 3 };
+struct Fp32ConvArgs {
+  int kind;              // FP32_*: which operand the GEMM's A tile is built from
+  const void *x;         // stem: the input frames in `layout`; otherwise an fp32 NHWC map [B][H][W][ldx]
+  int layout;            // stem only (tn_layout)
+  int ldx;               // channel stride of x (the 3x3: 128, the dense bottleneck)
+  int K;                 // reduction length: stem 147, 1x1 / transition the input channels, 3x3 9 * 128
+  const float *s, *t;    // BatchNorm applied (then ReLU) to the operand as it is loaded: [K] (3x3: [128]); unused by the stem
+  const float *w;        // [Kp][N] fp32, Kp = K rounded up to 32 with zero rows
+  int N;                 // output channels (stem 64, 1x1 128, 3x3 32, transition cout)
+  const float *es, *et;  // [N] epilogue BatchNorm + ReLU (the stem), nullptr: the raw product
+  float *y;              // [M][ldy] fp32, columns [yoff, yoff + N)
+  int ldy, yoff;
+  long M;                // output pixels B * Ho * Wo
+  int H, W;              // input map (stem: frame) size
+  int Ho, Wo;            // output map size
+};
+int launch_conv_fp32(const Fp32ConvArgs &a, hipStream_t s);
+// 3x3 stride 2 pad 1 max pool of an fp32 [B][H][W][64] map into channels [0, 64) of a map with channel stride ldy
+int launch_maxpool_fp32(const float *x, int B, int H, int W, float *y, int ldy, int Ho, int Wo, hipStream_t s);

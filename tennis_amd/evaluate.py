@@ -299,11 +299,12 @@ def best_or_newest_params(mod_path, need_scores):
 def build_parser():
     p = argparse.ArgumentParser(description="tennis_amd evaluate (flags of reference evaluate.py:30-75)")
     p.add_argument("--backbone", default="DenseNet121")
-    p.add_argument("--fp16_conversion", default="nearest", choices=["nearest", "calibrated", "exact"],
+    p.add_argument("--fp16_conversion", default="nearest", choices=["nearest", "calibrated", "exact", "fp32"],
                    help="how the checkpoint's fp32 conv weights become the fp16 model (not a reference flag): plain rounding, "
                         "rounding calibrated on the library's built-in calibration frames (the same model on every rank; features within "
-                        "1e-3 of the fp32 evaluation on natural content at full speed, DESIGN.md), or hi + lo weight pairs (the bar "
-                        "on any input at twice the MFMAs)")
+                        "1e-3 of the fp32 evaluation on natural content at full speed, DESIGN.md), hi + lo weight pairs (twice the "
+                        "MFMAs), or fp32: no conversion, the network evaluated in fp32 (the fp32 evaluation of any checkpoint within "
+                        "1e-3, at the f32 matrix rate)")
     p.add_argument("--model_id", default="0000")
     p.add_argument("--split_id", default="02")
     p.add_argument("--split", default="test")
