@@ -98,6 +98,20 @@ int tn_dbg_block28_run(void *handle, void *buf_f16, int ldc, int B);
 int tn_dbg_block28_run_ts(void *handle, void *buf_f16, int ldc, int B, unsigned long long *ts);
 void tn_dbg_block28_destroy(void *handle);
 
+/* The training kernels of the fine-tuning step (csrc/train.hip, linear.hip, finetune.hip) through the launchers the step calls; all
+ * operands device fp32, synchronous.
+ * tn_dbg_gemm_tn: C (M, N; row stride ldc) = A^T B over K rows, A (K, lda), B (K, ldb); bsc / bsh non-NULL: B -> relu(B bsc[n] + bsh[n])
+ * first.  workspace / workspace_floats: the caller's split-K scratch (NULL: never split) - it decides whether and how far K is split. */
+int tn_dbg_gemm_tn(tn_ctx *ctx, const float *A, int lda, const float *B, int ldb, const float *bsc, const float *bsh, float *Cm, int ldc,
+                   int M, int N, int K, float *workspace, int64_t workspace_floats);
+/* Y (M, N; row stride ldy) (+)= relu(X asc[k] + ash[k]) W^T (+ bias), X (M, ldx), W (N, ldw); accumulate: add to Y. */
+int tn_dbg_linear_bnrelu(tn_ctx *ctx, const float *X, int ldx, const float *asc, const float *ash, const float *W, int ldw,
+                         const float *bias, float *Y, int ldy, int M, int N, int K, int accumulate);
+/* Training-mode BatchNorm + ReLU of an (M, C) matrix x of row stride ld >= C: mean / var (C each, biased), y (M, C contiguous).
+ * dy (M, C contiguous) non-NULL: also dgamma, dbeta (C each) and dx (row stride ldd), assigned or accumulated. */
+int tn_dbg_bn_train(tn_ctx *ctx, const float *x, int ld, int64_t M, int C, const float *gamma, const float *beta, float *mean, float *var,
+                    float *y, const float *dy, float *dgamma, float *dbeta, float *dx, int ldd, int accumulate);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,9 @@ _SIGS = {
                                          _P, C.c_int]),
     "tn_dbg_linear": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_channel_mean": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int64, _P, C.c_size_t, _P, C.c_int]),
+    "tn_dbg_gemm_tn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
+    "tn_dbg_linear_bnrelu": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tn_dbg_bn_train": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int]),
     "tn_comm_unique_id": (C.c_int, [_P]),
     "tn_comm_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(_P)]),
     "tn_comm_rank": (C.c_int, [_P]),

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "linear.h"
+#include "train.h"
 
 namespace {
 template <typename T>
@@ -364,4 +365,49 @@ extern "C" void tn_dbg_block28_destroy(void *handle) {
   (void)hipFree(b->stream);
   (void)hipFree(b->scratch);
   delete b;
+}
+
+// The fine-tuning step's transposed GEMM (weight gradients): the split-K policy of gemm_tn_dispatch on the caller's workspace
+extern "C" int tn_dbg_gemm_tn(tn_ctx *ctx, const float *A, int lda, const float *B, int ldb, const float *bsc, const float *bsh, float *Cm,
+                              int ldc, int M, int N, int K, float *workspace, int64_t workspace_floats) {
+  TN_REQUIRE(ctx && A && B && Cm && (bsc == nullptr) == (bsh == nullptr), "tn_dbg_gemm_tn: null argument");
+  TN_REQUIRE(M > 0 && N > 0 && K > 0 && lda >= M && ldb >= N && ldc >= N && workspace_floats >= 0, "tn_dbg_gemm_tn: bad shape");
+  TN_ON_DEVICE(ctx->device);
+  const int rc = bsc ? launch_gemm_tn_f32_bnrelu(A, lda, B, ldb, bsc, bsh, Cm, ldc, M, N, K, ctx->stream, workspace, workspace_floats)
+                     : launch_gemm_tn_f32(A, lda, B, ldb, Cm, ldc, M, N, K, ctx->stream, workspace, workspace_floats);
+  if (rc) return rc;
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+
+// The forward 1x1 convolution of the fine-tuning step with its BatchNorm + ReLU applied to the X operand
+extern "C" int tn_dbg_linear_bnrelu(tn_ctx *ctx, const float *X, int ldx, const float *asc, const float *ash, const float *W, int ldw,
+                                    const float *bias, float *Y, int ldy, int M, int N, int K, int accumulate) {
+  TN_REQUIRE(ctx && X && asc && ash && W && Y, "tn_dbg_linear_bnrelu: null argument");
+  TN_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= K && ldw >= K && ldy >= N, "tn_dbg_linear_bnrelu: bad shape");
+  TN_ON_DEVICE(ctx->device);
+  const int rc = launch_linear_f32_bnrelu(X, ldx, asc, ash, W, ldw, bias, Y, ldy, M, N, K, accumulate, ctx->stream);
+  if (rc) return rc;
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+
+// The fine-tuning step's training-mode BatchNorm + ReLU and its backward (the same reduction slices as the step), scratch of its own
+extern "C" int tn_dbg_bn_train(tn_ctx *ctx, const float *x, int ld, int64_t M, int C, const float *gamma, const float *beta, float *mean,
+                               float *var, float *y, const float *dy, float *dgamma, float *dbeta, float *dx, int ldd, int accumulate) {
+  TN_REQUIRE(ctx && x && gamma && beta && mean && var && y, "tn_dbg_bn_train: null argument");
+  TN_REQUIRE(!dy || (dgamma && dbeta && dx), "tn_dbg_bn_train: dy needs dgamma, dbeta and dx");
+  TN_REQUIRE(M > 0 && C > 0 && ld >= C && (!dy || ldd >= C), "tn_dbg_bn_train: bad shape");
+  TN_ON_DEVICE(ctx->device);
+  float *ws = nullptr;
+  TN_HIP_CHECK(hipMalloc((void **)&ws, sizeof(float) * ft_bn_ws_floats((long)M, C)));
+  int rc = launch_ft_bn_stats(x, ld, (long)M, C, ws, mean, var, ctx->stream);
+  if (!rc) rc = launch_ft_bn_relu(x, ld, (long)M, C, mean, var, gamma, beta, y, ctx->stream);
+  if (!rc && dy) rc = launch_ft_bn_backward(dy, x, ld, (long)M, C, mean, var, gamma, beta, ws, dgamma, dbeta, dx, ldd, accumulate, ctx->stream);
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(ws);
+  if (rc) return rc;
+  TN_HIP_CHECK(e);
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
 }

@@ -91,25 +91,47 @@ __global__ void ft_col2im3_kernel(const float *__restrict__ dcol, int B, int H, 
 
 // ---- BatchNorm (training mode) + ReLU ---------------------------------------------------------------------------------
 // batch mean and biased variance of columns [0,C) of x (row stride ld).  Grid (C/64, RS): 64 columns x one of RS row slices
-// per workgroup; one pass over the data with the column's first element as the shift (sums of (x - x0) and (x - x0)^2:
-// no cancellation worth speaking of since x0 lies inside the data), slices added in order by the finish kernel.
+// per workgroup; one pass over the data as sums of (x - k) and (x - k)^2 about a shift k near the mean, slices added in order
+// (in double) by the finish kernel, which forms var = s2/M - d^2 with d = s1/M.  That difference cancels (k - mean)^2 / var of
+// its digits: k is the float64 mean of kStatSamples rows spread over the column, the same in every workgroup, so d is
+// about sigma / 8 for any column.  (The column's first row, the shift this used to take, is a zero-padded convolution's corner
+// pixel: 30 sigma from the mean it cost the variance three digits.)  A constant column gets k = the constant and var = 0 exactly.
+constexpr int kStatSamples = 64;
 __global__ __launch_bounds__(1024) void ft_bn_stats_kernel(const float *__restrict__ x, int ld, long M, int C,
                                                            float *__restrict__ part) {
   __shared__ float p1[16][64], p2[16][64];
+  __shared__ double ks[16][64];
   const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
   const long stride = 16L * gridDim.y;
+  // the shift: row group rg takes samples rg * 4 .. rg * 4 + 3, added in a fixed order.  Sample i is row frac((i + 1/2) phi) M:
+  // spread over the column without a stride that a power-of-two frame could alias (an even stride puts every sample on a border)
+  double k4 = 0.0;
+  if (c < C) {
+#pragma unroll
+    for (int j = 0; j < kStatSamples / 16; ++j) {
+      double f = (rg * (kStatSamples / 16) + j + 0.5) * 0.6180339887498949;
+      f -= floor(f);
+      const long r = min((long)(f * (double)M), M - 1);
+      k4 += (double)x[r * ld + c];
+    }
+  }
+  ks[rg][cl] = k4;
+  __syncthreads();
+  double ksum = 0.0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) ksum += ks[i][cl];
+  const float k = (float)(ksum / kStatSamples);
   float a1 = 0.f, a2 = 0.f;
   if (c < C) {
-    const float x0 = x[c];
     long r = (long)blockIdx.y * 16 + rg;
     for (; r + 15 * stride < M; r += 16 * stride) {
       float v[16];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = x[(r + i * stride) * ld + c] - x0;
+      for (int i = 0; i < 16; ++i) v[i] = x[(r + i * stride) * ld + c] - k;
 #pragma unroll
       for (int i = 0; i < 16; ++i) { a1 += v[i]; a2 = fmaf(v[i], v[i], a2); }
     }
-    for (; r < M; r += stride) { const float d = x[r * ld + c] - x0; a1 += d; a2 = fmaf(d, d, a2); }
+    for (; r < M; r += stride) { const float d = x[r * ld + c] - k; a1 += d; a2 = fmaf(d, d, a2); }
   }
   p1[rg][cl] = a1; p2[rg][cl] = a2;
   __syncthreads();
@@ -119,17 +141,18 @@ __global__ __launch_bounds__(1024) void ft_bn_stats_kernel(const float *__restri
     for (int i = 0; i < 16; ++i) { s1 += p1[i][cl]; s2 += p2[i][cl]; }
     part[((long)blockIdx.y * 2 + 0) * C + c] = s1;
     part[((long)blockIdx.y * 2 + 1) * C + c] = s2;
+    if (blockIdx.y == 0) part[(long)gridDim.y * 2 * C + c] = k;
   }
 }
-__global__ void ft_bn_stats_finish_kernel(const float *__restrict__ part, int RS, int C, const float *__restrict__ x, long M,
-                                          float *__restrict__ mean, float *__restrict__ var) {
+__global__ void ft_bn_stats_finish_kernel(const float *__restrict__ part, int RS, int C, long M, float *__restrict__ mean,
+                                          float *__restrict__ var) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  float s1 = 0.f, s2 = 0.f;
+  double s1 = 0.0, s2 = 0.0;
   for (int z = 0; z < RS; ++z) { s1 += part[((long)z * 2 + 0) * C + c]; s2 += part[((long)z * 2 + 1) * C + c]; }
-  const float d = s1 / (float)M;
-  mean[c] = x[c] + d;
-  var[c] = fmaxf(s2 / (float)M - d * d, 0.f);
+  const double d = s1 / (double)M;
+  mean[c] = (float)((double)part[(long)RS * 2 * C + c] + d);
+  var[c] = (float)fmax(s2 / (double)M - d * d, 0.0);
 }
 // y (M,C contiguous) = relu(gamma * (x - mean) / sqrt(var + eps) + beta)
 __global__ void ft_bn_relu_kernel(const float *__restrict__ x, int ld, long M, int C, const float *__restrict__ mean,
@@ -362,19 +385,39 @@ static int ft_slices(long M, int C) {
   if (RS > 512 / cb) RS = 512 / cb;
   return RS < 1 ? 1 : RS;
 }
+// The training-mode BatchNorm launchers (train.h), on raw device pointers: what the step calls and what tn_dbg_bn_train runs.
+// ws: at least ft_bn_ws_floats(M, C) floats of reduction slices.  (A launch error is peeked at, not cleared: the step checks once at its end.)
+long ft_bn_ws_floats(long M, int C) { return (2L * ft_slices(M, C) + 1) * C; }
+int launch_ft_bn_stats(const float *x, int ld, long M, int C, float *ws, float *mean, float *var, hipStream_t s) {
+  const int RS = ft_slices(M, C);
+  hipLaunchKernelGGL(ft_bn_stats_kernel, dim3((C + 63) / 64, RS), dim3(1024), 0, s, x, ld, M, C, ws);
+  hipLaunchKernelGGL(ft_bn_stats_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float *)ws, RS, C, M, mean, var);
+  TN_HIP_CHECK(hipPeekAtLastError());
+  return TN_OK;
+}
+int launch_ft_bn_relu(const float *x, int ld, long M, int C, const float *mean, const float *var, const float *gamma, const float *beta,
+                      float *y, hipStream_t s) {
+  hipLaunchKernelGGL(ft_bn_relu_kernel, dim3(nblk(M * C)), dim3(256), 0, s, x, ld, M, C, mean, var, gamma, beta, y);
+  TN_HIP_CHECK(hipPeekAtLastError());
+  return TN_OK;
+}
+int launch_ft_bn_backward(const float *dy, const float *x, int ld, long M, int C, const float *mean, const float *var, const float *gamma,
+                          const float *beta, float *ws, float *dgamma, float *dbeta, float *dx, int ldd, int accumulate, hipStream_t s) {
+  const int cb = (C + 63) / 64, RS = ft_slices(M, C);
+  hipLaunchKernelGGL(ft_bn_bwd_reduce_kernel, dim3(cb, RS), dim3(1024), 0, s, dy, x, ld, M, C, mean, var, gamma, beta, ws);
+  hipLaunchKernelGGL(ft_bn_bwd_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float *)ws, RS, C, dgamma, dbeta);
+  hipLaunchKernelGGL(ft_bn_bwd_apply_kernel, dim3(nblk(M * C)), dim3(256), 0, s, dy, x, ld, M, C, mean, var, gamma, beta,
+                     (const float *)dgamma, (const float *)dbeta, dx, ldd, accumulate);
+  TN_HIP_CHECK(hipPeekAtLastError());
+  return TN_OK;
+}
 static void ft_bn_forward(tn_finetune *f, const FtBn &bn, const float *x, int ld, long M, float *y, hipStream_t s) {
-  const int RS = ft_slices(M, bn.C);
-  hipLaunchKernelGGL(ft_bn_stats_kernel, dim3((bn.C + 63) / 64, RS), dim3(1024), 0, s, x, ld, M, bn.C, f->ws);
-  hipLaunchKernelGGL(ft_bn_stats_finish_kernel, dim3((bn.C + 255) / 256), dim3(256), 0, s, (const float *)f->ws, RS, bn.C, x, M, bn.mean,
-                     bn.var);
-  hipLaunchKernelGGL(ft_bn_relu_kernel, dim3(nblk(M * bn.C)), dim3(256), 0, s, x, ld, M, bn.C, (const float *)bn.mean,
-                     (const float *)bn.var, (const float *)(f->w + bn.o_gamma), (const float *)(f->w + bn.o_beta), y);
+  (void)launch_ft_bn_stats(x, ld, M, bn.C, f->ws, bn.mean, bn.var, s);
+  (void)launch_ft_bn_relu(x, ld, M, bn.C, bn.mean, bn.var, f->w + bn.o_gamma, f->w + bn.o_beta, y, s);
 }
 // batch statistics of columns [0, C) of x into mean / var (no BatchNorm attached: the shared per-channel statistics of a block)
 static void ft_stats(tn_finetune *f, const float *x, int ld, long M, int C, float *mean, float *var, hipStream_t s) {
-  const int RS = ft_slices(M, C);
-  hipLaunchKernelGGL(ft_bn_stats_kernel, dim3((C + 63) / 64, RS), dim3(1024), 0, s, x, ld, M, C, f->ws);
-  hipLaunchKernelGGL(ft_bn_stats_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float *)f->ws, RS, C, x, M, mean, var);
+  (void)launch_ft_bn_stats(x, ld, M, C, f->ws, mean, var, s);
 }
 // relu(x * sc + sh) of a BatchNorm whose batch statistics are known (bn.mean / bn.var)
 static void ft_bn_fold(tn_finetune *f, const FtBn &bn, hipStream_t s) {
@@ -382,20 +425,13 @@ static void ft_bn_fold(tn_finetune *f, const FtBn &bn, hipStream_t s) {
                      (const float *)(f->w + bn.o_gamma), (const float *)(f->w + bn.o_beta), bn.C, bn.sc, bn.sh);
 }
 static void ft_bn_recompute(tn_finetune *f, const FtBn &bn, const float *x, int ld, long M, float *y, hipStream_t s) {
-  hipLaunchKernelGGL(ft_bn_relu_kernel, dim3(nblk(M * bn.C)), dim3(256), 0, s, x, ld, M, bn.C, (const float *)bn.mean,
-                     (const float *)bn.var, (const float *)(f->w + bn.o_gamma), (const float *)(f->w + bn.o_beta), y);
+  (void)launch_ft_bn_relu(x, ld, M, bn.C, bn.mean, bn.var, f->w + bn.o_gamma, f->w + bn.o_beta, y, s);
 }
 // dy (M,C) contiguous -> gradients of gamma / beta into f->g and dx (stride ldd), assigned or accumulated
 static void ft_bn_backward(tn_finetune *f, const FtBn &bn, const float *dy, const float *x, int ld, long M, float *dx, int ldd,
                            int accumulate, hipStream_t s) {
-  const int cb = (bn.C + 63) / 64, RS = ft_slices(M, bn.C);
-  hipLaunchKernelGGL(ft_bn_bwd_reduce_kernel, dim3(cb, RS), dim3(1024), 0, s, dy, x, ld, M, bn.C, (const float *)bn.mean,
-                     (const float *)bn.var, (const float *)(f->w + bn.o_gamma), (const float *)(f->w + bn.o_beta), f->ws);
-  hipLaunchKernelGGL(ft_bn_bwd_finish_kernel, dim3((bn.C + 255) / 256), dim3(256), 0, s, (const float *)f->ws, RS, bn.C,
-                     f->g + bn.o_gamma, f->g + bn.o_beta);
-  hipLaunchKernelGGL(ft_bn_bwd_apply_kernel, dim3(nblk(M * bn.C)), dim3(256), 0, s, dy, x, ld, M, bn.C, (const float *)bn.mean,
-                     (const float *)bn.var, (const float *)(f->w + bn.o_gamma), (const float *)(f->w + bn.o_beta),
-                     (const float *)(f->g + bn.o_gamma), (const float *)(f->g + bn.o_beta), dx, ldd, accumulate);
+  (void)launch_ft_bn_backward(dy, x, ld, M, bn.C, bn.mean, bn.var, f->w + bn.o_gamma, f->w + bn.o_beta, f->ws, f->g + bn.o_gamma,
+                              f->g + bn.o_beta, dx, ldd, accumulate, s);
 }
 
 // conv weight (O, I, kh, kw) as Gluon stores it <-> the GEMM layout (O, kh*kw*I) used here

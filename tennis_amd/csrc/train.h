@@ -24,3 +24,12 @@ int launch_colsum_f32(const float *A, int lda, int rows, int cols, float *out, h
 int launch_sgd_momentum(float *w, const float *g, float *mom, long n, float lr, float momentum, float wd,
                         float rescale, hipStream_t s);
 int launch_transpose_f32(const float *src, int rows, int cols, float *dst, hipStream_t s);
+// Training-mode BatchNorm of the fine-tuning step (finetune.hip) on an (M, C) matrix of row stride ld: batch mean and biased
+// variance; y (M, C contiguous) = relu(gamma (x - mean) / sqrt(var + eps) + beta); its backward from dy (M, C contiguous) into
+// dgamma, dbeta and dx (row stride ldd, assigned or accumulated).  ws: ft_bn_ws_floats(M, C) floats.
+long ft_bn_ws_floats(long M, int C);
+int launch_ft_bn_stats(const float *x, int ld, long M, int C, float *ws, float *mean, float *var, hipStream_t s);
+int launch_ft_bn_relu(const float *x, int ld, long M, int C, const float *mean, const float *var, const float *gamma, const float *beta,
+                      float *y, hipStream_t s);
+int launch_ft_bn_backward(const float *dy, const float *x, int ld, long M, int C, const float *mean, const float *var, const float *gamma,
+                          const float *beta, float *ws, float *dgamma, float *dbeta, float *dx, int ldd, int accumulate, hipStream_t s);
