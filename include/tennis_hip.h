@@ -266,6 +266,36 @@ int tn_finetune_read_param(tn_finetune *f, const char *name, int gradient, float
                            int64_t *numel);
 int tn_finetune_destroy(tn_finetune *f);
 
+/* ---- end-to-end CNN-RNN training step ---------------------------- */
+/* CNNRNN(FrameModel(DenseNet-121 .features)) over TimeDistributed frames, trained as reference train.py:197-236 does with
+ * --window > 1 --temp_pool gru|lstm and no --feats_model: DenseNet-121 .features (BatchNorm in training mode over all
+ * batch x steps frames, which TimeDistributed merges into one batch, utils/layers.py:38-46) -> features (batch*steps, 1024) in frame
+ * order b*steps + t -> bi-GRU / bi-LSTM -> max over T -> Dense(classes) (definitions.py:75-110) -> SoftmaxCrossEntropyLoss per
+ * sample (train.py:324) -> backward of the summed losses (:419-421) through the head and, unless the backbone is frozen
+ * (--freeze_backbone, :231-233), through the backbone -> SGD with momentum and weight decay (:298-299,424).  fp32.
+ * Frozen: no backbone backward and no backbone update; its BatchNorms still normalise with batch statistics and still update
+ * their running statistics (MXNet under ag.record() with grad_req 'null').  The hidden size is read from the parameters.
+ * create: kind as tn_head_create; prefixes of the backbone (e.g. "densenet0_"), the recurrent layer ("cnnrnn0_gru0_") and the
+ * Dense ("cnnrnn0_dense0_"); square frames of a side divisible by 32.  When batch * steps frames do not fit the device, create
+ * returns TN_ERR_NOMEM and its message gives the frames that would.
+ * forward_backward: x (batch, steps, height, width, 3) fp32 normalised NHWC frames and labels (batch,) int32, DEVICE; batch,
+ * steps, height and width must equal the handle's.  loss (batch,) / logits (batch, classes): optional device outputs.
+ * buffers: the flat parameter / gradient arrays of the backbone (as tn_finetune_buffers) and of the head (as tn_head_buffers),
+ * e.g. to all-reduce them over ranks before sgd_step; any output pointer may be NULL.
+ * read_param: the Gluon names of both parts, the backbone's running statistics and its "<bn>_batch_mean" / "<bn>_batch_var". */
+typedef struct tn_cnnrnn_trainer tn_cnnrnn_trainer;
+int tn_cnnrnn_trainer_create(tn_ctx *ctx, tn_rnn_kind kind, const tn_param *params, int n_params, const char *backbone_prefix,
+                             const char *rnn_prefix, const char *dense_prefix, int height, int width, int classes, int batch,
+                             int steps, int freeze_backbone, tn_cnnrnn_trainer **out);
+int tn_cnnrnn_trainer_forward_backward(tn_cnnrnn_trainer *t, const float *x, const int32_t *labels, int batch, int steps,
+                                       int height, int width, float *loss, float *logits);
+int tn_cnnrnn_trainer_buffers(tn_cnnrnn_trainer *t, float **backbone_params, float **backbone_grads, int64_t *backbone_numel,
+                              float **head_params, float **head_grads, int64_t *head_numel);
+int tn_cnnrnn_trainer_sgd_step(tn_cnnrnn_trainer *t, float lr, float momentum, float wd, float rescale_grad);
+int tn_cnnrnn_trainer_read_param(tn_cnnrnn_trainer *t, const char *name, int gradient, float *out_host, int64_t capacity,
+                                 int64_t *numel);
+int tn_cnnrnn_trainer_destroy(tn_cnnrnn_trainer *t);
+
 /* ---- captioner training step ---------------------------------- */
 /* One step of reference train_gnmt.py::train (:328-337) for GRU or LSTM cells (--cell_type), num_layers = 2,
  * num_bi_layers = 1:

@@ -109,6 +109,9 @@ int tn_dbg_linear_bnrelu(tn_ctx *ctx, const float *X, int ldx, const float *asc,
                          const float *bias, float *Y, int ldy, int M, int N, int K, int accumulate);
 /* Training-mode BatchNorm + ReLU of an (M, C) matrix x of row stride ld >= C: mean / var (C each, biased), y (M, C contiguous).
  * dy (M, C contiguous) non-NULL: also dgamma, dbeta (C each) and dx (row stride ldd), assigned or accumulated. */
+/* C (M, N; row stride ldc) = A (M, K; row stride lda) B (K, N; row stride ldb), both row-major: the input gradient of the
+ * CNN-RNN step's bi-RNN head, dX = dGI W_ih (csrc/gemm_nn.hip). */
+int tn_dbg_gemm_nn(tn_ctx *ctx, const float *A, int lda, const float *B, int ldb, float *Cm, int ldc, int M, int N, int K);
 int tn_dbg_bn_train(tn_ctx *ctx, const float *x, int ld, int64_t M, int C, const float *gamma, const float *beta, float *mean, float *var,
                     float *y, const float *dy, float *dgamma, float *dbeta, float *dx, int ldd, int accumulate);
 

@@ -88,6 +88,14 @@ _SIGS = {
     "tn_finetune_sgd_step": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float]),
     "tn_finetune_read_param": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
     "tn_finetune_destroy": (C.c_int, [_P]),
+    "tn_cnnrnn_trainer_create": (C.c_int, [_P, C.c_int, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "tn_cnnrnn_trainer_forward_backward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tn_cnnrnn_trainer_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P),
+                                            C.POINTER(C.c_int64)]),
+    "tn_cnnrnn_trainer_sgd_step": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "tn_cnnrnn_trainer_read_param": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
+    "tn_cnnrnn_trainer_destroy": (C.c_int, [_P]),
     "tn_gnmt_trainer_create": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tn_gnmt_trainer_create_ex": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -122,6 +130,7 @@ _SIGS = {
     "tn_dbg_linear": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_channel_mean": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int64, _P, C.c_size_t, _P, C.c_int]),
     "tn_dbg_gemm_tn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
+    "tn_dbg_gemm_nn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_linear_bnrelu": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_bn_train": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int]),
     "tn_comm_unique_id": (C.c_int, [_P]),

@@ -1329,11 +1329,10 @@ extern "C" int tn_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int
   return TN_OK;
 }
 
-extern "C" int tn_head_forward_backward(tn_head *h, const float *x, const int32_t *labels, int B, int T, float *loss,
-                                        float *logits) {
-  TN_REQUIRE(h && x && labels, "tn_head_forward_backward: null argument");
-  TN_REQUIRE(B > 0 && B <= h->maxB && T > 0 && T <= h->maxT, "tn_head_forward_backward: batch / steps exceed the maxima");
-  TN_ON_DEVICE(h->ctx->device);
+// The head's step on x (B*T, F; rows b*T + t).  dx non-null: also the gradient with respect to x, dX = dGI W_ih (M, F; row
+// stride ldx, assigned) - what the end-to-end CNN-RNN step hands to the backbone's backward.
+static int head_step(tn_head *h, const float *x, const int32_t *labels, int B, int T, float *loss, float *logits, float *dx,
+                     int ldx) {
   hipStream_t s = h->ctx->stream;
   const int F = h->F, H = h->H, C = h->C, GH = h->G * h->H, M = B * T;
   const bool lstm = h->G == 4;
@@ -1359,10 +1358,19 @@ extern "C" int tn_head_forward_backward(tn_head *h, const float *x, const int32_
     TN_TRY(launch_gemm_tn_f32(dgh + d * GH, 2 * GH, h->hprev + (long)d * M * H, H, g + h->o_wh + (long)d * GH * H, H,
                               GH, H, M, s));
   TN_TRY(launch_colsum_f32(dgh, 2 * GH, M, 2 * GH, g + h->o_bh, s));
+  if (dx) TN_TRY(launch_gemm_nn_f32(h->dgi, 2 * GH, w + h->o_wi, F, dx, ldx, M, F, 2 * GH, 0, s));   // dX = dGI W_ih
 #undef TN_TRY
   if (loss) TN_HIP_CHECK(hipMemcpyAsync(loss, h->loss, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
   if (logits) TN_HIP_CHECK(hipMemcpyAsync(logits, h->logits, sizeof(float) * B * C, hipMemcpyDeviceToDevice, s));
   return TN_OK;
+}
+
+extern "C" int tn_head_forward_backward(tn_head *h, const float *x, const int32_t *labels, int B, int T, float *loss,
+                                        float *logits) {
+  TN_REQUIRE(h && x && labels, "tn_head_forward_backward: null argument");
+  TN_REQUIRE(B > 0 && B <= h->maxB && T > 0 && T <= h->maxT, "tn_head_forward_backward: batch / steps exceed the maxima");
+  TN_ON_DEVICE(h->ctx->device);
+  return head_step(h, x, labels, B, T, loss, logits, nullptr, 0);
 }
 
 extern "C" int tn_head_buffers(tn_head *h, float **params_dev, float **grads_dev, int64_t *numel) {
@@ -1411,6 +1419,118 @@ extern "C" int tn_head_destroy(tn_head *h) {
   (void)hipStreamSynchronize(h->ctx->stream);
   h->pool.release();
   delete h;
+  return TN_OK;
+}
+
+// ---- end-to-end CNN-RNN training step -------------------------------------------------
+// reference train.py:197-236 (--window > 1 --temp_pool gru|lstm, no --feats_model): the fine-tuning step's backbone
+// (finetune.hip, built without its classifier) over the batch*steps frames, the temporal head above on its features.
+struct tn_cnnrnn_trainer {
+  tn_ctx *ctx;
+  tn_finetune *bb;
+  tn_head *head;
+  int B, T, H, W, F;
+  bool frozen;
+  std::string bb_prefix, rnn_prefix, dense_prefix;
+};
+
+extern "C" int tn_cnnrnn_trainer_create(tn_ctx *ctx, tn_rnn_kind kind, const tn_param *params, int n_params,
+                                        const char *backbone_prefix, const char *rnn_prefix, const char *dense_prefix, int height,
+                                        int width, int classes, int batch, int steps, int freeze_backbone,
+                                        tn_cnnrnn_trainer **out) {
+  TN_REQUIRE(ctx && params && backbone_prefix && rnn_prefix && dense_prefix && out, "tn_cnnrnn_trainer_create: null argument");
+  TN_REQUIRE(kind == TN_RNN_GRU || kind == TN_RNN_LSTM, "tn_cnnrnn_trainer_create: type must be 'gru' or 'lstm'");
+  TN_REQUIRE(height > 0 && width > 0 && height % 32 == 0 && height == width,
+             "tn_cnnrnn_trainer_create: frames must be square with a side divisible by 32");
+  TN_REQUIRE(classes > 0, "tn_cnnrnn_trainer_create: classes must be positive");
+  TN_REQUIRE(batch > 0 && steps > 0 && (long)batch * steps <= (1L << 20), "tn_cnnrnn_trainer_create: bad batch / steps");
+  TN_ON_DEVICE(ctx->device);
+  // the hidden size: <rnn_prefix>l0_i2h_bias has gates * hidden entries
+  const int G = kind == TN_RNN_GRU ? 3 : 4;
+  const std::string bias_name = std::string(rnn_prefix) + "l0_i2h_bias";
+  int hidden = -1;
+  for (int i = 0; i < n_params; ++i)
+    if (bias_name == params[i].name) hidden = (int)(params[i].numel / G);
+  if (hidden <= 0) { tn_set_error("missing parameter: " + bias_name); return TN_ERR_MISSING; }
+  long fit = -1;
+  tn_finetune *bb = nullptr;
+  int rc = ft_create(ctx, params, n_params, backbone_prefix, nullptr, height, width, 0, batch * steps, &bb, &fit);
+  if (rc == TN_ERR_NOMEM && fit >= 0) {
+    tn_set_error("tn_cnnrnn_trainer_create: " + std::to_string((long)batch * steps) + " frames (batch x steps) of " +
+                 std::to_string(height) + "x" + std::to_string(width) + " do not fit the device; about " + std::to_string(fit) +
+                 " would");
+    return rc;
+  }
+  if (rc) return rc;
+  tn_head *head = nullptr;
+  rc = tn_head_create(ctx, kind, ft_feature_dim(bb), hidden, classes, params, n_params, rnn_prefix, dense_prefix, batch, steps, &head);
+  if (rc) { tn_finetune_destroy(bb); return rc; }
+  tn_cnnrnn_trainer *t = new tn_cnnrnn_trainer();
+  t->ctx = ctx; t->bb = bb; t->head = head; t->B = batch; t->T = steps; t->H = height; t->W = width; t->F = ft_feature_dim(bb);
+  t->frozen = freeze_backbone != 0;
+  t->bb_prefix = backbone_prefix; t->rnn_prefix = rnn_prefix; t->dense_prefix = dense_prefix;
+  *out = t;
+  return TN_OK;
+}
+
+// backbone forward (training-mode BatchNorm over all batch*steps frames) -> features (rows b*steps + t) -> head forward / backward
+// -> dX straight into the backbone's feature gradient -> backbone backward; frozen: no dX, no backbone backward.  Either way the
+// BatchNorm running statistics are updated from the batch statistics (the one place that decides it: docs/numerics.md).
+extern "C" int tn_cnnrnn_trainer_forward_backward(tn_cnnrnn_trainer *t, const float *x, const int32_t *labels, int batch, int steps,
+                                                  int height, int width, float *loss, float *logits) {
+  TN_REQUIRE(t && x && labels, "tn_cnnrnn_trainer_forward_backward: null argument");
+  TN_REQUIRE(batch == t->B && steps == t->T,
+             "tn_cnnrnn_trainer_forward_backward: batch and steps must equal the handle's (batch x steps frames, BatchNorm statistics over all)");
+  TN_REQUIRE(height == t->H && width == t->W, "tn_cnnrnn_trainer_forward_backward: the frame size must equal the handle's");
+  TN_ON_DEVICE(t->ctx->device);
+  int rc;
+#define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
+  TN_TRY(ft_forward_features(t->bb, x));
+  TN_TRY(head_step(t->head, ft_features(t->bb), labels, t->B, t->T, loss, logits, t->frozen ? nullptr : ft_feature_grad(t->bb), t->F));
+  if (!t->frozen) TN_TRY(ft_backward_features(t->bb));
+  ft_update_running(t->bb);
+#undef TN_TRY
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+
+extern "C" int tn_cnnrnn_trainer_buffers(tn_cnnrnn_trainer *t, float **backbone_params, float **backbone_grads, int64_t *backbone_numel,
+                                         float **head_params, float **head_grads, int64_t *head_numel) {
+  TN_REQUIRE(t, "tn_cnnrnn_trainer_buffers: null handle");
+  float *w, *g, *mom;
+  long n;
+  ft_param_buffers(t->bb, &w, &g, &mom, &n);
+  if (backbone_params) *backbone_params = w;
+  if (backbone_grads) *backbone_grads = g;
+  if (backbone_numel) *backbone_numel = n;
+  return tn_head_buffers(t->head, head_params, head_grads, head_numel);
+}
+
+extern "C" int tn_cnnrnn_trainer_sgd_step(tn_cnnrnn_trainer *t, float lr, float momentum, float wd, float rescale_grad) {
+  TN_REQUIRE(t, "tn_cnnrnn_trainer_sgd_step: null handle");
+  TN_ON_DEVICE(t->ctx->device);
+  if (!t->frozen) {                                        // frozen: the backbone's parameters are not touched (grad_req 'null')
+    const int rc = tn_finetune_sgd_step(t->bb, lr, momentum, wd, rescale_grad);
+    if (rc) return rc;
+  }
+  return tn_head_sgd_step(t->head, lr, momentum, wd, rescale_grad);
+}
+
+extern "C" int tn_cnnrnn_trainer_read_param(tn_cnnrnn_trainer *t, const char *name, int gradient, float *out_host, int64_t capacity,
+                                            int64_t *numel) {
+  TN_REQUIRE(t && name && out_host && numel, "tn_cnnrnn_trainer_read_param: null argument");
+  const std::string n(name);
+  if (n.rfind(t->rnn_prefix, 0) == 0 || n.rfind(t->dense_prefix, 0) == 0)
+    return tn_head_read_param(t->head, name, gradient, out_host, capacity, numel);
+  TN_REQUIRE(n.rfind(t->bb_prefix, 0) == 0, "tn_cnnrnn_trainer_read_param: unknown parameter name");
+  return tn_finetune_read_param(t->bb, name, gradient, out_host, capacity, numel);
+}
+
+extern "C" int tn_cnnrnn_trainer_destroy(tn_cnnrnn_trainer *t) {
+  if (!t) return TN_OK;
+  tn_head_destroy(t->head);
+  tn_finetune_destroy(t->bb);
+  delete t;
   return TN_OK;
 }
 

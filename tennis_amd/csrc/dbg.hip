@@ -380,6 +380,17 @@ extern "C" int tn_dbg_gemm_tn(tn_ctx *ctx, const float *A, int lda, const float 
   return TN_OK;
 }
 
+// The NN-layout product of the CNN-RNN step (dX = dGI W_ih), through the step's launcher
+extern "C" int tn_dbg_gemm_nn(tn_ctx *ctx, const float *A, int lda, const float *B, int ldb, float *Cm, int ldc, int M, int N, int K) {
+  TN_REQUIRE(ctx && A && B && Cm, "tn_dbg_gemm_nn: null argument");
+  TN_REQUIRE(M > 0 && N > 0 && K > 0 && lda >= K && ldb >= N && ldc >= N, "tn_dbg_gemm_nn: bad shape");
+  TN_ON_DEVICE(ctx->device);
+  const int rc = launch_gemm_nn_f32(A, lda, B, ldb, Cm, ldc, M, N, K, 0, ctx->stream);
+  if (rc) return rc;
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+
 // The forward 1x1 convolution of the fine-tuning step with its BatchNorm + ReLU applied to the X operand
 extern "C" int tn_dbg_linear_bnrelu(tn_ctx *ctx, const float *X, int ldx, const float *asc, const float *ash, const float *W, int ldw,
                                     const float *bias, float *Y, int ldy, int M, int N, int K, int accumulate) {

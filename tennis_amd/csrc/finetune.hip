@@ -326,7 +326,11 @@ __global__ void ft_gap_bwd_kernel(const float *__restrict__ df, int B, int P, in
 struct Pool {
   std::vector<void *> ptrs;
   bool failed = false;
+  bool dry = false;        // count the bytes only (what a batch would need), allocate nothing
+  size_t bytes = 0;
   float *fl(size_t n) {
+    bytes += (n ? n : 1) * sizeof(float);
+    if (dry) return nullptr;
     void *p = nullptr;
     if (hipMalloc(&p, (n ? n : 1) * sizeof(float)) != hipSuccess) { failed = true; return nullptr; }
     ptrs.push_back(p);
@@ -350,6 +354,7 @@ struct tn_finetune {
   tn_ctx *ctx;
   Pool pool;
   int B, H, W, classes;
+  bool dense;                   // false: the backbone alone (the CNN-RNN step's TimeDistributed part), no classifier
   std::string pre, cls;
   long n;                       // trainable parameters (GEMM layouts: conv weights as (Cout, ky*kx*Cin))
   long ns;                      // running statistics
@@ -448,16 +453,13 @@ static void ft_reorder_out(const float *src, float *dst, int O, int I, int kh, i
         for (int x = 0; x < kw; ++x) dst[(((long)o * I + i) * kh + y) * kw + x] = src[((long)o * kh * kw + y * kw + x) * I + i];
 }
 
-extern "C" int tn_finetune_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *backbone_prefix,
-                                  const char *dense_prefix, int height, int width, int classes, int batch, tn_finetune **out) {
-  TN_REQUIRE(ctx && params && backbone_prefix && dense_prefix && out, "tn_finetune_create: null argument");
-  TN_REQUIRE(height > 0 && width > 0 && height % 32 == 0 && width % 32 == 0 && height == width && classes > 0 && batch > 0,
-             "tn_finetune_create: frames must be square with a side divisible by 32");
-  TN_ON_DEVICE(ctx->device);
+int ft_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *backbone_prefix, const char *dense_prefix, int height,
+              int width, int classes, int batch, tn_finetune **out, long *fit_frames) {
   std::map<std::string, const tn_param *> pm;
   for (int i = 0; i < n_params; ++i) pm[params[i].name] = &params[i];
   tn_finetune *f = new tn_finetune();
-  f->ctx = ctx; f->B = batch; f->H = height; f->W = width; f->classes = classes; f->pre = backbone_prefix; f->cls = dense_prefix;
+  f->ctx = ctx; f->B = batch; f->H = height; f->W = width; f->dense = dense_prefix != nullptr; f->classes = f->dense ? classes : 0;
+  f->pre = backbone_prefix; f->cls = f->dense ? dense_prefix : "";
   const std::string pre = f->pre;
   static const int kCfg[4] = {6, 12, 24, 16};
   long o = 0, os = 0;
@@ -496,7 +498,7 @@ extern "C" int tn_finetune_create(tn_ctx *ctx, const tn_param *params, int n_par
     }
   }
   f->bnF = mkbn(pre + "batchnorm" + std::to_string(outer), c);
-  f->o_wd = take((long)classes * c); f->o_bd = take(classes);
+  f->o_wd = f->dense ? take((long)classes * c) : -1; f->o_bd = f->dense ? take(classes) : -1;
   f->n = o; f->ns = os;
   std::vector<float> w(f->n), st(f->ns);
   auto fail = [&](int code) { f->pool.release(); delete f; return code; };
@@ -529,13 +531,15 @@ extern "C" int tn_finetune_create(tn_ctx *ctx, const tn_param *params, int n_par
     }
   }
   loadbn(f->bnF);
-  if (const float *pd = get(f->cls + "weight", (long)classes * c)) memcpy(&w[f->o_wd], pd, sizeof(float) * classes * c);
-  if (const float *pb = get(f->cls + "bias", classes)) memcpy(&w[f->o_bd], pb, sizeof(float) * classes);
+  if (f->dense) {
+    if (const float *pd = get(f->cls + "weight", (long)classes * c)) memcpy(&w[f->o_wd], pd, sizeof(float) * classes * c);
+    if (const float *pb = get(f->cls + "bias", classes)) memcpy(&w[f->o_bd], pb, sizeof(float) * classes);
+  }
   if (!ok) return fail(TN_ERR_MISSING);
-  // device buffers
-  auto &P = f->pool;
+  // device buffers (alloc: in P, for B frames; a dry pool only counts the bytes)
+  auto alloc = [&](Pool &P, long B) {
   f->w = P.fl(f->n); f->g = P.fl(f->n); f->mom = P.fl(f->n); f->state = P.fl(f->ns);
-  const long B = batch, M0 = B * (height / 2) * (width / 2);
+  const long M0 = B * (height / 2) * (width / 2);
   f->x_in = P.fl(B * height * width * 3); f->col7 = P.fl(M0 * 147); f->z0 = P.fl(M0 * 64); f->a0 = P.fl(M0 * 64);
   long maxMK = M0 * 64, maxM128 = 0;
   for (int b = 0; b < 4; ++b) {
@@ -551,11 +555,11 @@ extern "C" int tn_finetune_create(tn_ctx *ctx, const tn_param *params, int n_par
   f->ta = P.fl(maxMK); f->tb = P.fl(maxMK > maxM128 ? maxMK : maxM128); f->col = P.fl(Mb0 * 1152); f->dcol = P.fl(Mb0 * 1152);
   f->tg = P.fl(maxMK); f->tw = P.fl(1024L * 1024);
   f->ws_floats = 16L << 20; f->ws = P.fl(f->ws_floats);
-  f->feat = P.fl(B * c); f->dfeat = P.fl(B * c); f->logits = P.fl(B * classes); f->loss = P.fl(B); f->dlog = P.fl(B * classes);
-  {
-    void *lp = nullptr;
-    if (hipMalloc(&lp, sizeof(int32_t) * B) != hipSuccess) P.failed = true; else P.ptrs.push_back(lp);
-    f->labels = (int32_t *)lp;
+  f->feat = P.fl(B * c); f->dfeat = P.fl(B * c);
+  f->logits = f->loss = f->dlog = nullptr; f->labels = nullptr;
+  if (f->dense) {
+    f->logits = P.fl(B * classes); f->loss = P.fl(B); f->dlog = P.fl(B * classes);
+    f->labels = (int32_t *)P.fl(B);                                 // (int32, the size of a float)
   }
   auto bnbuf = [&](FtBn &b) { b.mean = P.fl(b.C); b.var = P.fl(b.C); b.sc = P.fl(b.C); b.sh = P.fl(b.C); };
   // a BatchNorm over a prefix of a block's concat buffer reads the block's shared statistics
@@ -566,6 +570,24 @@ extern "C" int tn_finetune_create(tn_ctx *ctx, const tn_param *params, int n_par
     for (auto &L : f->layers[b]) { bnshared(L.bn1, b); bnbuf(L.bn2); }
     if (b < 3) bnshared(f->trans[b].bn, b);
   }
+  };
+  if (fit_frames) {
+    // what batch frames need against what the device has free: the allocation is linear in the frames
+    Pool d1, d2;
+    d1.dry = d2.dry = true;
+    alloc(d1, 1); alloc(d2, 2);
+    const long per = (long)(d2.bytes - d1.bytes), fixed = (long)d1.bytes - per;
+    size_t freeb = 0, totalb = 0;
+    TN_HIP_CHECK(hipMemGetInfo(&freeb, &totalb));
+    const long avail = (long)(freeb - freeb / 20);                   // 5 % left to the runtime and other allocations
+    if (fixed + per * (long)batch > avail) {
+      *fit_frames = avail > fixed ? (avail - fixed) / per : 0;
+      f->pool.release(); delete f;
+      return TN_ERR_NOMEM;
+    }
+  }
+  auto &P = f->pool;
+  alloc(P, batch);
   if (P.failed) { tn_set_error("device allocation failed"); return fail(TN_ERR_NOMEM); }
   TN_HIP_CHECK(hipMemcpy(f->w, w.data(), sizeof(float) * f->n, hipMemcpyHostToDevice));
   TN_HIP_CHECK(hipMemcpy(f->state, st.data(), sizeof(float) * f->ns, hipMemcpyHostToDevice));
@@ -575,22 +597,24 @@ extern "C" int tn_finetune_create(tn_ctx *ctx, const tn_param *params, int n_par
   return TN_OK;
 }
 
-// x (batch, H, W, 3) fp32 normalised frames (NHWC), labels (batch,) int32, both DEVICE.  Runs the training-mode forward,
-// the per-sample softmax cross-entropy and the backward of their SUM; loss (batch,) / logits (batch, classes) optional
-// device outputs.  Gradients land in the flat buffer (tn_finetune_buffers); BatchNorm running statistics are updated.
-extern "C" int tn_finetune_forward_backward(tn_finetune *f, const float *x, const int32_t *labels, int batch, int height, int width,
-                                            float *loss, float *logits) {
-  TN_REQUIRE(f && x && labels, "tn_finetune_forward_backward: null argument");
-  TN_REQUIRE(height == f->H && width == f->W, "tn_finetune_forward_backward: the frame size must equal the handle's");
-  TN_REQUIRE(batch == f->B, "tn_finetune_forward_backward: the batch must equal the handle's (BatchNorm statistics are per batch)");
-  TN_ON_DEVICE(f->ctx->device);
+extern "C" int tn_finetune_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *backbone_prefix,
+                                  const char *dense_prefix, int height, int width, int classes, int batch, tn_finetune **out) {
+  TN_REQUIRE(ctx && params && backbone_prefix && dense_prefix && out, "tn_finetune_create: null argument");
+  TN_REQUIRE(height > 0 && width > 0 && height % 32 == 0 && width % 32 == 0 && height == width && classes > 0 && batch > 0,
+             "tn_finetune_create: frames must be square with a side divisible by 32");
+  TN_ON_DEVICE(ctx->device);
+  return ft_create(ctx, params, n_params, backbone_prefix, dense_prefix, height, width, classes, batch, out, nullptr);
+}
+
+// The step in three parts (train.h), on the handle's stream; launch errors are peeked at by the launchers and checked once by the caller.
+// Forward of x (B, H, W, 3) through the backbone in training mode, batch statistics of every BatchNorm -> ft_features (B, 1024 ...)
+int ft_forward_features(tn_finetune *f, const float *x) {
   hipStream_t s = f->ctx->stream;
-  const int B = f->B, H = f->H, W = f->W, NC = f->classes;
+  const int B = f->B, H = f->H, W = f->W;
   const long M0 = (long)B * (H / 2) * (W / 2);
-  float *w = f->w, *g = f->g;
+  float *w = f->w;
   int rc;
 #define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
-  // ---------------- forward ----------------
   hipLaunchKernelGGL(ft_im2col7_kernel, dim3(nblk(M0 * 49)), dim3(256), 0, s, x, B, H, W, f->col7);
   TN_TRY(launch_linear_f32(f->col7, 147, w + f->o_w0, 147, nullptr, f->z0, 64, (int)M0, 64, 147, 0, s));
   ft_bn_forward(f, f->bn0, f->z0, 64, M0, f->a0, s);
@@ -626,13 +650,18 @@ extern "C" int tn_finetune_forward_backward(tn_finetune *f, const float *x, cons
   const long M3 = (long)B * P3;
   ft_bn_recompute(f, f->bnF, f->X[3], CF, M3, f->ta, s);
   hipLaunchKernelGGL(ft_gap_kernel, dim3(nblk((long)B * CF)), dim3(256), 0, s, (const float *)f->ta, B, P3, CF, f->feat);
-  TN_TRY(launch_linear_f32(f->feat, CF, w + f->o_wd, CF, w + f->o_bd, f->logits, NC, B, NC, CF, 0, s));
-  TN_HIP_CHECK(hipMemcpyAsync(f->labels, labels, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
-  TN_TRY(launch_softmax_ce(f->logits, f->labels, B, NC, f->loss, f->dlog, s));
-  if (loss) TN_HIP_CHECK(hipMemcpyAsync(loss, f->loss, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
-  if (logits) TN_HIP_CHECK(hipMemcpyAsync(logits, f->logits, sizeof(float) * B * NC, hipMemcpyDeviceToDevice, s));
-  // ---------------- backward ----------------
-  TN_TRY(launch_dense_bwd(f->dlog, f->feat, w + f->o_wd, B, NC, CF, g + f->o_wd, g + f->o_bd, f->dfeat, s));
+  return TN_OK;
+}
+
+// Backward of the backbone from the feature gradient ft_feature_grad (B, 1024 ...): every backbone gradient, assigned
+int ft_backward_features(tn_finetune *f) {
+  hipStream_t s = f->ctx->stream;
+  const int B = f->B, H = f->H, W = f->W;
+  const long M0 = (long)B * (H / 2) * (W / 2);
+  float *w = f->w, *g = f->g;
+  const int CF = f->Ctot[3], P3 = f->Hb[3] * f->Hb[3];
+  const long M3 = (long)B * P3;
+  int rc;
   hipLaunchKernelGGL(ft_gap_bwd_kernel, dim3(nblk(M3 * CF)), dim3(256), 0, s, (const float *)f->dfeat, B, P3, CF, f->tg);
   ft_bn_backward(f, f->bnF, f->tg, f->X[3], CF, M3, f->dX[3], CF, 0, s);
   for (int b = 3; b >= 0; --b) {
@@ -674,7 +703,12 @@ extern "C" int tn_finetune_forward_backward(tn_finetune *f, const float *x, cons
       TN_TRY(launch_gemm_tn_f32(f->tb, 64, f->col7, 147, g + f->o_w0, 147, 64, 147, (int)M0, s, f->ws, f->ws_floats));
     }
   }
-  // ---------------- BatchNorm running statistics ----------------
+  return TN_OK;
+}
+
+// BatchNorm running statistics from the batch statistics of the last forward: running = 0.9 running + 0.1 batch
+void ft_update_running(tn_finetune *f) {
+  hipStream_t s = f->ctx->stream;
   auto upd = [&](const FtBn &b) {
     hipLaunchKernelGGL(ft_bn_running_kernel, dim3((b.C + 255) / 256), dim3(256), 0, s, f->state + b.o_rm, f->state + b.o_rv,
                        (const float *)b.mean, (const float *)b.var, b.C);
@@ -684,6 +718,41 @@ extern "C" int tn_finetune_forward_backward(tn_finetune *f, const float *x, cons
     for (auto &L : f->layers[b]) { upd(L.bn1); upd(L.bn2); }
     if (b < 3) upd(f->trans[b].bn);
   }
+}
+#undef TN_TRY
+
+float *ft_features(tn_finetune *f) { return f->feat; }
+float *ft_feature_grad(tn_finetune *f) { return f->dfeat; }
+int ft_feature_dim(tn_finetune *f) { return f->Ctot[3]; }
+int ft_param_buffers(tn_finetune *f, float **w, float **g, float **mom, long *n) {
+  *w = f->w; *g = f->g; *mom = f->mom; *n = f->n;
+  return TN_OK;
+}
+
+// x (batch, H, W, 3) fp32 normalised frames (NHWC), labels (batch,) int32, both DEVICE.  Runs the training-mode forward,
+// the per-sample softmax cross-entropy and the backward of their SUM; loss (batch,) / logits (batch, classes) optional
+// device outputs.  Gradients land in the flat buffer (tn_finetune_buffers); BatchNorm running statistics are updated.
+extern "C" int tn_finetune_forward_backward(tn_finetune *f, const float *x, const int32_t *labels, int batch, int height, int width,
+                                            float *loss, float *logits) {
+  TN_REQUIRE(f && x && labels, "tn_finetune_forward_backward: null argument");
+  TN_REQUIRE(height == f->H && width == f->W, "tn_finetune_forward_backward: the frame size must equal the handle's");
+  TN_REQUIRE(batch == f->B, "tn_finetune_forward_backward: the batch must equal the handle's (BatchNorm statistics are per batch)");
+  TN_REQUIRE(f->dense, "tn_finetune_forward_backward: the handle has no classifier");
+  TN_ON_DEVICE(f->ctx->device);
+  hipStream_t s = f->ctx->stream;
+  const int B = f->B, NC = f->classes, CF = f->Ctot[3];
+  float *w = f->w, *g = f->g;
+  int rc;
+#define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
+  TN_TRY(ft_forward_features(f, x));
+  TN_TRY(launch_linear_f32(f->feat, CF, w + f->o_wd, CF, w + f->o_bd, f->logits, NC, B, NC, CF, 0, s));
+  TN_HIP_CHECK(hipMemcpyAsync(f->labels, labels, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
+  TN_TRY(launch_softmax_ce(f->logits, f->labels, B, NC, f->loss, f->dlog, s));
+  if (loss) TN_HIP_CHECK(hipMemcpyAsync(loss, f->loss, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
+  if (logits) TN_HIP_CHECK(hipMemcpyAsync(logits, f->logits, sizeof(float) * B * NC, hipMemcpyDeviceToDevice, s));
+  TN_TRY(launch_dense_bwd(f->dlog, f->feat, w + f->o_wd, B, NC, CF, g + f->o_wd, g + f->o_bd, f->dfeat, s));
+  TN_TRY(ft_backward_features(f));
+  ft_update_running(f);
 #undef TN_TRY
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
@@ -750,8 +819,8 @@ extern "C" int tn_finetune_read_param(tn_finetune *f, const char *name_c, int gr
       if (name == f->trans[b].nw) return copy(base + f->trans[b].o_w, (long)f->trans[b].Cout * f->trans[b].Cin);
     }
   }
-  if (name == f->cls + "weight") return copy(base + f->o_wd, (long)f->classes * f->Ctot[3]);
-  if (name == f->cls + "bias") return copy(base + f->o_bd, f->classes);
+  if (f->dense && name == f->cls + "weight") return copy(base + f->o_wd, (long)f->classes * f->Ctot[3]);
+  if (f->dense && name == f->cls + "bias") return copy(base + f->o_bd, f->classes);
   TN_REQUIRE(false, "tn_finetune_read_param: unknown parameter name");
 }
 

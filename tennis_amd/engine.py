@@ -584,3 +584,99 @@ class FrameModelTrainer:
                 self.handle = None
         except Exception:
             pass
+
+
+class CNNRNNTrainer:
+    """End-to-end training step of ``CNNRNN(FrameModel(DenseNet121.features))`` over ``TimeDistributed`` frames, the way reference
+    train.py:197-236 drives it with ``--window > 1 --temp_pool gru|lstm`` and no ``--feats_model``: the backbone's BatchNorms in
+    training mode over all batch x steps frames, bi-GRU / bi-LSTM -> max over T -> Dense, ``SoftmaxCrossEntropyLoss`` per sample
+    (:324), backward of the summed losses (:419-421) through the head and, unless ``freeze_backbone`` (:231-233), through the
+    backbone; ``gluon.Trainer('sgd', {lr, momentum, wd}).step(batch_size)`` (:298-299,424).  fp32.  Batch and steps are fixed at
+    construction (BatchNorm statistics are per batch).
+
+    ``grads`` is a tuple of flat device views: (backbone, head), or (head,) with a frozen backbone - what a data-parallel run
+    all-reduces before ``step`` (``train.allreduce_and_step``).  A frozen backbone is not updated, but its BatchNorms still
+    normalise with batch statistics and update their running statistics (docs/numerics.md)."""
+
+    def __init__(self, params: dict, size: int = 224, classes: int = 11, batch: int = 2, steps: int = 8, type: str = "gru",
+                 prefix: str = "densenet0_", rnn_prefix: str | None = None, dense_prefix: str = "cnnrnn0_dense0_",
+                 freeze_backbone: bool = False, ctx: _lib.Context | None = None):
+        if type not in ("gru", "lstm"):
+            raise ValueError(f"type must be 'gru' or 'lstm', got {type!r}")
+        if rnn_prefix is None:
+            rnn_prefix = f"cnnrnn0_{type}0_"
+        self.ctx = ctx or _lib.default_context()
+        self.lib = self.ctx.lib
+        self.type, self.size, self.classes, self.batch, self.steps = type, size, classes, batch, steps
+        self.frozen = bool(freeze_backbone)
+        self.prefix, self.rnn_prefix, self.dense_prefix = prefix, rnn_prefix, dense_prefix
+        self.names = [k for k in params if k.startswith((prefix, rnn_prefix, dense_prefix))]
+        self.shapes = {k: tuple(np.asarray(params[k]).shape) for k in self.names}
+        arr, keep = _lib.make_params({k: params[k] for k in self.names})
+        h = C.c_void_p()
+        check(self.lib.tn_cnnrnn_trainer_create(self.ctx.handle, _lib.RNN_GRU if type == "gru" else _lib.RNN_LSTM, arr, len(arr),
+                                                prefix.encode(), rnn_prefix.encode(), dense_prefix.encode(), size, size, classes,
+                                                batch, steps, 1 if self.frozen else 0, C.byref(h)), "tn_cnnrnn_trainer_create")
+        del keep
+        self.handle = h
+        bw, bg, bn, hw, hg, hn = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self.lib.tn_cnnrnn_trainer_buffers(h, C.byref(bw), C.byref(bg), C.byref(bn), C.byref(hw), C.byref(hg), C.byref(hn)),
+              "tn_cnnrnn_trainer_buffers")
+        self._bb = (bw.value, bg.value, bn.value)
+        self._head = (hw.value, hg.value, hn.value)
+
+    def _view(self, addr, n):
+        class _Arr:
+            __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (addr, False), "version": 3}
+        return torch.as_tensor(_Arr(), device=f"cuda:{self.ctx.device}")
+
+    @property
+    def grads(self) -> tuple:
+        head = self._view(self._head[1], self._head[2])
+        return (head,) if self.frozen else (self._view(self._bb[1], self._bb[2]), head)
+
+    @property
+    def params(self) -> tuple:
+        return self._view(self._bb[0], self._bb[2]), self._view(self._head[0], self._head[2])
+
+    def forward_backward(self, x: torch.Tensor, labels: torch.Tensor):
+        """x: (batch, steps) frames, NCHW or NHWC per frame, fp32 normalised or uint8 (ToTensor + Normalize applied here);
+        labels (batch,) -> (loss (batch,), logits (batch, classes))"""
+        _on_ctx_device(self.ctx, x, "CNNRNNTrainer")
+        b, t, sz = self.batch, self.steps, self.size
+        if x.dtype == torch.uint8:
+            x = to_tensor_normalize(x, ctx=self.ctx)
+        if x.dim() == 5 and tuple(x.shape[2:]) == (3, sz, sz):
+            x = x.permute(0, 1, 3, 4, 2)
+        if x.dim() != 5 or tuple(x.shape) != (b, t, sz, sz, 3):
+            raise ValueError(f"CNNRNNTrainer expects ({b}, {t}, 3, {sz}, {sz}) or ({b}, {t}, {sz}, {sz}, 3) frames, got {tuple(x.shape)}")
+        x = x.contiguous().float()
+        labels = labels.to(device=x.device, dtype=torch.int32).contiguous()
+        loss = torch.empty((b,), dtype=torch.float32, device=x.device)
+        logits = torch.empty((b, self.classes), dtype=torch.float32, device=x.device)
+        check(self.lib.tn_cnnrnn_trainer_forward_backward(self.handle, ptr(x), ptr(labels), b, t, sz, sz, ptr(loss), ptr(logits)),
+              "tn_cnnrnn_trainer_forward_backward")
+        return loss, logits
+
+    def step(self, batch_size: int, lr: float, momentum: float = 0.9, wd: float = 1e-4):
+        check(self.lib.tn_cnnrnn_trainer_sgd_step(self.handle, lr, momentum, wd, 1.0 / batch_size), "tn_cnnrnn_trainer_sgd_step")
+
+    def get(self, name: str, gradient: bool = False, shape=None) -> np.ndarray:
+        shape = shape or self.shapes[name]
+        out = np.empty(int(np.prod(shape)), np.float32)
+        n = C.c_int64()
+        check(self.lib.tn_cnnrnn_trainer_read_param(self.handle, name.encode(), 1 if gradient else 0,
+                                                    out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n)),
+              "tn_cnnrnn_trainer_read_param")
+        return out[:n.value].reshape(shape).copy()
+
+    def state_dict(self) -> dict:
+        return {k: self.get(k) for k in self.names}
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self.lib.tn_cnnrnn_trainer_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass

@@ -21,14 +21,17 @@ from .engine import TemporalHeadTrainer
 def allreduce_and_step(trainer, global_batch_size: int, lr: float, momentum: float, wd: float):
     """``trainer.step(batch_size)`` of a data-parallel run: sum the per-rank gradients of the summed losses, then
     Gluon's rescale 1/batch_size with the GLOBAL batch size (reference: one Trainer over all devices,
-    ``trainer.step(FLAGS.batch_size)``, train.py:424)."""
+    ``trainer.step(FLAGS.batch_size)``, train.py:424).  ``trainer.grads`` is one flat buffer or a tuple of them
+    (``CNNRNNTrainer``: backbone and head, or the head alone with a frozen backbone): every one is summed."""
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        comm = _grad_comm(trainer.grads.device)
-        if comm is not None:
-            comm.allreduce_(trainer.grads).wait()      # tn_allreduce_f32: RCCL behind the C-ABI
-        else:
-            dist.all_reduce(trainer.grads, op=dist.ReduceOp.SUM)
+        grads = trainer.grads
+        for g in (grads if isinstance(grads, (tuple, list)) else (grads,)):
+            comm = _grad_comm(g.device)
+            if comm is not None:
+                comm.allreduce_(g).wait()              # tn_allreduce_f32: RCCL behind the C-ABI
+            else:
+                dist.all_reduce(g, op=dist.ReduceOp.SUM)
     trainer.step(global_batch_size, lr, momentum, wd)
 
 
@@ -140,6 +143,21 @@ def train_model(head: TemporalHeadTrainer, train_batches, metrics, trainer: Trai
     return history
 
 
+def check_frames_route(flags):
+    """The end-to-end routes on frames (no ``--feats_model``): ``--window 1`` (the frame classifier) or ``--window > 1`` with
+    ``--temp_pool gru|lstm`` (CNNRNN).  Anything else exits with the reason."""
+    if flags.feats_model is not None:
+        return
+    if flags.window < 1:
+        raise SystemExit("--window must be at least 1")
+    if flags.window > 1 and flags.temp_pool not in ("gru", "lstm"):
+        raise SystemExit("--window > 1 on frames trains CNNRNN and needs --temp_pool gru|lstm; mean / max have no parameters "
+                         "of their own (the reference's train.py:236 leaves a FrameModel under a 5-D input there)")
+    if flags.window == 1 and flags.freeze_backbone:
+        raise SystemExit("--window 1 trains the frame classifier end to end; a frozen backbone trains on features "
+                         "(--feats_model after evaluate --save_feats) or under a temporal head (--window > 1 --temp_pool gru|lstm)")
+
+
 def build_parser():
     import argparse
     p = argparse.ArgumentParser(description="tennis_amd train (flags of reference train.py:30-95)")
@@ -154,7 +172,8 @@ def build_parser():
     p.add_argument("--window", type=int, default=1)
     p.add_argument("--padding", type=int, default=1)
     p.add_argument("--stride", type=int, default=1)
-    p.add_argument("--batch_size", type=int, default=64)
+    p.add_argument("--batch_size", type=int, default=64,
+                   help="end-to-end training on frames drops a ragged last batch (BatchNorm statistics are per batch)")
     p.add_argument("--epochs", type=int, default=20)
     p.add_argument("--lr", type=float, default=0.001)
     p.add_argument("--lr_factor", type=float, default=0.75)
@@ -179,15 +198,17 @@ def build_parser():
 
 
 def main(argv=None):
-    """reference train.py::main (:98-386) for the two trainable configurations on the hot path:
+    """reference train.py::main (:98-386) for the three trainable configurations on the hot path:
       * ``--feats_model <id> --window W --temp_pool gru|lstm``: the temporal head on pre-extracted features (backbone frozen);
-      * ``--window 1`` without ``--feats_model``: the frame classifier end to end (BatchNorm in training mode).
+      * ``--window 1`` without ``--feats_model``: the frame classifier end to end (BatchNorm in training mode);
+      * ``--window W > 1 --temp_pool gru|lstm`` without ``--feats_model``: CNNRNN over TimeDistributed frames end to end, or with
+        ``--freeze_backbone`` the head alone over a backbone whose BatchNorms still run in training mode (train.py:197-236).
     End-to-end training on frames from disk uses the reference's TRAIN transform for the train split (RandomResizedCrop,
     RandomFlipLeftRight, RandomColorJitter(0.4, 0.4, 0.4), RandomLighting(0.1); train.py:125-139 - round 4: one GPU launch group per
     batch, ``tennis_amd.transforms``), the test transform for validation; ``--no_augment`` keeps the test transform everywhere."""
     from . import transforms
     from .dataset import DataLoader, TennisSet
-    from .engine import FrameModelTrainer, TemporalHeadTrainer
+    from .engine import CNNRNNTrainer, FrameModelTrainer, TemporalHeadTrainer
     from .sharding import init_distributed
     from .evaluate import evaluate_model
     from .metrics.vision import PRF1
@@ -197,6 +218,7 @@ def main(argv=None):
     flags = build_parser().parse_args(argv)
     if flags.flow or flags.vis:
         raise NotImplementedError("--flow / --vis: optical-flow input and visualisation are outside the accelerated path (SURVEY 2a)")
+    check_frames_route(flags)
     if flags.num_workers < 0:                          # the reference's -1 = cpu_count() (train.py:101-102)
         flags.num_workers = 3                                               # (files -> features peaks at three decoder threads: scripts/bench_pipeline.py, profiles/r05_c_*)
     every = [int(s) for s in flags.every.split(",")]
@@ -237,10 +259,23 @@ def main(argv=None):
         mk_head = lambda p: TemporalHeadTrainer(p, feat_dim, 128, n_cls, max_batch=local_bs, max_steps=flags.window,
                                                 rnn_prefix=model.rnn.prefix, dense_prefix=model.classes.prefix,
                                                 type=flags.temp_pool)
+    elif flags.window > 1:
+        model = FrameModel(get_model(flags.backbone, pretrained=True).features, n_cls)
+        model.initialize()
+        model.classes._materialize(1024)
+        if flags.backbone_from_id:                     # train.py:218-229: the FrameModel checkpoint, loaded before wrapping
+            bb = newest_params(os.path.join(flags.exp_root, flags.backbone_from_id))
+            if bb is not None:
+                model.load_parameters(bb)
+                print("Loaded backbone params: {}".format(bb))
+        model = CNNRNN(model, num_classes=n_cls, type=flags.temp_pool, hidden_size=128)     # train.py:230
+        model.rnn._materialize(1024)
+        model.classes._materialize(256)
+        last = "discard"
+        mk_head = lambda p: CNNRNNTrainer(p, flags.data_shape, n_cls, batch=local_bs, steps=flags.window, type=flags.temp_pool,
+                                          prefix=model.td.model.prefix, rnn_prefix=model.rnn.prefix,
+                                          dense_prefix=model.classes.prefix, freeze_backbone=flags.freeze_backbone)
     else:
-        if flags.window != 1 or flags.freeze_backbone:
-            raise SystemExit("end-to-end training is built for --window 1 with a trainable backbone; a frozen backbone "
-                             "trains on features (--feats_model after evaluate --save_feats)")
         model = FrameModel(get_model(flags.backbone, pretrained=True).features, n_cls)
         model.initialize()
         model.classes._materialize(1024)
