@@ -270,12 +270,14 @@ struct tn_encoder {
   float *ones128 = nullptr;
   bool block7 = true;         // a 7x7 block runs on the LDS-resident kernel of dense_block7.hip (TN_NO_BLOCK7 disables)
   DenseBlock7Args b7[4] = {};  // its packed operands per block (buf == nullptr: not packed)
-  bool block14 = true;        // a 14x14 block runs on the streamed kernel of dense_block14.hip (TN_NO_BLOCK14 disables)
-  DenseBlock14Args b14[4] = {};
-  f16 *b14_scratch[4] = {nullptr, nullptr, nullptr, nullptr};   // its k-step-major working copy of the block's frames
-  bool block28 = false;       // a 28x28 block runs on the streamed kernel of dense_block28.hip (TN_BLOCK28=1 enables: measured, not the default)
-  DenseBlock28Args b28[4] = {};
-  f16 *b28_scratch[4] = {nullptr, nullptr, nullptr, nullptr};
+  // the streamed block kernels (kDenseStreamKernels, common.h): [0] a 14x14 block on dense_block14.hip (TN_NO_BLOCK14 disables),
+  // [1] a 28x28 block on dense_block28.hip (TN_BLOCK28=1 enables: measured, not the default)
+  bool block_stream[2] = {true, false};
+  static_assert(sizeof(kDenseStreamKernels) / sizeof(kDenseStreamKernels[0]) == 2 && kDenseStreamKernels[0].H == 14 && kDenseStreamKernels[1].H == 28,
+                "block_stream[] is indexed like kDenseStreamKernels");
+  DenseStreamArgs b_stream[4] = {};                             // packed operands per block (stream == nullptr: not packed)
+  const DenseStreamKernel *b_stream_kernel[4] = {nullptr, nullptr, nullptr, nullptr};
+  f16 *b_stream_scratch[4] = {nullptr, nullptr, nullptr, nullptr};   // the kernel's k-step-major working copy of the block's frames
   hipStream_t side[4];
   hipEvent_t ev_in, ev_done[2][4];   // completion of the side streams, alternating per forward call
   bool pipelined = false;            // tn_densenet121_set_pipelined: the caller's stream is not made to wait inside forward
@@ -464,8 +466,8 @@ extern "C" int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int
   e->nsplit = getenv("TN_SPLIT") ? atoi(getenv("TN_SPLIT")) : 2;
   if (e->nsplit != 4) e->nsplit = 2;
   e->block7 = getenv("TN_NO_BLOCK7") == nullptr;
-  e->block14 = getenv("TN_NO_BLOCK14") == nullptr;
-  e->block28 = getenv("TN_BLOCK28") != nullptr && atoi(getenv("TN_BLOCK28")) != 0;
+  e->block_stream[0] = getenv("TN_NO_BLOCK14") == nullptr;
+  e->block_stream[1] = getenv("TN_BLOCK28") != nullptr && atoi(getenv("TN_BLOCK28")) != 0;
   e->chain = getenv("TN_NO_CHAIN") == nullptr;   // measured: -20% on the 14x14 / 7x7 blocks, +2.8% end to end
   e->dl_variant = getenv("TN_DL_VARIANT") ? atoi(getenv("TN_DL_VARIANT")) : 0;
   e->fp32 = (flags & TN_ENC_FP32) != 0;
@@ -581,9 +583,10 @@ extern "C" int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int
   int outer = 1;
   for (int b = 0; b < 4; ++b) {
     const std::string sp = pre + "stage" + std::to_string(b + 1) + "_";
-    const bool pack14 = e->fuse && e->block14 && !e->exact && dense_block14_supported(e->Hb[b], e->Wb[b], e->Cin[b], kBlockCfg[b]);
-    const bool pack28 = e->fuse && e->block28 && !e->exact && dense_block28_supported(e->Hb[b], e->Wb[b], e->Cin[b], kBlockCfg[b]);
-    const bool pack7 = (e->fuse && e->block7 && !e->exact && dense_block7_supported(e->Hb[b], e->Wb[b], e->Cin[b], kBlockCfg[b])) || pack14 || pack28;
+    const DenseStreamKernel *sk = nullptr;      // the first enabled streamed kernel that supports the block: 14x14, then 28x28
+    for (int k = 0; k < 2 && !sk; ++k)
+      if (e->fuse && e->block_stream[k] && !e->exact && kDenseStreamKernels[k].supported(e->Hb[b], e->Wb[b], e->Cin[b], kBlockCfg[b])) sk = &kDenseStreamKernels[k];
+    const bool pack7 = (e->fuse && e->block7 && !e->exact && dense_block7_supported(e->Hb[b], e->Wb[b], e->Cin[b], kBlockCfg[b])) || sk;
     std::vector<std::vector<float>> h7[4];     // host copies for pack_block7: folded 1x1 weights, s1, t1, t2 per layer
     std::vector<const float *> h7w3;
     for (int l = 0; l < kBlockCfg[b]; ++l) {
@@ -669,22 +672,15 @@ extern "C" int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int
       if (L.w1s) L.w3s = e->pool.upload(pack_w3_strip(w3));
       e->layers[b].push_back(L);
     }
-    if (pack14) {
+    if (sk) {
       std::vector<Block14Layer> bl;
       for (int l = 0; l < kBlockCfg[b]; ++l)
         bl.push_back(Block14Layer{h7[0][l].data(), h7w3[l], h7[1][l].data(), h7[2][l].data(), h7[3][l].data()});
-      DenseBlock14Args &a14 = e->b14[b];
-      a14.stream = e->pool.upload(pack_block14(bl, e->Cin[b]));
-      a14.total_units = dense_block14_units(e->Cin[b], kBlockCfg[b]);
-      a14.ldc = e->Cb[b]; a14.K0 = e->Cin[b]; a14.nl = kBlockCfg[b];
-    } else if (pack28) {
-      std::vector<Block14Layer> bl;
-      for (int l = 0; l < kBlockCfg[b]; ++l)
-        bl.push_back(Block14Layer{h7[0][l].data(), h7w3[l], h7[1][l].data(), h7[2][l].data(), h7[3][l].data()});
-      DenseBlock28Args &a28 = e->b28[b];
-      a28.stream = e->pool.upload(pack_block28(bl, e->Cin[b]));
-      a28.total_units = dense_block28_units(e->Cin[b], kBlockCfg[b]);
-      a28.ldc = e->Cb[b]; a28.K0 = e->Cin[b]; a28.nl = kBlockCfg[b];
+      DenseStreamArgs &as = e->b_stream[b];
+      as.stream = e->pool.upload(sk->pack(bl, e->Cin[b]));
+      as.total_units = sk->units(e->Cin[b], kBlockCfg[b]);
+      as.ldc = e->Cb[b]; as.K0 = e->Cin[b]; as.nl = kBlockCfg[b];
+      e->b_stream_kernel[b] = sk;
     } else if (pack7) {
       std::vector<Block7Layer> bl;
       for (int l = 0; l < kBlockCfg[b]; ++l)
@@ -732,22 +728,15 @@ extern "C" int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int
     e->blockbuf[b] = (f16 *)e->pool.alloc(B * e->Hb[b] * e->Wb[b] * e->Cb[b] * sizeof(f16));
   if (e->b7[3].wa) e->head32 = (float *)e->pool.alloc(B * e->Hb[3] * e->Wb[3] * e->Cb[3] * sizeof(float));
   for (int b = 0; b < 4; ++b)
-    if (e->b14[b].stream) e->b14_scratch[b] = (f16 *)e->pool.alloc(B * dense_block14_scratch_halfs() * sizeof(f16));
-  for (int b = 0; b < 4; ++b)
-    if (e->b28[b].stream) e->b28_scratch[b] = (f16 *)e->pool.alloc(B * dense_block28_scratch_halfs() * sizeof(f16));
+    if (e->b_stream[b].stream) e->b_stream_scratch[b] = (f16 *)e->pool.alloc(B * e->b_stream_kernel[b]->scratch_halfs() * sizeof(f16));
   e->workspace_bytes = e->pool.bytes - weights_bytes;
   if (e->pool.failed) { tn_set_error("device allocation failed"); return fail(TN_ERR_NOMEM); }
-  // dense_block14.hip reads the 32 channels a layer is about to write as the zero-weighted pad of its last 64-channel super-step:
-  // whatever is there must be finite, so the buffer does not start as whatever the allocator left in it
+  // The streamed kernels read the 32 channels a layer is about to write as the zero-weighted pad of its last 64-channel super-step
+  // (dense_block28.hip also rows 28 .. 31 of a plane): whatever is there must be finite, so the buffers do not start as whatever
+  // the allocator left in them
   for (int b = 0; b < 4; ++b)
-    if (e->b14[b].stream && (hipMemset(e->blockbuf[b], 0, B * e->Hb[b] * e->Wb[b] * e->Cb[b] * sizeof(f16)) != hipSuccess ||
-                             hipMemset(e->b14_scratch[b], 0, B * dense_block14_scratch_halfs() * sizeof(f16)) != hipSuccess)) {
-      tn_set_error("hipMemset failed");
-      return fail(TN_ERR_HIP);
-    }
-  for (int b = 0; b < 4; ++b)      // (dense_block28.hip reads rows 28 .. 31 of a plane and the zero-weighted pad of a last super-step)
-    if (e->b28[b].stream && (hipMemset(e->blockbuf[b], 0, B * e->Hb[b] * e->Wb[b] * e->Cb[b] * sizeof(f16)) != hipSuccess ||
-                             hipMemset(e->b28_scratch[b], 0, B * dense_block28_scratch_halfs() * sizeof(f16)) != hipSuccess)) {
+    if (e->b_stream[b].stream && (hipMemset(e->blockbuf[b], 0, B * e->Hb[b] * e->Wb[b] * e->Cb[b] * sizeof(f16)) != hipSuccess ||
+                                  hipMemset(e->b_stream_scratch[b], 0, B * e->b_stream_kernel[b]->scratch_halfs() * sizeof(f16)) != hipSuccess)) {
       tn_set_error("hipMemset failed");
       return fail(TN_ERR_HIP);
     }
@@ -812,32 +801,24 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
     const int Hh = e->Hb[b], Ww = e->Wb[b];
     const int M = B * Hh * Ww;
     const bool fused = !cal && e->fuse && dense_layer_supported(Hh, Ww);
-    if (!cal && e->b14[b].stream && e->dl_variant == 0) {
-      // pixel-owning waves, all weights streamed through an LDS ring (dense_block14.hip)
-      DenseBlock14Args a14 = e->b14[b];
-      a14.buf = bbuf[b]; a14.B = B;
-      a14.scratch = e->b14_scratch[b] + (size_t)w0 * dense_block14_scratch_halfs();
+    // a whole block as one launch: its flops and bytes under one family name
+    auto begin_block = [&](const char *family) {
       double fl = 0, by = 0;
       for (auto &L : e->layers[b]) {
         fl += 2.0 * M * (128.0 * L.cin + 32.0 * 1152);
         by += (double)M * (L.cin + 32) * 2 + 128.0 * L.cin * 2 + 32.0 * 1152 * 2;
       }
-      tm.begin("dense_block_stream_14x14", fl, by);
-      rc = launch_dense_block14(a14, s);
-      tm.end();
-      if (rc) return rc;
-    } else if (!cal && e->b28[b].stream && e->dl_variant == 0) {
-      // the 28x28 block in four passes of eight rows, all weights streamed once per pass (dense_block28.hip)
-      DenseBlock28Args a28 = e->b28[b];
-      a28.buf = bbuf[b]; a28.B = B;
-      a28.scratch = e->b28_scratch[b] + (size_t)w0 * dense_block28_scratch_halfs();
-      double fl = 0, by = 0;
-      for (auto &L : e->layers[b]) {
-        fl += 2.0 * M * (128.0 * L.cin + 32.0 * 1152);
-        by += (double)M * (L.cin + 32) * 2 + 128.0 * L.cin * 2 + 32.0 * 1152 * 2;
-      }
-      tm.begin("dense_block_stream_28x28", fl, by);
-      rc = launch_dense_block28(a28, s);
+      tm.begin(family, fl, by);
+    };
+    if (!cal && e->b_stream[b].stream && e->dl_variant == 0) {
+      // pixel-owning waves, all weights streamed through an LDS ring (dense_block14.hip; dense_block28.hip: in four passes of eight
+      // rows, the weights streamed once per pass)
+      const DenseStreamKernel &sk = *e->b_stream_kernel[b];
+      DenseStreamArgs as = e->b_stream[b];
+      as.buf = bbuf[b]; as.B = B;
+      as.scratch = e->b_stream_scratch[b] + (size_t)w0 * sk.scratch_halfs();
+      begin_block(sk.family);
+      rc = sk.launch(as, s);
       tm.end();
       if (rc) return rc;
     } else if (!cal && e->b7[b].wa && e->dl_variant == 0) {
@@ -845,12 +826,7 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
       DenseBlock7Args a7 = e->b7[b];
       a7.buf = bbuf[b]; a7.B = B;
       a7.side = b == 3 ? h32 : nullptr;
-      double fl = 0, by = 0;
-      for (auto &L : e->layers[b]) {
-        fl += 2.0 * M * (128.0 * L.cin + 32.0 * 1152);
-        by += (double)M * (L.cin + 32) * 2 + 128.0 * L.cin * 2 + 32.0 * 1152 * 2;
-      }
-      tm.begin("dense_block_lds_7x7", fl, by);
+      begin_block("dense_block_lds_7x7");
       rc = launch_dense_block7(a7, s);
       tm.end();
       if (rc) return rc;
@@ -861,12 +837,7 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
       const int nl = (int)e->layers[b].size();
       DenseLayerArgs af{bbuf[b], e->Cb[b], L0.cin, L0.s1, L0.t1, L0.w1, L0.s2, L0.t2, L0.w3p, B, Hh, Ww, nullptr, e->dl_variant, e->chain_dev[b], nl};
       af.exact = e->exact;
-      double fl = 0, by = 0;
-      for (auto &L : e->layers[b]) {
-        fl += 2.0 * M * (128.0 * L.cin + 32.0 * 1152);
-        by += (double)M * (L.cin + 32) * 2 + 128.0 * L.cin * 2 + 32.0 * 1152 * 2;
-      }
-      tm.begin(Hh == 14 ? "dense_block_chained_14x14" : Hh == 16 ? "dense_block_chained_16x16" : "dense_block_chained_7x7", fl, by);
+      begin_block(Hh == 14 ? "dense_block_chained_14x14" : Hh == 16 ? "dense_block_chained_16x16" : "dense_block_chained_7x7");
       rc = launch_dense_layer(af, s);
       tm.end();
       if (rc) return rc;

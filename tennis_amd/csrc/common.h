@@ -236,13 +236,15 @@ bool dense_block7_supported(int H, int W, int K0, int nl);
 Block7Image pack_block7(const std::vector<Block7Layer> &layers, int K0);
 int launch_dense_block7(const DenseBlock7Args &a, hipStream_t s);
 
-// The 14x14 dense block as one launch of pixel-owning waves with all weights streamed through an LDS ring (dense_block14.hip).
-struct DenseBlock14Args {
-  f16 *buf;                      // concat buffer [B][196][ldc]: reads channels [0,K0), appends [K0, K0 + 32 nl)
+// The streamed dense blocks: one launch of pixel-owning waves with all weights streamed through an LDS ring.  dense_block14.hip is
+// the 14x14 block, dense_block28.hip the 28x28 block with the frame walked in four passes of eight rows; the core they share is
+// dense_stream.h.  Both take the same operands.
+struct DenseStreamArgs {
+  f16 *buf;                      // concat buffer [B][H W][ldc]: reads channels [0,K0), appends [K0, K0 + 32 nl)
   int ldc, K0, nl, B;
-  const unsigned char *stream;   // the block's weight stream (pack_block14)
-  int total_units;               // dense_block14_units(K0, nl)
-  f16 *scratch = nullptr;        // B x dense_block14_scratch_halfs(): the kernel's k-step-major working copy of the frames
+  const unsigned char *stream;   // the block's weight stream (pack_block14 / pack_block28)
+  int total_units;               // dense_blockNN_units(K0, nl)
+  f16 *scratch = nullptr;        // B x dense_blockNN_scratch_halfs(): the kernel's k-step-major working copy of the frames (zeroed once)
   unsigned long long *ts = nullptr;   // tuning hook: s_memtime per layer (64 per workgroup)
 };
 struct Block14Layer { const float *w1f /*[128][K], BN2 scale folded in*/, *w3 /*(32,128,3,3)*/, *s1, *t1 /*[K]*/, *t2 /*[128]*/; };
@@ -250,22 +252,26 @@ bool dense_block14_supported(int H, int W, int K0, int nl);
 int dense_block14_units(int K0, int nl);
 size_t dense_block14_scratch_halfs();   // per frame
 std::vector<unsigned char> pack_block14(const std::vector<Block14Layer> &layers, int K0);
-int launch_dense_block14(const DenseBlock14Args &a, hipStream_t s);
-
-// The 28x28 dense block as one launch: dense_block14.hip's recipe with the frame walked in four passes of eight rows (dense_block28.hip).
-struct DenseBlock28Args {
-  f16 *buf;                      // concat buffer [B][784][ldc]: reads channels [0,K0), appends [K0, K0 + 32 nl)
-  int ldc, K0, nl, B;
-  const unsigned char *stream;   // the block's weight stream (pack_block28)
-  int total_units;               // dense_block28_units(K0, nl)
-  f16 *scratch = nullptr;        // B x dense_block28_scratch_halfs(): the kernel's k-step-major working copy of the frames (zeroed once)
-  unsigned long long *ts = nullptr;   // tuning hook: s_memtime per layer (64 per workgroup)
-};
+int launch_dense_block14(const DenseStreamArgs &a, hipStream_t s);
 bool dense_block28_supported(int H, int W, int K0, int nl);
 int dense_block28_units(int K0, int nl);
 size_t dense_block28_scratch_halfs();   // per frame
 std::vector<unsigned char> pack_block28(const std::vector<Block14Layer> &layers, int K0);
-int launch_dense_block28(const DenseBlock28Args &a, hipStream_t s);
+int launch_dense_block28(const DenseStreamArgs &a, hipStream_t s);
+// the two kernels as a table, in the order the encoder tries them (api.hip, dbg.hip)
+struct DenseStreamKernel {
+  int H;                         // the square map it runs
+  const char *family;            // the name tn_densenet121_profile reports
+  bool (*supported)(int H, int W, int K0, int nl);
+  int (*units)(int K0, int nl);
+  size_t (*scratch_halfs)();
+  std::vector<unsigned char> (*pack)(const std::vector<Block14Layer> &layers, int K0);
+  int (*launch)(const DenseStreamArgs &a, hipStream_t s);
+};
+inline constexpr DenseStreamKernel kDenseStreamKernels[2] = {
+    {14, "dense_block_stream_14x14", dense_block14_supported, dense_block14_units, dense_block14_scratch_halfs, pack_block14, launch_dense_block14},
+    {28, "dense_block_stream_28x28", dense_block28_supported, dense_block28_units, dense_block28_scratch_halfs, pack_block28, launch_dense_block28},
+};
 
 // ---- the stem's operand (round 5) -------------------------------------------------------------------------------
 // The reference hands the network ToTensor + Normalize of a decoded frame, v = (x / 255 - mean_c) / std_c (evaluate.py:96-97).

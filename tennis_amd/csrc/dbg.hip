@@ -233,139 +233,95 @@ extern "C" void tn_dbg_block7_destroy(void *handle) {
 }
 
 
-// ---- the streamed 14x14 dense block (dense_block14.hip) ----
+// ---- the streamed dense blocks (dense_block14.hip, dense_block28.hip): one implementation behind both sets of symbols ----
 // same operand convention as tn_dbg_block7_create
-struct tn_dbg_block14 {
+struct tn_dbg_stream_block {
   tn_ctx *ctx;
+  const DenseStreamKernel *kernel;
   void *stream = nullptr, *scratch = nullptr;
   int scratch_frames = 0;
-  DenseBlock14Args args;
+  DenseStreamArgs args;
 };
+
+// (a handle is served by the kernel that created it, whichever of the run / destroy symbols it is passed to)
+static_assert(sizeof(kDenseStreamKernels) / sizeof(kDenseStreamKernels[0]) == 2 && kDenseStreamKernels[0].H == 14 && kDenseStreamKernels[1].H == 28,
+              "tn_dbg_block14_* / tn_dbg_block28_* index the table");
+static int dbg_stream_create(const DenseStreamKernel &sk, tn_ctx *ctx, int K0, int nl, const float *w1_all, const float *s1_all, const float *t1_all,
+                             const float *s2_all, const float *t2_all, const float *w3_all, void **out) {
+  const std::string who = "tn_dbg_block" + std::to_string(sk.H) + "_create";
+  TN_REQUIRE(ctx && w1_all && s1_all && t1_all && s2_all && t2_all && w3_all && out, who + ": null argument");
+  TN_REQUIRE(sk.supported(sk.H, sk.H, K0, nl), who + ": unsupported geometry");
+  TN_ON_DEVICE(ctx->device);
+  std::vector<std::vector<float>> folded(nl);
+  std::vector<Block14Layer> layers(nl);
+  size_t o1 = 0, ok = 0;
+  for (int l = 0; l < nl; ++l) {
+    const int K = K0 + 32 * l;
+    folded[l].resize((size_t)128 * K);
+    for (int n = 0; n < 128; ++n)
+      for (int k = 0; k < K; ++k) folded[l][(size_t)n * K + k] = w1_all[o1 + (size_t)n * K + k] * s2_all[(size_t)l * 128 + n];
+    layers[l] = Block14Layer{folded[l].data(), w3_all + (size_t)l * 32 * 128 * 9, s1_all + ok, t1_all + ok, t2_all + (size_t)l * 128};
+    o1 += (size_t)128 * K;
+    ok += K;
+  }
+  const std::vector<unsigned char> img = sk.pack(layers, K0);
+  tn_dbg_stream_block *b = new tn_dbg_stream_block();
+  b->ctx = ctx;
+  b->kernel = &sk;
+  if (hipMalloc(&b->stream, img.size()) != hipSuccess || hipMemcpy(b->stream, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    tn_set_error(who + ": device allocation failed");
+    delete b;
+    return TN_ERR_NOMEM;
+  }
+  b->args = DenseStreamArgs{nullptr, 0, K0, nl, 0, (const unsigned char *)b->stream, sk.units(K0, nl)};
+  *out = b;
+  return TN_OK;
+}
+
+static int dbg_stream_run(void *handle, void *buf_f16, int ldc, int B, unsigned long long *ts) {
+  tn_dbg_stream_block *b = (tn_dbg_stream_block *)handle;
+  TN_REQUIRE(b && buf_f16, "tn_dbg_block14_run / tn_dbg_block28_run: null argument");
+  const std::string who = "tn_dbg_block" + std::to_string(b->kernel->H) + "_run";
+  TN_ON_DEVICE(b->ctx->device);
+  const size_t scratch_bytes = (size_t)B * b->kernel->scratch_halfs() * sizeof(f16);
+  if (b->scratch_frames < B) {
+    (void)hipFree(b->scratch);
+    b->scratch = nullptr; b->scratch_frames = 0;
+    if (hipMalloc(&b->scratch, scratch_bytes) != hipSuccess) {
+      tn_set_error(who + ": device allocation failed");
+      return TN_ERR_NOMEM;
+    }
+    b->scratch_frames = B;
+    TN_HIP_CHECK(hipMemset(b->scratch, 0, scratch_bytes));
+  }
+  DenseStreamArgs a = b->args;
+  a.buf = (f16 *)buf_f16; a.ldc = ldc; a.B = B; a.ts = ts; a.scratch = (f16 *)b->scratch;
+  return b->kernel->launch(a, b->ctx->stream);
+}
+
+static void dbg_stream_destroy(void *handle) {
+  tn_dbg_stream_block *b = (tn_dbg_stream_block *)handle;
+  if (!b) return;
+  (void)hipFree(b->stream);
+  (void)hipFree(b->scratch);
+  delete b;
+}
 
 extern "C" int tn_dbg_block14_create(tn_ctx *ctx, int K0, int nl, const float *w1_all, const float *s1_all, const float *t1_all,
                                      const float *s2_all, const float *t2_all, const float *w3_all, void **out) {
-  TN_REQUIRE(ctx && w1_all && s1_all && t1_all && s2_all && t2_all && w3_all && out, "tn_dbg_block14_create: null argument");
-  TN_REQUIRE(dense_block14_supported(14, 14, K0, nl), "tn_dbg_block14_create: unsupported geometry");
-  TN_ON_DEVICE(ctx->device);
-  std::vector<std::vector<float>> folded(nl);
-  std::vector<Block14Layer> layers(nl);
-  size_t o1 = 0, ok = 0;
-  for (int l = 0; l < nl; ++l) {
-    const int K = K0 + 32 * l;
-    folded[l].resize((size_t)128 * K);
-    for (int n = 0; n < 128; ++n)
-      for (int k = 0; k < K; ++k) folded[l][(size_t)n * K + k] = w1_all[o1 + (size_t)n * K + k] * s2_all[(size_t)l * 128 + n];
-    layers[l] = Block14Layer{folded[l].data(), w3_all + (size_t)l * 32 * 128 * 9, s1_all + ok, t1_all + ok, t2_all + (size_t)l * 128};
-    o1 += (size_t)128 * K;
-    ok += K;
-  }
-  const std::vector<unsigned char> img = pack_block14(layers, K0);
-  tn_dbg_block14 *b = new tn_dbg_block14();
-  b->ctx = ctx;
-  if (hipMalloc(&b->stream, img.size()) != hipSuccess || hipMemcpy(b->stream, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    tn_set_error("tn_dbg_block14_create: device allocation failed");
-    delete b;
-    return TN_ERR_NOMEM;
-  }
-  b->args = DenseBlock14Args{nullptr, 0, K0, nl, 0, (const unsigned char *)b->stream, dense_block14_units(K0, nl)};
-  *out = b;
-  return TN_OK;
+  return dbg_stream_create(kDenseStreamKernels[0], ctx, K0, nl, w1_all, s1_all, t1_all, s2_all, t2_all, w3_all, out);
 }
-
-extern "C" int tn_dbg_block14_run_ts(void *handle, void *buf_f16, int ldc, int B, unsigned long long *ts) {
-  tn_dbg_block14 *b = (tn_dbg_block14 *)handle;
-  TN_REQUIRE(b && buf_f16, "tn_dbg_block14_run: null argument");
-  TN_ON_DEVICE(b->ctx->device);
-  if (b->scratch_frames < B) {
-    (void)hipFree(b->scratch);
-    b->scratch = nullptr; b->scratch_frames = 0;
-    if (hipMalloc(&b->scratch, (size_t)B * dense_block14_scratch_halfs() * sizeof(f16)) != hipSuccess) {
-      tn_set_error("tn_dbg_block14_run: device allocation failed");
-      return TN_ERR_NOMEM;
-    }
-    b->scratch_frames = B;
-    TN_HIP_CHECK(hipMemset(b->scratch, 0, (size_t)B * dense_block14_scratch_halfs() * sizeof(f16)));
-  }
-  DenseBlock14Args a = b->args;
-  a.buf = (f16 *)buf_f16; a.ldc = ldc; a.B = B; a.ts = ts; a.scratch = (f16 *)b->scratch;
-  return launch_dense_block14(a, b->ctx->stream);
-}
-extern "C" int tn_dbg_block14_run(void *handle, void *buf_f16, int ldc, int B) { return tn_dbg_block14_run_ts(handle, buf_f16, ldc, B, nullptr); }
-
-extern "C" void tn_dbg_block14_destroy(void *handle) {
-  tn_dbg_block14 *b = (tn_dbg_block14 *)handle;
-  if (!b) return;
-  (void)hipFree(b->stream);
-  (void)hipFree(b->scratch);
-  delete b;
-}
-
-// ---- the streamed 28x28 dense block (dense_block28.hip) ----
-// same operand convention as tn_dbg_block7_create
-struct tn_dbg_block28 {
-  tn_ctx *ctx;
-  void *stream = nullptr, *scratch = nullptr;
-  int scratch_frames = 0;
-  DenseBlock28Args args;
-};
+extern "C" int tn_dbg_block14_run_ts(void *handle, void *buf_f16, int ldc, int B, unsigned long long *ts) { return dbg_stream_run(handle, buf_f16, ldc, B, ts); }
+extern "C" int tn_dbg_block14_run(void *handle, void *buf_f16, int ldc, int B) { return dbg_stream_run(handle, buf_f16, ldc, B, nullptr); }
+extern "C" void tn_dbg_block14_destroy(void *handle) { dbg_stream_destroy(handle); }
 
 extern "C" int tn_dbg_block28_create(tn_ctx *ctx, int K0, int nl, const float *w1_all, const float *s1_all, const float *t1_all,
                                      const float *s2_all, const float *t2_all, const float *w3_all, void **out) {
-  TN_REQUIRE(ctx && w1_all && s1_all && t1_all && s2_all && t2_all && w3_all && out, "tn_dbg_block28_create: null argument");
-  TN_REQUIRE(dense_block28_supported(28, 28, K0, nl), "tn_dbg_block28_create: unsupported geometry");
-  TN_ON_DEVICE(ctx->device);
-  std::vector<std::vector<float>> folded(nl);
-  std::vector<Block14Layer> layers(nl);
-  size_t o1 = 0, ok = 0;
-  for (int l = 0; l < nl; ++l) {
-    const int K = K0 + 32 * l;
-    folded[l].resize((size_t)128 * K);
-    for (int n = 0; n < 128; ++n)
-      for (int k = 0; k < K; ++k) folded[l][(size_t)n * K + k] = w1_all[o1 + (size_t)n * K + k] * s2_all[(size_t)l * 128 + n];
-    layers[l] = Block14Layer{folded[l].data(), w3_all + (size_t)l * 32 * 128 * 9, s1_all + ok, t1_all + ok, t2_all + (size_t)l * 128};
-    o1 += (size_t)128 * K;
-    ok += K;
-  }
-  const std::vector<unsigned char> img = pack_block28(layers, K0);
-  tn_dbg_block28 *b = new tn_dbg_block28();
-  b->ctx = ctx;
-  if (hipMalloc(&b->stream, img.size()) != hipSuccess || hipMemcpy(b->stream, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    tn_set_error("tn_dbg_block28_create: device allocation failed");
-    delete b;
-    return TN_ERR_NOMEM;
-  }
-  b->args = DenseBlock28Args{nullptr, 0, K0, nl, 0, (const unsigned char *)b->stream, dense_block28_units(K0, nl)};
-  *out = b;
-  return TN_OK;
+  return dbg_stream_create(kDenseStreamKernels[1], ctx, K0, nl, w1_all, s1_all, t1_all, s2_all, t2_all, w3_all, out);
 }
-
-extern "C" int tn_dbg_block28_run_ts(void *handle, void *buf_f16, int ldc, int B, unsigned long long *ts) {
-  tn_dbg_block28 *b = (tn_dbg_block28 *)handle;
-  TN_REQUIRE(b && buf_f16, "tn_dbg_block28_run: null argument");
-  TN_ON_DEVICE(b->ctx->device);
-  if (b->scratch_frames < B) {
-    (void)hipFree(b->scratch);
-    b->scratch = nullptr; b->scratch_frames = 0;
-    if (hipMalloc(&b->scratch, (size_t)B * dense_block28_scratch_halfs() * sizeof(f16)) != hipSuccess) {
-      tn_set_error("tn_dbg_block28_run: device allocation failed");
-      return TN_ERR_NOMEM;
-    }
-    b->scratch_frames = B;
-    TN_HIP_CHECK(hipMemset(b->scratch, 0, (size_t)B * dense_block28_scratch_halfs() * sizeof(f16)));
-  }
-  DenseBlock28Args a = b->args;
-  a.buf = (f16 *)buf_f16; a.ldc = ldc; a.B = B; a.ts = ts; a.scratch = (f16 *)b->scratch;
-  return launch_dense_block28(a, b->ctx->stream);
-}
-extern "C" int tn_dbg_block28_run(void *handle, void *buf_f16, int ldc, int B) { return tn_dbg_block28_run_ts(handle, buf_f16, ldc, B, nullptr); }
-
-extern "C" void tn_dbg_block28_destroy(void *handle) {
-  tn_dbg_block28 *b = (tn_dbg_block28 *)handle;
-  if (!b) return;
-  (void)hipFree(b->stream);
-  (void)hipFree(b->scratch);
-  delete b;
-}
+extern "C" int tn_dbg_block28_run_ts(void *handle, void *buf_f16, int ldc, int B, unsigned long long *ts) { return dbg_stream_run(handle, buf_f16, ldc, B, ts); }
+extern "C" int tn_dbg_block28_run(void *handle, void *buf_f16, int ldc, int B) { return dbg_stream_run(handle, buf_f16, ldc, B, nullptr); }
+extern "C" void tn_dbg_block28_destroy(void *handle) { dbg_stream_destroy(handle); }
 
 // The fine-tuning step's transposed GEMM (weight gradients): the split-K policy of gemm_tn_dispatch on the caller's workspace
 extern "C" int tn_dbg_gemm_tn(tn_ctx *ctx, const float *A, int lda, const float *B, int ldb, const float *bsc, const float *bsh, float *Cm,

@@ -31,11 +31,7 @@
 //   super-steps later: 24 younger loads) and the DMA pieces (consumed three units later).  tests/test_cpu_block14.py replays
 //   the issue order of a whole block and proves every count.  The ring registers are only ever touched by asm statements
 //   (loads, waits, BN1): scripts/audit_block14_isa.py fails the build if hipcc copies one of them while its load is in flight.
-#include <array>
-#include <type_traits>
-#include <utility>
-
-#include "common.h"
+#include "dense_stream.h"
 
 #ifndef TN_B14_STAMPS
 #define TN_B14_STAMPS 0   // tuning build: wave 0 also stamps the start of every layer's tail and 3x3 phase and the end of its 3x3 phase (ts[64 ..])
@@ -46,12 +42,7 @@
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-
-constexpr int kUnitFrag = 16384;                  // 16 A fragments of 1 KiB
-constexpr int kUnitBytes = kUnitFrag + 512;       // + BN1 constants of the unit's k-steps: [k-step][lane >> 5][dword J: s[2J], s[2J+1], t[2J], t[2J+1]] fp32
-constexpr int kNR = 5;                            // ring slots
+// (the unit layout, the ring constants, the DMA / wait / ring-register helpers: dense_stream.h)
 constexpr int kTileRowB = 4096;                   // 16 slots x 256 B (128 bottleneck channels, fp16)
 constexpr int kTileRows = 18;                     // row 0: zeros above the image, 1 .. 14 the image, 15: zeros below, 16 / 17: wave 3's rows that do not exist
 constexpr int kTileBytes = kTileRows * kTileRowB;
@@ -60,60 +51,16 @@ constexpr int kPlaneB = 196 * 32;                 // one k-step (16 channels) of
 constexpr int kFrameScrB = 64 * kPlaneB;          // 1024 channels
 static_assert(kLdsBytes <= 160 * 1024, "LDS");
 
-// s_waitcnt vmcnt(N) constants (asm loads only; tests/test_cpu_block14.py derives every one of them from the issue order)
-constexpr int kVmRing = 24;        // a ring register pair is waited for two super-step intervals (2 x 13 loads) after its refills, at the slot of
-                                   // the FIRST of its two loads' k-step: 26 - 2 loads lie behind the second one (25 was one too many: the replay test)
-constexpr int kVmDmaSU0 = 12, kVmDmaSU = 20, kVmDmaTail = 24, kVmDmaB0 = 16, kVmDmaB = 10;
+// s_waitcnt vmcnt(N) constants of the intervals only this kernel has (tests/test_cpu_block14.py; the shared ones: dense_stream.h)
+constexpr int kVmDmaTail = 24, kVmDmaB0 = 16;
 
-#define TN_INL __attribute__((always_inline))
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-  [&]<int... I>(std::integer_sequence<int, I...>) TN_INL { (f(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, N>{});
-}
-template <int V>
-using ic = std::integral_constant<int, V>;
-#define TN_SB() __builtin_amdgcn_sched_barrier(0)
+// what this kernel hands the shared statements of dense_stream.h
+struct Policy14 {
+  static constexpr int kPlaneB = ::kPlaneB;
+  static constexpr int kExp = TN_B14_EXP;
+};
 
-__device__ __forceinline__ f32x16 mfma32(const u32x4 a, const u32x4 b, const f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-
-// LDS-DMA: global (wave-uniform base in SGPRs + per-lane 32-bit offset) -> LDS (M0 + lane * size).  The instruction offset
-// applies to the global AND the LDS address (scripts/microbench/dmaoff.hip), so two 1-KiB pieces share one M0.
-template <int OFF>
-__device__ __forceinline__ void dma16x2(const void *gbase, unsigned voff16, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3 offset:%c4\n\t"
-               "global_load_lds_dwordx4 %2, %3 offset:%c5\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(lds_dst), "v"(voff16), "s"(gbase), "n"(OFF), "n"(OFF + 1024));
-}
-__device__ __forceinline__ void dma4(const void *gbase, unsigned voff4, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(lds_dst), "v"(voff4), "s"(gbase));
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%c0)" ::"n"(N) : "memory"); }
-
-// The activation ring lives in LITERAL registers v[192:255]: its loads are in flight for two super-step intervals, and a value
-// hipcc knows about may be copied or spilled at any time - with the bytes of a pending load not there yet (the first version of
-// this kernel, ring in compiler-allocated registers tied through the waits: "scratch_store_dwordx4 v[28:31]" one instruction
-// behind the load that fills v[28:31]).  Every slot names the 64 registers as clobbered, which keeps compiler values out of them
-// (the technique of the strip kernel's accumulator window); scripts/audit_block14_isa.py checks the ISA for strays.
-#define TN_RING_BASE 192
-#define TN_RING_CLOBBER                                                                                                             \
-  "v192", "v193", "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207",   \
-  "v208", "v209", "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223",   \
-  "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239",   \
-  "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255"
-#define TN_RING_FENCE() asm volatile("" ::: TN_RING_CLOBBER)
-constexpr int ring_reg(int rs, int kq, int f) { return TN_RING_BASE + ((rs * 4 + kq) * 2 + f) * 4; }   // [super-step parity][k-step][fragment] x 4 dwords
-
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void dense_block14_kernel(DenseBlock14Args a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void dense_block14_kernel(DenseStreamArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef __attribute__((address_space(3))) void *lptr_t;
   const int tid = threadIdx.x;
@@ -171,14 +118,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int cdelta = kUnitFrag - wid * 4096 + (wid & 1) * 256;  // from there to this wave's piece of the constants
   unsigned nxt = kTileBytes;                                    // byte offset in smem of the slot of unit g + 1
   unsigned vb_cur = 0, vb_next = 0, vc_cur = 0, vc_next = 0;    // LDS byte offsets: fragments (+ lane * 16) / constants (+ h * 64) of unit g, g + 1
-  auto dma_pair = [&](auto pr_tag) TN_INL {
-    if (TN_B14_EXP & 8) return;
-    dma16x2<decltype(pr_tag)::value * 2048>(dsrc, lane16, ddst);
-  };
-  auto dma_consts = [&]() TN_INL {
-    if (TN_B14_EXP & 8) return;
-    dma4(dsrc + cdelta, lane4, ddst + cdelta);
-  };
   auto advance_dma = [&]() TN_INL {
     dsrc += kUnitBytes;
     ddst = ddst + kUnitBytes >= ring_end ? ddst + kUnitBytes - kNR * kUnitBytes : ddst + kUnitBytes;
@@ -208,14 +147,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   // ---- ring: asm loads into literal registers + counted waits ----
   const unsigned char *rb_a = scr, *rb_b = scr;   // scr + 4 planes * (super-step index) of the two refill targets of an interval
-  auto ring_load = [&](auto rs_tag, auto k_tag, auto f_tag, const unsigned char *base) TN_INL {
-    constexpr int KQ = decltype(k_tag)::value, F = decltype(f_tag)::value, R = ring_reg(decltype(rs_tag)::value, KQ, F);
-    if (TN_B14_EXP & 1) return;
-    const unsigned vo = (TN_B14_EXP & 16) ? lane16 + (unsigned)(wid * 8 + F * 4 + KQ) * 1024u : voff[F];
-    const unsigned char *pb = base + KQ * kPlaneB;
-    asm volatile("global_load_dwordx4 v[%c0:%c1], %2, %3" ::"n"(R), "n"(R + 3), "v"(vo), "s"(pb) : TN_RING_CLOBBER);
-  };
-  auto ring_wait = [&](auto rs_tag, auto k_tag) TN_INL { asm volatile("s_waitcnt vmcnt(%c0)" ::"n"(kVmRing) : TN_RING_CLOBBER); };
   // BN1 + ReLU of one dword (two channels) of a pixel fragment: relu(a x + b) with fp16 constants, fused multiply-add (one rounding), packed max
   auto bn_ring = [&](auto reg_tag, auto j_tag) TN_INL -> unsigned {      // input: ring register REG
     constexpr int J = decltype(j_tag)::value, REG = decltype(reg_tag)::value;
@@ -272,13 +203,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       {
         constexpr int J = E >> 1, BF = E & 1;
         if constexpr (Q < 3) {
-          if constexpr (E == 0) ring_wait(ic<RS>{}, ic<Q + 1>{});
+          if constexpr (E == 0) ring_wait();
           if (!(TN_B14_EXP & 4)) xb[(Q + 1) & 1][BF][J] = bn_ring(ic<ring_reg(RS, Q + 1, BF) + J>{}, ic<J>{});
-          if constexpr (J == 3) ring_load(ic<RS>{}, ic<Q + 1>{}, ic<BF>{}, rb_a);
+          if constexpr (J == 3) ring_load<Policy14>(ic<RS>{}, ic<Q + 1>{}, ic<BF>{}, rb_a, voff, lane16, wid);
         } else if constexpr (!LAST) {
-          if constexpr (E == 0) ring_wait(ic<RS ^ 1>{}, ic<0>{});
+          if constexpr (E == 0) ring_wait();
           if (!(TN_B14_EXP & 4)) xb[0][BF][J] = bn_ring(ic<ring_reg(RS ^ 1, 0, BF) + J>{}, ic<J>{});
-          if constexpr (J == 3) ring_load(ic<RS ^ 1>{}, ic<0>{}, ic<BF>{}, rb_b);
+          if constexpr (J == 3) ring_load<Policy14>(ic<RS ^ 1>{}, ic<0>{}, ic<BF>{}, rb_b, voff, lane16, wid);
         } else {
           if (!(TN_B14_EXP & 4)) xb[0][BF][J] = bn_dword(fwd[BF][0][J], ic<J>{});
         }
@@ -296,9 +227,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       if constexpr (LAST && Q == 3) TN_RING_FENCE();      // (no ring statement in these slots)
       if constexpr (E == 7) {
-        if constexpr (Q == 0) dma_pair(ic<0>{});
-        else if constexpr (Q == 1) dma_pair(ic<1>{});
-        else if constexpr (Q == 3) dma_consts();
+        if constexpr (Q == 0) stream_dma_pair<Policy14>(ic<0>{}, dsrc, lane16, ddst);
+        else if constexpr (Q == 1) stream_dma_pair<Policy14>(ic<1>{}, dsrc, lane16, ddst);
+        else if constexpr (Q == 3) stream_dma_consts<Policy14>(dsrc, cdelta, lane4, ddst);
       }
       TN_SB();
     });
@@ -360,9 +291,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       if constexpr (I == 17) wsh[0] = *(const u32x4 *)(smem + vb_cur + (2 * 4 + 2) * 1024);
       if constexpr (I == 19) wsh[1] = *(const u32x4 *)(smem + vb_cur + (2 * 4 + 3) * 1024);
       if constexpr (I >= 18 && I < 23) epa_items(ic<0>{}, ic<(I - 18) * 4>{}, ic<4>{});
-      if constexpr (I == 7) dma_pair(ic<0>{});
-      if constexpr (I == 11) dma_pair(ic<1>{});
-      if constexpr (I == 15) dma_consts();
+      if constexpr (I == 7) stream_dma_pair<Policy14>(ic<0>{}, dsrc, lane16, ddst);
+      if constexpr (I == 11) stream_dma_pair<Policy14>(ic<1>{}, dsrc, lane16, ddst);
+      if constexpr (I == 15) stream_dma_consts<Policy14>(dsrc, cdelta, lane4, ddst);
       // the 3x3's first operands: weight fragments of steps 0 / 1 (unit g + 1), pixel fragments of step 0 (tuple 0: block 0's epilogue is done)
       if constexpr (I >= 12 && I < 18) w3_read(ic<(I - 12) / 3>{}, ic<(I - 12) % 3>{}, vb_next);
       if constexpr (I == 23) { bop_read(ic<0>{}, ic<0>{}); bop_read(ic<0>{}, ic<1>{}); }
@@ -384,9 +315,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       consts_read(vc_next, ic<0>{}, ic<I>{});
     } else if constexpr (I < 10) {
       constexpr int E = I - 2, J = E >> 1, BF = E & 1;
-      if constexpr (E == 0) ring_wait(ic<PN>{}, ic<0>{});
+      if constexpr (E == 0) ring_wait();
       if (!(TN_B14_EXP & 4)) xb[0][BF][J] = bn_ring(ic<ring_reg(PN, 0, BF) + J>{}, ic<J>{});
-      if constexpr (J == 3) ring_load(ic<PN>{}, ic<0>{}, ic<BF>{}, rb_a);
+      if constexpr (J == 3) ring_load<Policy14>(ic<PN>{}, ic<0>{}, ic<BF>{}, rb_a, voff, lane16, wid);
       if constexpr (BF == 1) {
         if constexpr (J < 2) consts_read(vc_next, ic<0>{}, ic<J + 2>{});
         else consts_read(vc_next, ic<1>{}, ic<J - 2>{});
@@ -434,9 +365,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       if constexpr (J == 0 && I >= 20) epa_items(ic<3>{}, ic<(I - 20) * 5 / 3>{}, ic<(I - 19) * 5 / 3 - (I - 20) * 5 / 3>{});
       if constexpr (J == 1 && I < 8) epa_items(ic<3>{}, ic<(I + 4) * 5 / 3>{}, ic<(I + 5) * 5 / 3 - (I + 4) * 5 / 3>{});
       if constexpr (J == 5 && I < kPreItems) pre_item(pn_tag, ic<I>{});     // (ahead of the interval's DMA statements: kVmRing counts on it)
-      if constexpr (I == 15) dma_pair(ic<0>{});
-      if constexpr (I == 19) dma_pair(ic<1>{});
-      if constexpr (I == 23) dma_consts();
+      if constexpr (I == 15) stream_dma_pair<Policy14>(ic<0>{}, dsrc, lane16, ddst);
+      if constexpr (I == 19) stream_dma_pair<Policy14>(ic<1>{}, dsrc, lane16, ddst);
+      if constexpr (I == 23) stream_dma_consts<Policy14>(dsrc, cdelta, lane4, ddst);
       TN_RING_FENCE();
       TN_SB();
     });
@@ -479,9 +410,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       *(u32x4 *)(smem + 17 * kTileRowB + i * 16) = u32x4{0, 0, 0, 0};
     }
     for (int u = 0; u < 4; ++u) {      // units 0 .. 3 (unit 4 belongs to interval 0)
-      dma_pair(ic<0>{});
-      dma_pair(ic<1>{});
-      dma_consts();
+      stream_dma_pair<Policy14>(ic<0>{}, dsrc, lane16, ddst);
+      stream_dma_pair<Policy14>(ic<1>{}, dsrc, lane16, ddst);
+      stream_dma_consts<Policy14>(dsrc, cdelta, lane4, ddst);
       advance_dma();
     }
     // channels 0 .. K0 - 1 of this wave's pixels: NHWC -> the k-step-major copy (a wave only ever reads its own pixels' planes)
@@ -511,7 +442,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // the first layer's ring: super-steps 0 (slot 0) and 1 (slot 1); its "forwarded" channels K0 - 32 .. K0 - 1 from memory
     static_for<16>([&](auto i_tag) TN_INL {
       constexpr int I = decltype(i_tag)::value;
-      ring_load(ic<(I >> 3)>{}, ic<((I >> 1) & 3)>{}, ic<(I & 1)>{}, scr + 4 * kPlaneB * (I >> 3));
+      ring_load<Policy14>(ic<(I >> 3)>{}, ic<((I >> 1) & 3)>{}, ic<(I & 1)>{}, scr + 4 * kPlaneB * (I >> 3), voff, lane16, wid);
     });
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
@@ -602,101 +533,44 @@ int dense_block14_units(int K0, int nl) {      // (with the four units of paddin
 
 size_t dense_block14_scratch_halfs() { return (size_t)kFrameScrB / 2; }
 
-int launch_dense_block14(const DenseBlock14Args &a, hipStream_t s) {
-  TN_REQUIRE(a.buf && a.stream && a.scratch, "dense_block14: null operand");
-  TN_REQUIRE(dense_block14_supported(14, 14, a.K0, a.nl) && a.ldc % 64 == 0 && a.K0 + 32 * a.nl <= a.ldc, "dense_block14: unsupported geometry");
-  TN_REQUIRE(a.total_units == dense_block14_units(a.K0, a.nl), "dense_block14: stream does not match the block");
-  TN_HIP_CHECK(hipFuncSetAttribute((const void *)dense_block14_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-  hipLaunchKernelGGL(dense_block14_kernel, dim3(a.B), dim3(256), kLdsBytes, s, a);
-  TN_HIP_CHECK(hipGetLastError());
-  return TN_OK;
+int launch_dense_block14(const DenseStreamArgs &a, hipStream_t s) {
+  return launch_stream_block<dense_block14_kernel>("dense_block14", a, dense_block14_supported(14, 14, a.K0, a.nl), dense_block14_units(a.K0, a.nl), kLdsBytes, s);
 }
 
-// ---- host-side packing: the block's weight stream ----
-// Per layer (K input channels, G = K - 32 of them read from memory): ceil(G / 64) super-step units, the tail unit, six 3x3 units;
-// every unit is kUnitBytes = 16 fragments [64 lanes][8 halfs] + 128 floats of BN1 constants.
-//   super-step unit u: fragment (q, mb): lane l, j: bottleneck channel 32 mb + (l & 31), input channel c = 64 u + 16 q + 8 (l >> 5)
-//     + j (zero weight and zero constants for c >= G: the pad half of the last super-step is the forwarded channels, which
-//     the tail takes); constants (q, h), dword J: halves a1[c + 2 J], a1[c + 2 J + 1], b1[c + 2 J], b1[c + 2 J + 1] (+ 8 B unused)
-//     for c = 64 u + 16 q + 8 h (s1 / t1 of Block14Layer are those fp16 numbers: bn_relu_fold_fp16)
+// ---- host-side packing: the block's weight stream (what a unit of each kind holds: StreamWriter, dense_stream.h) ----
+// Per layer (K input channels, G = K - 32 of them read from memory): ceil(G / 64) super-step units clipped at G (the pad half of
+// the last super-step is the forwarded channels, which the tail takes), the tail unit, six 3x3 units.
 //   tail unit: k-step 0 / 1: input channel G + 16 (l >> 5) + 8 ks + j (the order in which the previous layer's 3x3 leaves its 32
-//     output channels in registers); k-step 2: the shift k-step of dense_strip.hip (fp16 hi + lo of BN2's shift, and 1 for the mask)
-//   3x3 unit J: fragments (step 4 J + s, dx), s = 0 .. 3: kernel rows in the order ky = 1, 0, 2, tuple t = step % 8; lane layout as
-//     pack_w3_strip (dense_strip.hip)
+//     output channels in registers); k-step 2 (fragments 8 .. 11): the shift k-step
+//   3x3 units: kernel rows in the order ky = 1, 0, 2
 std::vector<unsigned char> pack_block14(const std::vector<Block14Layer> &layers, int K0) {
   const int nl = (int)layers.size();
   std::vector<unsigned char> out((size_t)dense_block14_units(K0, nl) * kUnitBytes, 0);
+  const StreamWriter w{out};
   size_t unit = 0;
-  auto frag = [&](size_t u, int fi) { return (f16 *)(out.data() + u * kUnitBytes + (size_t)fi * 1024); };
-  auto cons = [&](size_t u, int q, int h) { return (f16 *)(out.data() + u * kUnitBytes + kUnitFrag + (q * 2 + h) * 64); };
-  // channel j (0 .. 7) of a (k-step, half) group: dword J = j >> 1 holds halves (a[2J], a[2J+1]) | (b[2J], b[2J+1]) | 8 B unused
-  auto put_const = [](f16 *d, int j, float a, float b) {
-    d[8 * (j >> 1) + (j & 1)] = (f16)a;
-    d[8 * (j >> 1) + 2 + (j & 1)] = (f16)b;
-  };
   for (int l = 0; l < nl; ++l) {
     const Block14Layer &L = layers[l];
     const int K = K0 + 32 * l, G = K - 32, nsu = (G + 63) / 64;
-    for (int u = 0; u < nsu; ++u, ++unit)
-      for (int q = 0; q < 4; ++q) {
-        for (int mb = 0; mb < 4; ++mb) {
-          f16 *d = frag(unit, q * 4 + mb);
-          for (int ln = 0; ln < 64; ++ln)
-            for (int j = 0; j < 8; ++j) {
-              const int c = 64 * u + 16 * q + 8 * (ln >> 5) + j;
-              d[ln * 8 + j] = c < G ? (f16)L.w1f[(size_t)(32 * mb + (ln & 31)) * K + c] : (f16)0.f;
-            }
-        }
-        for (int h = 0; h < 2; ++h) {
-          f16 *d = cons(unit, q, h);
-          for (int j = 0; j < 8; ++j) {
-            const int c = 64 * u + 16 * q + 8 * h + j;
-            put_const(d, j, c < G ? L.s1[c] : 0.f, c < G ? L.t1[c] : 0.f);
-          }
-        }
-      }
-    {  // tail
-      for (int ks = 0; ks < 2; ++ks) {
-        for (int mb = 0; mb < 4; ++mb) {
-          f16 *d = frag(unit, ks * 4 + mb);
-          for (int ln = 0; ln < 64; ++ln)
-            for (int j = 0; j < 8; ++j) {
-              const int c = G + 16 * (ln >> 5) + 8 * ks + j;
-              d[ln * 8 + j] = (f16)L.w1f[(size_t)(32 * mb + (ln & 31)) * K + c];
-            }
-        }
-        for (int h = 0; h < 2; ++h) {
-          f16 *d = cons(unit, ks, h);
-          for (int j = 0; j < 8; ++j) {
-            const int c = G + 16 * h + 8 * ks + j;
-            put_const(d, j, L.s1[c], L.t1[c]);
-          }
-        }
-      }
+    for (int u = 0; u < nsu; ++u) w.put_superstep(unit++, L, K, u, G);
+    for (int ks = 0; ks < 2; ++ks) {      // tail
       for (int mb = 0; mb < 4; ++mb) {
-        f16 *d = frag(unit, 2 * 4 + mb);
-        for (int ln = 0; ln < 32; ++ln) {
-          const float t = L.t2[32 * mb + ln];
-          d[ln * 8 + 0] = (f16)t;
-          d[ln * 8 + 1] = (f16)(t - (float)d[ln * 8 + 0]);
-          d[ln * 8 + 2] = (f16)1.f;
+        f16 *d = w.frag(unit, ks * 4 + mb);
+        for (int ln = 0; ln < 64; ++ln)
+          for (int j = 0; j < 8; ++j) {
+            const int c = G + 16 * (ln >> 5) + 8 * ks + j;
+            d[ln * 8 + j] = (f16)L.w1f[(size_t)(32 * mb + (ln & 31)) * K + c];
+          }
+      }
+      for (int h = 0; h < 2; ++h) {
+        f16 *d = w.cons(unit, ks, h);
+        for (int j = 0; j < 8; ++j) {
+          const int c = G + 16 * h + 8 * ks + j;
+          StreamWriter::put_const(d, j, L.s1[c], L.t1[c]);
         }
       }
-      ++unit;
     }
-    for (int J = 0; J < 6; ++J, ++unit)
-      for (int s = 0; s < 4; ++s) {
-        const int step = 4 * J + s, ky = step / 8 == 0 ? 1 : (step / 8 == 1 ? 0 : 2), t = step % 8;
-        for (int dx = 0; dx < 3; ++dx) {
-          f16 *d = frag(unit, s * 3 + dx);
-          for (int ln = 0; ln < 64; ++ln)
-            for (int j = 0; j < 8; ++j) {
-              const int m = ln & 31, o = 16 * ((m >> 2) & 1) + (m & 3) + 4 * (m >> 3);
-              const int c = 16 * t + 8 * (j >> 2) + 4 * (ln >> 5) + (j & 3);
-              d[ln * 8 + j] = (f16)L.w3[(((size_t)o * 128 + c) * 3 + ky) * 3 + dx];
-            }
-        }
-      }
+    w.put_shift(unit++, 8, L);
+    for (int J = 0; J < 6; ++J) w.put_3x3(unit++, L, J, {1, 0, 2});
   }
   return out;
 }

@@ -30,20 +30,11 @@
 //   slots of the previous pass' last 3x3 unit and wait in registers), so a pass' accumulators start from the shift and its last
 //   1x1 unit runs straight into the 3x3.
 // * vmcnt is hand-counted for every steady-state load as in dense_block14.hip (tests/test_cpu_block28.py replays the issue order).
-#include <array>
-#include <type_traits>
-#include <utility>
-
-#include "common.h"
+#include "dense_stream.h"
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-
-constexpr int kUnitFrag = 16384;                  // 16 A fragments of 1 KiB
-constexpr int kUnitBytes = kUnitFrag + 512;       // + BN1 constants of the unit's k-steps (dense_block14.hip's layout)
-constexpr int kNR = 5;                            // ring slots
+// (the unit layout, the ring constants, the DMA / wait / ring-register helpers: dense_stream.h)
 constexpr int kRowSlots = 30;                     // a tile row: columns -1 .. 28
 constexpr int kTileRowB = kRowSlots * 256;        // 128 bottleneck channels, fp16, per slot
 constexpr int kTileRows = 10;                     // rolling: row R lives in tile row (R + 2) % 10
@@ -58,56 +49,16 @@ constexpr int kFrameScrB = kPlanes * kPlaneB + 4096;   // (+ rows 28 .. 31 of th
 constexpr int kPassB = 8 * 28 * 32;               // a pass' rows inside a plane
 static_assert(kLdsBytes <= 160 * 1024, "LDS");
 
-// s_waitcnt vmcnt(N) constants (asm loads only; tests/test_cpu_block28.py derives every one of them from the issue order)
-constexpr int kVmRing = 24;        // a ring register pair is waited for two super-step intervals (2 x 13 loads) after its refills
-constexpr int kVmDmaSU0 = 12, kVmDmaSU = 20, kVmDmaB0 = 24, kVmDmaB = 10;
+// s_waitcnt vmcnt(N) of the first 3x3 interval, which here follows a super-step interval (tests/test_cpu_block28.py; the shared ones: dense_stream.h)
+constexpr int kVmDmaB0 = 24;
 
-#define TN_INL __attribute__((always_inline))
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-  [&]<int... I>(std::integer_sequence<int, I...>) TN_INL { (f(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, N>{});
-}
-template <int V>
-using ic = std::integral_constant<int, V>;
-#define TN_SB() __builtin_amdgcn_sched_barrier(0)
+// what this kernel hands the shared statements of dense_stream.h
+struct Policy28 {
+  static constexpr int kPlaneB = ::kPlaneB;
+  static constexpr int kExp = 0;
+};
 
-__device__ __forceinline__ f32x16 mfma32(const u32x4 a, const u32x4 b, const f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-
-// LDS-DMA: global (wave-uniform base in SGPRs + per-lane 32-bit offset) -> LDS (M0 + lane * size); the instruction offset applies
-// to the global AND the LDS address (dense_block14.hip)
-template <int OFF>
-__device__ __forceinline__ void dma16x2(const void *gbase, unsigned voff16, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3 offset:%c4\n\t"
-               "global_load_lds_dwordx4 %2, %3 offset:%c5\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(lds_dst), "v"(voff16), "s"(gbase), "n"(OFF), "n"(OFF + 1024));
-}
-__device__ __forceinline__ void dma4(const void *gbase, unsigned voff4, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(lds_dst), "v"(voff4), "s"(gbase));
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%c0)" ::"n"(N) : "memory"); }
-
-// The activation ring lives in LITERAL registers v[192:255] (dense_block14.hip: a value hipcc knows about may be copied or spilled
-// while its load is in flight); scripts/audit_block14_isa.py checks the ISA for strays.
-#define TN_RING_BASE 192
-#define TN_RING_CLOBBER                                                                                                             \
-  "v192", "v193", "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207",   \
-  "v208", "v209", "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223",   \
-  "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239",   \
-  "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255"
-#define TN_RING_FENCE() asm volatile("" ::: TN_RING_CLOBBER)
-constexpr int ring_reg(int rs, int kq, int f) { return TN_RING_BASE + ((rs * 4 + kq) * 2 + f) * 4; }   // [super-step parity][k-step][fragment] x 4 dwords
-
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void dense_block28_kernel(DenseBlock28Args a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void dense_block28_kernel(DenseStreamArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef __attribute__((address_space(3))) void *lptr_t;
   const int tid = threadIdx.x;
@@ -151,8 +102,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int cdelta = kUnitFrag - wid * 4096 + (wid & 1) * 256;  // from there to this wave's piece of the constants
   unsigned nxt = kRingOff;                                      // byte offset in smem of the slot of unit g + 1
   unsigned vb_cur = 0, vb_next = 0, vc_cur = 0, vc_next = 0;    // LDS byte offsets: fragments (+ lane * 16) / constants (+ h * 64) of unit g, g + 1
-  auto dma_pair = [&](auto pr_tag) TN_INL { dma16x2<decltype(pr_tag)::value * 2048>(dsrc, lane16, ddst); };
-  auto dma_consts = [&]() TN_INL { dma4(dsrc + cdelta, lane4, ddst + cdelta); };
   auto advance_dma = [&]() TN_INL {
     dsrc += kUnitBytes;
     ddst = ddst + kUnitBytes >= ring_end ? ddst + kUnitBytes - kNR * kUnitBytes : ddst + kUnitBytes;
@@ -182,13 +131,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   // ---- ring: asm loads into literal registers + counted waits ----
   const unsigned char *rb_a = scr, *rb_b = scr;   // plane base (pass offset included) of the two refill targets of an interval
-  auto ring_load = [&](auto rs_tag, auto k_tag, auto f_tag, const unsigned char *base) TN_INL {
-    constexpr int KQ = decltype(k_tag)::value, F = decltype(f_tag)::value, R = ring_reg(decltype(rs_tag)::value, KQ, F);
-    const unsigned vo = voff[F];
-    const unsigned char *pb = base + KQ * kPlaneB;
-    asm volatile("global_load_dwordx4 v[%c0:%c1], %2, %3" ::"n"(R), "n"(R + 3), "v"(vo), "s"(pb) : TN_RING_CLOBBER);
-  };
-  auto ring_wait = [&]() TN_INL { asm volatile("s_waitcnt vmcnt(%c0)" ::"n"(kVmRing) : TN_RING_CLOBBER); };
   // BN1 + ReLU of one dword (two channels) of a pixel fragment: relu(a x + b) with fp16 constants, fused multiply-add, packed max
   auto bn_ring = [&](auto reg_tag, auto j_tag) TN_INL -> unsigned {      // input: ring register REG
     constexpr int J = decltype(j_tag)::value, REG = decltype(reg_tag)::value;
@@ -271,11 +213,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if constexpr (Q < 3) {
           if constexpr (E == 0) ring_wait();
           xb[(Q + 1) & 1][BF][J] = bn_ring(ic<ring_reg(RS, Q + 1, BF) + J>{}, ic<J>{});
-          if constexpr (J == 3) ring_load(ic<RS>{}, ic<Q + 1>{}, ic<BF>{}, rb_a);
+          if constexpr (J == 3) ring_load<Policy28>(ic<RS>{}, ic<Q + 1>{}, ic<BF>{}, rb_a, voff, lane16, wid);
         } else {
           if constexpr (E == 0) ring_wait();
           xb[0][BF][J] = bn_ring(ic<ring_reg(RS ^ 1, 0, BF) + J>{}, ic<J>{});
-          if constexpr (J == 3) ring_load(ic<RS ^ 1>{}, ic<0>{}, ic<BF>{}, rb_b);
+          if constexpr (J == 3) ring_load<Policy28>(ic<RS ^ 1>{}, ic<0>{}, ic<BF>{}, rb_b, voff, lane16, wid);
         }
         if constexpr (BF == 1 && !(LAST && Q == 2 && J >= 2)) {
           if constexpr (J < 2) {
@@ -295,9 +237,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         TN_RING_FENCE();
       }
       if constexpr (E == 7) {
-        if constexpr (Q == 0) dma_pair(ic<0>{});
-        else if constexpr (Q == 1) dma_pair(ic<1>{});
-        else if constexpr (Q == 3) dma_consts();
+        if constexpr (Q == 0) stream_dma_pair<Policy28>(ic<0>{}, dsrc, lane16, ddst);
+        else if constexpr (Q == 1) stream_dma_pair<Policy28>(ic<1>{}, dsrc, lane16, ddst);
+        else if constexpr (Q == 3) stream_dma_consts<Policy28>(dsrc, cdelta, lane4, ddst);
       }
       TN_SB();
     });
@@ -317,7 +259,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       constexpr int E = I - 2, J = E >> 1, BF = E & 1;
       if constexpr (E == 0) ring_wait();
       xb[0][BF][J] = bn_ring(ic<ring_reg(PN, 0, BF) + J>{}, ic<J>{});
-      if constexpr (J == 3) ring_load(ic<PN>{}, ic<0>{}, ic<BF>{}, rb_a);
+      if constexpr (J == 3) ring_load<Policy28>(ic<PN>{}, ic<0>{}, ic<BF>{}, rb_a, voff, lane16, wid);
       if constexpr (BF == 1) {
         if constexpr (J < 2) consts_read(vc_next, ic<0>{}, ic<J + 2>{});
         else consts_read(vc_next, ic<1>{}, ic<J - 2>{});
@@ -368,9 +310,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       if constexpr (J == 1 && I < 8) epa_items(ic<3>{}, ic<(I + 4) * 5 / 3>{}, ic<(I + 5) * 5 / 3 - (I + 4) * 5 / 3>{});
       if constexpr (J == 5 && I < kPreItems) pre_item(pn_tag, ic<I>{});     // (ahead of the interval's DMA statements: kVmRing counts on it)
       if constexpr (J == 5 && I >= 16 && I < 20) wsh_read(ic<I - 16>{}, vb_cur);      // the next pass' shift fragments
-      if constexpr (I == 15) dma_pair(ic<0>{});
-      if constexpr (I == 19) dma_pair(ic<1>{});
-      if constexpr (I == 23) dma_consts();
+      if constexpr (I == 15) stream_dma_pair<Policy28>(ic<0>{}, dsrc, lane16, ddst);
+      if constexpr (I == 19) stream_dma_pair<Policy28>(ic<1>{}, dsrc, lane16, ddst);
+      if constexpr (I == 23) stream_dma_consts<Policy28>(dsrc, cdelta, lane4, ddst);
       TN_RING_FENCE();
       TN_SB();
     });
@@ -431,9 +373,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int i = tid; i < (2 * kTileRowB) / 16; i += 256) *(u32x4 *)(smem + i * 16) = u32x4{0, 0, 0, 0};
     if (tid < kDumpBytes / 16) *(u32x4 *)(smem + kTileBytes + tid * 16) = u32x4{0, 0, 0, 0};
     for (int u = 0; u < 4; ++u) {      // units 0 .. 3 (unit 0: the first pass' shift fragments)
-      dma_pair(ic<0>{});
-      dma_pair(ic<1>{});
-      dma_consts();
+      stream_dma_pair<Policy28>(ic<0>{}, dsrc, lane16, ddst);
+      stream_dma_pair<Policy28>(ic<1>{}, dsrc, lane16, ddst);
+      stream_dma_consts<Policy28>(dsrc, cdelta, lane4, ddst);
       advance_dma();
     }
     // channels 0 .. K0 - 1 of the frame: NHWC -> the k-step-major copy
@@ -455,7 +397,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // the first pass' ring: super-steps 0 (slot 0) and 1 (slot 1)
     static_for<16>([&](auto i_tag) TN_INL {
       constexpr int I = decltype(i_tag)::value;
-      ring_load(ic<(I >> 3)>{}, ic<((I >> 1) & 3)>{}, ic<(I & 1)>{}, scr + 4 * kPlaneB * (I >> 3));
+      ring_load<Policy28>(ic<(I >> 3)>{}, ic<((I >> 1) & 3)>{}, ic<(I & 1)>{}, scr + 4 * kPlaneB * (I >> 3), voff, lane16, wid);
     });
     asm volatile("s_waitcnt vmcnt(0)" ::: TN_RING_CLOBBER);
     // "interval 0": unit 0 = the first pass' shift fragments; unit 1 is the next unit
@@ -469,9 +411,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       rb_a = uniform_ptr(nsu0 > 2 ? scr + 4 * kPlaneB * 2 : scr + kPassB);
     }
     static_for<kPreItems>([&](auto i_tag) TN_INL { pre_item(ic<0>{}, i_tag); });
-    dma_pair(ic<0>{});
-    dma_pair(ic<1>{});
-    dma_consts();
+    stream_dma_pair<Policy28>(ic<0>{}, dsrc, lane16, ddst);
+    stream_dma_pair<Policy28>(ic<1>{}, dsrc, lane16, ddst);
+    stream_dma_consts<Policy28>(dsrc, cdelta, lane4, ddst);
     end_interval();
     asm volatile("s_waitcnt vmcnt(0)" ::: TN_RING_CLOBBER);
     TN_SB();
@@ -559,85 +501,31 @@ int dense_block28_units(int K0, int nl) {      // (the prologue unit in front, f
 
 size_t dense_block28_scratch_halfs() { return (size_t)kFrameScrB / 2; }
 
-int launch_dense_block28(const DenseBlock28Args &a, hipStream_t s) {
-  TN_REQUIRE(a.buf && a.stream && a.scratch, "dense_block28: null operand");
-  TN_REQUIRE(dense_block28_supported(28, 28, a.K0, a.nl) && a.ldc % 64 == 0 && a.K0 + 32 * a.nl <= a.ldc && a.B > 0, "dense_block28: unsupported geometry");
-  TN_REQUIRE(a.total_units == dense_block28_units(a.K0, a.nl), "dense_block28: stream does not match the block");
-  TN_SET_ATTR_ONCE_PER_DEVICE(TN_HIP_CHECK(hipFuncSetAttribute((const void *)dense_block28_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes)));
-  hipLaunchKernelGGL(dense_block28_kernel, dim3(a.B), dim3(256), kLdsBytes, s, a);
-  TN_HIP_CHECK(hipGetLastError());
-  return TN_OK;
+int launch_dense_block28(const DenseStreamArgs &a, hipStream_t s) {
+  return launch_stream_block<dense_block28_kernel>("dense_block28", a, dense_block28_supported(28, 28, a.K0, a.nl), dense_block28_units(a.K0, a.nl), kLdsBytes, s);
 }
 
-// ---- host-side packing: the block's weight stream ----
+// ---- host-side packing: the block's weight stream (what a unit of each kind holds: StreamWriter, dense_stream.h) ----
 // unit 0: fragments 12 .. 15 = the shift k-step of layer 0 (pass 0).  Then per layer, four times (once per pass):
-//   ceil(K / 64) super-step units: fragment (q, mb): lane l, j: bottleneck channel 32 mb + (l & 31), input channel c = 64 u + 16 q
-//     + 8 (l >> 5) + j (zero weight and zero constants for c >= K); constants (q, h), dword J: halves a1[c + 2 J], a1[c + 2 J + 1],
-//     b1[c + 2 J], b1[c + 2 J + 1] (+ 8 B unused) for c = 64 u + 16 q + 8 h (s1 / t1 of Block14Layer are those fp16 numbers);
-//   six 3x3 units J: fragments (step 4 J + s, dx) at s * 3 + dx, s = 0 .. 3: kernel rows in the order ky = 2, 1, 0 (dy = +1, 0, -1),
-//     tuple t = step % 8, lane layout as pack_w3_strip (dense_strip.hip); unit J = 5 also carries, in fragments 12 .. 15, the shift
-//     k-step (dense_strip.hip: fp16 hi + lo of BN2's shift, and 1 for the mask) of the NEXT pass: this layer's, or behind the
-//     fourth pass the next layer's.
+//   ceil(K / 64) super-step units clipped at K;
+//   six 3x3 units J, kernel rows in the order ky = 2, 1, 0 (dy = +1, 0, -1); unit J = 5 also carries, in fragments 12 .. 15, the
+//     shift k-step of the NEXT pass: this layer's, or behind the fourth pass the next layer's.
 std::vector<unsigned char> pack_block28(const std::vector<Block14Layer> &layers, int K0) {
   const int nl = (int)layers.size();
   std::vector<unsigned char> out((size_t)dense_block28_units(K0, nl) * kUnitBytes, 0);
+  const StreamWriter w{out};
   size_t unit = 0;
-  auto frag = [&](size_t u, int fi) { return (f16 *)(out.data() + u * kUnitBytes + (size_t)fi * 1024); };
-  auto cons = [&](size_t u, int q, int h) { return (f16 *)(out.data() + u * kUnitBytes + kUnitFrag + (q * 2 + h) * 64); };
-  auto put_const = [](f16 *d, int j, float a, float b) {
-    d[8 * (j >> 1) + (j & 1)] = (f16)a;
-    d[8 * (j >> 1) + 2 + (j & 1)] = (f16)b;
-  };
-  auto put_shift = [&](size_t u, const Block14Layer &L) {
-    for (int mb = 0; mb < 4; ++mb) {
-      f16 *d = frag(u, 12 + mb);
-      for (int ln = 0; ln < 32; ++ln) {
-        const float t = L.t2[32 * mb + ln];
-        d[ln * 8 + 0] = (f16)t;
-        d[ln * 8 + 1] = (f16)(t - (float)d[ln * 8 + 0]);
-        d[ln * 8 + 2] = (f16)1.f;
-      }
-    }
-  };
-  put_shift(unit++, layers[0]);
+  w.put_shift(unit++, 12, layers[0]);
   for (int l = 0; l < nl; ++l) {
     const Block14Layer &L = layers[l];
     const int K = K0 + 32 * l, nsu = (K + 63) / 64;
     for (int p = 0; p < 4; ++p) {
-      for (int u = 0; u < nsu; ++u, ++unit)
-        for (int q = 0; q < 4; ++q) {
-          for (int mb = 0; mb < 4; ++mb) {
-            f16 *d = frag(unit, q * 4 + mb);
-            for (int ln = 0; ln < 64; ++ln)
-              for (int j = 0; j < 8; ++j) {
-                const int c = 64 * u + 16 * q + 8 * (ln >> 5) + j;
-                d[ln * 8 + j] = c < K ? (f16)L.w1f[(size_t)(32 * mb + (ln & 31)) * K + c] : (f16)0.f;
-              }
-          }
-          for (int h = 0; h < 2; ++h) {
-            f16 *d = cons(unit, q, h);
-            for (int j = 0; j < 8; ++j) {
-              const int c = 64 * u + 16 * q + 8 * h + j;
-              put_const(d, j, c < K ? L.s1[c] : 0.f, c < K ? L.t1[c] : 0.f);
-            }
-          }
-        }
+      for (int u = 0; u < nsu; ++u) w.put_superstep(unit++, L, K, u, K);
       for (int J = 0; J < 6; ++J, ++unit) {
-        for (int s = 0; s < 4; ++s) {
-          const int step = 4 * J + s, ky = 2 - step / 8, t = step % 8;
-          for (int dx = 0; dx < 3; ++dx) {
-            f16 *d = frag(unit, s * 3 + dx);
-            for (int ln = 0; ln < 64; ++ln)
-              for (int j = 0; j < 8; ++j) {
-                const int m = ln & 31, o = 16 * ((m >> 2) & 1) + (m & 3) + 4 * (m >> 3);
-                const int c = 16 * t + 8 * (j >> 2) + 4 * (ln >> 5) + (j & 3);
-                d[ln * 8 + j] = (f16)L.w3[(((size_t)o * 128 + c) * 3 + ky) * 3 + dx];
-              }
-          }
-        }
+        w.put_3x3(unit, L, J, {2, 1, 0});
         if (J == 5) {
-          if (p < 3) put_shift(unit, L);
-          else if (l + 1 < nl) put_shift(unit, layers[l + 1]);
+          if (p < 3) w.put_shift(unit, 12, L);
+          else if (l + 1 < nl) w.put_shift(unit, 12, layers[l + 1]);
         }
       }
     }

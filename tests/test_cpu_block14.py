@@ -1,4 +1,5 @@
-"""-m "not gpu": the hand-counted s_waitcnt vmcnt(N) constants of dense_block14.hip, proven by replaying the kernel's issue order.
+"""-m "not gpu": the hand-counted s_waitcnt vmcnt(N) constants of dense_block14.hip (and of the core it shares with
+dense_block28.hip, dense_stream.h), proven by replaying the kernel's issue order.
 
 The 14x14 block kernel issues every steady-state vector-memory load from inline asm (the activation ring's refills and the
 LDS-DMA pieces of the weight stream) and waits for them with literal counts: vmcnt(N) returns when at most N loads are
@@ -6,67 +7,15 @@ outstanding, and loads complete in order, so a wait is correct iff at least N lo
 test re-states the issue order of one wave for whole blocks (every interval kind, both ring parities, odd and even super-step
 counts), takes the constants from the source, and checks every wait - plus that each ring register holds the super-step and
 k-step its consumer expects.  It is a model of the schedule, kept next to it: a change of the slot layout in the kernel has to
-be mirrored here (the comments name the lambdas)."""
-import os
-import re
-
+be mirrored here and in tests/tools/vmcnt_replay.py, which holds the wave model and the replay of a super-step interval (the
+comments name the kernel's statements)."""
 import pytest
 
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tennis_amd", "csrc", "dense_block14.hip")
+from tools.vmcnt_replay import Wave, constants as _constants
 
 
-def constants():
-    text = open(SRC).read()
-    c = {k: int(v) for k, v in re.findall(r"\b(kVm\w+) = (\d+)", text)}
-    c["kNR"] = int(re.search(r"constexpr int kNR = (\d+)", text).group(1))
-    c["kPreItems"] = int(re.search(r"constexpr int kPreItems = (\d+)", text).group(1))
-    return c
-
-
-class Wave:
-    def __init__(self, c):
-        self.c = c
-        self.n = 0                      # loads issued so far
-        self.done_upto = 0              # loads [0, done_upto) known complete (a vmcnt(0))
-        self.ring = {}                  # (rs, kq, f) -> (issue index, (layer, su, kq))
-        self.dma = {}                   # unit -> issue index of this wave's LAST piece
-        self.next_unit = 0              # unit the next DMA statements copy
-        self.min_slack = {}
-
-    def load(self):
-        self.n += 1
-        return self.n - 1
-
-    def need(self, idx, vm, what):
-        younger = self.n - 1 - idx
-        ok = idx < self.done_upto or younger >= vm
-        assert ok, f"{what}: vmcnt({vm}) with only {younger} loads behind the one it waits for"
-        if idx >= self.done_upto:
-            k = what.split(":")[0]
-            self.min_slack[k] = min(self.min_slack.get(k, 1 << 30), younger - vm)
-
-    # -- the kernel's statements
-    def dma_pair(self):
-        self.load(); self.load()
-
-    def dma_consts(self):
-        self.dma[self.next_unit] = self.load()
-        self.next_unit += 1             # (advance_dma at the end of the interval; nothing copies in between)
-
-    def ring_load(self, rs, kq, f, holds):
-        self.ring[(rs, kq, f)] = (self.load(), holds)
-
-    def ring_wait(self, rs, kq, expect):
-        for f in (0, 1):
-            idx, holds = self.ring[(rs, kq, f)]
-            assert holds == expect, f"ring[{rs}][{kq}][{f}] holds {holds}, its consumer expects {expect}"
-            self.need(idx, self.c["kVmRing"], "ring: %s" % (expect,))
-
-    def begin_interval(self, g, vm):
-        if g + 1 in self.dma:           # this wave's pieces of unit g + 1
-            self.need(self.dma[g + 1], vm, "dma: unit %d" % (g + 1))
-        else:
-            raise AssertionError(f"unit {g + 1} was never copied")
+def constants():      # (the shared ones from dense_stream.h, kVmDmaTail / kVmDmaB0 from the kernel's own file)
+    return _constants("dense_block14.hip", ["kVmRing", "kVmDmaSU0", "kVmDmaSU", "kVmDmaTail", "kVmDmaB0", "kVmDmaB", "kNR", "kPreItems"])
 
 
 def nsu_of(K):
@@ -102,28 +51,7 @@ def run_block(K0, nl, c):
         assert nsu >= 4
         for u in range(nsu):             # su_interval
             kind = 0 if u == 0 else (2 if u == nsu - 1 else 1)
-            rs = (u + par) & 1
-            w.begin_interval(g, c["kVmDmaSU0"] if kind == 0 else c["kVmDmaSU"])
-            la, ua = wrap(l, u + 2)
-            lb, ub = wrap(l, u + 3)
-            for q in range(4):
-                for e in range(8):
-                    j, bf = e >> 1, e & 1
-                    if q < 3:
-                        if e == 0:
-                            w.ring_wait(rs, q + 1, (l, u, q + 1))
-                        if j == 3:
-                            w.ring_load(rs, q + 1, bf, (la, ua, q + 1))
-                    elif kind != 2:
-                        if e == 0:
-                            w.ring_wait(rs ^ 1, 0, (l, u + 1, 0))
-                        if j == 3:
-                            w.ring_load(rs ^ 1, 0, bf, (lb, ub, 0))
-                    if e == 7:
-                        if q in (0, 1):
-                            w.dma_pair()
-                        elif q == 3:
-                            w.dma_consts()
+            w.su_interval(g, (u + par) & 1, kind, (l, u), (l, u + 1), wrap(l, u + 2), wrap(l, u + 3))
             g += 1
         # tail_interval
         w.begin_interval(g, c["kVmDmaTail"])

@@ -3,63 +3,15 @@
 the one it needs).  The 28x28 kernel walks a frame in four passes per layer: its stages are (layer, pass) pairs, the activation
 ring runs through pass and layer boundaries (two-super-step layers wrap through TWO stages), there is no tail interval (the shift
 k-step opens a pass' first 1x1 unit, no loads), and the last 1x1 unit of a pass runs straight into the six 3x3 units.  A change of
-the slot layout in the kernel has to be mirrored here (the comments name the lambdas)."""
-import os
-import re
-
+the slot layout in the kernel has to be mirrored here and in tests/tools/vmcnt_replay.py, which holds the wave model and the
+replay of a super-step interval (the comments name the kernel's statements)."""
 import pytest
 
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tennis_amd", "csrc", "dense_block28.hip")
+from tools.vmcnt_replay import Wave, constants as _constants
 
 
-def constants():
-    text = open(SRC).read()
-    c = {k: int(v) for k, v in re.findall(r"\b(kVm\w+) = (\d+)", text)}
-    c["kNR"] = int(re.search(r"constexpr int kNR = (\d+)", text).group(1))
-    c["kPreItems"] = int(re.search(r"constexpr int kPreItems = (\d+)", text).group(1))
-    return c
-
-
-class Wave:
-    def __init__(self, c):
-        self.c = c
-        self.n = 0                      # loads issued so far
-        self.done_upto = 0              # loads [0, done_upto) known complete (a vmcnt(0))
-        self.ring = {}                  # (rs, kq, f) -> (issue index, (stage, su, kq))
-        self.dma = {}                   # unit -> issue index of this wave's LAST piece
-        self.next_unit = 0
-        self.min_slack = {}
-
-    def load(self):
-        self.n += 1
-        return self.n - 1
-
-    def need(self, idx, vm, what):
-        younger = self.n - 1 - idx
-        assert idx < self.done_upto or younger >= vm, f"{what}: vmcnt({vm}) with only {younger} loads behind the one it waits for"
-        if idx >= self.done_upto:
-            k = what.split(":")[0]
-            self.min_slack[k] = min(self.min_slack.get(k, 1 << 30), younger - vm)
-
-    def dma_pair(self):
-        self.load(); self.load()
-
-    def dma_consts(self):
-        self.dma[self.next_unit] = self.load()
-        self.next_unit += 1
-
-    def ring_load(self, rs, kq, f, holds):
-        self.ring[(rs, kq, f)] = (self.load(), holds)
-
-    def ring_wait(self, rs, kq, expect):
-        for f in (0, 1):
-            idx, holds = self.ring[(rs, kq, f)]
-            assert holds == expect, f"ring[{rs}][{kq}][{f}] holds {holds}, its consumer expects {expect}"
-            self.need(idx, self.c["kVmRing"], "ring: %s" % (expect,))
-
-    def begin_interval(self, g, vm):
-        assert g + 1 in self.dma, f"unit {g + 1} was never copied"
-        self.need(self.dma[g + 1], vm, "dma: unit %d" % (g + 1))
+def constants():      # (the shared ones from dense_stream.h, this kernel's kVmDmaB0 from its own file)
+    return _constants("dense_block28.hip", ["kVmRing", "kVmDmaSU0", "kVmDmaSU", "kVmDmaB0", "kVmDmaB", "kNR", "kPreItems"])
 
 
 def nsu_of(K):
@@ -101,7 +53,6 @@ def run_block(K0, nl, c):
         for u in range(nsu):             # su_interval
             kind = 0 if u == 0 else (2 if u == nsu - 1 else 1)
             rs = (u + par) & 1
-            w.begin_interval(g, c["kVmDmaSU0"] if kind == 0 else c["kVmDmaSU"])
             ta, tb = wrap(si, u + 2), wrap(si, u + 3)
             # the kernel's straight-line `target` wraps at most twice, and only with the NEXT stage's count for the second wrap
             for t_, d in ((ta, 2), (tb, 3)):
@@ -112,24 +63,7 @@ def run_block(K0, nl, c):
                     if uu >= n1:
                         uu -= n1; ss = 2
                 assert (si + ss, uu) == t_, ((si, u, d), (si + ss, uu), t_)
-            for q in range(4):
-                for e in range(8):
-                    j, bf = e >> 1, e & 1
-                    if q < 3:
-                        if e == 0:
-                            w.ring_wait(rs, q + 1, (si, u, q + 1))
-                        if j == 3:
-                            w.ring_load(rs, q + 1, bf, ta + (q + 1,))
-                    elif kind != 2:
-                        if e == 0:
-                            w.ring_wait(rs ^ 1, 0, wrap(si, u + 1) + (0,))
-                        if j == 3:
-                            w.ring_load(rs ^ 1, 0, bf, tb + (0,))
-                    if e == 7:
-                        if q in (0, 1):
-                            w.dma_pair()
-                        elif q == 3:
-                            w.dma_consts()
+            w.su_interval(g, rs, kind, (si, u), wrap(si, u + 1), ta, tb)
             g += 1
         par = (par + nsu) & 1
         for j in range(6):               # b_interval
