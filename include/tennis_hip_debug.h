@@ -62,6 +62,21 @@ int tn_dbg_linear(tn_ctx *ctx, const float *x, const float *w, const float *bias
  * device fp32, scratch a device buffer of scratch_bytes >= 32 K doubles.  Synchronous. */
 int tn_dbg_channel_mean(tn_ctx *ctx, const void *x_f16, int ld, int K, const float *scale, const float *shift, int64_t rows,
                         void *scratch, size_t scratch_bytes, float *out, int clamp);
+/* The first kernels of a forward on their own: the pooled stem map (conv 7x7/2 + BatchNorm + ReLU + MaxPool 3x3/2) of B frames x
+ * (device, in `layout`) into y (device fp16, (B, Hp, Wp) pixels of 64 channels at row stride ldy).  conv0's weights (64,3,7,7) and
+ * batchnorm0's parameters are host fp32 and folded as tn_densenet121_create folds them; centre_host: the 64 channel means m_c the
+ * stored map is centred by, or NULL; exact: hi + lo weights (TN_ENC_EXACT_WEIGHTS); fused: the fused kernel, otherwise the stem
+ * kernel into a map of the hook's own followed by the max pool kernel (TN_NO_FUSE).  Synchronous. */
+int tn_dbg_stem(tn_ctx *ctx, const float *w0_host, const float *gamma_host, const float *beta_host, const float *mean_host,
+                const float *var_host, const float *centre_host, int exact, int fused, int layout, int B, int H, int W,
+                const void *x, void *y_f16, int ldy);
+/* MaxPool2D(3, 2, pad 1) of a device fp16 NHWC map (B,H,W,C) into y (B, Ho, Wo) at row stride ldy >= C.  Synchronous. */
+int tn_dbg_maxpool(tn_ctx *ctx, const void *x_f16, int B, int H, int W, int C, void *y_f16, int ldy, int Ho, int Wo);
+/* The last kernel: BatchNorm + ReLU + AvgPool2D(7) + NCHW flatten of a device NHWC map (B,H,W,C) into feat (B, C PH PW) device fp32,
+ * read from the fp16 map x_f16 or - x32 non-NULL - from the fp32 map x32 (x_f16 is then ignored); scale / shift device fp32.
+ * Synchronous. */
+int tn_dbg_head(tn_ctx *ctx, const void *x_f16, const float *x32, int B, int H, int W, int C, const float *scale, const float *shift,
+                float *feat, int PH, int PW);
 /* The strip-streaming fused dense layer (csrc/dense_strip.hip; 56x56 / 28x28 blocks, K <= 320): fp32 (128,K) 1x1 weights
  * with the folded scale / shift (128 each) of the BatchNorm behind them, and (32,128,3,3) 3x3 weights -> the MFMA
  * A-fragment images the kernel keeps resident in LDS ((K+16)*128 and 36864 halves; either output may be NULL), and one

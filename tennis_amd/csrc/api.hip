@@ -187,6 +187,64 @@ std::vector<f16> pack_stem(const float *w, bool zero_first) {
   return p;
 }
 
+}  // namespace
+
+// The stem's constants from conv0's weights (64,3,7,7) and batchnorm0's folded scale / shift: what tn_densenet121_create uploads and
+// what the tn_dbg_stem hook runs the kernels on.  centre: m_c of the centred output (StemArgs::floor; nullptr: not centred, no floor).
+StemFold fold_stem(const float *w0, const float *bn_scale, const float *bn_shift, const float *centre, bool exact) {
+  StemFold f;
+  std::vector<float> s(bn_scale, bn_scale + 64), t(bn_shift, bn_shift + 64);
+  // the input normalisation's 1 / (255 std_c) goes into the weights before they are rounded (common.h "the stem's operand")
+  std::vector<float> w0s((size_t)64 * 3 * 49), tu(64);
+  for (int n = 0; n < 64; ++n) {
+    double bias = 0.0;
+    for (int c = 0; c < 3; ++c)
+      for (int k = 0; k < 49; ++k) {
+        const size_t i = ((size_t)n * 3 + c) * 49 + k;
+        w0s[i] = w0[i] * stem_wfactor(c);
+        bias -= (double)(float)(f16)w0s[i] * stem_pad(c);
+      }
+    s[n] = (float)((double)s[n] / kStemWScale);
+    tu[n] = (float)((double)t[n] + (double)s[n] * bias);
+  }
+  f.wp = pack_stem(w0s.data(), false);
+  f.wp_zf = pack_stem(w0s.data(), true);
+  if (exact) {     // w = hi + lo: the second fragment image (the constant of the integer staging then uses hi + lo as well)
+    std::vector<float> lo(w0s.size());
+    for (int n = 0; n < 64; ++n) {
+      double bias = 0.0;
+      for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 49; ++k) {
+          const size_t i = ((size_t)n * 3 + c) * 49 + k;
+          const float hi = (float)(f16)w0s[i];
+          lo[i] = w0s[i] - hi;
+          bias -= ((double)hi + (double)(float)(f16)lo[i]) * stem_pad(c);
+        }
+      tu[n] = (float)((double)t[n] + (double)s[n] * bias);
+    }
+    f.wp_zf_lo = pack_stem(lo.data(), true);
+  }
+  if (centre) {
+    f.floor.resize(64);
+    for (int n = 0; n < 64; ++n) {
+      t[n] = (float)((double)t[n] - (double)centre[n]);
+      tu[n] = (float)((double)tu[n] - (double)centre[n]);
+      f.floor[n] = -centre[n];
+    }
+  }
+  f.scale = s; f.shift = t; f.shift_u8 = tu;
+  return f;
+}
+
+// the same from batchnorm0's raw parameters (the tn_dbg_stem hook): folded as fold_bn folds them
+StemFold fold_stem_bn(const float *w0, const float *gamma, const float *beta, const float *mean, const float *var, const float *centre, bool exact) {
+  float s[64], t[64];
+  bn_scale_shift(gamma, beta, mean, var, 64, kBnEps, s, t);
+  return fold_stem(w0, s, t, centre, exact);
+}
+
+namespace {
+
 struct EventTimer {  // brackets launches with HIP events when enabled
   bool on = false;
   hipStream_t s = nullptr;
@@ -534,49 +592,17 @@ extern "C" int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int
   auto centre_shift = [&](std::vector<float> &sc, std::vector<float> &sh) {       // a consumer of block 1's channels 0 .. 63
     for (int c = 0; c < 64; ++c) sh[c] = (float)((double)sh[c] + (double)sc[c] * (double)e->stem_centre[c]);
   };
-  {  // stem: conv0 + batchnorm0
+  {  // stem: conv0 + batchnorm0 (fold_stem, above)
     const float *w0 = pm.get(pre + "conv0_weight", 64 * 3 * 7 * 7);
     if (!w0 || !fold_bn(pm, pre + "batchnorm0", 64, s, t)) return fail(TN_ERR_MISSING);
-    // the input normalisation's 1 / (255 std_c) goes into the weights before they are rounded (common.h "the stem's operand")
-    std::vector<float> w0s((size_t)64 * 3 * 49), tu(64);
-    for (int n = 0; n < 64; ++n) {
-      double bias = 0.0;
-      for (int c = 0; c < 3; ++c)
-        for (int k = 0; k < 49; ++k) {
-          const size_t i = ((size_t)n * 3 + c) * 49 + k;
-          w0s[i] = w0[i] * stem_wfactor(c);
-          bias -= (double)(float)(f16)w0s[i] * stem_pad(c);
-        }
-      s[n] = (float)((double)s[n] / kStemWScale);
-      tu[n] = (float)((double)t[n] + (double)s[n] * bias);
-    }
-    e->stem_wp = e->pool.upload(pack_stem(w0s.data(), false));
-    e->stem_wp_zf = e->pool.upload(pack_stem(w0s.data(), true));
-    if (e->exact) {     // w = hi + lo: the second fragment image (the constant of the integer staging then uses hi + lo as well)
-      std::vector<float> lo(w0s.size());
-      for (int n = 0; n < 64; ++n) {
-        double bias = 0.0;
-        for (int c = 0; c < 3; ++c)
-          for (int k = 0; k < 49; ++k) {
-            const size_t i = ((size_t)n * 3 + c) * 49 + k;
-            const float hi = (float)(f16)w0s[i];
-            lo[i] = w0s[i] - hi;
-            bias -= ((double)hi + (double)(float)(f16)lo[i]) * stem_pad(c);
-          }
-        tu[n] = (float)((double)t[n] + (double)s[n] * bias);
-      }
-      e->stem_wp_zf_lo = e->pool.upload(pack_stem(lo.data(), true));
-    }
-    std::vector<float> fl(64);
-    for (int n = 0; n < 64; ++n) {
-      t[n] = (float)((double)t[n] - (double)e->stem_centre[n]);
-      tu[n] = (float)((double)tu[n] - (double)e->stem_centre[n]);
-      fl[n] = -e->stem_centre[n];
-    }
-    e->stem_scale = e->pool.upload(s);
-    e->stem_shift = e->pool.upload(t);
-    e->stem_shift_u8 = e->pool.upload(tu);
-    e->stem_floor = e->pool.upload(fl);
+    const StemFold f = fold_stem(w0, s.data(), t.data(), e->stem_centre.data(), e->exact);
+    e->stem_wp = e->pool.upload(f.wp);
+    e->stem_wp_zf = e->pool.upload(f.wp_zf);
+    if (e->exact) e->stem_wp_zf_lo = e->pool.upload(f.wp_zf_lo);
+    e->stem_scale = e->pool.upload(f.scale);
+    e->stem_shift = e->pool.upload(f.shift);
+    e->stem_shift_u8 = e->pool.upload(f.shift_u8);
+    e->stem_floor = e->pool.upload(f.floor);
   }
   e->zeros128 = e->pool.upload(std::vector<float>(128, 0.0f));
   e->ones128 = e->pool.upload(std::vector<float>(128, 1.0f));

@@ -307,6 +307,14 @@ struct StemArgs {
   // floor -m_c here (max pool and ReLU commute with the subtraction: max(v - m, -m) = relu(v) - m); nullptr: floor 0.
   const float *floor = nullptr;      // [64]
 };
+// the host side of StemArgs (api.hip::fold_stem): fragment images and BatchNorm constants as the kernels read them
+struct StemFold {
+  std::vector<f16> wp, wp_zf, wp_zf_lo;           // wp_zf_lo: exact-weights mode only
+  std::vector<float> scale, shift, shift_u8;      // [64] each
+  std::vector<float> floor;                       // [64], empty without a centre
+};
+StemFold fold_stem(const float *w0, const float *bn_scale, const float *bn_shift, const float *centre, bool exact);
+StemFold fold_stem_bn(const float *w0, const float *gamma, const float *beta, const float *mean, const float *var, const float *centre, bool exact);
 int launch_stem(const StemArgs &a, hipStream_t s);
 // fused stem + maxpool: writes the pooled map (Hp x Wp x 64) at row stride ldy
 int launch_stem_pool(const StemArgs &a, f16 *out, int ldy, int Hp, int Wp, hipStream_t s);

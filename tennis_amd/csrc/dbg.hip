@@ -131,6 +131,75 @@ extern "C" int tn_dbg_channel_mean(tn_ctx *ctx, const void *x_f16, int ld, int K
   return TN_OK;
 }
 
+// ---- the first and the last kernels of a forward: stem (+ maxpool) and head ----
+// The pooled stem map of B frames x (device, in `layout`) into y (device fp16, row stride ldy >= 64): conv0's raw weights (64,3,7,7)
+// and batchnorm0's parameters (host fp32) folded by the function tn_densenet121_create folds them with (api.hip::fold_stem), then
+// the launchers of the forward - fused: launch_stem_pool; otherwise launch_stem into a map of its own + launch_maxpool3x3s2
+// (TN_NO_FUSE).  centre_host: m_c of the centred output or NULL (no floor).  Synchronous.
+extern "C" int tn_dbg_stem(tn_ctx *ctx, const float *w0_host, const float *gamma_host, const float *beta_host, const float *mean_host,
+                           const float *var_host, const float *centre_host, int exact, int fused, int layout, int B, int H, int W,
+                           const void *x, void *y_f16, int ldy) {
+  TN_REQUIRE(ctx && w0_host && gamma_host && beta_host && mean_host && var_host && x && y_f16, "tn_dbg_stem: null argument");
+  TN_REQUIRE(layout >= 0 && layout <= 2, "tn_dbg_stem: unknown input layout");
+  TN_REQUIRE(B > 0 && H >= 16 && W >= 16 && H <= 1024 && W <= 1024, "tn_dbg_stem: bad shape (frames of 16 .. 1024 pixels a side)");
+  TN_REQUIRE(ldy >= 64 && ldy % 8 == 0, "tn_dbg_stem: the output stride must be a multiple of 8, at least 64");
+  TN_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)y_f16 & 15) == 0, "tn_dbg_stem: x and y must be 16-byte aligned");
+  TN_REQUIRE(fused || !exact, "tn_dbg_stem: the exact-weights mode has the fused kernel only");
+  TN_ON_DEVICE(ctx->device);
+  const StemFold f = fold_stem_bn(w0_host, gamma_host, beta_host, mean_host, var_host, centre_host, exact != 0);
+  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1, Hp = (Ho + 2 - 3) / 2 + 1, Wp = (Wo + 2 - 3) / 2 + 1;
+  f16 *wp = up(f.wp), *wp_zf = up(f.wp_zf), *wp_lo = exact ? up(f.wp_zf_lo) : nullptr, *map = nullptr;
+  float *sc = up(f.scale), *sh = up(f.shift), *shu = up(f.shift_u8), *fl = centre_host ? up(f.floor) : nullptr;
+  bool ok = wp && wp_zf && sc && sh && shu && (!exact || wp_lo) && (!centre_host || fl);
+  if (ok && !fused) ok = hipMalloc((void **)&map, (size_t)B * Ho * Wo * 64 * sizeof(f16)) == hipSuccess;
+  int rc = TN_OK;
+  if (ok) {
+    StemArgs a{x, layout, B, H, W, wp, wp_zf, sc, sh, map, Ho, Wo};
+    a.shift_u8 = shu;
+    a.wp_zf_lo = wp_lo;
+    a.floor = fl;
+    if (fused) rc = launch_stem_pool(a, (f16 *)y_f16, ldy, Hp, Wp, ctx->stream);
+    else {
+      rc = launch_stem(a, ctx->stream);
+      if (!rc) rc = launch_maxpool3x3s2(map, B, Ho, Wo, 64, (f16 *)y_f16, ldy, Hp, Wp, ctx->stream);
+    }
+  }
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(wp); (void)hipFree(wp_zf); (void)hipFree(wp_lo); (void)hipFree(map);
+  (void)hipFree(sc); (void)hipFree(sh); (void)hipFree(shu); (void)hipFree(fl);
+  TN_REQUIRE(ok, "tn_dbg_stem: device allocation failed");
+  if (rc) return rc;
+  TN_HIP_CHECK(e);
+  return TN_OK;
+}
+
+// MaxPool2D(3, 2, pad 1) of a device fp16 NHWC map (B,H,W,C) into y (B,Ho,Wo; row stride ldy): launch_maxpool3x3s2.  Synchronous.
+extern "C" int tn_dbg_maxpool(tn_ctx *ctx, const void *x_f16, int B, int H, int W, int C, void *y_f16, int ldy, int Ho, int Wo) {
+  TN_REQUIRE(ctx && x_f16 && y_f16, "tn_dbg_maxpool: null argument");
+  TN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && ldy >= C, "tn_dbg_maxpool: bad shape");
+  TN_REQUIRE(Ho == (H - 1) / 2 + 1 && Wo == (W - 1) / 2 + 1, "tn_dbg_maxpool: the output is ((H - 1) / 2 + 1) x ((W - 1) / 2 + 1)");
+  TN_REQUIRE(((uintptr_t)x_f16 & 15) == 0 && ((uintptr_t)y_f16 & 15) == 0, "tn_dbg_maxpool: x and y must be 16-byte aligned");
+  TN_ON_DEVICE(ctx->device);
+  const int rc = launch_maxpool3x3s2((const f16 *)x_f16, B, H, W, C, (f16 *)y_f16, ldy, Ho, Wo, ctx->stream);
+  if (rc) return rc;
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+
+// BatchNorm + ReLU + AvgPool2D(7) + NCHW flatten of a device NHWC map (B,H,W,C) into feat (B, C PH PW) device fp32: launch_head on the
+// fp16 map x_f16, or - x32 non-NULL - on the fp32 side buffer (x_f16 is then not read).  scale / shift device fp32.  Synchronous.
+extern "C" int tn_dbg_head(tn_ctx *ctx, const void *x_f16, const float *x32, int B, int H, int W, int C, const float *scale, const float *shift,
+                           float *feat, int PH, int PW) {
+  TN_REQUIRE(ctx && (x_f16 || x32) && scale && shift && feat, "tn_dbg_head: null argument");
+  TN_REQUIRE(B > 0 && C > 0 && PH > 0 && PW > 0 && 7 * PH <= H && 7 * PW <= W, "tn_dbg_head: bad shape (PH x PW windows of 7 x 7 inside H x W)");
+  TN_REQUIRE((((uintptr_t)x_f16 | (uintptr_t)x32) & 15) == 0, "tn_dbg_head: the map must be 16-byte aligned");
+  TN_ON_DEVICE(ctx->device);
+  const int rc = launch_head((const f16 *)x_f16, B, H, W, C, scale, shift, feat, PH, PW, ctx->stream, x32);
+  if (rc) return rc;
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+
 // fp32 linear: y = x W^T + b
 extern "C" int tn_dbg_linear(tn_ctx *ctx, const float *x, const float *w, const float *bias, float *y, int M, int N,
                              int K) {

@@ -287,6 +287,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((VEC && LAY
       const bool in = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
       const float pd[3] = {LAY == TN_LAYOUT_NHWC_U8 ? (float)stem_pad(0) : 0.f, LAY == TN_LAYOUT_NHWC_U8 ? (float)stem_pad(1) : 0.f,
                            LAY == TN_LAYOUT_NHWC_U8 ? (float)stem_pad(2) : 0.f};
+      // fp16 input: v * 255 std_c is rounded to fp32 and then to fp16, as the vector path and stem.hip round it.  Left to itself the
+      // compiler fuses the product and the conversion of THIS path into v_fma_mixlo_f16, which rounds once: one operand in 4000 came
+      // out an fp16 ulp away from what a frame of a width divisible by 8 stages (tests/test_gpu_stem_head.py); the empty asm keeps
+      // the fp32 product a value of its own
+      if constexpr (LAY == TN_LAYOUT_NHWC_F16) asm("" : "+v"(raw[i][0]), "+v"(raw[i][1]), "+v"(raw[i][2]));
       f16x4 v;
       v[0] = (f16)(in ? raw[i][0] : pd[0]);
       v[1] = (f16)(in ? raw[i][1] : pd[1]);
