@@ -323,6 +323,9 @@ struct tn_encoder {
   bool strip = true;          // 56x56 / 28x28 layers with K <= 320 run on the strip-streaming kernel (TN_NO_STRIP disables)
   int strip_min_batch = 64;   // ... from this many frames per launch on (one workgroup per frame: small batches leave CUs idle)
   DenseLayerDev *chain_dev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool strip_chain = true;    // the leading strip layers of a 56x56 / 28x28 block run in one launch (TN_NO_STRIP_CHAIN: one launch per layer)
+  DenseStripLayerDev *strip_chain_dev[4] = {nullptr, nullptr, nullptr, nullptr};   // their argument table
+  int strip_chain_nl[4] = {0, 0, 0, 0};                                             // ... and how many layers it holds (0: no chained launch for the block)
   float *calib_dev = nullptr;   // tn_densenet121_input_means: where the layer-wise pass leaves the mean of every convolution's input
   double *calib_scratch = nullptr;
   float *ones128 = nullptr;
@@ -532,6 +535,7 @@ extern "C" int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int
   e->exact = (flags & TN_ENC_EXACT_WEIGHTS) != 0 && !e->fp32;    // (TN_ENC_FP32 | TN_ENC_EXACT_WEIGHTS: the fp32 mode)
   e->strip = getenv("TN_NO_STRIP") == nullptr && !e->exact && e->fuse;
   if (getenv("TN_STRIP_MIN_BATCH")) e->strip_min_batch = atoi(getenv("TN_STRIP_MIN_BATCH"));
+  e->strip_chain = getenv("TN_NO_STRIP_CHAIN") == nullptr;
   for (int i = 0; i < 4; ++i) {
     if (hipStreamCreateWithFlags(&e->side[i], hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&e->ev_done[0][i], hipEventDisableTiming) != hipSuccess ||
@@ -722,6 +726,22 @@ extern "C" int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int
       for (auto &L : e->layers[b]) cd.push_back(DenseLayerDev{L.s1, L.t1, L.w1, L.s2, L.t2, L.w3p});
       e->chain_dev[b] = e->pool.upload(cd);
     }
+    if (e->strip_chain) {
+      // the block's leading strip layers as one launch: all of them packed for the strip kernel, and the sequence the chained
+      // kernel of the map was built for
+      const int nl = dense_strip_chain_layers(e->Hb[b], e->Wb[b], e->Cin[b]);
+      bool ok = nl > 0 && nl <= (int)e->layers[b].size();
+      std::vector<DenseStripLayerDev> sd;
+      for (int l = 0; ok && l < nl; ++l) {
+        const auto &L = e->layers[b][l];
+        ok = L.w1s && L.w3s && L.cin == e->Cin[b] + 32 * l;
+        sd.push_back(DenseStripLayerDev{L.s1, L.t1, L.w1s, L.w3s});
+      }
+      if (ok) {
+        e->strip_chain_dev[b] = e->pool.upload(sd);
+        e->strip_chain_nl[b] = nl;
+      }
+    }
     if (b < 3) {
       auto &T = e->trans[b];
       T.cin = e->Cb[b]; T.cout = e->Cb[b] / 2;
@@ -827,10 +847,11 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
     const int Hh = e->Hb[b], Ww = e->Wb[b];
     const int M = B * Hh * Ww;
     const bool fused = !cal && e->fuse && dense_layer_supported(Hh, Ww);
-    // a whole block as one launch: its flops and bytes under one family name
-    auto begin_block = [&](const char *family) {
+    // a whole block (or its first nl layers) as one launch: its flops and bytes under one family name
+    auto begin_block = [&](const char *family, size_t nl = ~(size_t)0) {
       double fl = 0, by = 0;
-      for (auto &L : e->layers[b]) {
+      for (size_t l = 0; l < e->layers[b].size() && l < nl; ++l) {
+        const auto &L = e->layers[b][l];
         fl += 2.0 * M * (128.0 * L.cin + 32.0 * 1152);
         by += (double)M * (L.cin + 32) * 2 + 128.0 * L.cin * 2 + 32.0 * 1152 * 2;
       }
@@ -867,8 +888,23 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
       rc = launch_dense_layer(af, s);
       tm.end();
       if (rc) return rc;
-    } else
-    for (auto &L : e->layers[b]) {
+    } else {
+    // where the per-layer strip route below would be taken for the block's leading layers: those layers in one launch (one
+    // workgroup per frame walks them; no drain of the chip, no dispatch and no cold start per layer).  The rest of the block
+    // follows layer by layer as before.
+    size_t l0 = 0;
+    if (e->fuse && e->strip_chain_nl[b] && B >= e->strip_min_batch && e->dl_variant == 0 && !cal) {
+      const int nl = e->strip_chain_nl[b];
+      DenseStripChainArgs ac{bbuf[b], e->Cb[b], e->Cin[b], nl, e->strip_chain_dev[b], B, Hh, Ww};
+      const std::string fam = "dense_block_strip_" + std::to_string(Hh) + "x" + std::to_string(Ww);
+      begin_block(fam.c_str(), (size_t)nl);
+      rc = launch_dense_strip_chain(ac, s);
+      tm.end();
+      if (rc) return rc;
+      l0 = (size_t)nl;
+    }
+    for (size_t li = l0; li < e->layers[b].size(); ++li) {
+      auto &L = e->layers[b][li];
       // (one workgroup per 56 x 56 / 28 x 28 frame, 5 / 3 per 128 x 128 / 64 x 64 frame: enough of them to fill the chip?)
       if (e->fuse && L.w1s && B * (Hh == 128 ? 5 : Hh == 64 ? 3 : 1) >= e->strip_min_batch && e->dl_variant == 0 && !cal) {
         DenseStripArgs as{bbuf[b], e->Cb[b], L.cin, L.s1, L.t1, L.w1s, L.w3s, B, Hh, Ww};
@@ -909,6 +945,7 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
       rc = launch_conv3x3(a3, s);
       tm.end();
       if (rc) return rc;
+    }
     }
     if (b < 3) {
       auto &T = e->trans[b];

@@ -213,6 +213,21 @@ struct DenseStripArgs {
 };
 bool dense_strip_supported(int H, int W, int K);
 int launch_dense_strip(const DenseStripArgs &a, hipStream_t s);
+// The strip layers of a 56 x 56 / 28 x 28 block in one launch (one workgroup = one frame walks layers K0, K0 + 32, ...;
+// dense_strip_impl.h::dense_strip_kernel_chain): same arithmetic in the same order as nl launches of launch_dense_strip.
+struct DenseStripLayerDev {   // one layer's parameters as the chained kernel reads them from device memory
+  const float *s1, *t1;
+  const f16 *w1s, *w3s;
+};
+struct DenseStripChainArgs {
+  f16 *buf;                          // concat buffer [B][H][W][ldc]: reads channels [0,K0), appends [K0, K0 + 32 nl)
+  int ldc, K0, nl;
+  const DenseStripLayerDev *layers;  // device array [nl]
+  int B, H, W;
+};
+bool dense_strip_chain_supported(int H, int W, int K0, int nl);
+int dense_strip_chain_layers(int H, int W, int K0);    // how many layers from K0 on the chained kernel of that map runs (0: none)
+int launch_dense_strip_chain(const DenseStripChainArgs &a, hipStream_t s);
 std::vector<f16> pack_w1_strip(const float *w /*[128][K], BN2 scale folded in*/, int K, const float *shift /*[128] BN2 shift*/);
 std::vector<f16> pack_w3_strip(const float *w /*(32,128,3,3)*/);
 

@@ -9,6 +9,8 @@ int launch_dense_strip_w56(const DenseStripArgs &a, hipStream_t s);
 int launch_dense_strip_w28(const DenseStripArgs &a, hipStream_t s);
 int launch_dense_strip_w128(const DenseStripArgs &a, hipStream_t s);
 int launch_dense_strip_w64(const DenseStripArgs &a, hipStream_t s);
+int launch_dense_strip_chain_w56(const DenseStripChainArgs &a, hipStream_t s);
+int launch_dense_strip_chain_w28(const DenseStripChainArgs &a, hipStream_t s);
 
 bool dense_strip_supported(int H, int W, int K) {
   // (128 x 128: K <= 288 - the K = 320 instantiation of that width spills one register; a 512 x 512 input needs K <= 224 there)
@@ -23,6 +25,23 @@ int launch_dense_strip(const DenseStripArgs &a, hipStream_t s) {
   if (a.W == 128) return launch_dense_strip_w128(a, s);
   if (a.W == 64) return launch_dense_strip_w64(a, s);
   return launch_dense_strip_w28(a, s);
+}
+
+// The chained kernels are built for the layer sequences of DenseNet-121 at 224 x 224 (dense_strip_impl.h::DSChain): the whole
+// 56 x 56 block's first five layers (K = 64 ... 192) and the 28 x 28 block's first six (K = 128 ... 288); K = 224 / K = 320 follow
+// as per-layer launches
+int dense_strip_chain_layers(int H, int W, int K0) {
+  if (H == 56 && W == 56 && K0 == 64) return 5;
+  if (H == 28 && W == 28 && K0 == 128) return 6;
+  return 0;
+}
+bool dense_strip_chain_supported(int H, int W, int K0, int nl) { return nl > 0 && dense_strip_chain_layers(H, W, K0) == nl; }
+
+int launch_dense_strip_chain(const DenseStripChainArgs &a, hipStream_t s) {
+  TN_REQUIRE(dense_strip_chain_supported(a.H, a.W, a.K0, a.nl), "dense_strip_chain: unsupported geometry");
+  TN_REQUIRE(a.buf && a.layers && a.B > 0, "dense_strip_chain: null operand");
+  TN_REQUIRE(a.ldc % 64 == 0 && a.K0 + 32 * a.nl <= a.ldc, "dense_strip_chain: bad channel geometry");
+  return a.W == 56 ? launch_dense_strip_chain_w56(a, s) : launch_dense_strip_chain_w28(a, s);
 }
 
 // ---- host-side packing (api.hip, dbg.hip) ----
