@@ -335,6 +335,42 @@ int tn_gnmt_trainer_read_param(tn_gnmt_trainer *t, const char *name, int gradien
                                int64_t *numel);
 int tn_gnmt_trainer_destroy(tn_gnmt_trainer *t);
 
+/* ---- end-to-end frame-mode captioner training step --------------- */
+/* train_gnmt.py without --feats_model (:148-203): the source embedding is TimeDistributed(FrameModel(DenseNet-121 .features)
+ * .backbone) inside the NMTModel, so one step runs the backbone in training mode over all batch x steps frames of the padded
+ * clips (utils/layers.py:38-46), the captioner step above on its features (rows b*steps + t), and - unless the backbone is frozen
+ * (--freeze_backbone, :164-166) - carries d loss / d src back through the backbone.  fp32.
+ * create (:149-186, 223-229): the arguments of tn_gnmt_trainer_create_ex without input_size, which is the backbone's feature
+ * width (parameters whose first encoder layer has another width are refused), plus the backbone's prefix ("densenet0_"), the
+ * side of the square frames (divisible by 32), max_frames >= the largest batch * steps of a call, and freeze_backbone.  When
+ * max_frames do not fit the device, create returns TN_ERR_NOMEM and its message gives the frames that would.
+ * forward_backward (:328-334): frames (batch, steps, side, side, 3) fp32 normalised NHWC, DEVICE; the other arguments as
+ * tn_gnmt_trainer_forward_backward.  Any batch <= max_batch, steps <= max_src_len with batch * steps <= max_frames.  The frames
+ * are read once into the handle's staging buffer, the slots t >= src_valid_len[b] as zeros - what Pad() puts there
+ * (utils/captioning.py:33) - whatever the caller left in them (they are not read); the padded slots go through the backbone with
+ * the others and count in its batch statistics, as in the reference.  The caller's buffer is not written.
+ * Frozen: no backbone backward and no backbone update; its BatchNorms still normalise with batch statistics and still update
+ * their running statistics (as tn_cnnrnn_trainer_*).
+ * buffers: the flat parameter / gradient arrays of the backbone (as tn_finetune_buffers) and of the captioner (as
+ * tn_gnmt_trainer_buffers), e.g. to all-reduce them over ranks before adam_step; any output pointer may be NULL.
+ * adam_step (:310,337): MXNet Adam over both parts, one update count; the running statistics are not parameters.
+ * read_param: the names of both parts, the backbone's running statistics and its "<bn>_batch_mean" / "<bn>_batch_var". */
+typedef struct tn_gnmt_frames_trainer tn_gnmt_frames_trainer;
+int tn_gnmt_frames_trainer_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *backbone_prefix, const char *prefix,
+                                  tn_rnn_kind cell_kind, int hidden, int embed, int vocab, int num_layers, int num_bi_layers, int flags,
+                                  int side, int max_batch, int max_src_len, int max_tgt_len, int max_frames, int freeze_backbone,
+                                  tn_gnmt_frames_trainer **out);
+int tn_gnmt_frames_trainer_forward_backward(tn_gnmt_frames_trainer *t, const float *frames, const int32_t *src_valid_len,
+                                            const int32_t *tgt, int ld, const int32_t *tgt_valid_len, int batch, int steps,
+                                            int tgt_len, float *loss, float *logits_out);
+int tn_gnmt_frames_trainer_buffers(tn_gnmt_frames_trainer *t, float **backbone_params, float **backbone_grads,
+                                   int64_t *backbone_numel, float **params_dev, float **grads_dev, int64_t *numel);
+int tn_gnmt_frames_trainer_set_dropout(tn_gnmt_frames_trainer *t, float p, uint64_t seed);
+int tn_gnmt_frames_trainer_adam_step(tn_gnmt_frames_trainer *t, float lr, float beta1, float beta2, float epsilon);
+int tn_gnmt_frames_trainer_read_param(tn_gnmt_frames_trainer *t, const char *name, int gradient, float *out_host,
+                                      int64_t capacity, int64_t *numel);
+int tn_gnmt_frames_trainer_destroy(tn_gnmt_frames_trainer *t);
+
 /* ---- device PRF1 confusion histogram -------------------------------------- */
 /* Replaces the argmax + per-sample python loop of PRF1.update (reference
  * metrics/vision.py:41-49).  logits (rows,classes) fp32, labels (rows,) int32;

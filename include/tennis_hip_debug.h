@@ -129,6 +129,12 @@ int tn_dbg_linear_bnrelu(tn_ctx *ctx, const float *X, int ldx, const float *asc,
 int tn_dbg_gemm_nn(tn_ctx *ctx, const float *A, int lda, const float *B, int ldb, float *Cm, int ldc, int M, int N, int K);
 int tn_dbg_bn_train(tn_ctx *ctx, const float *x, int ld, int64_t M, int C, const float *gamma, const float *beta, float *mean, float *var,
                     float *y, const float *dy, float *dgamma, float *dbeta, float *dx, int ldd, int accumulate);
+/* tn_gnmt_trainer_forward_backward that also leaves d loss / d src in dsrc (batch * steps, input_size; row stride ldd, DEVICE,
+ * assigned): the gradient the frame-mode step (tn_gnmt_frames_trainer_*) hands to the backbone.  Rows at or past src_valid_len[b]
+ * come out 0. */
+int tn_dbg_gnmt_trainer_src_grad(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len, const int32_t *tgt, int ld,
+                                 const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out,
+                                 float *dsrc, int ldd);
 
 #ifdef __cplusplus
 }

@@ -96,6 +96,17 @@ _SIGS = {
     "tn_cnnrnn_trainer_sgd_step": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float]),
     "tn_cnnrnn_trainer_read_param": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
     "tn_cnnrnn_trainer_destroy": (C.c_int, [_P]),
+    "tn_gnmt_frames_trainer_create": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.POINTER(_P)]),
+    "tn_gnmt_frames_trainer_forward_backward": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tn_gnmt_frames_trainer_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P),
+                                                 C.POINTER(C.c_int64)]),
+    "tn_gnmt_frames_trainer_set_dropout": (C.c_int, [_P, C.c_float, C.c_uint64]),
+    "tn_gnmt_frames_trainer_adam_step": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "tn_gnmt_frames_trainer_read_param": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
+    "tn_gnmt_frames_trainer_destroy": (C.c_int, [_P]),
+    "tn_dbg_gnmt_trainer_src_grad": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int]),
     "tn_gnmt_trainer_create": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tn_gnmt_trainer_create_ex": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

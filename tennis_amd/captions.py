@@ -4,7 +4,9 @@ utils/captioning.py::get_dataloaders/write_sentences (:28-95) and
 train_gnmt.py::evaluate (:264-302).  Two sources: ON DISK when ``root`` holds the reference's layout
 (``splits/<split_id>/<split>.txt``, ``annotations/points.txt`` + ``captions.txt``, per-frame ``.npy`` features under
 ``features/<feats_model>/`` as ``evaluate --save_feats`` writes them; parsed by ``TennisSet.load_data``), else SYNTHETIC
-(the TenniSet features and captions are not available).
+(the TenniSet features and captions are not available).  Either source yields FEATURES (``feats_model``, dataset.py:42-44,
+169-171) or, without ``feats_model``, the point's FRAMES (dataset.py:172-176: frame mode, the CNN inside the captioner) through
+``TennisSet``'s frame reading and ``transform``.
 
 One sample = one *point*: every `every`-th frame feature in [start, end), stacked (T,F), plus
 the caption ids ``[<bos>] + vocab[tokens][:max_cap_len] + [<eos>]`` as int32 (dataset.py:67-73);
@@ -27,25 +29,42 @@ WORDS = ("the near far player serves hits a forehand backhand return volley into
 
 
 class CaptionSet:
-    """``TennisSet(captions=True, feats_model=...)`` counterpart."""
+    """``TennisSet(captions=True, ...)`` counterpart.  The source is chosen by its arguments: ``feats_model`` -> (T, F) features;
+    ``frames=True`` -> the point's frames; neither, on disk -> ``ValueError`` (``TennisSet(captions=True, ...)`` passes ``frames="auto"``,
+    which is frames exactly where the reference reads frames: on disk without ``feats_model``, dataset.py:172-176).
+    Frame items are (T, 3, S, S) fp32 after a per-frame ``transform`` (default: ToTensor
+    + Normalize), or the decoded (T, H, W, 3) uint8 frames when the transform is ``device_batched`` (``tennis_amd.transforms.Compose``),
+    which ``bucketed_batches`` then runs once per batch on the GPU."""
 
     def __init__(self, split="train", every=1, max_cap_len=-1, vocab=None, inference=False, n_points=24,
-                 feature_dim=1024, mean_frames=40, seed=7, root=None, split_id="02", feats_model=None):
+                 feature_dim=1024, mean_frames=40, seed=7, root=None, split_id="02", feats_model=None, frames=False,
+                 transform=None, data_shape=224, decode="host"):
         self._captions, self._split, self._every, self._inference = True, split, every, inference
         self._points, self._samples = {}, []
-        self._feat_dir = None
+        self._feat_dir, self._frames, self._transform = None, None, None
         import os
-        if root is not None and os.path.exists(os.path.join(root, "splits", split_id, split + ".txt")):
-            # dataset.py:35-52: the points of this split from annotations/points.txt + captions.txt; frames as features
-            from .dataset import TennisSet
-            if feats_model is None:
-                raise ValueError("the caption source on disk reads pre-extracted features: pass feats_model (dataset.py:42-44)")
-            ts = TennisSet(root=root, split=split, split_id=split_id, every=1, balance=False, feats_model=feats_model)
+        from .dataset import TennisSet
+        on_disk = root is not None and os.path.exists(os.path.join(root, "splits", split_id, split + ".txt"))
+        if frames == "auto":          # TennisSet(captions=True): frames where the reference reads frames, features where it reads features
+            frames = on_disk and feats_model is None
+        if on_disk:
+            # dataset.py:35-52: the points of this split from annotations/points.txt + captions.txt; frames or their features
+            if feats_model is None and not frames:
+                raise ValueError("the caption source on disk reads pre-extracted features (feats_model, dataset.py:42-44) or the "
+                                 "points' frames (frames=True; TennisSet(captions=True, ...) without feats_model selects them)")
+            ts = TennisSet(root=root, split=split, split_id=split_id, every=1, balance=False, feats_model=feats_model,
+                           transform=transform, decode=decode)
             for pid, pt in ts._points.items():
                 self._points[pid] = [pt[0], int(pt[1]), int(pt[2]), 0, pt[-1]]
             self._samples = list(self._points.keys())
-            self._feat_dir, self._feat_path = ts.feat_dir, ts.get_feature_path
+            if feats_model is not None:
+                self._feat_dir, self._feat_path = ts.feat_dir, ts.get_feature_path
+            else:
+                self._frames, self._transform = ts, ts.transform
         else:
+            if frames:        # distinct synthetic frames per (video, frame): TennisSet's synthetic frame source
+                self._frames = TennisSet(transform=transform, data_shape=data_shape, frames_per_video=1, seed=seed, synthetic=True)
+                self._transform = self._frames.transform
             rng = np.random.default_rng(zlib.crc32(f"{split}:{seed}".encode()))
             for i in range(n_points):
                 start = int(rng.integers(0, 1000))
@@ -85,7 +104,8 @@ class CaptionSet:
     def __getitem__(self, idx):                                        # dataset.py:154-183
         point = self._points[self._samples[idx]]
         vid, start, end, cap = point[0], int(point[1]), int(point[2]), point[5]
-        imgs = np.stack([self._feature(vid, f) for c, f in enumerate(range(start, end)) if c % self._every == 0])
+        load = self._frames.load_frame if self._frames is not None else self._feature
+        imgs = np.stack([load(vid, f) for c, f in enumerate(range(start, end)) if c % self._every == 0])
         if self._inference:
             return imgs, cap, len(imgs), len(cap), idx
         return imgs, cap, len(imgs), len(cap)
@@ -94,12 +114,16 @@ class CaptionSet:
         return [(int((int(self._points[s][2]) - int(self._points[s][1]) + 1) / self._every), len(self._points[s][5]))
                 for s in self._samples]
 
+    def get_clip_lens(self):
+        """the exact number of frames item i stacks (``get_data_lens`` keeps the reference's rounding, which can fall one short)"""
+        return [len(range(int(self._points[s][1]), int(self._points[s][2]), self._every)) for s in self._samples]
+
 
 def pad_batchify(samples):
     """``btf.Tuple(Pad(), Pad(), Stack('float32'), Stack('float32')[, Stack()])`` (utils/captioning.py:33-37)."""
     tmax = max(s[0].shape[0] for s in samples)
     lmax = max(len(s[1]) for s in samples)
-    src = np.zeros((len(samples), tmax, samples[0][0].shape[1]), np.float32)
+    src = np.zeros((len(samples), tmax) + samples[0][0].shape[1:], samples[0][0].dtype)      # (T, F) features or (T, ...) frames
     tgt = np.zeros((len(samples), lmax), np.int32)
     for i, s in enumerate(samples):
         src[i, :s[0].shape[0]] = s[0]
@@ -136,8 +160,17 @@ def bucketed_batches(dataset, batch_size, num_buckets=5, shuffle=False, seed=0, 
     if world > 1:
         n = -(-len(batches) // world) * world
         batches = [batches[j % len(batches)] for j in range(n)][rank::world]
+    tf = getattr(dataset, "_transform", None)
     for ids in batches:
-        yield pad_batchify([dataset[i] for i in ids])
+        batch = pad_batchify([dataset[i] for i in ids])
+        if getattr(tf, "device_batched", False) and batch[0].dtype == np.uint8:
+            batch = (tf(batch[0]),) + batch[1:]      # frame source: one transform launch group per batch, (B, T, S, S, 3) uint8 on the GPU
+        yield batch
+
+
+def to_device(src):
+    """a batch's source as ``bucketed_batches`` yields it - a host array, or frames the transform already left on the GPU"""
+    return src.cuda() if isinstance(src, torch.Tensor) else torch.from_numpy(src).cuda()
 
 
 def write_sentences(sentences, file_path):                             # utils/captioning.py:89-95
@@ -153,7 +186,7 @@ def evaluate(data_loader, model, translator, data_train):
     translation_out, all_inst_ids = [], []
     avg_loss_denom, avg_loss = 0, 0.0
     for src_seq, tgt_seq, src_valid_length, tgt_valid_length, inst_ids in data_loader:
-        src = model.embed_source(torch.from_numpy(src_seq).cuda())     # frame mode: the clip's frames through the CNN
+        src = model.embed_source(to_device(src_seq))                   # frame mode: the clip's frames through the CNN
         tgt = torch.from_numpy(tgt_seq).cuda()
         svl = torch.from_numpy(src_valid_length).cuda()
         tvl = torch.from_numpy(tgt_valid_length).cuda()

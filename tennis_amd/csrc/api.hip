@@ -1519,9 +1519,9 @@ extern "C" int tn_cnnrnn_trainer_forward_backward(tn_cnnrnn_trainer *t, const fl
   TN_ON_DEVICE(t->ctx->device);
   int rc;
 #define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
-  TN_TRY(ft_forward_features(t->bb, x));
+  TN_TRY(ft_forward_features(t->bb, x, t->B * t->T));
   TN_TRY(head_step(t->head, ft_features(t->bb), labels, t->B, t->T, loss, logits, t->frozen ? nullptr : ft_feature_grad(t->bb), t->F));
-  if (!t->frozen) TN_TRY(ft_backward_features(t->bb));
+  if (!t->frozen) TN_TRY(ft_backward_features(t->bb, t->B * t->T));
   ft_update_running(t->bb);
 #undef TN_TRY
   TN_HIP_CHECK(hipGetLastError());
@@ -1563,6 +1563,135 @@ extern "C" int tn_cnnrnn_trainer_read_param(tn_cnnrnn_trainer *t, const char *na
 extern "C" int tn_cnnrnn_trainer_destroy(tn_cnnrnn_trainer *t) {
   if (!t) return TN_OK;
   tn_head_destroy(t->head);
+  tn_finetune_destroy(t->bb);
+  delete t;
+  return TN_OK;
+}
+
+// ---- end-to-end frame-mode captioner training step ------------------------------------
+// reference train_gnmt.py:148-203 without --feats_model: src_embed = TimeDistributed(FrameModel(DenseNet121.features).backbone)
+// inside the NMTModel, trained (or frozen, :164-166) by the same loss.backward() / trainer.step(1) (:334-337).  The fine-tuning
+// step's backbone (finetune.hip, no classifier) over the batch * steps frames of the padded clips, the captioner's step
+// (captioner.hip) on its features.
+struct tn_gnmt_frames_trainer {
+  tn_ctx *ctx;
+  tn_finetune *bb;
+  tn_gnmt_trainer *cap;
+  int side, F, maxB, maxT, maxN;
+  long step;                    // Adam's update count, one for both parts
+  bool frozen;
+  std::string bb_prefix, prefix;
+};
+
+extern "C" int tn_gnmt_frames_trainer_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *backbone_prefix,
+                                             const char *prefix, tn_rnn_kind cell_kind, int hidden, int embed, int vocab, int num_layers,
+                                             int num_bi_layers, int flags, int side, int max_batch, int max_src_len, int max_tgt_len,
+                                             int max_frames, int freeze_backbone, tn_gnmt_frames_trainer **out) {
+  TN_REQUIRE(ctx && params && backbone_prefix && prefix && out, "tn_gnmt_frames_trainer_create: null argument");
+  TN_REQUIRE(side > 0 && side % 32 == 0, "tn_gnmt_frames_trainer_create: frames must be square with a side divisible by 32");
+  TN_REQUIRE(max_batch > 0 && max_src_len > 0 && max_frames > 0 && max_frames <= 65535,
+             "tn_gnmt_frames_trainer_create: bad max_batch / max_src_len / max_frames");
+  TN_ON_DEVICE(ctx->device);
+  long fit = -1;
+  tn_finetune *bb = nullptr;
+  int rc = ft_create(ctx, params, n_params, backbone_prefix, nullptr, side, side, 0, max_frames, &bb, &fit);
+  if (rc == TN_ERR_NOMEM && fit >= 0) {
+    tn_set_error("tn_gnmt_frames_trainer_create: " + std::to_string(max_frames) + " frames (the longest padded batch, batch x steps) of " +
+                 std::to_string(side) + "x" + std::to_string(side) + " do not fit the device; about " + std::to_string(fit) + " would");
+    return rc;
+  }
+  if (rc) return rc;
+  const int F = ft_feature_dim(bb), G = cell_kind == TN_RNN_GRU ? 3 : 4;
+  // the captioner's first layer reads the backbone's features: refuse parameters made for another width
+  const std::string w0 = std::string(prefix) + (num_bi_layers > 0 ? "enc_rnn0_l_i2h_weight" : "enc_rnn0_i2h_weight");
+  for (int i = 0; i < n_params; ++i)
+    if (w0 == params[i].name && params[i].numel != (int64_t)G * hidden * F) {
+      tn_set_error("tn_gnmt_frames_trainer_create: " + w0 + " is not (gates * hidden, " + std::to_string(F) + "), the backbone's feature width");
+      tn_finetune_destroy(bb);
+      return TN_ERR_INVALID;
+    }
+  tn_gnmt_trainer *cap = nullptr;
+  rc = tn_gnmt_trainer_create_ex(ctx, params, n_params, prefix, cell_kind, F, hidden, embed, vocab, num_layers, num_bi_layers, flags,
+                                 max_batch, max_src_len, max_tgt_len, &cap);
+  if (!rc && !freeze_backbone) rc = ft_enable_adam(bb);
+  if (rc) { tn_gnmt_trainer_destroy(cap); tn_finetune_destroy(bb); return rc; }
+  tn_gnmt_frames_trainer *t = new tn_gnmt_frames_trainer();
+  t->ctx = ctx; t->bb = bb; t->cap = cap; t->side = side; t->F = F; t->maxB = max_batch; t->maxT = max_src_len; t->maxN = max_frames;
+  t->step = 0; t->frozen = freeze_backbone != 0; t->bb_prefix = backbone_prefix; t->prefix = prefix;
+  *out = t;
+  return TN_OK;
+}
+
+// frames into the handle's staging buffer, zeros in the padded slots -> backbone forward (training-mode BatchNorm over all batch * steps frames, the padded ones
+// included: TimeDistributed sends them through with the others) -> features, rows b * steps + t = the captioner's (batch, steps, F)
+// source as it stands -> captioner forward / backward, d loss / d src straight into the backbone's feature gradient -> backbone
+// backward; frozen: no source gradient, no backbone backward.  Either way the running statistics move (docs/numerics.md).
+extern "C" int tn_gnmt_frames_trainer_forward_backward(tn_gnmt_frames_trainer *t, const float *frames, const int32_t *src_valid_len,
+                                                       const int32_t *tgt, int ld, const int32_t *tgt_valid_len, int batch, int steps,
+                                                       int tgt_len, float *loss, float *logits_out) {
+  TN_REQUIRE(t && frames && src_valid_len && tgt && tgt_valid_len && loss, "tn_gnmt_frames_trainer_forward_backward: null argument");
+  TN_REQUIRE(batch > 0 && batch <= t->maxB, "tn_gnmt_frames_trainer_forward_backward: batch exceeds max_batch");
+  TN_REQUIRE(steps > 0 && steps <= t->maxT, "tn_gnmt_frames_trainer_forward_backward: steps exceed max_src_len");
+  TN_REQUIRE((long)batch * steps <= t->maxN, "tn_gnmt_frames_trainer_forward_backward: batch * steps exceeds max_frames");
+  TN_REQUIRE(tgt_len >= 2 && ld >= tgt_len, "tn_gnmt_frames_trainer_forward_backward: need tgt_len >= 2 and ld >= tgt_len");
+  TN_ON_DEVICE(t->ctx->device);
+  const int n = batch * steps;
+  int rc;
+#define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
+  float *x = ft_frame_staging(t->bb);
+  TN_TRY(launch_stage_frames(frames, src_valid_len, batch, steps, (long)t->side * t->side * 3, x, t->ctx->stream));
+  TN_TRY(ft_forward_features(t->bb, x, n));
+  TN_TRY(gnmt_trainer_step(t->cap, ft_features(t->bb), src_valid_len, tgt, ld, tgt_valid_len, batch, steps, tgt_len, loss, logits_out,
+                           t->frozen ? nullptr : ft_feature_grad(t->bb), t->F));
+  if (!t->frozen) TN_TRY(ft_backward_features(t->bb, n));
+  ft_update_running(t->bb);
+#undef TN_TRY
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+
+extern "C" int tn_gnmt_frames_trainer_buffers(tn_gnmt_frames_trainer *t, float **backbone_params, float **backbone_grads,
+                                              int64_t *backbone_numel, float **params_dev, float **grads_dev, int64_t *numel) {
+  TN_REQUIRE(t, "tn_gnmt_frames_trainer_buffers: null handle");
+  float *w, *g, *mom;
+  long n;
+  ft_param_buffers(t->bb, &w, &g, &mom, &n);
+  if (backbone_params) *backbone_params = w;
+  if (backbone_grads) *backbone_grads = g;
+  if (backbone_numel) *backbone_numel = n;
+  return tn_gnmt_trainer_buffers(t->cap, params_dev, grads_dev, numel);
+}
+
+extern "C" int tn_gnmt_frames_trainer_set_dropout(tn_gnmt_frames_trainer *t, float p, uint64_t seed) {
+  TN_REQUIRE(t, "tn_gnmt_frames_trainer_set_dropout: null handle");
+  return tn_gnmt_trainer_set_dropout(t->cap, p, seed);
+}
+
+// gluon.Trainer(model.collect_params(), 'adam').step(1) (train_gnmt.py:310,337) over both parts with one update count; frozen: the
+// backbone's parameters have grad_req 'null' (:164-166) and are not touched
+extern "C" int tn_gnmt_frames_trainer_adam_step(tn_gnmt_frames_trainer *t, float lr, float beta1, float beta2, float epsilon) {
+  TN_REQUIRE(t, "tn_gnmt_frames_trainer_adam_step: null handle");
+  TN_ON_DEVICE(t->ctx->device);
+  t->step += 1;
+  if (!t->frozen) {
+    const int rc = ft_adam_step(t->bb, lr, beta1, beta2, epsilon, t->step);
+    if (rc) return rc;
+  }
+  return gnmt_trainer_adam(t->cap, lr, beta1, beta2, epsilon, t->step);
+}
+
+extern "C" int tn_gnmt_frames_trainer_read_param(tn_gnmt_frames_trainer *t, const char *name, int gradient, float *out_host,
+                                                 int64_t capacity, int64_t *numel) {
+  TN_REQUIRE(t && name && out_host && numel, "tn_gnmt_frames_trainer_read_param: null argument");
+  const std::string n(name);
+  if (n.rfind(t->bb_prefix, 0) == 0) return tn_finetune_read_param(t->bb, name, gradient, out_host, capacity, numel);
+  TN_REQUIRE(n.rfind(t->prefix, 0) == 0, "tn_gnmt_frames_trainer_read_param: unknown parameter name");
+  return tn_gnmt_trainer_read_param(t->cap, name, gradient, out_host, capacity, numel);
+}
+
+extern "C" int tn_gnmt_frames_trainer_destroy(tn_gnmt_frames_trainer *t) {
+  if (!t) return TN_OK;
+  tn_gnmt_trainer_destroy(t->cap);
   tn_finetune_destroy(t->bb);
   delete t;
   return TN_OK;

@@ -1073,17 +1073,6 @@ __global__ void trn_mul_kernel(const float *__restrict__ x, const float *__restr
   if (i < n) y[i] = x[i] * m[i];
 }
 
-// MXNet Adam [EXT]: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; w -= lr_t m / (sqrt(v) + eps), lr_t bias-corrected
-__global__ void trn_adam_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
-                                float *__restrict__ v, long n, float lr_t, float b1, float b2, float eps) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float gi = g[i];
-  const float mi = b1 * m[i] + (1.f - b1) * gi, vi = b2 * v[i] + (1.f - b2) * gi * gi;
-  m[i] = mi; v[i] = vi;
-  w[i] -= lr_t * mi / (sqrtf(vi) + eps);
-}
-
 struct DevBuf {
   std::vector<void *> ptrs;
   bool failed = false;
@@ -1807,9 +1796,16 @@ __global__ void trn_dec_len_kernel(const int32_t *__restrict__ tgt_vl, int32_t *
 extern "C" int tn_gnmt_trainer_forward_backward(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len,
                                                 const int32_t *tgt, int ld, const int32_t *tgt_valid_len, int batch, int steps,
                                                 int tgt_len, float *loss, float *logits_out) {
+  return gnmt_trainer_step(t, src, src_valid_len, tgt, ld, tgt_valid_len, batch, steps, tgt_len, loss, logits_out, nullptr, 0);
+}
+
+// ... and, with dsrc, d loss / d src (train.h): the end-to-end frame-mode step hands it to the backbone's backward.
+int gnmt_trainer_step(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len, const int32_t *tgt, int ld,
+                      const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out, float *dsrc, int ldd) {
   TN_REQUIRE(t && src && src_valid_len && tgt && tgt_valid_len && loss, "tn_gnmt_trainer_forward_backward: null argument");
   TN_REQUIRE(batch > 0 && batch <= t->maxB && steps > 0 && steps <= t->maxT && tgt_len >= 2 && tgt_len - 1 <= t->maxL && ld >= tgt_len,
              "tn_gnmt_trainer_forward_backward: batch / source steps / target length exceed the handle");
+  TN_REQUIRE(!dsrc || ldd >= t->F, "gnmt_trainer_step: the source gradient's row stride is below input_size");
   TN_ON_DEVICE(t->ctx->device);
   hipStream_t s = t->ctx->stream;
   const int B = batch, T = steps, L = tgt_len - 1, H = t->H, E = t->E, V = t->V, G = t->G, GH = G * H, NL = t->NL;
@@ -2016,6 +2012,13 @@ extern "C" int tn_gnmt_trainer_forward_backward(tn_gnmt_trainer *t, const float 
       TrnEnc &below = t->enc[i - 1];
       TN_TRY(launch_linear_f32(e.dgi, DG, e.wiT, DG, nullptr, below.dxn, e.in, BT, e.in, DG, 0, s));
       if (e.res) hipLaunchKernelGGL(add_inplace_kernel, blocks((long)BT * e.in), dim3(256), 0, s, below.dxn, (const float *)e.dxn, (long)BT * e.in);
+    } else if (dsrc) {
+      // d src = dGI W_ih: dgi (BT, D GH) and W_ih (D GH, F) as the trainer keeps them (the directions stacked, row-major) are
+      // gemm_nn's operands as they stand.  This is the whole gradient: src reaches the loss through layer 0's input product alone -
+      // a residual connection adds a layer's input only for layers i > num_bi_layers >= 0 (gnmt.py:155-157), so never layer 0's,
+      // and dropout acts on layer outputs (gnmt.py:152).  Rows at or past the valid length: the recurrence backward does not
+      // write their dgi, which the memset above left at 0, so their product is exactly 0.
+      TN_TRY(launch_gemm_nn_f32(e.dgi, DG, w + e.o_wi, e.in, dsrc, ldd, BT, e.in, DG, 0, s));
     }
   }
 #undef TN_TRY
@@ -2059,13 +2062,13 @@ extern "C" int tn_gnmt_trainer_buffers(tn_gnmt_trainer *t, float **params_dev, f
 // epsilon 1e-8, no weight decay, no clipping, rescale_grad 1
 extern "C" int tn_gnmt_trainer_adam_step(tn_gnmt_trainer *t, float lr, float beta1, float beta2, float epsilon) {
   TN_REQUIRE(t, "tn_gnmt_trainer_adam_step: null handle");
+  return gnmt_trainer_adam(t, lr, beta1, beta2, epsilon, t->step + 1);
+}
+// the update for the step-th time (train.h): the frame-mode handle counts once for the backbone and the captioner
+int gnmt_trainer_adam(tn_gnmt_trainer *t, float lr, float beta1, float beta2, float epsilon, long step) {
   TN_ON_DEVICE(t->ctx->device);
-  t->step += 1;
-  const double c1 = 1.0 - pow((double)beta1, (double)t->step), c2 = 1.0 - pow((double)beta2, (double)t->step);
-  const float lr_t = (float)((double)lr * sqrt(c2) / c1);
-  hipLaunchKernelGGL(trn_adam_kernel, dim3((t->n + 255) / 256), dim3(256), 0, t->ctx->stream, t->w, (const float *)t->g, t->am, t->av, t->n,
-                     lr_t, beta1, beta2, epsilon);
-  TN_HIP_CHECK(hipGetLastError());
+  t->step = step;
+  if (int rc = launch_adam(t->w, t->g, t->am, t->av, t->n, lr, beta1, beta2, epsilon, step, t->ctx->stream)) return rc;
   return trainer_refresh(t);
 }
 

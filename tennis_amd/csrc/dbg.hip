@@ -416,6 +416,14 @@ extern "C" int tn_dbg_gemm_nn(tn_ctx *ctx, const float *A, int lda, const float 
   return TN_OK;
 }
 
+// The captioner's training step with its source gradient (train.h::gnmt_trainer_step), what the frame-mode step hands to the backbone
+extern "C" int tn_dbg_gnmt_trainer_src_grad(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len, const int32_t *tgt, int ld,
+                                            const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss,
+                                            float *logits_out, float *dsrc, int ldd) {
+  TN_REQUIRE(t && dsrc, "tn_dbg_gnmt_trainer_src_grad: null argument");
+  return gnmt_trainer_step(t, src, src_valid_len, tgt, ld, tgt_valid_len, batch, steps, tgt_len, loss, logits_out, dsrc, ldd);
+}
+
 // The forward 1x1 convolution of the fine-tuning step with its BatchNorm + ReLU applied to the X operand
 extern "C" int tn_dbg_linear_bnrelu(tn_ctx *ctx, const float *X, int ldx, const float *asc, const float *ash, const float *W, int ldw,
                                     const float *bias, float *Y, int ldy, int M, int N, int K, int accumulate) {

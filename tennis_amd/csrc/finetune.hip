@@ -359,6 +359,7 @@ struct tn_finetune {
   long n;                       // trainable parameters (GEMM layouts: conv weights as (Cout, ky*kx*Cin))
   long ns;                      // running statistics
   float *w, *g, *mom, *state;
+  float *av = nullptr;          // Adam's second moment (mom holds the first): ft_enable_adam
   long o_w0, o_wd, o_bd;
   FtBn bn0, bnF;
   std::vector<FtLayer> layers[4];
@@ -608,9 +609,10 @@ extern "C" int tn_finetune_create(tn_ctx *ctx, const tn_param *params, int n_par
 
 // The step in three parts (train.h), on the handle's stream; launch errors are peeked at by the launchers and checked once by the caller.
 // Forward of x (B, H, W, 3) through the backbone in training mode, batch statistics of every BatchNorm -> ft_features (B, 1024 ...)
-int ft_forward_features(tn_finetune *f, const float *x) {
+int ft_forward_features(tn_finetune *f, const float *x, int n) {
+  TN_REQUIRE(n > 0 && n <= f->B, "ft_forward_features: the frames of a step must be between 1 and the handle's capacity");
   hipStream_t s = f->ctx->stream;
-  const int B = f->B, H = f->H, W = f->W;
+  const int B = n, H = f->H, W = f->W;
   const long M0 = (long)B * (H / 2) * (W / 2);
   float *w = f->w;
   int rc;
@@ -654,9 +656,10 @@ int ft_forward_features(tn_finetune *f, const float *x) {
 }
 
 // Backward of the backbone from the feature gradient ft_feature_grad (B, 1024 ...): every backbone gradient, assigned
-int ft_backward_features(tn_finetune *f) {
+int ft_backward_features(tn_finetune *f, int n) {
+  TN_REQUIRE(n > 0 && n <= f->B, "ft_backward_features: the frames of a step must be between 1 and the handle's capacity");
   hipStream_t s = f->ctx->stream;
-  const int B = f->B, H = f->H, W = f->W;
+  const int B = n, H = f->H, W = f->W;
   const long M0 = (long)B * (H / 2) * (W / 2);
   float *w = f->w, *g = f->g;
   const int CF = f->Ctot[3], P3 = f->Hb[3] * f->Hb[3];
@@ -724,6 +727,19 @@ void ft_update_running(tn_finetune *f) {
 float *ft_features(tn_finetune *f) { return f->feat; }
 float *ft_feature_grad(tn_finetune *f) { return f->dfeat; }
 int ft_feature_dim(tn_finetune *f) { return f->Ctot[3]; }
+float *ft_frame_staging(tn_finetune *f) { return f->x_in; }
+// gluon.Trainer(model.collect_params(), 'adam') covers the backbone inside the captioner too (reference train_gnmt.py:310)
+int ft_enable_adam(tn_finetune *f) {
+  if (f->av) return TN_OK;
+  f->av = f->pool.fl(f->n);
+  if (!f->av) { tn_set_error("device allocation failed"); return TN_ERR_NOMEM; }
+  TN_HIP_CHECK(hipMemsetAsync(f->av, 0, sizeof(float) * f->n, f->ctx->stream));
+  return TN_OK;
+}
+int ft_adam_step(tn_finetune *f, float lr, float beta1, float beta2, float epsilon, long step) {
+  TN_REQUIRE(f->av, "ft_adam_step: ft_enable_adam has not run");
+  return launch_adam(f->w, f->g, f->mom, f->av, f->n, lr, beta1, beta2, epsilon, step, f->ctx->stream);
+}
 int ft_param_buffers(tn_finetune *f, float **w, float **g, float **mom, long *n) {
   *w = f->w; *g = f->g; *mom = f->mom; *n = f->n;
   return TN_OK;
@@ -744,14 +760,14 @@ extern "C" int tn_finetune_forward_backward(tn_finetune *f, const float *x, cons
   float *w = f->w, *g = f->g;
   int rc;
 #define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
-  TN_TRY(ft_forward_features(f, x));
+  TN_TRY(ft_forward_features(f, x, B));
   TN_TRY(launch_linear_f32(f->feat, CF, w + f->o_wd, CF, w + f->o_bd, f->logits, NC, B, NC, CF, 0, s));
   TN_HIP_CHECK(hipMemcpyAsync(f->labels, labels, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
   TN_TRY(launch_softmax_ce(f->logits, f->labels, B, NC, f->loss, f->dlog, s));
   if (loss) TN_HIP_CHECK(hipMemcpyAsync(loss, f->loss, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
   if (logits) TN_HIP_CHECK(hipMemcpyAsync(logits, f->logits, sizeof(float) * B * NC, hipMemcpyDeviceToDevice, s));
   TN_TRY(launch_dense_bwd(f->dlog, f->feat, w + f->o_wd, B, NC, CF, g + f->o_wd, g + f->o_bd, f->dfeat, s));
-  TN_TRY(ft_backward_features(f));
+  TN_TRY(ft_backward_features(f, B));
   ft_update_running(f);
 #undef TN_TRY
   TN_HIP_CHECK(hipGetLastError());

@@ -28,6 +28,12 @@ int launch_gemm_nn_f32(const float *A, int lda, const float *Bm, int ldb, float 
 int launch_colsum_f32(const float *A, int lda, int rows, int cols, float *out, hipStream_t s);
 int launch_sgd_momentum(float *w, const float *g, float *mom, long n, float lr, float momentum, float wd,
                         float rescale, hipStream_t s);
+// MXNet Adam (gluon.Trainer 'adam', reference train_gnmt.py:310,337): step = the 1-based update count, its bias correction folded
+// into the rate; no weight decay, rescale_grad 1.  Shared by the captioner's parameters (captioner.hip) and the backbone's (finetune.hip).
+int launch_adam(float *w, const float *g, float *m, float *v, long n, float lr, float beta1, float beta2, float epsilon, long step,
+                hipStream_t s);
+// y (B, T, frame_floats) = x with zeros in the frame slots t >= valid_len[b]: what Pad() leaves behind a clip's valid length
+int launch_stage_frames(const float *x, const int32_t *valid_len, int B, int T, long frame_floats, float *y, hipStream_t s);
 int launch_transpose_f32(const float *src, int rows, int cols, float *dst, hipStream_t s);
 // Training-mode BatchNorm of the fine-tuning step (finetune.hip) on an (M, C) matrix of row stride ld: batch mean and biased
 // variance; y (M, C contiguous) = relu(gamma (x - mean) / sqrt(var + eps) + beta); its backward from dy (M, C contiguous) into
@@ -41,15 +47,27 @@ int launch_ft_bn_backward(const float *dy, const float *x, int ld, long M, int C
 // The fine-tuning step in parts (finetune.hip), what tn_finetune_forward_backward chains and the CNN-RNN step (api.hip) drives.
 // ft_create: dense_prefix NULL builds the backbone alone (no classifier; classes ignored); fit_frames non-NULL: first compare the
 // memory batch frames need with what the device has free, and on a shortfall return TN_ERR_NOMEM with *fit_frames = the frames
-// that would fit.  ft_forward_features: training-mode forward of x (B, H, W, 3) -> ft_features (B, ft_feature_dim), batch
-// statistics kept; ft_backward_features: from ft_feature_grad (B, ft_feature_dim) every backbone gradient, assigned;
+// that would fit.  ft_forward_features: training-mode forward of x (n, H, W, 3) -> ft_features (n, ft_feature_dim), batch
+// statistics kept; ft_backward_features: from ft_feature_grad (n, ft_feature_dim) every backbone gradient, assigned;
 // ft_update_running: running = 0.9 running + 0.1 batch for every BatchNorm.
+// n: the frames of this step, 1 <= n <= ft_capacity (the batch the handle was created for).  Every row count, statistics divisor
+// and launch shape follows n alone, so a step of n frames is bit-identical on any handle that holds them; the backward's n must
+// be the forward's.  ft_enable_adam: the second-moment buffer (once, at creation); ft_adam_step: launch_adam on the trainable
+// parameters, the momentum buffer as the first moment (the running statistics are no parameters and are not touched).
 int ft_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *backbone_prefix, const char *dense_prefix, int height,
               int width, int classes, int batch, tn_finetune **out, long *fit_frames);
-int ft_forward_features(tn_finetune *f, const float *x);
-int ft_backward_features(tn_finetune *f);
+int ft_forward_features(tn_finetune *f, const float *x, int n);
+int ft_backward_features(tn_finetune *f, int n);
+int ft_enable_adam(tn_finetune *f);
+int ft_adam_step(tn_finetune *f, float lr, float beta1, float beta2, float epsilon, long step);
+float *ft_frame_staging(tn_finetune *f);      // (capacity, H, W, 3) floats of the handle's own, for a caller that stages its frames
 void ft_update_running(tn_finetune *f);
 float *ft_features(tn_finetune *f);
 float *ft_feature_grad(tn_finetune *f);
 int ft_feature_dim(tn_finetune *f);
 int ft_param_buffers(tn_finetune *f, float **w, float **g, float **mom, long *n);
+// The captioner's training step (captioner.hip), what tn_gnmt_trainer_forward_backward runs.  dsrc non-null: also the gradient of
+// the loss with respect to src, (batch * steps, input_size) of row stride ldd, assigned; rows at or past src_valid_len[b] are 0.
+int gnmt_trainer_step(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len, const int32_t *tgt, int ld,
+                      const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out, float *dsrc, int ldd);
+int gnmt_trainer_adam(tn_gnmt_trainer *t, float lr, float beta1, float beta2, float epsilon, long step);

@@ -461,6 +461,30 @@ __global__ void sgd_momentum_kernel(float *__restrict__ w, const float *__restri
   w[i] += m;
 }
 
+// MXNet Adam [EXT]: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; w -= lr_t m / (sqrt(v) + eps), lr_t bias-corrected
+__global__ void trn_adam_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
+                                float *__restrict__ v, long n, float lr_t, float b1, float b2, float eps) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float gi = g[i];
+  const float mi = b1 * m[i] + (1.f - b1) * gi, vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  m[i] = mi; v[i] = vi;
+  w[i] -= lr_t * mi / (sqrtf(vi) + eps);
+}
+
+// The step's frame staging: y (B, T, frame floats) = x, with zeros (the Pad() value of the normalised tensor,
+// utils/captioning.py:33) in the frame slots t >= valid_len[b], whose content in x is never read.  frame % 4 == 0.
+// Grid (blocks over a frame's float4s, B * T).
+__global__ void stage_frames_kernel(const float *__restrict__ x, const int32_t *__restrict__ valid_len, int T, long frame4,
+                                    float *__restrict__ y) {
+  const int slot = blockIdx.y, b = slot / T, t = slot % T;
+  const bool pad = t >= valid_len[b];
+  const float4 *src = (const float4 *)x + (long)slot * frame4;
+  float4 *dst = (float4 *)y + (long)slot * frame4;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < frame4; i += (long)gridDim.x * blockDim.x)
+    dst[i] = pad ? make_float4(0.f, 0.f, 0.f, 0.f) : src[i];
+}
+
 __global__ void transpose_f32_kernel(const float *__restrict__ src, int rows, int cols, float *__restrict__ dst) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)rows * cols) return;
@@ -569,6 +593,22 @@ int launch_colsum_f32(const float *A, int lda, int rows, int cols, float *out, h
 int launch_sgd_momentum(float *w, const float *g, float *mom, long n, float lr, float momentum, float wd,
                         float rescale, hipStream_t s) {
   hipLaunchKernelGGL(sgd_momentum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w, g, mom, n, lr, momentum, wd, rescale);
+  TN_LAUNCH_CHECK();
+}
+int launch_adam(float *w, const float *g, float *m, float *v, long n, float lr, float beta1, float beta2, float epsilon, long step,
+                hipStream_t s) {
+  const double c1 = 1.0 - pow((double)beta1, (double)step), c2 = 1.0 - pow((double)beta2, (double)step);
+  const float lr_t = (float)((double)lr * sqrt(c2) / c1);
+  hipLaunchKernelGGL(trn_adam_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w, g, m, v, n, lr_t, beta1, beta2, epsilon);
+  TN_LAUNCH_CHECK();
+}
+int launch_stage_frames(const float *x, const int32_t *valid_len, int B, int T, long frame_floats, float *y, hipStream_t s) {
+  TN_REQUIRE(x && y && valid_len && B > 0 && T > 0 && frame_floats > 0 && frame_floats % 4 == 0 && (long)B * T <= 65535,
+             "launch_stage_frames: bad shape");
+  TN_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "launch_stage_frames: the frame buffers must be 16-byte aligned");
+  const long f4 = frame_floats / 4;
+  const unsigned gx = (unsigned)((f4 + 255) / 256 < 64 ? (f4 + 255) / 256 : 64);
+  hipLaunchKernelGGL(stage_frames_kernel, dim3(gx, B * T), dim3(256), 0, s, x, valid_len, T, f4, y);
   TN_LAUNCH_CHECK();
 }
 int launch_transpose_f32(const float *src, int rows, int cols, float *dst, hipStream_t s) {

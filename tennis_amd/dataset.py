@@ -63,8 +63,9 @@ class TennisSet:
                 raise NotImplementedError("optical-flow input is outside the accelerated hot path (SURVEY §2a)")
             return CaptionSet(split=kw.get("split", "train"), every=kw.get("every", 1), max_cap_len=kw.get("max_cap_len", -1),
                               vocab=kw.get("vocab"), inference=kw.get("inference", False), root=root,
-                              split_id=kw.get("split_id", "02"), feats_model=kw.get("feats_model"),
-                              **{k: kw[k] for k in ("n_points", "feature_dim", "mean_frames", "seed") if k in kw})
+                              split_id=kw.get("split_id", "02"), feats_model=kw.get("feats_model"), frames=kw.get("frames", "auto"),
+                              **{k: kw[k] for k in ("n_points", "feature_dim", "mean_frames", "seed", "transform", "data_shape",
+                                                    "decode") if k in kw})
         return super().__new__(cls)
 
     def __init__(self, root="data", captions=False, transform=None, split="train", every=1, balance=True,
@@ -72,7 +73,8 @@ class TennisSet:
                  vocab=None, inference=False, feats_model=None, save_feats=False,
                  # synthetic-source knobs (not in the reference):
                  data_shape=224, videos=("V006", "V007"), frames_per_video=16, seed=1234, split_first=0,
-                 video_length=None, decode="host"):
+                 video_length=None, decode="host", synthetic=False):
+        """``synthetic=True``: the synthetic source whatever ``root`` holds (what ``CaptionSet(frames=True)`` without a dataset uses)."""
         if flow:
             raise NotImplementedError("optical-flow input is outside the accelerated hot path (SURVEY §2a)")
         if captions:      # __new__ redirects TennisSet(captions=True) to CaptionSet and never gets here; a subclass / object.__new__ path does
@@ -112,7 +114,7 @@ class TennisSet:
         self._annotations_dir = os.path.join(root, "annotations")
         self._labels_dir = os.path.join(root, "annotations", "labels")
         self._events, self._points, self._videos = [], {}, list(videos)
-        self.on_disk = os.path.exists(os.path.join(self._splits_dir, split_id, split + ".txt"))
+        self.on_disk = not synthetic and os.path.exists(os.path.join(self._splits_dir, split_id, split + ".txt"))
         if self.on_disk:
             self._samples, self._videos, self._events, self._points = self.load_data(split_id)
             self._video_lengths = self._get_video_lengths()
@@ -289,6 +291,15 @@ class TennisSet:
         if self._window > 1:
             return [(sample[0], f) for f in self.window_frames(sample)]
         return [(sample[0], sample[1])]
+
+    @property
+    def transform(self):
+        return self._transform
+
+    def load_frame(self, video, frame):
+        """one frame as an item carries it: its features, the transformed frame, or - under a ``device_batched`` transform, which runs
+        once per batch - the decoded uint8 frame (what ``CaptionSet``'s frame source stacks per point)"""
+        return self._load(video, frame)
 
     def _load(self, video, frame):
         if self._load_feats:

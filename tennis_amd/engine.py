@@ -680,3 +680,116 @@ class CNNRNNTrainer:
                 self.handle = None
         except Exception:
             pass
+
+
+class GNMTFramesTrainer:
+    """One frame-mode training step of the captioner, the way reference train_gnmt.py drives it without ``--feats_model``
+    (:148-203, 328-337): ``src_embed = TimeDistributed(FrameModel(DenseNet121.features).backbone)`` inside the ``NMTModel``, so the
+    backbone runs in training mode over all batch x steps frames of the padded clips and is trained - or, with ``freeze_backbone``
+    (:164-166), left alone - by the same ``loss.backward()`` and ``gluon.Trainer('adam').step(1)``.  fp32.
+
+    Any batch ``<= max_batch`` of any clip length ``<= max_src_len`` runs as long as ``batch * steps <= max_frames``.  The frame slots
+    behind a clip's valid length are zeroed (``Pad()``, utils/captioning.py:33) whatever the caller left there; they count in the
+    BatchNorm batch statistics, as in the reference (docs/numerics.md).
+
+    ``grads`` is a tuple of flat device views: (backbone, captioner), or (captioner,) with a frozen backbone - what a data-parallel
+    run all-reduces before ``step``.  A frozen backbone is not updated, but its BatchNorms still normalise with batch statistics
+    and update their running statistics (docs/numerics.md)."""
+
+    def __init__(self, params: dict, hidden: int, embed: int, vocab: int, size: int = 224, max_batch: int = 4, max_src_len: int = 16,
+                 max_tgt_len: int = 64, max_frames: int | None = None, prefix: str = "gnmt_", backbone_prefix: str = "densenet0_",
+                 freeze_backbone: bool = False, ctx: _lib.Context | None = None, cell_type: str = "gru", num_layers: int = 2,
+                 num_bi_layers: int = 1, use_residual: bool = False):
+        if cell_type not in ("gru", "lstm"):
+            raise ValueError(f"cell_type must be 'gru' or 'lstm', got {cell_type!r}")
+        self.ctx = ctx or _lib.default_context()
+        self.lib = self.ctx.lib
+        self.size, self.hidden, self.embed, self.vocab = size, hidden, embed, vocab
+        self.max_batch, self.max_src_len = max_batch, max_src_len
+        self.max_frames = max_batch * max_src_len if max_frames is None else max_frames
+        self.frozen = bool(freeze_backbone)
+        self.prefix, self.backbone_prefix, self.cell_type = prefix, backbone_prefix, cell_type
+        self.names = [k for k in params if k.startswith((prefix, backbone_prefix))]
+        self.shapes = {k: tuple(np.asarray(params[k]).shape) for k in self.names}
+        arr, keep = _lib.make_params({k: params[k] for k in self.names})
+        h = C.c_void_p()
+        check(self.lib.tn_gnmt_frames_trainer_create(self.ctx.handle, arr, len(arr), backbone_prefix.encode(), prefix.encode(),
+                                                     _lib.RNN_GRU if cell_type == "gru" else _lib.RNN_LSTM, hidden, embed, vocab,
+                                                     num_layers, num_bi_layers, 1 if use_residual else 0, size, max_batch, max_src_len,
+                                                     max_tgt_len, self.max_frames, 1 if self.frozen else 0, C.byref(h)),
+              "tn_gnmt_frames_trainer_create")
+        del keep
+        self.handle = h
+        bw, bg, bn, cw, cg, cn = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self.lib.tn_gnmt_frames_trainer_buffers(h, C.byref(bw), C.byref(bg), C.byref(bn), C.byref(cw), C.byref(cg), C.byref(cn)),
+              "tn_gnmt_frames_trainer_buffers")
+        self._bb = (bw.value, bg.value, bn.value)
+        self._cap = (cw.value, cg.value, cn.value)
+
+    def _view(self, addr, n):
+        class _Arr:
+            __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (addr, False), "version": 3}
+        return torch.as_tensor(_Arr(), device=f"cuda:{self.ctx.device}")
+
+    @property
+    def grads(self) -> tuple:
+        cap = self._view(self._cap[1], self._cap[2])
+        return (cap,) if self.frozen else (self._view(self._bb[1], self._bb[2]), cap)
+
+    @property
+    def params(self) -> tuple:
+        return self._view(self._bb[0], self._bb[2]), self._view(self._cap[0], self._cap[2])
+
+    def forward_backward(self, frames: torch.Tensor, src_valid_length: torch.Tensor, tgt: torch.Tensor,
+                         tgt_valid_length: torch.Tensor, return_logits: bool = False):
+        """frames (B,T) clips, NCHW or NHWC per frame, fp32 normalised or uint8 (ToTensor + Normalize applied here); tgt (B,L) token
+        ids incl. BOS / EOS, valid lengths (B,) -> loss (0-d tensor) [, logits (B,L-1,V)]"""
+        _on_ctx_device(self.ctx, frames, "GNMTFramesTrainer")
+        sz = self.size
+        x = frames
+        if x.dtype == torch.uint8:
+            x = to_tensor_normalize(x, ctx=self.ctx)
+        if x.dim() == 5 and tuple(x.shape[2:]) == (3, sz, sz):
+            x = x.permute(0, 1, 3, 4, 2)
+        if x.dim() != 5 or tuple(x.shape[2:]) != (sz, sz, 3):
+            raise ValueError(f"GNMTFramesTrainer expects (B, T, 3, {sz}, {sz}) or (B, T, {sz}, {sz}, 3) frames, got {tuple(frames.shape)}")
+        x = x.contiguous().float()                 # (read only: the handle stages the frames and zeroes the padded slots there)
+        b, t = x.shape[0], x.shape[1]
+        dev = x.device
+        tgt = tgt.to(device=dev, dtype=torch.int32).contiguous()
+        svl = src_valid_length.to(device=dev, dtype=torch.int32).contiguous()
+        tvl = tgt_valid_length.to(device=dev, dtype=torch.int32).contiguous()
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        logits = torch.empty((b, tgt.shape[1] - 1, self.vocab), dtype=torch.float32, device=dev) if return_logits else None
+        check(self.lib.tn_gnmt_frames_trainer_forward_backward(self.handle, ptr(x), ptr(svl), ptr(tgt), tgt.shape[1], ptr(tvl), b, t,
+                                                               tgt.shape[1], ptr(loss), ptr(logits)),
+              "tn_gnmt_frames_trainer_forward_backward")
+        return (loss[0], logits) if return_logits else loss[0]
+
+    def set_dropout(self, p: float, seed: int = 0):
+        """``--dropout`` of train_gnmt.py: after each encoder layer and on the decoder cells' outputs (the backbone has none)."""
+        check(self.lib.tn_gnmt_frames_trainer_set_dropout(self.handle, p, seed), "tn_gnmt_frames_trainer_set_dropout")
+
+    def step(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8):
+        check(self.lib.tn_gnmt_frames_trainer_adam_step(self.handle, lr, beta1, beta2, epsilon), "tn_gnmt_frames_trainer_adam_step")
+
+    def get(self, name: str, gradient: bool = False, shape=None) -> np.ndarray:
+        shape = shape or self.shapes[name]
+        out = np.empty(int(np.prod(shape)), np.float32)
+        n = C.c_int64()
+        check(self.lib.tn_gnmt_frames_trainer_read_param(self.handle, name.encode(), 1 if gradient else 0,
+                                                         out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n)),
+              "tn_gnmt_frames_trainer_read_param")
+        return out[:n.value].reshape(shape).copy()
+
+    def state_dict(self) -> dict:
+        """Every parameter of both parts and the backbone's running statistics, by name."""
+        return {k: self.get(k) for k in self.names}
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self.lib.tn_gnmt_frames_trainer_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass

@@ -1,7 +1,8 @@
 """Captioner evaluation driver - counterpart of reference evaluate_gnmt.py: load the best parameters of a model id
 (``valid_best.params``, else the newest epoch file) and report teacher-forced loss, perplexity and BLEU of the beam-search
 translations on the validation and test splits, writing the sentences out (evaluate_gnmt.py:196-258; same flag names as
-train_gnmt).  Feature mode (``--feats_model`` in the reference): the frame features are the inputs."""
+train_gnmt).  Feature mode (``--feats_model``): the frame features are the inputs.  Frame mode (no ``--feats_model``): the points'
+frames go through the backbone inside the model, whose parameters the checkpoint of a frame-mode training run holds."""
 from __future__ import annotations
 
 import math

@@ -11,6 +11,9 @@ model was built with them:
       keep the parameters with the best validation BLEU; lr *= lr_update_factor once
       epoch + 1 >= 2/3 of the epochs; save the epoch's parameters                                       :450-461
 
+Without ``--feats_model`` the model holds the CNN (``src_embed = TimeDistributed(FrameModel(...).backbone)``, :148-186) and the
+same step trains it, or with ``--freeze_backbone`` leaves it alone (:164-166): ``tn_gnmt_frames_trainer_*``.
+
 All arithmetic runs in libtennis_hip (``tn_gnmt_trainer_*`` for the step, ``tn_gnmt_*`` for evaluation); with
 ``torch.distributed`` initialised (backend nccl = RCCL) every rank trains on its own batches and the flat gradient
 buffer is averaged over ranks before the Adam update.  nlg-eval's METEOR / CIDEr stay external, as in the survey.
@@ -23,8 +26,8 @@ import os
 import numpy as np
 import torch
 
-from .captions import bucketed_batches, evaluate, write_sentences
-from .engine import GNMTTrainer
+from .captions import bucketed_batches, evaluate, to_device, write_sentences
+from .engine import GNMTFramesTrainer, GNMTTrainer
 from .metrics.bleu import compute_bleu
 
 
@@ -34,24 +37,31 @@ def allreduce_grads(trainer, n_tokens: int):
     weighted by the token counts: all-reduce n_r * g_r and n_r, then divide (reference loss: train_gnmt.py:332-333)."""
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        g = trainer.grads
-        cnt = torch.tensor([float(n_tokens)], dtype=torch.float32, device=g.device)
-        g *= float(n_tokens)
+        gs = trainer.grads if isinstance(trainer.grads, tuple) else (trainer.grads,)     # frame mode: (backbone, captioner)
+        cnt = torch.tensor([float(n_tokens)], dtype=torch.float32, device=gs[0].device)
         from .train import _grad_comm
-        comm = _grad_comm(g.device)
-        if comm is not None:                     # tn_allreduce_f32: RCCL behind the C-ABI
-            comm.allreduce_(g)
+        comm = _grad_comm(gs[0].device)
+        for g in gs:
+            g *= float(n_tokens)
+            if comm is not None:                 # tn_allreduce_f32: RCCL behind the C-ABI
+                comm.allreduce_(g)
+            else:
+                dist.all_reduce(g, op=dist.ReduceOp.SUM)
+        if comm is not None:
             comm.allreduce_(cnt).wait()
         else:
-            dist.all_reduce(g, op=dist.ReduceOp.SUM)
             dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
-        g /= cnt
+        for g in gs:
+            g /= cnt
 
 
 def train(data_train, data_val, data_test, model, translator, epochs: int, batch_size: int, lr: float = 1e-3,
           lr_update_factor: float = 0.5, dropout: float = 0.0, num_buckets: int = 5, test_batch_size: int = 32,
-          start_epoch: int = 0, save_dir: str | None = None, seed: int = 0, log=print):
-    """-> history: one dict per epoch (train loss, valid / test loss and BLEU, learning rate)."""
+          start_epoch: int = 0, save_dir: str | None = None, seed: int = 0, log=print, freeze_backbone: bool = False,
+          frame_size: int | None = None):
+    """-> history: one dict per epoch (train loss, valid / test loss and BLEU, learning rate).  A model with a ``src_embed`` trains on
+    frames (``GNMTFramesTrainer``: the backbone inside the step, frozen or trainable); its checkpoints carry the backbone under the
+    model's structural names (``src_embed.model. ...``)."""
     enc = model.encoder
     if enc._cell_type not in ("gru", "lstm"):
         raise NotImplementedError("the training step is built for GRU / LSTM cells")
@@ -62,10 +72,25 @@ def train(data_train, data_val, data_test, model, translator, epochs: int, batch
     params = {k: v.data for k, v in model.collect_params().items()}
     max_t = max(l[0] for l in data_train.get_data_lens())
     max_l = max(l[-1] for l in data_train.get_data_lens())
-    trainer = GNMTTrainer(params, model._input_size, enc._hidden_size, model._embed_size, len(model.tgt_vocab),
-                          max_batch=batch_size, max_src_len=max_t, max_tgt_len=max_l, prefix=model.prefix,
-                          cell_type=enc._cell_type, num_layers=enc._num_layers, num_bi_layers=enc._num_bi_layers,
-                          use_residual=bool(getattr(enc, "_use_residual", False)))
+    cell = dict(cell_type=enc._cell_type, num_layers=enc._num_layers, num_bi_layers=enc._num_bi_layers,
+                use_residual=bool(getattr(enc, "_use_residual", False)))
+    frame_mode = getattr(model, "src_embed", None) is not None
+    if frame_mode:
+        max_t = max(max_t, max(data_train.get_clip_lens()))
+        # the side of the frames the step sees: --data_shape, else the batch transform's crop, else that of per-frame (T, 3, S, S) items
+        item = data_train[0][0]
+        side = frame_size or getattr(getattr(data_train, "_transform", None), "crop", None)
+        if side is None and item.dtype == np.float32 and item.ndim == 4 and item.shape[1] == 3 and item.shape[2] == item.shape[3]:
+            side = int(item.shape[-1])
+        if side is None:
+            raise ValueError("train: frame_size is needed - the items are decoded frames and their transform names no crop size")
+        trainer = GNMTFramesTrainer(params, enc._hidden_size, model._embed_size, len(model.tgt_vocab), size=side, max_batch=batch_size,
+                                    max_src_len=max_t, max_tgt_len=max_l, max_frames=frame_capacity(data_train, batch_size, num_buckets),
+                                    prefix=model.prefix, backbone_prefix=model.src_embed.model.prefix, freeze_backbone=freeze_backbone,
+                                    **cell)
+    else:
+        trainer = GNMTTrainer(params, model._input_size, enc._hidden_size, model._embed_size, len(model.tgt_vocab),
+                              max_batch=batch_size, max_src_len=max_t, max_tgt_len=max_l, prefix=model.prefix, **cell)
     if dropout > 0:
         trainer.set_dropout(dropout, seed)
     val_tgt = data_val.get_captions(split=True) if data_val is not None else None
@@ -81,7 +106,7 @@ def train(data_train, data_val, data_test, model, translator, epochs: int, batch
         # FixedBucketSampler(..., shuffle=True) of the training loader (utils/captioning.py:48-55)
         for src, tgt, svl, tvl, *_ in bucketed_batches(data_train, batch_size, num_buckets, shuffle=True, seed=seed,
                                                        epoch=epoch_id, rank=rank, world=world):
-            loss = trainer.forward_backward(torch.from_numpy(src).cuda(), torch.from_numpy(svl.astype(np.int32)).cuda(),
+            loss = trainer.forward_backward(to_device(src), torch.from_numpy(svl.astype(np.int32)).cuda(),
                                             torch.from_numpy(tgt).cuda(), torch.from_numpy(tvl.astype(np.int32)).cuda())
             allreduce_grads(trainer, int((tvl.astype(np.int64) - 1).sum()))
             trainer.step(lr)                                                     # trainer.step(1)
@@ -101,14 +126,26 @@ def train(data_train, data_val, data_test, model, translator, epochs: int, batch
                 write_sentences(out, os.path.join(save_dir, "epoch{:d}_{}_out.txt".format(epoch_id, name)))
         if save_dir and rec.get("valid_bleu", 0.0) > best_valid_bleu:            # :450-454
             best_valid_bleu = rec["valid_bleu"]
-            model.save_parameters(os.path.join(save_dir, "valid_best.params"), structural=False)
+            model.save_parameters(os.path.join(save_dir, "valid_best.params"), structural=frame_mode)
         if epoch_id + 1 >= (epochs * 2) // 3:                                    # :456-459
             lr *= lr_update_factor
             log("Learning rate change to {}".format(lr))
         if save_dir:
-            model.save_parameters(os.path.join(save_dir, "{:04d}.params".format(epoch_id)), structural=False)
+            model.save_parameters(os.path.join(save_dir, "{:04d}.params".format(epoch_id)), structural=frame_mode)
         history.append(rec)
     return history
+
+
+def frame_capacity(data_train, batch_size, num_buckets):
+    """The most frames a training batch holds once padded (batch x its longest clip): batches are cut from the buckets in dataset
+    order or permuted, so the bound is, per bucket, the ``batch_size`` longest clips' count x the longest clip."""
+    tl = [l[-1] for l in data_train.get_data_lens()]
+    lo, hi = min(tl), max(tl)
+    width = max(1, math.ceil((hi - lo + 1) / num_buckets))
+    buckets = {}
+    for l, t in zip(tl, data_train.get_clip_lens()):
+        buckets.setdefault((l - lo) // width, []).append(t)
+    return max(min(batch_size, len(v)) * max(v) for v in buckets.values())
 
 
 def build_parser():
@@ -154,6 +191,8 @@ def build_parser():
     p.add_argument("--feature_dim", type=int, default=1024, help="width of the pre-extracted frame features (feats_model)")
     p.add_argument("--n_points", type=int, default=64, help="synthetic source: points per split")
     p.add_argument("--root", default="models/captioning/experiments")
+    p.add_argument("--no_augment", action="store_true", help="frame mode: the test transform for the train split too (not a reference flag)")
+    p.add_argument("--frames", action="store_true", help="synthetic source (no --data_root): frame mode on synthetic frames")
     return p
 
 
@@ -176,36 +215,73 @@ def load_target_embedding(flags, vocab, log=print):
 
 
 def build(flags):
-    """Datasets, model and translator as reference train_gnmt.py:120-256 assembles them (feature mode, ``--feats_model``): with
+    """Datasets, model and translator as reference train_gnmt.py:120-256 assembles them.  Feature mode (``--feats_model``): with
     ``--data_root`` the points, captions and per-frame ``.npy`` features come from disk (``TennisSet(captions=True, ...)``), the
-    target embedding from ``--emb_file``; without it everything is synthetic."""
+    target embedding from ``--emb_file``; without it everything is synthetic.  Frame mode (``--data_root`` without ``--feats_model``,
+    :148-186): the points' frames are the source, ``get_model(--backbone, pretrained=True).features`` inside ``FrameModel(..., 11)`` -
+    from ``--backbone_from_id``'s newest parameters when given - is the model's ``src_embed = TimeDistributed(cnn_model.backbone)``,
+    the train split gets the train transform of :172-179 (``--no_augment``: the test transform), val / test the test transform."""
     from .dataset import TennisSet
     from .models.captioning.gnmt import NMTModel, get_gnmt_encoder_decoder
     from .utils.translation import BeamSearchScorer, BeamSearchTranslator
     if flags.data_root is None and flags.feats_model is not None and os.path.isdir(os.path.join("data", "splits")):
         flags.data_root = "data"           # the reference's layout relative to the working directory (dataset.py:17: root='data')
-    if flags.data_root is not None and flags.feats_model is None:
-        raise NotImplementedError("train_gnmt on raw frames (no --feats_model) needs the frames of every point on disk and the backbone "
-                                  "inside the step; the accelerated path is the reference's feature mode (evaluate --save_feats first)")
+    frame_mode = flags.feats_model is None and (flags.data_root is not None or getattr(flags, "frames", False))
+    src_embed, tf, tf_train = None, None, None
+    if frame_mode:
+        src_embed = build_backbone(flags)
+        if flags.data_root is not None:             # frames from disk: one GPU launch group per batch (tennis_amd.transforms)
+            from . import transforms
+            norm = [transforms.ToTensor(), transforms.Normalize([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])]
+            tf = transforms.Compose([transforms.Resize(flags.data_shape + 32), transforms.CenterCrop(flags.data_shape)] + norm)
+            tf_train = tf if flags.no_augment else transforms.Compose(                                       # :172-179
+                [transforms.RandomResizedCrop(flags.data_shape), transforms.RandomFlipLeftRight(),
+                 transforms.RandomColorJitter(brightness=0.4, contrast=0.4, saturation=0.4), transforms.RandomLighting(0.1)] + norm, seed=1000)
     src = dict(root=flags.data_root, split_id=flags.split_id, feats_model=flags.feats_model) if flags.data_root is not None else dict(root=None)
     syn = {} if flags.data_root is not None else dict(feature_dim=flags.feature_dim)
+    if frame_mode and flags.data_root is None:
+        syn = dict(frames=True, data_shape=flags.data_shape)
+    mk = lambda t: dict(transform=t) if frame_mode and flags.data_root is not None else {}
     data_train = TennisSet(captions=True, split="train", every=flags.every, max_cap_len=flags.tgt_max_len,
-                           **src, **syn, **({} if flags.data_root is not None else dict(n_points=flags.n_points)))
+                           **src, **syn, **mk(tf_train), **({} if flags.data_root is not None else dict(n_points=flags.n_points)))
     data_val = TennisSet(captions=True, split="val", every=flags.every, vocab=data_train.vocab, inference=True,
-                         **src, **syn, **({} if flags.data_root is not None else dict(n_points=max(4, flags.n_points // 4))))
+                         **src, **syn, **mk(tf), **({} if flags.data_root is not None else dict(n_points=max(4, flags.n_points // 4))))
     data_test = TennisSet(captions=True, split="test", every=flags.every, vocab=data_train.vocab, inference=True,
-                          **src, **syn, **({} if flags.data_root is not None else dict(n_points=max(4, flags.n_points // 4))))
-    feature_dim = data_train[0][0].shape[1] if len(data_train) else flags.feature_dim      # the width evaluate --save_feats wrote
+                          **src, **syn, **mk(tf), **({} if flags.data_root is not None else dict(n_points=max(4, flags.n_points // 4))))
+    if frame_mode:
+        from . import weights as W
+        feature_dim = W.densenet121_layout()[2]        # input_size is the backbone's feature width
+    else:
+        feature_dim = data_train[0][0].shape[1] if len(data_train) else flags.feature_dim  # the width evaluate --save_feats wrote
     tgt_embed = load_target_embedding(flags, data_train.vocab)
     enc, dec = get_gnmt_encoder_decoder(cell_type=flags.cell_type, hidden_size=flags.num_hidden, dropout=flags.dropout,
                                         num_layers=flags.num_layers, num_bi_layers=flags.num_bi_layers)
     model = NMTModel(src_vocab=None, tgt_vocab=data_train.vocab, encoder=enc, decoder=dec, embed_size=flags.emb_size,
-                     prefix="gnmt_", input_size=feature_dim, tgt_embed=tgt_embed)                  # train_gnmt.py:228-229
+                     prefix="gnmt_", input_size=feature_dim, tgt_embed=tgt_embed, src_embed=src_embed)   # train_gnmt.py:228-229
     model.initialize()
     translator = BeamSearchTranslator(model=model, beam_size=flags.beam_size,
                                       scorer=BeamSearchScorer(alpha=flags.lp_alpha, K=flags.lp_k),
                                       max_length=flags.tgt_max_len + 100)                     # train_gnmt.py:250-252
     return data_train, data_val, data_test, model, translator
+
+
+def build_backbone(flags):
+    """reference train_gnmt.py:149-170: the CNN of the frame-mode model, ``TimeDistributed(cnn_model.backbone)``"""
+    from .model_zoo import get_model
+    from .models.vision.definitions import FrameModel
+    from .utils.layers import TimeDistributed
+    cnn_model = FrameModel(get_model(flags.backbone, pretrained=True).features, 11)                          # :150-151
+    if flags.backbone_from_id:                                                                               # :153-163
+        d = os.path.join("models", "vision", "experiments", flags.backbone_from_id)
+        if not os.path.isdir(d):
+            raise FileNotFoundError("Experiment folder ({}) does not exist".format(d))                       # :161-162
+        files = sorted(f for f in os.listdir(d) if f.endswith(".params"))
+        if files:
+            cnn_model.initialize()
+            cnn_model.classes._materialize(1024)
+            cnn_model.load_parameters(os.path.join(d, files[-1]))
+            print("Loaded backbone params: {}".format(os.path.join(d, files[-1])))
+    return TimeDistributed(cnn_model.backbone)                                                               # :168-170
 
 
 def main(argv=None):
@@ -225,7 +301,8 @@ def main(argv=None):
         print("Loaded model params: {}".format(os.path.join(save_dir, files[0])))
     hist = train(data_train, data_val, data_test, model, translator, flags.epochs, flags.batch_size, lr=flags.lr,
                  lr_update_factor=flags.lr_update_factor, dropout=flags.dropout, num_buckets=flags.num_buckets,
-                 test_batch_size=flags.test_batch_size, start_epoch=start_epoch, save_dir=save_dir)
+                 test_batch_size=flags.test_batch_size, start_epoch=start_epoch, save_dir=save_dir,
+                 freeze_backbone=flags.freeze_backbone, frame_size=flags.data_shape if getattr(model, "src_embed", None) is not None else None)
     if not hist:
         print("[Finished] nothing to do: {} epochs are on disk".format(start_epoch))
         return 0
