@@ -97,6 +97,18 @@ int tn_densenet121_create(tn_ctx *ctx, const tn_param *params, int n_params, con
  * the per-family profile (families "fp32_*").  tn_densenet121_input_means and tn_densenet121_read_tap refuse such an encoder.
  * TN_ENC_FP32 | TN_ENC_EXACT_WEIGHTS selects this mode as well. */
 #define TN_ENC_FP32 4
+/* TN_ENC_FP32X3: the fp32 mode's network - fp32 activation maps, fp32 accumulators, the same folds, workspace, layouts, batches,
+ * pipelining - with the products on the bf16 matrix pipe (csrc/dense_fp32x3.hip): every fp32 operand is handed over as three
+ * bf16 terms (v1 = bf16(v), v2 = bf16(v - v1), v3 = bf16(v - v1 - v2), 24 bits between them, fp32's exponent range: no scaling,
+ * no calibration, any checkpoint) and the six largest of the nine cross products are formed per 16-wide k-step, in a fixed order.
+ * The dropped products are below 2^-24 |a||b|: the result is an fp32 accumulation that differs from the fp32 mode's in summation
+ * grouping only, and holds the same 1e-3 bar.  Profile families "fp32x3_*"; tn_densenet121_input_means and
+ * tn_densenet121_read_tap refuse such an encoder.  TN_ENC_FP32X3 | TN_ENC_EXACT_WEIGHTS selects this mode as well;
+ * TN_ENC_FP32X3 | TN_ENC_FP32 is refused (two modes). */
+#define TN_ENC_FP32X3 8
+/* The three-term split of the fp32x3 mode on the host (no GPU involved): t1 + t2 + t3 reproduces w to 2^-24 |w|, every term the
+ * bit pattern of a bf16 number (round to nearest even). */
+int tn_fp32x3_split(const float *w, int64_t n, uint16_t *t1, uint16_t *t2, uint16_t *t3);
 int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int n_params, const char *prefix, int height, int width,
                              int max_batch, int flags, tn_encoder **out);
 int tn_densenet121_feature_dim(const tn_encoder *enc);

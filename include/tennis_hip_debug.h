@@ -136,6 +136,17 @@ int tn_dbg_gnmt_trainer_src_grad(tn_gnmt_trainer *t, const float *src, const int
                                  const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out,
                                  float *dsrc, int ldd);
 
+/* One convolution of the fp32x3 encoder mode (csrc/dense_fp32x3.hip; which = 0) or, on the same operands, of the fp32 mode
+ * (csrc/dense_fp32.hip; which = 1).  kind: 0 stem 7x7/2 (x: B frames in `layout`, H x W; epilogue relu(es y + et)), 1 dense 1x1,
+ * 2 dense 3x3 (K = 1152, ldx = 128), 3 transition (2x2 average of relu(s x + t), then the 1x1); x an fp32 NHWC map (.., ldx), s / t
+ * the BatchNorm applied on load (K values; 3x3: 128), es / et NULL except for the stem, y (M, ldy) fp32 written in columns
+ * [yoff, yoff + N), M = B Ho Wo output pixels: all DEVICE, 16-byte aligned.  w_host: the GEMM's B operand (K, N) fp32, k-major
+ * (stem k = c 49 + ky 7 + kx, 3x3 k = tap 128 + c), HOST; padded and - which = 0 - split and packed as tn_densenet121_create_ex
+ * does.  tile (which = 0): 0 the launcher's choice, 1 the small tile, 2 the large one.  Synchronous. */
+int tn_dbg_conv_fp32x3(tn_ctx *ctx, int which, int kind, int tile, int layout, const void *x, int ldx, int K, const float *s, const float *t,
+                       const float *w_host, int N, const float *es, const float *et, float *y, int ldy, int yoff, int64_t M, int H, int W,
+                       int Ho, int Wo);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("TENNIS_HIP_LIB") or os.path.join(_HERE, "lib", "libte
 LAYOUT_NCHW_F32, LAYOUT_NHWC_F16, LAYOUT_NHWC_U8 = 0, 1, 2
 ENC_EXACT_WEIGHTS = 1
 ENC_FP32 = 4
+ENC_FP32X3 = 8
 RNN_GRU, RNN_LSTM = 0, 1
 POOL_MAX, POOL_MEAN = 0, 1
 
@@ -143,6 +144,8 @@ _SIGS = {
     "tn_dbg_stem": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int]),
     "tn_dbg_maxpool": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_head": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int]),
+    "tn_dbg_conv_fp32x3": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int,
+                                     C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_gemm_tn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
     "tn_dbg_gemm_nn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_linear_bnrelu": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -165,6 +168,7 @@ _SIGS = {
     "tn_npy_writer_drain": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tn_npy_writer_destroy": (C.c_int, [_P]),
     "tn_bn_relu_clamp_fold": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "tn_fp32x3_split": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     "tn_round_fp16_calibrated": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_double, _P]),
     "tn_dbg_block7_create": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_void_p)]),
     "tn_dbg_block7_run": (C.c_int, [_P, _P, C.c_int, C.c_int]),

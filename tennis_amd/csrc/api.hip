@@ -351,11 +351,15 @@ struct tn_encoder {
   // TN_ENC_FP32 (dense_fp32.hip): fp32 weights, fp32 activations, f32-input MFMA.  Nothing above this is packed or allocated
   // for such an encoder, and nothing below for any other.
   bool fp32 = false;
-  struct Fp32Layer { float *s1, *t1, *w1, *s2, *t2, *w3; int cin; };   // w1 [cin][128], w3 [9 * 128][32] (k = tap * 128 + c)
+  // TN_ENC_FP32X3 (dense_fp32x3.hip): an fp32-mode encoder (fp32 is set as well) whose convolutions run on the bf16 MFMA from
+  // three-term weight images (the *x members: fp32x3_pack_weights of the fp32 arrays beside them, nullptr in the fp32 mode)
+  bool fp32x3 = false;
+  struct Fp32Layer { float *s1, *t1, *w1, *s2, *t2, *w3; int cin; uint16_t *w1x, *w3x; };   // w1 [cin][128], w3 [9 * 128][32] (k = tap * 128 + c)
   struct Fp32Net {
     float *stem_w = nullptr, *stem_s = nullptr, *stem_t = nullptr;      // stem_w [160][64] (k = c * 49 + ky * 7 + kx, zero past 147)
+    uint16_t *stem_wx = nullptr;
     std::vector<Fp32Layer> layers[4];
-    struct { float *s, *t, *w; int cin, cout; } trans[3];               // w [cin][cout]
+    struct { float *s, *t, *w; int cin, cout; uint16_t *wx; } trans[3];   // w [cin][cout]
     float *head_s = nullptr, *head_t = nullptr;
     float *stem = nullptr, *bott = nullptr, *buf[4] = {nullptr, nullptr, nullptr, nullptr};   // workspace: stem map, bottleneck, concat buffers
   } f32;
@@ -389,9 +393,14 @@ static std::vector<float> transpose_pad(const float *w, int rows, int k, int kp)
 static int create_fp32(tn_encoder *e, const ParamMap &pm, const std::string &pre) {
   auto &F = e->f32;
   std::vector<float> s, t;
+  // the B operand [kp][n] of a convolution: the fp32 array and - fp32x3 - its three-term bf16 image
+  auto upload_w = [&](const std::vector<float> &wk, int kp, int n, uint16_t *&wx) {
+    wx = e->fp32x3 ? e->pool.upload(fp32x3_pack_weights(wk.data(), kp, n)) : nullptr;
+    return e->pool.upload(wk);
+  };
   const float *w0 = pm.get(pre + "conv0_weight", 64 * 3 * 7 * 7);
   if (!w0 || !fold_bn_f64(pm, pre + "batchnorm0", 64, s, t)) return TN_ERR_MISSING;
-  F.stem_w = e->pool.upload(transpose_pad(w0, 64, 147, 160));       // (64, 3, 7, 7): k = c * 49 + ky * 7 + kx already
+  F.stem_w = upload_w(transpose_pad(w0, 64, 147, 160), 160, 64, F.stem_wx);       // (64, 3, 7, 7): k = c * 49 + ky * 7 + kx already
   F.stem_s = e->pool.upload(s); F.stem_t = e->pool.upload(t);
   int outer = 1;
   for (int b = 0; b < 4; ++b) {
@@ -406,12 +415,12 @@ static int create_fp32(tn_encoder *e, const ParamMap &pm, const std::string &pre
       L.s1 = e->pool.upload(s); L.t1 = e->pool.upload(t);
       if (!fold_bn_f64(pm, sp + "batchnorm" + std::to_string(2 * l + 1), 128, s, t)) return TN_ERR_MISSING;
       L.s2 = e->pool.upload(s); L.t2 = e->pool.upload(t);
-      L.w1 = e->pool.upload(transpose_pad(w1, 128, L.cin, L.cin));
+      L.w1 = upload_w(transpose_pad(w1, 128, L.cin, L.cin), L.cin, 128, L.w1x);
       std::vector<float> w3k((size_t)9 * 128 * 32);
       for (int n = 0; n < 32; ++n)
         for (int c = 0; c < 128; ++c)
           for (int tap = 0; tap < 9; ++tap) w3k[((size_t)tap * 128 + c) * 32 + n] = w3[((size_t)n * 128 + c) * 9 + tap];
-      L.w3 = e->pool.upload(w3k);
+      L.w3 = upload_w(w3k, 9 * 128, 32, L.w3x);
       F.layers[b].push_back(L);
     }
     if (b < 3) {
@@ -420,7 +429,7 @@ static int create_fp32(tn_encoder *e, const ParamMap &pm, const std::string &pre
       const float *wt = pm.get(pre + "conv" + std::to_string(outer) + "_weight", (int64_t)T.cout * T.cin);
       if (!wt || !fold_bn_f64(pm, pre + "batchnorm" + std::to_string(outer), T.cin, s, t)) return TN_ERR_MISSING;
       T.s = e->pool.upload(s); T.t = e->pool.upload(t);
-      T.w = e->pool.upload(transpose_pad(wt, T.cout, T.cin, T.cin));
+      T.w = upload_w(transpose_pad(wt, T.cout, T.cin, T.cin), T.cin, T.cout, T.wx);
       ++outer;
     }
   }
@@ -440,11 +449,15 @@ static int create_fp32(tn_encoder *e, const ParamMap &pm, const std::string &pre
 
 // Frames [b0, b0 + B) of an fp32-mode encoder, workspace frame slots from w0: stem (BN + ReLU in the epilogue), max pool,
 // per dense layer the 1x1 (BN1 + ReLU on load -> raw bottleneck) and the 3x3 (BN2 + ReLU on load -> 32 new channels),
-// transitions (BN + ReLU + 2x2 average on load), and the head on the last concat buffer.
+// transitions (BN + ReLU + 2x2 average on load), and the head on the last concat buffer.  An fp32x3 encoder runs the same
+// sequence with launch_conv_fp32x3 on the three-term weight images (families "fp32x3_*").
 static int encoder_run_range_fp32(tn_encoder *e, const void *x, tn_layout layout, int B, float *feat, hipStream_t s, EventTimer &tm,
                                   int w0) {
   auto &F = e->f32;
   int rc;
+  const bool x3 = e->fp32x3;
+  const std::string mode = x3 ? "fp32x3_" : "fp32_";
+  auto launch = [&](const Fp32ConvArgs &a) { return x3 ? launch_conv_fp32x3(a, s) : launch_conv_fp32(a, s); };
   const double fB = (double)B;
   float *stem = F.stem + (size_t)w0 * e->Hs * e->Ws * 64;
   float *bott = F.bott + (size_t)w0 * e->Hb[0] * e->Wb[0] * 128;
@@ -453,13 +466,13 @@ static int encoder_run_range_fp32(tn_encoder *e, const void *x, tn_layout layout
   const double in_bytes = layout == TN_LAYOUT_NCHW_F32 ? 4 : layout == TN_LAYOUT_NHWC_F16 ? 2 : 1;
   {
     Fp32ConvArgs a{};
-    a.kind = FP32_STEM; a.x = x; a.layout = (int)layout; a.K = 147; a.w = F.stem_w; a.N = 64; a.es = F.stem_s; a.et = F.stem_t;
+    a.kind = FP32_STEM; a.x = x; a.layout = (int)layout; a.K = 147; a.w = F.stem_w; a.wx = F.stem_wx; a.N = 64; a.es = F.stem_s; a.et = F.stem_t;
     a.y = stem; a.ldy = 64; a.M = (long)B * e->Hs * e->Ws; a.H = e->H; a.W = e->W; a.Ho = e->Hs; a.Wo = e->Ws;
-    tm.begin("fp32_stem_conv7x7_bn_relu", 2.0 * a.M * 64 * 147, fB * e->H * e->W * 3 * in_bytes + a.M * 64 * 4.0);
-    rc = launch_conv_fp32(a, s);
+    tm.begin((mode + "stem_conv7x7_bn_relu").c_str(), 2.0 * a.M * 64 * 147, fB * e->H * e->W * 3 * in_bytes + a.M * 64 * 4.0);
+    rc = launch(a);
     tm.end();
     if (rc) return rc;
-    tm.begin("fp32_maxpool3x3s2", 0.0, a.M * 64 * 4.0 + fB * e->Hb[0] * e->Wb[0] * 64 * 4);
+    tm.begin((mode + "maxpool3x3s2").c_str(), 0.0, a.M * 64 * 4.0 + fB * e->Hb[0] * e->Wb[0] * 64 * 4);
     rc = launch_maxpool_fp32(stem, B, e->Hs, e->Ws, buf[0], e->Cb[0], e->Hb[0], e->Wb[0], s);
     tm.end();
     if (rc) return rc;
@@ -468,32 +481,32 @@ static int encoder_run_range_fp32(tn_encoder *e, const void *x, tn_layout layout
     const int Hh = e->Hb[b], Ww = e->Wb[b];
     const long M = (long)B * Hh * Ww;
     const std::string geo = std::to_string(Hh) + "x" + std::to_string(Ww);
-    const std::string f1 = "fp32_dense1x1_" + geo, f3 = "fp32_dense3x3_" + geo;
+    const std::string f1 = mode + "dense1x1_" + geo, f3 = mode + "dense3x3_" + geo;
     for (auto &L : F.layers[b]) {
       Fp32ConvArgs a1{};
-      a1.kind = FP32_1X1; a1.x = buf[b]; a1.ldx = e->Cb[b]; a1.K = L.cin; a1.s = L.s1; a1.t = L.t1; a1.w = L.w1; a1.N = 128;
+      a1.kind = FP32_1X1; a1.x = buf[b]; a1.ldx = e->Cb[b]; a1.K = L.cin; a1.s = L.s1; a1.t = L.t1; a1.w = L.w1; a1.wx = L.w1x; a1.N = 128;
       a1.y = bott; a1.ldy = 128; a1.M = M; a1.H = Hh; a1.W = Ww; a1.Ho = Hh; a1.Wo = Ww;
       tm.begin(f1.c_str(), 2.0 * M * 128 * L.cin, (double)M * (L.cin + 128) * 4 + 128.0 * L.cin * 4);
-      rc = launch_conv_fp32(a1, s);
+      rc = launch(a1);
       tm.end();
       if (rc) return rc;
       Fp32ConvArgs a3{};
-      a3.kind = FP32_3X3; a3.x = bott; a3.ldx = 128; a3.K = 9 * 128; a3.s = L.s2; a3.t = L.t2; a3.w = L.w3; a3.N = 32;
+      a3.kind = FP32_3X3; a3.x = bott; a3.ldx = 128; a3.K = 9 * 128; a3.s = L.s2; a3.t = L.t2; a3.w = L.w3; a3.wx = L.w3x; a3.N = 32;
       a3.y = buf[b]; a3.ldy = e->Cb[b]; a3.yoff = L.cin; a3.M = M; a3.H = Hh; a3.W = Ww; a3.Ho = Hh; a3.Wo = Ww;
       tm.begin(f3.c_str(), 2.0 * M * 32 * 1152, (double)M * (128 + 32) * 4 + 32.0 * 1152 * 4);
-      rc = launch_conv_fp32(a3, s);
+      rc = launch(a3);
       tm.end();
       if (rc) return rc;
     }
     if (b < 3) {
       auto &T = F.trans[b];
       Fp32ConvArgs at{};
-      at.kind = FP32_TRANS; at.x = buf[b]; at.ldx = e->Cb[b]; at.K = T.cin; at.s = T.s; at.t = T.t; at.w = T.w; at.N = T.cout;
+      at.kind = FP32_TRANS; at.x = buf[b]; at.ldx = e->Cb[b]; at.K = T.cin; at.s = T.s; at.t = T.t; at.w = T.w; at.wx = T.wx; at.N = T.cout;
       at.y = buf[b + 1]; at.ldy = e->Cb[b + 1]; at.M = (long)B * e->Hb[b + 1] * e->Wb[b + 1]; at.H = Hh; at.W = Ww;
       at.Ho = e->Hb[b + 1]; at.Wo = e->Wb[b + 1];
-      tm.begin(("fp32_transition_" + geo).c_str(), 2.0 * at.M * T.cout * T.cin,
+      tm.begin((mode + "transition_" + geo).c_str(), 2.0 * at.M * T.cout * T.cin,
                (double)M * T.cin * 4 + (double)at.M * T.cout * 4 + (double)T.cout * T.cin * 4);
-      rc = launch_conv_fp32(at, s);
+      rc = launch(at);
       tm.end();
       if (rc) return rc;
     }
@@ -512,7 +525,9 @@ extern "C" int tn_densenet121_create(tn_ctx *ctx, const tn_param *params, int n_
 extern "C" int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int n_params, const char *prefix_c,
                                         int height, int width, int max_batch, int flags, tn_encoder **out) {
   TN_REQUIRE(ctx && params && out && prefix_c, "tn_densenet121_create: null argument");
-  TN_REQUIRE((flags & ~(TN_ENC_EXACT_WEIGHTS | TN_ENC_FP32)) == 0, "tn_densenet121_create_ex: unknown flag");
+  TN_REQUIRE((flags & ~(TN_ENC_EXACT_WEIGHTS | TN_ENC_FP32 | TN_ENC_FP32X3)) == 0, "tn_densenet121_create_ex: unknown flag");
+  TN_REQUIRE((flags & (TN_ENC_FP32 | TN_ENC_FP32X3)) != (TN_ENC_FP32 | TN_ENC_FP32X3),
+             "tn_densenet121_create_ex: TN_ENC_FP32 and TN_ENC_FP32X3 are two modes, choose one");
   TN_REQUIRE(max_batch > 0, "tn_densenet121_create: max_batch must be positive");
   TN_REQUIRE(height >= 224 && width >= 224 && height <= 1024 && width <= 1024,
              "tn_densenet121_create: input size must be in [224,1024] (AvgPool2D(7) needs a >=7x7 final map)");
@@ -531,8 +546,9 @@ extern "C" int tn_densenet121_create_ex(tn_ctx *ctx, const tn_param *params, int
   e->block_stream[1] = getenv("TN_BLOCK28") != nullptr && atoi(getenv("TN_BLOCK28")) != 0;
   e->chain = getenv("TN_NO_CHAIN") == nullptr;   // measured: -20% on the 14x14 / 7x7 blocks, +2.8% end to end
   e->dl_variant = getenv("TN_DL_VARIANT") ? atoi(getenv("TN_DL_VARIANT")) : 0;
-  e->fp32 = (flags & TN_ENC_FP32) != 0;
-  e->exact = (flags & TN_ENC_EXACT_WEIGHTS) != 0 && !e->fp32;    // (TN_ENC_FP32 | TN_ENC_EXACT_WEIGHTS: the fp32 mode)
+  e->fp32x3 = (flags & TN_ENC_FP32X3) != 0;
+  e->fp32 = (flags & TN_ENC_FP32) != 0 || e->fp32x3;             // (the fp32x3 mode is the fp32 mode's network on another kernel)
+  e->exact = (flags & TN_ENC_EXACT_WEIGHTS) != 0 && !e->fp32;    // (TN_ENC_FP32 / TN_ENC_FP32X3 | TN_ENC_EXACT_WEIGHTS: that mode)
   e->strip = getenv("TN_NO_STRIP") == nullptr && !e->exact && e->fuse;
   if (getenv("TN_STRIP_MIN_BATCH")) e->strip_min_batch = atoi(getenv("TN_STRIP_MIN_BATCH"));
   e->strip_chain = getenv("TN_NO_STRIP_CHAIN") == nullptr;
@@ -1092,6 +1108,7 @@ extern "C" int tn_densenet121_input_means(tn_encoder *e, const void *x, tn_layou
                                           int64_t capacity, int64_t *numel) {
   TN_REQUIRE(e && x && means_host && numel, "tn_densenet121_input_means: null argument");
   TN_REQUIRE(batch > 0 && batch <= e->maxB, "tn_densenet121_input_means: batch exceeds max_batch");
+  TN_REQUIRE(!e->fp32x3, "tn_densenet121_input_means: not for an fp32x3-mode encoder (TN_ENC_FP32X3: no fp16 conversion to calibrate)");
   TN_REQUIRE(!e->fp32, "tn_densenet121_input_means: not for an fp32-mode encoder (TN_ENC_FP32: no fp16 conversion to calibrate)");
   TN_REQUIRE(!e->exact, "tn_densenet121_input_means: not for an exact-weights encoder");
   TN_ON_DEVICE(e->ctx->device);
@@ -1136,6 +1153,7 @@ extern "C" int tn_densenet121_input_means(tn_encoder *e, const void *x, tn_layou
 extern "C" int tn_densenet121_read_tap(tn_encoder *e, const char *tap_c, int batch, float *out_host, size_t capacity,
                                        size_t *numel) {
   TN_REQUIRE(e && tap_c && out_host && numel, "tn_densenet121_read_tap: null argument");
+  TN_REQUIRE(!e->fp32x3, "read_tap: not for an fp32x3-mode encoder (TN_ENC_FP32X3: its maps are fp32, the taps hand out fp16 maps)");
   TN_REQUIRE(!e->fp32, "read_tap: not for an fp32-mode encoder (TN_ENC_FP32: its maps are fp32, the taps hand out fp16 maps)");
   TN_REQUIRE(batch > 0 && batch <= e->last_batch, "tn_densenet121_read_tap: batch exceeds the last forward");
   const std::string tap(tap_c);

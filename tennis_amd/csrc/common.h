@@ -376,6 +376,7 @@ struct Fp32ConvArgs {
   int K;                 // reduction length: stem 147, 1x1 / transition the input channels, 3x3 9 * 128
   const float *s, *t;    // BatchNorm applied (then ReLU) to the operand as it is loaded: [K] (3x3: [128]); unused by the stem
   const float *w;        // [Kp][N] fp32, Kp = K rounded up to 32 with zero rows
+  const uint16_t *wx = nullptr;   // the fp32x3 kernel's B operand instead of w: fp32x3_pack_weights of that [Kp][N] array
   int N;                 // output channels (stem 64, 1x1 128, 3x3 32, transition cout)
   const float *es, *et;  // [N] epilogue BatchNorm + ReLU (the stem), nullptr: the raw product
   float *y;              // [M][ldy] fp32, columns [yoff, yoff + N)
@@ -385,5 +386,12 @@ struct Fp32ConvArgs {
   int Ho, Wo;            // output map size
 };
 int launch_conv_fp32(const Fp32ConvArgs &a, hipStream_t s);
+// ---- the fp32x3 encoder mode (TN_ENC_FP32X3, dense_fp32x3.hip): the same network, every fp32 operand as three bf16 terms, six
+// products per k-step on the bf16 MFMA.  tile: 0 = the tile launch_conv_fp32 would take, 1 = the small one, 2 = the large one.
+int launch_conv_fp32x3(const Fp32ConvArgs &a, hipStream_t s, int tile = 0);
+// w = t1 + t2 + t3 (to 2^-24 |w|), each a bf16 number: t1 = bf16(w), t2 = bf16(w - t1), t3 = bf16(w - t1 - t2), round to nearest even
+void fp32x3_split(const float *w, int64_t n, uint16_t *t1, uint16_t *t2, uint16_t *t3);
+// wk [kp][N] fp32 (kp a multiple of 32, N of 32) -> the three terms in the kernel's fragment order (3 kp N bf16)
+std::vector<uint16_t> fp32x3_pack_weights(const float *wk, int kp, int N);
 // 3x3 stride 2 pad 1 max pool of an fp32 [B][H][W][64] map into channels [0, 64) of a map with channel stride ldy
 int launch_maxpool_fp32(const float *x, int B, int H, int W, float *y, int ldy, int Ho, int Wo, hipStream_t s);

@@ -455,3 +455,41 @@ extern "C" int tn_dbg_bn_train(tn_ctx *ctx, const float *x, int ld, int64_t M, i
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
 }
+
+// ---- the fp32x3 encoder mode's kernel (dense_fp32x3.hip) and, on the same operands, the fp32 mode's (dense_fp32.hip) ----
+extern "C" int tn_dbg_conv_fp32x3(tn_ctx *ctx, int which, int kind, int tile, int layout, const void *x, int ldx, int K, const float *s,
+                                  const float *t, const float *w_host, int N, const float *es, const float *et, float *y, int ldy, int yoff,
+                                  int64_t M, int H, int W, int Ho, int Wo) {
+  TN_REQUIRE(ctx && x && w_host && y, "tn_dbg_conv_fp32x3: null argument");
+  TN_REQUIRE(which == 0 || which == 1, "tn_dbg_conv_fp32x3: which must be 0 (fp32x3) or 1 (fp32)");
+  TN_REQUIRE(which == 0 || tile == 0, "tn_dbg_conv_fp32x3: the fp32 kernel takes its launcher's tile");
+  TN_REQUIRE(kind >= FP32_STEM && kind <= FP32_TRANS, "tn_dbg_conv_fp32x3: unknown kind");
+  TN_REQUIRE(layout >= 0 && layout <= 2, "tn_dbg_conv_fp32x3: unknown input layout");
+  TN_REQUIRE(M > 0 && K > 0 && N > 0 && N % 32 == 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && M % ((int64_t)Ho * Wo) == 0,
+             "tn_dbg_conv_fp32x3: bad shape (M = B Ho Wo, N a multiple of 32)");
+  if (kind == FP32_STEM) {
+    TN_REQUIRE(K == 147 && es && et && Ho == (H - 1) / 2 + 1 && Wo == (W - 1) / 2 + 1, "tn_dbg_conv_fp32x3: the stem has K = 147, an epilogue and a ((H - 1) / 2 + 1) x ((W - 1) / 2 + 1) output");
+  } else {
+    TN_REQUIRE(s && t && !es && !et && K % 32 == 0 && ldx % 4 == 0, "tn_dbg_conv_fp32x3: s / t, no epilogue, K a multiple of 32");
+    TN_REQUIRE(kind == FP32_3X3 ? (K == 1152 && ldx == 128) : ldx >= K, "tn_dbg_conv_fp32x3: K beyond the channel stride (3x3: K = 1152, ldx = 128)");
+    TN_REQUIRE(kind == FP32_TRANS ? (2 * Ho <= H && 2 * Wo <= W) : (Ho == H && Wo == W), "tn_dbg_conv_fp32x3: output map size does not fit the input's");
+  }
+  TN_ON_DEVICE(ctx->device);
+  const int kp = (K + 31) / 32 * 32;
+  std::vector<float> wk((size_t)kp * N, 0.f);
+  memcpy(wk.data(), w_host, (size_t)K * N * sizeof(float));
+  float *wd = nullptr;
+  uint16_t *wx = nullptr;
+  if (which == 0) wx = up(fp32x3_pack_weights(wk.data(), kp, N));
+  else wd = up(wk);
+  TN_REQUIRE(wd || wx, "tn_dbg_conv_fp32x3: device allocation failed");
+  Fp32ConvArgs a{};
+  a.kind = kind; a.x = x; a.layout = layout; a.ldx = ldx; a.K = K; a.s = s; a.t = t; a.w = wd; a.wx = wx; a.N = N; a.es = es; a.et = et;
+  a.y = y; a.ldy = ldy; a.yoff = yoff; a.M = (long)M; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
+  const int rc = which == 0 ? launch_conv_fp32x3(a, ctx->stream, tile) : launch_conv_fp32(a, ctx->stream);
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(wd); (void)hipFree(wx);
+  if (rc) return rc;
+  TN_HIP_CHECK(e);
+  return TN_OK;
+}

@@ -41,20 +41,23 @@ class DenseNet121Features:
     """``get_model('DenseNet121').features`` on the GPU (reference evaluate.py:125)."""
 
     def __init__(self, params: dict, size: int | tuple = 224, max_batch: int = 256, prefix: str = "densenet0_",
-                 ctx: _lib.Context | None = None, exact_weights: bool = False, fp32: bool = False):
+                 ctx: _lib.Context | None = None, exact_weights: bool = False, fp32: bool = False, fp32x3: bool = False):
         """``exact_weights``: keep the fp32 convolution weights of the dense layers / transitions as hi + lo fp16
         pairs (TN_ENC_EXACT_WEIGHTS) instead of rounding them to fp16 once — for parameters that were NOT converted
         with ``weights.as_fp16_model`` (a trained fp32 checkpoint) and a 1e-3 agreement with their fp32 evaluation.
         ``fp32``: the fp32 mode (TN_ENC_FP32) - fp32 weights, fp32 activations, every product in fp32: the fp32 evaluation of
-        any checkpoint within 1e-3, at the f32 matrix rate; ``read_tap`` and ``input_means`` are not available."""
+        any checkpoint within 1e-3, at the f32 matrix rate; ``read_tap`` and ``input_means`` are not available.
+        ``fp32x3``: the fp32x3 mode (TN_ENC_FP32X3) - the fp32 mode's network and fp32 activations, every operand handed to the
+        bf16 matrix pipe as three bf16 terms (six products per k-step): the same bar for any checkpoint, faster; not together
+        with ``fp32``."""
         self.ctx = ctx or _lib.default_context()
         self.lib = self.ctx.lib
         self.size = (size, size) if isinstance(size, int) else tuple(size)
         self.max_batch = max_batch
         arr, keep = _lib.make_params({k: v for k, v in params.items() if k.startswith(prefix)})
         h = C.c_void_p()
-        self.exact_weights, self.fp32 = bool(exact_weights), bool(fp32)
-        flags = (_lib.ENC_EXACT_WEIGHTS if exact_weights else 0) | (_lib.ENC_FP32 if fp32 else 0)
+        self.exact_weights, self.fp32, self.fp32x3 = bool(exact_weights), bool(fp32), bool(fp32x3)
+        flags = (_lib.ENC_EXACT_WEIGHTS if exact_weights else 0) | (_lib.ENC_FP32 if fp32 else 0) | (_lib.ENC_FP32X3 if fp32x3 else 0)
         check(self.lib.tn_densenet121_create_ex(self.ctx.handle, arr, len(arr), prefix.encode(), self.size[0], self.size[1],
                                                 max_batch, flags, C.byref(h)),
               "tn_densenet121_create")

@@ -299,12 +299,13 @@ def best_or_newest_params(mod_path, need_scores):
 def build_parser():
     p = argparse.ArgumentParser(description="tennis_amd evaluate (flags of reference evaluate.py:30-75)")
     p.add_argument("--backbone", default="DenseNet121")
-    p.add_argument("--fp16_conversion", default="nearest", choices=["nearest", "calibrated", "exact", "fp32"],
+    p.add_argument("--fp16_conversion", default="nearest", choices=["nearest", "calibrated", "exact", "fp32", "fp32x3"],
                    help="how the checkpoint's fp32 conv weights become the fp16 model (not a reference flag): plain rounding, "
                         "rounding calibrated on the library's built-in calibration frames (the same model on every rank; features within "
                         "1e-3 of the fp32 evaluation on natural content at full speed, DESIGN.md), hi + lo weight pairs (twice the "
-                        "MFMAs), or fp32: no conversion, the network evaluated in fp32 (the fp32 evaluation of any checkpoint within "
-                        "1e-3, at the f32 matrix rate)")
+                        "MFMAs), fp32: no conversion, the network evaluated in fp32 (the fp32 evaluation of any checkpoint within "
+                        "1e-3, at the f32 matrix rate), or fp32x3: that fp32 network with every operand as three bf16 terms on the "
+                        "bf16 matrix pipe (the same bar, faster)")
     p.add_argument("--model_id", default="0000")
     p.add_argument("--split_id", default="02")
     p.add_argument("--split", default="test")
