@@ -136,6 +136,12 @@ int tn_dbg_gnmt_trainer_src_grad(tn_gnmt_trainer *t, const float *src, const int
                                  const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out,
                                  float *dsrc, int ldd);
 
+/* Which instantiation the recurrent kernels run for a shape (csrc/rnn.h rnn_route, the one policy of launch_rnn_recurrent and of the
+ * BPTT launchers of csrc/train.hip): gates 3 GRU / 4 LSTM, B batch rows, H hidden, dirs 1 | 2.  *nb rows per workgroup (1 | 4), *kr the
+ * register-resident prefix of a W_hh column (0 | 64 | 96 | 128; 0 at nb = 4; not read when *big), *big 1 for the registers + LDS +
+ * stream form (H = 256 at nb = 1).  Host arithmetic only: touches no device. */
+int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int *kr, int *big);
+
 /* One convolution of the fp32x3 encoder mode (csrc/dense_fp32x3.hip; which = 0) or, on the same operands, of the fp32 mode
  * (csrc/dense_fp32.hip; which = 1).  kind: 0 stem 7x7/2 (x: B frames in `layout`, H x W; epilogue relu(es y + et)), 1 dense 1x1,
  * 2 dense 3x3 (K = 1152, ldx = 128), 3 transition (2x2 average of relu(s x + t), then the 1x1); x an fp32 NHWC map (.., ldx), s / t

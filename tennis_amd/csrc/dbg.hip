@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "linear.h"
+#include "rnn.h"
 #include "train.h"
 
 namespace {
@@ -413,6 +414,18 @@ extern "C" int tn_dbg_gemm_nn(tn_ctx *ctx, const float *A, int lda, const float 
   const int rc = launch_gemm_nn_f32(A, lda, B, ldb, Cm, ldc, M, N, K, 0, ctx->stream);
   if (rc) return rc;
   TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+
+// The recurrent kernels' dispatch policy (rnn.h rnn_route: what launch_rnn_recurrent and train.hip's BPTT launchers both follow) for a
+// shape; host arithmetic only, no device is touched
+extern "C" int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int *kr, int *big) {
+  TN_REQUIRE(nb && kr && big, "tn_dbg_rnn_route: null argument");
+  TN_REQUIRE(gates == 3 || gates == 4, "tn_dbg_rnn_route: gates must be 3 or 4");
+  TN_REQUIRE(B > 0 && (dirs == 1 || dirs == 2) && H > 0 && gates * H <= 1024 && H % 4 == 0,
+             "tn_dbg_rnn_route: gates*hidden must be <= 1024, hidden % 4 == 0, batch > 0, dirs 1 or 2");
+  const tn_rnn_route r = rnn_route(gates, B, H, dirs);
+  *nb = r.nb; *kr = r.kr; *big = r.big;
   return TN_OK;
 }
 

@@ -275,10 +275,8 @@ int launch_rnn_recurrent(int gates, const float *gi, int ldgi, const float *whT,
   TN_REQUIRE(gates == 3 || gates == 4, "rnn: gates must be 3 or 4");
   TN_REQUIRE(gates * H <= 1024 && H % 4 == 0, "rnn: gates*hidden must be <= 1024 and hidden % 4 == 0");
   const int threads = gates * H;
-  // rows per workgroup: 4 when that still gives every CU a workgroup, else 1 (latency-bound small batches)
-  const int nb = ((B + 3) / 4) * dirs >= 256 ? 4 : 1;
-  // register-resident prefix of each weight column, bounded by the VGPR budget the block size leaves
-  const int kr = (threads <= 512 && H >= 128) ? 128 : (threads <= 768 && H >= 96) ? 96 : H >= 64 ? 64 : 0;
+  const tn_rnn_route route = rnn_route(gates, B, H, dirs);   // rows per workgroup / register-resident prefix / big form (rnn.h)
+  const int nb = route.nb, kr = route.kr;
   const dim3 grid((B + nb - 1) / nb, dirs), block(threads);
   const size_t lds = (size_t)(nb * H * 2 + nb * gates * H) * sizeof(float);
 #define TN_RNN_LAUNCH(G_, NB_, KR_, MT_)                                                                               \
@@ -292,7 +290,7 @@ int launch_rnn_recurrent(int gates, const float *gi, int ldgi, const float *whT,
     else TN_RNN_LAUNCH(G_, NB_, 0, 1024);                      \
   } while (0)
   // one row per workgroup and a column that does not fit the registers (H = 256): registers + LDS + stream, h through DPP
-  if (nb == 1 && H == 256) {
+  if (route.big) {
     constexpr int KR3 = 112, KL3 = 48, KR4 = 64, KL4 = 32;
     const int kl = gates == 3 ? KL3 : KL4;
     const size_t lds2 = (size_t)(2 * H + gates * H + kl * gates * H) * sizeof(float);

@@ -9,6 +9,7 @@
 // weight gradients are three transposed GEMMs over all B*T rows afterwards.
 #include "common.h"
 #include "train.h"
+#include "rnn.h"
 #include "rnn_dot.h"
 
 namespace {
@@ -517,16 +518,16 @@ int launch_scatter_pool_grad(const float *dpooled, const int32_t *arg, int B, in
                      F, dseq);
   TN_LAUNCH_CHECK();
 }
-// rows per workgroup / register-resident prefix: the same policy as launch_rnn_recurrent (rnn.hip)
+// rows per workgroup / register-resident prefix: rnn_route (rnn.h), the policy of launch_rnn_recurrent, whose `save` these kernels read
 #define TN_BPTT_DISPATCH(KERNEL, GATES, DIRS, ...)                                                                      \
   do {                                                                                                            \
     const int threads = GATES * H;                                                                                \
     TN_REQUIRE(threads <= 1024 && H % 4 == 0, "train: gates*hidden must be <= 1024 and hidden % 4 == 0");        \
-    const int nb = ((B + 3) / 4) * (DIRS) >= 256 ? 4 : 1;                                                              \
-    const int kr = (threads <= 512 && H >= 128) ? 128 : (threads <= 768 && H >= 96) ? 96 : H >= 64 ? 64 : 0;      \
+    const tn_rnn_route route = rnn_route(GATES, B, H, DIRS);                                                      \
+    const int nb = route.nb, kr = route.kr;                                                                       \
     const dim3 grid((B + nb - 1) / nb, DIRS), block(threads);                                                     \
     const size_t lds = (size_t)(nb * H * (GATES == 4 ? 2 : 1) + 2 * nb * GATES * H) * sizeof(float);              \
-    if (nb == 1 && H == 256) {   /* the column does not fit the registers: registers + LDS + stream (rnn_dot.h) */       \
+    if (route.big) {             /* the column does not fit the registers: registers + LDS + stream (rnn_dot.h) */       \
       constexpr int KRb = GATES == 3 ? 112 : 64, KLb = GATES == 3 ? 48 : 32, MTb = GATES == 3 ? 768 : 1024;              \
       const size_t lds2 = lds + (size_t)KLb * GATES * H * sizeof(float);                                                 \
       TN_SET_ATTR_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void *)KERNEL<1, KRb, MTb, KLb>,                      \

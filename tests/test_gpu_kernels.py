@@ -181,7 +181,9 @@ def test_linear(ctx, report, M, N, K):
                                                   # ragged tails (hidden % 16 != 0), four rows per workgroup
                                                   ("lstm", 2, 4, 16, 256, True), ("gru", 3, 5, 16, 32, False),
                                                   ("gru", 2, 4, 16, 100, True), ("lstm", 3, 4, 16, 84, False),
-                                                  ("gru", 520, 3, 8, 32, True), ("lstm", 516, 2, 8, 36, False)])
+                                                  ("gru", 520, 3, 8, 32, True), ("lstm", 516, 2, 8, 36, False),
+                                                  # H = 256 off the registers + LDS + stream form: four rows per workgroup
+                                                  ("gru", 516, 2, 8, 256, True), ("lstm", 516, 2, 8, 256, False)])
 def test_birnn(ctx, report, mode, B, T, F, H, use_vl):
     from tennis_amd import weights as Wt
     from tennis_amd.engine import BiRNN
