@@ -277,6 +277,17 @@ int tn_finetune_sgd_step(tn_finetune *f, float lr, float momentum, float wd, flo
 int tn_finetune_read_param(tn_finetune *f, const char *name, int gradient, float *out_host, int64_t capacity,
                            int64_t *numel);
 int tn_finetune_destroy(tn_finetune *f);
+/* The matrix pipe of the backbone's GEMMs (the convolutions of reference train.py:410-424's record / backward, as GEMMs: the stem, the
+ * 58 x 2 dense-layer convolutions and the 3 transitions forward, their weight and input gradients backward).  TN_MATMUL_F32, the
+ * default: the exact-f32 matrix instruction.  TN_MATMUL_FP32X3: fp32 operands, accumulators and results with every operand value
+ * split into three bf16 terms and the six largest cross products on the bf16 matrix pipe (csrc/gemm_fp32x3.hip) - the same
+ * float64 bars, a kernel error below 5e-7 of sum |a||b|; a value beyond bf16's finite range (3.39e38) splits to NaN.  The mode
+ * may change between steps; an unknown value is an error.  Not switched: the classifier, the recurrent head, the captioner.
+ * matmul_stats: backbone GEMM launches per mode since creation (a trainable step: 120 forward + 239 backward); either may be NULL. */
+#define TN_MATMUL_F32 0
+#define TN_MATMUL_FP32X3 1
+int tn_finetune_set_matmul(tn_finetune *f, int mode);
+int tn_finetune_matmul_stats(tn_finetune *f, int64_t *f32_launches, int64_t *fp32x3_launches);
 
 /* ---- end-to-end CNN-RNN training step ---------------------------- */
 /* CNNRNN(FrameModel(DenseNet-121 .features)) over TimeDistributed frames, trained as reference train.py:197-236 does with
@@ -307,6 +318,9 @@ int tn_cnnrnn_trainer_sgd_step(tn_cnnrnn_trainer *t, float lr, float momentum, f
 int tn_cnnrnn_trainer_read_param(tn_cnnrnn_trainer *t, const char *name, int gradient, float *out_host, int64_t capacity,
                                  int64_t *numel);
 int tn_cnnrnn_trainer_destroy(tn_cnnrnn_trainer *t);
+/* tn_finetune_set_matmul / _matmul_stats of the step's backbone (reference train.py:410-424); a frozen step counts its 120 forward launches */
+int tn_cnnrnn_trainer_set_matmul(tn_cnnrnn_trainer *t, int mode);
+int tn_cnnrnn_trainer_matmul_stats(tn_cnnrnn_trainer *t, int64_t *f32_launches, int64_t *fp32x3_launches);
 
 /* ---- captioner training step ---------------------------------- */
 /* One step of reference train_gnmt.py::train (:328-337) for GRU or LSTM cells (--cell_type), num_layers = 2,
@@ -382,6 +396,9 @@ int tn_gnmt_frames_trainer_adam_step(tn_gnmt_frames_trainer *t, float lr, float 
 int tn_gnmt_frames_trainer_read_param(tn_gnmt_frames_trainer *t, const char *name, int gradient, float *out_host,
                                       int64_t capacity, int64_t *numel);
 int tn_gnmt_frames_trainer_destroy(tn_gnmt_frames_trainer *t);
+/* tn_finetune_set_matmul / _matmul_stats of the step's backbone (reference train_gnmt.py:148-203); the captioner's own GEMMs stay f32 */
+int tn_gnmt_frames_trainer_set_matmul(tn_gnmt_frames_trainer *t, int mode);
+int tn_gnmt_frames_trainer_matmul_stats(tn_gnmt_frames_trainer *t, int64_t *f32_launches, int64_t *fp32x3_launches);
 
 /* ---- device PRF1 confusion histogram -------------------------------------- */
 /* Replaces the argmax + per-sample python loop of PRF1.update (reference

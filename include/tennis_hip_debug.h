@@ -122,6 +122,12 @@ int tn_dbg_gemm_tn(tn_ctx *ctx, const float *A, int lda, const float *B, int ldb
 /* Y (M, N; row stride ldy) (+)= relu(X asc[k] + ash[k]) W^T (+ bias), X (M, ldx), W (N, ldw); accumulate: add to Y. */
 int tn_dbg_linear_bnrelu(tn_ctx *ctx, const float *X, int ldx, const float *asc, const float *ash, const float *W, int ldw,
                          const float *bias, float *Y, int ldy, int M, int N, int K, int accumulate);
+/* The same two products through the fp32x3 launchers (csrc/gemm_fp32x3.hip), what the step runs in TN_MATMUL_FP32X3: the arguments
+ * of tn_dbg_linear_bnrelu (asc / ash NULL together: no operand transform) and of tn_dbg_gemm_tn. */
+int tn_dbg_linear_fp32x3(tn_ctx *ctx, const float *X, int ldx, const float *asc, const float *ash, const float *W, int ldw,
+                         const float *bias, float *Y, int ldy, int M, int N, int K, int accumulate);
+int tn_dbg_gemm_tn_fp32x3(tn_ctx *ctx, const float *A, int lda, const float *B, int ldb, const float *bsc, const float *bsh, float *Cm,
+                          int ldc, int M, int N, int K, float *workspace, int64_t workspace_floats);
 /* Training-mode BatchNorm + ReLU of an (M, C) matrix x of row stride ld >= C: mean / var (C each, biased), y (M, C contiguous).
  * dy (M, C contiguous) non-NULL: also dgamma, dbeta (C each) and dx (row stride ldd), assigned or accumulated. */
 /* C (M, N; row stride ldc) = A (M, K; row stride lda) B (K, N; row stride ldb), both row-major: the input gradient of the

@@ -23,6 +23,14 @@ ENC_FP32 = 4
 ENC_FP32X3 = 8
 RNN_GRU, RNN_LSTM = 0, 1
 POOL_MAX, POOL_MEAN = 0, 1
+MATMUL_MODES = {"f32": 0, "fp32x3": 1}      # TN_MATMUL_F32 / TN_MATMUL_FP32X3: the matrix pipe of the backbone training steps
+
+
+def matmul_mode(name) -> int:
+    """The TN_MATMUL_* value of a ``matmul=`` / ``--matmul`` name; touches neither the library nor a device."""
+    if name not in MATMUL_MODES:
+        raise ValueError(f"matmul must be 'f32' or 'fp32x3', got {name!r}")
+    return MATMUL_MODES[name]
 
 
 class TnParam(C.Structure):
@@ -89,6 +97,12 @@ _SIGS = {
     "tn_finetune_sgd_step": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float]),
     "tn_finetune_read_param": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
     "tn_finetune_destroy": (C.c_int, [_P]),
+    "tn_finetune_set_matmul": (C.c_int, [_P, C.c_int]),
+    "tn_finetune_matmul_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tn_cnnrnn_trainer_set_matmul": (C.c_int, [_P, C.c_int]),
+    "tn_cnnrnn_trainer_matmul_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tn_gnmt_frames_trainer_set_matmul": (C.c_int, [_P, C.c_int]),
+    "tn_gnmt_frames_trainer_matmul_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tn_cnnrnn_trainer_create": (C.c_int, [_P, C.c_int, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tn_cnnrnn_trainer_forward_backward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
@@ -150,6 +164,8 @@ _SIGS = {
     "tn_dbg_gemm_nn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_rnn_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tn_dbg_linear_bnrelu": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tn_dbg_linear_fp32x3": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tn_dbg_gemm_tn_fp32x3": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
     "tn_dbg_bn_train": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int]),
     "tn_comm_unique_id": (C.c_int, [_P]),
     "tn_comm_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(_P)]),

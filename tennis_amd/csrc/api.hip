@@ -1578,6 +1578,15 @@ extern "C" int tn_cnnrnn_trainer_read_param(tn_cnnrnn_trainer *t, const char *na
   return tn_finetune_read_param(t->bb, name, gradient, out_host, capacity, numel);
 }
 
+extern "C" int tn_cnnrnn_trainer_set_matmul(tn_cnnrnn_trainer *t, int mode) {
+  TN_REQUIRE(t, "tn_cnnrnn_trainer_set_matmul: null handle");
+  return tn_finetune_set_matmul(t->bb, mode);
+}
+extern "C" int tn_cnnrnn_trainer_matmul_stats(tn_cnnrnn_trainer *t, int64_t *f32_launches, int64_t *fp32x3_launches) {
+  TN_REQUIRE(t, "tn_cnnrnn_trainer_matmul_stats: null handle");
+  return tn_finetune_matmul_stats(t->bb, f32_launches, fp32x3_launches);
+}
+
 extern "C" int tn_cnnrnn_trainer_destroy(tn_cnnrnn_trainer *t) {
   if (!t) return TN_OK;
   tn_head_destroy(t->head);
@@ -1705,6 +1714,15 @@ extern "C" int tn_gnmt_frames_trainer_read_param(tn_gnmt_frames_trainer *t, cons
   if (n.rfind(t->bb_prefix, 0) == 0) return tn_finetune_read_param(t->bb, name, gradient, out_host, capacity, numel);
   TN_REQUIRE(n.rfind(t->prefix, 0) == 0, "tn_gnmt_frames_trainer_read_param: unknown parameter name");
   return tn_gnmt_trainer_read_param(t->cap, name, gradient, out_host, capacity, numel);
+}
+
+extern "C" int tn_gnmt_frames_trainer_set_matmul(tn_gnmt_frames_trainer *t, int mode) {
+  TN_REQUIRE(t, "tn_gnmt_frames_trainer_set_matmul: null handle");
+  return tn_finetune_set_matmul(t->bb, mode);
+}
+extern "C" int tn_gnmt_frames_trainer_matmul_stats(tn_gnmt_frames_trainer *t, int64_t *f32_launches, int64_t *fp32x3_launches) {
+  TN_REQUIRE(t, "tn_gnmt_frames_trainer_matmul_stats: null handle");
+  return tn_finetune_matmul_stats(t->bb, f32_launches, fp32x3_launches);
 }
 
 extern "C" int tn_gnmt_frames_trainer_destroy(tn_gnmt_frames_trainer *t) {

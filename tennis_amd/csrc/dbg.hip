@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gemm_fp32x3.h"
 #include "linear.h"
 #include "rnn.h"
 #include "train.h"
@@ -444,6 +445,28 @@ extern "C" int tn_dbg_linear_bnrelu(tn_ctx *ctx, const float *X, int ldx, const 
   TN_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= K && ldw >= K && ldy >= N, "tn_dbg_linear_bnrelu: bad shape");
   TN_ON_DEVICE(ctx->device);
   const int rc = launch_linear_f32_bnrelu(X, ldx, asc, ash, W, ldw, bias, Y, ldy, M, N, K, accumulate, ctx->stream);
+  if (rc) return rc;
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+
+// The fp32x3 twins of the two hooks above (gemm_fp32x3.hip), through the launchers the step calls in TN_MATMUL_FP32X3
+extern "C" int tn_dbg_linear_fp32x3(tn_ctx *ctx, const float *X, int ldx, const float *asc, const float *ash, const float *W, int ldw,
+                                    const float *bias, float *Y, int ldy, int M, int N, int K, int accumulate) {
+  TN_REQUIRE(ctx && X && W && Y && (asc == nullptr) == (ash == nullptr), "tn_dbg_linear_fp32x3: null argument");
+  TN_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= K && ldw >= K && ldy >= N, "tn_dbg_linear_fp32x3: bad shape");
+  TN_ON_DEVICE(ctx->device);
+  const int rc = launch_linear_fp32x3(X, ldx, asc, ash, W, ldw, bias, Y, ldy, M, N, K, accumulate, ctx->stream);
+  if (rc) return rc;
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+extern "C" int tn_dbg_gemm_tn_fp32x3(tn_ctx *ctx, const float *A, int lda, const float *B, int ldb, const float *bsc, const float *bsh,
+                                     float *Cm, int ldc, int M, int N, int K, float *workspace, int64_t workspace_floats) {
+  TN_REQUIRE(ctx && A && B && Cm && (bsc == nullptr) == (bsh == nullptr), "tn_dbg_gemm_tn_fp32x3: null argument");
+  TN_REQUIRE(M > 0 && N > 0 && K > 0 && lda >= M && ldb >= N && ldc >= N && workspace_floats >= 0, "tn_dbg_gemm_tn_fp32x3: bad shape");
+  TN_ON_DEVICE(ctx->device);
+  const int rc = launch_gemm_tn_fp32x3(A, lda, B, ldb, bsc, bsh, Cm, ldc, M, N, K, ctx->stream, workspace, workspace_floats);
   if (rc) return rc;
   TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return TN_OK;

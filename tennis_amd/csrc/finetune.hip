@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gemm_fp32x3.h"
 #include "linear.h"
 #include "train.h"
 
@@ -374,6 +375,8 @@ struct tn_finetune {
   float *ta, *tb, *col, *dcol, *tg, *tw, *ws;      // ws: split-K partial results / BatchNorm reduction slices
   long ws_floats;
   int32_t *labels;
+  int matmul = TN_MATMUL_F32;   // which matrix pipe the backbone's GEMMs run on (tn_finetune_set_matmul), changeable between steps
+  int64_t n_f32 = 0, n_x3 = 0;  // backbone GEMM launches per mode since creation (tn_finetune_matmul_stats)
 };
 
 // sc = gamma / sqrt(var + eps), sh = beta - mean * sc
@@ -607,6 +610,44 @@ extern "C" int tn_finetune_create(tn_ctx *ctx, const tn_param *params, int n_par
   return ft_create(ctx, params, n_params, backbone_prefix, dense_prefix, height, width, classes, batch, out, nullptr);
 }
 
+// The backbone's GEMMs, one dispatch helper per form: the handle's matmul mode picks the f32 launchers (linear.hip, train.hip - the
+// calls and arguments the step has always made) or their fp32x3 twins (gemm_fp32x3.hip), and the launch is counted.
+// Y (M, N; ldy) = f(X) W^T, f the identity (sc == nullptr) or relu(x sc[k] + sh[k])
+static int ft_linear(tn_finetune *f, const float *X, int ldx, const float *sc, const float *sh, const float *Wt, int ldw, float *Y, int ldy,
+                     int M, int N, int K, hipStream_t s) {
+  if (f->matmul == TN_MATMUL_FP32X3) {
+    ++f->n_x3;
+    return launch_linear_fp32x3(X, ldx, sc, sh, Wt, ldw, nullptr, Y, ldy, M, N, K, 0, s);
+  }
+  ++f->n_f32;
+  if (sc) return launch_linear_f32_bnrelu(X, ldx, sc, sh, Wt, ldw, nullptr, Y, ldy, M, N, K, 0, s);
+  return launch_linear_f32(X, ldx, Wt, ldw, nullptr, Y, ldy, M, N, K, 0, s);
+}
+// C (M, N; ldc) = A^T g(B) over K rows, g the identity (sc == nullptr) or relu(b sc[n] + sh[n]); split-K on the handle's workspace
+static int ft_gemm_tn(tn_finetune *f, const float *A, int lda, const float *Bm, int ldb, const float *sc, const float *sh, float *Cm, int ldc,
+                      int M, int N, int K, hipStream_t s) {
+  if (f->matmul == TN_MATMUL_FP32X3) {
+    ++f->n_x3;
+    return launch_gemm_tn_fp32x3(A, lda, Bm, ldb, sc, sh, Cm, ldc, M, N, K, s, f->ws, f->ws_floats);
+  }
+  ++f->n_f32;
+  if (sc) return launch_gemm_tn_f32_bnrelu(A, lda, Bm, ldb, sc, sh, Cm, ldc, M, N, K, s, f->ws, f->ws_floats);
+  return launch_gemm_tn_f32(A, lda, Bm, ldb, Cm, ldc, M, N, K, s, f->ws, f->ws_floats);
+}
+
+extern "C" int tn_finetune_set_matmul(tn_finetune *f, int mode) {
+  TN_REQUIRE(f, "tn_finetune_set_matmul: null handle");
+  TN_REQUIRE(mode == TN_MATMUL_F32 || mode == TN_MATMUL_FP32X3, "tn_finetune_set_matmul: mode must be TN_MATMUL_F32 (0) or TN_MATMUL_FP32X3 (1)");
+  f->matmul = mode;
+  return TN_OK;
+}
+extern "C" int tn_finetune_matmul_stats(tn_finetune *f, int64_t *f32_launches, int64_t *fp32x3_launches) {
+  TN_REQUIRE(f, "tn_finetune_matmul_stats: null handle");
+  if (f32_launches) *f32_launches = f->n_f32;
+  if (fp32x3_launches) *fp32x3_launches = f->n_x3;
+  return TN_OK;
+}
+
 // The step in three parts (train.h), on the handle's stream; launch errors are peeked at by the launchers and checked once by the caller.
 // Forward of x (B, H, W, 3) through the backbone in training mode, batch statistics of every BatchNorm -> ft_features (B, 1024 ...)
 int ft_forward_features(tn_finetune *f, const float *x, int n) {
@@ -618,7 +659,7 @@ int ft_forward_features(tn_finetune *f, const float *x, int n) {
   int rc;
 #define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
   hipLaunchKernelGGL(ft_im2col7_kernel, dim3(nblk(M0 * 49)), dim3(256), 0, s, x, B, H, W, f->col7);
-  TN_TRY(launch_linear_f32(f->col7, 147, w + f->o_w0, 147, nullptr, f->z0, 64, (int)M0, 64, 147, 0, s));
+  TN_TRY(ft_linear(f, f->col7, 147, nullptr, nullptr, w + f->o_w0, 147, f->z0, 64, (int)M0, 64, 147, s));
   ft_bn_forward(f, f->bn0, f->z0, 64, M0, f->a0, s);
   hipLaunchKernelGGL(ft_maxpool_kernel, dim3(nblk((long)B * f->Hb[0] * f->Hb[0] * 64)), dim3(256), 0, s, (const float *)f->a0, B, H / 2, W / 2, 64,
                      f->X[0], f->Ctot[0]);
@@ -631,18 +672,18 @@ int ft_forward_features(tn_finetune *f, const float *x, int n) {
     const long M = (long)B * Hh * Hh;
     for (auto &L : f->layers[b]) {
       ft_bn_fold(f, L.bn1, s);
-      TN_TRY(launch_linear_f32_bnrelu(f->X[b], Ct, L.bn1.sc, L.bn1.sh, w + L.o_w1, L.K, nullptr, L.z1, 128, (int)M, 128, L.K, 0, s));
+      TN_TRY(ft_linear(f, f->X[b], Ct, L.bn1.sc, L.bn1.sh, w + L.o_w1, L.K, L.z1, 128, (int)M, 128, L.K, s));
       ft_stats(f, L.z1, 128, M, 128, L.bn2.mean, L.bn2.var, s);
       ft_bn_fold(f, L.bn2, s);
       hipLaunchKernelGGL(ft_im2col3_kernel, dim3(nblk(M * 9 * 32)), dim3(256), 0, s, (const float *)L.z1, B, Hh, Hh, 128, f->col,
                          (const float *)L.bn2.sc, (const float *)L.bn2.sh);
-      TN_TRY(launch_linear_f32(f->col, 1152, w + L.o_w3, 1152, nullptr, f->X[b] + L.K, Ct, (int)M, 32, 1152, 0, s));
+      TN_TRY(ft_linear(f, f->col, 1152, nullptr, nullptr, w + L.o_w3, 1152, f->X[b] + L.K, Ct, (int)M, 32, 1152, s));
       ft_stats(f, f->X[b] + L.K, Ct, M, 32, f->Xmean[b] + L.K, f->Xvar[b] + L.K, s);
     }
     if (b < 3) {
       FtTrans &T = f->trans[b];
       ft_bn_fold(f, T.bn, s);
-      TN_TRY(launch_linear_f32_bnrelu(f->X[b], Ct, T.bn.sc, T.bn.sh, w + T.o_w, T.Cin, nullptr, T.z, T.Cout, (int)M, T.Cout, T.Cin, 0, s));
+      TN_TRY(ft_linear(f, f->X[b], Ct, T.bn.sc, T.bn.sh, w + T.o_w, T.Cin, T.z, T.Cout, (int)M, T.Cout, T.Cin, s));
       hipLaunchKernelGGL(ft_avgpool2_kernel, dim3(nblk(M / 4 * T.Cout)), dim3(256), 0, s, (const float *)T.z, B, Hh, Hh, T.Cout, f->X[b + 1],
                          f->Ctot[b + 1]);
       ft_stats(f, f->X[b + 1], f->Ctot[b + 1], M / 4, T.Cout, f->Xmean[b + 1], f->Xvar[b + 1], s);
@@ -676,15 +717,15 @@ int ft_backward_features(tn_finetune *f, int n) {
       // 3x3: dW3 = dy^T col ; dcol = dy W3 ; col2im
       hipLaunchKernelGGL(ft_im2col3_kernel, dim3(nblk(M * 9 * 32)), dim3(256), 0, s, (const float *)L.z1, B, Hh, Hh, 128, f->col,
                          (const float *)L.bn2.sc, (const float *)L.bn2.sh);
-      TN_TRY(launch_gemm_tn_f32(dy, Ct, f->col, 1152, g + L.o_w3, 1152, 32, 1152, (int)M, s, f->ws, f->ws_floats));
+      TN_TRY(ft_gemm_tn(f, dy, Ct, f->col, 1152, nullptr, nullptr, g + L.o_w3, 1152, 32, 1152, (int)M, s));
       TN_TRY(launch_transpose_f32(w + L.o_w3, 32, 1152, f->tw, s));                      // (1152, 32)
-      TN_TRY(launch_linear_f32(dy, Ct, f->tw, 32, nullptr, f->dcol, 1152, (int)M, 1152, 32, 0, s));
+      TN_TRY(ft_linear(f, dy, Ct, nullptr, nullptr, f->tw, 32, f->dcol, 1152, (int)M, 1152, 32, s));
       hipLaunchKernelGGL(ft_col2im3_kernel, dim3(nblk(M * 32)), dim3(256), 0, s, (const float *)f->dcol, B, Hh, Hh, 128, f->tg);
       ft_bn_backward(f, L.bn2, f->tg, L.z1, 128, M, f->tb, 128, 0, s);                  // tb = d z1
       // 1x1: dW1 = dz1^T a ; da = dz1 W1
-      TN_TRY(launch_gemm_tn_f32_bnrelu(f->tb, 128, f->X[b], Ct, L.bn1.sc, L.bn1.sh, g + L.o_w1, L.K, 128, L.K, (int)M, s, f->ws, f->ws_floats));
+      TN_TRY(ft_gemm_tn(f, f->tb, 128, f->X[b], Ct, L.bn1.sc, L.bn1.sh, g + L.o_w1, L.K, 128, L.K, (int)M, s));
       TN_TRY(launch_transpose_f32(w + L.o_w1, 128, L.K, f->tw, s));                     // (K, 128)
-      TN_TRY(launch_linear_f32(f->tb, 128, f->tw, 128, nullptr, f->tg, L.K, (int)M, L.K, 128, 0, s));
+      TN_TRY(ft_linear(f, f->tb, 128, nullptr, nullptr, f->tw, 128, f->tg, L.K, (int)M, L.K, 128, s));
       ft_bn_backward(f, L.bn1, f->tg, f->X[b], Ct, M, f->dX[b], Ct, 1, s);               // accumulate into channels [0, K)
     }
     if (b > 0) {
@@ -692,10 +733,9 @@ int ft_backward_features(tn_finetune *f, int n) {
       const int Hp = f->Hb[b - 1], Cp = f->Ctot[b - 1];
       const long Mp = (long)B * Hp * Hp;
       hipLaunchKernelGGL(ft_avgpool2_bwd_kernel, dim3(nblk(Mp * T.Cout)), dim3(256), 0, s, (const float *)f->dX[b], Ct, B, Hp, Hp, T.Cout, f->tb);
-      TN_TRY(launch_gemm_tn_f32_bnrelu(f->tb, T.Cout, f->X[b - 1], Cp, T.bn.sc, T.bn.sh, g + T.o_w, T.Cin, T.Cout, T.Cin, (int)Mp, s, f->ws,
-                                       f->ws_floats));
+      TN_TRY(ft_gemm_tn(f, f->tb, T.Cout, f->X[b - 1], Cp, T.bn.sc, T.bn.sh, g + T.o_w, T.Cin, T.Cout, T.Cin, (int)Mp, s));
       TN_TRY(launch_transpose_f32(w + T.o_w, T.Cout, T.Cin, f->tw, s));                  // (Cin, Cout)
-      TN_TRY(launch_linear_f32(f->tb, T.Cout, f->tw, T.Cout, nullptr, f->tg, T.Cin, (int)Mp, T.Cin, T.Cout, 0, s));
+      TN_TRY(ft_linear(f, f->tb, T.Cout, nullptr, nullptr, f->tw, T.Cout, f->tg, T.Cin, (int)Mp, T.Cin, T.Cout, s));
       ft_bn_backward(f, T.bn, f->tg, f->X[b - 1], Cp, Mp, f->dX[b - 1], Cp, 0, s);
     } else {
       // stem: maxpool -> BN+ReLU -> conv 7x7 (its input gradient is not needed)
@@ -703,7 +743,7 @@ int ft_backward_features(tn_finetune *f, int n) {
       hipLaunchKernelGGL(ft_maxpool_bwd_kernel, dim3(nblk(M0 * 64)), dim3(256), 0, s, (const float *)f->a0, (const float *)f->dX[0], Ct, B, H / 2,
                          W / 2, 64, f->tg);
       ft_bn_backward(f, f->bn0, f->tg, f->z0, 64, M0, f->tb, 64, 0, s);
-      TN_TRY(launch_gemm_tn_f32(f->tb, 64, f->col7, 147, g + f->o_w0, 147, 64, 147, (int)M0, s, f->ws, f->ws_floats));
+      TN_TRY(ft_gemm_tn(f, f->tb, 64, f->col7, 147, nullptr, nullptr, g + f->o_w0, 147, 64, 147, (int)M0, s));
     }
   }
   return TN_OK;

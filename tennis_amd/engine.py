@@ -514,14 +514,35 @@ class GNMTTrainer:
             pass
 
 
-class FrameModelTrainer:
+class _BackboneMatmul:
+    """``matmul`` of the three backbone trainers: which matrix pipe the backbone's GEMMs run on.  ``"f32"`` (the default) is the
+    exact-f32 matrix instruction; ``"fp32x3"`` keeps fp32 operands, accumulators and results and forms every product from three
+    bf16 terms per operand on the bf16 matrix pipe (csrc/gemm_fp32x3.hip) - the same float64 bars.  ``_MATMUL_ABI`` names the
+    handle's C entry points."""
+
+    def set_matmul(self, name: str):
+        mode = _lib.matmul_mode(name)
+        fn = getattr(self.lib, self._MATMUL_ABI + "_set_matmul")
+        check(fn(self.handle, mode), self._MATMUL_ABI + "_set_matmul")
+        self.matmul = name
+
+    def matmul_stats(self) -> tuple:
+        """Backbone GEMM launches since construction: (f32, fp32x3)"""
+        a, b = C.c_int64(), C.c_int64()
+        fn = getattr(self.lib, self._MATMUL_ABI + "_matmul_stats")
+        check(fn(self.handle, C.byref(a), C.byref(b)), self._MATMUL_ABI + "_matmul_stats")
+        return a.value, b.value
+
+
+class FrameModelTrainer(_BackboneMatmul):
     """End-to-end fine-tuning step of ``FrameModel(DenseNet121.features, classes)`` the way reference train.py drives it
     with an un-frozen backbone: BatchNorm in training mode, ``SoftmaxCrossEntropyLoss`` per sample (:324), backward of the
     summed losses (:419-421), ``gluon.Trainer('sgd', {lr, momentum, wd}).step(batch_size)`` (:298-299,424).  fp32.  The batch
     size is fixed at construction (BatchNorm statistics are per batch)."""
 
     def __init__(self, params: dict, size: int = 224, classes: int = 11, batch: int = 8, prefix: str = "densenet0_",
-                 dense_prefix: str = "framemodel0_dense0_", ctx: _lib.Context | None = None):
+                 dense_prefix: str = "framemodel0_dense0_", ctx: _lib.Context | None = None, matmul: str = "f32"):
+        _lib.matmul_mode(matmul)                       # a wrong name raises before a context or the library is touched
         self.ctx = ctx or _lib.default_context()
         self.lib = self.ctx.lib
         self.size, self.classes, self.batch = size, classes, batch
@@ -536,6 +557,9 @@ class FrameModelTrainer:
         pw, pg, n = C.c_void_p(), C.c_void_p(), C.c_int64()
         check(self.lib.tn_finetune_buffers(h, C.byref(pw), C.byref(pg), C.byref(n)), "tn_finetune_buffers")
         self.numel, self._pw, self._pg = n.value, pw.value, pg.value
+        self.set_matmul(matmul)
+
+    _MATMUL_ABI = "tn_finetune"
 
     def _view(self, addr):
         class _Arr:
@@ -589,7 +613,7 @@ class FrameModelTrainer:
             pass
 
 
-class CNNRNNTrainer:
+class CNNRNNTrainer(_BackboneMatmul):
     """End-to-end training step of ``CNNRNN(FrameModel(DenseNet121.features))`` over ``TimeDistributed`` frames, the way reference
     train.py:197-236 drives it with ``--window > 1 --temp_pool gru|lstm`` and no ``--feats_model``: the backbone's BatchNorms in
     training mode over all batch x steps frames, bi-GRU / bi-LSTM -> max over T -> Dense, ``SoftmaxCrossEntropyLoss`` per sample
@@ -603,7 +627,8 @@ class CNNRNNTrainer:
 
     def __init__(self, params: dict, size: int = 224, classes: int = 11, batch: int = 2, steps: int = 8, type: str = "gru",
                  prefix: str = "densenet0_", rnn_prefix: str | None = None, dense_prefix: str = "cnnrnn0_dense0_",
-                 freeze_backbone: bool = False, ctx: _lib.Context | None = None):
+                 freeze_backbone: bool = False, ctx: _lib.Context | None = None, matmul: str = "f32"):
+        _lib.matmul_mode(matmul)                       # a wrong name raises before a context or the library is touched
         if type not in ("gru", "lstm"):
             raise ValueError(f"type must be 'gru' or 'lstm', got {type!r}")
         if rnn_prefix is None:
@@ -627,6 +652,9 @@ class CNNRNNTrainer:
               "tn_cnnrnn_trainer_buffers")
         self._bb = (bw.value, bg.value, bn.value)
         self._head = (hw.value, hg.value, hn.value)
+        self.set_matmul(matmul)
+
+    _MATMUL_ABI = "tn_cnnrnn_trainer"
 
     def _view(self, addr, n):
         class _Arr:
@@ -685,7 +713,7 @@ class CNNRNNTrainer:
             pass
 
 
-class GNMTFramesTrainer:
+class GNMTFramesTrainer(_BackboneMatmul):
     """One frame-mode training step of the captioner, the way reference train_gnmt.py drives it without ``--feats_model``
     (:148-203, 328-337): ``src_embed = TimeDistributed(FrameModel(DenseNet121.features).backbone)`` inside the ``NMTModel``, so the
     backbone runs in training mode over all batch x steps frames of the padded clips and is trained - or, with ``freeze_backbone``
@@ -702,7 +730,8 @@ class GNMTFramesTrainer:
     def __init__(self, params: dict, hidden: int, embed: int, vocab: int, size: int = 224, max_batch: int = 4, max_src_len: int = 16,
                  max_tgt_len: int = 64, max_frames: int | None = None, prefix: str = "gnmt_", backbone_prefix: str = "densenet0_",
                  freeze_backbone: bool = False, ctx: _lib.Context | None = None, cell_type: str = "gru", num_layers: int = 2,
-                 num_bi_layers: int = 1, use_residual: bool = False):
+                 num_bi_layers: int = 1, use_residual: bool = False, matmul: str = "f32"):
+        _lib.matmul_mode(matmul)                       # a wrong name raises before a context or the library is touched
         if cell_type not in ("gru", "lstm"):
             raise ValueError(f"cell_type must be 'gru' or 'lstm', got {cell_type!r}")
         self.ctx = ctx or _lib.default_context()
@@ -728,6 +757,9 @@ class GNMTFramesTrainer:
               "tn_gnmt_frames_trainer_buffers")
         self._bb = (bw.value, bg.value, bn.value)
         self._cap = (cw.value, cg.value, cn.value)
+        self.set_matmul(matmul)
+
+    _MATMUL_ABI = "tn_gnmt_frames_trainer"
 
     def _view(self, addr, n):
         class _Arr:

@@ -147,6 +147,9 @@ def check_frames_route(flags):
     """The end-to-end routes on frames (no ``--feats_model``): ``--window 1`` (the frame classifier) or ``--window > 1`` with
     ``--temp_pool gru|lstm`` (CNNRNN).  Anything else exits with the reason."""
     if flags.feats_model is not None:
+        if getattr(flags, "matmul", "f32") != "f32":
+            raise SystemExit("--matmul fp32x3 switches the backbone's GEMMs; with --feats_model there is no backbone in the step "
+                             "(the temporal head trains on stored features)")
         return
     if flags.window < 1:
         raise SystemExit("--window must be at least 1")
@@ -181,6 +184,9 @@ def build_parser():
     p.add_argument("--momentum", type=float, default=0.9)
     p.add_argument("--wd", type=float, default=0.0001)
     p.add_argument("--feats_model", default=None)
+    p.add_argument("--matmul", default="f32", choices=["f32", "fp32x3"],
+                   help="matrix pipe of the backbone's GEMMs when training on frames: f32 (exact-f32 MFMA) or fp32x3 (fp32 values as "
+                        "three bf16 terms on the bf16 MFMA, same float64 bars; not a reference flag)")
     # the rest of the reference's flags (train.py:32-93), accepted so that its command lines parse unchanged
     p.add_argument("--backbone_from_id", default=None, help="start the frame model from the newest .params of this model id (train.py:222-235)")
     p.add_argument("--log_interval", type=int, default=100)
@@ -274,7 +280,8 @@ def main(argv=None):
         last = "discard"
         mk_head = lambda p: CNNRNNTrainer(p, flags.data_shape, n_cls, batch=local_bs, steps=flags.window, type=flags.temp_pool,
                                           prefix=model.td.model.prefix, rnn_prefix=model.rnn.prefix,
-                                          dense_prefix=model.classes.prefix, freeze_backbone=flags.freeze_backbone)
+                                          dense_prefix=model.classes.prefix, freeze_backbone=flags.freeze_backbone,
+                                          matmul=flags.matmul)
     else:
         model = FrameModel(get_model(flags.backbone, pretrained=True).features, n_cls)
         model.initialize()
@@ -286,7 +293,7 @@ def main(argv=None):
                 print("Loaded backbone params: {}".format(bb))
         last = "discard"
         mk_head = lambda p: FrameModelTrainer(p, flags.data_shape, n_cls, batch=local_bs, prefix=model.backbone.prefix,
-                                              dense_prefix=model.classes.prefix)
+                                              dense_prefix=model.classes.prefix, matmul=flags.matmul)
     # resume from the newest NNNN.params of the experiment (train.py:286-295)
     start_epoch = 0
     newest = newest_params(save_dir)
@@ -295,6 +302,8 @@ def main(argv=None):
         start_epoch = int(os.path.basename(newest).split(".")[0]) + 1
         print("Loaded model params: {}".format(newest))
     head = mk_head({k: v.data for k, v in model.collect_params().items()})
+    if flags.feats_model is None and is_main_rank():
+        print("Backbone matmul: {}".format(head.matmul))
     train_data = DataLoader(train_set, flags.batch_size, shuffle=True, last_batch=last, num_workers=flags.num_workers)
     val_data = DataLoader(val_set, flags.batch_size, shuffle=False, num_workers=flags.num_workers)
     trainer = Trainer(head, "sgd", {"learning_rate": flags.lr, "momentum": flags.momentum, "wd": flags.wd})

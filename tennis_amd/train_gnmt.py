@@ -58,10 +58,10 @@ def allreduce_grads(trainer, n_tokens: int):
 def train(data_train, data_val, data_test, model, translator, epochs: int, batch_size: int, lr: float = 1e-3,
           lr_update_factor: float = 0.5, dropout: float = 0.0, num_buckets: int = 5, test_batch_size: int = 32,
           start_epoch: int = 0, save_dir: str | None = None, seed: int = 0, log=print, freeze_backbone: bool = False,
-          frame_size: int | None = None):
+          frame_size: int | None = None, matmul: str = "f32"):
     """-> history: one dict per epoch (train loss, valid / test loss and BLEU, learning rate).  A model with a ``src_embed`` trains on
     frames (``GNMTFramesTrainer``: the backbone inside the step, frozen or trainable); its checkpoints carry the backbone under the
-    model's structural names (``src_embed.model. ...``)."""
+    model's structural names (``src_embed.model. ...``).  ``matmul``: the matrix pipe of that backbone's GEMMs ("f32" | "fp32x3")."""
     enc = model.encoder
     if enc._cell_type not in ("gru", "lstm"):
         raise NotImplementedError("the training step is built for GRU / LSTM cells")
@@ -87,8 +87,11 @@ def train(data_train, data_val, data_test, model, translator, epochs: int, batch
         trainer = GNMTFramesTrainer(params, enc._hidden_size, model._embed_size, len(model.tgt_vocab), size=side, max_batch=batch_size,
                                     max_src_len=max_t, max_tgt_len=max_l, max_frames=frame_capacity(data_train, batch_size, num_buckets),
                                     prefix=model.prefix, backbone_prefix=model.src_embed.model.prefix, freeze_backbone=freeze_backbone,
-                                    **cell)
+                                    matmul=matmul, **cell)
+        log("Backbone matmul: {}".format(trainer.matmul))
     else:
+        if matmul != "f32":
+            raise ValueError("matmul='fp32x3' switches the backbone's GEMMs; a model without src_embed trains on features and has no backbone")
         trainer = GNMTTrainer(params, model._input_size, enc._hidden_size, model._embed_size, len(model.tgt_vocab),
                               max_batch=batch_size, max_src_len=max_t, max_tgt_len=max_l, prefix=model.prefix, **cell)
     if dropout > 0:
@@ -187,6 +190,9 @@ def build_parser():
     p.add_argument("--backbone", default="DenseNet121")
     p.add_argument("--backbone_from_id", default=None, help="frame mode only (the CNN inside the model); ignored with --feats_model, as in the reference")
     p.add_argument("--freeze_backbone", action="store_true")
+    p.add_argument("--matmul", default="f32", choices=["f32", "fp32x3"],
+                   help="frame mode: matrix pipe of the backbone's GEMMs, f32 (exact-f32 MFMA) or fp32x3 (fp32 values as three bf16 terms on "
+                        "the bf16 MFMA, same float64 bars; not a reference flag)")
     p.add_argument("--data_shape", type=int, default=512)
     p.add_argument("--feature_dim", type=int, default=1024, help="width of the pre-extracted frame features (feats_model)")
     p.add_argument("--n_points", type=int, default=64, help="synthetic source: points per split")
@@ -286,6 +292,9 @@ def build_backbone(flags):
 
 def main(argv=None):
     flags = build_parser().parse_args(argv)
+    if flags.matmul != "f32" and (flags.feats_model is not None or (flags.data_root is None and not flags.frames)):
+        raise SystemExit("--matmul fp32x3 switches the backbone's GEMMs; with --feats_model (or synthetic features) there is no backbone "
+                         "in the step - the captioner trains on stored features")
     data_train, data_val, data_test, model, translator = build(flags)
     save_dir = os.path.join(flags.root, flags.model_id)
     os.makedirs(save_dir, exist_ok=True)
@@ -302,7 +311,7 @@ def main(argv=None):
     hist = train(data_train, data_val, data_test, model, translator, flags.epochs, flags.batch_size, lr=flags.lr,
                  lr_update_factor=flags.lr_update_factor, dropout=flags.dropout, num_buckets=flags.num_buckets,
                  test_batch_size=flags.test_batch_size, start_epoch=start_epoch, save_dir=save_dir,
-                 freeze_backbone=flags.freeze_backbone, frame_size=flags.data_shape if getattr(model, "src_embed", None) is not None else None)
+                 freeze_backbone=flags.freeze_backbone, matmul=flags.matmul, frame_size=flags.data_shape if getattr(model, "src_embed", None) is not None else None)
     if not hist:
         print("[Finished] nothing to do: {} epochs are on disk".format(start_epoch))
         return 0
