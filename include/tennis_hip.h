@@ -239,6 +239,32 @@ int tn_jpeg_destroy(tn_jpeg *j);
 int tn_temporal_pool(tn_ctx *ctx, const float *x, int batch, int steps, int feat, tn_pool_kind kind,
                      float *y);
 
+/* ---- dense windowed evaluation of the temporal heads ------------------------ */
+/* Replaces the evaluation loop of reference evaluate.py:274-303 for `--feats_model M --window W --temp_pool gru|lstm`
+ * (model 0042): TennisSet.__getitem__ loading the W feature files of every sample (dataset.py:190-201,206-213), the
+ * loader stacking them to (B, W, F), and CNNRNN.forward in feature mode (models/vision/definitions.py:94-96,106-109:
+ * bi-GRU / bi-LSTM -> F.max(axis=1) -> Dense).  Here the (rows, F) feature matrix stays on the device, its i2h projection
+ * runs once per row (project), and forward gathers every sample's window inside the recurrent kernel: step t of sample b
+ * reads row clamp(centre[b] + (t - window/2) * stride, lo[b], hi[b]) - dataset.py:190-201 in units of matrix rows, the
+ * offsets range(int(-w/2), ceil(w/2)) - clamped once more to [0, rows-1], so no content of the index arrays reads outside.
+ * Neither (samples, W, F) nor the (samples, W, 2H) sequence is materialised.  Parameters as tn_head_create.
+ * project: feats (rows, F) fp32 DEVICE, rows <= max_rows; one project serves any number of forward calls.
+ * forward: centre / lo / hi (samples,) int32 DEVICE, samples <= max_samples; pooled (samples, 2H) fp32 or NULL, logits
+ * (samples, classes) fp32, DEVICE.  forward before project, nulls, rows / samples over the handle's limits and window or
+ * stride < 1 are TN_ERR_INVALID.  Neither call allocates. */
+typedef struct tn_window_head tn_window_head;
+int tn_window_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int hidden, int classes, const tn_param *params,
+                          int n_params, const char *rnn_prefix, const char *dense_prefix, int max_rows, int max_samples,
+                          tn_window_head **out);
+int tn_window_head_project(tn_window_head *h, const float *feats, int rows);
+int tn_window_head_forward(tn_window_head *h, const int32_t *centre, const int32_t *lo, const int32_t *hi, int samples,
+                           int window, int stride, float *pooled, float *logits);
+int tn_window_head_destroy(tn_window_head *h);
+/* TemporalPooling.forward in feature mode over the same windows (definitions.py:66-69 on the (B, W, F) batch of
+ * dataset.py:190-213): feats (rows, feat) -> y (samples, feat), max or mean over the window's gathered rows. */
+int tn_temporal_pool_windows(tn_ctx *ctx, const float *feats, int rows, int feat, const int32_t *centre, const int32_t *lo,
+                             const int32_t *hi, int samples, int window, int stride, tn_pool_kind kind, float *y);
+
 /* ---- temporal-head training step ------------------------------ */
 /* bi-GRU / bi-LSTM(hidden) (`kind`; CNNRNN type='gru'|'lstm', definitions.py:93-96; LSTM gates [i,f,g,o]) over
  * features -> max over T -> Dense(classes) -> SoftmaxCrossEntropyLoss, backward, SGD with

@@ -159,6 +159,10 @@ int tn_dbg_conv_fp32x3(tn_ctx *ctx, int which, int kind, int tile, int layout, c
                        const float *w_host, int N, const float *es, const float *et, float *y, int ldy, int yoff, int64_t M, int H, int W,
                        int Ho, int Wo);
 
+/* Tuning hook of the windowed recurrent kernel (csrc/rnn_window.hip): the samples one workgroup walks - 0 the library's choice,
+ * 4, or twice the gates (6 GRU / 8 LSTM).  The results do not depend on it (scripts/bench_window_head.py measures both). */
+int tn_dbg_window_head_rows_per_group(struct tn_window_head *h, int nb);
+
 #ifdef __cplusplus
 }
 #endif

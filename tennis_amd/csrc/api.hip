@@ -11,6 +11,7 @@
 #include "common.h"
 #include "linear.h"
 #include "rnn.h"
+#include "rnn_window.h"
 #include "train.h"
 
 bool dense_layer_big_supported(int H, int W);   // dense_layer_big.hip
@@ -1305,6 +1306,116 @@ extern "C" int tn_birnn_destroy(tn_birnn *r) {
   r->pool.release();
   delete r;
   return TN_OK;
+}
+
+// ---- dense windowed evaluation of the temporal heads ----------------------------------
+struct tn_window_head {
+  tn_ctx *ctx;
+  DevPool pool;
+  int gates, F, H, C, max_rows, max_samples;
+  int rows;    // rows of the matrix the last project() saw; 0: none yet
+  int nb;      // samples per workgroup of the recurrent kernel; 0: the library's choice
+  float *wi;   // [2*G*H][F]   both directions stacked -> one i2h GEMM
+  float *bi;   // [2*G*H]
+  float *whT;  // [2][H][G*H]
+  float *bh;   // [2][G*H]
+  float *wd;   // [C][2H]
+  float *bd;   // [C]
+  float *gi;      // [max_rows][2*G*H]: the projection of every row of the matrix
+  float *pooled;  // [max_samples][2H]
+};
+
+extern "C" int tn_window_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int hidden, int classes,
+                                     const tn_param *params, int n_params, const char *rnn_prefix, const char *dense_prefix,
+                                     int max_rows, int max_samples, tn_window_head **out) {
+  TN_REQUIRE(ctx && params && rnn_prefix && dense_prefix && out, "tn_window_head_create: null argument");
+  TN_REQUIRE(kind == TN_RNN_GRU || kind == TN_RNN_LSTM, "tn_window_head_create: unknown cell kind");
+  const int G = kind == TN_RNN_GRU ? 3 : 4;
+  TN_REQUIRE(input_size > 0 && hidden > 0 && hidden % 4 == 0 && G * hidden <= 1024 && classes > 0 && max_rows > 0 &&
+                 max_samples > 0, "tn_window_head_create: bad shape (gates*hidden must be <= 1024, hidden % 4 == 0)");
+  TN_ON_DEVICE(ctx->device);
+  ParamMap pm(params, n_params);
+  const int F = input_size, H = hidden, C = classes, GH = G * hidden;
+  std::vector<float> wi((size_t)2 * GH * F), bi((size_t)2 * GH), whT((size_t)2 * H * GH), bh((size_t)2 * GH);
+  for (int d = 0; d < 2; ++d) {
+    const std::string dp = std::string(rnn_prefix) + (d == 0 ? "l0_" : "r0_");
+    const float *a = pm.get(dp + "i2h_weight", (int64_t)GH * F), *b = pm.get(dp + "h2h_weight", (int64_t)GH * H);
+    const float *c = pm.get(dp + "i2h_bias", GH), *e = pm.get(dp + "h2h_bias", GH);
+    if (!a || !b || !c || !e) return TN_ERR_MISSING;
+    memcpy(&wi[(size_t)d * GH * F], a, sizeof(float) * GH * F);
+    memcpy(&bi[(size_t)d * GH], c, sizeof(float) * GH);
+    memcpy(&bh[(size_t)d * GH], e, sizeof(float) * GH);
+    for (int j = 0; j < GH; ++j)
+      for (int k = 0; k < H; ++k) whT[((size_t)d * H + k) * GH + j] = b[(size_t)j * H + k];
+  }
+  const float *wd = pm.get(std::string(dense_prefix) + "weight", (int64_t)C * 2 * H);
+  const float *bd = pm.get(std::string(dense_prefix) + "bias", C);
+  if (!wd || !bd) return TN_ERR_MISSING;
+  tn_window_head *h = new tn_window_head();
+  h->ctx = ctx; h->gates = G; h->F = F; h->H = H; h->C = C; h->max_rows = max_rows; h->max_samples = max_samples;
+  h->rows = 0; h->nb = 0;
+  h->wi = h->pool.upload(wi); h->bi = h->pool.upload(bi); h->whT = h->pool.upload(whT); h->bh = h->pool.upload(bh);
+  h->wd = h->pool.upload(std::vector<float>(wd, wd + (size_t)C * 2 * H));
+  h->bd = h->pool.upload(std::vector<float>(bd, bd + C));
+  h->gi = (float *)h->pool.alloc((size_t)max_rows * 2 * GH * sizeof(float));
+  h->pooled = (float *)h->pool.alloc((size_t)max_samples * 2 * H * sizeof(float));
+  if (h->pool.failed) { h->pool.release(); delete h; tn_set_error("device allocation failed"); return TN_ERR_NOMEM; }
+  *out = h;
+  return TN_OK;
+}
+
+extern "C" int tn_window_head_project(tn_window_head *h, const float *feats, int rows) {
+  TN_REQUIRE(h && feats, "tn_window_head_project: null argument");
+  TN_REQUIRE(rows > 0 && rows <= h->max_rows, "tn_window_head_project: rows must be in [1, max_rows]");
+  TN_ON_DEVICE(h->ctx->device);
+  const int N = 2 * h->gates * h->H;
+  h->rows = 0;
+  const int rc = launch_linear_f32(feats, h->F, h->wi, h->F, h->bi, h->gi, N, rows, N, h->F, 0, h->ctx->stream);
+  if (rc) return rc;
+  h->rows = rows;
+  return TN_OK;
+}
+
+extern "C" int tn_window_head_forward(tn_window_head *h, const int32_t *centre, const int32_t *lo, const int32_t *hi,
+                                      int samples, int window, int stride, float *pooled, float *logits) {
+  TN_REQUIRE(h && centre && lo && hi && logits, "tn_window_head_forward: null argument");
+  TN_REQUIRE(h->rows > 0, "tn_window_head_forward: no projected matrix (call tn_window_head_project first)");
+  TN_REQUIRE(samples > 0 && samples <= h->max_samples, "tn_window_head_forward: samples must be in [1, max_samples]");
+  TN_REQUIRE(window >= 1 && stride >= 1, "tn_window_head_forward: window and stride must be >= 1");
+  TN_ON_DEVICE(h->ctx->device);
+  hipStream_t s = h->ctx->stream;
+  const int H = h->H;
+  float *p = pooled ? pooled : h->pooled;
+  const int rc = launch_rnn_window(h->gates, h->gi, 2 * h->gates * H, h->rows, h->whT, h->bh, centre, lo, hi, p, samples, window,
+                                   stride, H, h->nb, s);
+  if (rc) return rc;
+  return launch_linear_f32(p, 2 * H, h->wd, 2 * H, h->bd, logits, h->C, samples, h->C, 2 * H, 0, s);
+}
+
+extern "C" int tn_dbg_window_head_rows_per_group(tn_window_head *h, int nb) {
+  TN_REQUIRE(h, "tn_dbg_window_head_rows_per_group: null argument");
+  TN_REQUIRE(nb == 0 || nb == 4 || nb == 2 * h->gates, "tn_dbg_window_head_rows_per_group: 0 (default), 4 or twice the gates");
+  h->nb = nb;
+  return TN_OK;
+}
+
+extern "C" int tn_window_head_destroy(tn_window_head *h) {
+  if (!h) return TN_OK;
+  TnDeviceGuard tn_dg_(h->ctx->device);
+  h->pool.release();
+  delete h;
+  return TN_OK;
+}
+
+extern "C" int tn_temporal_pool_windows(tn_ctx *ctx, const float *feats, int rows, int feat, const int32_t *centre,
+                                        const int32_t *lo, const int32_t *hi, int samples, int window, int stride,
+                                        tn_pool_kind kind, float *y) {
+  TN_REQUIRE(ctx && feats && centre && lo && hi && y, "tn_temporal_pool_windows: null argument");
+  TN_REQUIRE(rows > 0 && feat > 0 && samples > 0, "tn_temporal_pool_windows: bad shape");
+  TN_REQUIRE(window >= 1 && stride >= 1, "tn_temporal_pool_windows: window and stride must be >= 1");
+  TN_REQUIRE(kind == TN_POOL_MAX || kind == TN_POOL_MEAN, "tn_temporal_pool_windows: unknown pool kind");
+  TN_ON_DEVICE(ctx->device);
+  return launch_temporal_pool_windows(feats, rows, feat, centre, lo, hi, samples, window, stride, (int)kind, y, ctx->stream);
 }
 
 // ---- temporal-head training step -----------------------------------------------------

@@ -1,0 +1,15 @@
+// Launchers of the windowed recurrent / pooling kernels (rnn_window.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+// gi [rows][2*G*H]: the i2h projection of every row of the feature matrix (both directions); centre / lo / hi [B] device int32:
+// the window of sample b reads row clamp(centre[b] + (t - T/2) * stride, lo[b], hi[b]), clamped once more to [0, rows-1];
+// pooled [B][2*H] = max over the T steps of concat(fwd, bwd).  nb: samples per workgroup, 0 = rnn_window_default_nb(gates)
+// (4 or 6 for a GRU / 4 or 8 for an LSTM; the result does not depend on it).
+int rnn_window_default_nb(int gates);
+int launch_rnn_window(int gates, const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *centre,
+                      const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, int nb,
+                      hipStream_t s);
+// x [rows][F] -> y [B][F]: max / mean (tn_pool_kind) over the same gathered rows of x itself
+int launch_temporal_pool_windows(const float *x, int rows, int F, const int32_t *centre, const int32_t *lo, const int32_t *hi,
+                                 int B, int T, int stride, int kind, float *y, hipStream_t s);

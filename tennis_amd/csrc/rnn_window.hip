@@ -1,0 +1,254 @@
+// K9w/K11w — dense windowed evaluation of the temporal heads (reference evaluate.py --window W --temp_pool gru|lstm|mean|max over
+// models/vision/definitions.py:66-69,94-96,106-107 and the window sampling of dataset.py:190-201).
+//
+// The windows of neighbouring samples overlap, and the i2h projection of a frame does not depend on the window that asks for it:
+// the projection runs ONCE over the rows of the feature matrix (linear.hip), and the recurrent kernel below gathers, per sample
+// and step, the projected row its window names.  Neither the (samples, T, F) windows nor the (samples, T, 2H) sequence exist in
+// memory: the max over the steps (definitions.py:107) is kept per unit while the sequence is walked.
+//
+//   row(b, t) = clamp(centre[b] + (t - T/2) * stride, lo[b], hi[b])      (TennisSet.window_frames in units of matrix rows)
+//   and then clamp(row, 0, rows - 1), unconditionally: no content of centre / lo / hi makes a kernel read outside its input.
+#include "common.h"
+#include "rnn_dot.h"
+#include "rnn_window.h"
+
+namespace {
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+__device__ __forceinline__ long window_row(int centre, int lo, int hi, int t, int T, int stride, int rows) {
+  long r = (long)centre + (long)(t - T / 2) * stride;     // (64-bit: no content of the index arrays overflows)
+  r = min(max(r, (long)lo), (long)hi);
+  return min(max(r, 0L), (long)rows - 1);
+}
+
+// The recurrence of rnn_recurrent_kernel (rnn.hip): one workgroup = one direction x NB samples, all T steps; thread j owns gate
+// row j of W_hh and runs the same ascending-k fmaf chain with one accumulator per sample (measured against that path on the same
+// windows: LSTM logits bit-equal, GRU logits within 1.8e-7; tests/test_gpu_window_head.py records it).  What differs:
+//   * the gi row of (sample, step) is gathered (window_row); the reverse direction walks t = T-1 .. 0; no valid_len;
+//   * no sequence store: every (sample, unit) keeps the running maximum of h, started from the first step's value, and writes
+//     pooled[b][dir*H + u] once;
+//   * NB is a multiple of G where it can be (NB*H units over G*H threads: every thread then finishes exactly NB/G units per
+//     step) and the step's gi values are requested BEFORE the dot product, so their latency hides behind it;
+//   * DPP (H % 16 == 0): h is not read per FMA - a lane reads 16 bytes per 16 k-values and the FMAs take h through
+//     quad_perm (rnn_dot.h), 4 x fewer LDS instructions; KR = 128 (H == 128): the thread's whole weight column lives in
+//     registers for all T steps, nothing of W_hh is re-read.
+template <int G, int NB, int KR, bool DPP, int MAXT>
+__global__ __launch_bounds__(MAXT) void rnn_window_kernel(
+    const float *__restrict__ gi, int ldgi, int rows,   // [rows][2*G*H] i2h + b_i2h of every row of the feature matrix
+    const float *__restrict__ whT,                      // [2][H][G*H]
+    const float *__restrict__ bh,                       // [2][G*H]
+    const int32_t *__restrict__ centre, const int32_t *__restrict__ lo, const int32_t *__restrict__ hi,   // [B]
+    float *__restrict__ pooled,                         // [B][2*H]
+    int B, int T, int stride, int H) {
+  static_assert(!DPP || KR % 16 == 0, "whole 16-wide h chunks");
+  static_assert(DPP || KR == 0, "the register-resident prefix is part of the DPP form");
+  constexpr int MI = (NB + G - 1) / G;     // units a thread finishes per step (NB*H units over G*H threads)
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int GH = G * H;
+  float *hs = lds;                 // [NB][H]
+  float *gh = hs + NB * H;         // [NB][GH]
+  float *cs = gh + NB * GH;        // [NB][H] (LSTM)
+  const int j = threadIdx.x;       // gate row
+  const int dir = blockIdx.y;
+  const int b0 = blockIdx.x * NB;
+  const float *wcol = whT + (long)dir * H * GH + j;
+  const float bj = bh[dir * GH + j];
+  float wr[KR > 0 ? KR : 1];
+#pragma unroll
+  for (int k = 0; k < KR; ++k) wr[k] = wcol[(long)k * GH];
+
+  // the units this thread finishes: idx = j + m*GH -> (sample b0 + idx / H, unit idx % H)
+  int cen[MI], wlo[MI], whi[MI];
+  bool live[MI];
+  float hmax[MI];
+#pragma unroll
+  for (int m = 0; m < MI; ++m) {
+    const int idx = j + m * GH;
+    const int bg = b0 + idx / H;
+    live[m] = idx < NB * H && bg < B;
+    cen[m] = live[m] ? centre[bg] : 0;
+    wlo[m] = live[m] ? lo[bg] : 0;
+    whi[m] = live[m] ? hi[bg] : 0;
+    hmax[m] = 0.f;
+  }
+  for (int i = j; i < NB * H; i += GH) {
+    hs[i] = 0.f;
+    if (G == 4) cs[i] = 0.f;
+  }
+  __syncthreads();
+
+  for (int s = 0; s < T; ++s) {
+    const int t = dir ? T - 1 - s : s;
+    // this step's input pre-activations of the units the thread finishes below (requested now, used after the barrier)
+    float gq[MI][G];
+#pragma unroll
+    for (int m = 0; m < MI; ++m) {
+      if (live[m]) {
+        const int u = (j + m * GH) % H;
+        const float *g = gi + window_row(cen[m], wlo[m], whi[m], t, T, stride, rows) * ldgi + dir * GH + u;
+#pragma unroll
+        for (int e = 0; e < G; ++e) gq[m][e] = g[e * H];
+      }
+    }
+    float acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = bj;
+    if constexpr (DPP) {
+      const int lane4 = (j & 3) * 4;
+#pragma unroll
+      for (int k = 0; k < KR; k += 16) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          const float4 hq = *(const float4 *)(hs + b * H + k + lane4);
+#define TN_WV(i) wr[k + (i)]
+          TN_DOT16(acc[b], hq, TN_WV);
+#undef TN_WV
+        }
+      }
+      for (int k = KR; k < H; k += 16) {
+        float w[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[i] = wcol[(long)(k + i) * GH];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          const float4 hq = *(const float4 *)(hs + b * H + k + lane4);
+#define TN_WV(i) w[i]
+          TN_DOT16(acc[b], hq, TN_WV);
+#undef TN_WV
+        }
+      }
+    } else {
+      int k = 0;
+      for (; k + 16 <= H; k += 16) {
+        float w[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[i] = wcol[(long)(k + i) * GH];
+#pragma unroll
+        for (int i = 0; i < 16; i += 4) {
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            const float4 hv = *(const float4 *)(hs + b * H + k + i);
+            acc[b] = fmaf(w[i + 0], hv.x, acc[b]);
+            acc[b] = fmaf(w[i + 1], hv.y, acc[b]);
+            acc[b] = fmaf(w[i + 2], hv.z, acc[b]);
+            acc[b] = fmaf(w[i + 3], hv.w, acc[b]);
+          }
+        }
+      }
+      for (; k < H; k += 4) {
+        const float w0 = wcol[(long)(k + 0) * GH], w1 = wcol[(long)(k + 1) * GH];
+        const float w2 = wcol[(long)(k + 2) * GH], w3 = wcol[(long)(k + 3) * GH];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          const float4 hv = *(const float4 *)(hs + b * H + k);
+          acc[b] = fmaf(w0, hv.x, acc[b]);
+          acc[b] = fmaf(w1, hv.y, acc[b]);
+          acc[b] = fmaf(w2, hv.z, acc[b]);
+          acc[b] = fmaf(w3, hv.w, acc[b]);
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) gh[b * GH + j] = acc[b];
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < MI; ++m) {
+      if (!live[m]) continue;
+      const int idx = j + m * GH;
+      const int b = idx / H, u = idx - b * H;
+      const float *q = gh + b * GH;
+      float hn;
+      if (G == 3) {
+        const float r = sigmoidf_(gq[m][0] + q[u]);
+        const float z = sigmoidf_(gq[m][1] + q[H + u]);
+        const float n = tanhf(gq[m][2] + r * q[2 * H + u]);
+        hn = (1.f - z) * n + z * hs[idx];
+      } else {
+        const float ig = sigmoidf_(gq[m][0] + q[u]);
+        const float fg = sigmoidf_(gq[m][1] + q[H + u]);
+        const float gg = tanhf(gq[m][2] + q[2 * H + u]);
+        const float og = sigmoidf_(gq[m][G - 1] + q[3 * H + u]);
+        const float c2 = fg * cs[idx] + ig * gg;
+        cs[idx] = c2;
+        hn = og * tanhf(c2);
+      }
+      hs[idx] = hn;
+      hmax[m] = s == 0 ? hn : fmaxf(hmax[m], hn);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int m = 0; m < MI; ++m) {
+    if (!live[m]) continue;
+    const int idx = j + m * GH;
+    const int b = idx / H, u = idx - b * H;
+    pooled[(long)(b0 + b) * (2 * H) + dir * H + u] = hmax[m];
+  }
+}
+
+// F.max / F.mean over the gathered rows of the feature matrix itself (definitions.py:66-69 in feature mode), t ascending as in
+// temporal_pool_kernel (rnn.hip): x (rows, F) -> y (B, F)
+__global__ void temporal_pool_windows_kernel(const float *__restrict__ x, int rows, int F, const int32_t *__restrict__ centre,
+                                             const int32_t *__restrict__ lo, const int32_t *__restrict__ hi, int B, int T,
+                                             int stride, int kind, float *__restrict__ y) {
+  const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (long)B * F) return;
+  const int b = (int)(id / F), f = (int)(id % F);
+  const int c = centre[b], l = lo[b], h = hi[b];
+  float acc = kind == TN_POOL_MAX ? -INFINITY : 0.f;
+  for (int t = 0; t < T; ++t) {
+    const float v = x[window_row(c, l, h, t, T, stride, rows) * F + f];
+    acc = kind == TN_POOL_MAX ? fmaxf(acc, v) : acc + v;
+  }
+  y[id] = kind == TN_POOL_MAX ? acc : acc / (float)T;
+}
+
+template <int G, int NB>
+int launch_window_nb(const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *centre,
+                     const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, hipStream_t s) {
+  const dim3 grid((B + NB - 1) / NB, 2), block(G * H);
+  const size_t lds = (size_t)(NB * H * 2 + NB * G * H) * sizeof(float);
+#define TN_WIN_LAUNCH(KR_, DPP_, MT_)                                                                                          \
+  hipLaunchKernelGGL((rnn_window_kernel<G, NB, KR_, DPP_, MT_>), grid, block, lds, s, gi, ldgi, rows, whT, bh, centre, lo, hi, \
+                     pooled, B, T, stride, H)
+  if (H == 128) TN_WIN_LAUNCH(128, true, 512);          // the fast route: CNNRNN's width, the weight column in registers
+  else if (H % 16 == 0) TN_WIN_LAUNCH(0, true, 1024);
+  else TN_WIN_LAUNCH(0, false, 1024);
+#undef TN_WIN_LAUNCH
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+
+}  // namespace
+
+int rnn_window_default_nb(int gates) { return 2 * gates; }
+
+int launch_rnn_window(int gates, const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *centre,
+                      const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, int nb,
+                      hipStream_t s) {
+  TN_REQUIRE(gates == 3 || gates == 4, "rnn_window: gates must be 3 or 4");
+  TN_REQUIRE(gates * H <= 1024 && H % 4 == 0, "rnn_window: gates*hidden must be <= 1024 and hidden % 4 == 0");
+  TN_REQUIRE(rows > 0 && B > 0 && T > 0 && stride > 0, "rnn_window: bad shape");
+  if (nb == 0) nb = rnn_window_default_nb(gates);
+  if ((size_t)nb * (2 + gates) * H * sizeof(float) > 64 * 1024) nb = 4;      // (the LDS a workgroup may ask for without an attribute)
+#define TN_WIN_ARGS gi, ldgi, rows, whT, bh, centre, lo, hi, pooled, B, T, stride, H, s
+  if (gates == 3) {
+    if (nb == 4) return launch_window_nb<3, 4>(TN_WIN_ARGS);
+    if (nb == 6) return launch_window_nb<3, 6>(TN_WIN_ARGS);
+  } else {
+    if (nb == 4) return launch_window_nb<4, 4>(TN_WIN_ARGS);
+    if (nb == 8) return launch_window_nb<4, 8>(TN_WIN_ARGS);
+  }
+#undef TN_WIN_ARGS
+  TN_REQUIRE(false, "rnn_window: rows per workgroup must be 4 or 6 (GRU) / 4 or 8 (LSTM)");
+}
+
+int launch_temporal_pool_windows(const float *x, int rows, int F, const int32_t *centre, const int32_t *lo, const int32_t *hi,
+                                 int B, int T, int stride, int kind, float *y, hipStream_t s) {
+  const long total = (long)B * F;
+  hipLaunchKernelGGL(temporal_pool_windows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, rows, F, centre,
+                     lo, hi, B, T, stride, kind, y);
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}

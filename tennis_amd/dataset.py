@@ -307,15 +307,70 @@ class TennisSet:
         img = self.frame_u8(video, frame)
         return img if getattr(self._transform, "device_batched", False) else self._transform(img)
 
-    def window_frames(self, sample):
-        """Frame numbers a window sample reads (dataset.py:190-201)."""
+    def window_frames(self, sample, stride=None):
+        """Frame numbers a window sample reads (dataset.py:190-201); ``stride``: instead of the dataset's own."""
+        stride = self._stride if stride is None else stride
         offsets = list(range(int(-self._window / 2), int(math.ceil(self._window / 2))))
-        max_frame = self._video_lengths[sample[0]] - self._every
+        max_frame = self._max_frame(sample[0])
+        return [min(max(0, sample[1] + o * stride), int(max_frame)) for o in offsets]
+
+    def _max_frame(self, video):
+        """the last frame a window of ``video`` reads (dataset.py:194-199): a multiple of ``every`` with ``every`` frames behind it"""
+        max_frame = self._video_lengths[video] - self._every
         for i in range(self._every):
             if (max_frame - i) % self._every == 0:
                 max_frame -= i
                 break
-        return [min(max(0, sample[1] + o * self._stride), int(max_frame)) for o in offsets]
+        return max_frame
+
+    def window_rows(self, stride=None):
+        """Every sample's window in units of ROWS of the dataset-order feature matrix (row i = sample i: what
+        ``save_features_sharded`` returns): ``(centre, lo, hi, row_stride)``, int32 arrays of ``len(self)`` and an int, such that
+        the rows ``clamp(centre[i] + (t - window // 2) * row_stride, lo[i], hi[i])``, t = 0 .. window-1, are exactly the frames
+        ``window_frames(sample i)`` reads.  ``stride`` is in frames (default: the dataset's own).  Raises ``ValueError`` where that
+        mapping does not exist: a stride that is no multiple of ``every``, a video whose rows are not contiguous and equally spaced
+        in ascending frame order, or a window frame that has no row."""
+        stride = self._stride if stride is None else int(stride)
+        if stride < 1 or stride % self._every != 0:
+            raise ValueError(f"window_rows: stride {stride} is not a positive multiple of every = {self._every}")
+        n = len(self._samples)
+        centre, lo, hi = (np.zeros(n, np.int32) for _ in range(3))
+        by_video = {}
+        for i, s in enumerate(self._samples):
+            by_video.setdefault(s[0], []).append(i)
+        spacing = None
+        for v, ids in by_video.items():
+            ids = np.asarray(ids)
+            frames = np.asarray([self._samples[i][1] for i in ids], np.int64)
+            if np.any(np.diff(ids) != 1):
+                raise ValueError(f"window_rows: the rows of video {v} are not contiguous in dataset order")
+            if len(ids) > 1:
+                d = np.diff(frames)
+                if d[0] <= 0 or np.any(d != d[0]):
+                    raise ValueError(f"window_rows: the rows of video {v} are not equally spaced ascending frames")
+                if spacing is not None and spacing != int(d[0]):
+                    raise ValueError(f"window_rows: video {v} has frame spacing {int(d[0])}, an earlier one {spacing}")
+                spacing = int(d[0])
+            # (window_frames clamps to _max_frame: with every > 1 that can be the row before the video's last)
+            below = ids[frames <= self._max_frame(v)]
+            centre[ids], lo[ids], hi[ids] = ids, ids[0], below[-1] if len(below) else ids[-1]
+        spacing = self._every if spacing is None else spacing
+        if stride % spacing != 0:
+            raise ValueError(f"window_rows: stride {stride} is not a multiple of the rows' frame spacing {spacing}")
+        row_stride = stride // spacing
+        # the mapping must name the very frames window_frames reads (its clamp is to [0, max_frame] of the VIDEO, the rows' to
+        # [lo, hi] of the video's rows: they agree when the rows reach both ends, or no window reaches past them)
+        frame_of_row = np.asarray([s[1] for s in self._samples], np.int64)
+        offs = (np.arange(self._window) - self._window // 2) * row_stride
+        for v, ids in by_video.items():
+            ids = np.asarray(ids)
+            want = np.asarray([self.window_frames(self._samples[i], stride) for i in ids], np.int64)
+            rows = np.clip(ids[:, None] + offs[None, :], lo[ids][:, None], hi[ids][:, None])
+            bad = np.nonzero(frame_of_row[rows] != want)
+            if len(bad[0]):
+                raise ValueError(f"window_rows: frame {int(want[bad[0][0], bad[1][0]])} of video {v}, read by the window of frame "
+                                 f"{self._samples[ids[bad[0][0]]][1]}, has no row in the feature matrix")
+        return centre, lo, hi, row_stride
 
     def __getitem__(self, idx):                                                        # dataset.py:184-233
         sample = self._samples[idx]

@@ -226,6 +226,95 @@ def temporal_pool(x: torch.Tensor, kind: str, ctx: _lib.Context | None = None) -
     return y
 
 
+def _index_arrays(dev, *arrays):
+    """(samples,) index arrays (numpy / torch, any integer type) -> contiguous int32 tensors on ``dev``"""
+    out = []
+    for a in arrays:
+        a = torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a)
+        out.append(a.to(device=dev, dtype=torch.int32).contiguous())
+    if len({tuple(a.shape) for a in out}) != 1 or out[0].dim() != 1:
+        raise ValueError("centre, lo and hi must be one-dimensional arrays of one length")
+    return out
+
+
+class WindowHead:
+    """Dense windowed evaluation of ``CNNRNN`` in feature mode (reference evaluate.py:274-303 with ``--feats_model M --window W
+    --temp_pool gru|lstm``; definitions.py:94-96,106-109): ``project`` runs the i2h projection once per row of a device-resident
+    (rows, F) feature matrix, ``forward`` gathers every sample's window inside the recurrent kernel - step ``t`` of sample ``b`` reads
+    row ``clamp(centre[b] + (t - window // 2) * stride, lo[b], hi[b])`` (``TennisSet.window_rows``) - and returns the logits.  One
+    ``project`` serves any number of ``forward`` calls; neither allocates in the library."""
+
+    def __init__(self, mode: str, input_size: int, hidden: int, classes: int, params: dict, rnn_prefix: str, dense_prefix: str,
+                 max_rows: int = 65536, max_samples: int | None = None, ctx: _lib.Context | None = None):
+        if mode not in ("gru", "lstm"):
+            raise ValueError(f"mode must be 'gru' or 'lstm', got {mode!r}")
+        self.ctx = ctx or _lib.default_context()
+        self.lib = self.ctx.lib
+        self.mode, self.input_size, self.hidden, self.classes = mode, input_size, hidden, classes
+        self.max_rows = int(max_rows)
+        self.max_samples = int(max_rows if max_samples is None else max_samples)
+        arr, keep = _lib.make_params({k: v for k, v in params.items() if k.startswith(rnn_prefix) or k.startswith(dense_prefix)})
+        h = C.c_void_p()
+        check(self.lib.tn_window_head_create(self.ctx.handle, _lib.RNN_GRU if mode == "gru" else _lib.RNN_LSTM, input_size, hidden,
+                                             classes, arr, len(arr), rnn_prefix.encode(), dense_prefix.encode(), self.max_rows,
+                                             self.max_samples, C.byref(h)), "tn_window_head_create")
+        del keep
+        self.handle = h
+        self.rows = 0
+
+    def project(self, features: torch.Tensor):
+        _on_ctx_device(self.ctx, features, "WindowHead.project")
+        x = features.contiguous().float()
+        if x.dim() != 2 or x.shape[1] != self.input_size:
+            raise ValueError(f"WindowHead expects a (rows, {self.input_size}) feature matrix, got {tuple(x.shape)}")
+        self.rows = 0
+        check(self.lib.tn_window_head_project(self.handle, ptr(x), x.shape[0]), "tn_window_head_project")
+        self.rows = x.shape[0]
+        return self
+
+    def forward(self, centre, lo, hi, window: int, stride: int = 1, return_pooled: bool = False):
+        dev = torch.device("cuda", self.ctx.device)
+        centre, lo, hi = _index_arrays(dev, centre, lo, hi)
+        n = centre.shape[0]
+        logits = torch.empty((n, self.classes), dtype=torch.float32, device=dev)
+        pooled = torch.empty((n, 2 * self.hidden), dtype=torch.float32, device=dev) if return_pooled else None
+        check(self.lib.tn_window_head_forward(self.handle, ptr(centre), ptr(lo), ptr(hi), n, int(window), int(stride), ptr(pooled),
+                                              ptr(logits)), "tn_window_head_forward")
+        return (logits, pooled) if return_pooled else logits
+
+    __call__ = forward
+
+    def _set_rows_per_group(self, nb: int):
+        """tuning hook (scripts/bench_window_head.py): samples per workgroup of the recurrent kernel, 0 = the library's choice"""
+        check(self.lib.tn_dbg_window_head_rows_per_group(self.handle, int(nb)), "tn_dbg_window_head_rows_per_group")
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self.lib.tn_window_head_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def temporal_pool_windows(features: torch.Tensor, centre, lo, hi, window: int, stride: int, kind: str,
+                          ctx: _lib.Context | None = None) -> torch.Tensor:
+    """``F.max`` / ``F.mean`` over axis 1 of the windows of a (rows, F) feature matrix without materialising them
+    (definitions.py:66-69 on the batch of dataset.py:190-213) -> (samples, F)."""
+    ctx = ctx or _lib.default_context(features.device.index)
+    _on_ctx_device(ctx, features, "temporal_pool_windows")
+    x = features.contiguous().float()
+    if x.dim() != 2:
+        raise ValueError(f"temporal_pool_windows expects a (rows, F) feature matrix, got {tuple(x.shape)}")
+    centre, lo, hi = _index_arrays(x.device, centre, lo, hi)
+    n = centre.shape[0]
+    y = torch.empty((n, x.shape[1]), dtype=torch.float32, device=x.device)
+    check(ctx.lib.tn_temporal_pool_windows(ctx.handle, ptr(x), x.shape[0], x.shape[1], ptr(centre), ptr(lo), ptr(hi), n, int(window),
+                                           int(stride), _lib.POOL_MEAN if kind == "mean" else _lib.POOL_MAX, ptr(y)),
+          "tn_temporal_pool_windows")
+    return y
+
+
 def to_tensor_normalize(x: torch.Tensor, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
                         ctx: _lib.Context | None = None) -> torch.Tensor:
     """``transforms.ToTensor()`` + ``transforms.Normalize(mean, std)`` (reference evaluate.py:96-97) on a uint8

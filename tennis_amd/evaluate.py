@@ -50,6 +50,61 @@ def evaluate_model(net, loader, dataset, metrics, ctx=None):
     return results, ground_truths
 
 
+def load_feature_matrix(dataset):
+    """The dataset-order (len(dataset), F) feature matrix from the ``.npy`` files of ``dataset.feat_dir``: every frame's file is
+    read once (the loader path reads it once per window that contains it)."""
+    rows = [np.load(dataset.get_feature_path(dataset.feat_dir, s[0], s[1])).astype(np.float32).reshape(-1) for s in dataset._samples]
+    return np.stack(rows)
+
+
+def evaluate_windows(net, dataset, metrics, features=None, batch_size=65536):
+    """``evaluate_model`` for a windowed feature-mode model (``CNNRNN`` / ``TemporalPooling``) without the loader: the
+    dataset-order feature matrix (``features``: (len(dataset), F), e.g. what ``save_features_sharded`` returned; None: loaded from
+    the ``.npy`` files, each once) goes to the device once, ``net.forward_windows`` evaluates every sample's window from it
+    (``TennisSet.window_rows``), and the metrics are updated in dataset order in pieces of ``batch_size``.  Same return values:
+    results[img_path] = raw logits, ground_truths[img_path] = class index."""
+    centre, lo, hi, row_stride = dataset.window_rows()
+    if features is None:
+        features = load_feature_matrix(dataset)
+    if len(features) != len(dataset):
+        raise ValueError(f"evaluate_windows: {len(features)} feature rows for {len(dataset)} samples")
+    outputs = net.forward_windows(features, centre, lo, hi, dataset._window, row_stride)
+    labels = torch.tensor([dataset.classes.index(s[2]) for s in dataset._samples], dtype=torch.float32, device=outputs.device)
+    for a in range(0, len(dataset), batch_size):
+        for metric in metrics:
+            metric.update([labels[a:a + batch_size]], [outputs[a:a + batch_size]])
+    out = outputs.cpu().numpy()
+    results, ground_truths = dict(), dict()
+    for i, sample in enumerate(dataset._samples):
+        img_path = dataset.get_image_path(dataset._frames_dir, sample[0], sample[1])
+        results[img_path] = out[i]
+        ground_truths[img_path] = dataset.classes.index(sample[2])
+    return results, ground_truths
+
+
+def corpus_window_head(full, window, temp_pool, classes, stride=1, hidden=128):
+    """``--corpus_frames N --dense_windows``: the temporal head over the gathered (N, F) matrix as ONE sequence (lo = 0,
+    hi = N-1), one window per frame -> (logits, seconds of device work)."""
+    n = full.shape[0]
+    if temp_pool in ("gru", "lstm"):
+        model = CNNRNN(None, num_classes=classes, type=temp_pool, hidden_size=hidden)
+    elif temp_pool in ("mean", "max"):
+        model = TemporalPooling(None, num_classes=classes, pool=temp_pool, feats=True)
+    else:
+        raise AssertionError("--dense_windows needs --temp_pool gru, lstm, mean or max")
+    model.initialize()
+    centre = torch.arange(n, dtype=torch.int32, device=full.device)
+    lo, hi = torch.zeros_like(centre), torch.full_like(centre, n - 1)
+    model.forward_windows(full, centre, lo, hi, window, stride, max_rows=n)      # builds the handles and their workspaces (untimed)
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize(full.device)
+    t0.record()
+    logits = model.forward_windows(full, centre, lo, hi, window, stride, max_rows=n)      # (one sequence: nowhere to cut)
+    t1.record()
+    torch.cuda.synchronize(full.device)
+    return logits, t0.elapsed_time(t1) / 1e3
+
+
 class NpyWriter:
     """The ``.npy`` side of ``--save_feats``: ``tn_npy_writer_*`` (csrc/npy_host.hip), a pool of host threads behind the C ABI that
     writes one NumPy-format-1.0 float32 file per feature row, byte for byte what ``np.save(path, row)`` writes, creating the
@@ -340,6 +395,10 @@ def build_parser():
                         "the all-gather of the feature rows (786455 = the 5-match corpus); prints one JSON line")
     p.add_argument("--gather_block", type=int, default=4, help="batches per rank per all-gather round")
     p.add_argument("--corpus_reuse_frames", action="store_true", help="C4: generate one synthetic batch per rank and re-use it")
+    p.add_argument("--dense_windows", action="store_true",
+                   help="dense windowed evaluation (not a reference flag): with --feats_model M --window W --temp_pool gru|lstm|mean|max "
+                        "every frame's features are read once and projected once, the windows are gathered on the GPU "
+                        "(evaluate_windows); with --corpus_frames N the head runs over the gathered matrix as one sequence")
     return p
 
 
@@ -372,8 +431,13 @@ def _main_rank(flags, rank, world, dev):
         backbone = get_model(flags.backbone, pretrained=True, max_batch=flags.batch_size, conversion=flags.fp16_conversion).features
         full, st = extract_corpus(backbone, flags.corpus_frames, flags.batch_size, flags.data_shape, dev, rank, world,
                                   block=flags.gather_block, reuse_frames=flags.corpus_reuse_frames)
+        head = {}
+        if flags.dense_windows:                                             # the temporal stage over the matrix every rank now holds
+            logits, secs = corpus_window_head(full, flags.window, flags.temp_pool, len(TennisSet._get_classes(flags.root)), flags.stride)
+            head = {"window": flags.window, "temp_pool": flags.temp_pool, "head_seconds": round(secs, 4),
+                    "samples_per_sec": round(flags.corpus_frames / secs, 1), "logits_checksum": float(logits.double().sum().item())}
         if rank == 0:
-            print(json.dumps({"config": "C4 corpus feature-extract + all-gather", "frames": flags.corpus_frames,
+            print(json.dumps({**head, "config": "C4 corpus feature-extract + all-gather", "frames": flags.corpus_frames,
                               "n_gpus": world, "batch": flags.batch_size, "rounds": st["rounds"],
                               "frames_per_sec": round(st["frames_per_sec"], 1), "seconds": round(st["seconds"], 3),
                               "feature_matrix_MB": round(full.numel() * 4 / 1e6, 1),
@@ -443,7 +507,13 @@ def _main_rank(flags, rank, world, dev):
         model = TemporalPooling(model, pool=flags.temp_pool, num_classes=0, feats=flags.feats_model is not None)
     test_metrics = [PRF1(label_names=test_set.classes)]
     tic = time.time()
-    if world > 1:                                                           # each rank tests batches rank::world
+    if flags.dense_windows:
+        if flags.feats_model is None or flags.window <= 1 or flags.temp_pool not in ("gru", "lstm", "mean", "max"):
+            raise SystemExit("--dense_windows needs --feats_model M --window W (> 1) --temp_pool gru|lstm|mean|max")
+        if rank != 0:                                                       # one pass over one matrix: nothing to shard
+            return 0
+        results, gts = evaluate_windows(model, test_set, test_metrics)
+    elif world > 1:                                                           # each rank tests batches rank::world
         results, gts = evaluate_model(model, _RankBatches(test_data, rank, world), test_set, test_metrics)
         comm = sharding.feature_comm(dev)
         for m in test_metrics:                                              # confusion counts add up over the ranks

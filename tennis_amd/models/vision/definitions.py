@@ -5,10 +5,44 @@ Same class names, constructor arguments and attributes (``backbone``, ``classes`
 libtennis_hip.so.  Inputs may be numpy or torch tensors; outputs are torch CUDA
 tensors (fp32), the counterpart of MXNet NDArrays on ``mx.gpu``.
 """
+import numpy as np
+import torch
+
 from ...block import Block
-from ...engine import temporal_pool
+from ...engine import WindowHead, temporal_pool, temporal_pool_windows
 from ...nn import GRU, LSTM, Dense, _to_device
 from ...utils.layers import TimeDistributed
+
+
+WINDOW_MAX_ROWS = 1 << 18      # rows of the feature matrix one WindowHead projects at a time (its gi buffer: rows x 2*G*H fp32)
+
+
+def _host_index(a):
+    """an index array (numpy, list, or torch on any device) as int64 numpy"""
+    return np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a).astype(np.int64)
+
+
+def window_chunks(centre, lo, hi, rows, max_rows):
+    """Cuts a feature matrix of ``rows`` rows into pieces of at most ``max_rows`` at video boundaries: a sample never leaves
+    ``[lo, hi]``, so whole videos are independent.  -> [(first row, end row, sample ids)]; one piece when the matrix fits."""
+    centre, lo, hi = (_host_index(a) for a in (centre, lo, hi))
+    if rows <= max_rows:
+        return [(0, rows, np.arange(len(centre)))]
+    if np.any(lo < 0) or np.any(hi >= rows) or np.any(lo > hi):
+        raise ValueError("a matrix larger than the row budget is cut at video boundaries: every [lo, hi] must lie inside it")
+    segs = np.unique(np.stack([lo, hi], 1), axis=0)            # sorted by lo
+    if np.any(segs[1:, 0] <= segs[:-1, 1]):
+        raise ValueError("a matrix larger than the row budget is cut at video boundaries: the [lo, hi] ranges overlap")
+    pieces, first, end = [], int(segs[0, 0]), int(segs[0, 0])
+    for a, b in segs:
+        if b + 1 - a > max_rows:
+            raise ValueError(f"a video of {b + 1 - a} rows does not fit the row budget of {max_rows}")
+        if b + 1 - first > max_rows:
+            pieces.append((first, end))
+            first = int(a)
+        end = int(b) + 1
+    pieces.append((first, end))
+    return [(a, b, np.nonzero((lo >= a) & (hi < b))[0]) for a, b in pieces]
 
 
 class FrameModel(Block):
@@ -58,6 +92,27 @@ class TemporalPooling(Block):
             x = self.classes(x)
         return x
 
+    def forward_windows(self, features, centre, lo, hi, window, stride=1, max_rows=WINDOW_MAX_ROWS):
+        """``forward`` of every window of a (rows, F) feature matrix without materialising the (samples, window, F) batch: sample
+        ``b`` pools the rows ``clamp(centre[b] + (t - window // 2) * stride, lo[b], hi[b])``, t = 0 .. window-1
+        (``TennisSet.window_rows``) -> logits (samples, classes).  Feature mode only."""
+        if not self.feats:
+            raise NotImplementedError("forward_windows: feature mode only (TemporalPooling(..., feats=True))")
+        x = _to_device(features).float()
+        if x.dim() != 2:
+            raise ValueError(f"forward_windows expects a (rows, F) feature matrix, got {tuple(x.shape)}")
+        kind = "mean" if self.pool == "mean" else "max"
+        out = None
+        for a, b, ids in window_chunks(centre, lo, hi, x.shape[0], max_rows):
+            c, l, h = (_host_index(v)[ids] - a for v in (centre, lo, hi))
+            y = temporal_pool_windows(x[a:b], c, l, h, window, stride, kind)
+            if self.classes:
+                y = self.classes(y)
+            if out is None:
+                out = torch.empty((len(_host_index(centre)), y.shape[1]), dtype=torch.float32, device=y.device)
+            out[torch.from_numpy(ids).to(y.device)] = y
+        return out
+
 
 class CNNRNN(Block):
     """Reference definitions.py:75-110: [TimeDistributed CNN ->] bi-GRU/LSTM -> max over T -> Dense."""
@@ -85,6 +140,38 @@ class CNNRNN(Block):
         if self.classes:
             x = self.classes(x)                                        # :108-109
         return x
+
+    def forward_windows(self, features, centre, lo, hi, window, stride=1, max_rows=WINDOW_MAX_ROWS):
+        """``forward`` of every window of a (rows, F) feature matrix with ONE i2h projection per row (``engine.WindowHead``): sample
+        ``b`` runs over the rows ``clamp(centre[b] + (t - window // 2) * stride, lo[b], hi[b])``, t = 0 .. window-1
+        (``TennisSet.window_rows``) -> logits (samples, classes).  Feature mode only.  A matrix of more than ``max_rows`` rows is cut
+        at video boundaries."""
+        if not self.feats:
+            raise NotImplementedError("forward_windows: feature mode only (CNNRNN(model=None, ...))")
+        if not self.classes:
+            raise NotImplementedError("forward_windows returns logits: the model needs its Dense (num_classes > 0)")
+        x = _to_device(features).float()
+        if x.dim() != 2:
+            raise ValueError(f"forward_windows expects a (rows, F) feature matrix, got {tuple(x.shape)}")
+        n = len(_host_index(centre))
+        self.rnn._materialize(x.shape[1])
+        self.classes._materialize(2 * self.rnn._hidden)
+        pieces = window_chunks(centre, lo, hi, x.shape[0], max_rows)
+        need_rows = max(b - a for a, b, _ in pieces)
+        need_samples = max(len(ids) for _, _, ids in pieces)
+        eng = self._engine
+        if eng is None or eng.max_rows < need_rows or eng.max_samples < need_samples or eng.input_size != x.shape[1]:
+            self._engine = eng = None      # release the old workspace first
+            p = {k: v.data for blk in (self.rnn, self.classes) for k, v in blk._own_params.items()}
+            self._engine = eng = WindowHead(self.rnn._mode, x.shape[1], self.rnn._hidden, self.classes._units, p, self.rnn.prefix,
+                                            self.classes.prefix, max_rows=need_rows, max_samples=need_samples)
+        if len(pieces) == 1:
+            return eng.project(x).forward(centre, lo, hi, window, stride)
+        out = torch.empty((n, self.classes._units), dtype=torch.float32, device=x.device)
+        for a, b, ids in pieces:
+            c, l, h = (_host_index(v)[ids] - a for v in (centre, lo, hi))
+            out[torch.from_numpy(ids).to(x.device)] = eng.project(x[a:b]).forward(c, l, h, window, stride)
+        return out
 
 
 class TwoStreamModel(Block):
