@@ -18,9 +18,11 @@ bool dense_strip_supported(int H, int W, int K) {
 }
 
 int launch_dense_strip(const DenseStripArgs &a, hipStream_t s) {
-  TN_REQUIRE(dense_strip_supported(a.H, a.W, a.K), "dense_strip: unsupported geometry");
+  // (the message names the geometry; put together only when a call is refused)
+  const auto geom = [&] { return std::to_string(a.H) + " x " + std::to_string(a.W) + ", K = " + std::to_string(a.K) + ", ldc = " + std::to_string(a.ldc); };
+  TN_REQUIRE(dense_strip_supported(a.H, a.W, a.K), "dense_strip: unsupported geometry " + geom());
   TN_REQUIRE(a.buf && a.s1 && a.t1 && a.w1s && a.w3s, "dense_strip: null operand");
-  TN_REQUIRE(a.ldc % 64 == 0 && a.K + 32 <= a.ldc, "dense_strip: bad channel geometry");
+  TN_REQUIRE(a.ldc % 64 == 0 && a.K + 32 <= a.ldc, "dense_strip: bad channel geometry " + geom());
   if (a.W == 56) return launch_dense_strip_w56(a, s);
   if (a.W == 128) return launch_dense_strip_w128(a, s);
   if (a.W == 64) return launch_dense_strip_w64(a, s);

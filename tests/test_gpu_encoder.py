@@ -255,10 +255,23 @@ def test_encoder_448_mixed_kernels(report):
     err = float(np.abs(got - ref).max())
     report["features_448_maxabs_err"] = err
     assert err < TOL
-    big = DenseNet121Features(p, 448, max_batch=66)(xd[torch.arange(66, device="cuda") % 2]).cpu().numpy()   # strip kernels (batch >= 64)
+    enc66 = DenseNet121Features(p, 448, max_batch=66)
+    x66 = xd[torch.arange(66, device="cuda") % 2]
+    big = enc66(x66).cpu().numpy()   # strip kernels (batch >= 64; 66 frames are no multiple of 16, so the batch is not cut into halves)
     err = float(np.abs(big[:2] - ref).max())
     report["features_448_strip_maxabs_err"] = err
     assert err < TOL and np.array_equal(big[64:], big[:2])
+    # The route this test is here for, asserted and not assumed: the instrumented pass (never cut into halves) names the kernel
+    # families it launched.  56 x 56, K = 128 ... 320 and 28 x 28, K = 256 ... 320 on the strip kernel - the only whole-encoder run of
+    # the 56 x 56 instantiations past K = 224 -, held to the same oracle bar.
+    stats, prof = enc66.profile(x66)
+    fams = {s["name"]: s["launches"] for s in stats}
+    assert "dense_layer_strip_56x56" in fams and "dense_layer_strip_28x28" in fams, sorted(fams)
+    assert fams["dense_layer_strip_56x56"] == 7 and fams["dense_layer_strip_28x28"] == 3, fams
+    prof = prof.cpu().numpy()
+    err = float(np.abs(prof[:2] - ref).max())
+    report["features_448_strip_profiled_maxabs_err"] = err
+    assert err < TOL and np.array_equal(prof[64:], prof[:2])
 
 
 @pytest.mark.parametrize("size", [226, 232, 236])
