@@ -148,6 +148,13 @@ int tn_dbg_gnmt_trainer_src_grad(tn_gnmt_trainer *t, const float *src, const int
  * stream form (H = 256 at nb = 1).  Host arithmetic only: touches no device. */
 int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int *kr, int *big);
 
+/* Which kernel families the fp16 DenseNet-121 encoder launches for an input size, create flags (0 | TN_ENC_EXACT_WEIGHTS; the TN_*
+ * switches are read from the environment as tn_densenet121_create_ex reads them), a batch and a pass (calibrate: the layer-wise pass
+ * of tn_densenet121_input_means): what tn_densenet121_profile would fill for such an encoder - name, launches, flops and bytes in
+ * first-seen order, ms 0 - from the routing plan create and forward both follow (csrc/encoder_plan.h).  Refuses what create refuses
+ * for the size and the flags, and TN_ENC_FP32 / TN_ENC_FP32X3, which are not planned.  Host arithmetic only: touches no device. */
+int tn_dbg_encoder_plan(int height, int width, int flags, int batch, int calibrate, tn_kernel_stat *stats, int max_stats, int *n_stats);
+
 /* One convolution of the fp32x3 encoder mode (csrc/dense_fp32x3.hip; which = 0) or, on the same operands, of the fp32 mode
  * (csrc/dense_fp32.hip; which = 1).  kind: 0 stem 7x7/2 (x: B frames in `layout`, H x W; epilogue relu(es y + et)), 1 dense 1x1,
  * 2 dense 3x3 (K = 1152, ldx = 128), 3 transition (2x2 average of relu(s x + t), then the 1x1); x an fp32 NHWC map (.., ldx), s / t

@@ -273,7 +273,7 @@ int dense_block28_units(int K0, int nl);
 size_t dense_block28_scratch_halfs();   // per frame
 std::vector<unsigned char> pack_block28(const std::vector<Block14Layer> &layers, int K0);
 int launch_dense_block28(const DenseStreamArgs &a, hipStream_t s);
-// the two kernels as a table, in the order the encoder tries them (api.hip, dbg.hip)
+// the two kernels as a table, in the order the encoder tries them (encoder_plan.h, dbg.hip)
 struct DenseStreamKernel {
   int H;                         // the square map it runs
   const char *family;            // the name tn_densenet121_profile reports
@@ -318,11 +318,11 @@ struct StemArgs {
   const float *shift_u8 = nullptr;   // the shift for TN_LAYOUT_NHWC_U8 input (carries the constant of the integer staging, see above)
   const f16 *wp_zf_lo = nullptr;     // exact-weights mode: the lo halves of the weights (w = hi + lo), same fragment layout as wp_zf
   // Round 6: the pooled map is stored CENTRED, relu(bn(conv)) - m_c, with m_c the channel's mean as the consuming BatchNorms
-  // know it (api.hip "centred stem output").  The kernels get `shift` / `shift_u8` with m_c already subtracted and the ReLU's
+  // know it (encoder.hip "centred stem output").  The kernels get `shift` / `shift_u8` with m_c already subtracted and the ReLU's
   // floor -m_c here (max pool and ReLU commute with the subtraction: max(v - m, -m) = relu(v) - m); nullptr: floor 0.
   const float *floor = nullptr;      // [64]
 };
-// the host side of StemArgs (api.hip::fold_stem): fragment images and BatchNorm constants as the kernels read them
+// the host side of StemArgs (encoder.hip::fold_stem): fragment images and BatchNorm constants as the kernels read them
 struct StemFold {
   std::vector<f16> wp, wp_zf, wp_zf_lo;           // wp_zf_lo: exact-weights mode only
   std::vector<float> scale, shift, shift_u8;      // [64] each

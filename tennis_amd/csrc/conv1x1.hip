@@ -36,7 +36,7 @@ constexpr int smem_bytes() {
 // NB = output channels per workgroup (128, or 256 for the transitions with N >= 256: every column tile streams
 // the pixel tile again and repeats its BN+ReLU+average, so wider tiles cut both)
 // EX (exact-weights mode): w = hi + lo as two fp16 numbers, rows [hi (Kp) | lo (Kp)], Kp = K rounded up to the
-// k-tile (zero-padded; api.hip::split_hi_lo_rows); the k-tile loop runs over 2 Kp, the activation side (and its BatchNorm
+// k-tile (zero-padded; encoder.hip::split_hi_lo_rows); the k-tile loop runs over 2 Kp, the activation side (and its BatchNorm
 // constants) wrapping around after the hi half.  Round 6: also without POOL (the un-fused dense layers of map sizes no fused
 // kernel tiles - the 128 x 128 block of a 512 x 512 input - in the exact-weights mode).
 // ONCE (a transition with a single column tile): the activations are read exactly once, through non-temporal loads.

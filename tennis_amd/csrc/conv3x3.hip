@@ -21,7 +21,7 @@ constexpr int TILE_PX = 128;
 constexpr int RED_BYTES = 4 * TILE_PX * 32 * 4;  // 4 waves x 128 px x 32 n fp32 = 64 KiB
 
 // EX (exact-weights mode, round 6: the un-fused layers of map sizes no fused kernel tiles): w = hi + lo as two packed images,
-// the lo image 2 x 72 x 64 fragments further on (api.hip packs both MFMA layouts of an image back to back, then the next
+// the lo image 2 x 72 x 64 fragments further on (encoder.hip packs both MFMA layouts of an image back to back, then the next
 // image); every pixel fragment is multiplied with both.
 template <int V, bool EX = false>
 __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3x3Args a, int lds_px) {

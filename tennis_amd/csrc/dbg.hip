@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.h"
+#include "encoder_plan.h"
 #include "gemm_fp32x3.h"
 #include "linear.h"
 #include "rnn.h"
@@ -22,7 +23,7 @@ T *up(const std::vector<T> &h) {
 }
 }  // namespace
 
-std::vector<f16> pack_conv3x3(const float *w);  // api.hip
+std::vector<f16> pack_conv3x3(const float *w);  // encoder.hip
 
 // fp32 (32,128,3,3) -> the packed fp16 fragment image the conv3x3 kernel consumes (72*64*8 halfs).
 extern "C" int tn_dbg_pack_conv3x3(const float *w_host, uint16_t *out_host) {
@@ -135,7 +136,7 @@ extern "C" int tn_dbg_channel_mean(tn_ctx *ctx, const void *x_f16, int ld, int K
 
 // ---- the first and the last kernels of a forward: stem (+ maxpool) and head ----
 // The pooled stem map of B frames x (device, in `layout`) into y (device fp16, row stride ldy >= 64): conv0's raw weights (64,3,7,7)
-// and batchnorm0's parameters (host fp32) folded by the function tn_densenet121_create folds them with (api.hip::fold_stem), then
+// and batchnorm0's parameters (host fp32) folded by the function tn_densenet121_create folds them with (encoder.hip::fold_stem), then
 // the launchers of the forward - fused: launch_stem_pool; otherwise launch_stem into a map of its own + launch_maxpool3x3s2
 // (TN_NO_FUSE).  centre_host: m_c of the centred output or NULL (no floor).  Synchronous.
 extern "C" int tn_dbg_stem(tn_ctx *ctx, const float *w0_host, const float *gamma_host, const float *beta_host, const float *mean_host,
@@ -427,6 +428,59 @@ extern "C" int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int 
              "tn_dbg_rnn_route: gates*hidden must be <= 1024, hidden % 4 == 0, batch > 0, dirs 1 or 2");
   const tn_rnn_route r = rnn_route(gates, B, H, dirs);
   *nb = r.nb; *kr = r.kr; *big = r.big;
+  return TN_OK;
+}
+
+// The fp16 encoder's launches for an input size, create flags (and the TN_* environment of the call), batch and pass, as
+// tn_densenet121_profile would report them: families in first-seen order with launches, flops and bytes (ms 0).  Built from
+// what create and encoder_run_range follow (encoder_plan.h: enc_policy, enc_geom, enc_block_plan); host arithmetic only, no device
+// is touched.  Refuses what create refuses for the size and the flags, and the fp32 / fp32x3 modes, which are not planned.
+extern "C" int tn_dbg_encoder_plan(int height, int width, int flags, int batch, int calibrate, tn_kernel_stat *stats, int max_stats,
+                                   int *n_stats) {
+  TN_REQUIRE(stats && n_stats && max_stats > 0, "tn_dbg_encoder_plan: null argument");
+  TN_REQUIRE((flags & ~TN_ENC_EXACT_WEIGHTS) == 0, "tn_dbg_encoder_plan: unknown flag, or a mode that is not planned (TN_ENC_FP32, TN_ENC_FP32X3)");
+  TN_REQUIRE(batch > 0, "tn_dbg_encoder_plan: batch must be positive");
+  TN_REQUIRE(height >= 224 && width >= 224 && height <= 1024 && width <= 1024, "tn_dbg_encoder_plan: input size must be in [224,1024]");
+  const EncPolicy p = enc_policy(flags);
+  const EncGeom g = enc_geom(height, width);
+  if (const char *why = enc_refusal(p, g)) { tn_set_error(why); return TN_ERR_INVALID; }
+  std::vector<tn_kernel_stat> fams;
+  auto add = [&](const std::string &name, const EncCost &c) {
+    size_t i = 0;
+    while (i < fams.size() && name != fams[i].name) ++i;
+    if (i == fams.size()) {
+      tn_kernel_stat st;
+      memset(&st, 0, sizeof(st));
+      strncpy(st.name, name.c_str(), sizeof(st.name) - 1);
+      fams.push_back(st);
+    }
+    fams[i].launches += 1;
+    fams[i].flops += c.flops;
+    fams[i].bytes += c.bytes;
+  };
+  const double fB = (double)batch;
+  if (p.fuse) {
+    add("stem_conv_bn_relu_maxpool", stem_pool_cost(g, fB));
+  } else {
+    add("stem_conv7x7_bn_relu", stem_cost(g, fB));
+    add("maxpool3x3s2", maxpool_cost(g, fB));
+  }
+  for (int b = 0; b < 4; ++b) {
+    const int M = batch * g.Hb[b] * g.Wb[b];
+    for (const EncStep &st : enc_block_plan(p, g, b, batch, calibrate != 0)) {
+      if (st.route == ENC_LAYERWISE) {
+        add(family_name(st, g, b), conv1x1_cost(M, enc_layer_cin(g, b, st.l0)));
+        add("conv3x3_bnrelu", conv3x3_cost(M));
+      } else {
+        add(family_name(st, g, b), step_cost(st, g, b, M));
+      }
+    }
+    if (b < 3) add("transition_conv1x1_avgpool", transition_cost(M, batch * g.Hb[b + 1] * g.Wb[b + 1], g.Cb[b], g.Cb[b] / 2));
+  }
+  add("head_bnrelu_avgpool7", head_cost(g, fB));
+  const int n = (int)fams.size() < max_stats ? (int)fams.size() : max_stats;
+  for (int i = 0; i < n; ++i) stats[i] = fams[i];
+  *n_stats = n;
   return TN_OK;
 }
 

@@ -46,7 +46,7 @@ int launch_dense_strip_chain(const DenseStripChainArgs &a, hipStream_t s) {
   return a.W == 56 ? launch_dense_strip_chain_w56(a, s) : launch_dense_strip_chain_w28(a, s);
 }
 
-// ---- host-side packing (api.hip, dbg.hip) ----
+// ---- host-side packing (encoder.hip, dbg.hip) ----
 // 1x1 weights [128][K] (BN2's scale already folded in) + BN2's shift [128] -> v_mfma_f32_32x32x16_f16 A fragments
 // [K/16 + 1 k-steps][4 blocks][64 lanes][8]: lane l: bottleneck channel 32 mb + (l & 31); input channels of 64-channel
 // super-step u, k-step i: 64 u + 32 (l >> 5) + 8 i + j (a lane's four k-steps are 64 contiguous bytes of the pixel); the

@@ -242,7 +242,7 @@ __global__ void pack_trans_frags_kernel(const f16 *__restrict__ w, int N, int K,
 
 }  // namespace
 
-// host form of pack_trans_frags_kernel (api.hip packs a model's weights once, at create)
+// host form of pack_trans_frags_kernel (encoder.hip packs a model's weights once, at create)
 std::vector<f16> pack_trans_frags(const f16 *w, int N, int K) {
   std::vector<f16> out((size_t)N * K);
   for (int g = 0; g < K / 16; ++g)

@@ -63,7 +63,7 @@ def _bn(rng, prefix, c, var_center=1.0):
     }
 
 
-BN_EPS = 1e-5     # gluon BatchNorm default (csrc/api.hip kBnEps)
+BN_EPS = 1e-5     # gluon BatchNorm default (csrc/encoder.hip kBnEps)
 
 
 def _round_fp16_error_feedback(wf: np.ndarray, mean: np.ndarray) -> np.ndarray:
@@ -220,7 +220,7 @@ def as_fp16_model(params: dict, input_means: dict | None = None, bias_correction
 
     The 1x1 convolution of a dense layer (``stageB_conv{2l}``) is followed directly by a
     BatchNorm (``stageB_batchnorm{2l+1}``) whose scale the encoder folds into the
-    weights (the usual conv-BN fusion; csrc/api.hip, csrc/dense_strip_impl.h): for those the
+    weights (the usual conv-BN fusion; csrc/encoder.hip, csrc/dense_strip_impl.h): for those the
     number that is rounded to fp16 is ``scale[n] * w[n][k]``, and the converted weight is
     ``fp16(scale[n] w[n][k]) / scale[n]`` — one rounding per weight either way.  Round 5: the factor also carries the SCALE
     ``sw[k]`` of the BatchNorm in front of the convolution, whose ReLU the kernels evaluate as a clamp of the stored activation
@@ -283,7 +283,7 @@ def as_fp16_model(params: dict, input_means: dict | None = None, bias_correction
             prefix = k[:-len("conv0_weight")]
         with np.errstate(over="ignore", invalid="ignore"):
             folded = (v * s).astype(np.float32) if s is not None else v.astype(np.float32)
-        # the library refuses such a model at create ("a 1x1 weight leaves the fp16 range", csrc/api.hip): the conversion must not
+        # the library refuses such a model at create ("a 1x1 weight leaves the fp16 range", csrc/encoder.hip): the conversion must not
         # hand out inf / NaN weights silently - nor let the oracle and a saved checkpoint carry them
         amax = float(np.abs(folded).max()) if folded.size else 0.0
         if not np.isfinite(amax) or amax > 65504.0:

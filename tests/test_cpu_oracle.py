@@ -829,7 +829,7 @@ def test_operand_means_oracle_units_hold_together():
     convs, _, _ = W.densenet121_layout()
     assert list(m) == [pre + c["name"] + "_weight" for c in convs if c["kind"] != "stem"]
     assert all(m[pre + c["name"] + "_weight"].shape == (1, c["cin"]) for c in convs if c["kind"] != "stem")
-    numel, c = 0, W.INIT_FEATURES                     # csrc/api.hip tn_densenet121_input_means
+    numel, c = 0, W.INIT_FEATURES                     # csrc/encoder.hip tn_densenet121_input_means
     for b, nl in enumerate(W.BLOCK_CONFIG):
         numel += sum(c + W.GROWTH * l + 128 for l in range(nl))
         c += W.GROWTH * nl

@@ -148,7 +148,7 @@ def _kinds():
 def _centred_threshold_slack(q):
     """{block-1 1x1 weight name: (cin,) float64}: how far the library's clamp thresholds of stem channels 0 .. 63 may sit from the
     oracle's.  The library stores the pooled stem map centred, x - m_c (m_c: the average running_mean of the channel's seven
-    consumers, csrc/api.hip), and folds each consumer's BatchNorm on the centred map - its threshold is fp16(c - m_c) + m_c where
+    consumers, csrc/encoder.hip), and folds each consumer's BatchNorm on the centred map - its threshold is fp16(c - m_c) + m_c where
     the header's clamp has fp16(c).  A mean of a clamp moves by at most the move of its threshold: up to an fp16 ulp of c, which
     is 2 for a near-dead channel clipped at c ~ 3000 (the trained-looking set has them).  Zero for every other channel, and for a
     degenerate clamp (lo == hi), whose operand is 0 in both."""

@@ -483,7 +483,7 @@ def test_batch_larger_than_handle_is_an_error():
 def test_pipelined_forwards_with_changing_batch_size():
     """Pipelined split forwards share the workspace by row range per side stream; a call with a different batch size (a
     corpus' ragged last batch: 128 behind 256) moves the ranges across the streams and must be ordered behind everything
-    the earlier calls left on either of them (api.hip split path)."""
+    the earlier calls left on either of them (encoder.hip split path)."""
     from tennis_amd import weights as W
     from tennis_amd.engine import DenseNet121Features
     p = W.make_densenet121_weights(0)

@@ -84,7 +84,7 @@ def test_timed_path_parity(kind, mode, refs, report):
 def test_near_dead_batchnorm_channels(report):
     """7 % of the gammas of one BatchNorm group scaled by 1e-2 .. 1e-6 (what trained checkpoints contain), seeded weights otherwise:
     the exact-weights mode stays at the seeded model's error whatever the sign of the dead channels' beta (round 6: 4.8e-3 with
-    negative betas before the clamp form's constant was split at clamp(0, lo, hi): csrc/api.hip), and so do the default kernels
+    negative betas before the clamp form's constant was split at clamp(0, lo, hi): csrc/encoder.hip), and so do the default kernels
     on the plainly converted model."""
     import re
     from oracle.torch_ref import TorchDenseNet121
