@@ -55,6 +55,12 @@ int tn_dbg_conv3x3_dev(tn_ctx *ctx, const void *x_f16, const float *scale, const
 int tn_dbg_dense_layer_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K, const float *s1, const float *t1,
                            const void *w1_f16, const float *s2, const float *t2, const void *w3p_f16, int B,
                            int H, int W, unsigned long long *ts /* NULL or stamps */, int variant /* 0 auto, 1 big, 2 small */);
+/* nchain consecutive fused dense layers (K0, K0 + 32, ...) as one chained launch of the tile kernel (16x16, 14x14, 7x7): s1 ... w3p_f16
+ * are host arrays of nchain device pointers, one per layer, in the forms tn_dbg_dense_layer_dev takes; variant likewise (bit 17:
+ * exact weights; bit 19: nchain is passed on without the layer array, which the launcher has to refuse).  Synchronous. */
+int tn_dbg_dense_chain_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K0, int nchain, const float *const *s1, const float *const *t1,
+                           const void *const *w1_f16, const float *const *s2, const float *const *t2, const void *const *w3p_f16,
+                           int B, int H, int W, int variant);
 int tn_dbg_linear(tn_ctx *ctx, const float *x, const float *w, const float *bias, float *y, int M, int N,
                   int K);
 /* The reduction behind tn_densenet121_input_means on its own: out[c] (device fp32, K values) = mean over `rows` rows of the device

@@ -119,6 +119,36 @@ extern "C" int tn_dbg_dense_layer_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K
   return launch_dense_layer(a, ctx->stream);
 }
 
+// nchain consecutive fused dense layers (K0, K0 + 32, ...) in place on buf (B,H,W,ldc) as ONE chained launch: the per-layer device
+// pointers come as host arrays of nchain entries each; the DenseLayerDev array is built on the device here.  variant as
+// tn_dbg_dense_layer_dev (bit 17: exact weights; bit 19: hand the launcher nchain WITHOUT the layer array - a call it has to
+// refuse).  Synchronous; frees what it allocates.
+extern "C" int tn_dbg_dense_chain_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K0, int nchain, const float *const *s1, const float *const *t1,
+                                      const void *const *w1_f16, const float *const *s2, const float *const *t2, const void *const *w3p_f16,
+                                      int B, int H, int W, int variant) {
+  TN_REQUIRE(ctx && buf_f16 && s1 && t1 && w1_f16 && s2 && t2 && w3p_f16, "tn_dbg_dense_chain_dev: null argument");
+  TN_REQUIRE(nchain > 0 && nchain <= 64, "tn_dbg_dense_chain_dev: nchain must be 1 ... 64");
+  std::vector<DenseLayerDev> cd(nchain);
+  for (int l = 0; l < nchain; ++l) {
+    TN_REQUIRE(s1[l] && t1[l] && w1_f16[l] && s2[l] && t2[l] && w3p_f16[l], "tn_dbg_dense_chain_dev: null layer operand");
+    cd[l] = DenseLayerDev{s1[l], t1[l], (const f16 *)w1_f16[l], s2[l], t2[l], (const f16 *)w3p_f16[l]};
+  }
+  TN_ON_DEVICE(ctx->device);
+  DenseLayerDev *chain = up(cd);
+  TN_REQUIRE(chain, "tn_dbg_dense_chain_dev: device allocation failed");
+  DenseLayerArgs a{(f16 *)buf_f16, ldc, K0, cd[0].s1, cd[0].t1, cd[0].w1, cd[0].s2, cd[0].t2, cd[0].w3p, B, H, W};
+  a.variant = variant & 0xffff;
+  a.exact = (variant >> 17) & 1;
+  a.chain = ((variant >> 19) & 1) ? nullptr : chain;
+  a.nchain = nchain;
+  const int rc = launch_dense_layer(a, ctx->stream);
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(chain);
+  if (rc) return rc;
+  TN_HIP_CHECK(e);
+  return TN_OK;
+}
+
 // The calibration statistic of tn_densenet121_input_means on its own: per-channel mean over `rows` rows of x (rows, ld) fp16 of
 // relu(scale x + shift), or of clamp(x, lo = scale, hi = shift) with `clamp`; one synchronous launch_channel_mean, all operands
 // on the device, the scratch the caller's (scratch_bytes: at least 32 K doubles)

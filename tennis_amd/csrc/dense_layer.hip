@@ -12,6 +12,6 @@ bool dense_layer_supported(int H, int W) { return dense_layer_big_supported(H, W
 int dense_layer_kmax(int W) { return dense_layer_big_kmax(W); }
 
 int launch_dense_layer(const DenseLayerArgs &a, hipStream_t s) {
-  TN_REQUIRE(dense_layer_big_supported(a.H, a.W), "dense_layer: unsupported spatial size");
+  TN_REQUIRE(dense_layer_big_supported(a.H, a.W), "dense_layer: unsupported spatial size " + std::to_string(a.H) + " x " + std::to_string(a.W));
   return launch_dense_layer_big(a, s);
 }

@@ -12,16 +12,17 @@
 //   trip) through a 3-stage ring with counted vmcnt waits and ONE raw s_barrier per
 //   k-tile, so two stages are always in flight behind the MFMAs.  The DMA destination is
 //   lane-linear, so the bank-conflict swizzle is applied to the per-lane SOURCE address
-//   and again on the fragment read.  BN1+ReLU (fp32 math, one rounding) is applied to the
+//   and again on the fragment read.  BN1+ReLU (a clamp: no arithmetic, no rounding) is applied to the
 //   pixel fragment after the ds_read; each wave owns all 128 output channels of its rows,
 //   so every element is transformed exactly once.  v_mfma_f32_16x16x32_f16 with the
 //   weight fragment as the A operand: a lane ends with 4 consecutive channels of a pixel.
 // Epilogue A: BN2+ReLU in fp32, fp16, scatter into an LDS tile of (ROUT+2) x (W+2) pixel
 //   slots of 256 B with the zero padding materialised (the conv pads after the activation).
 // Phase B: the 3x3 is a constant-offset walk over the flattened tile with
-//   v_mfma_f32_32x32x16_f16 — no bounds logic; K = 1152 is split by channel halves over
-//   wave pairs (partials meet in LDS); the packed 3x3 weights stream through a 2 x 8 KiB
-//   LDS ring, one tap per barrier, three taps of prefetch in registers.
+//   v_mfma_f32_16x16x32_f16 on 16-slot output fragments - no bounds logic; a wave owns whole
+//   fragments over the full K = 9 x 128, so there are no partial sums to combine; the packed
+//   3x3 weights stream through a 3 x 8 KiB LDS ring, one barrier per tap (in its middle),
+//   three taps of prefetch in registers (docs/kernels.md).
 // Writing the 32 output channels at channel offset K of the same buffer IS the concat.
 #include <type_traits>
 
@@ -736,8 +737,9 @@ __global__ __launch_bounds__(512) void dense_layer_kernel(DenseLayerArgs a) {
         if (idx < nxK) { nxs[i] = dn.s1[idx]; nxt[i] = dn.t1[idx]; }
       }
       if (t < 256) nx2 = t < 128 ? dn.s2[t] : dn.t2[t - 128];
-      // the next layer's first two k-tiles (its own weight pitch; a chained layer has at least four k-tiles, so
-      // the activation pointers do not wrap yet)
+      // the next layer's first two (PP 4: three) k-tiles, its own weight pitch.  The request is unconditional, goes out before this
+      // layer's output channels [K, K + 32) are stored and does not wrap the activation pointers: those k-tiles have to lie inside
+      // the channels this layer read (2 BK <= K, PP 4: 3 BK <= K), which launch_dense_layer_big requires of a chain's first layer
       const int nxc = (nxK + BK - 1) / BK;
       set_src(xbase, MA, dn.w1, EX ? 2 * nxc * BK : nxK);
 #pragma unroll
@@ -823,12 +825,40 @@ bool dense_layer_big_supported(int H, int W) { return H == W && (H == 56 || H ==
 // than 224 can put a 56x56 map into the second block (448: K up to 480), where the tile kernel has no room for it
 int dense_layer_big_kmax(int W) { return W == 56 ? 256 : W == 28 ? 512 : 1024; }
 
+// k-tiles the chained kernel requests for a layer while the layer before it still computes its last stores (PP 4: three, else two).
+// The request is unconditional, does not wrap the activation pointers (exact mode) and goes out BEFORE the current layer's 32 output
+// channels are stored: those k-tiles have to lie inside the channels the current layer READ, primed * BK <= K.  K grows along the
+// chain, so the first layer decides; a chain that starts below that is refused - what the launcher accepts is what the kernel
+// computes.  (The rule also gives the next layer more k-tiles than are requested ahead, so in exact mode the wrap behind k-tile
+// nkc - 1 is always left to advance().)
+static int chain_primed_ktiles(int pp) { return pp == 4 ? 3 : 2; }
+
 int launch_dense_layer_big(const DenseLayerArgs &a, hipStream_t s) {
   const int klast = a.K + 32 * (a.nchain > 0 ? a.nchain - 1 : 0);
-  TN_REQUIRE(a.K % 32 == 0 && klast <= 1024 && a.ldc % 8 == 0 && klast + 32 <= a.ldc, "dense_layer: bad channel geometry");
+  // (the message names the geometry; put together only when a call is refused)
+  const auto geom = [&] {
+    return std::to_string(a.H) + " x " + std::to_string(a.W) + ", K = " + std::to_string(a.K) + ", ldc = " + std::to_string(a.ldc) +
+           ", nchain = " + std::to_string(a.nchain) + (a.exact ? ", exact weights" : "");
+  };
+  TN_REQUIRE(dense_layer_big_supported(a.H, a.W), "dense_layer: unsupported spatial size " + geom());
+  TN_REQUIRE(a.nchain >= 0 && a.K >= 32 && a.K % 32 == 0, "dense_layer: the input channels must be a positive multiple of 32: " + geom());
+  TN_REQUIRE(klast <= dense_layer_big_kmax(a.W), "dense_layer: more input channels than this block's table space holds (" +
+                                                     std::to_string(dense_layer_big_kmax(a.W)) + "): " + geom());
+  TN_REQUIRE(a.ldc % 8 == 0, "dense_layer: the row pitch must be a multiple of 8: " + geom());
+  TN_REQUIRE(klast + 32 <= a.ldc, "dense_layer: the row pitch does not hold the last layer's output: " + geom());
+  if (a.nchain > 0) {
+    TN_REQUIRE(a.H == 14 || a.H == 7 || a.H == 16, "dense_layer: layer chaining needs whole-frame tiles (16x16, 14x14, 7x7): " + geom());
+    TN_REQUIRE(a.chain, "dense_layer: nchain > 0 without the chain's layer array: " + geom());
+    if (a.nchain > 1) {
+      const int bk = a.H == 16 ? 32 : 64;
+      const int pp = (!a.exact && a.H == 7 && !(a.variant & (32 | 512))) ? 4 : 2;
+      const int need = chain_primed_ktiles(pp) * bk;
+      TN_REQUIRE(a.K >= need, "dense_layer: a chain of this geometry starts at K >= " + std::to_string(need) + " (the chained kernel requests the next layer's first " +
+                                  std::to_string(chain_primed_ktiles(pp)) + " k-tiles of " + std::to_string(bk) + " channels before the current layer's output is stored): " + geom());
+    }
+  }
   if (a.exact) {     // hi + lo weights: the default K loop only
     if (a.nchain > 0) {
-      TN_REQUIRE(a.H == a.W && (a.H == 14 || a.H == 7 || a.H == 16) && a.chain, "dense_layer: layer chaining needs whole-frame tiles (16x16, 14x14, 7x7)");
       if (a.H == 14) return launch_geom<14, 14, 256, 64, 2, true, true>(a, s);
       if (a.H == 16) return launch_geom<16, 16, 384, 32, 2, true, true>(a, s);
       return launch_geom<7, 7, 64, 64, 2, true, true>(a, s);
@@ -841,10 +871,9 @@ int launch_dense_layer_big(const DenseLayerArgs &a, hipStream_t s) {
     if (a.H == 64 && a.W == 64) return launch_geom<64, 4, 384, 32, 2, false, true>(a, s);
     if (a.H == 32 && a.W == 32) return launch_geom<32, 8, 384, 32, 2, false, true>(a, s);
     if (a.H == 16 && a.W == 16) return launch_geom<16, 16, 384, 32, 2, false, true>(a, s);
-    TN_REQUIRE(false, "dense_layer: unsupported spatial size");
+    TN_REQUIRE(false, "dense_layer: unsupported spatial size " + geom());
   }
   if (a.nchain > 0) {
-    TN_REQUIRE(a.H == a.W && (a.H == 14 || a.H == 7 || a.H == 16) && a.chain, "dense_layer: layer chaining needs whole-frame tiles (16x16, 14x14, 7x7)");
     if (a.H == 14) return launch_geom<14, 14, 256, 64, 2, true>(a, s);
     if (a.H == 16) return launch_geom<16, 16, 384, 32, 2, true>(a, s);
     // 7x7: 4 x 2 wave split over a 64-row tile (variant bit 5: the 8 x 1 split over 128 rows, for A/B runs)
@@ -870,5 +899,5 @@ int launch_dense_layer_big(const DenseLayerArgs &a, hipStream_t s) {
     return TN_GEOM(7, 7, 128, 64);
   }
 #undef TN_GEOM
-  TN_REQUIRE(false, "dense_layer: unsupported spatial size");
+  TN_REQUIRE(false, "dense_layer: unsupported spatial size " + geom());
 }
