@@ -161,6 +161,24 @@ int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int *kr, int *b
  * for the size and the flags, and TN_ENC_FP32 / TN_ENC_FP32X3, which are not planned.  Host arithmetic only: touches no device. */
 int tn_dbg_encoder_plan(int height, int width, int flags, int batch, int calibrate, tn_kernel_stat *stats, int max_stats, int *n_stats);
 
+/* The parameter table of a training handle, built by the function its create calls (csrc/param_table.h): one row per readable name,
+ * in the order of the flat buffers.  where: 0 the flat parameter / gradient buffers (tn_*_buffers) at `offset` floats, 1 the
+ * backbone's running-statistics buffer at `offset`, 2 a device buffer of its own (the "<bn>_batch_mean" / "_batch_var" test hooks;
+ * offset 0).  The backbone's convolution weights sit in the flat buffers in (O, kh, kw, I) order.
+ * which / dims / prefixes: TN_TRAINER_HEAD (gates, input, hidden, classes), rnn and dense prefix; TN_TRAINER_GNMT (gates, input,
+ * hidden, embed, vocab, num_layers, num_bi_layers), the prefix, prefix_b ignored; TN_TRAINER_BACKBONE (classes, or 0 for the
+ * backbone alone), backbone prefix and the classifier's (NULL with 0 classes).  Writes at most max_rows rows (rows NULL with
+ * max_rows 0: count only); *n_rows the table's rows, *numel / *state_numel (optional) the floats of the flat buffers / of the
+ * state buffer.  Host arithmetic only: touches no device. */
+enum { TN_TRAINER_HEAD = 0, TN_TRAINER_GNMT = 1, TN_TRAINER_BACKBONE = 2 };
+typedef struct tn_param_row {
+  char name[96];
+  int where;
+  int64_t offset, count;
+} tn_param_row;
+int tn_dbg_trainer_params(int which, const int *dims, int n_dims, const char *prefix_a, const char *prefix_b, tn_param_row *rows,
+                          int max_rows, int *n_rows, int64_t *numel, int64_t *state_numel);
+
 /* One convolution of the fp32x3 encoder mode (csrc/dense_fp32x3.hip; which = 0) or, on the same operands, of the fp32 mode
  * (csrc/dense_fp32.hip; which = 1).  kind: 0 stem 7x7/2 (x: B frames in `layout`, H x W; epilogue relu(es y + et)), 1 dense 1x1,
  * 2 dense 3x3 (K = 1152, ldx = 128), 3 transition (2x2 average of relu(s x + t), then the 1x1); x an fp32 NHWC map (.., ldx), s / t

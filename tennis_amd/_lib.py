@@ -42,6 +42,13 @@ class TnKernelStat(C.Structure):
                 ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class TnParamRow(C.Structure):
+    _fields_ = [("name", C.c_char * 96), ("where", C.c_int), ("offset", C.c_int64), ("count", C.c_int64)]
+
+
+TRAINER_HEAD, TRAINER_GNMT, TRAINER_BACKBONE = 0, 1, 2      # tn_dbg_trainer_params: which handle's table
+PARAM_FLAT, PARAM_STATE, PARAM_PTR = 0, 1, 2                # tn_param_row.where
+
 _P = C.c_void_p
 _SIGS = {
     "tn_version": (C.c_int, []),
@@ -172,6 +179,8 @@ _SIGS = {
     "tn_dbg_gemm_nn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_rnn_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tn_dbg_encoder_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TnKernelStat), C.c_int, C.POINTER(C.c_int)]),
+    "tn_dbg_trainer_params": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p, C.c_char_p, C.POINTER(TnParamRow), C.c_int,
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tn_dbg_linear_bnrelu": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_linear_fp32x3": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_gemm_tn_fp32x3": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
@@ -237,6 +246,20 @@ def check(rc: int, what: str = ""):
     if rc != 0:
         msg = load().tn_last_error().decode("utf-8", "replace")
         raise RuntimeError(f"libtennis_hip {what} failed ({rc}): {msg}")
+
+
+def trainer_params(which: int, dims, prefix_a: str, prefix_b: str | None = None):
+    """``tn_dbg_trainer_params``: ([(name, where, offset, count), ...], flat numel, state numel) of a training handle's parameter
+    table; touches no device."""
+    lib = load()
+    d = (C.c_int * len(dims))(*[int(v) for v in dims])
+    b = None if prefix_b is None else prefix_b.encode()
+    n, numel, ns = C.c_int(), C.c_int64(), C.c_int64()
+    check(lib.tn_dbg_trainer_params(which, d, len(dims), prefix_a.encode(), b, None, 0, C.byref(n), None, None), "tn_dbg_trainer_params")
+    rows = (TnParamRow * n.value)()
+    check(lib.tn_dbg_trainer_params(which, d, len(dims), prefix_a.encode(), b, rows, n.value, C.byref(n), C.byref(numel), C.byref(ns)),
+          "tn_dbg_trainer_params")
+    return [(r.name.decode(), r.where, r.offset, r.count) for r in rows], numel.value, ns.value
 
 
 def make_params(params: dict):

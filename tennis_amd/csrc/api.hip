@@ -271,18 +271,13 @@ extern "C" int tn_temporal_pool_windows(tn_ctx *ctx, const float *feats, int row
 }
 
 // ---- temporal-head training step -----------------------------------------------------
-struct tn_head {
-  tn_ctx *ctx;
-  DevPool pool;
+struct tn_head : TrainParams, HeadOffsets {
   int F, H, C, maxB, maxT;
   int G;                           // gates per cell: 3 GRU, 4 LSTM
-  long n;                          // parameters in the flat buffers
-  long o_wi, o_bi, o_wh, o_bh, o_wd, o_bd;
-  float *w, *g, *mom;              // [n] parameters, gradients, momentum
+  float *mom;                      // [n] momentum, next to the parameters w and the gradients g
   float *whT;                      // [2][H][G*H] transposed h2h for the forward recurrence
   float *gi, *seq, *gates, *pooled, *dlog, *dpool, *dseq, *dgi, *dgh, *hprev, *logits, *loss;
   int32_t *arg;
-  std::string rnn_prefix, dense_prefix;
 };
 
 static int head_refresh_whT(tn_head *h) {
@@ -303,38 +298,23 @@ extern "C" int tn_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int
   TN_REQUIRE(input_size > 0 && hidden > 0 && hidden % 4 == 0 && G * hidden <= 1024 && classes > 0 && max_batch > 0 &&
                  max_steps > 0, "tn_head_create: bad shape (gates*hidden must be <= 1024, hidden % 4 == 0)");
   TN_ON_DEVICE(ctx->device);
-  ParamMap pm(params, n_params);
   const int F = input_size, H = hidden, C = classes, GH = G * hidden;
   tn_head *h = new tn_head();
   h->ctx = ctx; h->G = G; h->F = F; h->H = H; h->C = C; h->maxB = max_batch; h->maxT = max_steps;
-  h->rnn_prefix = rnn_prefix; h->dense_prefix = dense_prefix;
-  h->o_wi = 0; h->o_bi = h->o_wi + 2L * GH * F; h->o_wh = h->o_bi + 2L * GH; h->o_bh = h->o_wh + 2L * GH * H;
-  h->o_wd = h->o_bh + 2L * GH; h->o_bd = h->o_wd + (long)C * 2 * H; h->n = h->o_bd + C;
-  std::vector<float> w(h->n);
+  h->table = head_param_table(G, F, H, C, rnn_prefix, dense_prefix, h);
+  h->n = h->table.n;
   auto fail = [&](int rc) { h->pool.release(); delete h; return rc; };
-  for (int d = 0; d < 2; ++d) {
-    const std::string dp = h->rnn_prefix + (d == 0 ? "l0_" : "r0_");
-    const float *a = pm.get(dp + "i2h_weight", (int64_t)GH * F), *b = pm.get(dp + "h2h_weight", (int64_t)GH * H);
-    const float *c = pm.get(dp + "i2h_bias", GH), *e = pm.get(dp + "h2h_bias", GH);
-    if (!a || !b || !c || !e) return fail(TN_ERR_MISSING);
-    memcpy(&w[h->o_wi + (long)d * GH * F], a, sizeof(float) * GH * F);
-    memcpy(&w[h->o_bi + (long)d * GH], c, sizeof(float) * GH);
-    memcpy(&w[h->o_wh + (long)d * GH * H], b, sizeof(float) * GH * H);
-    memcpy(&w[h->o_bh + (long)d * GH], e, sizeof(float) * GH);
-  }
-  const float *wd = pm.get(h->dense_prefix + "weight", (int64_t)C * 2 * H), *bd = pm.get(h->dense_prefix + "bias", C);
-  if (!wd || !bd) return fail(TN_ERR_MISSING);
-  memcpy(&w[h->o_wd], wd, sizeof(float) * C * 2 * H);
-  memcpy(&w[h->o_bd], bd, sizeof(float) * C);
+  std::vector<float> w, st;
+  if (!h->table.load(ParamMap(params, n_params), w, st)) return fail(TN_ERR_MISSING);
   h->w = h->pool.upload(w);
   const size_t rows = (size_t)max_batch * max_steps;
-  auto fl = [&](size_t n) { return (float *)h->pool.alloc(n * sizeof(float)); };
+  auto fl = [&](size_t n) { return h->pool.alloc<float>(n); };
   h->g = fl(h->n); h->mom = fl(h->n); h->whT = fl(2L * H * GH);
   h->gi = fl(rows * 2 * GH); h->seq = fl(rows * 2 * H); h->gates = fl(2 * rows * (G + 1) * H);
   h->pooled = fl((size_t)max_batch * 2 * H); h->dlog = fl((size_t)max_batch * C); h->dpool = fl((size_t)max_batch * 2 * H);
   h->dseq = fl(rows * 2 * H); h->dgi = fl(rows * 2 * GH); h->dgh = fl(rows * 2 * GH); h->hprev = fl(2 * rows * H);
   h->logits = fl((size_t)max_batch * C); h->loss = fl(max_batch);
-  h->arg = (int32_t *)h->pool.alloc((size_t)max_batch * 2 * H * sizeof(int32_t));
+  h->arg = h->pool.alloc<int32_t>((size_t)max_batch * 2 * H);
   if (h->pool.failed) { tn_set_error("device allocation failed"); return fail(TN_ERR_NOMEM); }
   TN_HIP_CHECK(hipMemsetAsync(h->mom, 0, h->n * sizeof(float), ctx->stream));
   TN_HIP_CHECK(hipMemsetAsync(h->g, 0, h->n * sizeof(float), ctx->stream));
@@ -389,11 +369,7 @@ extern "C" int tn_head_forward_backward(tn_head *h, const float *x, const int32_
 }
 
 extern "C" int tn_head_buffers(tn_head *h, float **params_dev, float **grads_dev, int64_t *numel) {
-  TN_REQUIRE(h, "tn_head_buffers: null handle");
-  if (params_dev) *params_dev = h->w;
-  if (grads_dev) *grads_dev = h->g;
-  if (numel) *numel = h->n;
-  return TN_OK;
+  return train_buffers("tn_head_buffers", h, params_dev, grads_dev, numel);
 }
 
 extern "C" int tn_head_sgd_step(tn_head *h, float lr, float momentum, float wd, float rescale_grad) {
@@ -404,28 +380,8 @@ extern "C" int tn_head_sgd_step(tn_head *h, float lr, float momentum, float wd, 
   return head_refresh_whT(h);
 }
 
-extern "C" int tn_head_read_param(tn_head *h, const char *name_c, int gradient, float *out_host, int64_t capacity,
-                                  int64_t *numel) {
-  TN_REQUIRE(h && name_c && out_host && numel, "tn_head_read_param: null argument");
-  const std::string name(name_c);
-  const long GH = (long)h->G * h->H;
-  long off = -1, cnt = 0;
-  for (int d = 0; d < 2; ++d) {
-    const std::string dp = h->rnn_prefix + (d == 0 ? "l0_" : "r0_");
-    if (name == dp + "i2h_weight") { off = h->o_wi + d * GH * h->F; cnt = GH * h->F; }
-    if (name == dp + "i2h_bias") { off = h->o_bi + d * GH; cnt = GH; }
-    if (name == dp + "h2h_weight") { off = h->o_wh + d * GH * h->H; cnt = GH * h->H; }
-    if (name == dp + "h2h_bias") { off = h->o_bh + d * GH; cnt = GH; }
-  }
-  if (name == h->dense_prefix + "weight") { off = h->o_wd; cnt = (long)h->C * 2 * h->H; }
-  if (name == h->dense_prefix + "bias") { off = h->o_bd; cnt = h->C; }
-  TN_REQUIRE(off >= 0, "tn_head_read_param: unknown parameter name");
-  TN_REQUIRE(capacity >= cnt, "tn_head_read_param: host buffer too small");
-  TN_ON_DEVICE(h->ctx->device);
-  TN_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));
-  TN_HIP_CHECK(hipMemcpy(out_host, (gradient ? h->g : h->w) + off, sizeof(float) * cnt, hipMemcpyDeviceToHost));
-  *numel = cnt;
-  return TN_OK;
+extern "C" int tn_head_read_param(tn_head *h, const char *name, int gradient, float *out_host, int64_t capacity, int64_t *numel) {
+  return train_read_param("tn_head_read_param", h, name, gradient, out_host, capacity, numel);
 }
 
 extern "C" int tn_head_destroy(tn_head *h) {
@@ -463,9 +419,7 @@ extern "C" int tn_cnnrnn_trainer_create(tn_ctx *ctx, tn_rnn_kind kind, const tn_
   // the hidden size: <rnn_prefix>l0_i2h_bias has gates * hidden entries
   const int G = kind == TN_RNN_GRU ? 3 : 4;
   const std::string bias_name = std::string(rnn_prefix) + "l0_i2h_bias";
-  int hidden = -1;
-  for (int i = 0; i < n_params; ++i)
-    if (bias_name == params[i].name) hidden = (int)(params[i].numel / G);
+  const int hidden = (int)(ParamMap(params, n_params).numel(bias_name) / G);
   if (hidden <= 0) { tn_set_error("missing parameter: " + bias_name); return TN_ERR_MISSING; }
   long fit = -1;
   tn_finetune *bb = nullptr;
@@ -512,12 +466,7 @@ extern "C" int tn_cnnrnn_trainer_forward_backward(tn_cnnrnn_trainer *t, const fl
 extern "C" int tn_cnnrnn_trainer_buffers(tn_cnnrnn_trainer *t, float **backbone_params, float **backbone_grads, int64_t *backbone_numel,
                                          float **head_params, float **head_grads, int64_t *head_numel) {
   TN_REQUIRE(t, "tn_cnnrnn_trainer_buffers: null handle");
-  float *w, *g, *mom;
-  long n;
-  ft_param_buffers(t->bb, &w, &g, &mom, &n);
-  if (backbone_params) *backbone_params = w;
-  if (backbone_grads) *backbone_grads = g;
-  if (backbone_numel) *backbone_numel = n;
+  if (int rc = tn_finetune_buffers(t->bb, backbone_params, backbone_grads, backbone_numel)) return rc;
   return tn_head_buffers(t->head, head_params, head_grads, head_numel);
 }
 
@@ -594,12 +543,12 @@ extern "C" int tn_gnmt_frames_trainer_create(tn_ctx *ctx, const tn_param *params
   const int F = ft_feature_dim(bb), G = cell_kind == TN_RNN_GRU ? 3 : 4;
   // the captioner's first layer reads the backbone's features: refuse parameters made for another width
   const std::string w0 = std::string(prefix) + (num_bi_layers > 0 ? "enc_rnn0_l_i2h_weight" : "enc_rnn0_i2h_weight");
-  for (int i = 0; i < n_params; ++i)
-    if (w0 == params[i].name && params[i].numel != (int64_t)G * hidden * F) {
-      tn_set_error("tn_gnmt_frames_trainer_create: " + w0 + " is not (gates * hidden, " + std::to_string(F) + "), the backbone's feature width");
-      tn_finetune_destroy(bb);
-      return TN_ERR_INVALID;
-    }
+  const int64_t w0_numel = ParamMap(params, n_params).numel(w0);
+  if (w0_numel >= 0 && w0_numel != (int64_t)G * hidden * F) {
+    tn_set_error("tn_gnmt_frames_trainer_create: " + w0 + " is not (gates * hidden, " + std::to_string(F) + "), the backbone's feature width");
+    tn_finetune_destroy(bb);
+    return TN_ERR_INVALID;
+  }
   tn_gnmt_trainer *cap = nullptr;
   rc = tn_gnmt_trainer_create_ex(ctx, params, n_params, prefix, cell_kind, F, hidden, embed, vocab, num_layers, num_bi_layers, flags,
                                  max_batch, max_src_len, max_tgt_len, &cap);
@@ -643,12 +592,7 @@ extern "C" int tn_gnmt_frames_trainer_forward_backward(tn_gnmt_frames_trainer *t
 extern "C" int tn_gnmt_frames_trainer_buffers(tn_gnmt_frames_trainer *t, float **backbone_params, float **backbone_grads,
                                               int64_t *backbone_numel, float **params_dev, float **grads_dev, int64_t *numel) {
   TN_REQUIRE(t, "tn_gnmt_frames_trainer_buffers: null handle");
-  float *w, *g, *mom;
-  long n;
-  ft_param_buffers(t->bb, &w, &g, &mom, &n);
-  if (backbone_params) *backbone_params = w;
-  if (backbone_grads) *backbone_grads = g;
-  if (backbone_numel) *backbone_numel = n;
+  if (int rc = tn_finetune_buffers(t->bb, backbone_params, backbone_grads, backbone_numel)) return rc;
   return tn_gnmt_trainer_buffers(t->cap, params_dev, grads_dev, numel);
 }
 

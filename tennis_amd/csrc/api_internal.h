@@ -1,51 +1,80 @@
-// What the handles of api.hip and encoder.hip share on the host: the device allocations of a handle and the lookup of its
-// parameters by name.
+// What the handles of api.hip, encoder.hip, finetune.hip and captioner.hip share on the host: the device allocations of a handle
+// (DevPool), the lookup of its parameters by name and the table of where each lives (param_table.h), and - for the training
+// handles - the flat buffers with the one read-back and the one buffers query that go through that table (TrainParams).
 #pragma once
-#include <map>
 #include <string>
 #include <vector>
 
 #include "common.h"
+#include "param_table.h"
 
 struct DevPool {  // owns device allocations of one handle
   std::vector<void *> ptrs;
   size_t bytes = 0;
   bool failed = false;
-  void *alloc(size_t n) {
+  bool dry = false;  // count the bytes only (what a handle would need), allocate nothing
+  void *alloc(size_t n) {  // n bytes
+    bytes += n;
+    if (dry) return nullptr;
     void *p = nullptr;
     if (hipMalloc(&p, n ? n : 16) != hipSuccess) { failed = true; return nullptr; }
     ptrs.push_back(p);
-    bytes += n;
     return p;
   }
   template <typename T>
-  T *upload(const std::vector<T> &h) {
-    T *d = (T *)alloc(h.size() * sizeof(T));
-    if (d && hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { failed = true; return nullptr; }
+  T *alloc(size_t n) {  // n elements; a request for none counts, and is, one element
+    return (T *)alloc((n ? n : 1) * sizeof(T));
+  }
+  template <typename T>
+  T *upload(const T *h, size_t n) {
+    T *d = (T *)alloc(n * sizeof(T));
+    if (d && hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { failed = true; return nullptr; }
     return d;
   }
+  template <typename T>
+  T *upload(const std::vector<T> &h) { return upload(h.data(), h.size()); }
   void release() {
     for (void *p : ptrs) (void)hipFree(p);
     ptrs.clear();
   }
 };
 
-struct ParamMap {
-  std::map<std::string, const tn_param *> m;
-  ParamMap(const tn_param *p, int n) {
-    for (int i = 0; i < n; ++i) m[p[i].name] = &p[i];
-  }
-  const float *get(const std::string &name, int64_t numel) const {
-    auto it = m.find(name);
-    if (it == m.end()) {
-      tn_set_error("missing parameter: " + name);
-      return nullptr;
-    }
-    if (it->second->numel != numel) {
-      tn_set_error("parameter " + name + " has " + std::to_string(it->second->numel) + " elements, expected " +
-                   std::to_string(numel));
-      return nullptr;
-    }
-    return it->second->data_host;
-  }
+// The head of every training handle (tn_head, tn_finetune, tn_gnmt_trainer): the flat parameter / gradient buffers, the state
+// buffer of the handles that have one, and the table that names their contents.
+struct TrainParams {
+  tn_ctx *ctx = nullptr;
+  DevPool pool;
+  ParamTable table;
+  long n = 0;                 // parameters in the flat buffers (= table.n)
+  float *w = nullptr, *g = nullptr, *state = nullptr;
 };
+
+// *_read_param of a training handle: the named parameter (a convolution weight back in (O, I, kh, kw) order), its gradient
+// (gradient = 1; state and pointer rows have none and read the same either way) into out_host.  fn: the caller's name, for the errors.
+inline int train_read_param(const char *fn, TrainParams *h, const char *name, int gradient, float *out_host, int64_t capacity,
+                            int64_t *numel) {
+  TN_REQUIRE(h && name && out_host && numel, std::string(fn) + ": null argument");
+  const ParamTable::Row *r = h->table.find(name);
+  TN_REQUIRE(r && (r->where != ParamTable::PTR || r->ptr), std::string(fn) + ": unknown parameter name");
+  TN_REQUIRE(capacity >= r->count, std::string(fn) + ": host buffer too small");
+  TN_ON_DEVICE(h->ctx->device);
+  TN_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));
+  const float *dev = r->where == ParamTable::PTR ? r->ptr : (r->where == ParamTable::STATE ? h->state : gradient ? h->g : h->w) + r->off;
+  if (r->O) {
+    std::vector<float> tmp(r->count);
+    TN_HIP_CHECK(hipMemcpy(tmp.data(), dev, sizeof(float) * r->count, hipMemcpyDeviceToHost));
+    conv_from_gemm(tmp.data(), out_host, r->O, r->I, r->kh, r->kw);
+  } else {
+    TN_HIP_CHECK(hipMemcpy(out_host, dev, sizeof(float) * r->count, hipMemcpyDeviceToHost));
+  }
+  *numel = r->count;
+  return TN_OK;
+}
+
+inline int train_buffers(const char *fn, TrainParams *h, float **params_dev, float **grads_dev, int64_t *numel) {
+  TN_REQUIRE(h, std::string(fn) + ": null handle");
+  if (params_dev) *params_dev = h->w;
+  if (grads_dev) *grads_dev = h->g;
+  if (numel) *numel = h->n;
+  return TN_OK;
+}

@@ -14,11 +14,10 @@
 // looks at a device flag every 16 steps only to stop early once every beam has finished.
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "api_internal.h"
 #include "linear.h"
 #include "rnn.h"
 #include "train.h"
@@ -1073,24 +1072,6 @@ __global__ void trn_mul_kernel(const float *__restrict__ x, const float *__restr
   if (i < n) y[i] = x[i] * m[i];
 }
 
-struct DevBuf {
-  std::vector<void *> ptrs;
-  bool failed = false;
-  template <typename T>
-  T *alloc(size_t n) {
-    void *p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) { failed = true; return nullptr; }
-    ptrs.push_back(p);
-    return (T *)p;
-  }
-  float *upload(const float *h, size_t n) {
-    float *d = alloc<float>(n);
-    if (d && hipMemcpy(d, h, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) failed = true;
-    return d;
-  }
-  void release() { for (void *p : ptrs) (void)hipFree(p); ptrs.clear(); }
-};
-
 }  // namespace
 
 // a decoder cell between the first and the last one (num_layers > 2)
@@ -1098,7 +1079,7 @@ struct GnmtMid { float *w, *b, *sx, *g, *hn, *cn, *ccur; };
 
 struct tn_gnmt {
   tn_ctx *ctx;
-  DevBuf pool;
+  DevPool pool;
   // encoder: num_bi_layers bidirectional layers (F | 2H -> 2H), then uni-directional ones (2H | H -> H); gnmt.py:84-111
   std::vector<tn_birnn *> enc;
   int NL, NBI;
@@ -1157,14 +1138,7 @@ extern "C" int tn_gnmt_create_ex(tn_ctx *ctx, const tn_param *params, int n_para
              "tn_gnmt_create: bad shape");
   TN_ON_DEVICE(ctx->device);
   const std::string pre(prefix_c);
-  std::map<std::string, const tn_param *> pm;
-  for (int i = 0; i < n_params; ++i) pm[params[i].name] = &params[i];
-  auto get = [&](const std::string &name, int64_t numel) -> const float * {
-    auto it = pm.find(name);
-    if (it == pm.end()) { tn_set_error("missing parameter: " + name); return nullptr; }
-    if (it->second->numel != numel) { tn_set_error("parameter " + name + " has the wrong size"); return nullptr; }
-    return it->second->data_host;
-  };
+  const ParamMap pm(params, n_params);
   tn_gnmt *g = new tn_gnmt();   // value-initialised: every pointer member starts null
   g->ctx = ctx; g->F = input_size; g->H = hidden; g->E = embed; g->V = vocab; g->maxB = max_batch; g->maxT = max_src_len;
   g->beam = beam; g->maxL = max_length + 2; g->G = cell_kind == TN_RNN_GRU ? 3 : 4;
@@ -1182,7 +1156,7 @@ extern "C" int tn_gnmt_create_ex(tn_ctx *ctx, const tn_param *params, int n_para
       for (int k = 0; k < 4; ++k) {
         const std::string src = pre + "enc_rnn" + std::to_string(i) + "_" + (bi ? (d ? "r_" : "l_") : "") + sfx[k];
         const int64_t n = k == 0 ? (int64_t)G3 * fin : k == 1 ? (int64_t)G3 * H : G3;
-        const float *v = get(src, n);
+        const float *v = pm.get(src, n);
         if (!v) return fail(TN_ERR_MISSING);
         names.push_back(std::string(d ? "r0_" : "l0_") + sfx[k]);
         pl.push_back(tn_param{nullptr, v, n});
@@ -1196,7 +1170,7 @@ extern "C" int tn_gnmt_create_ex(tn_ctx *ctx, const tn_param *params, int n_para
   }
   // decoder
   const float *a;
-#define UP(dst, name, n) do { a = get(pre + name, (int64_t)(n)); if (!a) return fail(TN_ERR_MISSING); dst = g->pool.upload(a, (size_t)(n)); } while (0)
+#define UP(dst, name, n) do { a = pm.get(pre + name, (int64_t)(n)); if (!a) return fail(TN_ERR_MISSING); dst = g->pool.upload(a, (size_t)(n)); } while (0)
   UP(g->wk, "dec_attention_key_weight", (int64_t)H * H);
   UP(g->wp, "tgt_proj_weight", (int64_t)vocab * H); UP(g->bp, "tgt_proj_bias", vocab);
   UP(g->emb, "tgt_embed_weight", (int64_t)vocab * embed);
@@ -1207,8 +1181,8 @@ extern "C" int tn_gnmt_create_ex(tn_ctx *ctx, const tn_param *params, int n_para
     // (n = tanh(n_i2h + r * n_h2h)): rows 2H..3H = [Wi_n | 0], rows 3H..4H = [0 | Wh_n].
     std::vector<float> last_w, last_b;      // host copies of the matrix stack() made last
     auto stack = [&](const std::string &cell, int in_dim, float **w_out, float **b_out) -> bool {
-      const float *wi = get(pre + cell + "i2h_weight", (int64_t)G3 * in_dim), *wh = get(pre + cell + "h2h_weight", (int64_t)G3 * H);
-      const float *bi = get(pre + cell + "i2h_bias", G3), *bh = get(pre + cell + "h2h_bias", G3);
+      const float *wi = pm.get(pre + cell + "i2h_weight", (int64_t)G3 * in_dim), *wh = pm.get(pre + cell + "h2h_weight", (int64_t)G3 * H);
+      const float *bi = pm.get(pre + cell + "i2h_bias", G3), *bh = pm.get(pre + cell + "h2h_bias", G3);
       if (!wi || !wh || !bi || !bh) return false;
       const int Kc = in_dim + H;
       std::vector<float> w((size_t)4 * H * Kc, 0.f), bv(4 * H, 0.f);
@@ -1268,13 +1242,13 @@ extern "C" int tn_gnmt_create_ex(tn_ctx *ctx, const tn_param *params, int n_para
     g->mid.resize(num_layers - 2);
     for (int i = 1; i + 1 < num_layers; ++i)
       if (!stack("dec_rnn" + std::to_string(i) + "_", 2 * H, &g->mid[i - 1].w, &g->mid[i - 1].b)) return fail(TN_ERR_MISSING);
-    const float *wp = get(pre + "tgt_proj_weight", (int64_t)vocab * H);
+    const float *wp = pm.get(pre + "tgt_proj_weight", (int64_t)vocab * H);
     const int vp = (vocab + 3) & ~3;        // rows of Wp^T padded to 16 bytes (dec_beam_kernel loads four columns at a time)
     std::vector<float> wt((size_t)H * vp, 0.f);
     for (int v = 0; v < vocab; ++v)
       for (int k = 0; k < H; ++k) wt[(size_t)k * vp + v] = wp[(size_t)v * H + k];
     g->wpT = g->pool.upload(wt.data(), wt.size());
-    const float *bpv = get(pre + "tgt_proj_bias", vocab);
+    const float *bpv = pm.get(pre + "tgt_proj_bias", vocab);
     std::vector<float> bpad(vp, 0.f);
     if (bpv) memcpy(bpad.data(), bpv, sizeof(float) * vocab);
     g->bpp = g->pool.upload(bpad.data(), bpad.size());
@@ -1613,17 +1587,16 @@ __global__ void trn_mul_add_kernel(const float *__restrict__ x, const float *__r
   y[i] = v;
 }
 
-struct TrnEnc {          // encoder layer i: bidirectional (i < num_bi_layers: in -> 2H) or uni-directional (in -> H)
+struct TrnEnc : CellOffsets {   // encoder layer i: bidirectional (i < num_bi_layers: in -> 2H) or uni-directional (in -> H)
+  // (the offsets: the directions adjacent per tensor kind - one GEMM / one recurrent launch serves both)
   int in, D, out;        // input width, directions, output width D * H
   bool res;              // use_residual && i > num_bi_layers (gnmt.py:155-157)
-  long o_wi, o_bi, o_wh, o_bh;     // the directions adjacent per tensor kind: one GEMM / one recurrent launch serves both
   float *whT, *wiT;      // per direction (H, GH); (in, D GH) [layers behind the first]
   float *gi, *seq, *sav, *hl, *cl, *M, *xn;       // xn: what the next layer (or the attention) reads = dropout(seq) (+ input)
   float *dxn, *dseq, *dgi, *dgh, *hp, *dhl, *dcl; // dxn: gradient w.r.t. xn
 };
-struct TrnDec {          // decoder cell j: step input x = [embedding | layer input, attention, h_prev], K = in + H columns
+struct TrnDec : CellOffsets {   // decoder cell j: step input x = [embedding | layer input, attention, h_prev], K = in + H columns
   int in, K;
-  long o_wi, o_bi, o_wh, o_bh;
   float *wc, *bc, *wcT;  // stacked (4H, K) step matrix, its bias, its transpose
   float *X, *G, *C, *Hs, *M;       // per step (L, B, .): inputs, stacked pre-activations, cell states (LSTM), states h (j >= 1), dropout masks (j >= 1)
   float *dG, *dX, *dhz, *dcz, *dW, *db;
@@ -1631,16 +1604,13 @@ struct TrnDec {          // decoder cell j: step input x = [embedding | layer in
 
 }  // namespace
 
-struct tn_gnmt_trainer {
-  tn_ctx *ctx;
-  DevBuf pool;
+struct tn_gnmt_trainer : TrainParams {
   int F, H, E, V, maxB, maxT, maxL, NL, NBI;
   bool residual;
   int G;                          // gates per cell: 3 GRU, 4 LSTM
-  std::string prefix;
-  long n, step;
+  long step;
   long o_wk, o_wp, o_bp, o_emb;
-  float *w, *g, *am, *av;         // flat parameter / gradient / Adam-moment buffers
+  float *am, *av;                 // Adam's moments, next to the parameters w and the gradients g
   std::vector<TrnEnc> enc;
   std::vector<TrnDec> dec;
   float *wpT, *wkT;
@@ -1686,60 +1656,29 @@ extern "C" int tn_gnmt_trainer_create_ex(tn_ctx *ctx, const tn_param *params, in
   TN_REQUIRE(input_size > 0 && hidden > 0 && hidden % 4 == 0 && G_ * hidden <= 1024 && embed > 0 && vocab > 1 && max_batch > 0 &&
                  max_src_len > 0 && max_tgt_len > 1, "tn_gnmt_trainer_create: bad shape (gates*hidden <= 1024, hidden % 4 == 0)");
   TN_ON_DEVICE(ctx->device);
-  const std::string pre(prefix_c);
-  std::map<std::string, const tn_param *> pm;
-  for (int i = 0; i < n_params; ++i) pm[params[i].name] = &params[i];
   tn_gnmt_trainer *t = new tn_gnmt_trainer();
   t->ctx = ctx; t->F = input_size; t->H = hidden; t->E = embed; t->V = vocab; t->maxB = max_batch; t->maxT = max_src_len;
-  t->maxL = max_tgt_len - 1; t->prefix = pre; t->step = 0; t->G = G_; t->NL = num_layers; t->NBI = num_bi_layers;
+  t->maxL = max_tgt_len - 1; t->step = 0; t->G = G_; t->NL = num_layers; t->NBI = num_bi_layers;
   t->residual = (flags & TN_GNMT_USE_RESIDUAL) != 0;
-  const long H = hidden, E = embed, V = vocab, GH = (long)G_ * H;
-  long o = 0;
-  auto take = [&](long cnt) { const long r = o; o += cnt; return r; };
+  const long H = hidden, V = vocab, GH = (long)G_ * H;
+  GnmtOffsets o;
+  t->table = gnmt_param_table(G_, input_size, hidden, embed, vocab, num_layers, num_bi_layers, prefix_c, &o);
+  t->n = t->table.n;
+  t->o_wk = o.o_wk; t->o_wp = o.o_wp; t->o_bp = o.o_bp; t->o_emb = o.o_emb;
   t->enc.resize(num_layers); t->dec.resize(num_layers);
-  int fin = input_size;
   for (int i = 0; i < num_layers; ++i) {
     TrnEnc &e = t->enc[i];
-    e.in = fin; e.D = i < num_bi_layers ? 2 : 1; e.out = e.D * hidden; e.res = t->residual && i > num_bi_layers;
-    e.o_wi = take(e.D * GH * e.in); e.o_bi = take(e.D * GH); e.o_wh = take(e.D * GH * H); e.o_bh = take(e.D * GH);
-    fin = e.out;
+    static_cast<CellOffsets &>(e) = o.enc[i];
+    e.in = gnmt_enc_in(i, input_size, hidden, num_bi_layers); e.D = gnmt_enc_dirs(i, num_bi_layers); e.out = e.D * hidden;
+    e.res = t->residual && i > num_bi_layers;
+    TrnDec &d = t->dec[i];
+    static_cast<CellOffsets &>(d) = o.dec[i];
+    d.in = gnmt_dec_in(i, hidden, embed); d.K = d.in + hidden;
   }
-  for (int j = 0; j < num_layers; ++j) {
-    TrnDec &d = t->dec[j];
-    d.in = j == 0 ? embed + hidden : 2 * hidden; d.K = d.in + hidden;
-    d.o_wi = take(GH * d.in); d.o_bi = take(GH); d.o_wh = take(GH * H); d.o_bh = take(GH);
-  }
-  t->o_wk = take(H * H); t->o_wp = take(V * H); t->o_bp = take(V); t->o_emb = take(V * E);
-  t->n = o;
-  std::vector<float> w(t->n);
   auto fail = [&](int code) { t->pool.release(); delete t; return code; };
-  bool ok = true;
-  auto put = [&](const std::string &name, long off, long cnt) {
-    auto it = pm.find(pre + name);
-    if (it == pm.end()) { tn_set_error("missing parameter: " + pre + name); ok = false; return; }
-    if (it->second->numel != cnt) { tn_set_error("parameter " + pre + name + " has the wrong size"); ok = false; return; }
-    memcpy(&w[off], it->second->data_host, sizeof(float) * cnt);
-  };
-  for (int i = 0; i < num_layers && ok; ++i) {
-    const TrnEnc &e = t->enc[i];
-    for (int d = 0; d < e.D && ok; ++d) {
-      const std::string c = "enc_rnn" + std::to_string(i) + (e.D == 2 ? (d ? "_r_" : "_l_") : "_");
-      put(c + "i2h_weight", e.o_wi + d * GH * e.in, GH * e.in); put(c + "i2h_bias", e.o_bi + d * GH, GH);
-      put(c + "h2h_weight", e.o_wh + d * GH * H, GH * H); put(c + "h2h_bias", e.o_bh + d * GH, GH);
-    }
-  }
-  for (int j = 0; j < num_layers && ok; ++j) {
-    const TrnDec &d = t->dec[j];
-    const std::string c = "dec_rnn" + std::to_string(j) + "_";
-    put(c + "i2h_weight", d.o_wi, GH * d.in); put(c + "i2h_bias", d.o_bi, GH);
-    put(c + "h2h_weight", d.o_wh, GH * H); put(c + "h2h_bias", d.o_bh, GH);
-  }
-  if (ok) {
-    put("dec_attention_key_weight", t->o_wk, H * H); put("tgt_proj_weight", t->o_wp, V * H); put("tgt_proj_bias", t->o_bp, V);
-    put("tgt_embed_weight", t->o_emb, V * E);
-  }
-  if (!ok) return fail(TN_ERR_MISSING);
-  t->w = t->pool.upload(w.data(), w.size());
+  std::vector<float> w, st;
+  if (!t->table.load(ParamMap(params, n_params), w, st)) return fail(TN_ERR_MISSING);
+  t->w = t->pool.upload(w);
   auto fl = [&](size_t n) { return t->pool.alloc<float>(n); };
   t->g = fl(t->n); t->am = fl(t->n); t->av = fl(t->n);
   const size_t B = max_batch, T = max_src_len, L = t->maxL, BT = B * T, LB = L * B;
@@ -2051,11 +1990,7 @@ extern "C" int tn_gnmt_trainer_dropout_masks(tn_gnmt_trainer *t, float **m_enc0,
 }
 
 extern "C" int tn_gnmt_trainer_buffers(tn_gnmt_trainer *t, float **params_dev, float **grads_dev, int64_t *numel) {
-  TN_REQUIRE(t, "tn_gnmt_trainer_buffers: null handle");
-  if (params_dev) *params_dev = t->w;
-  if (grads_dev) *grads_dev = t->g;
-  if (numel) *numel = t->n;
-  return TN_OK;
+  return train_buffers("tn_gnmt_trainer_buffers", t, params_dev, grads_dev, numel);
 }
 
 // gluon.Trainer(params, 'adam', {'learning_rate': lr}).step(1) (train_gnmt.py:310,337): MXNet Adam, beta1 0.9, beta2 0.999,
@@ -2072,37 +2007,9 @@ int gnmt_trainer_adam(tn_gnmt_trainer *t, float lr, float beta1, float beta2, fl
   return trainer_refresh(t);
 }
 
-extern "C" int tn_gnmt_trainer_read_param(tn_gnmt_trainer *t, const char *name_c, int gradient, float *out_host, int64_t capacity,
+extern "C" int tn_gnmt_trainer_read_param(tn_gnmt_trainer *t, const char *name, int gradient, float *out_host, int64_t capacity,
                                           int64_t *numel) {
-  TN_REQUIRE(t && name_c && out_host && numel, "tn_gnmt_trainer_read_param: null argument");
-  const std::string name(name_c), pre = t->prefix;
-  const long H = t->H, E = t->E, V = t->V, GH = (long)t->G * H;
-  long off = -1, cnt = 0;
-  auto cell = [&](const std::string &c, long owi, long obi, long owh, long obh, long in) {
-    if (name == pre + c + "i2h_weight") { off = owi; cnt = GH * in; }
-    if (name == pre + c + "i2h_bias") { off = obi; cnt = GH; }
-    if (name == pre + c + "h2h_weight") { off = owh; cnt = GH * H; }
-    if (name == pre + c + "h2h_bias") { off = obh; cnt = GH; }
-  };
-  for (int i = 0; i < t->NL; ++i) {
-    const TrnEnc &e = t->enc[i];
-    for (int d = 0; d < e.D; ++d)
-      cell("enc_rnn" + std::to_string(i) + (e.D == 2 ? (d ? "_r_" : "_l_") : "_"), e.o_wi + d * GH * e.in, e.o_bi + d * GH, e.o_wh + d * GH * H,
-           e.o_bh + d * GH, e.in);
-    const TrnDec &dc = t->dec[i];
-    cell("dec_rnn" + std::to_string(i) + "_", dc.o_wi, dc.o_bi, dc.o_wh, dc.o_bh, dc.in);
-  }
-  if (name == pre + "dec_attention_key_weight") { off = t->o_wk; cnt = H * H; }
-  if (name == pre + "tgt_proj_weight") { off = t->o_wp; cnt = V * H; }
-  if (name == pre + "tgt_proj_bias") { off = t->o_bp; cnt = V; }
-  if (name == pre + "tgt_embed_weight") { off = t->o_emb; cnt = V * E; }
-  TN_REQUIRE(off >= 0, "tn_gnmt_trainer_read_param: unknown parameter name");
-  TN_REQUIRE(capacity >= cnt, "tn_gnmt_trainer_read_param: host buffer too small");
-  TN_ON_DEVICE(t->ctx->device);
-  TN_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
-  TN_HIP_CHECK(hipMemcpy(out_host, (gradient ? t->g : t->w) + off, sizeof(float) * cnt, hipMemcpyDeviceToHost));
-  *numel = cnt;
-  return TN_OK;
+  return train_read_param("tn_gnmt_trainer_read_param", t, name, gradient, out_host, capacity, numel);
 }
 
 extern "C" int tn_gnmt_trainer_destroy(tn_gnmt_trainer *t) {

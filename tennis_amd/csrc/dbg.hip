@@ -10,6 +10,7 @@
 #include "encoder_plan.h"
 #include "gemm_fp32x3.h"
 #include "linear.h"
+#include "param_table.h"
 #include "rnn.h"
 #include "train.h"
 
@@ -458,6 +459,41 @@ extern "C" int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int 
              "tn_dbg_rnn_route: gates*hidden must be <= 1024, hidden % 4 == 0, batch > 0, dirs 1 or 2");
   const tn_rnn_route r = rnn_route(gates, B, H, dirs);
   *nb = r.nb; *kr = r.kr; *big = r.big;
+  return TN_OK;
+}
+
+// The parameter table of a training handle, from the builder its create calls (param_table.h); host arithmetic only, no device
+extern "C" int tn_dbg_trainer_params(int which, const int *dims, int n_dims, const char *prefix_a, const char *prefix_b, tn_param_row *rows,
+                                     int max_rows, int *n_rows, int64_t *numel, int64_t *state_numel) {
+  TN_REQUIRE(dims && prefix_a && n_rows && (rows || max_rows == 0), "tn_dbg_trainer_params: null argument");
+  ParamTable t;
+  if (which == TN_TRAINER_HEAD) {
+    TN_REQUIRE(n_dims == 4 && prefix_b, "tn_dbg_trainer_params: the head takes (gates, input, hidden, classes) and two prefixes");
+    HeadOffsets o;
+    t = head_param_table(dims[0], dims[1], dims[2], dims[3], prefix_a, prefix_b, &o);
+  } else if (which == TN_TRAINER_GNMT) {
+    TN_REQUIRE(n_dims == 7 && dims[5] >= 2 && dims[6] >= 0 && dims[6] < dims[5],
+               "tn_dbg_trainer_params: the captioner takes (gates, input, hidden, embed, vocab, num_layers, num_bi_layers < num_layers)");
+    GnmtOffsets o;
+    t = gnmt_param_table(dims[0], dims[1], dims[2], dims[3], dims[4], dims[5], dims[6], prefix_a, &o);
+  } else if (which == TN_TRAINER_BACKBONE) {
+    TN_REQUIRE(n_dims == 1 && (dims[0] > 0) == (prefix_b != nullptr),
+               "tn_dbg_trainer_params: the backbone takes (classes) and the classifier's prefix, or (0) and none");
+    FtNet net;
+    t = ft_param_table(prefix_a, prefix_b, dims[0], &net);
+  } else {
+    TN_REQUIRE(false, "tn_dbg_trainer_params: which must be TN_TRAINER_HEAD, TN_TRAINER_GNMT or TN_TRAINER_BACKBONE");
+  }
+  for (size_t i = 0; i < t.rows.size() && (int)i < max_rows; ++i) {
+    const ParamTable::Row &r = t.rows[i];
+    TN_REQUIRE(r.name.size() < sizeof(rows[i].name), "tn_dbg_trainer_params: a name does not fit tn_param_row");
+    memset(&rows[i], 0, sizeof(rows[i]));
+    memcpy(rows[i].name, r.name.data(), r.name.size());
+    rows[i].where = (int)r.where; rows[i].offset = r.off; rows[i].count = r.count;
+  }
+  *n_rows = (int)t.rows.size();
+  if (numel) *numel = t.n;
+  if (state_numel) *state_numel = t.ns;
   return TN_OK;
 }
 

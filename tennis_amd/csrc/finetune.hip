@@ -13,11 +13,10 @@
 // convolution outputs and the batch statistics are kept.
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "api_internal.h"
 #include "gemm_fp32x3.h"
 #include "linear.h"
 #include "train.h"
@@ -324,48 +323,17 @@ __global__ void ft_gap_bwd_kernel(const float *__restrict__ df, int B, int P, in
   da[id] = df[(long)b * C + c] / (float)P;
 }
 
-struct Pool {
-  std::vector<void *> ptrs;
-  bool failed = false;
-  bool dry = false;        // count the bytes only (what a batch would need), allocate nothing
-  size_t bytes = 0;
-  float *fl(size_t n) {
-    bytes += (n ? n : 1) * sizeof(float);
-    if (dry) return nullptr;
-    void *p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(float)) != hipSuccess) { failed = true; return nullptr; }
-    ptrs.push_back(p);
-    return (float *)p;
-  }
-  void release() { for (void *p : ptrs) (void)hipFree(p); ptrs.clear(); }
-};
-
 inline unsigned nblk(long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
-// One BatchNorm: offsets of gamma / beta in the flat parameter buffer, of the running statistics and batch statistics
-struct FtBn { long o_gamma, o_beta; long o_rm, o_rv; int C; float *mean, *var; std::string name; float *sc = nullptr, *sh = nullptr; };
-// (sc, sh: the folded form relu(x * sc + sh) of the layer's training-mode BatchNorm + ReLU, refreshed in every forward - what the
-//  GEMMs' operand transforms and the fused im2col read instead of a stored activation)
-struct FtLayer { FtBn bn1, bn2; long o_w1, o_w3; int K; float *z1; std::string n1, n3; };
-struct FtTrans { FtBn bn; long o_w; int Cin, Cout; float *z; std::string nw; };
-
-struct tn_finetune {
-  tn_ctx *ctx;
-  Pool pool;
+// (the network's BatchNorms, layers and offsets: FtNet of param_table.h, filled by ft_param_table)
+struct tn_finetune : TrainParams, FtNet {
   int B, H, W, classes;
   bool dense;                   // false: the backbone alone (the CNN-RNN step's TimeDistributed part), no classifier
-  std::string pre, cls;
-  long n;                       // trainable parameters (GEMM layouts: conv weights as (Cout, ky*kx*Cin))
-  long ns;                      // running statistics
-  float *w, *g, *mom, *state;
+  float *mom;                   // momentum, next to the parameters w, the gradients g and the running statistics in state
   float *av = nullptr;          // Adam's second moment (mom holds the first): ft_enable_adam
-  long o_w0, o_wd, o_bd;
-  FtBn bn0, bnF;
-  std::vector<FtLayer> layers[4];
-  FtTrans trans[3];
-  int Cin[4], Ctot[4], Hb[4];
+  int Hb[4];
   // activations kept for backward
   float *x_in, *col7, *z0, *a0, *X[4], *dX[4], *feat, *logits, *loss, *dlog, *dfeat;
   // batch statistics of every channel of a block's concat buffer, computed ONCE when the channel is produced: the BatchNorms in
@@ -443,132 +411,46 @@ static void ft_bn_backward(tn_finetune *f, const FtBn &bn, const float *dy, cons
                               f->g + bn.o_beta, dx, ldd, accumulate, s);
 }
 
-// conv weight (O, I, kh, kw) as Gluon stores it <-> the GEMM layout (O, kh*kw*I) used here
-static void ft_reorder_in(const float *src, float *dst, int O, int I, int kh, int kw) {
-  for (int o = 0; o < O; ++o)
-    for (int i = 0; i < I; ++i)
-      for (int y = 0; y < kh; ++y)
-        for (int x = 0; x < kw; ++x) dst[((long)o * kh * kw + y * kw + x) * I + i] = src[(((long)o * I + i) * kh + y) * kw + x];
-}
-static void ft_reorder_out(const float *src, float *dst, int O, int I, int kh, int kw) {
-  for (int o = 0; o < O; ++o)
-    for (int i = 0; i < I; ++i)
-      for (int y = 0; y < kh; ++y)
-        for (int x = 0; x < kw; ++x) dst[(((long)o * I + i) * kh + y) * kw + x] = src[((long)o * kh * kw + y * kw + x) * I + i];
-}
-
 int ft_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *backbone_prefix, const char *dense_prefix, int height,
               int width, int classes, int batch, tn_finetune **out, long *fit_frames) {
-  std::map<std::string, const tn_param *> pm;
-  for (int i = 0; i < n_params; ++i) pm[params[i].name] = &params[i];
   tn_finetune *f = new tn_finetune();
   f->ctx = ctx; f->B = batch; f->H = height; f->W = width; f->dense = dense_prefix != nullptr; f->classes = f->dense ? classes : 0;
-  f->pre = backbone_prefix; f->cls = f->dense ? dense_prefix : "";
-  const std::string pre = f->pre;
-  static const int kCfg[4] = {6, 12, 24, 16};
-  long o = 0, os = 0;
-  auto take = [&](long c) { const long r = o; o += c; return r; };
-  auto mkbn = [&](const std::string &name, int C) {
-    FtBn b; b.name = name; b.C = C; b.o_gamma = take(C); b.o_beta = take(C); b.o_rm = os; os += C; b.o_rv = os; os += C;
-    b.mean = nullptr; b.var = nullptr;
-    return b;
-  };
-  f->o_w0 = take(64 * 147);
-  f->bn0 = mkbn(pre + "batchnorm0", 64);
-  int c = 64, outer = 1;
-  for (int b = 0; b < 4; ++b) {
-    const std::string sp = pre + "stage" + std::to_string(b + 1) + "_";
-    f->Cin[b] = c;
-    for (int l = 0; l < kCfg[b]; ++l) {
-      FtLayer L;
-      L.K = c + 32 * l;
-      L.bn1 = mkbn(sp + "batchnorm" + std::to_string(2 * l), L.K);
-      L.n1 = sp + "conv" + std::to_string(2 * l) + "_weight"; L.o_w1 = take(128L * L.K);
-      L.bn2 = mkbn(sp + "batchnorm" + std::to_string(2 * l + 1), 128);
-      L.n3 = sp + "conv" + std::to_string(2 * l + 1) + "_weight"; L.o_w3 = take(32L * 1152);
-      L.z1 = nullptr;
-      f->layers[b].push_back(L);
-    }
-    c += 32 * kCfg[b];
-    f->Ctot[b] = c;
-    if (b < 3) {
-      FtTrans &T = f->trans[b];
-      T.Cin = c; T.Cout = c / 2;
-      T.bn = mkbn(pre + "batchnorm" + std::to_string(outer), c);
-      T.nw = pre + "conv" + std::to_string(outer) + "_weight"; T.o_w = take((long)T.Cout * T.Cin);
-      T.z = nullptr;
-      c /= 2;
-      ++outer;
-    }
-  }
-  f->bnF = mkbn(pre + "batchnorm" + std::to_string(outer), c);
-  f->o_wd = f->dense ? take((long)classes * c) : -1; f->o_bd = f->dense ? take(classes) : -1;
-  f->n = o; f->ns = os;
-  std::vector<float> w(f->n), st(f->ns);
+  f->table = ft_param_table(backbone_prefix, dense_prefix, classes, f);
+  f->n = f->table.n;
+  const int c = f->Ctot[3];
   auto fail = [&](int code) { f->pool.release(); delete f; return code; };
-  bool ok = true;
-  auto get = [&](const std::string &name, long cnt) -> const float * {
-    auto it = pm.find(name);
-    if (it == pm.end()) { tn_set_error("missing parameter: " + name); ok = false; return nullptr; }
-    if (it->second->numel != cnt) { tn_set_error("parameter " + name + " has the wrong size"); ok = false; return nullptr; }
-    return it->second->data_host;
-  };
-  auto loadbn = [&](const FtBn &b) {
-    const float *ga = get(b.name + "_gamma", b.C), *be = get(b.name + "_beta", b.C), *rm = get(b.name + "_running_mean", b.C),
-                *rv = get(b.name + "_running_var", b.C);
-    if (!ga || !be || !rm || !rv) return;
-    memcpy(&w[b.o_gamma], ga, sizeof(float) * b.C); memcpy(&w[b.o_beta], be, sizeof(float) * b.C);
-    memcpy(&st[b.o_rm], rm, sizeof(float) * b.C); memcpy(&st[b.o_rv], rv, sizeof(float) * b.C);
-  };
-  if (const float *p0 = get(pre + "conv0_weight", 64 * 147)) ft_reorder_in(p0, &w[f->o_w0], 64, 3, 7, 7);
-  loadbn(f->bn0);
-  for (int b = 0; b < 4 && ok; ++b) {
-    for (auto &L : f->layers[b]) {
-      loadbn(L.bn1); loadbn(L.bn2);
-      if (const float *p1 = get(L.n1, 128L * L.K)) memcpy(&w[L.o_w1], p1, sizeof(float) * 128 * L.K);
-      if (const float *p3 = get(L.n3, 32L * 1152)) ft_reorder_in(p3, &w[L.o_w3], 32, 128, 3, 3);
-    }
-    if (b < 3) {
-      loadbn(f->trans[b].bn);
-      if (const float *pt = get(f->trans[b].nw, (long)f->trans[b].Cout * f->trans[b].Cin))
-        memcpy(&w[f->trans[b].o_w], pt, sizeof(float) * f->trans[b].Cout * f->trans[b].Cin);
-    }
-  }
-  loadbn(f->bnF);
-  if (f->dense) {
-    if (const float *pd = get(f->cls + "weight", (long)classes * c)) memcpy(&w[f->o_wd], pd, sizeof(float) * classes * c);
-    if (const float *pb = get(f->cls + "bias", classes)) memcpy(&w[f->o_bd], pb, sizeof(float) * classes);
-  }
-  if (!ok) return fail(TN_ERR_MISSING);
+  std::vector<float> w, st;
+  if (!f->table.load(ParamMap(params, n_params), w, st)) return fail(TN_ERR_MISSING);
   // device buffers (alloc: in P, for B frames; a dry pool only counts the bytes)
-  auto alloc = [&](Pool &P, long B) {
-  f->w = P.fl(f->n); f->g = P.fl(f->n); f->mom = P.fl(f->n); f->state = P.fl(f->ns);
+  auto alloc = [&](DevPool &P, long B) {
+  auto fl = [&P](long n) { return P.alloc<float>((size_t)n); };
+  f->w = fl(f->n); f->g = fl(f->n); f->mom = fl(f->n); f->state = fl(f->table.ns);
   const long M0 = B * (height / 2) * (width / 2);
-  f->x_in = P.fl(B * height * width * 3); f->col7 = P.fl(M0 * 147); f->z0 = P.fl(M0 * 64); f->a0 = P.fl(M0 * 64);
+  f->x_in = fl(B * height * width * 3); f->col7 = fl(M0 * 147); f->z0 = fl(M0 * 64); f->a0 = fl(M0 * 64);
   long maxMK = M0 * 64, maxM128 = 0;
   for (int b = 0; b < 4; ++b) {
     f->Hb[b] = height / (4 << b);
     const long M = B * f->Hb[b] * f->Hb[b];
-    f->X[b] = P.fl(M * f->Ctot[b]); f->dX[b] = P.fl(M * f->Ctot[b]);
-    for (auto &L : f->layers[b]) L.z1 = P.fl(M * 128);
-    if (b < 3) f->trans[b].z = P.fl(M * f->trans[b].Cout);
+    f->X[b] = fl(M * f->Ctot[b]); f->dX[b] = fl(M * f->Ctot[b]);
+    for (auto &L : f->layers[b]) L.z1 = fl(M * 128);
+    if (b < 3) f->trans[b].z = fl(M * f->trans[b].Cout);
     if (M * f->Ctot[b] > maxMK) maxMK = M * f->Ctot[b];
     if (M * 128 > maxM128) maxM128 = M * 128;
   }
   const long Mb0 = B * f->Hb[0] * f->Hb[0];
-  f->ta = P.fl(maxMK); f->tb = P.fl(maxMK > maxM128 ? maxMK : maxM128); f->col = P.fl(Mb0 * 1152); f->dcol = P.fl(Mb0 * 1152);
-  f->tg = P.fl(maxMK); f->tw = P.fl(1024L * 1024);
-  f->ws_floats = 16L << 20; f->ws = P.fl(f->ws_floats);
-  f->feat = P.fl(B * c); f->dfeat = P.fl(B * c);
+  f->ta = fl(maxMK); f->tb = fl(maxMK > maxM128 ? maxMK : maxM128); f->col = fl(Mb0 * 1152); f->dcol = fl(Mb0 * 1152);
+  f->tg = fl(maxMK); f->tw = fl(1024L * 1024);
+  f->ws_floats = 16L << 20; f->ws = fl(f->ws_floats);
+  f->feat = fl(B * c); f->dfeat = fl(B * c);
   f->logits = f->loss = f->dlog = nullptr; f->labels = nullptr;
   if (f->dense) {
-    f->logits = P.fl(B * classes); f->loss = P.fl(B); f->dlog = P.fl(B * classes);
-    f->labels = (int32_t *)P.fl(B);                                 // (int32, the size of a float)
+    f->logits = fl(B * classes); f->loss = fl(B); f->dlog = fl(B * classes);
+    f->labels = (int32_t *)fl(B);                                 // (int32, the size of a float)
   }
-  auto bnbuf = [&](FtBn &b) { b.mean = P.fl(b.C); b.var = P.fl(b.C); b.sc = P.fl(b.C); b.sh = P.fl(b.C); };
+  auto bnbuf = [&](FtBn &b) { b.mean = fl(b.C); b.var = fl(b.C); b.sc = fl(b.C); b.sh = fl(b.C); };
   // a BatchNorm over a prefix of a block's concat buffer reads the block's shared statistics
-  auto bnshared = [&](FtBn &b, int blk) { b.mean = f->Xmean[blk]; b.var = f->Xvar[blk]; b.sc = P.fl(b.C); b.sh = P.fl(b.C); };
-  for (int b = 0; b < 4; ++b) { f->Xmean[b] = P.fl(f->Ctot[b]); f->Xvar[b] = P.fl(f->Ctot[b]); }
+  auto bnshared = [&](FtBn &b, int blk) { b.mean = f->Xmean[blk]; b.var = f->Xvar[blk]; b.sc = fl(b.C); b.sh = fl(b.C); };
+  for (int b = 0; b < 4; ++b) { f->Xmean[b] = fl(f->Ctot[b]); f->Xvar[b] = fl(f->Ctot[b]); }
   bnbuf(f->bn0); bnshared(f->bnF, 3);
   for (int b = 0; b < 4; ++b) {
     for (auto &L : f->layers[b]) { bnshared(L.bn1, b); bnbuf(L.bn2); }
@@ -577,7 +459,7 @@ int ft_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *bac
   };
   if (fit_frames) {
     // what batch frames need against what the device has free: the allocation is linear in the frames
-    Pool d1, d2;
+    DevPool d1, d2;
     d1.dry = d2.dry = true;
     alloc(d1, 1); alloc(d2, 2);
     const long per = (long)(d2.bytes - d1.bytes), fixed = (long)d1.bytes - per;
@@ -593,8 +475,9 @@ int ft_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *bac
   auto &P = f->pool;
   alloc(P, batch);
   if (P.failed) { tn_set_error("device allocation failed"); return fail(TN_ERR_NOMEM); }
+  f->each_bn([&](FtBn &b) { f->table.set_ptr(b.name + "_batch_mean", b.mean); f->table.set_ptr(b.name + "_batch_var", b.var); });
   TN_HIP_CHECK(hipMemcpy(f->w, w.data(), sizeof(float) * f->n, hipMemcpyHostToDevice));
-  TN_HIP_CHECK(hipMemcpy(f->state, st.data(), sizeof(float) * f->ns, hipMemcpyHostToDevice));
+  TN_HIP_CHECK(hipMemcpy(f->state, st.data(), sizeof(float) * f->table.ns, hipMemcpyHostToDevice));
   TN_HIP_CHECK(hipMemset(f->g, 0, sizeof(float) * f->n));
   TN_HIP_CHECK(hipMemset(f->mom, 0, sizeof(float) * f->n));
   *out = f;
@@ -752,15 +635,10 @@ int ft_backward_features(tn_finetune *f, int n) {
 // BatchNorm running statistics from the batch statistics of the last forward: running = 0.9 running + 0.1 batch
 void ft_update_running(tn_finetune *f) {
   hipStream_t s = f->ctx->stream;
-  auto upd = [&](const FtBn &b) {
+  f->each_bn([&](const FtBn &b) {
     hipLaunchKernelGGL(ft_bn_running_kernel, dim3((b.C + 255) / 256), dim3(256), 0, s, f->state + b.o_rm, f->state + b.o_rv,
                        (const float *)b.mean, (const float *)b.var, b.C);
-  };
-  upd(f->bn0); upd(f->bnF);
-  for (int b = 0; b < 4; ++b) {
-    for (auto &L : f->layers[b]) { upd(L.bn1); upd(L.bn2); }
-    if (b < 3) upd(f->trans[b].bn);
-  }
+  });
 }
 #undef TN_TRY
 
@@ -771,7 +649,7 @@ float *ft_frame_staging(tn_finetune *f) { return f->x_in; }
 // gluon.Trainer(model.collect_params(), 'adam') covers the backbone inside the captioner too (reference train_gnmt.py:310)
 int ft_enable_adam(tn_finetune *f) {
   if (f->av) return TN_OK;
-  f->av = f->pool.fl(f->n);
+  f->av = f->pool.alloc<float>(f->n);
   if (!f->av) { tn_set_error("device allocation failed"); return TN_ERR_NOMEM; }
   TN_HIP_CHECK(hipMemsetAsync(f->av, 0, sizeof(float) * f->n, f->ctx->stream));
   return TN_OK;
@@ -780,11 +658,6 @@ int ft_adam_step(tn_finetune *f, float lr, float beta1, float beta2, float epsil
   TN_REQUIRE(f->av, "ft_adam_step: ft_enable_adam has not run");
   return launch_adam(f->w, f->g, f->mom, f->av, f->n, lr, beta1, beta2, epsilon, step, f->ctx->stream);
 }
-int ft_param_buffers(tn_finetune *f, float **w, float **g, float **mom, long *n) {
-  *w = f->w; *g = f->g; *mom = f->mom; *n = f->n;
-  return TN_OK;
-}
-
 // x (batch, H, W, 3) fp32 normalised frames (NHWC), labels (batch,) int32, both DEVICE.  Runs the training-mode forward,
 // the per-sample softmax cross-entropy and the backward of their SUM; loss (batch,) / logits (batch, classes) optional
 // device outputs.  Gradients land in the flat buffer (tn_finetune_buffers); BatchNorm running statistics are updated.
@@ -815,11 +688,7 @@ extern "C" int tn_finetune_forward_backward(tn_finetune *f, const float *x, cons
 }
 
 extern "C" int tn_finetune_buffers(tn_finetune *f, float **params_dev, float **grads_dev, int64_t *numel) {
-  TN_REQUIRE(f, "tn_finetune_buffers: null handle");
-  if (params_dev) *params_dev = f->w;
-  if (grads_dev) *grads_dev = f->g;
-  if (numel) *numel = f->n;
-  return TN_OK;
+  return train_buffers("tn_finetune_buffers", f, params_dev, grads_dev, numel);
 }
 
 extern "C" int tn_finetune_sgd_step(tn_finetune *f, float lr, float momentum, float wd, float rescale_grad) {
@@ -830,54 +699,8 @@ extern "C" int tn_finetune_sgd_step(tn_finetune *f, float lr, float momentum, fl
 
 // Gluon-named parameter (conv weights back in (O, I, kh, kw) order), its gradient (gradient = 1), a running statistic, or
 // a BatchNorm's batch statistic of the last step ("<bn>_batch_mean" / "<bn>_batch_var", test hook)
-extern "C" int tn_finetune_read_param(tn_finetune *f, const char *name_c, int gradient, float *out_host, int64_t capacity,
-                                      int64_t *numel) {
-  TN_REQUIRE(f && name_c && out_host && numel, "tn_finetune_read_param: null argument");
-  const std::string name(name_c);
-  TN_ON_DEVICE(f->ctx->device);
-  TN_HIP_CHECK(hipStreamSynchronize(f->ctx->stream));
-  const float *base = gradient ? f->g : f->w;
-  auto copy = [&](const float *dev, long cnt) -> int {
-    TN_REQUIRE(capacity >= cnt, "tn_finetune_read_param: host buffer too small");
-    TN_HIP_CHECK(hipMemcpy(out_host, dev, sizeof(float) * cnt, hipMemcpyDeviceToHost));
-    *numel = cnt;
-    return TN_OK;
-  };
-  auto conv = [&](long off, int O, int I, int kh, int kw) -> int {
-    const long cnt = (long)O * I * kh * kw;
-    TN_REQUIRE(capacity >= cnt, "tn_finetune_read_param: host buffer too small");
-    std::vector<float> tmp(cnt);
-    TN_HIP_CHECK(hipMemcpy(tmp.data(), base + off, sizeof(float) * cnt, hipMemcpyDeviceToHost));
-    ft_reorder_out(tmp.data(), out_host, O, I, kh, kw);
-    *numel = cnt;
-    return TN_OK;
-  };
-  auto bn = [&](const FtBn &b, int &rcode) -> bool {
-    if (name == b.name + "_gamma") { rcode = copy(base + b.o_gamma, b.C); return true; }
-    if (name == b.name + "_beta") { rcode = copy(base + b.o_beta, b.C); return true; }
-    if (name == b.name + "_running_mean") { rcode = copy(f->state + b.o_rm, b.C); return true; }
-    if (name == b.name + "_running_var") { rcode = copy(f->state + b.o_rv, b.C); return true; }
-    if (name == b.name + "_batch_mean") { rcode = copy(b.mean, b.C); return true; }
-    if (name == b.name + "_batch_var") { rcode = copy(b.var, b.C); return true; }
-    return false;
-  };
-  int rcode = TN_OK;
-  if (name == f->pre + "conv0_weight") return conv(f->o_w0, 64, 3, 7, 7);
-  if (bn(f->bn0, rcode) || bn(f->bnF, rcode)) return rcode;
-  for (int b = 0; b < 4; ++b) {
-    for (auto &L : f->layers[b]) {
-      if (bn(L.bn1, rcode) || bn(L.bn2, rcode)) return rcode;
-      if (name == L.n1) return copy(base + L.o_w1, 128L * L.K);
-      if (name == L.n3) return conv(L.o_w3, 32, 128, 3, 3);
-    }
-    if (b < 3) {
-      if (bn(f->trans[b].bn, rcode)) return rcode;
-      if (name == f->trans[b].nw) return copy(base + f->trans[b].o_w, (long)f->trans[b].Cout * f->trans[b].Cin);
-    }
-  }
-  if (f->dense && name == f->cls + "weight") return copy(base + f->o_wd, (long)f->classes * f->Ctot[3]);
-  if (f->dense && name == f->cls + "bias") return copy(base + f->o_bd, f->classes);
-  TN_REQUIRE(false, "tn_finetune_read_param: unknown parameter name");
+extern "C" int tn_finetune_read_param(tn_finetune *f, const char *name, int gradient, float *out_host, int64_t capacity, int64_t *numel) {
+  return train_read_param("tn_finetune_read_param", f, name, gradient, out_host, capacity, numel);
 }
 
 extern "C" int tn_finetune_destroy(tn_finetune *f) {

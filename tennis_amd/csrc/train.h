@@ -45,7 +45,8 @@ int launch_ft_bn_relu(const float *x, int ld, long M, int C, const float *mean, 
 int launch_ft_bn_backward(const float *dy, const float *x, int ld, long M, int C, const float *mean, const float *var, const float *gamma,
                           const float *beta, float *ws, float *dgamma, float *dbeta, float *dx, int ldd, int accumulate, hipStream_t s);
 // The fine-tuning step in parts (finetune.hip), what tn_finetune_forward_backward chains and the CNN-RNN step (api.hip) drives.
-// ft_create: dense_prefix NULL builds the backbone alone (no classifier; classes ignored); fit_frames non-NULL: first compare the
+// ft_create: the table of param_table.h::ft_param_table, loaded, uploaded, then the workspaces; dense_prefix NULL builds the backbone
+// alone (no classifier; classes ignored); fit_frames non-NULL: first compare the
 // memory batch frames need with what the device has free, and on a shortfall return TN_ERR_NOMEM with *fit_frames = the frames
 // that would fit.  ft_forward_features: training-mode forward of x (n, H, W, 3) -> ft_features (n, ft_feature_dim), batch
 // statistics kept; ft_backward_features: from ft_feature_grad (n, ft_feature_dim) every backbone gradient, assigned;
@@ -65,7 +66,6 @@ void ft_update_running(tn_finetune *f);
 float *ft_features(tn_finetune *f);
 float *ft_feature_grad(tn_finetune *f);
 int ft_feature_dim(tn_finetune *f);
-int ft_param_buffers(tn_finetune *f, float **w, float **g, float **mom, long *n);
 // The captioner's training step (captioner.hip), what tn_gnmt_trainer_forward_backward runs.  dsrc non-null: also the gradient of
 // the loss with respect to src, (batch * steps, input_size) of row stride ldd, assigned; rows at or past src_valid_len[b] are 0.
 int gnmt_trainer_step(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len, const int32_t *tgt, int ld,

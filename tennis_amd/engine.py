@@ -37,8 +37,85 @@ def _layout_of(x: torch.Tensor, size_hw):
                      "(expected NCHW float32, NHWC float16 or NHWC uint8)")
 
 
-class DenseNet121Features:
+def _device_view(ctx, addr, shape):
+    """torch view of an fp32 device buffer owned by the library (for all-reduce / inspection)"""
+    class _Arr:
+        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (addr, False), "version": 3}
+    return torch.as_tensor(_Arr(), device=f"cuda:{ctx.device}")
+
+
+class _Handle:
+    """Owns one library handle on a context; ``_ABI`` is the prefix of its C entry points (``tn_dense`` -> ``tn_dense_destroy``)."""
+    _ABI = ""
+    handle = None
+
+    def __init__(self, ctx: _lib.Context | None = None):
+        self.ctx = ctx or _lib.default_context()
+        self.lib = self.ctx.lib
+
+    def __del__(self):
+        try:
+            if self.handle:
+                getattr(self.lib, self._ABI + "_destroy")(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+class _FlatTrainer(_Handle):
+    """A training handle whose parameters and gradients live in flat device buffers (``<_ABI>_buffers``) and are read back by
+    name (``<_ABI>_read_param``).  ``_PARTS`` = 2: a backbone and the part on top of it, each with buffers of its own -
+    ``params`` / ``grads`` are then tuples, and ``grads`` leaves a ``frozen`` backbone's out."""
+    _PARTS = 1
+    frozen = False
+
+    def _select(self, params: dict, *prefixes):
+        """Records ``names`` / ``shapes`` of the parameters under ``prefixes`` -> (tn_param array, keep-alive list)"""
+        self.names = [k for k in params if k.startswith(prefixes)]
+        self.shapes = {k: tuple(np.asarray(params[k]).shape) for k in self.names}
+        return _lib.make_params({k: params[k] for k in self.names})
+
+    def _adopt(self, h):
+        """Owns the created handle ``h`` and asks for its flat buffers: (params address, grads address, numel) per part"""
+        self.handle = h
+        out = [c() for _ in range(self._PARTS) for c in (C.c_void_p, C.c_void_p, C.c_int64)]
+        check(getattr(self.lib, self._ABI + "_buffers")(h, *[C.byref(o) for o in out]), self._ABI + "_buffers")
+        self._parts = [tuple(o.value for o in out[3 * i:3 * i + 3]) for i in range(self._PARTS)]
+        if self._PARTS == 1:
+            self.numel = self._parts[0][2]
+
+    def _views(self, which: int, trainable_only: bool = False):
+        v = [_device_view(self.ctx, p[which], (p[2],)) for p in self._parts]
+        if self._PARTS == 1:
+            return v[0]
+        return tuple(v[1:] if trainable_only and self.frozen else v)
+
+    @property
+    def grads(self):
+        return self._views(1, True)
+
+    @property
+    def params(self):
+        return self._views(0)
+
+    def get(self, name: str, gradient: bool = False, shape=None) -> np.ndarray:
+        shape = shape or self.shapes[name]
+        out = np.empty(int(np.prod(shape)), np.float32)
+        n = C.c_int64()
+        check(getattr(self.lib, self._ABI + "_read_param")(self.handle, name.encode(), 1 if gradient else 0,
+                                                           out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n)),
+              self._ABI + "_read_param")
+        return out[:n.value].reshape(shape if n.value == out.size else (n.value,)).copy()
+
+    def state_dict(self) -> dict:
+        """Every recorded parameter (for a backbone: its running statistics too), by name."""
+        return {k: self.get(k) for k in self.names}
+
+
+class DenseNet121Features(_Handle):
     """``get_model('DenseNet121').features`` on the GPU (reference evaluate.py:125)."""
+
+    _ABI = "tn_densenet121"
 
     def __init__(self, params: dict, size: int | tuple = 224, max_batch: int = 256, prefix: str = "densenet0_",
                  ctx: _lib.Context | None = None, exact_weights: bool = False, fp32: bool = False, fp32x3: bool = False):
@@ -50,8 +127,7 @@ class DenseNet121Features:
         ``fp32x3``: the fp32x3 mode (TN_ENC_FP32X3) - the fp32 mode's network and fp32 activations, every operand handed to the
         bf16 matrix pipe as three bf16 terms (six products per k-step): the same bar for any checkpoint, faster; not together
         with ``fp32``."""
-        self.ctx = ctx or _lib.default_context()
-        self.lib = self.ctx.lib
+        super().__init__(ctx)
         self.size = (size, size) if isinstance(size, int) else tuple(size)
         self.max_batch = max_batch
         arr, keep = _lib.make_params({k: v for k, v in params.items() if k.startswith(prefix)})
@@ -131,21 +207,15 @@ class DenseNet121Features:
         ws = (self.size[1] - 1) // 2 + 1
         return batch * hs * ws * 64  # stem / stage1 taps are the largest
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.tn_densenet121_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
-class Dense:
+class Dense(_Handle):
     """``nn.Dense(units, flatten=True)`` (reference definitions.py:25)."""
 
+    _ABI = "tn_dense"
+
     def __init__(self, weight: np.ndarray, bias: np.ndarray | None, ctx: _lib.Context | None = None):
-        self.ctx = ctx or _lib.default_context()
-        self.lib = self.ctx.lib
+        super().__init__(ctx)
         w = np.ascontiguousarray(weight, dtype=np.float32)
         b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
         self.units, self.in_units = w.shape
@@ -164,22 +234,16 @@ class Dense:
         check(self.lib.tn_dense_forward(self.handle, ptr(x), x.shape[0], ptr(y)), "tn_dense_forward")
         return y
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.tn_dense_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
-class BiRNN:
+class BiRNN(_Handle):
     """``mx.gluon.rnn.GRU/LSTM(hidden, layout='NTC', bidirectional=...)`` (definitions.py:94-96)."""
+
+    _ABI = "tn_birnn"
 
     def __init__(self, mode: str, input_size: int, hidden: int, params: dict, prefix: str,
                  bidirectional: bool = True, max_rows: int = 4096, ctx: _lib.Context | None = None):
-        self.ctx = ctx or _lib.default_context()
-        self.lib = self.ctx.lib
+        super().__init__(ctx)
         self.mode, self.hidden, self.input_size = mode, hidden, input_size
         self.dirs = 2 if bidirectional else 1
         self.max_rows = max_rows
@@ -205,13 +269,6 @@ class BiRNN:
               "tn_birnn_forward")
         return (seq, hl, cl) if return_state else seq
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.tn_birnn_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 def temporal_pool(x: torch.Tensor, kind: str, ctx: _lib.Context | None = None) -> torch.Tensor:
@@ -237,19 +294,20 @@ def _index_arrays(dev, *arrays):
     return out
 
 
-class WindowHead:
+class WindowHead(_Handle):
     """Dense windowed evaluation of ``CNNRNN`` in feature mode (reference evaluate.py:274-303 with ``--feats_model M --window W
     --temp_pool gru|lstm``; definitions.py:94-96,106-109): ``project`` runs the i2h projection once per row of a device-resident
     (rows, F) feature matrix, ``forward`` gathers every sample's window inside the recurrent kernel - step ``t`` of sample ``b`` reads
     row ``clamp(centre[b] + (t - window // 2) * stride, lo[b], hi[b])`` (``TennisSet.window_rows``) - and returns the logits.  One
     ``project`` serves any number of ``forward`` calls; neither allocates in the library."""
 
+    _ABI = "tn_window_head"
+
     def __init__(self, mode: str, input_size: int, hidden: int, classes: int, params: dict, rnn_prefix: str, dense_prefix: str,
                  max_rows: int = 65536, max_samples: int | None = None, ctx: _lib.Context | None = None):
         if mode not in ("gru", "lstm"):
             raise ValueError(f"mode must be 'gru' or 'lstm', got {mode!r}")
-        self.ctx = ctx or _lib.default_context()
-        self.lib = self.ctx.lib
+        super().__init__(ctx)
         self.mode, self.input_size, self.hidden, self.classes = mode, input_size, hidden, classes
         self.max_rows = int(max_rows)
         self.max_samples = int(max_rows if max_samples is None else max_samples)
@@ -288,13 +346,6 @@ class WindowHead:
         """tuning hook (scripts/bench_window_head.py): samples per workgroup of the recurrent kernel, 0 = the library's choice"""
         check(self.lib.tn_dbg_window_head_rows_per_group(self.handle, int(nb)), "tn_dbg_window_head_rows_per_group")
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.tn_window_head_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 def temporal_pool_windows(features: torch.Tensor, centre, lo, hi, window: int, stride: int, kind: str,
@@ -331,9 +382,11 @@ def to_tensor_normalize(x: torch.Tensor, mean=(0.485, 0.456, 0.406), std=(0.229,
     return y
 
 
-class GNMTCaptioner:
+class GNMTCaptioner(_Handle):
     """Encoder + attention decoder + beam search of the reference captioner on the GPU
     (train_gnmt.py:223-252 assembly; evaluate() at train_gnmt.py:264-302)."""
+
+    _ABI = "tn_gnmt"
 
     def __init__(self, params: dict, input_size: int, hidden: int, embed: int, vocab: int, beam: int = 4,
                  max_length: int = 150, max_batch: int = 32, max_src_len: int = 640, prefix: str = "gnmt_",
@@ -341,8 +394,7 @@ class GNMTCaptioner:
                  ctx: _lib.Context | None = None):
         """``num_layers`` / ``num_bi_layers`` / ``use_residual`` as in ``get_gnmt_encoder_decoder`` (reference gnmt.py:407-455):
         2 <= num_layers, num_bi_layers < num_layers (gnmt.py:78-80 and the attention's key width, see tn_gnmt_create_ex)."""
-        self.ctx = ctx or _lib.default_context()
-        self.lib = self.ctx.lib
+        super().__init__(ctx)
         self.hidden, self.beam, self.max_length, self.vocab = hidden, beam, max_length, vocab
         arr, keep = _lib.make_params({k: v for k, v in params.items() if k.startswith(prefix)})
         h = C.c_void_p()
@@ -382,13 +434,6 @@ class GNMTCaptioner:
                                            C.byref(n)), "tn_gnmt_beam_search")
         return samples[:, :, :n.value].contiguous(), scores, vlen
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.tn_gnmt_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 def masked_softmax_ce(logits: torch.Tensor, labels: torch.Tensor, valid_length: torch.Tensor,
@@ -405,7 +450,7 @@ def masked_softmax_ce(logits: torch.Tensor, labels: torch.Tensor, valid_length: 
     return loss
 
 
-class TemporalHeadTrainer:
+class TemporalHeadTrainer(_FlatTrainer):
     """Training step of ``CNNRNN(model=None, type='gru' | 'lstm')`` in feature mode (reference definitions.py:94-110) the way
     train.py drives it: ``SoftmaxCrossEntropyLoss`` per sample (:324), ``ag.backward`` of the per-sample losses and
     ``gluon.Trainer(params, 'sgd', {learning_rate, momentum, wd}).step(batch_size)`` (:298-299, :410-424).
@@ -413,6 +458,7 @@ class TemporalHeadTrainer:
     ``forward_backward`` leaves the gradient of the SUM of the per-sample losses in a flat device buffer
     (``grads``); with several ranks all-reduce that buffer (``torch.distributed.all_reduce(trainer.grads)``)
     before ``step(batch_size)``, whose ``rescale_grad = 1 / batch_size`` is Gluon's."""
+    _ABI = "tn_head"
 
     def __init__(self, params: dict, input_size: int, hidden: int = 128, classes: int = 11, max_batch: int = 32,
                  max_steps: int = 64, rnn_prefix: str | None = None, dense_prefix: str = "cnnrnn0_dense0_",
@@ -422,34 +468,15 @@ class TemporalHeadTrainer:
         if rnn_prefix is None:
             rnn_prefix = f"cnnrnn0_{type}0_"
         self.type, self.gates = type, 3 if type == "gru" else 4
-        self.ctx = ctx or _lib.default_context()
-        self.lib = self.ctx.lib
+        super().__init__(ctx)
         self.input_size, self.hidden, self.classes = input_size, hidden, classes
         self.rnn_prefix, self.dense_prefix = rnn_prefix, dense_prefix
-        arr, keep = _lib.make_params({k: v for k, v in params.items() if k.startswith(rnn_prefix) or k.startswith(dense_prefix)})
+        arr, keep = self._select(params, rnn_prefix, dense_prefix)
         h = C.c_void_p()
         check(self.lib.tn_head_create(self.ctx.handle, _lib.RNN_GRU if type == "gru" else _lib.RNN_LSTM, input_size, hidden, classes, arr, len(arr), rnn_prefix.encode(),
                                       dense_prefix.encode(), max_batch, max_steps, C.byref(h)), "tn_head_create")
         del keep
-        self.handle = h
-        pw, pg, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.tn_head_buffers(h, C.byref(pw), C.byref(pg), C.byref(n)), "tn_head_buffers")
-        self.numel = n.value
-        self._pw, self._pg = pw.value, pg.value
-
-    def _view(self, addr):
-        """torch view of a flat fp32 device buffer owned by the library (for all-reduce / inspection)."""
-        class _Arr:
-            __cuda_array_interface__ = {"shape": (self.numel,), "typestr": "<f4", "data": (addr, False), "version": 3}
-        return torch.as_tensor(_Arr(), device=f"cuda:{self.ctx.device}")
-
-    @property
-    def grads(self) -> torch.Tensor:
-        return self._view(self._pg)
-
-    @property
-    def params(self) -> torch.Tensor:
-        return self._view(self._pw)
+        self._adopt(h)
 
     def forward_backward(self, x: torch.Tensor, labels: torch.Tensor):
         x = x.contiguous().float()
@@ -464,42 +491,20 @@ class TemporalHeadTrainer:
     def step(self, batch_size: int, lr: float, momentum: float = 0.9, wd: float = 1e-4):
         check(self.lib.tn_head_sgd_step(self.handle, lr, momentum, wd, 1.0 / batch_size), "tn_head_sgd_step")
 
-    def get(self, name: str, gradient: bool = False) -> np.ndarray:
-        cap = self.gates * self.hidden * max(self.input_size, self.hidden, 2 * self.classes) + 16
-        out = np.empty(cap, np.float32)
-        n = C.c_int64()
-        check(self.lib.tn_head_read_param(self.handle, name.encode(), 1 if gradient else 0,
-                                          out.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(n)), "tn_head_read_param")
-        return out[:n.value].copy()
-
-    def state_dict(self) -> dict:
-        h, f, c = self.hidden, self.input_size, self.classes
-        out = {}
-        for d in ("l0_", "r0_"):
-            out[self.rnn_prefix + d + "i2h_weight"] = self.get(self.rnn_prefix + d + "i2h_weight").reshape(self.gates * h, f)
-            out[self.rnn_prefix + d + "h2h_weight"] = self.get(self.rnn_prefix + d + "h2h_weight").reshape(self.gates * h, h)
-            out[self.rnn_prefix + d + "i2h_bias"] = self.get(self.rnn_prefix + d + "i2h_bias")
-            out[self.rnn_prefix + d + "h2h_bias"] = self.get(self.rnn_prefix + d + "h2h_bias")
-        out[self.dense_prefix + "weight"] = self.get(self.dense_prefix + "weight").reshape(c, 2 * h)
-        out[self.dense_prefix + "bias"] = self.get(self.dense_prefix + "bias")
-        return out
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.tn_head_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
+    def get(self, name: str, gradient: bool = False, shape=None) -> np.ndarray:
+        """A name without a recorded shape is read flat (no parameter is larger than the flat buffer); an unknown one raises the
+        library's error."""
+        return super().get(name, gradient, shape or self.shapes.get(name) or (self.numel,))
 
 
-class GNMTTrainer:
+class GNMTTrainer(_FlatTrainer):
     """One training step of the captioner the way reference train_gnmt.py::train drives it (:328-337): teacher-forced
     ``NMTModel`` forward, token-averaged ``MaskedSoftmaxCELoss``, ``loss.backward()``, ``gluon.Trainer('adam').step(1)``.
     GRU (the reference's flag default) or LSTM cells; ``num_layers`` / ``num_bi_layers`` / ``use_residual`` as the reference's
     flags pass them into the model it trains (train_gnmt.py:58-61,223-227; round 4: any ``num_layers >= 2`` with
     ``num_bi_layers < num_layers``).  ``grads`` / ``params`` are flat device views for a data-parallel all-reduce between
     ``forward_backward`` and ``step``."""
+    _ABI = "tn_gnmt_trainer"
 
     def __init__(self, params: dict, input_size: int, hidden: int, embed: int, vocab: int, max_batch: int = 32,
                  max_src_len: int = 256, max_tgt_len: int = 64, prefix: str = "gnmt_", ctx: _lib.Context | None = None,
@@ -507,36 +512,17 @@ class GNMTTrainer:
         if cell_type not in ("gru", "lstm"):
             raise ValueError(f"cell_type must be 'gru' or 'lstm', got {cell_type!r}")
         self.num_layers, self.num_bi_layers, self.use_residual = num_layers, num_bi_layers, bool(use_residual)
-        self.ctx = ctx or _lib.default_context()
-        self.lib = self.ctx.lib
+        super().__init__(ctx)
         self.input_size, self.hidden, self.embed, self.vocab, self.prefix = input_size, hidden, embed, vocab, prefix
         self.cell_type = cell_type
-        self.names = [k for k in params if k.startswith(prefix)]
-        self.shapes = {k: tuple(np.asarray(params[k]).shape) for k in self.names}
-        arr, keep = _lib.make_params({k: params[k] for k in self.names})
+        arr, keep = self._select(params, prefix)
         h = C.c_void_p()
         check(self.lib.tn_gnmt_trainer_create_ex(self.ctx.handle, arr, len(arr), prefix.encode(),
                                                  _lib.RNN_GRU if cell_type == "gru" else _lib.RNN_LSTM, input_size, hidden, embed, vocab,
                                                  num_layers, num_bi_layers, 1 if use_residual else 0,
                                                  max_batch, max_src_len, max_tgt_len, C.byref(h)), "tn_gnmt_trainer_create_ex")
         del keep
-        self.handle = h
-        pw, pg, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.tn_gnmt_trainer_buffers(h, C.byref(pw), C.byref(pg), C.byref(n)), "tn_gnmt_trainer_buffers")
-        self.numel, self._pw, self._pg = n.value, pw.value, pg.value
-
-    def _view(self, addr):
-        class _Arr:
-            __cuda_array_interface__ = {"shape": (self.numel,), "typestr": "<f4", "data": (addr, False), "version": 3}
-        return torch.as_tensor(_Arr(), device=f"cuda:{self.ctx.device}")
-
-    @property
-    def grads(self) -> torch.Tensor:
-        return self._view(self._pg)
-
-    @property
-    def params(self) -> torch.Tensor:
-        return self._view(self._pw)
+        self._adopt(h)
 
     def forward_backward(self, src: torch.Tensor, src_valid_length: torch.Tensor, tgt: torch.Tensor,
                          tgt_valid_length: torch.Tensor, return_logits: bool = False):
@@ -561,65 +547,36 @@ class GNMTTrainer:
         """The last step's masks as tensors: (B,T,2H), (B,T,H), (L,B,H) (step-major) - for tests against the oracle."""
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
         check(self.lib.tn_gnmt_trainer_dropout_masks(self.handle, C.byref(a), C.byref(b), C.byref(c)), "tn_gnmt_trainer_dropout_masks")
-        h = self.hidden
-
-        def view(addr, shape):
-            class _Arr:
-                __cuda_array_interface__ = {"shape": shape, "typestr": "<f4", "data": (addr, False), "version": 3}
-            return torch.as_tensor(_Arr(), device=f"cuda:{self.ctx.device}")
-        return (view(a.value, (batch, src_steps, 2 * h)), view(b.value, (batch, src_steps, h)), view(c.value, (tgt_steps, batch, h)))
+        h, view = self.hidden, lambda addr, shape: _device_view(self.ctx, addr.value, shape)
+        return view(a, (batch, src_steps, 2 * h)), view(b, (batch, src_steps, h)), view(c, (tgt_steps, batch, h))
 
     def dropout_mask(self, which: int, shape) -> torch.Tensor:
         """One mask of the last step: ``which`` = encoder layer ``i`` -> (B,T,dirs*H); ``num_layers + j`` -> decoder layer ``j >= 1``,
         (L,B,H) step-major."""
         a = C.c_void_p()
         check(self.lib.tn_gnmt_trainer_dropout_mask(self.handle, which, C.byref(a)), "tn_gnmt_trainer_dropout_mask")
-
-        class _Arr:
-            __cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (a.value, False), "version": 3}
-        return torch.as_tensor(_Arr(), device=f"cuda:{self.ctx.device}")
+        return _device_view(self.ctx, a.value, shape)
 
     def step(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8):
         check(self.lib.tn_gnmt_trainer_adam_step(self.handle, lr, beta1, beta2, epsilon), "tn_gnmt_trainer_adam_step")
 
-    def get(self, name: str, gradient: bool = False) -> np.ndarray:
-        shape = self.shapes[name]
-        out = np.empty(int(np.prod(shape)), np.float32)
-        n = C.c_int64()
-        check(self.lib.tn_gnmt_trainer_read_param(self.handle, name.encode(), 1 if gradient else 0,
-                                                  out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n)),
-              "tn_gnmt_trainer_read_param")
-        return out[:n.value].reshape(shape).copy()
 
-    def state_dict(self) -> dict:
-        return {k: self.get(k) for k in self.names}
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.tn_gnmt_trainer_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
-
-class _BackboneMatmul:
+class _BackboneMatmul(_FlatTrainer):
     """``matmul`` of the three backbone trainers: which matrix pipe the backbone's GEMMs run on.  ``"f32"`` (the default) is the
     exact-f32 matrix instruction; ``"fp32x3"`` keeps fp32 operands, accumulators and results and forms every product from three
-    bf16 terms per operand on the bf16 matrix pipe (csrc/gemm_fp32x3.hip) - the same float64 bars.  ``_MATMUL_ABI`` names the
-    handle's C entry points."""
+    bf16 terms per operand on the bf16 matrix pipe (csrc/gemm_fp32x3.hip) - the same float64 bars."""
 
     def set_matmul(self, name: str):
         mode = _lib.matmul_mode(name)
-        fn = getattr(self.lib, self._MATMUL_ABI + "_set_matmul")
-        check(fn(self.handle, mode), self._MATMUL_ABI + "_set_matmul")
+        fn = getattr(self.lib, self._ABI + "_set_matmul")
+        check(fn(self.handle, mode), self._ABI + "_set_matmul")
         self.matmul = name
 
     def matmul_stats(self) -> tuple:
         """Backbone GEMM launches since construction: (f32, fp32x3)"""
         a, b = C.c_int64(), C.c_int64()
-        fn = getattr(self.lib, self._MATMUL_ABI + "_matmul_stats")
-        check(fn(self.handle, C.byref(a), C.byref(b)), self._MATMUL_ABI + "_matmul_stats")
+        fn = getattr(self.lib, self._ABI + "_matmul_stats")
+        check(fn(self.handle, C.byref(a), C.byref(b)), self._ABI + "_matmul_stats")
         return a.value, b.value
 
 
@@ -628,36 +585,20 @@ class FrameModelTrainer(_BackboneMatmul):
     with an un-frozen backbone: BatchNorm in training mode, ``SoftmaxCrossEntropyLoss`` per sample (:324), backward of the
     summed losses (:419-421), ``gluon.Trainer('sgd', {lr, momentum, wd}).step(batch_size)`` (:298-299,424).  fp32.  The batch
     size is fixed at construction (BatchNorm statistics are per batch)."""
+    _ABI = "tn_finetune"
 
     def __init__(self, params: dict, size: int = 224, classes: int = 11, batch: int = 8, prefix: str = "densenet0_",
                  dense_prefix: str = "framemodel0_dense0_", ctx: _lib.Context | None = None, matmul: str = "f32"):
         _lib.matmul_mode(matmul)                       # a wrong name raises before a context or the library is touched
-        self.ctx = ctx or _lib.default_context()
-        self.lib = self.ctx.lib
+        super().__init__(ctx)
         self.size, self.classes, self.batch = size, classes, batch
-        self.names = [k for k in params if k.startswith(prefix) or k.startswith(dense_prefix)]
-        self.shapes = {k: tuple(np.asarray(params[k]).shape) for k in self.names}
-        arr, keep = _lib.make_params({k: params[k] for k in self.names})
+        arr, keep = self._select(params, prefix, dense_prefix)
         h = C.c_void_p()
         check(self.lib.tn_finetune_create(self.ctx.handle, arr, len(arr), prefix.encode(), dense_prefix.encode(), size, size, classes,
                                           batch, C.byref(h)), "tn_finetune_create")
         del keep
-        self.handle = h
-        pw, pg, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.tn_finetune_buffers(h, C.byref(pw), C.byref(pg), C.byref(n)), "tn_finetune_buffers")
-        self.numel, self._pw, self._pg = n.value, pw.value, pg.value
+        self._adopt(h)
         self.set_matmul(matmul)
-
-    _MATMUL_ABI = "tn_finetune"
-
-    def _view(self, addr):
-        class _Arr:
-            __cuda_array_interface__ = {"shape": (self.numel,), "typestr": "<f4", "data": (addr, False), "version": 3}
-        return torch.as_tensor(_Arr(), device=f"cuda:{self.ctx.device}")
-
-    @property
-    def grads(self) -> torch.Tensor:
-        return self._view(self._pg)
 
     def forward_backward(self, x: torch.Tensor, labels: torch.Tensor):
         """x: frames as NCHW fp32 (the reference layout) or NHWC fp32, normalised; labels (B,) -> (loss (B,), logits (B, classes))"""
@@ -682,25 +623,6 @@ class FrameModelTrainer(_BackboneMatmul):
     def step(self, batch_size: int, lr: float, momentum: float = 0.9, wd: float = 1e-4):
         check(self.lib.tn_finetune_sgd_step(self.handle, lr, momentum, wd, 1.0 / batch_size), "tn_finetune_sgd_step")
 
-    def get(self, name: str, gradient: bool = False, shape=None) -> np.ndarray:
-        shape = shape or self.shapes[name]
-        out = np.empty(int(np.prod(shape)), np.float32)
-        n = C.c_int64()
-        check(self.lib.tn_finetune_read_param(self.handle, name.encode(), 1 if gradient else 0,
-                                              out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n)), "tn_finetune_read_param")
-        return out[:n.value].reshape(shape).copy()
-
-    def state_dict(self) -> dict:
-        return {k: self.get(k) for k in self.names}
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.tn_finetune_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
 
 class CNNRNNTrainer(_BackboneMatmul):
     """End-to-end training step of ``CNNRNN(FrameModel(DenseNet121.features))`` over ``TimeDistributed`` frames, the way reference
@@ -713,6 +635,8 @@ class CNNRNNTrainer(_BackboneMatmul):
     ``grads`` is a tuple of flat device views: (backbone, head), or (head,) with a frozen backbone - what a data-parallel run
     all-reduces before ``step`` (``train.allreduce_and_step``).  A frozen backbone is not updated, but its BatchNorms still
     normalise with batch statistics and update their running statistics (docs/numerics.md)."""
+    _PARTS = 2
+    _ABI = "tn_cnnrnn_trainer"
 
     def __init__(self, params: dict, size: int = 224, classes: int = 11, batch: int = 2, steps: int = 8, type: str = "gru",
                  prefix: str = "densenet0_", rnn_prefix: str | None = None, dense_prefix: str = "cnnrnn0_dense0_",
@@ -722,42 +646,18 @@ class CNNRNNTrainer(_BackboneMatmul):
             raise ValueError(f"type must be 'gru' or 'lstm', got {type!r}")
         if rnn_prefix is None:
             rnn_prefix = f"cnnrnn0_{type}0_"
-        self.ctx = ctx or _lib.default_context()
-        self.lib = self.ctx.lib
+        super().__init__(ctx)
         self.type, self.size, self.classes, self.batch, self.steps = type, size, classes, batch, steps
         self.frozen = bool(freeze_backbone)
         self.prefix, self.rnn_prefix, self.dense_prefix = prefix, rnn_prefix, dense_prefix
-        self.names = [k for k in params if k.startswith((prefix, rnn_prefix, dense_prefix))]
-        self.shapes = {k: tuple(np.asarray(params[k]).shape) for k in self.names}
-        arr, keep = _lib.make_params({k: params[k] for k in self.names})
+        arr, keep = self._select(params, prefix, rnn_prefix, dense_prefix)
         h = C.c_void_p()
         check(self.lib.tn_cnnrnn_trainer_create(self.ctx.handle, _lib.RNN_GRU if type == "gru" else _lib.RNN_LSTM, arr, len(arr),
                                                 prefix.encode(), rnn_prefix.encode(), dense_prefix.encode(), size, size, classes,
                                                 batch, steps, 1 if self.frozen else 0, C.byref(h)), "tn_cnnrnn_trainer_create")
         del keep
-        self.handle = h
-        bw, bg, bn, hw, hg, hn = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.tn_cnnrnn_trainer_buffers(h, C.byref(bw), C.byref(bg), C.byref(bn), C.byref(hw), C.byref(hg), C.byref(hn)),
-              "tn_cnnrnn_trainer_buffers")
-        self._bb = (bw.value, bg.value, bn.value)
-        self._head = (hw.value, hg.value, hn.value)
+        self._adopt(h)
         self.set_matmul(matmul)
-
-    _MATMUL_ABI = "tn_cnnrnn_trainer"
-
-    def _view(self, addr, n):
-        class _Arr:
-            __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (addr, False), "version": 3}
-        return torch.as_tensor(_Arr(), device=f"cuda:{self.ctx.device}")
-
-    @property
-    def grads(self) -> tuple:
-        head = self._view(self._head[1], self._head[2])
-        return (head,) if self.frozen else (self._view(self._bb[1], self._bb[2]), head)
-
-    @property
-    def params(self) -> tuple:
-        return self._view(self._bb[0], self._bb[2]), self._view(self._head[0], self._head[2])
 
     def forward_backward(self, x: torch.Tensor, labels: torch.Tensor):
         """x: (batch, steps) frames, NCHW or NHWC per frame, fp32 normalised or uint8 (ToTensor + Normalize applied here);
@@ -781,26 +681,6 @@ class CNNRNNTrainer(_BackboneMatmul):
     def step(self, batch_size: int, lr: float, momentum: float = 0.9, wd: float = 1e-4):
         check(self.lib.tn_cnnrnn_trainer_sgd_step(self.handle, lr, momentum, wd, 1.0 / batch_size), "tn_cnnrnn_trainer_sgd_step")
 
-    def get(self, name: str, gradient: bool = False, shape=None) -> np.ndarray:
-        shape = shape or self.shapes[name]
-        out = np.empty(int(np.prod(shape)), np.float32)
-        n = C.c_int64()
-        check(self.lib.tn_cnnrnn_trainer_read_param(self.handle, name.encode(), 1 if gradient else 0,
-                                                    out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n)),
-              "tn_cnnrnn_trainer_read_param")
-        return out[:n.value].reshape(shape).copy()
-
-    def state_dict(self) -> dict:
-        return {k: self.get(k) for k in self.names}
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.tn_cnnrnn_trainer_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
 
 class GNMTFramesTrainer(_BackboneMatmul):
     """One frame-mode training step of the captioner, the way reference train_gnmt.py drives it without ``--feats_model``
@@ -815,6 +695,8 @@ class GNMTFramesTrainer(_BackboneMatmul):
     ``grads`` is a tuple of flat device views: (backbone, captioner), or (captioner,) with a frozen backbone - what a data-parallel
     run all-reduces before ``step``.  A frozen backbone is not updated, but its BatchNorms still normalise with batch statistics
     and update their running statistics (docs/numerics.md)."""
+    _PARTS = 2
+    _ABI = "tn_gnmt_frames_trainer"
 
     def __init__(self, params: dict, hidden: int, embed: int, vocab: int, size: int = 224, max_batch: int = 4, max_src_len: int = 16,
                  max_tgt_len: int = 64, max_frames: int | None = None, prefix: str = "gnmt_", backbone_prefix: str = "densenet0_",
@@ -823,16 +705,13 @@ class GNMTFramesTrainer(_BackboneMatmul):
         _lib.matmul_mode(matmul)                       # a wrong name raises before a context or the library is touched
         if cell_type not in ("gru", "lstm"):
             raise ValueError(f"cell_type must be 'gru' or 'lstm', got {cell_type!r}")
-        self.ctx = ctx or _lib.default_context()
-        self.lib = self.ctx.lib
+        super().__init__(ctx)
         self.size, self.hidden, self.embed, self.vocab = size, hidden, embed, vocab
         self.max_batch, self.max_src_len = max_batch, max_src_len
         self.max_frames = max_batch * max_src_len if max_frames is None else max_frames
         self.frozen = bool(freeze_backbone)
         self.prefix, self.backbone_prefix, self.cell_type = prefix, backbone_prefix, cell_type
-        self.names = [k for k in params if k.startswith((prefix, backbone_prefix))]
-        self.shapes = {k: tuple(np.asarray(params[k]).shape) for k in self.names}
-        arr, keep = _lib.make_params({k: params[k] for k in self.names})
+        arr, keep = self._select(params, prefix, backbone_prefix)
         h = C.c_void_p()
         check(self.lib.tn_gnmt_frames_trainer_create(self.ctx.handle, arr, len(arr), backbone_prefix.encode(), prefix.encode(),
                                                      _lib.RNN_GRU if cell_type == "gru" else _lib.RNN_LSTM, hidden, embed, vocab,
@@ -840,29 +719,8 @@ class GNMTFramesTrainer(_BackboneMatmul):
                                                      max_tgt_len, self.max_frames, 1 if self.frozen else 0, C.byref(h)),
               "tn_gnmt_frames_trainer_create")
         del keep
-        self.handle = h
-        bw, bg, bn, cw, cg, cn = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.tn_gnmt_frames_trainer_buffers(h, C.byref(bw), C.byref(bg), C.byref(bn), C.byref(cw), C.byref(cg), C.byref(cn)),
-              "tn_gnmt_frames_trainer_buffers")
-        self._bb = (bw.value, bg.value, bn.value)
-        self._cap = (cw.value, cg.value, cn.value)
+        self._adopt(h)
         self.set_matmul(matmul)
-
-    _MATMUL_ABI = "tn_gnmt_frames_trainer"
-
-    def _view(self, addr, n):
-        class _Arr:
-            __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (addr, False), "version": 3}
-        return torch.as_tensor(_Arr(), device=f"cuda:{self.ctx.device}")
-
-    @property
-    def grads(self) -> tuple:
-        cap = self._view(self._cap[1], self._cap[2])
-        return (cap,) if self.frozen else (self._view(self._bb[1], self._bb[2]), cap)
-
-    @property
-    def params(self) -> tuple:
-        return self._view(self._bb[0], self._bb[2]), self._view(self._cap[0], self._cap[2])
 
     def forward_backward(self, frames: torch.Tensor, src_valid_length: torch.Tensor, tgt: torch.Tensor,
                          tgt_valid_length: torch.Tensor, return_logits: bool = False):
@@ -896,24 +754,3 @@ class GNMTFramesTrainer(_BackboneMatmul):
 
     def step(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8):
         check(self.lib.tn_gnmt_frames_trainer_adam_step(self.handle, lr, beta1, beta2, epsilon), "tn_gnmt_frames_trainer_adam_step")
-
-    def get(self, name: str, gradient: bool = False, shape=None) -> np.ndarray:
-        shape = shape or self.shapes[name]
-        out = np.empty(int(np.prod(shape)), np.float32)
-        n = C.c_int64()
-        check(self.lib.tn_gnmt_frames_trainer_read_param(self.handle, name.encode(), 1 if gradient else 0,
-                                                         out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n)),
-              "tn_gnmt_frames_trainer_read_param")
-        return out[:n.value].reshape(shape).copy()
-
-    def state_dict(self) -> dict:
-        """Every parameter of both parts and the backbone's running statistics, by name."""
-        return {k: self.get(k) for k in self.names}
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self.lib.tn_gnmt_frames_trainer_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
