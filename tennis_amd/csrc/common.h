@@ -248,6 +248,7 @@ struct Block7Image {
   unsigned a_off[4], b_off[4];
 };
 bool dense_block7_supported(int H, int W, int K0, int nl);
+inline constexpr const char *kDenseBlock7Range = "7 x 7, K0 = 448 ... 992 in steps of 32, nl >= 1, K0 + 32 nl <= 1024";
 Block7Image pack_block7(const std::vector<Block7Layer> &layers, int K0);
 int launch_dense_block7(const DenseBlock7Args &a, hipStream_t s);
 
@@ -273,6 +274,9 @@ int dense_block28_units(int K0, int nl);
 size_t dense_block28_scratch_halfs();   // per frame
 std::vector<unsigned char> pack_block28(const std::vector<Block14Layer> &layers, int K0);
 int launch_dense_block28(const DenseStreamArgs &a, hipStream_t s);
+// what the two predicates accept, in words, for the messages of a refusal
+inline constexpr const char *kDenseBlock14Range = "14 x 14, K0 = 256 ... 992 in steps of 32, nl >= 1, K0 + 32 nl <= 1024";
+inline constexpr const char *kDenseBlock28Range = "28 x 28, K0 = 128 ... 512 in steps of 32, nl >= 1, K0 + 32 (nl - 1) <= 512";
 // the two kernels as a table, in the order the encoder tries them (encoder_plan.h, dbg.hip)
 struct DenseStreamKernel {
   int H;                         // the square map it runs
@@ -282,10 +286,11 @@ struct DenseStreamKernel {
   size_t (*scratch_halfs)();
   std::vector<unsigned char> (*pack)(const std::vector<Block14Layer> &layers, int K0);
   int (*launch)(const DenseStreamArgs &a, hipStream_t s);
+  const char *range;             // what `supported` accepts, in words
 };
 inline constexpr DenseStreamKernel kDenseStreamKernels[2] = {
-    {14, "dense_block_stream_14x14", dense_block14_supported, dense_block14_units, dense_block14_scratch_halfs, pack_block14, launch_dense_block14},
-    {28, "dense_block_stream_28x28", dense_block28_supported, dense_block28_units, dense_block28_scratch_halfs, pack_block28, launch_dense_block28},
+    {14, "dense_block_stream_14x14", dense_block14_supported, dense_block14_units, dense_block14_scratch_halfs, pack_block14, launch_dense_block14, kDenseBlock14Range},
+    {28, "dense_block_stream_28x28", dense_block28_supported, dense_block28_units, dense_block28_scratch_halfs, pack_block28, launch_dense_block28, kDenseBlock28Range},
 };
 
 // ---- the stem's operand (round 5) -------------------------------------------------------------------------------

@@ -285,7 +285,8 @@ struct tn_dbg_block7 {
 extern "C" int tn_dbg_block7_create(tn_ctx *ctx, int K0, int nl, const float *w1_all, const float *s1_all, const float *t1_all,
                                     const float *s2_all, const float *t2_all, const float *w3_all, void **out) {
   TN_REQUIRE(ctx && w1_all && s1_all && t1_all && s2_all && t2_all && w3_all && out, "tn_dbg_block7_create: null argument");
-  TN_REQUIRE(dense_block7_supported(7, 7, K0, nl), "tn_dbg_block7_create: unsupported geometry");
+  TN_REQUIRE(dense_block7_supported(7, 7, K0, nl), std::string("tn_dbg_block7_create: unsupported geometry (dense_block7 runs ") + kDenseBlock7Range + "): 7 x 7, K0 = " + std::to_string(K0) +
+                                                       ", nl = " + std::to_string(nl));
   TN_ON_DEVICE(ctx->device);
   std::vector<std::vector<float>> folded(nl);
   std::vector<Block7Layer> layers(nl);
@@ -353,7 +354,8 @@ static int dbg_stream_create(const DenseStreamKernel &sk, tn_ctx *ctx, int K0, i
                              const float *s2_all, const float *t2_all, const float *w3_all, void **out) {
   const std::string who = "tn_dbg_block" + std::to_string(sk.H) + "_create";
   TN_REQUIRE(ctx && w1_all && s1_all && t1_all && s2_all && t2_all && w3_all && out, who + ": null argument");
-  TN_REQUIRE(sk.supported(sk.H, sk.H, K0, nl), who + ": unsupported geometry");
+  TN_REQUIRE(sk.supported(sk.H, sk.H, K0, nl), who + ": unsupported geometry (dense_block" + std::to_string(sk.H) + " runs " + sk.range + "): " + std::to_string(sk.H) + " x " + std::to_string(sk.H) +
+                                                   ", K0 = " + std::to_string(K0) + ", nl = " + std::to_string(nl));
   TN_ON_DEVICE(ctx->device);
   std::vector<std::vector<float>> folded(nl);
   std::vector<Block14Layer> layers(nl);
@@ -385,6 +387,8 @@ static int dbg_stream_run(void *handle, void *buf_f16, int ldc, int B, unsigned 
   tn_dbg_stream_block *b = (tn_dbg_stream_block *)handle;
   TN_REQUIRE(b && buf_f16, "tn_dbg_block14_run / tn_dbg_block28_run: null argument");
   const std::string who = "tn_dbg_block" + std::to_string(b->kernel->H) + "_run";
+  TN_REQUIRE(B > 0, who + ": the batch must be positive: " + std::to_string(b->kernel->H) + " x " + std::to_string(b->kernel->H) + ", K0 = " + std::to_string(b->args.K0) +
+                        ", nl = " + std::to_string(b->args.nl) + ", ldc = " + std::to_string(ldc) + ", B = " + std::to_string(B));
   TN_ON_DEVICE(b->ctx->device);
   const size_t scratch_bytes = (size_t)B * b->kernel->scratch_halfs() * sizeof(f16);
   if (b->scratch_frames < B) {

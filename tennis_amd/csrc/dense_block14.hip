@@ -48,7 +48,10 @@ constexpr int kTileRows = 18;                     // row 0: zeros above the imag
 constexpr int kTileBytes = kTileRows * kTileRowB;
 constexpr int kLdsBytes = kTileBytes + kNR * kUnitBytes;
 constexpr int kPlaneB = 196 * 32;                 // one k-step (16 channels) of a frame in the private k-step-major copy
-constexpr int kFrameScrB = 64 * kPlaneB;          // 1024 channels
+constexpr int kScrPlanes = 64;                    // planes of the private copy: 1024 channels, the block's input AND everything it appends
+constexpr int kScrChannels = 16 * kScrPlanes;     // what dense_block14_supported admits: the ring refills are plain global loads, not bounded by srsrc
+constexpr int kFrameScrB = kScrPlanes * kPlaneB;
+static_assert(kScrChannels == 1024 && kFrameScrB == kScrChannels / 16 * kPlaneB, "dense_block14_supported is tied to the scratch a frame has");
 static_assert(kLdsBytes <= 160 * 1024, "LDS");
 
 // s_waitcnt vmcnt(N) constants of the intervals only this kernel has (tests/test_cpu_block14.py; the shared ones: dense_stream.h)
@@ -522,7 +525,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }  // namespace
 
 bool dense_block14_supported(int H, int W, int K0, int nl) {
-  return H == 14 && W == 14 && K0 % 32 == 0 && K0 >= 256 && nl >= 1 && K0 + 32 * (nl - 1) <= 2048;
+  // every channel the block reads or appends has a plane in the frame's scratch (kFrameScrB): a ring refill past plane kScrPlanes - 1
+  // would read the next frame's planes, or past the allocation
+  return H == 14 && W == 14 && K0 % 32 == 0 && K0 >= 256 && nl >= 1 && K0 + 32 * nl <= kScrChannels;
 }
 
 int dense_block14_units(int K0, int nl) {      // (with the four units of padding the last intervals' DMA reads)
@@ -534,7 +539,7 @@ int dense_block14_units(int K0, int nl) {      // (with the four units of paddin
 size_t dense_block14_scratch_halfs() { return (size_t)kFrameScrB / 2; }
 
 int launch_dense_block14(const DenseStreamArgs &a, hipStream_t s) {
-  return launch_stream_block<dense_block14_kernel>("dense_block14", a, dense_block14_supported(14, 14, a.K0, a.nl), dense_block14_units(a.K0, a.nl), kLdsBytes, s);
+  return launch_stream_block<dense_block14_kernel>("dense_block14", 14, kDenseBlock14Range, a, dense_block14_supported(14, 14, a.K0, a.nl), dense_block14_units(a.K0, a.nl), kLdsBytes, s);
 }
 
 // ---- host-side packing: the block's weight stream (what a unit of each kind holds: StreamWriter, dense_stream.h) ----

@@ -502,7 +502,7 @@ int dense_block28_units(int K0, int nl) {      // (the prologue unit in front, f
 size_t dense_block28_scratch_halfs() { return (size_t)kFrameScrB / 2; }
 
 int launch_dense_block28(const DenseStreamArgs &a, hipStream_t s) {
-  return launch_stream_block<dense_block28_kernel>("dense_block28", a, dense_block28_supported(28, 28, a.K0, a.nl), dense_block28_units(a.K0, a.nl), kLdsBytes, s);
+  return launch_stream_block<dense_block28_kernel>("dense_block28", 28, kDenseBlock28Range, a, dense_block28_supported(28, 28, a.K0, a.nl), dense_block28_units(a.K0, a.nl), kLdsBytes, s);
 }
 
 // ---- host-side packing: the block's weight stream (what a unit of each kind holds: StreamWriter, dense_stream.h) ----

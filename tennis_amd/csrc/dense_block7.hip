@@ -422,8 +422,11 @@ Block7Image pack_block7(const std::vector<Block7Layer> &layers, int K0) {
 }
 
 int launch_dense_block7(const DenseBlock7Args &a, hipStream_t s) {
-  TN_REQUIRE(dense_block7_supported(7, 7, a.K0, a.nl) && a.ldc % 8 == 0 && a.K0 + 32 * a.nl <= a.ldc && a.B > 0,
-             "dense_block7: bad geometry");
+  const std::string geom = "7 x 7, K0 = " + std::to_string(a.K0) + ", nl = " + std::to_string(a.nl) + ", ldc = " + std::to_string(a.ldc) + ", B = " + std::to_string(a.B);
+  TN_REQUIRE(dense_block7_supported(7, 7, a.K0, a.nl), std::string("dense_block7: unsupported geometry (this kernel runs ") + kDenseBlock7Range + "): " + geom);
+  TN_REQUIRE(a.ldc % 8 == 0, "dense_block7: the row pitch must be a multiple of 8: " + geom);
+  TN_REQUIRE(a.K0 + 32 * a.nl <= a.ldc, "dense_block7: the row pitch does not hold the last layer's output: " + geom);
+  TN_REQUIRE(a.B > 0, "dense_block7: the batch must be positive: " + geom);
   TN_SET_ATTR_ONCE_PER_DEVICE(TN_HIP_CHECK(hipFuncSetAttribute((const void *)dense_block7_kernel<kRingDepth>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes)));
   hipLaunchKernelGGL((dense_block7_kernel<kRingDepth>), dim3(a.B), dim3(256), kLdsBytes, s, a);
   TN_HIP_CHECK(hipGetLastError());

@@ -178,11 +178,17 @@ struct StreamWriter {
 };
 
 // One launch helper for both kernels: the operand checks, the once-per-device opt-in to the kernel's dynamic LDS, the launch.
-// `supported` / `units`: the kernel's own dense_blockNN_supported / dense_blockNN_units for (a.K0, a.nl).
+// `supported` / `units`: the kernel's own dense_blockNN_supported / dense_blockNN_units for (a.K0, a.nl); hw, range: the map size and
+// the accepted range in words - every refusal names the geometry it was asked for.
 template <void (*KERNEL)(DenseStreamArgs)>
-int launch_stream_block(const char *name, const DenseStreamArgs &a, bool supported, int units, int lds_bytes, hipStream_t s) {
+int launch_stream_block(const char *name, int hw, const char *range, const DenseStreamArgs &a, bool supported, int units, int lds_bytes, hipStream_t s) {
   TN_REQUIRE(a.buf && a.stream && a.scratch, std::string(name) + ": null operand");
-  TN_REQUIRE(supported && a.ldc % 64 == 0 && a.K0 + 32 * a.nl <= a.ldc && a.B > 0, std::string(name) + ": unsupported geometry");
+  const std::string geom = std::to_string(hw) + " x " + std::to_string(hw) + ", K0 = " + std::to_string(a.K0) + ", nl = " + std::to_string(a.nl) +
+                           ", ldc = " + std::to_string(a.ldc) + ", B = " + std::to_string(a.B);
+  TN_REQUIRE(supported, std::string(name) + ": unsupported geometry (this kernel runs " + range + "): " + geom);
+  TN_REQUIRE(a.ldc % 64 == 0, std::string(name) + ": the row pitch must be a multiple of 64: " + geom);
+  TN_REQUIRE(a.K0 + 32 * a.nl <= a.ldc, std::string(name) + ": the row pitch does not hold the last layer's output: " + geom);
+  TN_REQUIRE(a.B > 0, std::string(name) + ": the batch must be positive: " + geom);
   TN_REQUIRE(a.total_units == units, std::string(name) + ": stream does not match the block");
   TN_SET_ATTR_ONCE_PER_DEVICE(TN_HIP_CHECK(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)));
   hipLaunchKernelGGL(KERNEL, dim3(a.B), dim3(256), lds_bytes, s, a);
