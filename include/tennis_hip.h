@@ -280,6 +280,23 @@ int tn_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int hidden, in
                    int n_params, const char *rnn_prefix, const char *dense_prefix, int max_batch, int max_steps, tn_head **out);
 int tn_head_forward_backward(tn_head *h, const float *x, const int32_t *labels, int batch, int steps, float *loss,
                              float *logits);
+/* The same step from a device-resident feature table.  Replaces what feeds the step in the reference: TennisSet.__getitem__
+ * opening one .npy per window step (dataset.py:190-213), the loader stacking them to (B, T, F) and the per-batch copy to the
+ * device in front of ag.record / backward / trainer.step (train.py:410-424).  The table is uploaded once; a step names its
+ * window rows, and the two kernels that read the (B*T, F) window matrix (the i2h projection and dW_ih = dGI^T X) gather them
+ * while they stage the operand, in the arithmetic order of the materialised step: the results are bit-identical to
+ * tn_head_forward_backward on the gathered matrix.
+ * set_features: feats (rows, F) fp32 DEVICE of row stride ld >= F floats; BORROWED, not copied - it must stay alive and
+ *   unchanged while rows calls use it; a later set_features replaces it.
+ * forward_backward_rows: row_idx (batch * steps) int32 DEVICE in order b * steps + t; an index is clamped to [0, rows - 1]
+ *   inside the kernels, so no content of the array reads outside the table.  Everything else as tn_head_forward_backward.
+ * forward_rows: the forward half only, logits (batch, classes) fp32 DEVICE; gradients, momentum and parameters untouched.
+ * A rows call before set_features, null arguments and batch or steps over the handle's maxima are TN_ERR_INVALID.  No call
+ * allocates. */
+int tn_head_set_features(tn_head *h, const float *feats, int rows, int ld);
+int tn_head_forward_backward_rows(tn_head *h, const int32_t *row_idx, const int32_t *labels, int batch, int steps, float *loss,
+                                  float *logits);
+int tn_head_forward_rows(tn_head *h, const int32_t *row_idx, int batch, int steps, float *logits);
 int tn_head_buffers(tn_head *h, float **params_dev, float **grads_dev, int64_t *numel);
 int tn_head_sgd_step(tn_head *h, float lr, float momentum, float wd, float rescale_grad);
 int tn_head_read_param(tn_head *h, const char *name, int gradient, float *out_host, int64_t capacity, int64_t *numel);

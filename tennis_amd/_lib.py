@@ -100,6 +100,9 @@ _SIGS = {
     "tn_head_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_char_p, C.c_int,
                                  C.c_int, C.POINTER(_P)]),
     "tn_head_forward_backward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "tn_head_set_features": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "tn_head_forward_backward_rows": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "tn_head_forward_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "tn_head_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
     "tn_head_sgd_step": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float]),
     "tn_head_read_param": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),

@@ -278,6 +278,8 @@ struct tn_head : TrainParams, HeadOffsets {
   float *whT;                      // [2][H][G*H] transposed h2h for the forward recurrence
   float *gi, *seq, *gates, *pooled, *dlog, *dpool, *dseq, *dgi, *dgh, *hprev, *logits, *loss;
   int32_t *arg;
+  const float *feats = nullptr;    // tn_head_set_features: the caller's (feat_rows, F) table of row stride feat_ld, borrowed
+  int feat_rows = 0, feat_ld = 0;
 };
 
 static int head_refresh_whT(tn_head *h) {
@@ -326,8 +328,11 @@ extern "C" int tn_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int
 
 // The head's step on x (B*T, F; rows b*T + t).  dx non-null: also the gradient with respect to x, dX = dGI W_ih (M, F; row
 // stride ldx, assigned) - what the end-to-end CNN-RNN step hands to the backbone's backward.
-static int head_step(tn_head *h, const float *x, const int32_t *labels, int B, int T, float *loss, float *logits, float *dx,
-                     int ldx) {
+// rows non-null: x is never materialised - row m of it is row rows[m] of the handle's feature table (tn_head_set_features),
+// gathered inside the two kernels that read x (the i2h projection and dW_ih = dGI^T X).  labels null: the forward half only
+// (through the logits; gradients, momentum and parameters untouched).
+static int head_step(tn_head *h, const float *x, const int32_t *rows, const int32_t *labels, int B, int T, float *loss, float *logits,
+                     float *dx, int ldx) {
   hipStream_t s = h->ctx->stream;
   const int F = h->F, H = h->H, C = h->C, GH = h->G * h->H, M = B * T;
   const bool lstm = h->G == 4;
@@ -335,11 +340,16 @@ static int head_step(tn_head *h, const float *x, const int32_t *labels, int B, i
   int rc;
 #define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
   // forward: one i2h GEMM for both directions, recurrence with saved gates, max over T (argmax kept), Dense
-  TN_TRY(launch_linear_f32(x, F, w + h->o_wi, F, w + h->o_bi, h->gi, 2 * GH, M, 2 * GH, F, 0, s));
+  if (rows) TN_TRY(launch_linear_f32_rows(h->feats, h->feat_ld, rows, h->feat_rows, w + h->o_wi, F, w + h->o_bi, h->gi, 2 * GH, M, 2 * GH, F, 0, s));
+  else TN_TRY(launch_linear_f32(x, F, w + h->o_wi, F, w + h->o_bi, h->gi, 2 * GH, M, 2 * GH, F, 0, s));
   TN_TRY(launch_rnn_recurrent(h->G, h->gi, 2 * GH, h->whT, w + h->o_bh, nullptr, h->seq, 2 * H, nullptr, nullptr, B, T, H, 2, s,
                               h->gates));
   TN_TRY(launch_pool_max_arg(h->seq, B, T, 2 * H, h->pooled, h->arg, s));
   TN_TRY(launch_linear_f32(h->pooled, 2 * H, w + h->o_wd, 2 * H, w + h->o_bd, h->logits, C, B, C, 2 * H, 0, s));
+  if (!labels) {
+    if (logits) TN_HIP_CHECK(hipMemcpyAsync(logits, h->logits, sizeof(float) * B * C, hipMemcpyDeviceToDevice, s));
+    return TN_OK;
+  }
   TN_TRY(launch_softmax_ce(h->logits, labels, B, C, h->loss, h->dlog, s));
   // backward
   TN_TRY(launch_dense_bwd(h->dlog, h->pooled, w + h->o_wd, B, C, 2 * H, g + h->o_wd, g + h->o_bd, h->dpool, s));
@@ -347,7 +357,8 @@ static int head_step(tn_head *h, const float *x, const int32_t *labels, int B, i
   if (lstm) TN_TRY(launch_lstm_train_bwd(h->seq, h->gates, h->dseq, w + h->o_wh, h->dgi, h->hprev, B, T, H, s));
   else TN_TRY(launch_gru_train_bwd(h->seq, h->gates, h->dseq, w + h->o_wh, h->dgi, h->dgh, h->hprev, B, T, H, s));
   const float *dgh = lstm ? h->dgi : h->dgh;   // LSTM: one pre-activation gradient feeds both branches
-  TN_TRY(launch_gemm_tn_f32(h->dgi, 2 * GH, x, F, g + h->o_wi, F, 2 * GH, F, M, s));      // dW_ih = dGI^T X
+  if (rows) TN_TRY(launch_gemm_tn_f32_rows(h->dgi, 2 * GH, h->feats, h->feat_ld, rows, h->feat_rows, g + h->o_wi, F, 2 * GH, F, M, s));
+  else TN_TRY(launch_gemm_tn_f32(h->dgi, 2 * GH, x, F, g + h->o_wi, F, 2 * GH, F, M, s));      // dW_ih = dGI^T X
   TN_TRY(launch_colsum_f32(h->dgi, 2 * GH, M, 2 * GH, g + h->o_bi, s));
   for (int d = 0; d < 2; ++d)                                                              // dW_hh = dGH^T H_prev
     TN_TRY(launch_gemm_tn_f32(dgh + d * GH, 2 * GH, h->hprev + (long)d * M * H, H, g + h->o_wh + (long)d * GH * H, H,
@@ -365,7 +376,31 @@ extern "C" int tn_head_forward_backward(tn_head *h, const float *x, const int32_
   TN_REQUIRE(h && x && labels, "tn_head_forward_backward: null argument");
   TN_REQUIRE(B > 0 && B <= h->maxB && T > 0 && T <= h->maxT, "tn_head_forward_backward: batch / steps exceed the maxima");
   TN_ON_DEVICE(h->ctx->device);
-  return head_step(h, x, labels, B, T, loss, logits, nullptr, 0);
+  return head_step(h, x, nullptr, labels, B, T, loss, logits, nullptr, 0);
+}
+
+extern "C" int tn_head_set_features(tn_head *h, const float *feats, int rows, int ld) {
+  TN_REQUIRE(h && feats, "tn_head_set_features: null argument");
+  TN_REQUIRE(rows > 0 && ld >= h->F, "tn_head_set_features: needs rows > 0 and ld >= the handle's input size");
+  h->feats = feats; h->feat_rows = rows; h->feat_ld = ld;
+  return TN_OK;
+}
+
+extern "C" int tn_head_forward_backward_rows(tn_head *h, const int32_t *row_idx, const int32_t *labels, int B, int T, float *loss,
+                                             float *logits) {
+  TN_REQUIRE(h && row_idx && labels, "tn_head_forward_backward_rows: null argument");
+  TN_REQUIRE(h->feats, "tn_head_forward_backward_rows: no feature table (call tn_head_set_features first)");
+  TN_REQUIRE(B > 0 && B <= h->maxB && T > 0 && T <= h->maxT, "tn_head_forward_backward_rows: batch / steps exceed the maxima");
+  TN_ON_DEVICE(h->ctx->device);
+  return head_step(h, nullptr, row_idx, labels, B, T, loss, logits, nullptr, 0);
+}
+
+extern "C" int tn_head_forward_rows(tn_head *h, const int32_t *row_idx, int B, int T, float *logits) {
+  TN_REQUIRE(h && row_idx && logits, "tn_head_forward_rows: null argument");
+  TN_REQUIRE(h->feats, "tn_head_forward_rows: no feature table (call tn_head_set_features first)");
+  TN_REQUIRE(B > 0 && B <= h->maxB && T > 0 && T <= h->maxT, "tn_head_forward_rows: batch / steps exceed the maxima");
+  TN_ON_DEVICE(h->ctx->device);
+  return head_step(h, nullptr, row_idx, nullptr, B, T, nullptr, logits, nullptr, 0);
 }
 
 extern "C" int tn_head_buffers(tn_head *h, float **params_dev, float **grads_dev, int64_t *numel) {
@@ -455,7 +490,7 @@ extern "C" int tn_cnnrnn_trainer_forward_backward(tn_cnnrnn_trainer *t, const fl
   int rc;
 #define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
   TN_TRY(ft_forward_features(t->bb, x, t->B * t->T));
-  TN_TRY(head_step(t->head, ft_features(t->bb), labels, t->B, t->T, loss, logits, t->frozen ? nullptr : ft_feature_grad(t->bb), t->F));
+  TN_TRY(head_step(t->head, ft_features(t->bb), nullptr, labels, t->B, t->T, loss, logits, t->frozen ? nullptr : ft_feature_grad(t->bb), t->F));
   if (!t->frozen) TN_TRY(ft_backward_features(t->bb, t->B * t->T));
   ft_update_running(t->bb);
 #undef TN_TRY

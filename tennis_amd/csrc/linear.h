@@ -62,6 +62,10 @@ __device__ __forceinline__ void lat_tile_f32(const float *__restrict__ X, int ld
 
 int launch_linear_f32(const float *X, int ldx, const float *Wt, int ldw, const float *bias, float *Y, int ldy,
                       int M, int N, int K, int accumulate, hipStream_t s);
+// The X operand gathered from a table: row m of X is table + (long)clamp(rows[m], 0, n_rows - 1) * ld (rows: M int32, DEVICE).
+// Dispatch, k order and MFMA order are launch_linear_f32's, so the result equals that of the materialised X bit for bit.
+int launch_linear_f32_rows(const float *table, int ld, const int32_t *rows, int n_rows, const float *Wt, int ldw, const float *bias,
+                           float *Y, int ldy, int M, int N, int K, int accumulate, hipStream_t s);
 // Latency-optimised form for skinny problems (few rows, K >= 128, float4-aligned operands; falls back to launch_linear_f32
 // otherwise): 16 x 16 output tiles, K split over the four waves of a workgroup, every operand requested up front.
 int launch_linear_f32_lat(const float *X, int ldx, const float *Wt, int ldw, const float *bias, float *Y, int ldy, int M, int N, int K,

@@ -16,12 +16,16 @@ constexpr int kPD = 4;   // k-tiles of 16 in flight per thread (registers) ahead
 // what is launched; skinny problems go to linear_f32_skinny_kernel below).
 // BN (round 4, the fine-tuning path): the X operand is transformed while it is staged, x -> relu(x * asc[k] + ash[k]) - a
 // training-mode BatchNorm + ReLU in front of a 1x1 convolution never materialises its output (finetune.hip).
-template <int F, bool BN = false>
+// GX (the temporal head trained from a feature table): row m of the X operand is row clamp(xrows[m], 0, xn - 1) of the table X
+// points to (row stride ldx).  A thread stages the same row for every k-tile, so its index is loaded once, before the loop; the
+// clamp keeps every read inside the table whatever xrows holds.  k-loop and MFMA order are those of the plain form.
+template <int F, bool BN = false, bool GX = false>
 __global__ __launch_bounds__(256) void linear_f32_kernel(const float *__restrict__ X, int ldx,
                                                          const float *__restrict__ Wt, int ldw,
                                                          const float *__restrict__ bias, float *__restrict__ Y,
                                                          int ldy, int M, int N, int K, int accumulate,
-                                                         const float *__restrict__ asc = nullptr, const float *__restrict__ ash = nullptr) {
+                                                         const float *__restrict__ asc = nullptr, const float *__restrict__ ash = nullptr,
+                                                         const int32_t *__restrict__ xrows = nullptr, int xn = 0) {
   constexpr int BT = 32 * F;             // tile rows (M) = tile columns (N)
   __shared__ float As[2][BT][17];
   __shared__ float Bs[2][BT][17];
@@ -34,6 +38,7 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float *__restrict
   const bool vec = ((ldx | ldw | K) & 3) == 0 && (((uintptr_t)X | (uintptr_t)Wt) & 15) == 0;
   const int am = m0 + srow, bn = n0 + srow;
   const float *xrow = X + (long)am * ldx, *wrow = Wt + (long)bn * ldw;
+  if constexpr (GX) xrow = X + (long)(doA && am < M ? min(max(xrows[am], 0), xn - 1) : 0) * ldx;
   const int nk = (K + 15) / 16;
 
   f32x4 acc[F][F];
@@ -126,12 +131,13 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float *__restrict
 
 // Skinny problems (fewer than two 64x64 tiles per CU): 32x32 tile, one 16x16 fragment per wave, BK = 32 so that a
 // k-tile carries 8 MFMAs per barrier.  Same k order per output element as linear_f32_kernel (one accumulator chain).
-template <bool BN = false>
+template <bool BN = false, bool GX = false>        // GX: as in linear_f32_kernel
 __global__ __launch_bounds__(256) void linear_f32_skinny_kernel(const float *__restrict__ X, int ldx,
                                                                 const float *__restrict__ Wt, int ldw,
                                                                 const float *__restrict__ bias, float *__restrict__ Y,
                                                                 int ldy, int M, int N, int K, int accumulate,
-                                                                const float *__restrict__ asc = nullptr, const float *__restrict__ ash = nullptr) {
+                                                                const float *__restrict__ asc = nullptr, const float *__restrict__ ash = nullptr,
+                                                                const int32_t *__restrict__ xrows = nullptr, int xn = 0) {
   __shared__ float As[2][32][33];
   __shared__ float Bs[2][32][33];
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
@@ -141,6 +147,7 @@ __global__ __launch_bounds__(256) void linear_f32_skinny_kernel(const float *__r
   const bool vec = ((ldx | ldw | K) & 3) == 0 && (((uintptr_t)X | (uintptr_t)Wt) & 15) == 0;
   const int am = m0 + srow, bn = n0 + srow;
   const float *xrow = X + (long)am * ldx, *wrow = Wt + (long)bn * ldw;
+  if constexpr (GX) xrow = X + (long)(am < M ? min(max(xrows[am], 0), xn - 1) : 0) * ldx;
   const int nk = (K + 31) / 32;
   f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
   constexpr int PD = 3;
@@ -298,11 +305,31 @@ int launch_linear_f32(const float *X, int ldx, const float *Wt, int ldw, const f
   if (big >= 512) {
     const dim3 grid((N + 63) / 64, (M + 63) / 64), block(256);
     hipLaunchKernelGGL((linear_f32_kernel<2, false>), grid, block, 0, s, X, ldx, Wt, ldw, bias, Y, ldy, M, N, K, accumulate, (const float *)nullptr,
-                       (const float *)nullptr);
+                       (const float *)nullptr, (const int32_t *)nullptr, 0);
   } else {   // fewer than two 64x64 tiles per CU: quarter-size tiles put four times as many CUs to work
     const dim3 grid((N + 31) / 32, (M + 31) / 32), block(256);
     hipLaunchKernelGGL(linear_f32_skinny_kernel<false>, grid, block, 0, s, X, ldx, Wt, ldw, bias, Y, ldy, M, N, K, accumulate, (const float *)nullptr,
-                       (const float *)nullptr);
+                       (const float *)nullptr, (const int32_t *)nullptr, 0);
+  }
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+
+// Y = G W^T (+ bias) with G[m] = table[clamp(rows[m], 0, n_rows - 1)]: the X operand gathered from a table while it is staged.
+// Same tile-count dispatch, k order and MFMA order as launch_linear_f32 on the materialised G.
+int launch_linear_f32_rows(const float *table, int ld, const int32_t *rows, int n_rows, const float *Wt, int ldw, const float *bias,
+                           float *Y, int ldy, int M, int N, int K, int accumulate, hipStream_t s) {
+  if (M <= 0 || N <= 0) return TN_OK;
+  TN_REQUIRE(table && rows && n_rows > 0 && ld >= K, "linear_f32_rows: needs a table of at least one row, ld >= K, and the row indices");
+  const long big = (long)((N + 63) / 64) * ((M + 63) / 64);
+  if (big >= 512) {
+    const dim3 grid((N + 63) / 64, (M + 63) / 64), block(256);
+    hipLaunchKernelGGL((linear_f32_kernel<2, false, true>), grid, block, 0, s, table, ld, Wt, ldw, bias, Y, ldy, M, N, K, accumulate,
+                       (const float *)nullptr, (const float *)nullptr, rows, n_rows);
+  } else {
+    const dim3 grid((N + 31) / 32, (M + 31) / 32), block(256);
+    hipLaunchKernelGGL((linear_f32_skinny_kernel<false, true>), grid, block, 0, s, table, ld, Wt, ldw, bias, Y, ldy, M, N, K, accumulate,
+                       (const float *)nullptr, (const float *)nullptr, rows, n_rows);
   }
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
@@ -315,10 +342,10 @@ int launch_linear_f32_bnrelu(const float *X, int ldx, const float *asc, const fl
   const long big = (long)((N + 63) / 64) * ((M + 63) / 64);
   if (big >= 512) {
     const dim3 grid((N + 63) / 64, (M + 63) / 64), block(256);
-    hipLaunchKernelGGL((linear_f32_kernel<2, true>), grid, block, 0, s, X, ldx, Wt, ldw, bias, Y, ldy, M, N, K, accumulate, asc, ash);
+    hipLaunchKernelGGL((linear_f32_kernel<2, true>), grid, block, 0, s, X, ldx, Wt, ldw, bias, Y, ldy, M, N, K, accumulate, asc, ash, (const int32_t *)nullptr, 0);
   } else {
     const dim3 grid((N + 31) / 32, (M + 31) / 32), block(256);
-    hipLaunchKernelGGL(linear_f32_skinny_kernel<true>, grid, block, 0, s, X, ldx, Wt, ldw, bias, Y, ldy, M, N, K, accumulate, asc, ash);
+    hipLaunchKernelGGL(linear_f32_skinny_kernel<true>, grid, block, 0, s, X, ldx, Wt, ldw, bias, Y, ldy, M, N, K, accumulate, asc, ash, (const int32_t *)nullptr, 0);
   }
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;

@@ -22,6 +22,10 @@ int launch_gemm_tn_f32(const float *A, int lda, const float *Bm, int ldb, float 
 // ... with B -> relu(B * bsc[n] + bsh[n]) applied while the operand is staged
 int launch_gemm_tn_f32_bnrelu(const float *A, int lda, const float *Bm, int ldb, const float *bsc, const float *bsh, float *Cm, int ldc,
                               int M, int N, int K, hipStream_t s, float *workspace = nullptr, long workspace_floats = 0);
+// ... with the B operand gathered from a table: row k of B is table + (long)clamp(rows[k], 0, n_rows - 1) * ld (rows: K int32,
+// DEVICE).  Un-split only; equals launch_gemm_tn_f32 (no workspace) on the materialised B bit for bit.
+int launch_gemm_tn_f32_rows(const float *A, int lda, const float *table, int ld, const int32_t *rows, int n_rows, float *Cm, int ldc,
+                            int M, int N, int K, hipStream_t s);
 // C (M, N; row stride ldc) (+)= A (M, K; row stride lda) B (K, N; row stride ldb), both row-major (gemm_nn.hip)
 int launch_gemm_nn_f32(const float *A, int lda, const float *Bm, int ldb, float *Cm, int ldc, int M, int N, int K, int accumulate,
                        hipStream_t s);

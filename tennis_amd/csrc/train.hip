@@ -324,14 +324,21 @@ __global__ __launch_bounds__(MAXT) void lstm_train_bwd_kernel(const float *__res
 // fragments want (lane = (column, k)): rows of 64 columns are staged as they lie, no transposes.  kTnPD k-tiles of 16
 // stay in flight in registers (the compiler does not overlap a plain load -> LDS -> MFMA loop by itself).
 constexpr int kTnPD = 4;
-template <bool BNB = false>       // BNB: the B operand goes through relu(b * bsc[n] + bsh[n]) while it is staged (finetune.hip)
+// BNB: the B operand goes through relu(b * bsc[n] + bsh[n]) while it is staged (finetune.hip).
+// GB (the temporal head trained from a feature table): row k of B is row clamp(brows[k], 0, bn_rows - 1) of the table Bm points to
+// (row stride ldb).  The staged row changes with every k-tile, so a thread keeps the index of its next data fetch in a register,
+// loaded kTnPD k-tiles before that fetch is issued: no data load waits on an index load inside the loop.  The clamp keeps every
+// read inside the table whatever brows holds.  k-loop and MFMA order are those of the plain form.
+template <bool BNB = false, bool GB = false>
 __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(const float *__restrict__ A, int lda,
                                                           const float *__restrict__ Bm, int ldb,
                                                           float *__restrict__ Cm, int ldc, int M, int N, int K, int kchunk,
-                                                          const float *__restrict__ bsc = nullptr, const float *__restrict__ bsh = nullptr) {
+                                                          const float *__restrict__ bsc = nullptr, const float *__restrict__ bsh = nullptr,
+                                                          const int32_t *__restrict__ brows = nullptr, int bn_rows = 0) {
   // split-K: slice blockIdx.z covers rows [z*kchunk, (z+1)*kchunk) and writes its own (M, N) partial result
   A += (long)blockIdx.z * kchunk * lda;
-  Bm += (long)blockIdx.z * kchunk * ldb;
+  if constexpr (GB) brows += (long)blockIdx.z * kchunk;       // a slice of a gathered B is a slice of its index array
+  else Bm += (long)blockIdx.z * kchunk * ldb;
   Cm += (long)blockIdx.z * M * ldc;
   K = min(kchunk, K - (int)blockIdx.z * kchunk);
   __shared__ float As[2][16][64 + 4], Bs[2][16][64 + 4];
@@ -346,13 +353,19 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(const float *__restric
 #pragma unroll
     for (int q = 0; q < 2; ++q) acc[i][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float av[kTnPD][4], bv[kTnPD][4];
-  auto fetch = [&](int it, float *a4, float *b4) {
+  int bidx[kTnPD];                  // GB: slot p holds the table row of the k-tile slot p fetches next
+  auto row_of = [&](int it) {       // the table row this thread stages for k-tile `it` (0 past the end: never read)
+    const int k = it * 16 + sk;
+    return it < nk && k < K ? min(max(brows[k], 0), bn_rows - 1) : 0;
+  };
+  auto fetch = [&](int it, float *a4, float *b4, int brow) {
     const int k = it * 16 + sk;
 #pragma unroll
     for (int q = 0; q < 4; ++q) { a4[q] = 0.f; b4[q] = 0.f; }
     if (it >= nk || k >= K) return;
+    const long bk = GB ? brow : k;            // the row of Bm staged for this k
     if (vec) {
-      const float4 va = *(const float4 *)(A + (long)k * lda + m0 + sc), vb = *(const float4 *)(Bm + (long)k * ldb + n0 + sc);
+      const float4 va = *(const float4 *)(A + (long)k * lda + m0 + sc), vb = *(const float4 *)(Bm + bk * ldb + n0 + sc);
       a4[0] = va.x; a4[1] = va.y; a4[2] = va.z; a4[3] = va.w;
       b4[0] = vb.x; b4[1] = vb.y; b4[2] = vb.z; b4[3] = vb.w;
       if constexpr (BNB) {
@@ -365,14 +378,22 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(const float *__restric
       for (int q = 0; q < 4; ++q) {
         if (m0 + sc + q < M) a4[q] = A[(long)k * lda + m0 + sc + q];
         if (n0 + sc + q < N) {
-          b4[q] = Bm[(long)k * ldb + n0 + sc + q];
+          b4[q] = Bm[bk * ldb + n0 + sc + q];
           if constexpr (BNB) b4[q] = fmaxf(fmaf(b4[q], bsc[n0 + sc + q], bsh[n0 + sc + q]), 0.f);
         }
       }
     }
   };
+  if constexpr (GB) {               // the indices of the first 2 kTnPD k-tiles are requested together, ahead of any data
+    int first[kTnPD];
 #pragma unroll
-  for (int p = 0; p < kTnPD; ++p) fetch(p, av[p], bv[p]);
+    for (int p = 0; p < kTnPD; ++p) { first[p] = row_of(p); bidx[p] = row_of(p + kTnPD); }
+#pragma unroll
+    for (int p = 0; p < kTnPD; ++p) fetch(p, av[p], bv[p], first[p]);
+  } else {
+#pragma unroll
+    for (int p = 0; p < kTnPD; ++p) fetch(p, av[p], bv[p], 0);
+  }
   for (int it0 = 0; it0 < nk; it0 += kTnPD) {
 #pragma unroll
     for (int p = 0; p < kTnPD; ++p) {
@@ -381,7 +402,12 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(const float *__restric
         const int buf = it & 1;
         *(float4 *)&As[buf][sk][sc] = make_float4(av[p][0], av[p][1], av[p][2], av[p][3]);
         *(float4 *)&Bs[buf][sk][sc] = make_float4(bv[p][0], bv[p][1], bv[p][2], bv[p][3]);
-        fetch(it + kTnPD, av[p], bv[p]);
+        if constexpr (GB) {
+          fetch(it + kTnPD, av[p], bv[p], bidx[p]);
+          bidx[p] = row_of(it + 2 * kTnPD);
+        } else {
+          fetch(it + kTnPD, av[p], bv[p], 0);
+        }
         __syncthreads();
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -555,6 +581,7 @@ int launch_lstm_train_bwd(const float *seq, const float *gates, const float *dse
 // C (M,N) = A^T B over K rows; bsc / bsh non-null: B -> relu(B * bsc[n] + bsh[n]) on the way in (a BatchNorm + ReLU that is never stored)
 static int gemm_tn_dispatch(const float *A, int lda, const float *Bm, int ldb, const float *bsc, const float *bsh, float *Cm, int ldc, int M,
                             int N, int K, hipStream_t s, float *workspace, long workspace_floats) {
+  const int32_t *const no_rows = nullptr;
   const int tiles = ((N + 63) / 64) * ((M + 63) / 64);
   // few output tiles and a long reduction (weight gradients over all pixels): split K over workgroups, partial results
   // in the caller's workspace, summed in slice order (deterministic)
@@ -567,15 +594,15 @@ static int gemm_tn_dispatch(const float *A, int lda, const float *Bm, int ldb, c
   const bool bn = bsc != nullptr;
   if (S <= 1) {
     const dim3 grid((N + 63) / 64, (M + 63) / 64, 1);
-    if (bn) hipLaunchKernelGGL(gemm_tn_f32_kernel<true>, grid, dim3(256), 0, s, A, lda, Bm, ldb, Cm, ldc, M, N, K, K, bsc, bsh);
-    else hipLaunchKernelGGL(gemm_tn_f32_kernel<false>, grid, dim3(256), 0, s, A, lda, Bm, ldb, Cm, ldc, M, N, K, K, bsc, bsh);
+    if (bn) hipLaunchKernelGGL(gemm_tn_f32_kernel<true>, grid, dim3(256), 0, s, A, lda, Bm, ldb, Cm, ldc, M, N, K, K, bsc, bsh, no_rows, 0);
+    else hipLaunchKernelGGL(gemm_tn_f32_kernel<false>, grid, dim3(256), 0, s, A, lda, Bm, ldb, Cm, ldc, M, N, K, K, bsc, bsh, no_rows, 0);
     TN_LAUNCH_CHECK();
   }
   const int kchunk = (((K + S - 1) / S) + 15) / 16 * 16;
   S = (K + kchunk - 1) / kchunk;
   const dim3 grid((N + 63) / 64, (M + 63) / 64, S);
-  if (bn) hipLaunchKernelGGL(gemm_tn_f32_kernel<true>, grid, dim3(256), 0, s, A, lda, Bm, ldb, workspace, N, M, N, K, kchunk, bsc, bsh);
-  else hipLaunchKernelGGL(gemm_tn_f32_kernel<false>, grid, dim3(256), 0, s, A, lda, Bm, ldb, workspace, N, M, N, K, kchunk, bsc, bsh);
+  if (bn) hipLaunchKernelGGL(gemm_tn_f32_kernel<true>, grid, dim3(256), 0, s, A, lda, Bm, ldb, workspace, N, M, N, K, kchunk, bsc, bsh, no_rows, 0);
+  else hipLaunchKernelGGL(gemm_tn_f32_kernel<false>, grid, dim3(256), 0, s, A, lda, Bm, ldb, workspace, N, M, N, K, kchunk, bsc, bsh, no_rows, 0);
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(((long)M * N + 255) / 256), dim3(256), 0, s, (const float *)workspace, S, M, N, Cm, ldc);
   TN_LAUNCH_CHECK();
 }
@@ -586,6 +613,16 @@ int launch_gemm_tn_f32(const float *A, int lda, const float *Bm, int ldb, float 
 int launch_gemm_tn_f32_bnrelu(const float *A, int lda, const float *Bm, int ldb, const float *bsc, const float *bsh, float *Cm, int ldc,
                               int M, int N, int K, hipStream_t s, float *workspace, long workspace_floats) {
   return gemm_tn_dispatch(A, lda, Bm, ldb, bsc, bsh, Cm, ldc, M, N, K, s, workspace, workspace_floats);
+}
+// C (M, N) = A^T G over K rows with G[k] = table[clamp(rows[k], 0, n_rows - 1)]: the B operand gathered from a table while it is
+// staged.  One slice (no split-K), as launch_gemm_tn_f32 without a workspace: the same k order, the same result bit for bit.
+int launch_gemm_tn_f32_rows(const float *A, int lda, const float *table, int ld, const int32_t *rows, int n_rows, float *Cm, int ldc,
+                            int M, int N, int K, hipStream_t s) {
+  TN_REQUIRE(table && rows && n_rows > 0 && ld >= N, "gemm_tn_f32_rows: needs a table of at least one row, ld >= N, and the row indices");
+  const dim3 grid((N + 63) / 64, (M + 63) / 64, 1);
+  hipLaunchKernelGGL((gemm_tn_f32_kernel<false, true>), grid, dim3(256), 0, s, A, lda, table, ld, Cm, ldc, M, N, K, K, (const float *)nullptr,
+                     (const float *)nullptr, rows, n_rows);
+  TN_LAUNCH_CHECK();
 }
 int launch_colsum_f32(const float *A, int lda, int rows, int cols, float *out, hipStream_t s) {
   hipLaunchKernelGGL(colsum_f32_kernel, dim3((cols + 63) / 64), dim3(1024), 0, s, A, lda, rows, cols, out);

@@ -372,6 +372,22 @@ class TennisSet:
                                  f"{self._samples[ids[bad[0][0]]][1]}, has no row in the feature matrix")
         return centre, lo, hi, row_stride
 
+    def window_table(self, stride=None):
+        """Every sample's window as rows of a feature TABLE: ``(frames, idx)`` - ``frames`` the sorted list of the distinct
+        ``(video, frame)`` pairs any sample's ``window_frames(sample, stride)`` reads, ``idx`` a ``(len(self), window)`` int32 array
+        with ``frames[idx[i, t]] == (sample_i.video, window_frames(sample_i, stride)[t])``.  Unlike ``window_rows`` it assumes nothing
+        about the samples: they may be thinned out (``_balance_classes``), lie in separate sections of a video, come in any order,
+        and their windows may read frames that are no sample of the split.  Needs ``window > 1``."""
+        if self._window <= 1:
+            raise ValueError(f"window_table: needs window > 1, this dataset has window = {self._window}")
+        want = [(s[0], self.window_frames(s, stride)) for s in self._samples]
+        frames = sorted({(v, f) for v, fs in want for f in fs})
+        row = {vf: r for r, vf in enumerate(frames)}
+        idx = np.empty((len(want), self._window), np.int32)
+        for i, (v, fs) in enumerate(want):
+            idx[i] = [row[(v, f)] for f in fs]
+        return frames, idx
+
     def __getitem__(self, idx):                                                        # dataset.py:184-233
         sample = self._samples[idx]
         label = self.classes.index(sample[2])

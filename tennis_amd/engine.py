@@ -488,6 +488,57 @@ class TemporalHeadTrainer(_FlatTrainer):
               "tn_head_forward_backward")
         return loss, logits
 
+    def set_features(self, table: torch.Tensor):
+        """The (rows, F) fp32 feature table the ``*_rows`` calls gather their windows from.  It has to be on the handle's GPU already
+        (uploaded once); the library borrows it, so the trainer keeps the tensor alive."""
+        _on_ctx_device(self.ctx, table, "TemporalHeadTrainer.set_features")
+        if table.dim() != 2 or table.shape[1] != self.input_size or table.shape[0] < 1 or table.dtype != torch.float32:
+            raise ValueError(f"set_features: need a (rows, {self.input_size}) float32 table, got {tuple(table.shape)} {table.dtype}")
+        table = table.contiguous()
+        check(self.lib.tn_head_set_features(self.handle, ptr(table), table.shape[0], table.stride(0)), "tn_head_set_features")
+        self._features = table
+
+    def _row_idx(self, idx, what: str) -> torch.Tensor:
+        """(B, T) window rows -> int32 on the handle's GPU.  A host-side ``idx`` (numpy array, CPU tensor, nested list) is
+        range-checked here, before any launch; a device tensor is passed through and the kernels clamp."""
+        table = getattr(self, "_features", None)
+        if table is None:
+            raise RuntimeError(f"{what}: no feature table (call set_features first)")
+        if isinstance(idx, torch.Tensor) and idx.is_cuda:
+            _on_ctx_device(self.ctx, idx, what)
+        else:
+            host = idx.numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)
+            if host.dtype.kind not in "iu":
+                raise ValueError(f"{what}: idx must hold integers, got {host.dtype}")
+            if host.size and (int(host.min()) < 0 or int(host.max()) >= table.shape[0]):
+                raise ValueError(f"{what}: idx must lie in [0, {table.shape[0] - 1}], got [{int(host.min())}, {int(host.max())}]")
+            idx = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(table.device)
+        if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
+            raise ValueError(f"{what}: idx must be (batch, steps), got {tuple(idx.shape)}")
+        return idx.to(torch.int32).contiguous()
+
+    def forward_backward_rows(self, idx, labels: torch.Tensor):
+        """``forward_backward(table[idx], labels)`` without the (B, T, F) batch: ``idx`` (B, T) names each window step's row of the
+        table given to ``set_features``; the kernels gather the rows while they stage them, in the same arithmetic order, so loss,
+        logits and gradients are bit-identical to the materialised step."""
+        idx = self._row_idx(idx, "forward_backward_rows")
+        b, t = idx.shape
+        labels = labels.to(device=idx.device, dtype=torch.int32).contiguous()
+        loss = torch.empty((b,), dtype=torch.float32, device=idx.device)
+        logits = torch.empty((b, self.classes), dtype=torch.float32, device=idx.device)
+        check(self.lib.tn_head_forward_backward_rows(self.handle, ptr(idx), ptr(labels), b, t, ptr(loss), ptr(logits)),
+              "tn_head_forward_backward_rows")
+        return loss, logits
+
+    def predict_rows(self, idx) -> torch.Tensor:
+        """The forward half of ``forward_backward_rows``: (B, classes) logits of the current parameters; gradients, momentum and
+        parameters are untouched."""
+        idx = self._row_idx(idx, "predict_rows")
+        b, t = idx.shape
+        logits = torch.empty((b, self.classes), dtype=torch.float32, device=idx.device)
+        check(self.lib.tn_head_forward_rows(self.handle, ptr(idx), b, t, ptr(logits)), "tn_head_forward_rows")
+        return logits
+
     def step(self, batch_size: int, lr: float, momentum: float = 0.9, wd: float = 1e-4):
         check(self.lib.tn_head_sgd_step(self.handle, lr, momentum, wd, 1.0 / batch_size), "tn_head_sgd_step")
 

@@ -96,13 +96,15 @@ def is_main_rank() -> bool:
 
 def train_model(head: TemporalHeadTrainer, train_batches, metrics, trainer: Trainer, epochs: int, batch_size: int,
                 lr_steps=(10, 20), lr_factor: float = 0.75, start_epoch: int = 0, val_fn=None, save_dir: str | None = None,
-                log=print, model=None, score_key: str = "AVG_NB_f1"):
+                log=print, model=None, score_key: str = "AVG_NB_f1", step_fn=None):
     """reference train.py:388-499 with the model call, loss and backward fused into ``head.forward_backward``.
     ``train_batches``: callable -> iterable of (features (B,T,F) tensor, labels (B,) tensor) per epoch.
     Per epoch (rank 0 only): the validation ``AVG_NB_f1`` is appended to ``<save_dir>/scores.txt`` (:487-489) and the
     parameters go to ``<save_dir>/NNNN.params`` (:497) — through ``model.save_parameters`` (the MXNet container with
     Gluon's structural names, what the reference's ``load_parameters`` reads) when the mirror ``model`` is given,
-    else an ``.npz`` of the trainer's prefixed names under ``NNNN.npz``."""
+    else an ``.npz`` of the trainer's prefixed names under ``NNNN.npz``.  ``step_fn``: what a step calls instead of
+    ``head.forward_backward`` (``--dense_windows``: ``head.forward_backward_rows`` on (window rows (B,T), labels) batches)."""
+    step_fn = step_fn or head.forward_backward
     lr_counter = 0
     lr_steps = list(lr_steps) + [1 << 30]
     history = []
@@ -118,7 +120,7 @@ def train_model(head: TemporalHeadTrainer, train_batches, metrics, trainer: Trai
             m.reset()
         train_sum_loss, nb = 0.0, 0
         for x, y in train_batches():
-            loss, logits = head.forward_backward(x, y)                      # :415-421
+            loss, logits = step_fn(x, y)                                    # :415-421
             trainer.step(batch_size)                                        # :424
             train_sum_loss += float(loss.mean())                            # :427
             nb += 1
@@ -161,6 +163,65 @@ def check_frames_route(flags):
                          "(--feats_model after evaluate --save_feats) or under a temporal head (--window > 1 --temp_pool gru|lstm)")
 
 
+def check_dense_windows(flags):
+    """``--dense_windows`` trains the temporal head from a device-resident feature table: it needs stored features, a window and a
+    head with parameters.  Anything else exits with the reason."""
+    if not getattr(flags, "dense_windows", False):
+        return
+    if flags.feats_model is None:
+        raise SystemExit("--dense_windows gathers windows from a table of stored features and needs --feats_model "
+                         "(after evaluate --save_feats); on frames the backbone runs in every step")
+    if flags.window <= 1:
+        raise SystemExit("--dense_windows needs --window > 1: with --window 1 there is no window to gather")
+    if flags.temp_pool not in ("gru", "lstm"):
+        raise SystemExit("--dense_windows needs --temp_pool gru|lstm: mean / max have no parameters to train")
+
+
+class DeviceWindows:
+    """One split for ``--dense_windows``: its feature table (``TennisSet.window_table`` / ``evaluate.load_feature_table``: every
+    ``.npy`` read once), every sample's window rows ``idx`` (N, window) int32 and the labels, each uploaded once."""
+
+    def __init__(self, dataset, feat_dim: int, device, split: str, log=print):
+        import time
+        from .evaluate import load_feature_table
+        frames, idx = dataset.window_table()
+        need = len(frames) * feat_dim * 4
+        free = int(torch.cuda.mem_get_info(device)[0])
+        if need > free:
+            raise SystemExit(f"--dense_windows: the {split} split's feature table ({len(frames)} frames x {feat_dim} floats) needs "
+                             f"{need} bytes and the device has {free} bytes free; train without --dense_windows, or thin the "
+                             "split out with --every")
+        t0 = time.perf_counter()
+        table = load_feature_table(dataset, frames)
+        self.table = torch.from_numpy(table).to(device)
+        self.idx = torch.from_numpy(idx).to(device)
+        labels = np.array([dataset.classes.index(s[2]) for s in dataset._samples])
+        self.labels = torch.from_numpy(labels.astype(np.int32)).to(device)
+        self.load_seconds = time.perf_counter() - t0
+        log("[dense_windows] {} split: {} samples, table of {} frames ({} bytes) loaded in {:.2f} s".format(
+            split, len(dataset), len(frames), need, self.load_seconds))
+
+    def epoch_batches(self, loader, local_bs_of, max_batches: int = -1):
+        """The epoch's batches from ``loader._batches()`` - the stream the loader route draws from, so the same seed gives the same
+        order - as (window rows (b, window), labels (b,)) device slices.  ``local_bs_of(ids)``: the rows of a batch this rank trains on
+        (None: the batch is dropped).  The epoch's sample order goes to the device in one copy; a step then only slices."""
+        chosen = []
+        for i, ids in enumerate(loader._batches()):
+            if max_batches > 0 and i > max_batches:                         # train.py:405
+                break
+            ids = local_bs_of(ids)
+            if ids is not None and len(ids):
+                chosen.append(np.asarray(ids, np.int64))
+        if not chosen:
+            return
+        order = torch.from_numpy(np.concatenate(chosen)).to(self.idx.device)
+        rows, labels = self.idx[order], self.labels[order]                 # one gather per epoch
+        a = 0
+        for ids in chosen:
+            yield rows[a:a + len(ids)], labels[a:a + len(ids)]
+            a += len(ids)
+
+
 def build_parser():
     import argparse
     p = argparse.ArgumentParser(description="tennis_amd train (flags of reference train.py:30-95)")
@@ -184,6 +245,10 @@ def build_parser():
     p.add_argument("--momentum", type=float, default=0.9)
     p.add_argument("--wd", type=float, default=0.0001)
     p.add_argument("--feats_model", default=None)
+    p.add_argument("--dense_windows", action="store_true",
+                   help="with --feats_model --window W --temp_pool gru|lstm: every split's features go to the device once as a table "
+                        "and the training kernels gather each step's windows from it - no per-step file reads, stacking or "
+                        "host-to-device copies; bit-identical parameters (not a reference flag)")
     p.add_argument("--matmul", default="f32", choices=["f32", "fp32x3"],
                    help="matrix pipe of the backbone's GEMMs when training on frames: f32 (exact-f32 MFMA) or fp32x3 (fp32 values as "
                         "three bf16 terms on the bf16 MFMA, same float64 bars; not a reference flag)")
@@ -225,6 +290,7 @@ def main(argv=None):
     if flags.flow or flags.vis:
         raise NotImplementedError("--flow / --vis: optical-flow input and visualisation are outside the accelerated path (SURVEY 2a)")
     check_frames_route(flags)
+    check_dense_windows(flags)
     if flags.num_workers < 0:                          # the reference's -1 = cpu_count() (train.py:101-102)
         flags.num_workers = 3                                               # (files -> features peaks at three decoder threads: scripts/bench_pipeline.py, profiles/r05_c_*)
     every = [int(s) for s in flags.every.split(",")]
@@ -327,8 +393,34 @@ def main(argv=None):
         evaluate_model(model, val_data, val_set, vm)
         return dict(vm[0].get())
 
+    step_fn = None
+    if flags.dense_windows:
+        log = print if is_main_rank() else (lambda *a: None)
+        train_win = DeviceWindows(train_set, feat_dim, dev, "train", log)
+        val_win = DeviceWindows(val_set, feat_dim, dev, "val", log)
+
+        def my_rows(ids):           # the rows rank::world of a batch, as batches() slices them
+            if world > 1:
+                return None if len(ids) % world else ids[rank::world]
+            return ids
+
+        def batches():
+            head.set_features(train_win.table)
+            yield from train_win.epoch_batches(train_data, my_rows, flags.max_batches)
+
+        def validate(h):            # predict_rows over the val split's table, PRF1 fed as evaluate_model feeds it
+            h.set_features(val_win.table)
+            vm = [PRF1(label_names=val_set.classes)]
+            lab = val_win.labels.to(torch.float32)
+            for a in range(0, len(val_set), local_bs):
+                vm[0].update([lab[a:a + local_bs]], [h.predict_rows(val_win.idx[a:a + local_bs])])
+            return dict(vm[0].get())
+
+        step_fn = head.forward_backward_rows
+
     hist = train_model(head, batches, metrics, trainer, flags.epochs, flags.batch_size, lr_steps=lr_steps,
-                       lr_factor=flags.lr_factor, start_epoch=start_epoch, val_fn=validate, save_dir=save_dir, model=model)
+                       lr_factor=flags.lr_factor, start_epoch=start_epoch, val_fn=validate, save_dir=save_dir, model=model,
+                       step_fn=step_fn)
     if hist and is_main_rank():
         best = max(hist, key=lambda r: r["val"].get("AVG_NB_f1", 0.0))
         print("[Finished] best epoch {} val AVG_NB_f1={:.3f}".format(best["epoch"], best["val"].get("AVG_NB_f1", 0.0)))
