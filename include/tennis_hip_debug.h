@@ -50,8 +50,22 @@ int tn_dbg_pack_conv3x3(const float *w_host, uint16_t *out_host);
 int tn_dbg_conv1x1_dev(tn_ctx *ctx, const void *x_f16, int ldx, int K, const float *scale, const float *shift,
                        const void *w_f16, int N, void *y_f16, int ldy, int yoff, int M, int pool, int H, int W,
                        int variant);
+/* variant: the low 16 bits the kernel choice (9: weights fetched inside the loop); bit 17: exact weights, wp_f16 = the hi image
+ * followed by the lo image (two tn_dbg_pack_conv3x3 images). */
 int tn_dbg_conv3x3_dev(tn_ctx *ctx, const void *x_f16, const float *scale, const float *shift,
                        const void *wp_f16, void *y_f16, int ldy, int yoff, int B, int H, int W, int variant);
+/* tn_dbg_conv1x1_dev with the remaining arguments of the launcher (csrc/conv1x1.hip, csrc/trans_ws.hip): bias (device fp32 [N],
+ * added before the rounding; or NULL), clamp (scale / shift hold lo / hi and the operand is clamp(x, lo, hi)), y32 (device fp32
+ * [M][ld32], the un-rounded result once more; or NULL) and wfrag (device: the caller's MFMA-order image of w, which sends a
+ * supported transition to the warp-specialised kernel; or NULL).  variant bit 17: w is [N][2 Kp] = [hi | lo].  Asynchronous.
+ * Refuses y32 with ld32 < N and wfrag with a geometry the warp-specialised kernel does not support. */
+int tn_dbg_conv1x1_ex(tn_ctx *ctx, const void *x_f16, int ldx, int K, const float *scale, const float *shift, const void *w_f16, int N,
+                      void *y_f16, int ldy, int yoff, int M, int pool, int H, int W, int variant, const float *bias, int clamp,
+                      float *y32, int ld32, const void *wfrag);
+/* w [N][K] fp16 -> the fragment image the warp-specialised transition reads, [K / 16][N / 32][64 lanes][8] (lane l: row l & 31,
+ * k offset 8 (l >> 5)): the host function tn_densenet121_create packs with (touches no device), and the device kernel. */
+int tn_dbg_pack_trans_frags(const uint16_t *w_f16_host, int N, int K, uint16_t *out_host);
+int tn_dbg_pack_trans_frags_dev(tn_ctx *ctx, const void *w_f16, int N, int K, void *out_f16);
 int tn_dbg_dense_layer_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K, const float *s1, const float *t1,
                            const void *w1_f16, const float *s2, const float *t2, const void *w3p_f16, int B,
                            int H, int W, unsigned long long *ts /* NULL or stamps */, int variant /* 0 auto, 1 big, 2 small */);

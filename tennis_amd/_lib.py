@@ -168,6 +168,10 @@ _SIGS = {
     "tn_dbg_conv1x1_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_conv3x3_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tn_dbg_conv1x1_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P]),
+    "tn_dbg_pack_trans_frags": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "tn_dbg_pack_trans_frags_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "tn_dbg_dense_layer_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int,
                                          _P, C.c_int]),
     "tn_dbg_dense_chain_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -62,12 +62,53 @@ extern "C" int tn_dbg_conv1x1_dev(tn_ctx *ctx, const void *x_f16, int ldx, int K
   return launch_conv1x1(a, ctx->stream);
 }
 
+// tn_dbg_conv1x1_dev with every argument of Conv1x1Args a test has to reach: bias (device fp32 [N], or NULL), clamp (scale / shift hold
+// lo / hi), y32 / ld32 (the fp32 side output, or NULL) and wfrag - the CALLER's fragment image of w (device; what pack_trans_frags made
+// of it on the host, as tn_densenet121_create does, or launch_pack_trans_frags on the device), or NULL.  variant: bit 17 exact weights.
+// Asynchronous.
+extern "C" int tn_dbg_conv1x1_ex(tn_ctx *ctx, const void *x_f16, int ldx, int K, const float *scale, const float *shift, const void *w_f16,
+                                 int N, void *y_f16, int ldy, int yoff, int M, int pool, int H, int W, int variant, const float *bias,
+                                 int clamp, float *y32, int ld32, const void *wfrag) {
+  TN_REQUIRE(ctx && x_f16 && y_f16 && scale && shift && w_f16, "tn_dbg_conv1x1_ex: null argument");
+  TN_REQUIRE(M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= yoff + N && yoff >= 0, "tn_dbg_conv1x1_ex: bad shape (M, K, N positive, ldx >= K, ldy >= yoff + N)");
+  TN_REQUIRE(!pool || (H >= 2 && W >= 2 && M % ((H / 2) * (W / 2)) == 0), "tn_dbg_conv1x1_ex: pooling needs H, W >= 2 and M = B (H / 2) (W / 2)");
+  TN_REQUIRE(!y32 || (ld32 >= N && ld32 % 4 == 0 && ((uintptr_t)y32 & 15) == 0), "tn_dbg_conv1x1_ex: y32 needs ld32 >= N, a multiple of 4, and 16-byte alignment");
+  Conv1x1Args a{(const f16 *)x_f16, ldx, K, scale, shift, (const f16 *)w_f16, N, (f16 *)y_f16, ldy, yoff, M, pool, H, W};
+  a.variant = variant & 0xffff;
+  a.exact = (variant >> 17) & 1;
+  a.bias = bias;
+  a.clamp = clamp != 0;
+  a.y32 = y32;
+  a.ld32 = ld32;
+  a.wfrag = (const f16 *)wfrag;
+  TN_REQUIRE(!wfrag || trans_ws_supported(a), "tn_dbg_conv1x1_ex: wfrag with a geometry trans_ws does not support (pooling, fp16 weights, no bias, N = 512 | 256, K % 128 == 0, even H and W)");
+  TN_ON_DEVICE(ctx->device);
+  return launch_conv1x1(a, ctx->stream);
+}
+
+// The two forms of the warp-specialised transition's weight packer: the host function tn_densenet121_create calls (no device is
+// touched) and the device kernel; w [N][K] fp16 -> [K / 16][N / 32][64 lanes][8], N K halves
+extern "C" int tn_dbg_pack_trans_frags(const uint16_t *w_f16_host, int N, int K, uint16_t *out_host) {
+  TN_REQUIRE(w_f16_host && out_host, "tn_dbg_pack_trans_frags: null argument");
+  TN_REQUIRE(N > 0 && K > 0 && N % 32 == 0 && K % 16 == 0, "tn_dbg_pack_trans_frags: N % 32 or K % 16");
+  const std::vector<f16> p = pack_trans_frags((const f16 *)w_f16_host, N, K);
+  memcpy(out_host, p.data(), p.size() * sizeof(f16));
+  return TN_OK;
+}
+extern "C" int tn_dbg_pack_trans_frags_dev(tn_ctx *ctx, const void *w_f16, int N, int K, void *out_f16) {
+  TN_REQUIRE(ctx && w_f16 && out_f16, "tn_dbg_pack_trans_frags_dev: null argument");
+  TN_REQUIRE(N > 0 && K > 0, "tn_dbg_pack_trans_frags_dev: N and K must be positive");
+  TN_ON_DEVICE(ctx->device);
+  return launch_pack_trans_frags((const f16 *)w_f16, N, K, (f16 *)out_f16, ctx->stream);
+}
+
 extern "C" int tn_dbg_conv3x3_dev(tn_ctx *ctx, const void *x_f16, const float *scale, const float *shift,
                                   const void *wp_f16, void *y_f16, int ldy, int yoff, int B, int H, int W,
                                   int variant) {
   TN_REQUIRE(ctx && x_f16 && y_f16 && scale && shift && wp_f16, "tn_dbg_conv3x3_dev: null argument");
   Conv3x3Args a{(const f16 *)x_f16, scale, shift, (const f16 *)wp_f16, (f16 *)y_f16, ldy, yoff, B * H * W, H, W};
-  a.variant = variant;
+  a.variant = variant & 0xffff;
+  a.exact = (variant >> 17) & 1;      // bit 17: wp is the hi image (both MFMA layouts, tn_dbg_pack_conv3x3) followed by the lo image
   return launch_conv3x3(a, ctx->stream);
 }
 

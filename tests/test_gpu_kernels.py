@@ -79,6 +79,9 @@ def test_conv1x1(ctx, report, M, K, ldx, N, yoff, ldy):
 
 @pytest.mark.parametrize("B,H,W,K,N", [(2, 28, 28, 512, 256), (3, 14, 14, 1024, 512), (1, 56, 56, 256, 128)])
 def test_conv1x1_pool(ctx, report, B, H, W, K, N):
+    """The transition kernel against the mean of the four BN + ReLU'd pixels as the kernel defines it since round 5: NOT rounded to
+    fp16 (the kernel multiplies hi + lo of it).  A loose max-abs check; tests/test_gpu_layerwise_instantiations.py holds every
+    instantiation to the float64 reference and sees the lo half."""
     from tennis_amd import _lib
     rng = np.random.default_rng(B * H + K)
     x = rng.normal(0, 1.5, (B, H, W, K)).astype(np.float16)
@@ -94,7 +97,7 @@ def test_conv1x1_pool(ctx, report, B, H, W, K, N):
                                       ldy, 0, Mo, 1, H, W), "dbg_conv1x1 pool")
     y = yd.cpu().numpy().astype(np.float32)[:, :N]
     a = np.maximum(x.astype(np.float32) * s + t, 0.0)
-    a = _h(dn.avgpool(a, 2))
+    a = dn.avgpool(a, 2)                                  # un-rounded: the operand is hi + lo
     ref = (a.reshape(-1, K) @ _h(w).T)
     err = np.abs(y - ref).max()
     report[f"conv1x1_pool_{B}x{H}x{W}x{K}"] = float(err)
@@ -310,7 +313,8 @@ def test_dense_layer_exact_weights(ctx, report, B, H, K, ldc):
 
 @pytest.mark.parametrize("B,H,K,N", [(2, 56, 256, 128), (2, 28, 512, 256), (3, 14, 1024, 512)])
 def test_transition_exact_weights(ctx, report, B, H, K, N):
-    """TN_ENC_EXACT_WEIGHTS in the transition kernel (BN+ReLU, 2x2 average, 1x1 conv over [hi | lo] weights)."""
+    """TN_ENC_EXACT_WEIGHTS in the transition kernel (BN+ReLU, 2x2 average kept as hi + lo - the reference does not round it -, 1x1 conv
+    over [hi | lo] weights)."""
     from tennis_amd import _lib
     rng = np.random.default_rng(H + K)
     M = B * H * H
@@ -324,7 +328,7 @@ def test_transition_exact_weights(ctx, report, B, H, K, N):
     _lib.check(ctx.lib.tn_dbg_conv1x1_dev(ctx.handle, _lib.ptr(d["x"]), K, K, _lib.ptr(d["sc"]), _lib.ptr(d["sh"]), _lib.ptr(d["w"]), N,
                                           _lib.ptr(y), N, 0, Mo, 1, H, H, 1 << 17), "conv1x1")
     a = np.maximum(x.astype(np.float32) * sc + sh, 0).reshape(B, H // 2, 2, H // 2, 2, K).mean(axis=(2, 4))
-    a = _h(a).reshape(Mo, K)
+    a = a.reshape(Mo, K)                                  # un-rounded: the operand is hi + lo
     ref = a.astype(np.float64) @ w.astype(np.float64).T
     got = y.cpu().numpy().astype(np.float64)
     err = np.abs(got - ref).max()
