@@ -391,6 +391,19 @@ int tn_gnmt_trainer_create_ex(tn_ctx *ctx, const tn_param *params, int n_params,
 int tn_gnmt_trainer_forward_backward(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len,
                                      const int32_t *tgt, int ld, const int32_t *tgt_valid_len, int batch, int steps,
                                      int tgt_len, float *loss, float *logits_out);
+/* The same step from a device-resident feature table.  Replaces what feeds the step in the reference's feature mode: TennisSet.
+ * __getitem__ opening one .npy per frame of every point of the batch (dataset.py:161-178), the batchify function stacking them into a
+ * zero-padded (B, T, F) array and the per-batch copy to the device in front of the step (train_gnmt.py:318-337).  The table (n_rows,
+ * input_size) fp32 DEVICE of row stride ld >= input_size floats is uploaded once by the caller and only read here: the call keeps no
+ * pointer to it.  row_idx (batch * steps) int32 DEVICE in order b * steps + t names each step's row; a NEGATIVE index is a pad step
+ * (behind a clip shorter than the batch's longest) and stands for a row of zeros, an index >= n_rows is clamped to n_rows - 1, so no
+ * content of the array reads outside the table.  The two kernels that read src - encoder layer 0's i2h product and dW_ih = dGI^T src -
+ * gather the rows while they stage them, in the arithmetic order of the materialised step: loss, logits and gradients are
+ * bit-identical to tn_gnmt_trainer_forward_backward on the zero-padded batch.  Everything else as that call; n_rows < 1, ld <
+ * input_size and null arguments are TN_ERR_INVALID.  No call allocates. */
+int tn_gnmt_trainer_forward_backward_rows(tn_gnmt_trainer *t, const float *table, int n_rows, int ld, const int32_t *row_idx,
+                                          const int32_t *src_valid_len, const int32_t *tgt, int ld_tgt, const int32_t *tgt_valid_len,
+                                          int batch, int steps, int tgt_len, float *loss, float *logits_out);
 int tn_gnmt_trainer_buffers(tn_gnmt_trainer *t, float **params_dev, float **grads_dev, int64_t *numel);
 /* --dropout of train_gnmt.py (gnmt.py:152,395: after each encoder layer and on the top decoder cell's output), inverted
  * dropout from a counter-based generator; 0 until set.  tn_gnmt_trainer_dropout_masks: the last step's masks (test hook). */
@@ -508,6 +521,14 @@ int tn_gnmt_create_ex(tn_ctx *ctx, const tn_param *params, int n_params, const c
                       int input_size, int hidden, int embed, int vocab, int num_layers, int num_bi_layers,
                       int max_batch, int max_src_len, int beam, int max_length, int flags, tn_gnmt **out);
 int tn_gnmt_encode(tn_gnmt *g, const float *src, const int32_t *valid_len, int batch, int steps, float *mem_out);
+/* tn_gnmt_encode from a device-resident feature table: what evaluate() (train_gnmt.py:264-302) and evaluate_gnmt.py feed model.encode
+ * with, minus the loader - one .npy per frame of every point (dataset.py:161-178), the padded (B, T, F) batch and its copy, for every
+ * batch of every validation and test pass.  table, n_rows, ld and row_idx (batch * steps, negative = a pad step = zeros, >= n_rows
+ * clamped) as in tn_gnmt_trainer_forward_backward_rows; encoder layer 0's i2h product gathers the rows, and mem, the states and the
+ * key projection are bit-identical to tn_gnmt_encode on the zero-padded batch.  tn_gnmt_decode_seq / tn_gnmt_beam_search follow it
+ * as they follow tn_gnmt_encode. */
+int tn_gnmt_encode_rows(tn_gnmt *g, const float *table, int n_rows, int ld, const int32_t *row_idx, const int32_t *valid_len, int batch,
+                        int steps, float *mem_out);
 int tn_gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, float K, int max_length, int32_t *samples,
                         float *scores, int32_t *valid_length, int *length_host);
 /* Teacher forcing: model(src, tgt[:, :-1], ...) of evaluate() (train_gnmt.py:280) ->

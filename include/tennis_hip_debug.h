@@ -161,6 +161,10 @@ int tn_dbg_bn_train(tn_ctx *ctx, const float *x, int ld, int64_t M, int C, const
 int tn_dbg_gnmt_trainer_src_grad(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len, const int32_t *tgt, int ld,
                                  const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out,
                                  float *dsrc, int ldd);
+/* The gathered i2h product of tn_gnmt_trainer_forward_backward_rows / tn_gnmt_encode_rows skips the k-loop of a workgroup whose rows
+ * are all padding.  on = 0 launches the instantiation compiled without that skip (same results), so that the skip can be measured
+ * against it; on = 1 (the default) restores it.  Process-wide. */
+int tn_dbg_rows_pad_skip(int on);
 
 /* Which instantiation the recurrent kernels run for a shape (csrc/rnn.h rnn_route, the one policy of launch_rnn_recurrent and of the
  * BPTT launchers of csrc/train.hip): gates 3 GRU / 4 LSTM, B batch rows, H hidden, dirs 1 | 2.  *nb rows per workgroup (1 | 4), *kr the

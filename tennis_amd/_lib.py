@@ -138,6 +138,7 @@ _SIGS = {
     "tn_gnmt_frames_trainer_adam_step": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float]),
     "tn_gnmt_frames_trainer_read_param": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
     "tn_gnmt_frames_trainer_destroy": (C.c_int, [_P]),
+    "tn_dbg_rows_pad_skip": (C.c_int, [C.c_int]),
     "tn_dbg_gnmt_trainer_src_grad": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int]),
     "tn_gnmt_trainer_create": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -145,6 +146,7 @@ _SIGS = {
                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tn_gnmt_trainer_dropout_mask": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "tn_gnmt_trainer_forward_backward": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tn_gnmt_trainer_forward_backward_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "tn_gnmt_trainer_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
     "tn_gnmt_trainer_set_dropout": (C.c_int, [_P, C.c_float, C.c_uint64]),
     "tn_gnmt_trainer_dropout_masks": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
@@ -156,6 +158,7 @@ _SIGS = {
     "tn_gnmt_create_ex": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tn_gnmt_encode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "tn_gnmt_encode_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "tn_gnmt_beam_search": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P, _P,
                                       C.POINTER(C.c_int)]),
     "tn_gnmt_decode_seq": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),

@@ -119,6 +119,50 @@ class CaptionSet:
         return [len(range(int(self._points[s][1]), int(self._points[s][2]), self._every)) for s in self._samples]
 
 
+    def clip_frames(self, idx):
+        """the (video, frame) pairs item ``idx`` stacks, in order (``every`` honoured) - ``__getitem__``'s own selection"""
+        point = self._points[self._samples[idx]]
+        return [(point[0], f) for f in range(int(point[1]), int(point[2]), self._every)]
+
+    def clip_table(self):
+        """-> (frames, idx, lens): the split as rows of one feature table, for training and evaluating from a device-resident table
+        instead of the loader.  ``frames``: the sorted distinct (video, frame) pairs any point reads; ``idx`` (len(self), max clip
+        length) int32: item i's step t is table row ``idx[i, t]``, -1 past the clip's length; ``lens`` = ``get_clip_lens()``.  Points may
+        overlap, repeat or come in any order: a frame two points share is one row."""
+        if self._frames is not None:
+            raise ValueError("clip_table: the feature table serves feature mode; this set reads frames")
+        clips = [self.clip_frames(i) for i in range(len(self))]
+        frames = sorted({vf for c in clips for vf in c})
+        row = {vf: r for r, vf in enumerate(frames)}
+        lens = [len(c) for c in clips]
+        idx = np.full((len(clips), max(lens, default=0)), -1, np.int32)
+        for i, c in enumerate(clips):
+            idx[i, :len(c)] = [row[vf] for vf in c]
+        return frames, idx, lens
+
+
+def load_clip_table(dataset, frames):
+    """The (len(frames), F) float32 feature table of ``CaptionSet.clip_table``: row r is the feature of ``frames[r]`` = (video, frame)
+    through the dataset's own ``_feature`` - the ``.npy`` under its feature directory, each read exactly once (the loader reads it once
+    per point that holds it, every epoch), or the synthetic source's vector."""
+    if not len(frames):
+        raise ValueError("load_clip_table: no frames")
+    from .evaluate import read_rows
+    return read_rows(lambda r: dataset._feature(frames[r][0], frames[r][1]), len(frames))
+
+
+def upload_clip_table(dataset):
+    """-> (table on the GPU, idx): one split's features uploaded once (``--feats_on_device``).  Every rank of a data-parallel run holds
+    the whole table; one that does not fit raises with its size - the loader route remains the answer there."""
+    frames, idx, _ = dataset.clip_table()
+    host = load_clip_table(dataset, frames)
+    try:
+        return torch.from_numpy(host).cuda(), idx
+    except RuntimeError as e:           # torch.cuda.OutOfMemoryError is one
+        raise RuntimeError("feats_on_device: the {} x {} float32 feature table ({:.1f} MiB) does not fit on the GPU; train without "
+                           "the flag (the loader route)".format(host.shape[0], host.shape[1], host.nbytes / 2 ** 20)) from e
+
+
 def pad_batchify(samples):
     """``btf.Tuple(Pad(), Pad(), Stack('float32'), Stack('float32')[, Stack()])`` (utils/captioning.py:33-37)."""
     tmax = max(s[0].shape[0] for s in samples)
@@ -134,14 +178,16 @@ def pad_batchify(samples):
     return tuple(out)
 
 
-def bucketed_batches(dataset, batch_size, num_buckets=5, shuffle=False, seed=0, epoch=0, rank=0, world=1):
+def bucketed_batches(dataset, batch_size, num_buckets=5, shuffle=False, seed=0, epoch=0, rank=0, world=1, rows=None):
     """Stand-in for ``FixedBucketSampler(lengths, batch_size, num_buckets, shuffle)`` with constant-width buckets:
     samples are grouped by target length so padding stays small; instance ids travel with the batch, evaluate()
     restores the dataset order.  ``shuffle=False`` is the reference's validation / test sampler
     (utils/captioning.py:62-86); ``shuffle=True`` its TRAINING sampler (:48-55): the samples of a bucket are permuted
     before they are cut into batches and the batches are visited in random order, afresh every epoch
     (``default_rng(seed + epoch)``).  ``rank`` / ``world``: a data-parallel rank takes batches rank::world of that
-    (identically seeded) list, padded by wrapping so that every rank runs the same number of steps."""
+    (identically seeded) list, padded by wrapping so that every rank runs the same number of steps.
+    ``rows``: ``CaptionSet.clip_table()``'s idx - the same batches, targets and lengths, but the source element is the batch's
+    (B, longest clip of the batch) int32 table rows (-1 = padding) instead of the stacked features; no item is read, no file opened."""
     lens = [l[-1] for l in dataset.get_data_lens()]
     lo, hi = min(lens), max(lens)
     width = max(1, math.ceil((hi - lo + 1) / num_buckets))
@@ -160,6 +206,17 @@ def bucketed_batches(dataset, batch_size, num_buckets=5, shuffle=False, seed=0, 
     if world > 1:
         n = -(-len(batches) // world) * world
         batches = [batches[j % len(batches)] for j in range(n)][rank::world]
+    if rows is not None:
+        caps, clens = dataset.get_captions(ids=True), dataset.get_clip_lens()
+        for ids in batches:
+            tmax, lmax = max(clens[i] for i in ids), max(len(caps[i]) for i in ids)
+            tgt = np.zeros((len(ids), lmax), np.int32)
+            for j, i in enumerate(ids):
+                tgt[j, :len(caps[i])] = caps[i]
+            batch = (np.ascontiguousarray(rows[ids, :tmax], dtype=np.int32), tgt, np.array([clens[i] for i in ids], np.float32),
+                     np.array([len(caps[i]) for i in ids], np.float32))
+            yield batch + (np.array(ids, np.int64),) if dataset._inference else batch
+        return
     tf = getattr(dataset, "_transform", None)
     for ids in batches:
         batch = pad_batchify([dataset[i] for i in ids])
@@ -179,26 +236,35 @@ def write_sentences(sentences, file_path):                             # utils/c
             of.write((u" ".join(sent) if isinstance(sent, (list, tuple)) else sent) + u"\n")
 
 
-def evaluate(data_loader, model, translator, data_train):
+def evaluate(data_loader, model, translator, data_train, table=None):
     """reference train_gnmt.py:264-302: teacher-forced MaskedSoftmaxCELoss + beam search; returns
-    (avg_loss, translations ordered by instance id).  Everything numeric runs on the GPU."""
+    (avg_loss, translations ordered by instance id).  Everything numeric runs on the GPU.
+    ``table``: the split's device-resident feature table; a loader that yields table rows (``bucketed_batches(rows=...)``: an int32
+    (B, T) source) is then encoded by ``encode_rows`` / ``translate_rows``, with the same results."""
     from .engine import masked_softmax_ce
     translation_out, all_inst_ids = [], []
     avg_loss_denom, avg_loss = 0, 0.0
     for src_seq, tgt_seq, src_valid_length, tgt_valid_length, inst_ids in data_loader:
-        src = model.embed_source(to_device(src_seq))                   # frame mode: the clip's frames through the CNN
+        by_rows = isinstance(src_seq, np.ndarray) and src_seq.ndim == 2 and src_seq.dtype.kind == "i"
+        if by_rows and table is None:
+            raise ValueError("evaluate: the loader yields table rows but no feature table was given")
+        src = src_seq if by_rows else model.embed_source(to_device(src_seq))    # frame mode: the clip's frames through the CNN
         tgt = torch.from_numpy(tgt_seq).cuda()
         svl = torch.from_numpy(src_valid_length).cuda()
         tvl = torch.from_numpy(tgt_valid_length).cuda()
         b, t = src.shape[0], src.shape[1]
         cap = model._captioner(translator._beam_size, translator._max_length, b, t)
-        cap.encode(src, svl)
+        if by_rows:
+            cap.encode_rows(table, src, src_valid_length)
+        else:
+            cap.encode(src, svl)
         out = cap.decode_seq(tgt[:, :-1])                              # model(src, tgt[:, :-1], ...)   :280
         loss = masked_softmax_ce(out, tgt[:, 1:], tvl - 1).mean().item()   # :281
         all_inst_ids.extend(inst_ids.astype(np.int32).tolist())
         avg_loss += loss * (tgt_seq.shape[1] - 1)
         avg_loss_denom += (tgt_seq.shape[1] - 1)
-        samples, _, sample_valid_length = translator.translate(src, svl)   # :287-288
+        samples, _, sample_valid_length = (translator.translate_rows(table, src, src_valid_length) if by_rows
+                                           else translator.translate(src, svl))   # :287-288
         max_score_sample = samples[:, 0, :].cpu().numpy()
         svl0 = sample_valid_length[:, 0].cpu().numpy()
         for i in range(max_score_sample.shape[0]):                     # :291-294

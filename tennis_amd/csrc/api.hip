@@ -152,6 +152,22 @@ extern "C" int tn_birnn_forward(tn_birnn *r, const float *x, int batch, int step
   return launch_rnn_recurrent(r->gates, r->gi, N, r->whT, r->bh, valid_len, seq, r->dirs * r->H, h_last, c_last,
                               batch, steps, r->H, r->dirs, s);
 }
+// tn_birnn_forward with x never materialised: row b * steps + t of x is row row_idx[b * steps + t] of table (n_rows, F; row stride
+// ld), zeros where the index is negative; the i2h product gathers the rows while it stages them (api_internal.h).
+int birnn_forward_rows(tn_birnn *r, const float *table, int n_rows, int ld, const int32_t *row_idx, int batch, int steps,
+                       const int32_t *valid_len, float *seq, float *h_last, float *c_last) {
+  TN_REQUIRE(r && table && row_idx && seq, "birnn_forward_rows: null argument");
+  TN_REQUIRE(n_rows >= 1 && ld >= r->F, "birnn_forward_rows: needs n_rows >= 1 and ld >= input_size");
+  TN_REQUIRE(batch > 0 && steps > 0 && (long)batch * steps <= r->max_rows, "birnn_forward_rows: B*T exceeds max_rows");
+  TN_ON_DEVICE(r->ctx->device);
+  hipStream_t s = r->ctx->stream;
+  const int GH = r->gates * r->H, N = r->dirs * GH, rows = batch * steps;
+  int rc = launch_linear_f32_padrows(table, ld, row_idx, n_rows, r->wi, r->F, r->bi, r->gi, N, rows, N, r->F, 0, s);
+  if (rc) return rc;
+  if (valid_len) TN_HIP_CHECK(hipMemsetAsync(seq, 0, (size_t)rows * r->dirs * r->H * sizeof(float), s));
+  return launch_rnn_recurrent(r->gates, r->gi, N, r->whT, r->bh, valid_len, seq, r->dirs * r->H, h_last, c_last,
+                              batch, steps, r->H, r->dirs, s);
+}
 extern "C" int tn_birnn_destroy(tn_birnn *r) {
   if (!r) return TN_OK;
   TnDeviceGuard tn_dg_(r->ctx->device);

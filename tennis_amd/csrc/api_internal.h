@@ -39,6 +39,11 @@ struct DevPool {  // owns device allocations of one handle
   }
 };
 
+// tn_birnn_forward (api.hip) with its input never materialised: row b * steps + t of x is row row_idx[b * steps + t] of table (n_rows,
+// input_size; row stride ld, DEVICE), a row of zeros where the index is negative; what tn_gnmt_encode_rows runs for encoder layer 0.
+int birnn_forward_rows(tn_birnn *r, const float *table, int n_rows, int ld, const int32_t *row_idx, int batch, int steps,
+                       const int32_t *valid_len, float *seq, float *h_last, float *c_last);
+
 // The head of every training handle (tn_head, tn_finetune, tn_gnmt_trainer): the flat parameter / gradient buffers, the state
 // buffer of the handles that have one, and the table that names their contents.
 struct TrainParams {

@@ -1286,9 +1286,23 @@ extern "C" int tn_gnmt_create_ex(tn_ctx *ctx, const tn_param *params, int n_para
 
 // GNMTEncoder.forward + the attention key projection; keeps mem / states inside the handle.
 // mem_out (B,T,H) may be NULL.
+static int gnmt_encode(tn_gnmt *g, const float *src, const float *table, int n_rows, int ld, const int32_t *row_idx,
+                       const int32_t *valid_len, int batch, int steps, float *mem_out);
 extern "C" int tn_gnmt_encode(tn_gnmt *g, const float *src, const int32_t *valid_len, int batch, int steps, float *mem_out) {
   TN_REQUIRE(g && src && valid_len, "tn_gnmt_encode: null argument");
   TN_REQUIRE(batch > 0 && batch <= g->maxB && steps > 0 && steps <= g->maxT, "tn_gnmt_encode: batch/steps exceed the handle");
+  return gnmt_encode(g, src, nullptr, 0, 0, nullptr, valid_len, batch, steps, mem_out);
+}
+// tn_gnmt_encode from a device-resident feature table (tennis_hip.h): encoder layer 0's i2h product gathers its rows.
+extern "C" int tn_gnmt_encode_rows(tn_gnmt *g, const float *table, int n_rows, int ld, const int32_t *row_idx, const int32_t *valid_len,
+                                   int batch, int steps, float *mem_out) {
+  TN_REQUIRE(g && table && row_idx && valid_len, "tn_gnmt_encode_rows: null argument");
+  TN_REQUIRE(n_rows >= 1 && ld >= g->F, "tn_gnmt_encode_rows: needs n_rows >= 1 and ld >= the handle's input size");
+  TN_REQUIRE(batch > 0 && batch <= g->maxB && steps > 0 && steps <= g->maxT, "tn_gnmt_encode_rows: batch/steps exceed the handle");
+  return gnmt_encode(g, nullptr, table, n_rows, ld, row_idx, valid_len, batch, steps, mem_out);
+}
+static int gnmt_encode(tn_gnmt *g, const float *src, const float *table, int n_rows, int ld, const int32_t *row_idx,
+                       const int32_t *valid_len, int batch, int steps, float *mem_out) {
   TN_ON_DEVICE(g->ctx->device);
   hipStream_t s = g->ctx->stream;
   const int H = g->H;
@@ -1299,7 +1313,8 @@ extern "C" int tn_gnmt_encode(tn_gnmt *g, const float *src, const int32_t *valid
   const float *in = src;
   for (int i = 0; i < g->NL; ++i) {
     float *outp = i == g->NL - 1 ? g->mem : (i & 1) ? g->seqB : g->seq0;
-    rc = tn_birnn_forward(g->enc[i], in, batch, steps, g->vl, outp, g->hl[i], g->cl[i]);   // bi: hl / cl = [fwd, bwd] final states
+    if (i == 0 && row_idx) rc = birnn_forward_rows(g->enc[i], table, n_rows, ld, row_idx, batch, steps, g->vl, outp, g->hl[i], g->cl[i]);
+    else rc = tn_birnn_forward(g->enc[i], in, batch, steps, g->vl, outp, g->hl[i], g->cl[i]);   // bi: hl / cl = [fwd, bwd] final states
     if (rc) return rc;
     if (g->residual && i > g->NBI) {      // gnmt.py:155-157: outputs + inputs from the SECOND uni-directional layer on
       const long nel = (long)batch * steps * H;
@@ -1738,10 +1753,37 @@ extern "C" int tn_gnmt_trainer_forward_backward(tn_gnmt_trainer *t, const float 
   return gnmt_trainer_step(t, src, src_valid_len, tgt, ld, tgt_valid_len, batch, steps, tgt_len, loss, logits_out, nullptr, 0);
 }
 
+// The source of a step that is never materialised: row b * steps + t of src is row idx[b * steps + t] of a device-resident feature
+// table (n_rows, F; row stride ld), a row of zeros where the index is negative (the padding behind a clip shorter than the batch's
+// longest).  Layer 0's two readers of src gather it while they stage it.
+struct SrcRows {
+  const float *table;
+  int n_rows, ld;
+  const int32_t *idx;
+};
+static int trainer_step(tn_gnmt_trainer *t, const float *src, const SrcRows *rows, const int32_t *src_valid_len, const int32_t *tgt, int ld,
+                        const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out, float *dsrc, int ldd);
+
 // ... and, with dsrc, d loss / d src (train.h): the end-to-end frame-mode step hands it to the backbone's backward.
 int gnmt_trainer_step(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len, const int32_t *tgt, int ld,
                       const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out, float *dsrc, int ldd) {
   TN_REQUIRE(t && src && src_valid_len && tgt && tgt_valid_len && loss, "tn_gnmt_trainer_forward_backward: null argument");
+  return trainer_step(t, src, nullptr, src_valid_len, tgt, ld, tgt_valid_len, batch, steps, tgt_len, loss, logits_out, dsrc, ldd);
+}
+
+// The same step from a device-resident feature table (tennis_hip.h): everything but layer 0's two readers of src is the code above.
+extern "C" int tn_gnmt_trainer_forward_backward_rows(tn_gnmt_trainer *t, const float *table, int n_rows, int ld, const int32_t *row_idx,
+                                                     const int32_t *src_valid_len, const int32_t *tgt, int ld_tgt,
+                                                     const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss,
+                                                     float *logits_out) {
+  TN_REQUIRE(t && table && row_idx && src_valid_len && tgt && tgt_valid_len && loss, "tn_gnmt_trainer_forward_backward_rows: null argument");
+  TN_REQUIRE(n_rows >= 1 && ld >= t->F, "tn_gnmt_trainer_forward_backward_rows: needs n_rows >= 1 and ld >= the handle's input size");
+  const SrcRows rows{table, n_rows, ld, row_idx};
+  return trainer_step(t, nullptr, &rows, src_valid_len, tgt, ld_tgt, tgt_valid_len, batch, steps, tgt_len, loss, logits_out, nullptr, 0);
+}
+
+static int trainer_step(tn_gnmt_trainer *t, const float *src, const SrcRows *rows, const int32_t *src_valid_len, const int32_t *tgt, int ld,
+                        const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out, float *dsrc, int ldd) {
   TN_REQUIRE(batch > 0 && batch <= t->maxB && steps > 0 && steps <= t->maxT && tgt_len >= 2 && tgt_len - 1 <= t->maxL && ld >= tgt_len,
              "tn_gnmt_trainer_forward_backward: batch / source steps / target length exceed the handle");
   TN_REQUIRE(!dsrc || ldd >= t->F, "gnmt_trainer_step: the source gradient's row stride is below input_size");
@@ -1773,7 +1815,10 @@ int gnmt_trainer_step(tn_gnmt_trainer *t, const float *src, const int32_t *src_v
   for (int i = 0; i < NL; ++i) {
     TrnEnc &e = t->enc[i];
     const int DG = e.D * GH;
-    TN_TRY(launch_linear_f32(xin[i], e.in, w + e.o_wi, e.in, w + e.o_bi, e.gi, DG, BT, DG, e.in, 0, s));
+    if (i == 0 && rows)
+      TN_TRY(launch_linear_f32_padrows(rows->table, rows->ld, rows->idx, rows->n_rows, w + e.o_wi, e.in, w + e.o_bi, e.gi, DG, BT, DG, e.in, 0, s));
+    else
+      TN_TRY(launch_linear_f32(xin[i], e.in, w + e.o_wi, e.in, w + e.o_bi, e.gi, DG, BT, DG, e.in, 0, s));
     TN_HIP_CHECK(hipMemsetAsync(e.seq, 0, sizeof(float) * (size_t)BT * e.out, s));
     TN_TRY(launch_rnn_recurrent(G, e.gi, DG, e.whT, w + e.o_bh, t->vl, e.seq, e.out, e.hl, lstm ? e.cl : nullptr, B, T, H, e.D, s, e.sav));
     // dropout on the layer's output (the states are not dropped), then the residual connection (gnmt.py:152-157)
@@ -1942,7 +1987,10 @@ int gnmt_trainer_step(tn_gnmt_trainer *t, const float *src, const int32_t *src_v
     if (lstm) TN_TRY(launch_lstm_train_bwd(e.seq, e.sav, dseq, w + e.o_wh, e.dgi, e.hp, B, T, H, s, e.D, t->vl, e.dhl, e.dcl));
     else TN_TRY(launch_gru_train_bwd(e.seq, e.sav, dseq, w + e.o_wh, e.dgi, e.dgh, e.hp, B, T, H, s, e.D, t->vl, e.dhl));
     const float *dgh = lstm ? e.dgi : e.dgh;      // LSTM: one pre-activation gradient feeds both branches
-    TN_TRY(launch_gemm_tn_f32(e.dgi, DG, xin[i], e.in, g + e.o_wi, e.in, DG, e.in, BT, s));
+    if (i == 0 && rows)       // dW_ih = dGI^T src, src gathered: one slice, as the call below (no workspace)
+      TN_TRY(launch_gemm_tn_f32_padrows(e.dgi, DG, rows->table, rows->ld, rows->idx, rows->n_rows, g + e.o_wi, e.in, DG, e.in, BT, s));
+    else
+      TN_TRY(launch_gemm_tn_f32(e.dgi, DG, xin[i], e.in, g + e.o_wi, e.in, DG, e.in, BT, s));
     TN_TRY(launch_colsum_f32(e.dgi, DG, BT, DG, g + e.o_bi, s));
     for (int d = 0; d < e.D; ++d)
       TN_TRY(launch_gemm_tn_f32(dgh + (size_t)d * GH, DG, e.hp + (size_t)d * BT * H, H, g + e.o_wh + (long)d * GH * H, H, GH, H, BT, s));

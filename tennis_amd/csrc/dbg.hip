@@ -603,6 +603,12 @@ extern "C" int tn_dbg_gnmt_trainer_src_grad(tn_gnmt_trainer *t, const float *src
   return gnmt_trainer_step(t, src, src_valid_len, tgt, ld, tgt_valid_len, batch, steps, tgt_len, loss, logits_out, dsrc, ldd);
 }
 
+// Measurement switch of the pad-row gathered linear kernels (linear.h): 0 launches the instantiation without the pad-tile skip
+extern "C" int tn_dbg_rows_pad_skip(int on) {
+  linear_rows_set_pad_skip(on != 0);
+  return TN_OK;
+}
+
 // The forward 1x1 convolution of the fine-tuning step with its BatchNorm + ReLU applied to the X operand
 extern "C" int tn_dbg_linear_bnrelu(tn_ctx *ctx, const float *X, int ldx, const float *asc, const float *ash, const float *W, int ldw,
                                     const float *bias, float *Y, int ldy, int M, int N, int K, int accumulate) {

@@ -66,6 +66,12 @@ int launch_linear_f32(const float *X, int ldx, const float *Wt, int ldw, const f
 // Dispatch, k order and MFMA order are launch_linear_f32's, so the result equals that of the materialised X bit for bit.
 int launch_linear_f32_rows(const float *table, int ld, const int32_t *rows, int n_rows, const float *Wt, int ldw, const float *bias,
                            float *Y, int ldy, int M, int N, int K, int accumulate, hipStream_t s);
+// ... for ragged clips: rows[m] < 0 is a row of zeros, rows[m] >= n_rows clamps to the last row.  Equals launch_linear_f32 on the
+// zero-padded materialised X bit for bit; a workgroup whose M-tile is all pad rows runs no k-loop.  linear_rows_set_pad_skip(false)
+// launches the instantiation without that skip (measurement only; process-wide).
+int launch_linear_f32_padrows(const float *table, int ld, const int32_t *rows, int n_rows, const float *Wt, int ldw, const float *bias,
+                              float *Y, int ldy, int M, int N, int K, int accumulate, hipStream_t s);
+void linear_rows_set_pad_skip(bool on);
 // Latency-optimised form for skinny problems (few rows, K >= 128, float4-aligned operands; falls back to launch_linear_f32
 // otherwise): 16 x 16 output tiles, K split over the four waves of a workgroup, every operand requested up front.
 int launch_linear_f32_lat(const float *X, int ldx, const float *Wt, int ldw, const float *bias, float *Y, int ldy, int M, int N, int K,

@@ -19,7 +19,12 @@ constexpr int kPD = 4;   // k-tiles of 16 in flight per thread (registers) ahead
 // GX (the temporal head trained from a feature table): row m of the X operand is row clamp(xrows[m], 0, xn - 1) of the table X
 // points to (row stride ldx).  A thread stages the same row for every k-tile, so its index is loaded once, before the loop; the
 // clamp keeps every read inside the table whatever xrows holds.  k-loop and MFMA order are those of the plain form.
-template <int F, bool BN = false, bool GX = false>
+// ZR (with GX; the captioner trained from a feature table, whose clips are ragged): an index below 0 names a PAD row - the thread
+// stages zeros for it, as the zero-padded batch holds them, and reads nothing; an index >= xn still clamps.  ZR = 1: a workgroup
+// whose whole M-tile is pad rows runs no k-loop (nk = 0, block-uniform) and goes straight to the epilogue, whose accumulators are
+// the +0 the k-loop would have left (0 * w summed from +0, finite w): it writes bias, or adds it when accumulating, exactly as the
+// materialised step does.  ZR = 2: the same rows without that skip (the measurement's control, tn_dbg_rows_pad_skip).
+template <int F, bool BN = false, bool GX = false, int ZR = 0>
 __global__ __launch_bounds__(256) void linear_f32_kernel(const float *__restrict__ X, int ldx,
                                                          const float *__restrict__ Wt, int ldw,
                                                          const float *__restrict__ bias, float *__restrict__ Y,
@@ -39,7 +44,14 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float *__restrict
   const int am = m0 + srow, bn = n0 + srow;
   const float *xrow = X + (long)am * ldx, *wrow = Wt + (long)bn * ldw;
   if constexpr (GX) xrow = X + (long)(doA && am < M ? min(max(xrows[am], 0), xn - 1) : 0) * ldx;
-  const int nk = (K + 15) / 16;
+  bool pad = false;                      // ZR: this thread's row of X is a pad row
+  if constexpr (GX && ZR != 0) pad = doA && am < M && xrows[am] < 0;
+  bool skip = false;                     // ZR = 1: the whole M-tile is pad rows (block-uniform)
+  if constexpr (GX && ZR == 1) {         // F = 2: the 256 threads cover the tile's 64 rows, so the vote sees every row
+    static_assert(F == 2, "the pad-tile vote needs every thread to stage a row of X");
+    skip = __syncthreads_and(pad || am >= M);
+  }
+  const int nk = skip ? 0 : (K + 15) / 16;
 
   f32x4 acc[F][F];
 #pragma unroll
@@ -55,7 +67,7 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float *__restrict
     for (int j = 0; j < 4; ++j) { a4[j] = 0.f; b4[j] = 0.f; }
     if (it >= nk) return;
     if (vec) {
-      if (doA && am < M && kk < K) {
+      if (doA && am < M && !pad && kk < K) {
         const float4 v = *(const float4 *)(xrow + kk);
         a4[0] = v.x; a4[1] = v.y; a4[2] = v.z; a4[3] = v.w;
         if constexpr (BN) {
@@ -68,7 +80,7 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float *__restrict
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (doA && am < M && kk + j < K) {
+        if (doA && am < M && !pad && kk + j < K) {
           a4[j] = xrow[kk + j];
           if constexpr (BN) a4[j] = fmaxf(fmaf(a4[j], asc[kk + j], ash[kk + j]), 0.f);
         }
@@ -131,7 +143,7 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float *__restrict
 
 // Skinny problems (fewer than two 64x64 tiles per CU): 32x32 tile, one 16x16 fragment per wave, BK = 32 so that a
 // k-tile carries 8 MFMAs per barrier.  Same k order per output element as linear_f32_kernel (one accumulator chain).
-template <bool BN = false, bool GX = false>        // GX: as in linear_f32_kernel
+template <bool BN = false, bool GX = false, int ZR = 0>        // GX, ZR: as in linear_f32_kernel (the M-tile is 32 rows here)
 __global__ __launch_bounds__(256) void linear_f32_skinny_kernel(const float *__restrict__ X, int ldx,
                                                                 const float *__restrict__ Wt, int ldw,
                                                                 const float *__restrict__ bias, float *__restrict__ Y,
@@ -148,7 +160,10 @@ __global__ __launch_bounds__(256) void linear_f32_skinny_kernel(const float *__r
   const int am = m0 + srow, bn = n0 + srow;
   const float *xrow = X + (long)am * ldx, *wrow = Wt + (long)bn * ldw;
   if constexpr (GX) xrow = X + (long)(am < M ? min(max(xrows[am], 0), xn - 1) : 0) * ldx;
-  const int nk = (K + 31) / 32;
+  bool pad = false, skip = false;
+  if constexpr (GX && ZR != 0) pad = am < M && xrows[am] < 0;
+  if constexpr (GX && ZR == 1) skip = __syncthreads_and(pad || am >= M);
+  const int nk = skip ? 0 : (K + 31) / 32;
   f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
   constexpr int PD = 3;
   float av[PD][4], bv[PD][4];
@@ -158,7 +173,7 @@ __global__ __launch_bounds__(256) void linear_f32_skinny_kernel(const float *__r
     for (int j = 0; j < 4; ++j) { a4[j] = 0.f; b4[j] = 0.f; }
     if (it >= nk) return;
     if (vec) {
-      if (am < M && kk < K) {
+      if (am < M && !pad && kk < K) {
         const float4 v = *(const float4 *)(xrow + kk);
         a4[0] = v.x; a4[1] = v.y; a4[2] = v.z; a4[3] = v.w;
         if constexpr (BN) {
@@ -171,7 +186,7 @@ __global__ __launch_bounds__(256) void linear_f32_skinny_kernel(const float *__r
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (am < M && kk + j < K) {
+        if (am < M && !pad && kk + j < K) {
           a4[j] = xrow[kk + j];
           if constexpr (BN) a4[j] = fmaxf(fmaf(a4[j], asc[kk + j], ash[kk + j]), 0.f);
         }
@@ -330,6 +345,35 @@ int launch_linear_f32_rows(const float *table, int ld, const int32_t *rows, int 
     const dim3 grid((N + 31) / 32, (M + 31) / 32), block(256);
     hipLaunchKernelGGL((linear_f32_skinny_kernel<false, true>), grid, block, 0, s, table, ld, Wt, ldw, bias, Y, ldy, M, N, K, accumulate,
                        (const float *)nullptr, (const float *)nullptr, rows, n_rows);
+  }
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+
+// ... with pad rows: rows[m] < 0 is a row of zeros (what a batch zero-padded to its longest clip holds there), rows[m] >= n_rows
+// clamps to the last row; no content of rows reads outside the table.  Equals launch_linear_f32 on the materialised zero-padded X
+// bit for bit.  A workgroup whose M-tile holds only pad rows skips its k-loop and writes the bias (g_rows_pad_skip, on unless a
+// measurement switches it off).
+static bool g_rows_pad_skip = true;
+void linear_rows_set_pad_skip(bool on) { g_rows_pad_skip = on; }
+int launch_linear_f32_padrows(const float *table, int ld, const int32_t *rows, int n_rows, const float *Wt, int ldw, const float *bias,
+                              float *Y, int ldy, int M, int N, int K, int accumulate, hipStream_t s) {
+  if (M <= 0 || N <= 0) return TN_OK;
+  TN_REQUIRE(table && rows && n_rows > 0 && ld >= K, "linear_f32_padrows: needs a table of at least one row, ld >= K, and the row indices");
+  const long big = (long)((N + 63) / 64) * ((M + 63) / 64);
+  const float *const nof = nullptr;
+  if (big >= 512) {
+    const dim3 grid((N + 63) / 64, (M + 63) / 64), block(256);
+    if (g_rows_pad_skip)
+      hipLaunchKernelGGL((linear_f32_kernel<2, false, true, 1>), grid, block, 0, s, table, ld, Wt, ldw, bias, Y, ldy, M, N, K, accumulate, nof, nof, rows, n_rows);
+    else
+      hipLaunchKernelGGL((linear_f32_kernel<2, false, true, 2>), grid, block, 0, s, table, ld, Wt, ldw, bias, Y, ldy, M, N, K, accumulate, nof, nof, rows, n_rows);
+  } else {
+    const dim3 grid((N + 31) / 32, (M + 31) / 32), block(256);
+    if (g_rows_pad_skip)
+      hipLaunchKernelGGL((linear_f32_skinny_kernel<false, true, 1>), grid, block, 0, s, table, ld, Wt, ldw, bias, Y, ldy, M, N, K, accumulate, nof, nof, rows, n_rows);
+    else
+      hipLaunchKernelGGL((linear_f32_skinny_kernel<false, true, 2>), grid, block, 0, s, table, ld, Wt, ldw, bias, Y, ldy, M, N, K, accumulate, nof, nof, rows, n_rows);
   }
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;

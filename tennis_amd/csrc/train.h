@@ -26,6 +26,10 @@ int launch_gemm_tn_f32_bnrelu(const float *A, int lda, const float *Bm, int ldb,
 // DEVICE).  Un-split only; equals launch_gemm_tn_f32 (no workspace) on the materialised B bit for bit.
 int launch_gemm_tn_f32_rows(const float *A, int lda, const float *table, int ld, const int32_t *rows, int n_rows, float *Cm, int ldc,
                             int M, int N, int K, hipStream_t s);
+// ... for ragged clips: rows[k] < 0 is a row of zeros, rows[k] >= n_rows clamps to the last row; equals launch_gemm_tn_f32 (no
+// workspace) on the zero-padded materialised B bit for bit.  Pad rows are staged, not skipped: the k-tiles keep their members.
+int launch_gemm_tn_f32_padrows(const float *A, int lda, const float *table, int ld, const int32_t *rows, int n_rows, float *Cm, int ldc,
+                               int M, int N, int K, hipStream_t s);
 // C (M, N; row stride ldc) (+)= A (M, K; row stride lda) B (K, N; row stride ldb), both row-major (gemm_nn.hip)
 int launch_gemm_nn_f32(const float *A, int lda, const float *Bm, int ldb, float *Cm, int ldc, int M, int N, int K, int accumulate,
                        hipStream_t s);

@@ -329,7 +329,10 @@ constexpr int kTnPD = 4;
 // (row stride ldb).  The staged row changes with every k-tile, so a thread keeps the index of its next data fetch in a register,
 // loaded kTnPD k-tiles before that fetch is issued: no data load waits on an index load inside the loop.  The clamp keeps every
 // read inside the table whatever brows holds.  k-loop and MFMA order are those of the plain form.
-template <bool BNB = false, bool GB = false>
+// ZB (with GB; the captioner trained from a feature table): an index below 0 names a PAD row of a ragged clip - zeros are staged
+// for it, as the zero-padded batch holds them, and nothing is read; an index >= bn_rows still clamps.  Pad k-rows stay in their
+// k-tiles: which k's share an MFMA is unchanged, so the sum is that of the materialised operand bit for bit.
+template <bool BNB = false, bool GB = false, bool ZB = false>
 __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(const float *__restrict__ A, int lda,
                                                           const float *__restrict__ Bm, int ldb,
                                                           float *__restrict__ Cm, int ldc, int M, int N, int K, int kchunk,
@@ -356,7 +359,12 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(const float *__restric
   int bidx[kTnPD];                  // GB: slot p holds the table row of the k-tile slot p fetches next
   auto row_of = [&](int it) {       // the table row this thread stages for k-tile `it` (0 past the end: never read)
     const int k = it * 16 + sk;
-    return it < nk && k < K ? min(max(brows[k], 0), bn_rows - 1) : 0;
+    if constexpr (ZB) {             // -1: a pad row, staged as zeros
+      const int r = it < nk && k < K ? brows[k] : 0;
+      return r < 0 ? -1 : min(r, bn_rows - 1);
+    } else {
+      return it < nk && k < K ? min(max(brows[k], 0), bn_rows - 1) : 0;
+    }
   };
   auto fetch = [&](int it, float *a4, float *b4, int brow) {
     const int k = it * 16 + sk;
@@ -364,10 +372,20 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(const float *__restric
     for (int q = 0; q < 4; ++q) { a4[q] = 0.f; b4[q] = 0.f; }
     if (it >= nk || k >= K) return;
     const long bk = GB ? brow : k;            // the row of Bm staged for this k
+    const bool brd = !ZB || brow >= 0;        // ZB: a pad row keeps the zeros
     if (vec) {
-      const float4 va = *(const float4 *)(A + (long)k * lda + m0 + sc), vb = *(const float4 *)(Bm + bk * ldb + n0 + sc);
-      a4[0] = va.x; a4[1] = va.y; a4[2] = va.z; a4[3] = va.w;
-      b4[0] = vb.x; b4[1] = vb.y; b4[2] = vb.z; b4[3] = vb.w;
+      if constexpr (ZB) {
+        const float4 va = *(const float4 *)(A + (long)k * lda + m0 + sc);
+        a4[0] = va.x; a4[1] = va.y; a4[2] = va.z; a4[3] = va.w;
+        if (brd) {
+          const float4 vb = *(const float4 *)(Bm + bk * ldb + n0 + sc);
+          b4[0] = vb.x; b4[1] = vb.y; b4[2] = vb.z; b4[3] = vb.w;
+        }
+      } else {
+        const float4 va = *(const float4 *)(A + (long)k * lda + m0 + sc), vb = *(const float4 *)(Bm + bk * ldb + n0 + sc);
+        a4[0] = va.x; a4[1] = va.y; a4[2] = va.z; a4[3] = va.w;
+        b4[0] = vb.x; b4[1] = vb.y; b4[2] = vb.z; b4[3] = vb.w;
+      }
       if constexpr (BNB) {
         const float4 s4 = *(const float4 *)(bsc + n0 + sc), h4 = *(const float4 *)(bsh + n0 + sc);
         b4[0] = fmaxf(fmaf(b4[0], s4.x, h4.x), 0.f); b4[1] = fmaxf(fmaf(b4[1], s4.y, h4.y), 0.f);
@@ -377,7 +395,7 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(const float *__restric
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         if (m0 + sc + q < M) a4[q] = A[(long)k * lda + m0 + sc + q];
-        if (n0 + sc + q < N) {
+        if ((!ZB || brd) && n0 + sc + q < N) {
           b4[q] = Bm[bk * ldb + n0 + sc + q];
           if constexpr (BNB) b4[q] = fmaxf(fmaf(b4[q], bsc[n0 + sc + q], bsh[n0 + sc + q]), 0.f);
         }
@@ -621,6 +639,16 @@ int launch_gemm_tn_f32_rows(const float *A, int lda, const float *table, int ld,
   TN_REQUIRE(table && rows && n_rows > 0 && ld >= N, "gemm_tn_f32_rows: needs a table of at least one row, ld >= N, and the row indices");
   const dim3 grid((N + 63) / 64, (M + 63) / 64, 1);
   hipLaunchKernelGGL((gemm_tn_f32_kernel<false, true>), grid, dim3(256), 0, s, A, lda, table, ld, Cm, ldc, M, N, K, K, (const float *)nullptr,
+                     (const float *)nullptr, rows, n_rows);
+  TN_LAUNCH_CHECK();
+}
+// ... with pad rows: rows[k] < 0 is a row of zeros (a batch zero-padded to its longest clip), rows[k] >= n_rows clamps to the last
+// row.  Un-split; equals launch_gemm_tn_f32 (no workspace) on the materialised zero-padded B bit for bit.
+int launch_gemm_tn_f32_padrows(const float *A, int lda, const float *table, int ld, const int32_t *rows, int n_rows, float *Cm, int ldc,
+                               int M, int N, int K, hipStream_t s) {
+  TN_REQUIRE(table && rows && n_rows > 0 && ld >= N, "gemm_tn_f32_padrows: needs a table of at least one row, ld >= N, and the row indices");
+  const dim3 grid((N + 63) / 64, (M + 63) / 64, 1);
+  hipLaunchKernelGGL((gemm_tn_f32_kernel<false, true, true>), grid, dim3(256), 0, s, A, lda, table, ld, Cm, ldc, M, N, K, K, (const float *)nullptr,
                      (const float *)nullptr, rows, n_rows);
   TN_LAUNCH_CHECK();
 }

@@ -23,6 +23,47 @@ def _on_ctx_device(ctx, x: torch.Tensor, what: str):
         raise ValueError(f"{what}: input is on cuda:{x.device.index} but this handle was built on cuda:{ctx.device}")
 
 
+def _clip_table(ctx, table: torch.Tensor, input_size: int, what: str) -> torch.Tensor:
+    """The (rows, F) fp32 feature table the captioner's ``*_rows`` calls gather their clips from: on the handle's GPU already (uploaded
+    once), rows of unit element stride - a column slice of a wider table passes, its row stride travels as ``ld``."""
+    if not isinstance(table, torch.Tensor):
+        raise ValueError(f"{what}: the table must be a torch tensor on the GPU, got {type(table).__name__}")
+    _on_ctx_device(ctx, table, what)
+    if table.dim() != 2 or table.shape[1] != input_size or table.shape[0] < 1 or table.dtype != torch.float32:
+        raise ValueError(f"{what}: need a (rows, {input_size}) float32 table, got {tuple(table.shape)} {table.dtype}")
+    if table.stride(1) != 1 or table.stride(0) < input_size:
+        table = table.contiguous()
+    return table
+
+
+def _clip_rows(ctx, table: torch.Tensor, idx, valid_length, what: str) -> torch.Tensor:
+    """(B, T) clip rows -> int32 on the handle's GPU.  A host-side ``idx`` (numpy array, CPU tensor, nested list) is checked here,
+    before any launch: -1 <= idx < rows, and no -1 (a pad step) before a clip's valid length.  A device tensor is passed through: the
+    kernels read zeros for a negative index and clamp one past the table."""
+    if isinstance(idx, torch.Tensor) and idx.is_cuda:
+        _on_ctx_device(ctx, idx, what)
+    else:
+        host = idx.numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)
+        if host.dtype.kind not in "iu":
+            raise ValueError(f"{what}: idx must hold integers, got {host.dtype}")
+        if host.ndim != 2:
+            raise ValueError(f"{what}: idx must be (batch, steps), got {host.shape}")
+        if host.size and (int(host.min()) < -1 or int(host.max()) >= table.shape[0]):
+            raise ValueError(f"{what}: idx must lie in [-1, {table.shape[0] - 1}], got [{int(host.min())}, {int(host.max())}]")
+        vl = valid_length.detach().cpu().numpy() if isinstance(valid_length, torch.Tensor) else np.asarray(valid_length)
+        vl = np.rint(vl).astype(np.int64).reshape(-1)
+        if vl.shape[0] != host.shape[0] or (vl.size and (int(vl.min()) < 0 or int(vl.max()) > host.shape[1])):
+            raise ValueError(f"{what}: valid lengths must be one per clip within [0, {host.shape[1]}]")
+        inside = np.arange(host.shape[1])[None, :] < vl[:, None]
+        if bool(((host < 0) & inside).any()):
+            b = int(np.argmax(((host < 0) & inside).any(1)))
+            raise ValueError(f"{what}: clip {b} has a pad step (-1) before its valid length {int(vl[b])}")
+        idx = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(table.device)
+    if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
+        raise ValueError(f"{what}: idx must be (batch, steps), got {tuple(idx.shape)}")
+    return idx.to(torch.int32).contiguous()
+
+
 def _layout_of(x: torch.Tensor, size_hw):
     """Pick the tn_layout of a frame batch from dtype/shape (reference frames are
     NCHW float32 after ToTensor+Normalize, evaluate.py:96-97)."""
@@ -395,7 +436,7 @@ class GNMTCaptioner(_Handle):
         """``num_layers`` / ``num_bi_layers`` / ``use_residual`` as in ``get_gnmt_encoder_decoder`` (reference gnmt.py:407-455):
         2 <= num_layers, num_bi_layers < num_layers (gnmt.py:78-80 and the attention's key width, see tn_gnmt_create_ex)."""
         super().__init__(ctx)
-        self.hidden, self.beam, self.max_length, self.vocab = hidden, beam, max_length, vocab
+        self.hidden, self.beam, self.max_length, self.vocab, self.input_size = hidden, beam, max_length, vocab, input_size
         arr, keep = _lib.make_params({k: v for k, v in params.items() if k.startswith(prefix)})
         h = C.c_void_p()
         kind = _lib.RNN_GRU if cell_type == "gru" else _lib.RNN_LSTM
@@ -412,6 +453,21 @@ class GNMTCaptioner(_Handle):
         vl = valid_length.to(device=src.device).round().to(torch.int32).contiguous()
         mem = torch.empty((b, t, self.hidden), dtype=torch.float32, device=src.device)
         check(self.lib.tn_gnmt_encode(self.handle, ptr(src), ptr(vl), b, t, ptr(mem)), "tn_gnmt_encode")
+        self._batch = b
+        return mem
+
+    def encode_rows(self, table: torch.Tensor, idx, valid_length) -> torch.Tensor:
+        """``encode(pad(table[idx]), valid_length)`` without the (B, T, F) batch: ``idx`` (B, T) names each step's row of the
+        device-resident ``table`` (rows, F), -1 behind a clip's end (a row of zeros); encoder layer 0's i2h product gathers the rows
+        while it stages them, in the same arithmetic order: ``mem`` and everything ``decode_seq`` / ``beam_search`` derive from it are
+        bit-identical to the materialised route."""
+        table = _clip_table(self.ctx, table, self.input_size, "encode_rows")
+        idx = _clip_rows(self.ctx, table, idx, valid_length, "encode_rows")
+        b, t = idx.shape
+        vl = torch.as_tensor(valid_length).to(device=table.device).round().to(torch.int32).contiguous()
+        mem = torch.empty((b, t, self.hidden), dtype=torch.float32, device=table.device)
+        check(self.lib.tn_gnmt_encode_rows(self.handle, ptr(table), table.shape[0], table.stride(0), ptr(idx), ptr(vl), b, t, ptr(mem)),
+              "tn_gnmt_encode_rows")
         self._batch = b
         return mem
 
@@ -588,6 +644,26 @@ class GNMTTrainer(_FlatTrainer):
         logits = torch.empty((b, tgt.shape[1] - 1, self.vocab), dtype=torch.float32, device=dev) if return_logits else None
         check(self.lib.tn_gnmt_trainer_forward_backward(self.handle, ptr(src), ptr(svl), ptr(tgt), tgt.shape[1], ptr(tvl), b, t,
                                                         tgt.shape[1], ptr(loss), ptr(logits)), "tn_gnmt_trainer_forward_backward")
+        return (loss[0], logits) if return_logits else loss[0]
+
+    def forward_backward_rows(self, table: torch.Tensor, idx, src_valid_length, tgt: torch.Tensor, tgt_valid_length,
+                              return_logits: bool = False):
+        """``forward_backward(pad(table[idx]), ...)`` without the (B, T, F) batch: ``table`` (rows, F) fp32 lives on the GPU (uploaded
+        once per split), ``idx`` (B, T) names each step's row, -1 behind a clip's end (the zero padding of the materialised batch).
+        Layer 0's i2h product and dW_ih gather the rows while they stage them, in the same arithmetic order: loss, logits and
+        gradients are bit-identical to the materialised step."""
+        table = _clip_table(self.ctx, table, self.input_size, "forward_backward_rows")
+        idx = _clip_rows(self.ctx, table, idx, src_valid_length, "forward_backward_rows")
+        b, t = idx.shape
+        dev = table.device
+        tgt = torch.as_tensor(tgt).to(device=dev, dtype=torch.int32).contiguous()
+        svl = torch.as_tensor(src_valid_length).to(device=dev, dtype=torch.int32).contiguous()
+        tvl = torch.as_tensor(tgt_valid_length).to(device=dev, dtype=torch.int32).contiguous()
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        logits = torch.empty((b, tgt.shape[1] - 1, self.vocab), dtype=torch.float32, device=dev) if return_logits else None
+        check(self.lib.tn_gnmt_trainer_forward_backward_rows(self.handle, ptr(table), table.shape[0], table.stride(0), ptr(idx), ptr(svl),
+                                                             ptr(tgt), tgt.shape[1], ptr(tvl), b, t, tgt.shape[1], ptr(loss), ptr(logits)),
+              "tn_gnmt_trainer_forward_backward_rows")
         return (loss[0], logits) if return_logits else loss[0]
 
     def set_dropout(self, p: float, seed: int = 0):

@@ -60,23 +60,28 @@ def load_feature_matrix(dataset):
 TABLE_LOAD_THREADS = 8      # host threads of load_feature_table: file reads overlap; a constant, not the machine's core count
 
 
+def read_rows(read, n):
+    """(n, F) float32: row r = ``read(r)`` flattened, every r read once on the table readers' thread pool (row 0 first, for the width)."""
+    first = np.asarray(read(0), np.float32).reshape(-1)
+    table = np.empty((n, first.size), np.float32)
+    table[0] = first
+
+    def fill(r):
+        table[r] = np.asarray(read(r)).reshape(-1)
+
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=TABLE_LOAD_THREADS) as pool:
+        list(pool.map(fill, range(1, n)))
+    return table
+
+
 def load_feature_table(dataset, frames):
     """The (len(frames), F) float32 feature table of ``TennisSet.window_table``: row r is the ``.npy`` of ``frames[r]`` = (video,
     frame) under ``dataset.feat_dir``, every file read exactly once (the loader path reads it about ``window`` times per epoch)."""
     if not len(frames):
         raise ValueError("load_feature_table: no frames")
     path = lambda vf: dataset.get_feature_path(dataset.feat_dir, vf[0], vf[1])
-    first = np.load(path(frames[0])).astype(np.float32).reshape(-1)
-    table = np.empty((len(frames), first.size), np.float32)
-    table[0] = first
-
-    def fill(r):
-        table[r] = np.load(path(frames[r])).reshape(-1)
-
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=TABLE_LOAD_THREADS) as pool:
-        list(pool.map(fill, range(1, len(frames))))
-    return table
+    return read_rows(lambda r: np.load(path(frames[r])), len(frames))
 
 
 def evaluate_windows(net, dataset, metrics, features=None, batch_size=65536):

@@ -10,11 +10,12 @@ import os
 
 from .captions import bucketed_batches, evaluate, write_sentences
 from .metrics.bleu import compute_bleu
-from .train_gnmt import build, build_parser
+from .train_gnmt import build, build_parser, require_feature_mode
 
 
 def main(argv=None):
     flags = build_parser().parse_args(argv)
+    require_feature_mode(flags)
     data_train, data_val, data_test, model, translator = build(flags)
     exp = os.path.join(flags.root, flags.model_id)
     path = os.path.join(exp, "valid_best.params")
@@ -27,7 +28,12 @@ def main(argv=None):
     print("Loaded params: {}".format(path))
     out = {}
     for name, ds in (("valid", data_val), ("test", data_test)):
-        loss, sents = evaluate(bucketed_batches(ds, flags.test_batch_size, flags.num_buckets), model, translator, data_train)
+        table, rows = (None, None)
+        if flags.feats_on_device:          # the split's features read once, uploaded once; encode_rows gathers every batch's clips
+            from .captions import upload_clip_table
+            table, rows = upload_clip_table(ds)
+        loss, sents = evaluate(bucketed_batches(ds, flags.test_batch_size, flags.num_buckets, rows=rows), model, translator, data_train,
+                               table=table)
         bleu = compute_bleu([ds.get_captions(split=True)], sents)[0]
         print("Best model {} Loss={:.4f}, {} ppl={:.4f}, {} bleu={:.2f}".format(name, loss, name, math.exp(min(loss, 50.0)), name, bleu * 100))
         write_sentences(sents, os.path.join(exp, "best_{}_out.txt".format(name)))

@@ -26,7 +26,7 @@ import os
 import numpy as np
 import torch
 
-from .captions import bucketed_batches, evaluate, to_device, write_sentences
+from .captions import bucketed_batches, evaluate, to_device, upload_clip_table, write_sentences
 from .engine import GNMTFramesTrainer, GNMTTrainer
 from .metrics.bleu import compute_bleu
 
@@ -58,10 +58,13 @@ def allreduce_grads(trainer, n_tokens: int):
 def train(data_train, data_val, data_test, model, translator, epochs: int, batch_size: int, lr: float = 1e-3,
           lr_update_factor: float = 0.5, dropout: float = 0.0, num_buckets: int = 5, test_batch_size: int = 32,
           start_epoch: int = 0, save_dir: str | None = None, seed: int = 0, log=print, freeze_backbone: bool = False,
-          frame_size: int | None = None, matmul: str = "f32"):
+          frame_size: int | None = None, matmul: str = "f32", feats_on_device: bool = False):
     """-> history: one dict per epoch (train loss, valid / test loss and BLEU, learning rate).  A model with a ``src_embed`` trains on
     frames (``GNMTFramesTrainer``: the backbone inside the step, frozen or trainable); its checkpoints carry the backbone under the
-    model's structural names (``src_embed.model. ...``).  ``matmul``: the matrix pipe of that backbone's GEMMs ("f32" | "fp32x3")."""
+    model's structural names (``src_embed.model. ...``).  ``matmul``: the matrix pipe of that backbone's GEMMs ("f32" | "fp32x3").
+    ``feats_on_device`` (feature mode): each split's features are read once and uploaded as one table; the train step and the
+    per-epoch validation / test passes gather their clips from it inside the kernels (``forward_backward_rows`` / ``encode_rows``)
+    instead of reading one ``.npy`` per frame and copying a host-built batch every step.  Same parameters, losses and sentences."""
     enc = model.encoder
     if enc._cell_type not in ("gru", "lstm"):
         raise NotImplementedError("the training step is built for GRU / LSTM cells")
@@ -75,6 +78,8 @@ def train(data_train, data_val, data_test, model, translator, epochs: int, batch
     cell = dict(cell_type=enc._cell_type, num_layers=enc._num_layers, num_bi_layers=enc._num_bi_layers,
                 use_residual=bool(getattr(enc, "_use_residual", False)))
     frame_mode = getattr(model, "src_embed", None) is not None
+    if feats_on_device and frame_mode:
+        raise ValueError("feats_on_device serves feature mode: a model with a src_embed trains on frames, which no feature table holds")
     if frame_mode:
         max_t = max(max_t, max(data_train.get_clip_lens()))
         # the side of the frames the step sees: --data_shape, else the batch transform's crop, else that of per-frame (T, 3, S, S) items
@@ -104,13 +109,20 @@ def train(data_train, data_val, data_test, model, translator, epochs: int, batch
     import torch.distributed as dist
     ddp = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if ddp else (0, 1)
+    # one table per split, uploaded once; under torch.distributed every rank holds the whole table (the batch split is the loader's)
+    tables = {id(ds): upload_clip_table(ds) for ds in (data_train, data_val, data_test) if feats_on_device and ds is not None}
+    train_table, train_rows = tables.get(id(data_train), (None, None))
     for epoch_id in range(start_epoch, epochs):
         tot, nb = 0.0, 0
         # FixedBucketSampler(..., shuffle=True) of the training loader (utils/captioning.py:48-55)
         for src, tgt, svl, tvl, *_ in bucketed_batches(data_train, batch_size, num_buckets, shuffle=True, seed=seed,
-                                                       epoch=epoch_id, rank=rank, world=world):
-            loss = trainer.forward_backward(to_device(src), torch.from_numpy(svl.astype(np.int32)).cuda(),
-                                            torch.from_numpy(tgt).cuda(), torch.from_numpy(tvl.astype(np.int32)).cuda())
+                                                       epoch=epoch_id, rank=rank, world=world, rows=train_rows):
+            if feats_on_device:
+                loss = trainer.forward_backward_rows(train_table, src, svl.astype(np.int32), torch.from_numpy(tgt).cuda(),
+                                                     torch.from_numpy(tvl.astype(np.int32)).cuda())
+            else:
+                loss = trainer.forward_backward(to_device(src), torch.from_numpy(svl.astype(np.int32)).cuda(),
+                                                torch.from_numpy(tgt).cuda(), torch.from_numpy(tvl.astype(np.int32)).cuda())
             allreduce_grads(trainer, int((tvl.astype(np.int64) - 1).sum()))
             trainer.step(lr)                                                     # trainer.step(1)
             tot += float(loss)
@@ -120,7 +132,9 @@ def train(data_train, data_val, data_test, model, translator, epochs: int, batch
         for name, ds, ref in (("valid", data_val, val_tgt), ("test", data_test, test_tgt)):
             if ds is None:
                 continue
-            ev_loss, out = evaluate(bucketed_batches(ds, test_batch_size, num_buckets), model, translator, data_train)
+            ev_table, ev_rows = tables.get(id(ds), (None, None))
+            ev_loss, out = evaluate(bucketed_batches(ds, test_batch_size, num_buckets, rows=ev_rows), model, translator, data_train,
+                                    table=ev_table)
             bleu = compute_bleu([ref], out)[0]
             rec[f"{name}_loss"], rec[f"{name}_bleu"] = ev_loss, bleu
             log("[Epoch {}] {} Loss={:.4f}, {} ppl={:.4f}, {} bleu={:.2f}".format(epoch_id, name, ev_loss, name,
@@ -193,6 +207,10 @@ def build_parser():
     p.add_argument("--matmul", default="f32", choices=["f32", "fp32x3"],
                    help="frame mode: matrix pipe of the backbone's GEMMs, f32 (exact-f32 MFMA) or fp32x3 (fp32 values as three bf16 terms on "
                         "the bf16 MFMA, same float64 bars; not a reference flag)")
+    p.add_argument("--feats_on_device", action="store_true",
+                   help="feature mode: read each split's features once into one device-resident table and gather every batch's clips "
+                        "from it inside the kernels, instead of one .npy read per frame and one host-to-device copy per batch (not a "
+                        "reference flag; same results)")
     p.add_argument("--data_shape", type=int, default=512)
     p.add_argument("--feature_dim", type=int, default=1024, help="width of the pre-extracted frame features (feats_model)")
     p.add_argument("--n_points", type=int, default=64, help="synthetic source: points per split")
@@ -290,11 +308,20 @@ def build_backbone(flags):
     return TimeDistributed(cnn_model.backbone)                                                               # :168-170
 
 
+def require_feature_mode(flags):
+    """--feats_on_device is a feature-mode switch; in frame mode it ends the run with a message, like --matmul in feature mode"""
+    frame_mode = flags.feats_model is None and (flags.data_root is not None or getattr(flags, "frames", False))
+    if flags.feats_on_device and frame_mode:
+        raise SystemExit("--feats_on_device keeps pre-extracted features on the GPU; without --feats_model (frame mode) the captioner "
+                         "reads frames through its backbone and there is no feature table")
+
+
 def main(argv=None):
     flags = build_parser().parse_args(argv)
     if flags.matmul != "f32" and (flags.feats_model is not None or (flags.data_root is None and not flags.frames)):
         raise SystemExit("--matmul fp32x3 switches the backbone's GEMMs; with --feats_model (or synthetic features) there is no backbone "
                          "in the step - the captioner trains on stored features")
+    require_feature_mode(flags)
     data_train, data_val, data_test, model, translator = build(flags)
     save_dir = os.path.join(flags.root, flags.model_id)
     os.makedirs(save_dir, exist_ok=True)
@@ -311,7 +338,7 @@ def main(argv=None):
     hist = train(data_train, data_val, data_test, model, translator, flags.epochs, flags.batch_size, lr=flags.lr,
                  lr_update_factor=flags.lr_update_factor, dropout=flags.dropout, num_buckets=flags.num_buckets,
                  test_batch_size=flags.test_batch_size, start_epoch=start_epoch, save_dir=save_dir,
-                 freeze_backbone=flags.freeze_backbone, matmul=flags.matmul, frame_size=flags.data_shape if getattr(model, "src_embed", None) is not None else None)
+                 freeze_backbone=flags.freeze_backbone, matmul=flags.matmul, feats_on_device=flags.feats_on_device, frame_size=flags.data_shape if getattr(model, "src_embed", None) is not None else None)
     if not hist:
         print("[Finished] nothing to do: {} epochs are on disk".format(start_epoch))
         return 0

@@ -38,3 +38,13 @@ class BeamSearchTranslator:
         cap = self._model._captioner(self._beam_size, self._max_length, b, t)
         cap.encode(src, vl.to(src.device))                                            # translation.py:76-78
         return cap.beam_search(self._bos_id, self._eos_id, self._scorer._alpha, self._scorer._K, self._max_length)
+
+    def translate_rows(self, table, idx, valid_length):
+        """``translate`` from a device-resident feature table: ``idx`` (B, T) names each clip step's row of ``table`` (rows, F), -1
+        behind a clip's end (``GNMTCaptioner.encode_rows``).  Feature mode only; same outputs as ``translate`` on the padded batch."""
+        if getattr(self._model, "src_embed", None) is not None:
+            raise ValueError("translate_rows: a model with a src_embed reads frames; the feature table serves feature mode only")
+        b, t = (tuple(idx.shape) if hasattr(idx, "shape") else np.asarray(idx).shape)[:2]
+        cap = self._model._captioner(self._beam_size, self._max_length, b, t)
+        cap.encode_rows(table, idx, valid_length)
+        return cap.beam_search(self._bos_id, self._eos_id, self._scorer._alpha, self._scorer._K, self._max_length)
