@@ -179,7 +179,9 @@ int tn_dense_destroy(tn_dense *d);
  * LSTM [i,f,g,o].  x (B,T,F) fp32 -> seq (B,T,2H) fp32 = concat(fwd,bwd);
  * zero initial state.  valid_len (B,) int32 or NULL: steps >= valid_len are
  * skipped and emit zeros; the reverse direction starts at valid_len-1.
- * h_last/c_last (2,B,H) fp32 or NULL receive the final states [fwd,bwd]. */
+ * h_last/c_last (2,B,H) fp32 or NULL receive the final states [fwd,bwd].
+ * hidden % 4 == 0 and gates*hidden <= 2048 (gates 3 GRU / 4 LSTM: GRU up to 680, LSTM up to 512); past gates*hidden = 1024
+ * the recurrence runs two gate rows per thread and streams W_hh every step (docs/kernels.md). */
 int tn_birnn_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int hidden, const tn_param *params,
                     int n_params, const char *prefix, int bidirectional, int max_rows, tn_birnn **out);
 int tn_birnn_forward(tn_birnn *r, const float *x, int batch, int steps, const int32_t *valid_len,
@@ -251,7 +253,9 @@ int tn_temporal_pool(tn_ctx *ctx, const float *x, int batch, int steps, int feat
  * project: feats (rows, F) fp32 DEVICE, rows <= max_rows; one project serves any number of forward calls.
  * forward: centre / lo / hi (samples,) int32 DEVICE, samples <= max_samples; pooled (samples, 2H) fp32 or NULL, logits
  * (samples, classes) fp32, DEVICE.  forward before project, nulls, rows / samples over the handle's limits and window or
- * stride < 1 are TN_ERR_INVALID.  Neither call allocates. */
+ * stride < 1 are TN_ERR_INVALID.  Neither call allocates.
+ * The windowed recurrent kernel keeps one gate row per thread: gates*hidden <= 1024 here (GRU 340, LSTM 256), not the 2048 of
+ * tn_birnn_create / tn_head_create; dense windowed evaluation of a wider head is refused at create. */
 typedef struct tn_window_head tn_window_head;
 int tn_window_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int hidden, int classes, const tn_param *params,
                           int n_params, const char *rnn_prefix, const char *dense_prefix, int max_rows, int max_samples,
@@ -274,7 +278,8 @@ int tn_temporal_pool_windows(tn_ctx *ctx, const float *feats, int rows, int feat
  * Parameters use the Gluon names (<rnn_prefix>{l0,r0}_{i2h,h2h}_{weight,bias}, <dense_prefix>{weight,bias}).
  * forward_backward leaves d(sum of per-sample losses)/d(param) in the gradient buffer; the caller may all-reduce
  * that buffer over ranks (tn_head_buffers gives the flat device arrays) before tn_head_sgd_step, whose update is
- * MXNet's sgd_mom_update: mom = momentum*mom - lr*(rescale_grad*grad + wd*w); w += mom. */
+ * MXNet's sgd_mom_update: mom = momentum*mom - lr*(rescale_grad*grad + wd*w); w += mom.
+ * hidden % 4 == 0 and gates*hidden <= 2048, as tn_birnn_create. */
 typedef struct tn_head tn_head;
 int tn_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int hidden, int classes, const tn_param *params,
                    int n_params, const char *rnn_prefix, const char *dense_prefix, int max_batch, int max_steps, tn_head **out);
@@ -384,7 +389,8 @@ int tn_gnmt_trainer_create(tn_ctx *ctx, const tn_param *params, int n_params, co
 /* Any layer count the inference handle serves (tn_gnmt_create_ex): num_layers >= 2, 0 <= num_bi_layers < num_layers, flags =
  * TN_GNMT_USE_RESIDUAL or 0 - the arguments the reference passes into the model it trains (train_gnmt.py:58-61,223-227;
  * models/captioning/gnmt.py:71-111,153-157,393-396).  Parameter names: enc_rnn{i}_l_ / _r_ (bidirectional layers), enc_rnn{i}_,
- * dec_rnn{j}_.  tn_gnmt_trainer_create = (2, 1, 0), the reference's flag defaults. */
+ * dec_rnn{j}_.  tn_gnmt_trainer_create = (2, 1, 0), the reference's flag defaults.  hidden % 4 == 0 and gates*hidden <= 2048
+ * (--num_hidden up to 680 with GRU cells, 512 with LSTM cells), the encoder's bound as in tn_birnn_create. */
 int tn_gnmt_trainer_create_ex(tn_ctx *ctx, const tn_param *params, int n_params, const char *prefix, tn_rnn_kind cell_kind,
                               int input_size, int hidden, int embed, int vocab, int num_layers, int num_bi_layers, int flags,
                               int max_batch, int max_src_len, int max_tgt_len, tn_gnmt_trainer **out);

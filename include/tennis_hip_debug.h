@@ -172,6 +172,20 @@ int tn_dbg_rows_pad_skip(int on);
  * stream form (H = 256 at nb = 1).  Host arithmetic only: touches no device. */
 int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int *kr, int *big);
 
+/* The dispatch policy of the wide recurrent kernels (csrc/rnn.h rnn_wide_route), which serve 1024 < gates*H <= 2048 with two gate rows
+ * per thread: *threads the block (whole waves, <= 1024), *rows the gate rows per thread (2; row j + *threads is guarded against
+ * gates*H), *nb batch rows per workgroup (1 | 4, the threshold of tn_dbg_rnn_route), *lds_fwd / *lds_bwd the dynamic LDS bytes of the
+ * forward kernel and of the cell's BPTT kernel.  Refuses gates*H <= 1024 (tn_dbg_rnn_route answers for those) and > 2048.  Host
+ * arithmetic only: touches no device. */
+int tn_dbg_rnn_wide_route(int gates, int B, int H, int dirs, int *threads, int *rows, int *nb, int64_t *lds_fwd, int64_t *lds_bwd);
+/* on = 1: every recurrent launch of the process (forward and BPTT) runs the wide kernels, also at gates*H <= 1024, where they give
+ * the bits of the default kernels - which is what the hook is there to show; on = 0 (the default) restores the policy.  Process-wide,
+ * not synchronised with launches in flight.  A test hook, not for production use: the wide kernels keep nothing of W_hh on chip. */
+int tn_dbg_rnn_force_wide(int on);
+/* *count: how many launches of the process took the wide recurrent kernels so far (forward and BPTT together), so that a test can tell
+ * which family served a call. */
+int tn_dbg_rnn_wide_launches(int64_t *count);
+
 /* Which kernel families the fp16 DenseNet-121 encoder launches for an input size, create flags (0 | TN_ENC_EXACT_WEIGHTS; the TN_*
  * switches are read from the environment as tn_densenet121_create_ex reads them), a batch and a pass (calibrate: the layer-wise pass
  * of tn_densenet121_input_means): what tn_densenet121_profile would fill for such an encoder - name, launches, flops and bytes in

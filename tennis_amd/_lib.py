@@ -187,6 +187,10 @@ _SIGS = {
                                      C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_gemm_tn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
     "tn_dbg_gemm_nn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tn_dbg_rnn_wide_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tn_dbg_rnn_force_wide": (C.c_int, [C.c_int]),
+    "tn_dbg_rnn_wide_launches": (C.c_int, [C.POINTER(C.c_int64)]),
     "tn_dbg_rnn_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tn_dbg_encoder_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TnKernelStat), C.c_int, C.POINTER(C.c_int)]),
     "tn_dbg_trainer_params": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p, C.c_char_p, C.POINTER(TnParamRow), C.c_int,

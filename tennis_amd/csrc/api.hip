@@ -108,7 +108,7 @@ extern "C" int tn_birnn_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, in
   TN_REQUIRE(kind == TN_RNN_GRU || kind == TN_RNN_LSTM, "tn_birnn_create: unknown cell kind");
   TN_REQUIRE(input_size > 0 && hidden > 0 && hidden % 4 == 0 && max_rows > 0, "tn_birnn_create: bad shape");
   const int G = kind == TN_RNN_GRU ? 3 : 4;
-  TN_REQUIRE(G * hidden <= 1024, "tn_birnn_create: gates*hidden must be <= 1024");
+  TN_REQUIRE(G * hidden <= 2048, "tn_birnn_create: gates*hidden must be <= 2048");
   TN_ON_DEVICE(ctx->device);
   const std::string pre(prefix_c);
   ParamMap pm(params, n_params);
@@ -200,7 +200,8 @@ extern "C" int tn_window_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_si
   TN_REQUIRE(kind == TN_RNN_GRU || kind == TN_RNN_LSTM, "tn_window_head_create: unknown cell kind");
   const int G = kind == TN_RNN_GRU ? 3 : 4;
   TN_REQUIRE(input_size > 0 && hidden > 0 && hidden % 4 == 0 && G * hidden <= 1024 && classes > 0 && max_rows > 0 &&
-                 max_samples > 0, "tn_window_head_create: bad shape (gates*hidden must be <= 1024, hidden % 4 == 0)");
+                 max_samples > 0, "tn_window_head_create: bad shape (the windowed kernel serves gates*hidden <= 1024, hidden % 4 == 0; dense windowed "
+                 "evaluation of a wider head is not supported)");
   TN_ON_DEVICE(ctx->device);
   ParamMap pm(params, n_params);
   const int F = input_size, H = hidden, C = classes, GH = G * hidden;
@@ -313,8 +314,8 @@ extern "C" int tn_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int
   TN_REQUIRE(ctx && params && rnn_prefix && dense_prefix && out, "tn_head_create: null argument");
   TN_REQUIRE(kind == TN_RNN_GRU || kind == TN_RNN_LSTM, "tn_head_create: type must be 'gru' or 'lstm'");
   const int G = kind == TN_RNN_GRU ? 3 : 4;
-  TN_REQUIRE(input_size > 0 && hidden > 0 && hidden % 4 == 0 && G * hidden <= 1024 && classes > 0 && max_batch > 0 &&
-                 max_steps > 0, "tn_head_create: bad shape (gates*hidden must be <= 1024, hidden % 4 == 0)");
+  TN_REQUIRE(input_size > 0 && hidden > 0 && hidden % 4 == 0 && G * hidden <= 2048 && classes > 0 && max_batch > 0 &&
+                 max_steps > 0, "tn_head_create: bad shape (gates*hidden must be <= 2048, hidden % 4 == 0)");
   TN_ON_DEVICE(ctx->device);
   const int F = input_size, H = hidden, C = classes, GH = G * hidden;
   tn_head *h = new tn_head();

@@ -1668,8 +1668,8 @@ extern "C" int tn_gnmt_trainer_create_ex(tn_ctx *ctx, const tn_param *params, in
   TN_REQUIRE(num_layers >= 2 && num_layers <= 8 && num_bi_layers >= 0 && num_bi_layers < num_layers,
              "tn_gnmt_trainer_create: need 2 <= num_layers <= 8 and 0 <= num_bi_layers < num_layers");
   const int G_ = cell_kind == TN_RNN_GRU ? 3 : 4;
-  TN_REQUIRE(input_size > 0 && hidden > 0 && hidden % 4 == 0 && G_ * hidden <= 1024 && embed > 0 && vocab > 1 && max_batch > 0 &&
-                 max_src_len > 0 && max_tgt_len > 1, "tn_gnmt_trainer_create: bad shape (gates*hidden <= 1024, hidden % 4 == 0)");
+  TN_REQUIRE(input_size > 0 && hidden > 0 && hidden % 4 == 0 && G_ * hidden <= 2048 && embed > 0 && vocab > 1 && max_batch > 0 &&
+                 max_src_len > 0 && max_tgt_len > 1, "tn_gnmt_trainer_create: bad shape (gates*hidden <= 2048, hidden % 4 == 0)");
   TN_ON_DEVICE(ctx->device);
   tn_gnmt_trainer *t = new tn_gnmt_trainer();
   t->ctx = ctx; t->F = input_size; t->H = hidden; t->E = embed; t->V = vocab; t->maxB = max_batch; t->maxT = max_src_len;

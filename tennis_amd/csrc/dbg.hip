@@ -507,6 +507,30 @@ extern "C" int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int 
   return TN_OK;
 }
 
+// The wide recurrent kernels' dispatch policy (rnn.h rnn_wide_route) for the shapes that need it, 1024 < gates*H <= 2048; host arithmetic
+// only, no device is touched
+extern "C" int tn_dbg_rnn_wide_route(int gates, int B, int H, int dirs, int *threads, int *rows, int *nb, int64_t *lds_fwd, int64_t *lds_bwd) {
+  TN_REQUIRE(threads && rows && nb && lds_fwd && lds_bwd, "tn_dbg_rnn_wide_route: null argument");
+  TN_REQUIRE(gates == 3 || gates == 4, "tn_dbg_rnn_wide_route: gates must be 3 or 4");
+  TN_REQUIRE(B > 0 && (dirs == 1 || dirs == 2) && H > 0 && gates * H > 1024 && gates * H <= 2048 && H % 4 == 0,
+             "tn_dbg_rnn_wide_route: gates*hidden must be in (1024, 2048], hidden % 4 == 0, batch > 0, dirs 1 or 2");
+  const tn_rnn_wide_route r = rnn_wide_route(gates, B, H, dirs);
+  *threads = r.threads; *rows = r.rows; *nb = r.nb; *lds_fwd = (int64_t)r.lds_fwd; *lds_bwd = (int64_t)r.lds_bwd;
+  return TN_OK;
+}
+
+// Test hook: every recurrent launch of the process takes the wide kernels, the shapes the one-row-per-thread kernels serve included
+extern "C" int tn_dbg_rnn_force_wide(int on) {
+  rnn_set_force_wide(on != 0);
+  return TN_OK;
+}
+
+extern "C" int tn_dbg_rnn_wide_launches(int64_t *count) {
+  TN_REQUIRE(count, "tn_dbg_rnn_wide_launches: null argument");
+  *count = (int64_t)rnn_wide_launches();
+  return TN_OK;
+}
+
 // The parameter table of a training handle, from the builder its create calls (param_table.h); host arithmetic only, no device
 extern "C" int tn_dbg_trainer_params(int which, const int *dims, int n_dims, const char *prefix_a, const char *prefix_b, tn_param_row *rows,
                                      int max_rows, int *n_rows, int64_t *numel, int64_t *state_numel) {

@@ -17,6 +17,33 @@ inline tn_rnn_route rnn_route(int gates, int B, int H, int dirs) {
   r.big = r.nb == 1 && H == 256;
   return r;
 }
+// The wide recurrence, 1024 < gates*H <= 2048 (LSTM up to H = 512, GRU up to H = 680): a workgroup cannot give every gate row a thread
+// of its own, so a thread owns `rows` = 2 of them, j and j + threads (the second one guarded against gates*H).  Like rnn_route the one
+// policy of the forward kernel (rnn.hip) and of the BPTT kernels (train.hip), so that both agree on the rows per workgroup:
+//   threads  the block: half the gate rows, rounded up to whole waves (<= 1024)
+//   rows     gate rows per thread (2)
+//   nb       batch rows per workgroup, rnn_route's threshold: 4 when that still gives every CU a workgroup, else 1
+//   lds_fwd  dynamic LDS of the forward kernel, h | gates | c
+//   lds_bwd  ... of the cell's BPTT kernel, dh (| dc) | pre-activation gradients | partial sums; above 64 KiB at nb = 4 from H = 412
+//            (LSTM) / 588 (GRU): the launcher raises the kernel's limit
+// The arithmetic also holds for gates*H <= 1024, which only the test hook tn_dbg_rnn_force_wide sends this way.
+struct tn_rnn_wide_route { int threads, rows, nb; size_t lds_fwd, lds_bwd; };
+inline tn_rnn_wide_route rnn_wide_route(int gates, int B, int H, int dirs) {
+  const int GH = gates * H;
+  tn_rnn_wide_route r;
+  r.rows = 2;
+  r.threads = ((GH + 1) / 2 + 63) / 64 * 64;
+  r.nb = ((B + 3) / 4) * dirs >= 256 ? 4 : 1;
+  r.lds_fwd = (size_t)(r.nb * H * 2 + r.nb * GH) * sizeof(float);
+  r.lds_bwd = (size_t)(r.nb * H * (gates == 4 ? 2 : 1) + 2 * r.nb * GH) * sizeof(float);
+  return r;
+}
+// true for the shapes the wide kernels serve: every gates*H > 1024, and every shape while tn_dbg_rnn_force_wide is on
+bool rnn_takes_wide(int gates, int H);
+void rnn_set_force_wide(bool on);
+// launches of the wide kernels so far, forward and BPTT (what tn_dbg_rnn_wide_launches reports: a test can tell which family ran)
+void rnn_count_wide_launch();
+long rnn_wide_launches();
 int launch_rnn_recurrent(int gates, const float *gi, int ldgi, const float *whT, const float *bh,
                          const int32_t *valid_len, float *seq, int ldo, float *h_last, float *c_last, int B, int T,
                          int H, int dirs, hipStream_t s, float *save = nullptr);

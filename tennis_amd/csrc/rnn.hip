@@ -13,7 +13,8 @@
 //       gate non-linearities.  valid_length semantics of
 //       BidirectionalCell.unroll(valid_length=...) [EXT]: steps >= valid_len
 //       do not update state and emit zeros; the reverse pass starts at
-//       valid_len-1.
+//       valid_len-1.  Past G*H = 1024 gate rows (up to 2048: LSTM H = 512,
+//       GRU H = 680) a thread owns two rows: rnn_recurrent_wide_kernel.
 #include "common.h"
 #include "linear.h"
 #include "rnn.h"
@@ -240,6 +241,141 @@ __global__ __launch_bounds__(MAXT) void rnn_recurrent_big_kernel(
   }
 }
 
+// The same recurrence for 1024 < G*H <= 2048 (LSTM up to H = 512, GRU up to H = 680), where a workgroup has fewer threads than gate
+// rows: a thread owns TWO rows, j and j + blockDim.x (rnn.h rnn_wide_route: the block is half the rows, in whole waves).  A row past
+// G*H reads the last column and stores nothing, so the loops carry no branch.  Both columns are streamed with 16 k-values in flight
+// each; the float4 of h read from LDS serves both rows.  Nothing of W_hh stays in registers or LDS: per step a workgroup streams all
+// 4*G*H*H bytes (3 MB at GRU H = 512, 4 MB at LSTM H = 512) from L2 / Infinity Cache, and that stream bounds the step.
+// Per row the dot product is that of rnn_recurrent_kernel - one accumulator, the bias first, k ascending - and the cell phase is its
+// loop with the block size as stride: results are bit-identical wherever both kernels can run.
+template <int G, int NB>
+__global__ __launch_bounds__(1024) void rnn_recurrent_wide_kernel(
+    const float *__restrict__ gi, int ldgi, const float *__restrict__ whT, const float *__restrict__ bh,
+    const int32_t *__restrict__ valid_len, float *__restrict__ seq, int ldo, float *__restrict__ h_last,
+    float *__restrict__ c_last, float *__restrict__ save, int B, int T, int H) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int GH = G * H, nt = blockDim.x;
+  float *hs = lds;                 // [NB][H]
+  float *gh = hs + NB * H;         // [NB][GH]
+  float *cs = gh + NB * GH;        // [NB][H] (LSTM)
+  const int j = threadIdx.x;
+  const int dir = blockIdx.y;
+  const int b0 = blockIdx.x * NB;
+  const int row[2] = {j, j + nt};                                 // gate rows
+  const bool own[2] = {row[0] < GH, row[1] < GH};
+  const float *wcol[2];
+  float bj[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int rr = min(row[r], GH - 1);
+    wcol[r] = whT + (long)dir * H * GH + rr;
+    bj[r] = bh[dir * GH + rr];
+  }
+
+  for (int i = j; i < NB * H; i += nt) {
+    hs[i] = 0.f;
+    if (G == 4) cs[i] = 0.f;
+  }
+  __syncthreads();
+
+  for (int s = 0; s < T; ++s) {
+    float acc[2][NB];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int b = 0; b < NB; ++b) acc[r][b] = bj[r];
+    int k = 0;
+    for (; k + 16 <= H; k += 16) {
+      float w[2][16];
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[r][i] = wcol[r][(long)(k + i) * GH];
+#pragma unroll
+      for (int i = 0; i < 16; i += 4) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          const float4 hv = *(const float4 *)(hs + b * H + k + i);
+#pragma unroll
+          for (int r = 0; r < 2; ++r) {
+            acc[r][b] = fmaf(w[r][i + 0], hv.x, acc[r][b]);
+            acc[r][b] = fmaf(w[r][i + 1], hv.y, acc[r][b]);
+            acc[r][b] = fmaf(w[r][i + 2], hv.z, acc[r][b]);
+            acc[r][b] = fmaf(w[r][i + 3], hv.w, acc[r][b]);
+          }
+        }
+      }
+    }
+    for (; k < H; k += 4) {
+      float w[2][4];
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[r][i] = wcol[r][(long)(k + i) * GH];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const float4 hv = *(const float4 *)(hs + b * H + k);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          acc[r][b] = fmaf(w[r][0], hv.x, acc[r][b]);
+          acc[r][b] = fmaf(w[r][1], hv.y, acc[r][b]);
+          acc[r][b] = fmaf(w[r][2], hv.z, acc[r][b]);
+          acc[r][b] = fmaf(w[r][3], hv.w, acc[r][b]);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+      if (own[r]) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) gh[b * GH + row[r]] = acc[r][b];
+      }
+    __syncthreads();
+    for (int idx = j; idx < NB * H; idx += nt) {
+      const int b = idx / H, u = idx - b * H;
+      const int bg = b0 + b;
+      if (bg >= B) continue;
+      const int vlen = valid_len ? valid_len[bg] : T;
+      if (s >= vlen) continue;
+      const int ti = dir ? (vlen - 1 - s) : s;
+      const float *g = gi + ((long)bg * T + ti) * ldgi + dir * GH;
+      const float *q = gh + b * GH;
+      float hn;
+      if (G == 3) {
+        const float r = sigmoidf_(g[u] + q[u]);
+        const float z = sigmoidf_(g[H + u] + q[H + u]);
+        const float n = tanhf(g[2 * H + u] + r * q[2 * H + u]);
+        hn = (1.f - z) * n + z * hs[idx];
+        if (save) {
+          float *sv = save + ((long)dir * B * T + (long)bg * T + ti) * (4 * H);
+          sv[u] = r; sv[H + u] = z; sv[2 * H + u] = n; sv[3 * H + u] = q[2 * H + u];
+        }
+      } else {
+        const float ig = sigmoidf_(g[u] + q[u]);
+        const float fg = sigmoidf_(g[H + u] + q[H + u]);
+        const float gg = tanhf(g[2 * H + u] + q[2 * H + u]);
+        const float og = sigmoidf_(g[3 * H + u] + q[3 * H + u]);
+        const float c2 = fg * cs[idx] + ig * gg;
+        cs[idx] = c2;
+        hn = og * tanhf(c2);
+        if (save) {
+          float *sv = save + ((long)dir * B * T + (long)bg * T + ti) * (5 * H);
+          sv[u] = ig; sv[H + u] = fg; sv[2 * H + u] = gg; sv[3 * H + u] = og; sv[4 * H + u] = c2;
+        }
+      }
+      hs[idx] = hn;
+      seq[((long)bg * T + ti) * ldo + dir * H + u] = hn;
+    }
+    __syncthreads();
+  }
+  for (int idx = j; idx < NB * H; idx += nt) {
+    const int b = idx / H, u = idx - b * H;
+    if (b0 + b >= B) continue;
+    if (h_last) h_last[((long)dir * B + b0 + b) * H + u] = hs[idx];
+    if (c_last && G == 4) c_last[((long)dir * B + b0 + b) * H + u] = cs[idx];
+  }
+}
+
 __global__ void temporal_pool_kernel(const float *__restrict__ x, int B, int T, int F, int kind,
                                      float *__restrict__ y) {
   const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -269,11 +405,33 @@ __global__ void prf1_kernel(const float *__restrict__ logits, const int32_t *__r
 
 }  // namespace
 
+// tn_dbg_rnn_force_wide: a test hook, off unless a test turns it on (process-wide; not synchronised with launches in flight)
+static bool g_rnn_force_wide = false;
+void rnn_set_force_wide(bool on) { g_rnn_force_wide = on; }
+bool rnn_takes_wide(int gates, int H) { return gates * H > 1024 || g_rnn_force_wide; }
+static std::atomic<long> g_rnn_wide_launches{0};
+void rnn_count_wide_launch() { g_rnn_wide_launches.fetch_add(1, std::memory_order_relaxed); }
+long rnn_wide_launches() { return g_rnn_wide_launches.load(std::memory_order_relaxed); }
+
 int launch_rnn_recurrent(int gates, const float *gi, int ldgi, const float *whT, const float *bh,
                          const int32_t *valid_len, float *seq, int ldo, float *h_last, float *c_last, int B, int T,
                          int H, int dirs, hipStream_t s, float *save) {
   TN_REQUIRE(gates == 3 || gates == 4, "rnn: gates must be 3 or 4");
-  TN_REQUIRE(gates * H <= 1024 && H % 4 == 0, "rnn: gates*hidden must be <= 1024 and hidden % 4 == 0");
+  TN_REQUIRE(H > 0 && gates * H <= 2048 && H % 4 == 0, "rnn: gates*hidden must be <= 2048 and hidden % 4 == 0");
+  if (rnn_takes_wide(gates, H)) {   // two gate rows per thread (rnn.h rnn_wide_route)
+    const tn_rnn_wide_route wr = rnn_wide_route(gates, B, H, dirs);
+    const dim3 wgrid((B + wr.nb - 1) / wr.nb, dirs), wblock(wr.threads);
+    // (the forward kernel's LDS stays below the 64 KiB a launch may ask for unraised: 54 KiB at GRU H = 680, four rows)
+#define TN_RNN_WIDE(G_, NB_)                                                                                              \
+  hipLaunchKernelGGL((rnn_recurrent_wide_kernel<G_, NB_>), wgrid, wblock, wr.lds_fwd, s, gi, ldgi, whT, bh, valid_len, seq, \
+                     ldo, h_last, c_last, save, B, T, H)
+    if (gates == 3) { if (wr.nb == 4) TN_RNN_WIDE(3, 4); else TN_RNN_WIDE(3, 1); }
+    else { if (wr.nb == 4) TN_RNN_WIDE(4, 4); else TN_RNN_WIDE(4, 1); }
+#undef TN_RNN_WIDE
+    rnn_count_wide_launch();
+    TN_HIP_CHECK(hipGetLastError());
+    return TN_OK;
+  }
   const int threads = gates * H;
   const tn_rnn_route route = rnn_route(gates, B, H, dirs);   // rows per workgroup / register-resident prefix / big form (rnn.h)
   const int nb = route.nb, kr = route.kr;

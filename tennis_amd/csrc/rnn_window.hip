@@ -228,7 +228,7 @@ int launch_rnn_window(int gates, const float *gi, int ldgi, int rows, const floa
                       const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, int nb,
                       hipStream_t s) {
   TN_REQUIRE(gates == 3 || gates == 4, "rnn_window: gates must be 3 or 4");
-  TN_REQUIRE(gates * H <= 1024 && H % 4 == 0, "rnn_window: gates*hidden must be <= 1024 and hidden % 4 == 0");
+  TN_REQUIRE(gates * H <= 1024 && H % 4 == 0, "rnn_window: the windowed kernel serves gates*hidden <= 1024 and hidden % 4 == 0");
   TN_REQUIRE(rows > 0 && B > 0 && T > 0 && stride > 0, "rnn_window: bad shape");
   if (nb == 0) nb = rnn_window_default_nb(gates);
   if ((size_t)nb * (2 + gates) * H * sizeof(float) > 64 * 1024) nb = 4;      // (the LDS a workgroup may ask for without an attribute)

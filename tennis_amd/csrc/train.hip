@@ -319,6 +319,207 @@ __global__ __launch_bounds__(MAXT) void lstm_train_bwd_kernel(const float *__res
   }
 }
 
+// ---- BPTT for 1024 < gates*H <= 2048: two gate rows per thread (rnn.h rnn_wide_route), as rnn.hip's wide forward kernel ----
+// Thread j owns the rows j and j + blockDim.x of W_hh^T's product; a row past gates*H works on the last row and stores nothing.
+// Both W_hh columns are streamed with 16 values in flight each.  Per row: one accumulator from 0, jj ascending - the sums of the
+// kernels above, bit for bit.
+template <int NB>
+__device__ __forceinline__ void bptt_dot_two_rows(float (&acc)[2][NB], const float *const (&wrow)[2], const int (&gofs)[2],
+                                                  const float *dgs, int GH, int H) {
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[r][b] = 0.f;
+  int jj = 0;
+  for (; jj + 16 <= H; jj += 16) {
+    float w[2][16];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) w[r][i] = wrow[r][(long)(jj + i) * H];
+#pragma unroll
+    for (int i = 0; i < 16; i += 4) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          const float4 dv = *(const float4 *)(dgs + b * GH + gofs[r] + jj + i);
+          acc[r][b] = fmaf(w[r][i + 0], dv.x, acc[r][b]);
+          acc[r][b] = fmaf(w[r][i + 1], dv.y, acc[r][b]);
+          acc[r][b] = fmaf(w[r][i + 2], dv.z, acc[r][b]);
+          acc[r][b] = fmaf(w[r][i + 3], dv.w, acc[r][b]);
+        }
+      }
+    }
+  }
+  for (; jj < H; jj += 4) {
+    float w[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) w[r][i] = wrow[r][(long)(jj + i) * H];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const float4 dv = *(const float4 *)(dgs + b * GH + gofs[r] + jj);
+        acc[r][b] = fmaf(w[r][0], dv.x, acc[r][b]);
+        acc[r][b] = fmaf(w[r][1], dv.y, acc[r][b]);
+        acc[r][b] = fmaf(w[r][2], dv.z, acc[r][b]);
+        acc[r][b] = fmaf(w[r][3], dv.w, acc[r][b]);
+      }
+    }
+  }
+}
+
+// gru_train_bwd_kernel's contract and LDS layout; the element-wise phases are its loops with the block size as stride
+template <int NB>
+__global__ __launch_bounds__(1024) void gru_train_bwd_wide_kernel(const float *__restrict__ seq, const float *__restrict__ gates,
+                                     const float *__restrict__ dseq, const float *__restrict__ wh, float *__restrict__ dgi,
+                                     float *__restrict__ dgh, float *__restrict__ hprev, int B, int T, int H, int dirs,
+                                     const int32_t *__restrict__ valid_len, const float *__restrict__ dh_last) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int GH = 3 * H, nt = blockDim.x;
+  float *dh = lds;                  // [NB][H]
+  float *dgs = dh + NB * H;         // [NB][3H]
+  float *part = dgs + NB * GH;      // [NB][3][H]
+  const int j = threadIdx.x, dir = blockIdx.y, b0 = blockIdx.x * NB;
+  const bool own[2] = {j < GH, j + nt < GH};
+  int gofs[2], pofs[2];             // where the row's gate block starts in dgs; where its sum goes in a batch row's part
+  const float *wrow[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int rr = min(j + r * nt, GH - 1), g = rr / H, u = rr - g * H;
+    gofs[r] = g * H;
+    pofs[r] = rr;                   // (b * 3 + g) * H + u = b * GH + rr
+    wrow[r] = wh + (long)dir * GH * H + (long)g * H * H + u;   // W_hh[g*H + jj][u], jj = 0..H-1
+  }
+  for (int i = j; i < NB * H; i += nt) dh[i] = 0.f;
+  __syncthreads();
+  for (int s = T - 1; s >= 0; --s) {          // reverse of the direction's own walking order
+    for (int idx = j; idx < NB * H; idx += nt) {
+      const int b = idx / H, uu = idx - b * H, bg = b0 + b;
+      float d_r = 0.f, d_z = 0.f, d_n = 0.f, d_nr = 0.f, dhp = 0.f, hp = 0.f;
+      const int vlen = bg < B ? (valid_len ? valid_len[bg] : T) : 0;
+      if (s < vlen) {
+        const int t = dir ? vlen - 1 - s : s;       // the reverse direction starts at the row's last valid step
+        const int tp = dir ? t + 1 : t - 1;         // where h_prev of this step was emitted
+        const long row = (long)bg * T + t;
+        const float *sv = gates + ((long)dir * B * T + row) * (4 * H);
+        const float r = sv[uu], z = sv[H + uu], n = sv[2 * H + uu], ghn = sv[3 * H + uu];
+        hp = s > 0 ? seq[((long)bg * T + tp) * (dirs * H) + dir * H + uu] : 0.f;
+        const float carry = (s == vlen - 1 && dh_last) ? dh_last[((long)dir * B + bg) * H + uu] : dh[idx];
+        const float dht = carry + dseq[row * (dirs * H) + dir * H + uu];
+        const float dn = dht * (1.f - z), dz = dht * (hp - n);
+        dhp = dht * z;
+        d_n = dn * (1.f - n * n);
+        d_z = dz * z * (1.f - z);
+        d_r = d_n * ghn * r * (1.f - r);
+        d_nr = d_n * r;
+        float *o1 = dgi + row * (dirs * GH) + dir * GH, *o2 = dgh + row * (dirs * GH) + dir * GH;
+        o1[uu] = d_r; o1[H + uu] = d_z; o1[2 * H + uu] = d_n;
+        o2[uu] = d_r; o2[H + uu] = d_z; o2[2 * H + uu] = d_nr;
+        hprev[((long)dir * B * T + row) * H + uu] = hp;
+      }
+      dgs[b * GH + uu] = d_r; dgs[b * GH + H + uu] = d_z; dgs[b * GH + 2 * H + uu] = d_nr;
+      dh[idx] = dhp;
+    }
+    __syncthreads();
+    float acc[2][NB];
+    bptt_dot_two_rows<NB>(acc, wrow, gofs, dgs, GH, H);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+      if (own[r]) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) part[b * GH + pofs[r]] = acc[r][b];
+      }
+    __syncthreads();
+    for (int idx = j; idx < NB * H; idx += nt) {
+      const int b = idx / H, uu = idx - b * H;
+      dh[idx] += part[(b * 3 + 0) * H + uu] + part[(b * 3 + 1) * H + uu] + part[(b * 3 + 2) * H + uu];
+    }
+    __syncthreads();
+  }
+}
+
+// lstm_train_bwd_kernel's contract and LDS layout, two gate rows per thread
+template <int NB>
+__global__ __launch_bounds__(1024) void lstm_train_bwd_wide_kernel(const float *__restrict__ seq, const float *__restrict__ gates,
+                                      const float *__restrict__ dseq, const float *__restrict__ wh, float *__restrict__ dgi,
+                                      float *__restrict__ hprev, int B, int T, int H, int dirs,
+                                      const int32_t *__restrict__ valid_len, const float *__restrict__ dh_last,
+                                      const float *__restrict__ dc_last) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int GH = 4 * H, nt = blockDim.x;
+  float *dh = lds;                  // [NB][H]
+  float *dc = dh + NB * H;          // [NB][H]
+  float *dgs = dc + NB * H;         // [NB][4H]
+  float *part = dgs + NB * GH;      // [NB][4][H]
+  const int j = threadIdx.x, dir = blockIdx.y, b0 = blockIdx.x * NB;
+  const bool own[2] = {j < GH, j + nt < GH};
+  int gofs[2], pofs[2];
+  const float *wrow[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int rr = min(j + r * nt, GH - 1), g = rr / H, u = rr - g * H;
+    gofs[r] = g * H;
+    pofs[r] = rr;                   // (b * 4 + g) * H + u = b * GH + rr
+    wrow[r] = wh + (long)dir * GH * H + (long)g * H * H + u;
+  }
+  for (int i = j; i < NB * H; i += nt) { dh[i] = 0.f; dc[i] = 0.f; }
+  __syncthreads();
+  for (int s = T - 1; s >= 0; --s) {
+    for (int idx = j; idx < NB * H; idx += nt) {
+      const int b = idx / H, uu = idx - b * H, bg = b0 + b;
+      float d_i = 0.f, d_f = 0.f, d_g = 0.f, d_o = 0.f, dcp = 0.f;
+      const int vlen = bg < B ? (valid_len ? valid_len[bg] : T) : 0;
+      if (s < vlen) {
+        const int t = dir ? vlen - 1 - s : s;
+        const int tp = dir ? t + 1 : t - 1;
+        const long row = (long)bg * T + t;
+        const float *sv = gates + ((long)dir * B * T + row) * (5 * H);
+        const float ig = sv[uu], fg = sv[H + uu], gg = sv[2 * H + uu], og = sv[3 * H + uu], c2 = sv[4 * H + uu];
+        float hp = 0.f, cp = 0.f;
+        if (s > 0) {
+          const long rp = (long)bg * T + tp;
+          hp = seq[rp * (dirs * H) + dir * H + uu];
+          cp = gates[((long)dir * B * T + rp) * (5 * H) + 4 * H + uu];
+        }
+        const bool lastp = s == vlen - 1;
+        const float tc = tanhf(c2);
+        const float dht = ((lastp && dh_last) ? dh_last[((long)dir * B + bg) * H + uu] : dh[idx]) + dseq[row * (dirs * H) + dir * H + uu];
+        const float dct = ((lastp && dc_last) ? dc_last[((long)dir * B + bg) * H + uu] : dc[idx]) + dht * og * (1.f - tc * tc);
+        d_o = dht * tc * og * (1.f - og);
+        d_i = dct * gg * ig * (1.f - ig);
+        d_f = dct * cp * fg * (1.f - fg);
+        d_g = dct * ig * (1.f - gg * gg);
+        dcp = dct * fg;
+        float *o1 = dgi + row * (dirs * GH) + dir * GH;
+        o1[uu] = d_i; o1[H + uu] = d_f; o1[2 * H + uu] = d_g; o1[3 * H + uu] = d_o;
+        hprev[((long)dir * B * T + row) * H + uu] = hp;
+      }
+      dgs[b * GH + uu] = d_i; dgs[b * GH + H + uu] = d_f; dgs[b * GH + 2 * H + uu] = d_g; dgs[b * GH + 3 * H + uu] = d_o;
+      dc[idx] = dcp;
+    }
+    __syncthreads();
+    float acc[2][NB];
+    bptt_dot_two_rows<NB>(acc, wrow, gofs, dgs, GH, H);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+      if (own[r]) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) part[b * GH + pofs[r]] = acc[r][b];
+      }
+    __syncthreads();
+    for (int idx = j; idx < NB * H; idx += nt) {
+      const int b = idx / H, uu = idx - b * H;
+      dh[idx] = part[(b * 4 + 0) * H + uu] + part[(b * 4 + 1) * H + uu] + part[(b * 4 + 2) * H + uu] +
+                part[(b * 4 + 3) * H + uu];
+    }
+    __syncthreads();
+  }
+}
+
 // C[M][N] = A^T B, A [K][lda] (M columns), B [K][ldb] (N columns): the weight gradients dW = dG^T X over all B*T rows.
 // Exact-f32 MFMA 16x16x4, 64x64 tile, 4 waves each 32x32.  Both operands are k-major in memory, which is what the
 // fragments want (lane = (column, k)): rows of 64 columns are staged as they lie, no transposes.  kTnPD k-tiles of 16
@@ -563,10 +764,24 @@ int launch_scatter_pool_grad(const float *dpooled, const int32_t *arg, int B, in
   TN_LAUNCH_CHECK();
 }
 // rows per workgroup / register-resident prefix: rnn_route (rnn.h), the policy of launch_rnn_recurrent, whose `save` these kernels read
-#define TN_BPTT_DISPATCH(KERNEL, GATES, DIRS, ...)                                                                      \
+// ... and past gates*hidden = 1024 (or under tn_dbg_rnn_force_wide) rnn_wide_route: two gate rows per thread, WIDE<nb>
+#define TN_BPTT_DISPATCH(KERNEL, WIDE, GATES, DIRS, ...)                                                                \
   do {                                                                                                            \
     const int threads = GATES * H;                                                                                \
-    TN_REQUIRE(threads <= 1024 && H % 4 == 0, "train: gates*hidden must be <= 1024 and hidden % 4 == 0");        \
+    TN_REQUIRE(H > 0 && threads <= 2048 && H % 4 == 0, "train: gates*hidden must be <= 2048 and hidden % 4 == 0"); \
+    if (rnn_takes_wide(GATES, H)) {                                                                               \
+      const tn_rnn_wide_route wr = rnn_wide_route(GATES, B, H, DIRS);                                             \
+      const dim3 wgrid((B + wr.nb - 1) / wr.nb, DIRS), wblock(wr.threads);                                        \
+      if (wr.nb == 4) {          /* 80 KiB at LSTM H = 512: above what a launch may ask for unraised */           \
+        TN_SET_ATTR_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void *)WIDE<4>,                              \
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+        hipLaunchKernelGGL((WIDE<4>), wgrid, wblock, wr.lds_bwd, s, __VA_ARGS__);                                 \
+      } else {                                                                                                    \
+        hipLaunchKernelGGL((WIDE<1>), wgrid, wblock, wr.lds_bwd, s, __VA_ARGS__);                                 \
+      }                                                                                                           \
+      rnn_count_wide_launch();                                                                                    \
+      break;                                                                                                      \
+    }                                                                                                             \
     const tn_rnn_route route = rnn_route(GATES, B, H, DIRS);                                                      \
     const int nb = route.nb, kr = route.kr;                                                                       \
     const dim3 grid((B + nb - 1) / nb, DIRS), block(threads);                                                     \
@@ -587,13 +802,13 @@ int launch_scatter_pool_grad(const float *dpooled, const int32_t *arg, int B, in
 int launch_gru_train_bwd(const float *seq, const float *gates, const float *dseq, const float *wh, float *dgi,
                          float *dgh, float *hprev, int B, int T, int H, hipStream_t s, int dirs, const int32_t *valid_len,
                          const float *dh_last) {
-  TN_BPTT_DISPATCH(gru_train_bwd_kernel, 3, dirs, seq, gates, dseq, wh, dgi, dgh, hprev, B, T, H, dirs, valid_len, dh_last);
+  TN_BPTT_DISPATCH(gru_train_bwd_kernel, gru_train_bwd_wide_kernel, 3, dirs, seq, gates, dseq, wh, dgi, dgh, hprev, B, T, H, dirs, valid_len, dh_last);
   TN_LAUNCH_CHECK();
 }
 int launch_lstm_train_bwd(const float *seq, const float *gates, const float *dseq, const float *wh, float *dgi,
                           float *hprev, int B, int T, int H, hipStream_t s, int dirs, const int32_t *valid_len,
                           const float *dh_last, const float *dc_last) {
-  TN_BPTT_DISPATCH(lstm_train_bwd_kernel, 4, dirs, seq, gates, dseq, wh, dgi, hprev, B, T, H, dirs, valid_len, dh_last, dc_last);
+  TN_BPTT_DISPATCH(lstm_train_bwd_kernel, lstm_train_bwd_wide_kernel, 4, dirs, seq, gates, dseq, wh, dgi, hprev, B, T, H, dirs, valid_len, dh_last, dc_last);
   TN_LAUNCH_CHECK();
 }
 // C (M,N) = A^T B over K rows; bsc / bsh non-null: B -> relu(B * bsc[n] + bsh[n]) on the way in (a BatchNorm + ReLU that is never stored)
