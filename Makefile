@@ -9,7 +9,7 @@ HFLAGS := $(EXTRA) --offload-arch=$(ARCH) -O3 -std=c++20 -fPIC -Wall -Wno-unused
 
 all: $(OUT)
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/tennis_hip.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/tennis_hip.h include/tennis_hip_debug.h
 	$(HIPCC) $(HFLAGS) -c $< -o $@
 
 # the strip kernel pins its own schedule: SLP packing of its scalar f32 arithmetic (v_pk_add_f32 ...) only costs issue slots.
@@ -21,7 +21,7 @@ STRIP_OBJS  := $(STRIP_UNITS:%=$(CSRC)/%.o)
 ISA_DIR     := $(CSRC)/isa
 # (grouped target: one recipe makes the object AND its ISA listing)
 define STRIP_RULE
-$(CSRC)/$(1).o $(ISA_DIR)/$(1).s &: $(CSRC)/$(1).hip $(wildcard $(CSRC)/*.h) include/tennis_hip.h
+$(CSRC)/$(1).o $(ISA_DIR)/$(1).s &: $(CSRC)/$(1).hip $(wildcard $(CSRC)/*.h) include/tennis_hip.h include/tennis_hip_debug.h
 	@mkdir -p $(ISA_DIR)
 	$(HIPCC) $(HFLAGS) -fno-slp-vectorize -save-temps=obj -c $(CSRC)/$(1).hip -o $(CSRC)/$(1).o
 	@mv $(CSRC)/$(1)-hip-amdgcn-amd-amdhsa-gfx950.s $(ISA_DIR)/$(1).s

@@ -462,6 +462,33 @@ int tn_gnmt_frames_trainer_destroy(tn_gnmt_frames_trainer *t);
 int tn_gnmt_frames_trainer_set_matmul(tn_gnmt_frames_trainer *t, int mode);
 int tn_gnmt_frames_trainer_matmul_stats(tn_gnmt_frames_trainer *t, int64_t *f32_launches, int64_t *fp32x3_launches);
 
+/* ---- global-norm gradient clipping of the five training steps (opt-in) ------------------
+ * gluon.utils.clip_global_norm(grads, clip) [EXT], the call the gluonnlp script behind reference train_gnmt.py makes between
+ * loss.backward() and trainer.step(1).  The reference defines the flag (train_gnmt.py:97-98, --clip) and never applies it; so
+ * clipping is OFF after every create, and a handle that never calls set_clip runs the steps it always ran, bit for bit.
+ *   norm  = sqrt(sum over every TRAINABLE gradient element of (r g)^2)      r = rescale_grad of the sgd_step, 1 for adam_step
+ *   scale = min(1, max_norm / (norm + 1e-8))
+ *   the update runs on scale g in place of g  (SGD: mom = momentum mom - lr (r scale g + wd w);  Adam: g' = scale g)
+ * The SGD norm is taken over r g, the gradient the optimizer sees, so a threshold keeps its meaning when the batch size changes.
+ * The gradient buffers are not modified (*_buffers / read_param(gradient = 1) still show the unclipped gradient): the scale is
+ * applied inside the update kernel.  Below the threshold scale is exactly 1 and the step leaves the bits of an unclipped one.  A
+ * non-finite norm propagates as the formula says (MXNet warns and goes on).  A frozen backbone adds nothing to the norm; the
+ * two-part handles take ONE norm over backbone + head / captioner and give both parts the one scale.  The sum is a two-stage
+ * reduction in a fixed order (no atomics): equal gradients give equal bits on every rank.  No host synchronisation in a step.
+ * set_clip: max_norm 0 switches clipping off; negative or non-finite is TN_ERR_INVALID.
+ * clip_stats: the last step's norm and scale and the steps with scale < 1 since create (any pointer may be NULL); synchronises
+ * the handle's stream, so call it per epoch or log point, not per step; an error while clipping is off or before a clipped step. */
+int tn_head_set_clip(tn_head *h, float max_norm);
+int tn_head_clip_stats(tn_head *h, float *norm, float *scale, int64_t *clipped_steps);
+int tn_finetune_set_clip(tn_finetune *f, float max_norm);
+int tn_finetune_clip_stats(tn_finetune *f, float *norm, float *scale, int64_t *clipped_steps);
+int tn_cnnrnn_trainer_set_clip(tn_cnnrnn_trainer *t, float max_norm);
+int tn_cnnrnn_trainer_clip_stats(tn_cnnrnn_trainer *t, float *norm, float *scale, int64_t *clipped_steps);
+int tn_gnmt_trainer_set_clip(tn_gnmt_trainer *t, float max_norm);
+int tn_gnmt_trainer_clip_stats(tn_gnmt_trainer *t, float *norm, float *scale, int64_t *clipped_steps);
+int tn_gnmt_frames_trainer_set_clip(tn_gnmt_frames_trainer *t, float max_norm);
+int tn_gnmt_frames_trainer_clip_stats(tn_gnmt_frames_trainer *t, float *norm, float *scale, int64_t *clipped_steps);
+
 /* ---- device PRF1 confusion histogram -------------------------------------- */
 /* Replaces the argmax + per-sample python loop of PRF1.update (reference
  * metrics/vision.py:41-49).  logits (rows,classes) fp32, labels (rows,) int32;

@@ -226,6 +226,18 @@ int tn_dbg_conv_fp32x3(tn_ctx *ctx, int which, int kind, int tile, int layout, c
  * 4, or twice the gates (6 GRU / 8 LSTM).  The results do not depend on it (scripts/bench_window_head.py measures both). */
 int tn_dbg_window_head_rows_per_group(struct tn_window_head *h, int nb);
 
+/* The sum of squares behind the global-norm clipping of the training steps (csrc/train.hip, grad_sumsq_kernel), run on caller
+ * buffers: (dev, n) and (dev2, n2), DEVICE fp32, 4-byte aligned, any counts, either may be empty (NULL, 0).  *sumsq_host: the
+ * sum as the finalize kernel holds it, in double.  Synchronous.  The layout the error bound of a test follows from: a grid of
+ * TN_GRAD_SUMSQ_GRID workgroups of TN_GRAD_SUMSQ_BLOCK threads; the 16-byte-aligned body of a segment is cut into chunks of
+ * TN_GRAD_SUMSQ_CHUNK floats, chunk c goes to workgroup c % GRID, and a thread adds CHUNK / BLOCK squares of a chunk to its fp32
+ * partial serially; up to 3 floats before and 3 after the body go one each to threads of workgroup 0 (one more term per
+ * segment); the BLOCK partials of a workgroup meet in an fp32 tree, the GRID results in double. */
+#define TN_GRAD_SUMSQ_BLOCK 256
+#define TN_GRAD_SUMSQ_CHUNK 4096
+#define TN_GRAD_SUMSQ_GRID 1024
+int tn_dbg_grad_sumsq(tn_ctx *ctx, const float *dev, int64_t n, const float *dev2, int64_t n2, double *sumsq_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,17 @@ _SIGS = {
     "tn_gnmt_frames_trainer_adam_step": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float]),
     "tn_gnmt_frames_trainer_read_param": (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
     "tn_gnmt_frames_trainer_destroy": (C.c_int, [_P]),
+    "tn_head_set_clip": (C.c_int, [_P, C.c_float]),
+    "tn_head_clip_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "tn_finetune_set_clip": (C.c_int, [_P, C.c_float]),
+    "tn_finetune_clip_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "tn_cnnrnn_trainer_set_clip": (C.c_int, [_P, C.c_float]),
+    "tn_cnnrnn_trainer_clip_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "tn_gnmt_trainer_set_clip": (C.c_int, [_P, C.c_float]),
+    "tn_gnmt_trainer_clip_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "tn_gnmt_frames_trainer_set_clip": (C.c_int, [_P, C.c_float]),
+    "tn_gnmt_frames_trainer_clip_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "tn_dbg_grad_sumsq": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_double)]),
     "tn_dbg_rows_pad_skip": (C.c_int, [C.c_int]),
     "tn_dbg_gnmt_trainer_src_grad": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int]),
     "tn_gnmt_trainer_create": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

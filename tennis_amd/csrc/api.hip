@@ -424,12 +424,28 @@ extern "C" int tn_head_buffers(tn_head *h, float **params_dev, float **grads_dev
   return train_buffers("tn_head_buffers", h, params_dev, grads_dev, numel);
 }
 
+// the update alone; scale non-null: the clipped form, on the scale of a reduction the caller has queued
+static int head_sgd_update(tn_head *h, float lr, float momentum, float wd, float rescale_grad, const float *scale) {
+  int rc = launch_sgd_momentum(h->w, h->g, h->mom, h->n, lr, momentum, wd, rescale_grad, h->ctx->stream, scale);
+  if (rc) return rc;
+  return head_refresh_whT(h);
+}
+
 extern "C" int tn_head_sgd_step(tn_head *h, float lr, float momentum, float wd, float rescale_grad) {
   TN_REQUIRE(h, "tn_head_sgd_step: null handle");
   TN_ON_DEVICE(h->ctx->device);
-  int rc = launch_sgd_momentum(h->w, h->g, h->mom, h->n, lr, momentum, wd, rescale_grad, h->ctx->stream);
-  if (rc) return rc;
-  return head_refresh_whT(h);
+  if (!h->clip.on()) return head_sgd_update(h, lr, momentum, wd, rescale_grad, nullptr);
+  if (int rc = h->clip.reduce(h->ctx, h->g, h->n, nullptr, 0, rescale_grad)) return rc;
+  return head_sgd_update(h, lr, momentum, wd, rescale_grad, h->clip.scale());
+}
+
+extern "C" int tn_head_set_clip(tn_head *h, float max_norm) {
+  TN_REQUIRE(h, "tn_head_set_clip: null handle");
+  return h->clip.set("tn_head_set_clip", h->ctx, max_norm);
+}
+extern "C" int tn_head_clip_stats(tn_head *h, float *norm, float *scale, int64_t *clipped_steps) {
+  TN_REQUIRE(h, "tn_head_clip_stats: null handle");
+  return h->clip.stats("tn_head_clip_stats", h->ctx, norm, scale, clipped_steps);
 }
 
 extern "C" int tn_head_read_param(tn_head *h, const char *name, int gradient, float *out_host, int64_t capacity, int64_t *numel) {
@@ -440,6 +456,7 @@ extern "C" int tn_head_destroy(tn_head *h) {
   if (!h) return TN_OK;
   TnDeviceGuard tn_dg_(h->ctx->device);
   (void)hipStreamSynchronize(h->ctx->stream);
+  h->clip.release();
   h->pool.release();
   delete h;
   return TN_OK;
@@ -455,6 +472,7 @@ struct tn_cnnrnn_trainer {
   int B, T, H, W, F;
   bool frozen;
   std::string bb_prefix, rnn_prefix, dense_prefix;
+  GradClip clip;                // one norm over backbone + head, one scale for both updates
 };
 
 extern "C" int tn_cnnrnn_trainer_create(tn_ctx *ctx, tn_rnn_kind kind, const tn_param *params, int n_params,
@@ -525,11 +543,28 @@ extern "C" int tn_cnnrnn_trainer_buffers(tn_cnnrnn_trainer *t, float **backbone_
 extern "C" int tn_cnnrnn_trainer_sgd_step(tn_cnnrnn_trainer *t, float lr, float momentum, float wd, float rescale_grad) {
   TN_REQUIRE(t, "tn_cnnrnn_trainer_sgd_step: null handle");
   TN_ON_DEVICE(t->ctx->device);
+  const float *scale = nullptr;
+  if (t->clip.on()) {                                      // frozen: the backbone's gradient is no part of the norm
+    float *bg = nullptr;
+    int64_t bn = 0;
+    if (!t->frozen) if (int rc = tn_finetune_buffers(t->bb, nullptr, &bg, &bn)) return rc;
+    if (int rc = t->clip.reduce(t->ctx, bg, bn, t->head->g, t->head->n, rescale_grad)) return rc;
+    scale = t->clip.scale();
+  }
   if (!t->frozen) {                                        // frozen: the backbone's parameters are not touched (grad_req 'null')
-    const int rc = tn_finetune_sgd_step(t->bb, lr, momentum, wd, rescale_grad);
+    const int rc = ft_sgd_update(t->bb, lr, momentum, wd, rescale_grad, scale);
     if (rc) return rc;
   }
-  return tn_head_sgd_step(t->head, lr, momentum, wd, rescale_grad);
+  return head_sgd_update(t->head, lr, momentum, wd, rescale_grad, scale);
+}
+
+extern "C" int tn_cnnrnn_trainer_set_clip(tn_cnnrnn_trainer *t, float max_norm) {
+  TN_REQUIRE(t, "tn_cnnrnn_trainer_set_clip: null handle");
+  return t->clip.set("tn_cnnrnn_trainer_set_clip", t->ctx, max_norm);
+}
+extern "C" int tn_cnnrnn_trainer_clip_stats(tn_cnnrnn_trainer *t, float *norm, float *scale, int64_t *clipped_steps) {
+  TN_REQUIRE(t, "tn_cnnrnn_trainer_clip_stats: null handle");
+  return t->clip.stats("tn_cnnrnn_trainer_clip_stats", t->ctx, norm, scale, clipped_steps);
 }
 
 extern "C" int tn_cnnrnn_trainer_read_param(tn_cnnrnn_trainer *t, const char *name, int gradient, float *out_host, int64_t capacity,
@@ -553,8 +588,12 @@ extern "C" int tn_cnnrnn_trainer_matmul_stats(tn_cnnrnn_trainer *t, int64_t *f32
 
 extern "C" int tn_cnnrnn_trainer_destroy(tn_cnnrnn_trainer *t) {
   if (!t) return TN_OK;
-  tn_head_destroy(t->head);
+  tn_head_destroy(t->head);                    // (each drains the one stream)
   tn_finetune_destroy(t->bb);
+  {
+    TnDeviceGuard tn_dg_(t->ctx->device);
+    t->clip.release();
+  }
   delete t;
   return TN_OK;
 }
@@ -572,6 +611,7 @@ struct tn_gnmt_frames_trainer {
   long step;                    // Adam's update count, one for both parts
   bool frozen;
   std::string bb_prefix, prefix;
+  GradClip clip;                // one norm over backbone + captioner, one scale for both updates
 };
 
 extern "C" int tn_gnmt_frames_trainer_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *backbone_prefix,
@@ -658,12 +698,30 @@ extern "C" int tn_gnmt_frames_trainer_set_dropout(tn_gnmt_frames_trainer *t, flo
 extern "C" int tn_gnmt_frames_trainer_adam_step(tn_gnmt_frames_trainer *t, float lr, float beta1, float beta2, float epsilon) {
   TN_REQUIRE(t, "tn_gnmt_frames_trainer_adam_step: null handle");
   TN_ON_DEVICE(t->ctx->device);
+  const float *scale = nullptr;
+  if (t->clip.on()) {                                      // frozen: the backbone's gradient is no part of the norm
+    float *bg = nullptr, *cg = nullptr;
+    int64_t bn = 0, cn = 0;
+    if (!t->frozen) if (int rc = tn_finetune_buffers(t->bb, nullptr, &bg, &bn)) return rc;
+    if (int rc = tn_gnmt_trainer_buffers(t->cap, nullptr, &cg, &cn)) return rc;
+    if (int rc = t->clip.reduce(t->ctx, bg, bn, cg, cn, 1.f)) return rc;
+    scale = t->clip.scale();
+  }
   t->step += 1;
   if (!t->frozen) {
-    const int rc = ft_adam_step(t->bb, lr, beta1, beta2, epsilon, t->step);
+    const int rc = ft_adam_step(t->bb, lr, beta1, beta2, epsilon, t->step, scale);
     if (rc) return rc;
   }
-  return gnmt_trainer_adam(t->cap, lr, beta1, beta2, epsilon, t->step);
+  return gnmt_trainer_adam(t->cap, lr, beta1, beta2, epsilon, t->step, scale);
+}
+
+extern "C" int tn_gnmt_frames_trainer_set_clip(tn_gnmt_frames_trainer *t, float max_norm) {
+  TN_REQUIRE(t, "tn_gnmt_frames_trainer_set_clip: null handle");
+  return t->clip.set("tn_gnmt_frames_trainer_set_clip", t->ctx, max_norm);
+}
+extern "C" int tn_gnmt_frames_trainer_clip_stats(tn_gnmt_frames_trainer *t, float *norm, float *scale, int64_t *clipped_steps) {
+  TN_REQUIRE(t, "tn_gnmt_frames_trainer_clip_stats: null handle");
+  return t->clip.stats("tn_gnmt_frames_trainer_clip_stats", t->ctx, norm, scale, clipped_steps);
 }
 
 extern "C" int tn_gnmt_frames_trainer_read_param(tn_gnmt_frames_trainer *t, const char *name, int gradient, float *out_host,
@@ -686,8 +744,12 @@ extern "C" int tn_gnmt_frames_trainer_matmul_stats(tn_gnmt_frames_trainer *t, in
 
 extern "C" int tn_gnmt_frames_trainer_destroy(tn_gnmt_frames_trainer *t) {
   if (!t) return TN_OK;
-  tn_gnmt_trainer_destroy(t->cap);
+  tn_gnmt_trainer_destroy(t->cap);             // (each drains the one stream)
   tn_finetune_destroy(t->bb);
+  {
+    TnDeviceGuard tn_dg_(t->ctx->device);
+    t->clip.release();
+  }
   delete t;
   return TN_OK;
 }

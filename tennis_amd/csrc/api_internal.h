@@ -2,11 +2,13 @@
 // (DevPool), the lookup of its parameters by name and the table of where each lives (param_table.h), and - for the training
 // handles - the flat buffers with the one read-back and the one buffers query that go through that table (TrainParams).
 #pragma once
+#include <cmath>
 #include <string>
 #include <vector>
 
 #include "common.h"
 #include "param_table.h"
+#include "train.h"
 
 struct DevPool {  // owns device allocations of one handle
   std::vector<void *> ptrs;
@@ -44,6 +46,54 @@ struct DevPool {  // owns device allocations of one handle
 int birnn_forward_rows(tn_birnn *r, const float *table, int n_rows, int ld, const int32_t *row_idx, int batch, int steps,
                        const int32_t *valid_len, float *seq, float *h_last, float *c_last);
 
+// Global-norm gradient clipping of one training handle (tn_<handle>_set_clip / _clip_stats, tennis_hip.h): the threshold on the
+// host, the reduction's workspace and the record on the device, allocated when clipping is first switched on.  A step with
+// clipping on calls reduce() over its trainable gradient buffer(s) and hands scale() to launch_sgd_momentum / launch_adam.
+struct GradClip {
+  float max_norm = 0.f;             // 0: off
+  long steps = 0;                   // steps taken with clipping on
+  float *partials = nullptr;        // TN_GRAD_SUMSQ_GRID floats, the record behind them (one allocation)
+  tn_clip_record *rec = nullptr;
+  bool on() const { return max_norm > 0.f; }
+  const float *scale() const { return &rec->scale; }
+  int set(const char *fn, tn_ctx *ctx, float v) {
+    TN_REQUIRE(std::isfinite(v) && v >= 0.f, std::string(fn) + ": max_norm must be finite and >= 0 (0 switches clipping off)");
+    if (v > 0.f && !partials) {
+      TN_ON_DEVICE(ctx->device);
+      void *p = nullptr;
+      const size_t ws = sizeof(float) * TN_GRAD_SUMSQ_GRID;
+      if (hipMalloc(&p, ws + sizeof(tn_clip_record)) != hipSuccess) { tn_set_error("device allocation failed"); return TN_ERR_NOMEM; }
+      partials = (float *)p;
+      rec = (tn_clip_record *)((char *)p + ws);
+      TN_HIP_CHECK(hipMemsetAsync(rec, 0, sizeof(tn_clip_record), ctx->stream));
+    }
+    max_norm = v;
+    return TN_OK;
+  }
+  // a, b: the trainable gradient segments of this step (b may be empty); rescale: the step's rescale_grad
+  int reduce(tn_ctx *ctx, const float *a, long na, const float *b, long nb, float rescale) {
+    if (int rc = launch_grad_sumsq(a, na, b, nb, rescale, max_norm, partials, rec, ctx->stream)) return rc;
+    ++steps;
+    return TN_OK;
+  }
+  int stats(const char *fn, tn_ctx *ctx, float *norm, float *scale, int64_t *clipped_steps) {
+    TN_REQUIRE(on(), std::string(fn) + ": clipping is off (set_clip first)");
+    TN_REQUIRE(steps > 0, std::string(fn) + ": no step has run with clipping on");
+    TN_ON_DEVICE(ctx->device);
+    tn_clip_record r;
+    TN_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+    TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (norm) *norm = r.norm;
+    if (scale) *scale = r.scale;
+    if (clipped_steps) *clipped_steps = r.clipped;
+    return TN_OK;
+  }
+  void release() {          // after the stream has drained
+    if (partials) (void)hipFree(partials);
+    partials = nullptr; rec = nullptr;
+  }
+};
+
 // The head of every training handle (tn_head, tn_finetune, tn_gnmt_trainer): the flat parameter / gradient buffers, the state
 // buffer of the handles that have one, and the table that names their contents.
 struct TrainParams {
@@ -52,6 +102,7 @@ struct TrainParams {
   ParamTable table;
   long n = 0;                 // parameters in the flat buffers (= table.n)
   float *w = nullptr, *g = nullptr, *state = nullptr;
+  GradClip clip;              // off after create
 };
 
 // *_read_param of a training handle: the named parameter (a convolution weight back in (O, I, kh, kw) order), its gradient

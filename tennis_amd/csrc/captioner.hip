@@ -2042,16 +2042,28 @@ extern "C" int tn_gnmt_trainer_buffers(tn_gnmt_trainer *t, float **params_dev, f
 }
 
 // gluon.Trainer(params, 'adam', {'learning_rate': lr}).step(1) (train_gnmt.py:310,337): MXNet Adam, beta1 0.9, beta2 0.999,
-// epsilon 1e-8, no weight decay, no clipping, rescale_grad 1
+// epsilon 1e-8, no weight decay, rescale_grad 1; no clipping unless tn_gnmt_trainer_set_clip switched it on (the reference defines
+// --clip, train_gnmt.py:97-98, and never applies it), then gluon.utils.clip_global_norm [EXT] ahead of the update
 extern "C" int tn_gnmt_trainer_adam_step(tn_gnmt_trainer *t, float lr, float beta1, float beta2, float epsilon) {
   TN_REQUIRE(t, "tn_gnmt_trainer_adam_step: null handle");
-  return gnmt_trainer_adam(t, lr, beta1, beta2, epsilon, t->step + 1);
+  if (!t->clip.on()) return gnmt_trainer_adam(t, lr, beta1, beta2, epsilon, t->step + 1, nullptr);
+  TN_ON_DEVICE(t->ctx->device);
+  if (int rc = t->clip.reduce(t->ctx, t->g, t->n, nullptr, 0, 1.f)) return rc;
+  return gnmt_trainer_adam(t, lr, beta1, beta2, epsilon, t->step + 1, t->clip.scale());
+}
+extern "C" int tn_gnmt_trainer_set_clip(tn_gnmt_trainer *t, float max_norm) {
+  TN_REQUIRE(t, "tn_gnmt_trainer_set_clip: null handle");
+  return t->clip.set("tn_gnmt_trainer_set_clip", t->ctx, max_norm);
+}
+extern "C" int tn_gnmt_trainer_clip_stats(tn_gnmt_trainer *t, float *norm, float *scale, int64_t *clipped_steps) {
+  TN_REQUIRE(t, "tn_gnmt_trainer_clip_stats: null handle");
+  return t->clip.stats("tn_gnmt_trainer_clip_stats", t->ctx, norm, scale, clipped_steps);
 }
 // the update for the step-th time (train.h): the frame-mode handle counts once for the backbone and the captioner
-int gnmt_trainer_adam(tn_gnmt_trainer *t, float lr, float beta1, float beta2, float epsilon, long step) {
+int gnmt_trainer_adam(tn_gnmt_trainer *t, float lr, float beta1, float beta2, float epsilon, long step, const float *scale) {
   TN_ON_DEVICE(t->ctx->device);
   t->step = step;
-  if (int rc = launch_adam(t->w, t->g, t->am, t->av, t->n, lr, beta1, beta2, epsilon, step, t->ctx->stream)) return rc;
+  if (int rc = launch_adam(t->w, t->g, t->am, t->av, t->n, lr, beta1, beta2, epsilon, step, t->ctx->stream, scale)) return rc;
   return trainer_refresh(t);
 }
 
@@ -2064,6 +2076,7 @@ extern "C" int tn_gnmt_trainer_destroy(tn_gnmt_trainer *t) {
   if (!t) return TN_OK;
   TnDeviceGuard tn_dg_(t->ctx->device);
   (void)hipStreamSynchronize(t->ctx->stream);
+  t->clip.release();
   t->pool.release();
   delete t;
   return TN_OK;

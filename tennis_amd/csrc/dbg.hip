@@ -495,6 +495,26 @@ extern "C" int tn_dbg_gemm_nn(tn_ctx *ctx, const float *A, int lda, const float 
   return TN_OK;
 }
 
+// The clipping reduction of the training steps (train.hip launch_grad_sumsq) on caller buffers; max_norm 0: no scale, no count
+extern "C" int tn_dbg_grad_sumsq(tn_ctx *ctx, const float *dev, int64_t n, const float *dev2, int64_t n2, double *sumsq_host) {
+  TN_REQUIRE(ctx && sumsq_host, "tn_dbg_grad_sumsq: null argument");
+  TN_REQUIRE(n >= 0 && n2 >= 0 && (dev || !n) && (dev2 || !n2), "tn_dbg_grad_sumsq: a non-empty segment needs a pointer, counts >= 0");
+  TN_ON_DEVICE(ctx->device);
+  void *ws = nullptr;
+  const size_t part_bytes = sizeof(float) * TN_GRAD_SUMSQ_GRID;
+  TN_HIP_CHECK(hipMalloc(&ws, part_bytes + sizeof(tn_clip_record)));
+  tn_clip_record *rec = (tn_clip_record *)((char *)ws + part_bytes), r;
+  int rc = launch_grad_sumsq(dev, n, dev2, n2, 1.f, 0.f, (float *)ws, rec, ctx->stream);
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, ctx->stream);
+  if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(ws);
+  if (rc) return rc;
+  TN_HIP_CHECK(e);
+  *sumsq_host = r.sumsq;
+  return TN_OK;
+}
+
 // The recurrent kernels' dispatch policy (rnn.h rnn_route: what launch_rnn_recurrent and train.hip's BPTT launchers both follow) for a
 // shape; host arithmetic only, no device is touched
 extern "C" int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int *kr, int *big) {

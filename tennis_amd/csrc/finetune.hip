@@ -654,9 +654,12 @@ int ft_enable_adam(tn_finetune *f) {
   TN_HIP_CHECK(hipMemsetAsync(f->av, 0, sizeof(float) * f->n, f->ctx->stream));
   return TN_OK;
 }
-int ft_adam_step(tn_finetune *f, float lr, float beta1, float beta2, float epsilon, long step) {
+int ft_adam_step(tn_finetune *f, float lr, float beta1, float beta2, float epsilon, long step, const float *scale) {
   TN_REQUIRE(f->av, "ft_adam_step: ft_enable_adam has not run");
-  return launch_adam(f->w, f->g, f->mom, f->av, f->n, lr, beta1, beta2, epsilon, step, f->ctx->stream);
+  return launch_adam(f->w, f->g, f->mom, f->av, f->n, lr, beta1, beta2, epsilon, step, f->ctx->stream, scale);
+}
+int ft_sgd_update(tn_finetune *f, float lr, float momentum, float wd, float rescale_grad, const float *scale) {
+  return launch_sgd_momentum(f->w, f->g, f->mom, f->n, lr, momentum, wd, rescale_grad, f->ctx->stream, scale);
 }
 // x (batch, H, W, 3) fp32 normalised frames (NHWC), labels (batch,) int32, both DEVICE.  Runs the training-mode forward,
 // the per-sample softmax cross-entropy and the backward of their SUM; loss (batch,) / logits (batch, classes) optional
@@ -694,7 +697,18 @@ extern "C" int tn_finetune_buffers(tn_finetune *f, float **params_dev, float **g
 extern "C" int tn_finetune_sgd_step(tn_finetune *f, float lr, float momentum, float wd, float rescale_grad) {
   TN_REQUIRE(f, "tn_finetune_sgd_step: null handle");
   TN_ON_DEVICE(f->ctx->device);
-  return launch_sgd_momentum(f->w, f->g, f->mom, f->n, lr, momentum, wd, rescale_grad, f->ctx->stream);
+  if (!f->clip.on()) return ft_sgd_update(f, lr, momentum, wd, rescale_grad, nullptr);
+  if (int rc = f->clip.reduce(f->ctx, f->g, f->n, nullptr, 0, rescale_grad)) return rc;
+  return ft_sgd_update(f, lr, momentum, wd, rescale_grad, f->clip.scale());
+}
+
+extern "C" int tn_finetune_set_clip(tn_finetune *f, float max_norm) {
+  TN_REQUIRE(f, "tn_finetune_set_clip: null handle");
+  return f->clip.set("tn_finetune_set_clip", f->ctx, max_norm);
+}
+extern "C" int tn_finetune_clip_stats(tn_finetune *f, float *norm, float *scale, int64_t *clipped_steps) {
+  TN_REQUIRE(f, "tn_finetune_clip_stats: null handle");
+  return f->clip.stats("tn_finetune_clip_stats", f->ctx, norm, scale, clipped_steps);
 }
 
 // Gluon-named parameter (conv weights back in (O, I, kh, kw) order), its gradient (gradient = 1), a running statistic, or
@@ -707,6 +721,7 @@ extern "C" int tn_finetune_destroy(tn_finetune *f) {
   if (!f) return TN_OK;
   TnDeviceGuard tn_dg_(f->ctx->device);
   (void)hipStreamSynchronize(f->ctx->stream);
+  f->clip.release();
   f->pool.release();
   delete f;
   return TN_OK;

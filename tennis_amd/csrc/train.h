@@ -34,12 +34,25 @@ int launch_gemm_tn_f32_padrows(const float *A, int lda, const float *table, int 
 int launch_gemm_nn_f32(const float *A, int lda, const float *Bm, int ldb, float *Cm, int ldc, int M, int N, int K, int accumulate,
                        hipStream_t s);
 int launch_colsum_f32(const float *A, int lda, int rows, int cols, float *out, hipStream_t s);
+// scale non-null (both updates): the clipped form, on *scale * g - the scale of a clip record that launch_grad_sumsq filled on the
+// same stream; null: the un-clipped kernel, which never sees the pointer's target
 int launch_sgd_momentum(float *w, const float *g, float *mom, long n, float lr, float momentum, float wd,
-                        float rescale, hipStream_t s);
+                        float rescale, hipStream_t s, const float *scale = nullptr);
 // MXNet Adam (gluon.Trainer 'adam', reference train_gnmt.py:310,337): step = the 1-based update count, its bias correction folded
 // into the rate; no weight decay, rescale_grad 1.  Shared by the captioner's parameters (captioner.hip) and the backbone's (finetune.hip).
 int launch_adam(float *w, const float *g, float *m, float *v, long n, float lr, float beta1, float beta2, float epsilon, long step,
-                hipStream_t s);
+                hipStream_t s, const float *scale = nullptr);
+// The device record of a handle's clipping: what grad_sumsq_finalize_kernel writes and the clipped update kernels read (scale)
+struct tn_clip_record {
+  double sumsq;        // the sum of squares of the last reduction
+  float norm, scale;   // of the last reduction
+  long long clipped;   // reductions with scale < 1 since the record was zeroed
+};
+// Global-norm clipping, gluon.utils.clip_global_norm [EXT]: the two-stage, bit-deterministic sum of squares of the segments
+// (a, na) and (b, nb) (either may be empty; 4-byte aligned, any count) and the record norm = |rescale| sqrt(sum),
+// scale = min(1, max_norm / (norm + 1e-8)), clipped += scale < 1.  partials: TN_GRAD_SUMSQ_GRID floats.  No host synchronisation.
+int launch_grad_sumsq(const float *a, long na, const float *b, long nb, float rescale, float max_norm, float *partials,
+                      tn_clip_record *rec, hipStream_t s);
 // y (B, T, frame_floats) = x with zeros in the frame slots t >= valid_len[b]: what Pad() leaves behind a clip's valid length
 int launch_stage_frames(const float *x, const int32_t *valid_len, int B, int T, long frame_floats, float *y, hipStream_t s);
 int launch_transpose_f32(const float *src, int rows, int cols, float *dst, hipStream_t s);
@@ -68,7 +81,9 @@ int ft_create(tn_ctx *ctx, const tn_param *params, int n_params, const char *bac
 int ft_forward_features(tn_finetune *f, const float *x, int n);
 int ft_backward_features(tn_finetune *f, int n);
 int ft_enable_adam(tn_finetune *f);
-int ft_adam_step(tn_finetune *f, float lr, float beta1, float beta2, float epsilon, long step);
+int ft_adam_step(tn_finetune *f, float lr, float beta1, float beta2, float epsilon, long step, const float *scale = nullptr);
+// tn_finetune_sgd_step's update alone (scale: launch_sgd_momentum's), for the CNN-RNN step, whose one norm spans both parts
+int ft_sgd_update(tn_finetune *f, float lr, float momentum, float wd, float rescale_grad, const float *scale);
 float *ft_frame_staging(tn_finetune *f);      // (capacity, H, W, 3) floats of the handle's own, for a caller that stages its frames
 void ft_update_running(tn_finetune *f);
 float *ft_features(tn_finetune *f);
@@ -78,4 +93,5 @@ int ft_feature_dim(tn_finetune *f);
 // the loss with respect to src, (batch * steps, input_size) of row stride ldd, assigned; rows at or past src_valid_len[b] are 0.
 int gnmt_trainer_step(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len, const int32_t *tgt, int ld,
                       const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out, float *dsrc, int ldd);
-int gnmt_trainer_adam(tn_gnmt_trainer *t, float lr, float beta1, float beta2, float epsilon, long step);
+// scale: launch_adam's - the frame-mode handle reduces once over both parts and hands the one scale to both updates
+int gnmt_trainer_adam(tn_gnmt_trainer *t, float lr, float beta1, float beta2, float epsilon, long step, const float *scale = nullptr);

@@ -697,25 +697,109 @@ __global__ __launch_bounds__(1024) void colsum_f32_kernel(const float *__restric
   }
 }
 
-// MXNet sgd_mom_update [EXT]: mom = momentum*mom - lr*(rescale*grad + wd*w); w += mom
+// MXNet sgd_mom_update [EXT]: mom = momentum*mom - lr*(rescale*grad + wd*w); w += mom.  CLIP: on scale * grad, the scale read from
+// the handle's clip record (grad_sumsq_finalize_kernel); the un-clipped instantiation never reads the pointer.
+template <bool CLIP>
 __global__ void sgd_momentum_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ mom,
-                                    long n, float lr, float momentum, float wd, float rescale) {
+                                    long n, float lr, float momentum, float wd, float rescale, const float *__restrict__ scale) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (CLIP) rescale *= *scale;
   const float m = momentum * mom[i] - lr * (rescale * g[i] + wd * w[i]);
   mom[i] = m;
   w[i] += m;
 }
 
-// MXNet Adam [EXT]: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; w -= lr_t m / (sqrt(v) + eps), lr_t bias-corrected
+// MXNet Adam [EXT]: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; w -= lr_t m / (sqrt(v) + eps), lr_t bias-corrected.  CLIP: g is
+// scale * g, as above.
+template <bool CLIP>
 __global__ void trn_adam_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
-                                float *__restrict__ v, long n, float lr_t, float b1, float b2, float eps) {
+                                float *__restrict__ v, long n, float lr_t, float b1, float b2, float eps,
+                                const float *__restrict__ scale) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float gi = g[i];
+  const float gi = CLIP ? *scale * g[i] : g[i];
   const float mi = b1 * m[i] + (1.f - b1) * gi, vi = b2 * v[i] + (1.f - b2) * gi * gi;
   m[i] = mi; v[i] = vi;
   w[i] -= lr_t * mi / (sqrtf(vi) + eps);
+}
+
+// ---- global-norm gradient clipping (gluon.utils.clip_global_norm [EXT]) ----
+// Stage one of the sum of squares over up to two (pointer, count) segments.  A segment is split at its first 16-byte boundary:
+// at most 3 head floats, a body of float4s, at most 3 tail floats.  The body is cut into chunks of TN_GRAD_SUMSQ_CHUNK floats;
+// workgroup b of the TN_GRAD_SUMSQ_GRID walks chunks b, b + GRID, b + 2 GRID, ...; in a chunk thread t loads the float4s t, t + 256,
+// t + 512, t + 768 (all four in flight) and adds their 16 squares to its one fp32 partial in index order.  Head and tail floats
+// go one each to threads 0..2 and 64..66 of workgroup 0.  The 256 partials of a workgroup meet in a fixed tree (xor shuffles
+// 32, 16, .., 1 inside a wave, then waves 0 + 1 + 2 + 3 through LDS); one float per workgroup lands in part[].  Nothing here
+// depends on the order the workgroups run in.
+__device__ __forceinline__ float sumsq_segment(const float *__restrict__ p, long n, float acc) {
+  if (n <= 0) return acc;
+  const long mis = (long)(((uintptr_t)p >> 2) & 3);                  // floats past a 16-byte boundary
+  long head = mis ? 4 - mis : 0;
+  if (head > n) head = n;
+  const long body4 = (n - head) >> 2, tail = (n - head) & 3;
+  const float4 *__restrict__ q = (const float4 *)(p + head);
+  constexpr long C4 = TN_GRAD_SUMSQ_CHUNK / 4;
+  for (long c0 = (long)blockIdx.x * C4; c0 < body4; c0 += (long)TN_GRAD_SUMSQ_GRID * C4) {
+    float4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long i = c0 + threadIdx.x + j * TN_GRAD_SUMSQ_BLOCK;
+      v[j] = i < body4 ? q[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc = fmaf(v[j].x, v[j].x, acc); acc = fmaf(v[j].y, v[j].y, acc);
+      acc = fmaf(v[j].z, v[j].z, acc); acc = fmaf(v[j].w, v[j].w, acc);
+    }
+  }
+  if (blockIdx.x == 0) {
+    const int t = threadIdx.x;
+    if (t < head) acc = fmaf(p[t], p[t], acc);
+    if (t >= 64 && t - 64 < tail) { const float x = p[head + 4 * body4 + (t - 64)]; acc = fmaf(x, x, acc); }
+  }
+  return acc;
+}
+
+__global__ __launch_bounds__(TN_GRAD_SUMSQ_BLOCK) void grad_sumsq_kernel(const float *__restrict__ a, long na,
+                                                                         const float *__restrict__ b, long nb,
+                                                                         float *__restrict__ part) {
+  __shared__ float wave_sum[TN_GRAD_SUMSQ_BLOCK / 64];
+  float acc = sumsq_segment(a, na, 0.f);
+  acc = sumsq_segment(b, nb, acc);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+}
+
+// Stage two, one workgroup: thread t adds part[t], part[t + 256], ... in double, the 256 doubles meet in a fixed LDS tree, and
+// thread 0 writes the record: norm = |rescale| sqrt(sum), scale = min(1, max_norm / (norm + 1e-8)) in fp32 as MXNet's NDArrays
+// compute it (a NaN norm gives a NaN scale), clipped += scale < 1.  max_norm <= 0 (the debug hook): scale 1, nothing counted.
+__global__ __launch_bounds__(256) void grad_sumsq_finalize_kernel(const float *__restrict__ part, int parts, float rescale,
+                                                                  float max_norm, tn_clip_record *__restrict__ rec) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < parts; i += 256) s += (double)part[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)(fabs((double)rescale) * sqrt(red[0]));
+    float scale = 1.f;
+    if (max_norm > 0.f) {
+      const float q = max_norm / (norm + 1e-8f);
+      scale = q < 1.f || q != q ? q : 1.f;
+      if (scale < 1.f) rec->clipped += 1;
+    }
+    rec->sumsq = red[0];
+    rec->norm = norm;
+    rec->scale = scale;
+  }
 }
 
 // The step's frame staging: y (B, T, frame floats) = x, with zeros (the Pad() value of the normalised tensor,
@@ -872,15 +956,28 @@ int launch_colsum_f32(const float *A, int lda, int rows, int cols, float *out, h
   TN_LAUNCH_CHECK();
 }
 int launch_sgd_momentum(float *w, const float *g, float *mom, long n, float lr, float momentum, float wd,
-                        float rescale, hipStream_t s) {
-  hipLaunchKernelGGL(sgd_momentum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w, g, mom, n, lr, momentum, wd, rescale);
+                        float rescale, hipStream_t s, const float *scale) {
+  const dim3 grid((n + 255) / 256), block(256);
+  if (scale) hipLaunchKernelGGL(sgd_momentum_kernel<true>, grid, block, 0, s, w, g, mom, n, lr, momentum, wd, rescale, scale);
+  else hipLaunchKernelGGL(sgd_momentum_kernel<false>, grid, block, 0, s, w, g, mom, n, lr, momentum, wd, rescale, scale);
   TN_LAUNCH_CHECK();
 }
 int launch_adam(float *w, const float *g, float *m, float *v, long n, float lr, float beta1, float beta2, float epsilon, long step,
-                hipStream_t s) {
+                hipStream_t s, const float *scale) {
   const double c1 = 1.0 - pow((double)beta1, (double)step), c2 = 1.0 - pow((double)beta2, (double)step);
   const float lr_t = (float)((double)lr * sqrt(c2) / c1);
-  hipLaunchKernelGGL(trn_adam_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w, g, m, v, n, lr_t, beta1, beta2, epsilon);
+  const dim3 grid((n + 255) / 256), block(256);
+  if (scale) hipLaunchKernelGGL(trn_adam_kernel<true>, grid, block, 0, s, w, g, m, v, n, lr_t, beta1, beta2, epsilon, scale);
+  else hipLaunchKernelGGL(trn_adam_kernel<false>, grid, block, 0, s, w, g, m, v, n, lr_t, beta1, beta2, epsilon, scale);
+  TN_LAUNCH_CHECK();
+}
+int launch_grad_sumsq(const float *a, long na, const float *b, long nb, float rescale, float max_norm, float *partials,
+                      tn_clip_record *rec, hipStream_t s) {
+  TN_REQUIRE(partials && rec && na >= 0 && nb >= 0 && (a || !na) && (b || !nb), "launch_grad_sumsq: bad argument");
+  TN_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 3) == 0, "launch_grad_sumsq: the segments must be 4-byte aligned");
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(TN_GRAD_SUMSQ_GRID), dim3(TN_GRAD_SUMSQ_BLOCK), 0, s, a, na, b, nb, partials);
+  hipLaunchKernelGGL(grad_sumsq_finalize_kernel, dim3(1), dim3(256), 0, s, (const float *)partials, TN_GRAD_SUMSQ_GRID, rescale,
+                     max_norm, rec);
   TN_LAUNCH_CHECK();
 }
 int launch_stage_frames(const float *x, const int32_t *valid_len, int B, int T, long frame_floats, float *y, hipStream_t s) {

@@ -152,6 +152,20 @@ class _FlatTrainer(_Handle):
         """Every recorded parameter (for a backbone: its running statistics too), by name."""
         return {k: self.get(k) for k in self.names}
 
+    def set_clip(self, max_norm: float):
+        """Global-norm gradient clipping of ``step`` (``gluon.utils.clip_global_norm``): the update runs on ``scale * g`` with
+        ``scale = min(1, max_norm / (norm + 1e-8))``, ``norm`` over every trainable gradient element (for the SGD trainers: of
+        ``rescale_grad * g``; for the two-part trainers: over both parts).  ``grads`` stay unclipped.  0 switches it off, which is
+        the state after construction; negative or non-finite values raise."""
+        check(getattr(self.lib, self._ABI + "_set_clip")(self.handle, float(max_norm)), self._ABI + "_set_clip")
+
+    def clip_stats(self) -> tuple:
+        """(norm, scale) of the last clipped ``step`` and the steps with ``scale < 1`` since construction.  Synchronises the stream:
+        for a log point, not for every step.  Raises while clipping is off or before a clipped step."""
+        n, sc, k = C.c_float(), C.c_float(), C.c_int64()
+        check(getattr(self.lib, self._ABI + "_clip_stats")(self.handle, C.byref(n), C.byref(sc), C.byref(k)), self._ABI + "_clip_stats")
+        return n.value, sc.value, k.value
+
 
 class DenseNet121Features(_Handle):
     """``get_model('DenseNet121').features`` on the GPU (reference evaluate.py:125)."""

@@ -96,15 +96,21 @@ def is_main_rank() -> bool:
 
 def train_model(head: TemporalHeadTrainer, train_batches, metrics, trainer: Trainer, epochs: int, batch_size: int,
                 lr_steps=(10, 20), lr_factor: float = 0.75, start_epoch: int = 0, val_fn=None, save_dir: str | None = None,
-                log=print, model=None, score_key: str = "AVG_NB_f1", step_fn=None):
+                log=print, model=None, score_key: str = "AVG_NB_f1", step_fn=None, clip: float = 0.0):
     """reference train.py:388-499 with the model call, loss and backward fused into ``head.forward_backward``.
     ``train_batches``: callable -> iterable of (features (B,T,F) tensor, labels (B,) tensor) per epoch.
     Per epoch (rank 0 only): the validation ``AVG_NB_f1`` is appended to ``<save_dir>/scores.txt`` (:487-489) and the
     parameters go to ``<save_dir>/NNNN.params`` (:497) — through ``model.save_parameters`` (the MXNet container with
     Gluon's structural names, what the reference's ``load_parameters`` reads) when the mirror ``model`` is given,
     else an ``.npz`` of the trainer's prefixed names under ``NNNN.npz``.  ``step_fn``: what a step calls instead of
-    ``head.forward_backward`` (``--dense_windows``: ``head.forward_backward_rows`` on (window rows (B,T), labels) batches)."""
+    ``head.forward_backward`` (``--dense_windows``: ``head.forward_backward_rows`` on (window rows (B,T), labels) batches).
+    ``clip`` > 0 (``--clip_grad_norm``, not in the reference): ``head.set_clip(clip)`` - the global norm of ``rescale_grad * g`` over
+    every trainable gradient is held at ``clip`` inside ``step``; each epoch's row then carries ``grad_norm`` (the last step's) and
+    ``clipped_steps`` (the epoch's), read once per epoch."""
     step_fn = step_fn or head.forward_backward
+    if clip:
+        head.set_clip(clip)
+    clipped_before = 0
     lr_counter = 0
     lr_steps = list(lr_steps) + [1 << 30]
     history = []
@@ -127,10 +133,19 @@ def train_model(head: TemporalHeadTrainer, train_batches, metrics, trainer: Trai
             for m in metrics:
                 m.update([y], [logits])                                     # :430-431
         row = {"epoch": epoch, "lr": trainer.learning_rate, "loss": train_sum_loss / max(1, nb)}
+        if clip and nb:
+            norm, _, clipped = head.clip_stats()
+            row["grad_norm"], row["clipped_steps"] = norm, clipped - clipped_before
+            clipped_before = clipped
         if val_fn is not None:
             row["val"] = val_fn(head)
         history.append(row)
         log("[Epoch {}] loss: {:.3f} lr: {:.2E}".format(epoch, row["loss"], trainer.learning_rate))
+        if "grad_norm" in row:
+            log("[Epoch {}] grad_norm={:.4f} (last step), clipped_steps={} of {} (clip_grad_norm={})".format(
+                epoch, row["grad_norm"], row["clipped_steps"], nb, clip))
+            if not np.isfinite(row["grad_norm"]):
+                log("[Epoch {}] WARNING: the gradient norm is not finite; the clipped updates carried it into the parameters".format(epoch))
         if save_dir and is_main_rank():
             os.makedirs(save_dir, exist_ok=True)
             if isinstance(row.get("val"), dict) and score_key in row["val"]:   # :487-489
@@ -249,6 +264,9 @@ def build_parser():
                    help="with --feats_model --window W --temp_pool gru|lstm: every split's features go to the device once as a table "
                         "and the training kernels gather each step's windows from it - no per-step file reads, stacking or "
                         "host-to-device copies; bit-identical parameters (not a reference flag)")
+    p.add_argument("--clip_grad_norm", type=float, default=0.0,
+                   help="X > 0: hold the global norm of the step's gradient (rescaled by 1 / batch_size, over every trainable "
+                        "parameter) at X, gluon.utils.clip_global_norm; 0 = off, the reference's step (not a reference flag)")
     p.add_argument("--matmul", default="f32", choices=["f32", "fp32x3"],
                    help="matrix pipe of the backbone's GEMMs when training on frames: f32 (exact-f32 MFMA) or fp32x3 (fp32 values as "
                         "three bf16 terms on the bf16 MFMA, same float64 bars; not a reference flag)")
@@ -291,6 +309,8 @@ def main(argv=None):
         raise NotImplementedError("--flow / --vis: optical-flow input and visualisation are outside the accelerated path (SURVEY 2a)")
     check_frames_route(flags)
     check_dense_windows(flags)
+    if not (np.isfinite(flags.clip_grad_norm) and flags.clip_grad_norm >= 0):
+        raise SystemExit("--clip_grad_norm must be finite and >= 0 (0 = off)")
     if flags.num_workers < 0:                          # the reference's -1 = cpu_count() (train.py:101-102)
         flags.num_workers = 3                                               # (files -> features peaks at three decoder threads: scripts/bench_pipeline.py, profiles/r05_c_*)
     every = [int(s) for s in flags.every.split(",")]
@@ -420,7 +440,7 @@ def main(argv=None):
 
     hist = train_model(head, batches, metrics, trainer, flags.epochs, flags.batch_size, lr_steps=lr_steps,
                        lr_factor=flags.lr_factor, start_epoch=start_epoch, val_fn=validate, save_dir=save_dir, model=model,
-                       step_fn=step_fn)
+                       step_fn=step_fn, clip=flags.clip_grad_norm)
     if hist and is_main_rank():
         best = max(hist, key=lambda r: r["val"].get("AVG_NB_f1", 0.0))
         print("[Finished] best epoch {} val AVG_NB_f1={:.3f}".format(best["epoch"], best["val"].get("AVG_NB_f1", 0.0)))

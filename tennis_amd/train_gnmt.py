@@ -58,13 +58,16 @@ def allreduce_grads(trainer, n_tokens: int):
 def train(data_train, data_val, data_test, model, translator, epochs: int, batch_size: int, lr: float = 1e-3,
           lr_update_factor: float = 0.5, dropout: float = 0.0, num_buckets: int = 5, test_batch_size: int = 32,
           start_epoch: int = 0, save_dir: str | None = None, seed: int = 0, log=print, freeze_backbone: bool = False,
-          frame_size: int | None = None, matmul: str = "f32", feats_on_device: bool = False):
+          frame_size: int | None = None, matmul: str = "f32", feats_on_device: bool = False, clip: float = 0.0):
     """-> history: one dict per epoch (train loss, valid / test loss and BLEU, learning rate).  A model with a ``src_embed`` trains on
     frames (``GNMTFramesTrainer``: the backbone inside the step, frozen or trainable); its checkpoints carry the backbone under the
     model's structural names (``src_embed.model. ...``).  ``matmul``: the matrix pipe of that backbone's GEMMs ("f32" | "fp32x3").
     ``feats_on_device`` (feature mode): each split's features are read once and uploaded as one table; the train step and the
     per-epoch validation / test passes gather their clips from it inside the kernels (``forward_backward_rows`` / ``encode_rows``)
-    instead of reading one ``.npy`` per frame and copying a host-built batch every step.  Same parameters, losses and sentences."""
+    instead of reading one ``.npy`` per frame and copying a host-built batch every step.  Same parameters, losses and sentences.
+    ``clip`` > 0: ``gluon.utils.clip_global_norm(grads, clip)`` between the backward and the update, as the gluonnlp script the
+    reference's trainer came from has it and the reference does not (0, the default: no clipping, the reference's step); each
+    epoch's record then carries ``grad_norm`` (the last step's) and ``clipped_steps`` (the epoch's)."""
     enc = model.encoder
     if enc._cell_type not in ("gru", "lstm"):
         raise NotImplementedError("the training step is built for GRU / LSTM cells")
@@ -101,6 +104,9 @@ def train(data_train, data_val, data_test, model, translator, epochs: int, batch
                               max_batch=batch_size, max_src_len=max_t, max_tgt_len=max_l, prefix=model.prefix, **cell)
     if dropout > 0:
         trainer.set_dropout(dropout, seed)
+    if clip:
+        trainer.set_clip(clip)
+    clipped_before = 0
     val_tgt = data_val.get_captions(split=True) if data_val is not None else None
     test_tgt = data_test.get_captions(split=True) if data_test is not None else None
     best_valid_bleu, history = 0.0, []
@@ -128,6 +134,14 @@ def train(data_train, data_val, data_test, model, translator, epochs: int, batch
             tot += float(loss)
             nb += 1
         rec = {"epoch": epoch_id, "train_loss": tot / max(1, nb), "lr": lr}
+        if clip and nb:                                                          # one read per epoch: clip_stats synchronises
+            norm, _, clipped = trainer.clip_stats()
+            rec["grad_norm"], rec["clipped_steps"] = norm, clipped - clipped_before
+            clipped_before = clipped
+            log("[Epoch {}] grad_norm={:.4f} (last step), clipped_steps={} of {} (clip={})".format(epoch_id, norm, rec["clipped_steps"],
+                                                                                                  nb, clip))
+            if not math.isfinite(norm):
+                log("[Epoch {}] WARNING: the gradient norm is not finite; the clipped updates carried it into the parameters".format(epoch_id))
         model.set_params(trainer.state_dict())                                   # evaluation runs on the updated weights
         for name, ds, ref in (("valid", data_val, val_tgt), ("test", data_test, test_tgt)):
             if ds is None:
@@ -200,6 +214,9 @@ def build_parser():
     p.add_argument("--bucket_ratio", type=float, default=0.0)
     p.add_argument("--optimizer", default="adam", choices=["adam"])
     p.add_argument("--clip", type=float, default=5.0, help="accepted; the reference defines the flag and never applies it (train_gnmt.py:305-470)")
+    p.add_argument("--apply_clip", action="store_true",
+                   help="apply --clip: gluon.utils.clip_global_norm(grads, clip) before every update, as the gluonnlp script behind the "
+                        "reference's trainer does (not a reference flag; without it --clip stays accepted and ignored)")
     p.add_argument("--log_interval", type=int, default=100)
     p.add_argument("--num_gpus", type=int, default=1, help="the reference's captioner is single-GPU (train_gnmt.py:126-127); data parallelism here comes from torch.distributed")
     p.add_argument("--backbone", default="DenseNet121")
@@ -317,8 +334,15 @@ def require_feature_mode(flags):
                          "reads frames through its backbone and there is no feature table")
 
 
+def applied_clip(flags) -> float:
+    """What ``train`` gets as ``clip``: --clip only under --apply_clip, else 0 (the reference parses the flag and never uses it)"""
+    return float(flags.clip) if flags.apply_clip else 0.0
+
+
 def main(argv=None):
     flags = build_parser().parse_args(argv)
+    if flags.apply_clip and not (math.isfinite(flags.clip) and flags.clip > 0):
+        raise SystemExit("--apply_clip needs a finite --clip > 0")
     if flags.matmul != "f32" and (flags.feats_model is not None or (flags.data_root is None and not flags.frames)):
         raise SystemExit("--matmul fp32x3 switches the backbone's GEMMs; with --feats_model (or synthetic features) there is no backbone "
                          "in the step - the captioner trains on stored features")
@@ -339,7 +363,7 @@ def main(argv=None):
     hist = train(data_train, data_val, data_test, model, translator, flags.epochs, flags.batch_size, lr=flags.lr,
                  lr_update_factor=flags.lr_update_factor, dropout=flags.dropout, num_buckets=flags.num_buckets,
                  test_batch_size=flags.test_batch_size, start_epoch=start_epoch, save_dir=save_dir,
-                 freeze_backbone=flags.freeze_backbone, matmul=flags.matmul, feats_on_device=flags.feats_on_device, frame_size=flags.data_shape if getattr(model, "src_embed", None) is not None else None)
+                 freeze_backbone=flags.freeze_backbone, matmul=flags.matmul, feats_on_device=flags.feats_on_device, clip=applied_clip(flags), frame_size=flags.data_shape if getattr(model, "src_embed", None) is not None else None)
     if not hist:
         print("[Finished] nothing to do: {} epochs are on disk".format(start_epoch))
         return 0
