@@ -194,7 +194,7 @@ struct DenseLayerArgs {
   unsigned long long *ts = nullptr;  // tuning hook: 8 s_memtime stamps per workgroup
   int variant = 0;                   // tuning hook of the K loop: bit 3 = refill up front
   const DenseLayerDev *chain = nullptr;  // device array: run nchain consecutive layers (K, K+32, ...) in one launch
-  int nchain = 0;                        // (whole-frame tiles only: 16x16, 14x14 and 7x7)
+  int nchain = 0;                        // (whole-frame tiles: 16x16, 14x14, 7x7; 28x28 with fp16 weights: two row tiles)
   int exact = 0;                         // weights as hi + lo fp16 pairs: w1 [128][2 Kp] = [hi | lo], w3p = hi image then lo image
 };
 bool dense_layer_supported(int H, int W);

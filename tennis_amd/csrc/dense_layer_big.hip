@@ -131,9 +131,11 @@ __device__ __forceinline__ void pp_barrier() {
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// CHAIN (whole-frame tiles only): the workgroup runs a.nchain consecutive layers of the block on its frame
+// CHAIN: the workgroup runs a.nchain consecutive layers of the block on its frame
 // inside one launch; layer l reads channels [0, K0 + 32 l) -- its own earlier outputs included, which the
 // same CU's L1 sees coherently once the stores have been waited for -- with parameters from a.chain[l].
+// Whole-frame tiles (14x14, 7x7, 16x16), or - 28x28, the default fp16 K loop only - the frame's two row tiles
+// one after the other per layer (MT below).
 // EX (exact-weights mode): every weight is the sum of two fp16 numbers, w = hi + lo (lo = fp16(w - hi):
 // 22 bits of the fp32 weight).  The 1x1 weights come as [128][2 Kp] = [hi | lo] (Kp = K rounded up to BK) and the K
 // loop simply runs over 2 Kp "channels", the activation side wrapping around after the hi half; the 3x3 weights
@@ -164,10 +166,17 @@ __global__ __launch_bounds__(512) void dense_layer_kernel(DenseLayerArgs a) {
   // all row-tiles of a frame share (virtual) blockIdx % 8 (the XCD) when B % 8 == 0, so the halo rows two
   // neighbouring tiles both read are L2 hits on that XCD instead of second HBM fetches
   const int tiles_per_img = H / ROUT;
+  // MT: a chain over a map of more than one row tile (28x28: two).  The workgroup is the FRAME (virtual block vb = frame,
+  // grid = B) and walks layer by layer over the frame's tiles in order: frame -> layer -> tile.
+  constexpr bool MT = CHAIN && ROUT != W;
+  constexpr int TPI = W / ROUT;                 // (MT: square maps, the launcher checks it) row tiles of a frame
   struct TileAt { int img, r0, MA, top_pad; const f16 *xbase; };
-  auto tile_at = [&](int vb) {
+  auto tile_at = [&](int vb, int mt_tix = 0) {
     int img, tix;
-    if ((a.B & 7) == 0) {
+    if constexpr (MT) {
+      img = vb;
+      tix = mt_tix;
+    } else if ((a.B & 7) == 0) {
       const int j = vb >> 3;
       img = (j / tiles_per_img) * 8 + (vb & 7);
       tix = j % tiles_per_img;
@@ -185,20 +194,24 @@ __global__ __launch_bounds__(512) void dense_layer_kernel(DenseLayerArgs a) {
     ta.xbase = a.buf + ((long)img * H * W + (long)rlo * W) * ldc;
     return ta;
   };
-  static_assert(!CHAIN || ROUT == W, "layer chaining needs whole-frame tiles");
+  static_assert(!MT || (PP == 2 && !EX && BK == 32 && W % ROUT == 0), "the multi-tile chain is built for the flat fp16 K loop with 32-channel stages");
   // Persistent tiles (flat K loops, one layer per launch): the grid is one workgroup per CU and each walks
   // the tiles vb = blockIdx.x, blockIdx.x + gridDim.x, ...  Right after a tile's phase B (ring region free
   // again) it already requests the first two stages of its NEXT tile, so that tile's cold-start latency and
   // this tile's store drain overlap instead of adding up once per tile.
-  const int nvb = a.B * tiles_per_img;
+  const int nvb = MT ? a.B : a.B * tiles_per_img;
   bool primed = false;      // the first two stages (and the tables) of the next tile / layer have already been requested
   for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-  const TileAt ta = tile_at(vb);
-  const int img = ta.img, r0 = ta.r0, MA = ta.MA, top_pad = ta.top_pad;
-  const f16 *xbase = ta.xbase;
+  const TileAt ta0 = tile_at(vb);
   const int nlayers = CHAIN ? a.nchain : 1;
   const int K0 = a.K;
-  for (int layer = 0; layer < nlayers; ++layer) {
+  const int nit = MT ? nlayers * TPI : nlayers;    // MT: (layer, tile) pairs of the frame, the tile index running fastest
+  for (int it = 0; it < nit; ++it) {
+  const int layer = MT ? it / TPI : it;
+  [[maybe_unused]] const int tix = MT ? it - layer * TPI : 0;
+  const TileAt ta = MT ? tile_at(vb, tix) : ta0;
+  const int img = ta.img, r0 = ta.r0, MA = ta.MA, top_pad = ta.top_pad;
+  const f16 *xbase = ta.xbase;
   // per-layer copies of the thread coordinates, laundered so that the compiler does not hoist every
   // address computation of the body out of the tile / layer loops (that costs ~80 VGPRs and spills)
   int t_ = threadIdx.x;
@@ -728,6 +741,15 @@ __global__ __launch_bounds__(512) void dense_layer_kernel(DenseLayerArgs a) {
         }
         primed = true;
       }
+    } else if (MT && tix + 1 < TPI) {     // same frame, same layer, next row tile: what the persistent walk does between two tiles
+      // (tables and weights stay).  The two k-tiles are channels [0, 2 BK) of the next tile's rows, its halo row - this tile's last
+      // output row - included: with 2 BK <= K they share no 128-byte line with the channels [K, K + 32) this tile is about to store
+      // (a chain of ONE layer may start at K = 32, where they do: no later layer of the launch reads that line).
+      const TileAt nx = tile_at(vb, tix + 1);
+      set_src(nx.xbase, nx.MA, a.w1, w1ld);
+      issue(1, 0);
+      if (nk > 1) issue(2, 1);
+      primed = true;
     } else if (layer + 1 < nlayers) {     // same frame, next layer: its first 128 input channels exist already
       const DenseLayerDev dn = a.chain[layer + 1];
       nxK = K + 32;
@@ -741,7 +763,8 @@ __global__ __launch_bounds__(512) void dense_layer_kernel(DenseLayerArgs a) {
       // layer's output channels [K, K + 32) are stored and does not wrap the activation pointers: those k-tiles have to lie inside
       // the channels this layer read (2 BK <= K, PP 4: 3 BK <= K), which launch_dense_layer_big requires of a chain's first layer
       const int nxc = (nxK + BK - 1) / BK;
-      set_src(xbase, MA, dn.w1, EX ? 2 * nxc * BK : nxK);
+      const TileAt n0 = MT ? tile_at(vb, 0) : ta;     // (MT: the next layer starts over at the frame's first row tile)
+      set_src(n0.xbase, n0.MA, dn.w1, EX ? 2 * nxc * BK : nxK);
 #pragma unroll
       for (int st = 1; st <= (PP == 4 ? 3 : 2); ++st)       // (the pipelined loop keeps three k-tiles requested: slots 1, 2, 3)
 #pragma unroll
@@ -786,11 +809,18 @@ __global__ __launch_bounds__(512) void dense_layer_kernel(DenseLayerArgs a) {
       }
       if (t < 256) tab2[t] = nx2;
     }
+    // MT: the same sequence closes EVERY tile of the frame, not only a layer's last one.  Layer l + 1, tile 0 reads output row
+    // ROUT of layer l, which tile 1 of layer l stored from this workgroup; and tile 1 of layer l reads, as its halo, the
+    // channels [0, K) of row ROUT - 1 whose channels [K, K + 32) tile 0 has just stored: at K % 64 == 32 the same 128-byte line.
+    // A load that misses while a store to its line's other half is still on its way may bring the old half into L1, where the next
+    // layer would find it.  With the stores retired first the rule CHAIN and dense_block14.hip rest on covers both cases: same CU,
+    // write-through L1 that a store updates, plain loads and stores without cache bits - a load issued after the workgroup's own
+    // store has completed sees it.  (The k-tiles requested AHEAD of the stores lie in channels [0, 2 BK): other lines, see above.)
     wait_vmcnt<0>();      // this layer's stores have completed (stores count in vmcnt on gfx9) ...
     __syncthreads();      // ... for every wave, before the next layer's loads of the same frame
   }
-  }   // layer
-  }   // tile
+  }   // layer (MT: layer and row tile)
+  }   // tile (MT: frame)
 }
 
 template <int W, int ROUT, int BM, int BK, int PP, bool CHAIN = false, bool EX = false>
@@ -808,7 +838,7 @@ int launch_geom(const DenseLayerArgs &a, hipStream_t s) {
     if (getenv("TN_PERSIST_WGS")) ncu = atoi(getenv("TN_PERSIST_WGS"));   // tuning hook
   }
   TN_REQUIRE(a.K + 32 * (a.nchain > 0 ? a.nchain - 1 : 0) <= G::KMAX, "dense_layer: more input channels than this block's table space holds");
-  const int nvb = a.B * (a.H / ROUT);
+  const int nvb = (CHAIN && ROUT != W) ? a.B : a.B * (a.H / ROUT);      // (a chain over row tiles: one workgroup per frame)
   // one workgroup per CU walking its tiles (flat K loops, single layer); otherwise one workgroup per tile
   const bool persist = !CHAIN && (PP == 0 || PP == 2) && !(a.variant & 16) && nvb > ncu && ncu > 0;
   const dim3 grid(persist ? ncu : nvb), block(512);
@@ -833,6 +863,12 @@ int dense_layer_big_kmax(int W) { return W == 56 ? 256 : W == 28 ? 512 : 1024; }
 // nkc - 1 is always left to advance().)
 static int chain_primed_ktiles(int pp) { return pp == 4 ? 3 : 2; }
 
+// The chain over the two row tiles of a 28 x 28 frame (MT in the kernel): the default fp16 K loop, one workgroup per frame.
+// What holds this instantiation to float64, to the bits of per-layer launches and to its tile seam is
+// tests/test_gpu_chain28_kernel.py; the table of tests/tools/tile_ref.py lists the 30 instantiations that came before it.
+static bool chain_tiled28(const DenseLayerArgs &a) { return a.H == 28 && a.W == 28 && !a.exact; }
+static int launch_chain_tiled28(const DenseLayerArgs &a, hipStream_t s) { return launch_geom<28, 14, 512, 32, 2, true>(a, s); }
+
 int launch_dense_layer_big(const DenseLayerArgs &a, hipStream_t s) {
   const int klast = a.K + 32 * (a.nchain > 0 ? a.nchain - 1 : 0);
   // (the message names the geometry; put together only when a call is refused)
@@ -847,10 +883,11 @@ int launch_dense_layer_big(const DenseLayerArgs &a, hipStream_t s) {
   TN_REQUIRE(a.ldc % 8 == 0, "dense_layer: the row pitch must be a multiple of 8: " + geom());
   TN_REQUIRE(klast + 32 <= a.ldc, "dense_layer: the row pitch does not hold the last layer's output: " + geom());
   if (a.nchain > 0) {
-    TN_REQUIRE(a.H == 14 || a.H == 7 || a.H == 16, "dense_layer: layer chaining needs whole-frame tiles (16x16, 14x14, 7x7): " + geom());
+    TN_REQUIRE(a.H == 14 || a.H == 7 || a.H == 16 || chain_tiled28(a),
+               "dense_layer: layer chaining needs whole-frame tiles (16x16, 14x14, 7x7) or the two row tiles of 28x28 with fp16 weights: " + geom());
     TN_REQUIRE(a.chain, "dense_layer: nchain > 0 without the chain's layer array: " + geom());
     if (a.nchain > 1) {
-      const int bk = a.H == 16 ? 32 : 64;
+      const int bk = (a.H == 16 || a.H == 28) ? 32 : 64;
       const int pp = (!a.exact && a.H == 7 && !(a.variant & (32 | 512))) ? 4 : 2;
       const int need = chain_primed_ktiles(pp) * bk;
       TN_REQUIRE(a.K >= need, "dense_layer: a chain of this geometry starts at K >= " + std::to_string(need) + " (the chained kernel requests the next layer's first " +
@@ -874,6 +911,7 @@ int launch_dense_layer_big(const DenseLayerArgs &a, hipStream_t s) {
     TN_REQUIRE(false, "dense_layer: unsupported spatial size " + geom());
   }
   if (a.nchain > 0) {
+    if (a.H == 28) return launch_chain_tiled28(a, s);
     if (a.H == 14) return launch_geom<14, 14, 256, 64, 2, true>(a, s);
     if (a.H == 16) return launch_geom<16, 16, 384, 32, 2, true>(a, s);
     // 7x7: 4 x 2 wave split over a 64-row tile (variant bit 5: the 8 x 1 split over 128 rows, for A/B runs)

@@ -747,9 +747,10 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
           break;
         }
         case ENC_CHAIN_TILE:      // one workgroup per frame walks the whole block: no launch gaps, no cold prologue per layer
+                                  // (28 x 28: layers [l0, l0 + nl) behind the strip layers, chain_dev from entry l0 on)
         case ENC_TILE: {
           const bool ch = st.route == ENC_CHAIN_TILE;
-          DenseLayerArgs af{bbuf[b], g.Cb[b], L.cin, L.s1, L.t1, L.w1, L.s2, L.t2, L.w3p, B, Hh, Ww, nullptr, p.dl_variant, ch ? e->chain_dev[b] : nullptr, ch ? st.nl : 0};
+          DenseLayerArgs af{bbuf[b], g.Cb[b], L.cin, L.s1, L.t1, L.w1, L.s2, L.t2, L.w3p, B, Hh, Ww, nullptr, p.dl_variant, ch ? e->chain_dev[b] + st.l0 : nullptr, ch ? st.nl : 0};
           af.exact = p.exact;
           rc = launch_dense_layer(af, s);
           break;

@@ -5,7 +5,8 @@
 //
 // Precedence inside a block, first match wins (docs/kernels.md "Routes of the dense blocks"):
 //   streamed 14x14 / 28x28 block > LDS-resident 7x7 block > chained tile-kernel block >
-//   (chained strip launch for the leading layers, then per layer: strip > fused tile kernel > layer-wise 1x1 + 3x3)
+//   (chained strip launch for the leading layers, then per layer: strip > fused tile kernel > layer-wise 1x1 + 3x3;
+//    28x28 at 128 frames or more: the tile-kernel layers behind the strip layers as one chained tile-kernel launch)
 #pragma once
 #include <cstdlib>
 #include <string>
@@ -19,6 +20,9 @@ inline constexpr int kBlockCfg[4] = {6, 12, 24, 16};
 struct EncPolicy {
   bool fuse = true;            // fused kernels (TN_NO_FUSE: stem, max pool, 1x1 and 3x3 as kernels of their own)
   bool chain = true;           // whole-frame blocks (14x14, 7x7) run all their layers in one launch (TN_NO_CHAIN disables)
+  bool chain28 = true;         // the tile-kernel layers of a 28x28 block (K > 320) run in one launch (TN_NO_CHAIN28 or TN_NO_CHAIN: one per layer)
+  int chain28_min_batch = 128; // ... from this many frames per launch on (one workgroup per frame, where the per-layer launches spread two
+                               // tiles per frame: below it the chained launch leaves more than half of the CUs without work)
   bool exact = false;          // TN_ENC_EXACT_WEIGHTS: dense-layer and transition weights as hi + lo fp16 pairs
   bool strip = true;           // 56x56 / 28x28 layers with K <= 320 run on the strip-streaming kernel (TN_NO_STRIP disables)
   bool strip_chain = true;     // the leading strip layers of a 56x56 / 28x28 block run in one launch (TN_NO_STRIP_CHAIN: one launch per layer)
@@ -41,6 +45,8 @@ inline EncPolicy enc_policy(int flags) {
   p.exact = (flags & TN_ENC_EXACT_WEIGHTS) != 0 && !fp32;    // (TN_ENC_FP32 / TN_ENC_FP32X3 | TN_ENC_EXACT_WEIGHTS: that mode)
   p.strip = getenv("TN_NO_STRIP") == nullptr && !p.exact && p.fuse;
   p.strip_chain = getenv("TN_NO_STRIP_CHAIN") == nullptr;
+  p.chain28 = p.chain && getenv("TN_NO_CHAIN28") == nullptr;
+  if (getenv("TN_CHAIN28_MIN_BATCH")) p.chain28_min_batch = atoi(getenv("TN_CHAIN28_MIN_BATCH"));
   if (getenv("TN_STRIP_MIN_BATCH")) p.strip_min_batch = atoi(getenv("TN_STRIP_MIN_BATCH"));
   p.block7 = getenv("TN_NO_BLOCK7") == nullptr;
   p.block_stream[0] = getenv("TN_NO_BLOCK14") == nullptr;
@@ -121,6 +127,17 @@ inline bool enc_block_chained_tile(const EncPolicy &p, const EncGeom &g, int b) 
   return p.chain && (p.dl_variant & ~(32 | 64 | 128 | 256 | 512)) == 0 && Hh == Ww && (Hh == 14 || Hh == 7 || Hh == 16) &&
          enc_layer_tile(p, g, b, kBlockCfg[b] - 1);
 }
+// the tile-kernel layers [l0, n) of a 28 x 28 block as one chained launch (dense_layer_kernel<28, 14, 512, 32, 2, true>: one workgroup
+// per frame walks layer by layer over the frame's two row tiles): the default fp16 kernels only, every layer from l0 on a tile-kernel
+// layer, at least two of them, and the first one at K >= 64 (the two 32-channel k-tiles the kernel requests ahead of a layer's stores).
+// Needs no packing of its own: the chain's DenseLayerDev table is the block's chain_dev from entry l0 on.
+inline bool enc_chain28(const EncPolicy &p, const EncGeom &g, int b, int l0) {
+  if (!p.chain28 || p.exact || p.dl_variant != 0 || g.Hb[b] != 28 || g.Wb[b] != 28) return false;
+  if (kBlockCfg[b] - l0 < 2 || enc_layer_cin(g, b, l0) < 64) return false;
+  for (int l = l0; l < kBlockCfg[b]; ++l)
+    if (!enc_layer_tile(p, g, b, l)) return false;
+  return true;
+}
 
 // ---- the plan -------------------------------------------------------------------------------------------------------------------
 enum EncRoute { ENC_STREAM14, ENC_STREAM28, ENC_BLOCK7, ENC_CHAIN_TILE, ENC_STRIP_CHAIN, ENC_STRIP, ENC_TILE, ENC_LAYERWISE, ENC_NROUTES };
@@ -160,8 +177,16 @@ inline std::vector<EncStep> enc_block_plan(const EncPolicy &p, const EncGeom &g,
   if (l > 0) plan.push_back({ENC_STRIP_CHAIN, 0, l});
   // (one workgroup per 56 x 56 / 28 x 28 frame, 5 / 3 per 128 x 128 / 64 x 64 frame: enough of them to fill the chip?)
   const bool strip_fills = B * (Hh == 128 ? 5 : Hh == 64 ? 3 : 1) >= p.strip_min_batch;
-  for (; l < n; ++l)
-    plan.push_back({!tuned && strip_fills && enc_layer_strip(p, g, b, l) ? ENC_STRIP : enc_layer_tile(p, g, b, l) ? ENC_TILE : ENC_LAYERWISE, l, 1});
+  for (; l < n; ++l) {
+    const EncRoute r = !tuned && strip_fills && enc_layer_strip(p, g, b, l) ? ENC_STRIP : enc_layer_tile(p, g, b, l) ? ENC_TILE : ENC_LAYERWISE;
+    // behind the strip layers of a 28 x 28 block: the rest of the block, all of it tile-kernel layers, in one launch (a threshold
+    // of its own: one workgroup per frame fills the chip from 128 frames on, together with the neighbouring stream's call)
+    if (r == ENC_TILE && B >= p.chain28_min_batch && enc_chain28(p, g, b, l)) {
+      plan.push_back({ENC_CHAIN_TILE, l, n - l});
+      break;
+    }
+    plan.push_back({r, l, 1});
+  }
   return plan;
 }
 
