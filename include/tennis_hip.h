@@ -568,6 +568,21 @@ int tn_gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, float K, int 
  * GNMTDecoder.decode_seq (gnmt.py:254-304).  tgt (B, ld) int32 DEVICE tokens, first `steps`
  * columns are fed; logits (B, steps, V) fp32.  Needs a preceding tn_gnmt_encode. */
 int tn_gnmt_decode_seq(tn_gnmt *g, const int32_t *tgt, int ld, int steps, float *logits);
+/* The decoder's attention weights, the additional outputs of GNMTDecoder(output_attention=True) (gnmt.py:302-303,402-403):
+ * the scaled-Luong distribution over the T encoder steps of the last tn_gnmt_encode[_rows], exact zeros at and beyond a clip's
+ * valid_len.  Both calls are their namesakes with one more DEVICE output, which must not be NULL (TN_ERR_INVALID); the
+ * namesakes are the same code with no such output and launch what they always launched.
+ *   tn_gnmt_decode_seq_attention   attention (B, steps, T) fp32: decode_seq stacks the steps' weights (gnmt.py:302-303).
+ *   tn_gnmt_beam_search_attention  attention (B, beam, max_length + 1, T) fp32 with max_length the one given to tn_gnmt_create:
+ *                                  row i of hypothesis (b, k) holds the weights of the decoder step (gnmt.py:402-403) that
+ *                                  emitted samples[b, k, i + 1], followed through the beam reshuffling; rows whose token no
+ *                                  decoder step emitted (the -1 padding, the <eos> appended at max_length) are zeros.
+ *                                  The first call that asks allocates the steps' history inside the handle,
+ *                                  4 * max_length * max_batch * beam * max_src_len bytes (61.4 MB for 150 x 32 x 5 x 640),
+ *                                  released by tn_gnmt_destroy; a handle that never asks allocates nothing. */
+int tn_gnmt_decode_seq_attention(tn_gnmt *g, const int32_t *tgt, int ld, int steps, float *logits, float *attention);
+int tn_gnmt_beam_search_attention(tn_gnmt *g, int bos, int eos, float alpha, float K, int max_length, int32_t *samples,
+                                  float *scores, int32_t *valid_length, int *length_host, float *attention);
 /* MaskedSoftmaxCELoss [EXT gluonnlp] (train_gnmt.py:256,281): loss (B,) fp32. */
 int tn_masked_softmax_ce(tn_ctx *ctx, const float *logits, const int32_t *labels, int ld_labels,
                          const int32_t *valid_len, int batch, int steps, int vocab, float *loss);

@@ -236,11 +236,68 @@ def write_sentences(sentences, file_path):                             # utils/c
             of.write((u" ".join(sent) if isinstance(sent, (list, tuple)) else sent) + u"\n")
 
 
-def evaluate(data_loader, model, translator, data_train, table=None):
+def alignment_record(inst_id, attention, sample_valid_length, src_valid_length):
+    """One instance's record for ``evaluate(alignments=...)``: ``(instance id, weights (words, T_valid) float32)`` from the best beam's
+    attention rows ``attention`` (L - 1, T).  Row ``j`` belongs to token ``j + 1`` of the sample; ``evaluate`` writes out tokens
+    ``1 .. sample_valid_length - 2`` (between <bos> and <eos>), so rows ``0 .. sample_valid_length - 3`` stay, cut to the clip's valid steps."""
+    words = max(int(sample_valid_length) - 2, 0)
+    tv = max(min(int(round(float(src_valid_length))), attention.shape[1]), 0)
+    return int(inst_id), np.ascontiguousarray(attention[:words, :tv], dtype=np.float32)
+
+
+def save_alignments(file_path, records, frame_ids=None):
+    """``evaluate(alignments=...)``'s records as one ``.npz`` of flat arrays (``np.load(..., allow_pickle=False)`` reads it):
+    ``inst_ids`` (N,), ``words`` / ``steps`` (N,) = each record's shape, ``offsets`` (N + 1,) into ``weights`` (the records' rows,
+    concatenated and flattened), ``word_offsets`` (N + 1,) into ``argmax`` (the source step with the largest weight, per word), and -
+    with ``frame_ids`` = {instance id: the (video, frame number) of each source step, as ``CaptionSet.clip_frames`` / ``clip_table``
+    name it} - ``frame_offsets`` (N + 1,) into ``frame_videos`` (strings) and ``frame_numbers`` (int64).
+    Records are written in instance-id order."""
+    records = sorted(records, key=lambda r: r[0])
+    ids = np.array([r[0] for r in records], np.int64)
+    words = np.array([r[1].shape[0] for r in records], np.int64)
+    steps = np.array([r[1].shape[1] for r in records], np.int64)
+    offsets = np.concatenate([[0], np.cumsum(words * steps)]).astype(np.int64)
+    word_offsets = np.concatenate([[0], np.cumsum(words)]).astype(np.int64)
+    weights = np.concatenate([r[1].reshape(-1) for r in records]).astype(np.float32) if records else np.zeros(0, np.float32)
+    argmax = np.concatenate([r[1].argmax(axis=1) if r[1].size else np.zeros(r[1].shape[0], np.int64)
+                             for r in records]).astype(np.int32) if records else np.zeros(0, np.int32)
+    out = dict(inst_ids=ids, words=words, steps=steps, offsets=offsets, weights=weights, word_offsets=word_offsets, argmax=argmax)
+    if frame_ids is not None:
+        clips = [list(frame_ids[int(i)]) for i in ids]
+        out["frame_offsets"] = np.concatenate([[0], np.cumsum([len(c) for c in clips])]).astype(np.int64)
+        flat = [vf for c in clips for vf in c]
+        out["frame_videos"] = np.array([str(v) for v, _ in flat], dtype=np.str_) if flat else np.zeros(0, "<U1")
+        out["frame_numbers"] = np.array([int(f) for _, f in flat], np.int64)
+    np.savez(file_path, **out)
+
+
+def load_alignments(file_path):
+    """-> [(instance id, weights (words, steps), argmax (words,), [(video, frame number)] or None)] from ``save_alignments``' file."""
+    with np.load(file_path, allow_pickle=False) as z:
+        d = {k: z[k] for k in z.files}
+    out = []
+    for n, i in enumerate(d["inst_ids"]):
+        w = d["weights"][d["offsets"][n]:d["offsets"][n + 1]].reshape(int(d["words"][n]), int(d["steps"][n]))
+        am = d["argmax"][d["word_offsets"][n]:d["word_offsets"][n + 1]]
+        fo = d["frame_offsets"][n:n + 2] if "frame_offsets" in d else None
+        fr = None if fo is None else list(zip(d["frame_videos"][fo[0]:fo[1]].tolist(), d["frame_numbers"][fo[0]:fo[1]].tolist()))
+        out.append((int(i), w, am, fr))
+    return out
+
+
+def clip_frame_ids(dataset):
+    """{instance id: [(video, frame number)] per source step} of a ``CaptionSet`` (``clip_frames``; ``clip_table``'s
+    ``frames[idx[i, t]]`` is the same pair): what ``save_alignments`` stores next to the weights."""
+    return {i: dataset.clip_frames(i) for i in range(len(dataset))}
+
+
+def evaluate(data_loader, model, translator, data_train, table=None, alignments=None):
     """reference train_gnmt.py:264-302: teacher-forced MaskedSoftmaxCELoss + beam search; returns
     (avg_loss, translations ordered by instance id).  Everything numeric runs on the GPU.
     ``table``: the split's device-resident feature table; a loader that yields table rows (``bucketed_batches(rows=...)``: an int32
-    (B, T) source) is then encoded by ``encode_rows`` / ``translate_rows``, with the same results."""
+    (B, T) source) is then encoded by ``encode_rows`` / ``translate_rows``, with the same results.
+    ``alignments``: a list; one ``alignment_record`` per instance is appended to it - the best beam's attention weights over the clip's
+    valid steps, one row per word written out.  The return value does not change."""
     from .engine import masked_softmax_ce
     translation_out, all_inst_ids = [], []
     avg_loss_denom, avg_loss = 0, 0.0
@@ -263,10 +320,18 @@ def evaluate(data_loader, model, translator, data_train, table=None):
         all_inst_ids.extend(inst_ids.astype(np.int32).tolist())
         avg_loss += loss * (tgt_seq.shape[1] - 1)
         avg_loss_denom += (tgt_seq.shape[1] - 1)
-        samples, _, sample_valid_length = (translator.translate_rows(table, src, src_valid_length) if by_rows
-                                           else translator.translate(src, svl))   # :287-288
+        if alignments is None:
+            samples, _, sample_valid_length = (translator.translate_rows(table, src, src_valid_length) if by_rows
+                                               else translator.translate(src, svl))   # :287-288
+        else:
+            samples, _, sample_valid_length, att = (translator.translate_rows(table, src, src_valid_length, return_attention=True)
+                                                    if by_rows else translator.translate(src, svl, return_attention=True))
         max_score_sample = samples[:, 0, :].cpu().numpy()
         svl0 = sample_valid_length[:, 0].cpu().numpy()
+        if alignments is not None:
+            att0 = att[:, 0].cpu().numpy()
+            for i in range(att0.shape[0]):
+                alignments.append(alignment_record(inst_ids[i], att0[i], svl0[i], src_valid_length[i]))
         for i in range(max_score_sample.shape[0]):                     # :291-294
             translation_out.append([data_train.vocab.idx_to_token[ele]
                                     for ele in max_score_sample[i][1:(svl0[i] - 1)]])

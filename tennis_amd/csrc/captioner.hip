@@ -12,6 +12,10 @@
 // projection + beam update + the next step's gathered inputs) resp. dec_tf_cell1_kernel + the projection GEMM.
 // The whole token loop is enqueued on the stream with no per-step host sync; the host
 // looks at a device flag every 16 steps only to stop early once every beam has finished.
+// On request (tn_gnmt_decode_seq_attention / tn_gnmt_beam_search_attention, gnmt.py:302-303,402-403) the steps' attention weights
+// are returned too: teacher forcing stores them in place, the beam search keeps every step's rows in a history of
+// 4 * max_length * max_batch * beam * max_src_len bytes (61.4 MB for 150 x 32 x 5 x 640; allocated by the first search that asks,
+// never otherwise) and gathers the final hypotheses' rows along their back-pointers (beam_att_rows_kernel, beam_att_gather_kernel).
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -104,7 +108,8 @@ __global__ __launch_bounds__(kBeamThreads) void dec_attention_kernel(
     const float *__restrict__ kpT, const float *__restrict__ mem, const int32_t *__restrict__ valid_len,
     float *__restrict__ ctx, int beam, int rows, int T, int H, float *__restrict__ wsave = nullptr,
     const int32_t *__restrict__ tok = nullptr, const int32_t *__restrict__ par = nullptr, const float *__restrict__ ew = nullptr,
-    const float *__restrict__ p0 = nullptr, int split = 16) {
+    const float *__restrict__ p0 = nullptr, int split = 16, long wpitch = 0) {
+  // wsave != NULL: the row's T attention weights are stored at wsave + row * wpitch (wpitch 0: T, rows back to back)
   // ew != NULL (beam search, two decoder layers, from the second step on): the row's pre-activations are put together here,
   // g = ew[tok[row]] + p0[parent row] (dec_beam_kernel), and h_prev / c_prev are the PARENT row's (hprev / cprev then hold
   // the previous step's new states, one row per beam, pitch ldh / H)
@@ -157,7 +162,9 @@ __global__ __launch_bounds__(kBeamThreads) void dec_attention_kernel(
   __syncthreads();
   DEC_STAMP(1);
   // ---- scores: thread = (slice of H, four source steps); HG partial sums per step ----
-  const int S4 = (vl + 3) >> 2, CG = step_groups(S4, split), HG = kBeamThreads / CG;
+  // (the groups follow the PADDED length, as att_lds_bytes counts the partial rows: dealing a clip shorter than T over fewer
+  // threads would ask for more rows of pitch Tp than the launch has LDS for, once T > 256)
+  const int S4 = (vl + 3) >> 2, CG = step_groups(Tp >> 2, split), HG = kBeamThreads / CG;
   {
     const int hg = t / CG, hn_ = (H + HG - 1) / HG, h0 = hg * hn_, h1 = min(H, h0 + hn_);
     const float *kp = kpT + (long)b * H * Tp;
@@ -209,7 +216,7 @@ __global__ __launch_bounds__(kBeamThreads) void dec_attention_kernel(
     for (int s = lane; s < T; s += 64) {
       const float v = s < vl ? w[s] * rs : 0.f;
       w[s] = v;
-      if (wsave) wsave[r * T + s] = v;      // training keeps the attention weights
+      if (wsave) wsave[r * (wpitch ? wpitch : (long)T) + s] = v;      // training / the attention outputs keep the weights
     }
   }
   __syncthreads();
@@ -763,6 +770,61 @@ __global__ void beam_finalize_kernel(const int32_t *alive, int32_t *vlen, int32_
   vlen[id] += alive[id] ? 1 : 0;
 }
 
+// ---- attention weights of the final hypotheses (tn_gnmt_beam_search_attention) ----
+// While a search that asked for them runs, every step's dec_attention_kernel stores its R = B * beam rows into the step-major
+// history hist (steps, R, T): 4 * max_length * max_batch * beam * max_src_len bytes at the handle's capacities (61.4 MB at
+// config C5 with max_src_len 640), allocated by the first call that asks and never by a handle that does not.
+// Afterwards the alignments are put together in two launches:
+//   beam_att_rows_kernel   the walk of beam_samples_kernel again, keeping the ROW instead of the word: samples[b, k, i + 1]
+//                          was emitted by step i in the row of the hypothesis' ancestor at that step, par[i][cur];
+//                          rowtab (R, steps) holds that row, or -1 where no decoder step emitted the token (the -1 a
+//                          finished beam carries)
+//   beam_att_gather_kernel attention[b, k, i, :] = hist[i, rowtab[b * beam + k, i], :], exact zeros where the table says
+//                          -1 and for i >= steps (behind the search's last step, which is also where the sampler appends
+//                          <eos> to a beam still alive); one workgroup per (hypothesis, kAttGatherSteps steps), 16-byte
+//                          accesses when T is a multiple of 4 and the output is 16-byte aligned.
+__global__ __launch_bounds__(256) void beam_att_rows_kernel(const int32_t *__restrict__ bp_par, const int32_t *__restrict__ bp_word,
+                                                            int32_t *__restrict__ rowtab, int steps, int R, int beam) {
+  __shared__ int32_t par[kSampChunk * 16], word[kSampChunk * 16];
+  const int b = blockIdx.x, t = threadIdx.x;
+  int cur = t;
+  int32_t *dst = rowtab + ((long)b * beam + (t < beam ? t : 0)) * steps;
+  for (int hi = steps; hi > 0; hi -= kSampChunk) {
+    const int lo = hi > kSampChunk ? hi - kSampChunk : 0, n = hi - lo;
+    __syncthreads();
+    for (int i = t; i < n * beam; i += 256) {
+      const int s = i / beam, k = i - s * beam;
+      par[i] = bp_par[(long)(lo + s) * R + b * beam + k];
+      word[i] = bp_word[(long)(lo + s) * R + b * beam + k];
+    }
+    __syncthreads();
+    if (t < beam)
+      for (int s = n - 1; s >= 0; --s) {
+        const int p = par[s * beam + cur];
+        dst[lo + s] = word[s * beam + cur] >= 0 ? b * beam + p : -1;
+        cur = p;
+      }
+  }
+}
+
+constexpr int kAttGatherSteps = 8;
+template <bool VEC>
+__global__ __launch_bounds__(256) void beam_att_gather_kernel(const float *__restrict__ hist, const int32_t *__restrict__ rowtab,
+                                                              float *__restrict__ out, int steps, int R, int T, int LA) {
+  const int hyp = blockIdx.x, i0 = blockIdx.y * kAttGatherSteps, i1 = min(LA, i0 + kAttGatherSteps), t = threadIdx.x;
+  for (int i = i0; i < i1; ++i) {
+    const int row = i < steps ? rowtab[(long)hyp * steps + i] : -1;
+    float *d = out + ((long)hyp * LA + i) * T;
+    const float *sp = row >= 0 ? hist + ((long)i * R + row) * T : nullptr;
+    if (VEC) {
+      for (int c = t; c < (T >> 2); c += 256)
+        ((float4 *)d)[c] = sp ? ((const float4 *)sp)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      for (int c = t; c < T; c += 256) d[c] = sp ? sp[c] : 0.f;
+    }
+  }
+}
+
 // MaskedSoftmaxCELoss [EXT gluonnlp]: per sample, mean over the L time steps of
 // -log_softmax(logits[b,t])[label[b,t]] * (t < valid_len[b]).  One workgroup per sample.
 __global__ __launch_bounds__(256) void masked_ce_kernel(const float *__restrict__ logits, const int32_t *__restrict__ labels,
@@ -1109,6 +1171,10 @@ struct tn_gnmt {
   int K1p;                 // pitch of w1cp / w1x / sx1p, see kGemmPitchPad
   bool ew_ready;
   int32_t *bp_par, *bp_word;   // (maxL, R) back-pointers of the search
+  // attention weights on request (tn_gnmt_beam_search_attention): the steps' rows (max_length, R, maxT) and the final
+  // hypotheses' ancestor rows (R, max_length); null until a search asks for the weights (beam_att_rows_kernel)
+  float *att_hist;
+  int32_t *att_rows;
   int B, T;
 };
 
@@ -1335,9 +1401,22 @@ static int gnmt_encode(tn_gnmt *g, const float *src, const float *table, int n_r
 // BeamSearchTranslator.translate after tn_gnmt_encode.  samples (B,beam,max_length+2) int32 padded
 // with -1, scores (B,beam), valid_length (B,beam) are DEVICE buffers; *length_host receives the
 // number of valid columns of `samples` (what the reference's sampler would have returned).
+static int gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, float K, int max_length, int32_t *samples, float *scores,
+                            int32_t *valid_length, int *length_host, float *attention);
 extern "C" int tn_gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, float K, int max_length, int32_t *samples,
                                    float *scores, int32_t *valid_length, int *length_host) {
   TN_REQUIRE(g && samples && scores && valid_length && length_host, "tn_gnmt_beam_search: null argument");
+  return gnmt_beam_search(g, bos, eos, alpha, K, max_length, samples, scores, valid_length, length_host, nullptr);
+}
+// tn_gnmt_beam_search that also returns the final hypotheses' attention weights (B, beam, maxL - 1, T), what the reference's
+// decoder hands up as step_additional_outputs with output_attention=True (gnmt.py:302-303,402-403)
+extern "C" int tn_gnmt_beam_search_attention(tn_gnmt *g, int bos, int eos, float alpha, float K, int max_length, int32_t *samples,
+                                             float *scores, int32_t *valid_length, int *length_host, float *attention) {
+  TN_REQUIRE(g && samples && scores && valid_length && length_host && attention, "tn_gnmt_beam_search_attention: null argument");
+  return gnmt_beam_search(g, bos, eos, alpha, K, max_length, samples, scores, valid_length, length_host, attention);
+}
+static int gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, float K, int max_length, int32_t *samples, float *scores,
+                            int32_t *valid_length, int *length_host, float *attention) {
   TN_REQUIRE(g->B > 0, "tn_gnmt_beam_search: call tn_gnmt_encode first");
   TN_REQUIRE(max_length >= 1 && max_length + 2 <= g->maxL, "tn_gnmt_beam_search: max_length exceeds the handle");
   TN_REQUIRE(bos >= 0 && bos < g->V && eos >= 0 && eos < g->V, "tn_gnmt_beam_search: bos/eos outside the vocabulary");
@@ -1359,6 +1438,18 @@ extern "C" int tn_gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, fl
   if (int rc = allow_lds(dec_attention_kernel<1>, att_lds)) return rc;
   if (int rc = nbm == 4 ? allow_lds(dec_beam_kernel<4>, beam_lds) : nbm == 5 ? allow_lds(dec_beam_kernel<5>, beam_lds)
                : nbm == 8 ? allow_lds(dec_beam_kernel<8>, beam_lds) : allow_lds(dec_beam_kernel<16>, beam_lds)) return rc;
+  if (attention && !(g->att_hist && g->att_rows)) {      // the first search that asks: history and row table at the handle's capacities
+    const size_t Rmax = (size_t)g->maxB * beam, Smax = (size_t)(g->maxL - 2);
+    if (!g->att_hist) g->att_hist = g->pool.alloc<float>(Smax * Rmax * g->maxT);
+    if (!g->att_rows) g->att_rows = g->pool.alloc<int32_t>(Rmax * Smax);
+    if (!g->att_hist || !g->att_rows) {
+      g->pool.failed = false;
+      tn_set_error("tn_gnmt_beam_search_attention: device allocation failed");
+      return TN_ERR_NOMEM;
+    }
+  }
+  float *const hist = attention ? g->att_hist : nullptr;      // step i's rows at hist + i * R * T
+  const size_t hist_step = (size_t)R * T;
   TN_HIP_CHECK(hipMemsetAsync(g->samples[0], 0xff, sizeof(int32_t) * (size_t)R * L, s));
   // decoder layer i starts from encoder layer i's state, the BACKWARD direction's for a bidirectional layer (gnmt.py:146-150,224-252)
   const int NL = g->NL, nmid = NL - 2;
@@ -1405,12 +1496,14 @@ extern "C" int tn_gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, fl
       hipLaunchKernelGGL(dec_attention_kernel<1>, dim3(R), dim3(kBeamThreads), att_lds, s, (const float *)g->g0,
                          (const float *)(g->sx0 + E + H), K0, (const float *)g->c0cur, lstm ? 1 : 0, h0buf[cur], c0buf[cur], x_after0, ld_after0,
                          (const float *)g->keyprojT, (const float *)g->mem, (const int32_t *)g->vl, g->ctxn, beam, 1, T, H,
-                         (float *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, (const float *)nullptr, (const float *)nullptr, asplit);
+                         hist ? hist + (size_t)i * hist_step : (float *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr,
+                         (const float *)nullptr, (const float *)nullptr, asplit, (long)T);
     } else {
       hipLaunchKernelGGL(dec_attention_kernel<1>, dim3(R), dim3(kBeamThreads), att_lds, s, (const float *)nullptr,
                          (const float *)h0buf[cur ^ 1], H, (const float *)c0buf[cur ^ 1], lstm ? 1 : 0, h0buf[cur], c0buf[cur], x_after0, ld_after0,
                          (const float *)g->keyprojT, (const float *)g->mem, (const int32_t *)g->vl, g->ctxn, beam, 1, T, H,
-                         (float *)nullptr, (const int32_t *)g->tok, (const int32_t *)g->parent, (const float *)g->ew, (const float *)g->p0, asplit);
+                         hist ? hist + (size_t)i * hist_step : (float *)nullptr, (const int32_t *)g->tok, (const int32_t *)g->parent,
+                         (const float *)g->ew, (const float *)g->p0, asplit, (long)T);
     }
     for (int j = 0; j < nmid; ++j) {
       GnmtMid &m = g->mid[j];
@@ -1452,6 +1545,18 @@ extern "C" int tn_gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, fl
   // the token prefixes, from the back-pointers of the steps taken
   hipLaunchKernelGGL(beam_samples_kernel, dim3(B), dim3(256), 0, s, (const int32_t *)g->bp_par, (const int32_t *)g->bp_word, g->samples[0], L,
                      steps_done, R, beam, bos);
+  if (attention) {      // the hypotheses' ancestor rows, then their weights out of the history
+    const int LA = L - 1;
+    hipLaunchKernelGGL(beam_att_rows_kernel, dim3(B), dim3(256), 0, s, (const int32_t *)g->bp_par, (const int32_t *)g->bp_word, g->att_rows,
+                       steps_done, R, beam);
+    const dim3 grid(R, (LA + kAttGatherSteps - 1) / kAttGatherSteps);
+    if (T % 4 == 0 && ((uintptr_t)attention & 15) == 0)
+      hipLaunchKernelGGL(beam_att_gather_kernel<true>, grid, dim3(256), 0, s, (const float *)hist, (const int32_t *)g->att_rows, attention,
+                         steps_done, R, T, LA);
+    else
+      hipLaunchKernelGGL(beam_att_gather_kernel<false>, grid, dim3(256), 0, s, (const float *)hist, (const int32_t *)g->att_rows, attention,
+                         steps_done, R, T, LA);
+  }
   if (!all_dead) {
     hipLaunchKernelGGL(beam_finalize_kernel, dim3((R + 255) / 256), dim3(256), 0, s, g->alive, g->vlen, g->samples[0], L, steps_done + 1, R, eos);
     *length_host = steps_done + 2;
@@ -1474,9 +1579,20 @@ extern "C" int tn_gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, fl
 // models/captioning/gnmt.py:254-304) as called by evaluate() (train_gnmt.py:280): feeds
 // tgt[:, 0..L-1] one step at a time from the encoder state left by tn_gnmt_encode and writes the
 // projected logits (B, L, V).  tgt is a DEVICE (B, ld) int32 array.
+static int gnmt_decode_seq(tn_gnmt *g, const int32_t *tgt, int ld, int steps, float *logits, float *attention);
 extern "C" int tn_gnmt_decode_seq(tn_gnmt *g, const int32_t *tgt, int ld, int steps, float *logits) {
   TN_REQUIRE(g && tgt && logits, "tn_gnmt_decode_seq: null argument");
-  TN_REQUIRE(g->B > 0, "tn_gnmt_decode_seq: call tn_gnmt_encode first");
+  return gnmt_decode_seq(g, tgt, ld, steps, logits, nullptr);
+}
+// tn_gnmt_decode_seq that also returns every step's attention weights (B, steps, T): decode_seq with output_attention=True
+// stacks the attention cell's weights as additional outputs (gnmt.py:302-303,402-403).  The step kernel stores row b of step i
+// straight at attention[b, i, :] (row pitch steps * T).
+extern "C" int tn_gnmt_decode_seq_attention(tn_gnmt *g, const int32_t *tgt, int ld, int steps, float *logits, float *attention) {
+  TN_REQUIRE(g && tgt && logits && attention, "tn_gnmt_decode_seq_attention: null argument");
+  return gnmt_decode_seq(g, tgt, ld, steps, logits, attention);
+}
+static int gnmt_decode_seq(tn_gnmt *g, const int32_t *tgt, int ld, int steps, float *logits, float *attention) {
+  TN_REQUIRE(g->B > 0, attention ? "tn_gnmt_decode_seq_attention: call tn_gnmt_encode first" : "tn_gnmt_decode_seq: call tn_gnmt_encode first");
   TN_REQUIRE(steps >= 1 && ld >= steps, "tn_gnmt_decode_seq: bad target length");
   TN_ON_DEVICE(g->ctx->device);
   hipStream_t s = g->ctx->stream;
@@ -1506,7 +1622,8 @@ extern "C" int tn_gnmt_decode_seq(tn_gnmt *g, const int32_t *tgt, int ld, int st
     hipLaunchKernelGGL(dec_attention_kernel<1>, dim3(R), dim3(kBeamThreads), att_lds, s, (const float *)g->g0,
                        (const float *)(g->sx0 + E + H), K0, (const float *)g->c0cur, lstm ? 1 : 0, g->h0n, g->c0n, x_after0, K1,
                        (const float *)g->keyprojT, (const float *)g->mem, (const int32_t *)g->vl, g->ctxn, 1, 1, T, H,
-                       (float *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, (const float *)nullptr, (const float *)nullptr, asplit);
+                       attention ? attention + (size_t)i * T : (float *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr,
+                       (const float *)nullptr, (const float *)nullptr, asplit, (long)steps * T);
     for (int j = 0; j < nmid; ++j) {
       GnmtMid &m = g->mid[j];
       rc = launch_linear_f32_lat(m.sx, K1, m.w, K1, m.b, m.g, 4 * H, R, 4 * H, K1, s);

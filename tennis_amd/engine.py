@@ -459,7 +459,7 @@ class GNMTCaptioner(_Handle):
                                          1 if use_residual else 0, C.byref(h)), "tn_gnmt_create")
         del keep
         self.handle = h
-        self._batch = 0
+        self._batch = self._steps = 0
 
     def encode(self, src: torch.Tensor, valid_length: torch.Tensor) -> torch.Tensor:
         src = src.contiguous().float()
@@ -467,7 +467,7 @@ class GNMTCaptioner(_Handle):
         vl = valid_length.to(device=src.device).round().to(torch.int32).contiguous()
         mem = torch.empty((b, t, self.hidden), dtype=torch.float32, device=src.device)
         check(self.lib.tn_gnmt_encode(self.handle, ptr(src), ptr(vl), b, t, ptr(mem)), "tn_gnmt_encode")
-        self._batch = b
+        self._batch, self._steps = b, t
         return mem
 
     def encode_rows(self, table: torch.Tensor, idx, valid_length) -> torch.Tensor:
@@ -482,24 +482,41 @@ class GNMTCaptioner(_Handle):
         mem = torch.empty((b, t, self.hidden), dtype=torch.float32, device=table.device)
         check(self.lib.tn_gnmt_encode_rows(self.handle, ptr(table), table.shape[0], table.stride(0), ptr(idx), ptr(vl), b, t, ptr(mem)),
               "tn_gnmt_encode_rows")
-        self._batch = b
+        self._batch, self._steps = b, t
         return mem
 
-    def decode_seq(self, tgt: torch.Tensor) -> torch.Tensor:
-        """Teacher-forced logits (B, L, V) for target tokens (B, L) after encode()."""
+    def decode_seq(self, tgt: torch.Tensor, return_attention: bool = False):
+        """Teacher-forced logits (B, L, V) for target tokens (B, L) after encode().  ``return_attention``: ``(logits, attention)``
+        with the decoder's attention weights (B, L, T) over the T encoder steps of the last ``encode`` / ``encode_rows`` (what
+        ``GNMTDecoder(output_attention=True).decode_seq`` stacks, reference gnmt.py:302-303), zeros at and beyond a clip's
+        ``valid_length``."""
         tgt = tgt.to(device=torch.device("cuda", self.ctx.device)).round().to(torch.int32).contiguous()
         b, l = tgt.shape
         logits = torch.empty((b, l, self.vocab), dtype=torch.float32, device=tgt.device)
+        if return_attention:
+            att = torch.empty((b, l, self._steps), dtype=torch.float32, device=tgt.device)
+            check(self.lib.tn_gnmt_decode_seq_attention(self.handle, ptr(tgt), l, l, ptr(logits), ptr(att)),
+                  "tn_gnmt_decode_seq_attention")
+            return logits, att
         check(self.lib.tn_gnmt_decode_seq(self.handle, ptr(tgt), l, l, ptr(logits)), "tn_gnmt_decode_seq")
         return logits
 
-    def beam_search(self, bos: int, eos: int, alpha: float = 1.0, K: float = 5.0, max_length: int | None = None):
+    def beam_search(self, bos: int, eos: int, alpha: float = 1.0, K: float = 5.0, max_length: int | None = None,
+                    return_attention: bool = False):
+        """``(samples (B, beam, n), scores, valid_length)``; with ``return_attention`` a fourth tensor ``attention (B, beam, n - 1, T)``:
+        row ``i`` of a hypothesis holds the weights of the decoder step that emitted its token ``i + 1``, followed through the
+        beam reshuffling, zeros where no step emitted the token (the ``-1`` padding, an ``<eos>`` appended at ``max_length``)."""
         ml = self.max_length if max_length is None else max_length
         b, dev = self._batch, torch.device("cuda", self.ctx.device)
         samples = torch.empty((b, self.beam, self.max_length + 2), dtype=torch.int32, device=dev)
         scores = torch.empty((b, self.beam), dtype=torch.float32, device=dev)
         vlen = torch.empty((b, self.beam), dtype=torch.int32, device=dev)
         n = C.c_int(0)
+        if return_attention:
+            att = torch.empty((b, self.beam, self.max_length + 1, max(self._steps, 1)), dtype=torch.float32, device=dev)
+            check(self.lib.tn_gnmt_beam_search_attention(self.handle, bos, eos, alpha, K, ml, ptr(samples), ptr(scores), ptr(vlen),
+                                                         C.byref(n), ptr(att)), "tn_gnmt_beam_search_attention")
+            return samples[:, :, :n.value].contiguous(), scores, vlen, att[:, :, :n.value - 1].contiguous()
         check(self.lib.tn_gnmt_beam_search(self.handle, bos, eos, alpha, K, ml, ptr(samples), ptr(scores), ptr(vlen),
                                            C.byref(n)), "tn_gnmt_beam_search")
         return samples[:, :, :n.value].contiguous(), scores, vlen

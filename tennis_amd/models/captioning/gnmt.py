@@ -55,7 +55,13 @@ class GNMTEncoder(Block):
 
 
 class GNMTDecoder(Block):
-    """reference gnmt.py:163-404."""
+    """reference gnmt.py:163-404.
+
+    ``output_attention`` is kept as an attribute and changes no return value here: in the reference it makes ``decode_seq`` / the step
+    hand the attention weights up as additional outputs (gnmt.py:302-303,402-403), but gluonnlp's sampler never returns additional
+    outputs and this ``NMTModel`` has no forward of its own.  The weights are asked for where the decoder runs:
+    ``GNMTCaptioner.decode_seq(tgt, return_attention=True)``, ``GNMTCaptioner.beam_search(..., return_attention=True)``,
+    ``BeamSearchTranslator.translate / translate_rows(..., return_attention=True)`` and ``captions.evaluate(..., alignments=[])``."""
 
     def __init__(self, cell_type="lstm", attention_cell="scaled_luong", num_layers=2, hidden_size=128, dropout=0.0,
                  use_residual=True, output_attention=False, prefix=None, **kwargs):
