@@ -263,11 +263,25 @@ int tn_window_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int hid
 int tn_window_head_project(tn_window_head *h, const float *feats, int rows);
 int tn_window_head_forward(tn_window_head *h, const int32_t *centre, const int32_t *lo, const int32_t *hi, int samples,
                            int window, int stride, float *pooled, float *logits);
+/* forward over a row TABLE instead of (centre, lo, hi): the evaluation loop of reference evaluate.py:274-303 for a split whose
+ * windows (dataset.py:190-201) have no arithmetic form - thinned-out or scattered samples, a stride that is no multiple of
+ * `every`, window frames that are no sample (TennisSet.window_table) - and for CNNRNN on frames (definitions.py:104-109), whose
+ * rows the model's own backbone produced.  idx (samples, window) int32 DEVICE, row-major: step t of sample b reads row
+ * clamp(idx[b * window + t], 0, rows-1) of the projected matrix, unconditionally; a negative entry is row 0, not a zero row.
+ * Runs after tn_window_head_project, with the limits and errors of tn_window_head_forward (samples <= max_samples, fewer than
+ * 2^30 table entries); a table that spells out a (centre, lo, hi, stride) window gives that call's bits.  Does not allocate. */
+int tn_window_head_forward_rows(tn_window_head *h, const int32_t *idx, int samples, int window, float *pooled /* may be NULL */,
+                                float *logits);
 int tn_window_head_destroy(tn_window_head *h);
 /* TemporalPooling.forward in feature mode over the same windows (definitions.py:66-69 on the (B, W, F) batch of
  * dataset.py:190-213): feats (rows, feat) -> y (samples, feat), max or mean over the window's gathered rows. */
 int tn_temporal_pool_windows(tn_ctx *ctx, const float *feats, int rows, int feat, const int32_t *centre, const int32_t *lo,
                              const int32_t *hi, int samples, int window, int stride, tn_pool_kind kind, float *y);
+/* ... and over a row table (definitions.py:66-69 on the batch of dataset.py:190-201 for any split layout, and for
+ * TemporalPooling on frames, evaluate.py:242-244): y[b] = max / mean over t ascending of row clamp(idx[b * window + t], 0,
+ * rows-1); idx (samples, window) int32 DEVICE.  The bits of tn_temporal_pool_windows on a table that spells out its windows. */
+int tn_temporal_pool_rows(tn_ctx *ctx, const float *feats, int rows, int feat, const int32_t *idx, int samples, int window,
+                          tn_pool_kind kind, float *y);
 
 /* ---- temporal-head training step ------------------------------ */
 /* bi-GRU / bi-LSTM(hidden) (`kind`; CNNRNN type='gru'|'lstm', definitions.py:93-96; LSTM gates [i,f,g,o]) over

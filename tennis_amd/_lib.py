@@ -93,8 +93,10 @@ _SIGS = {
                                         C.c_int, C.c_int, C.POINTER(_P)]),
     "tn_window_head_project": (C.c_int, [_P, _P, C.c_int]),
     "tn_window_head_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tn_window_head_forward_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "tn_window_head_destroy": (C.c_int, [_P]),
     "tn_temporal_pool_windows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "tn_temporal_pool_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "tn_dbg_window_head_rows_per_group": (C.c_int, [_P, C.c_int]),
     "tn_prf1_update": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "tn_head_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_char_p, C.c_int,

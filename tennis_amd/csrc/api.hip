@@ -261,6 +261,22 @@ extern "C" int tn_window_head_forward(tn_window_head *h, const int32_t *centre, 
   return launch_linear_f32(p, 2 * H, h->wd, 2 * H, h->bd, logits, h->C, samples, h->C, 2 * H, 0, s);
 }
 
+extern "C" int tn_window_head_forward_rows(tn_window_head *h, const int32_t *idx, int samples, int window, float *pooled,
+                                           float *logits) {
+  TN_REQUIRE(h && idx && logits, "tn_window_head_forward_rows: null argument");
+  TN_REQUIRE(h->rows > 0, "tn_window_head_forward_rows: no projected matrix (call tn_window_head_project first)");
+  TN_REQUIRE(samples > 0 && samples <= h->max_samples, "tn_window_head_forward_rows: samples must be in [1, max_samples]");
+  TN_REQUIRE(window >= 1, "tn_window_head_forward_rows: window must be >= 1");
+  TN_ON_DEVICE(h->ctx->device);
+  hipStream_t s = h->ctx->stream;
+  const int H = h->H;
+  float *p = pooled ? pooled : h->pooled;
+  const int rc = launch_rnn_window_rows(h->gates, h->gi, 2 * h->gates * H, h->rows, h->whT, h->bh, idx, p, samples, window, H,
+                                        h->nb, s);
+  if (rc) return rc;
+  return launch_linear_f32(p, 2 * H, h->wd, 2 * H, h->bd, logits, h->C, samples, h->C, 2 * H, 0, s);
+}
+
 extern "C" int tn_dbg_window_head_rows_per_group(tn_window_head *h, int nb) {
   TN_REQUIRE(h, "tn_dbg_window_head_rows_per_group: null argument");
   TN_REQUIRE(nb == 0 || nb == 4 || nb == 2 * h->gates, "tn_dbg_window_head_rows_per_group: 0 (default), 4 or twice the gates");
@@ -285,6 +301,16 @@ extern "C" int tn_temporal_pool_windows(tn_ctx *ctx, const float *feats, int row
   TN_REQUIRE(kind == TN_POOL_MAX || kind == TN_POOL_MEAN, "tn_temporal_pool_windows: unknown pool kind");
   TN_ON_DEVICE(ctx->device);
   return launch_temporal_pool_windows(feats, rows, feat, centre, lo, hi, samples, window, stride, (int)kind, y, ctx->stream);
+}
+
+extern "C" int tn_temporal_pool_rows(tn_ctx *ctx, const float *feats, int rows, int feat, const int32_t *idx, int samples,
+                                     int window, tn_pool_kind kind, float *y) {
+  TN_REQUIRE(ctx && feats && idx && y, "tn_temporal_pool_rows: null argument");
+  TN_REQUIRE(rows > 0 && feat > 0 && samples > 0, "tn_temporal_pool_rows: bad shape");
+  TN_REQUIRE(window >= 1, "tn_temporal_pool_rows: window must be >= 1");
+  TN_REQUIRE(kind == TN_POOL_MAX || kind == TN_POOL_MEAN, "tn_temporal_pool_rows: unknown pool kind");
+  TN_ON_DEVICE(ctx->device);
+  return launch_temporal_pool_rows(feats, rows, feat, idx, samples, window, (int)kind, y, ctx->stream);
 }
 
 // ---- temporal-head training step -----------------------------------------------------

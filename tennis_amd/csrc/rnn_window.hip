@@ -8,6 +8,9 @@
 //
 //   row(b, t) = clamp(centre[b] + (t - T/2) * stride, lo[b], hi[b])      (TennisSet.window_frames in units of matrix rows)
 //   and then clamp(row, 0, rows - 1), unconditionally: no content of centre / lo / hi makes a kernel read outside its input.
+//
+// The TABLE form (TAB) of both kernels takes the rows from an index table instead (TennisSet.window_table: any sample layout):
+//   row(b, t) = clamp(idx[b * T + t], 0, rows - 1)      (a negative entry is row 0, not a zero row)
 #include "common.h"
 #include "rnn_dot.h"
 #include "rnn_window.h"
@@ -33,7 +36,11 @@ __device__ __forceinline__ long window_row(int centre, int lo, int hi, int t, in
 //   * DPP (H % 16 == 0): h is not read per FMA - a lane reads 16 bytes per 16 k-values and the FMAs take h through
 //     quad_perm (rnn_dot.h), 4 x fewer LDS instructions; KR = 128 (H == 128): the thread's whole weight column lives in
 //     registers for all T steps, nothing of W_hh is re-read.
-template <int G, int NB, int KR, bool DPP, int MAXT>
+// TAB: `centre` is the (B, T) row table, lo / hi / stride are not read.  The table adds a dependent load (index -> gi row) in front
+// of the gi request, so the indices run one step ahead: step s requests its gi values through the index registers that step s - 1
+// loaded (one register per unit the thread finishes) and then requests the indices of step s + 1; both requests are in flight
+// behind the dot product, and the gi request at the top of a step never waits on an index load.
+template <int G, int NB, int KR, bool DPP, int MAXT, bool TAB>
 __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
     const float *__restrict__ gi, int ldgi, int rows,   // [rows][2*G*H] i2h + b_i2h of every row of the feature matrix
     const float *__restrict__ whT,                      // [2][H][G*H]
@@ -60,6 +67,17 @@ __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
 
   // the units this thread finishes: idx = j + m*GH -> (sample b0 + idx / H, unit idx % H)
   int cen[MI], wlo[MI], whi[MI];
+  // TAB: byte offset of the row of unit 0's sample in the table (B * T < 2^30: the launcher checks); unit m belongs to the
+  // sample m * G further on (idx / H = j / H + m * G): that distance and the step are uniform and go into the scalar base of the load
+  int jb = 0, ju = 0;
+  unsigned tab = 0;
+  int gtab = 0;                    // ... and every unit of a thread is the same u = (j + m * GH) % H = j % H
+  if constexpr (TAB) {
+    jb = j / H, ju = j - jb * H;
+    tab = (unsigned)(b0 + jb) * (unsigned)T * 4u;
+    gtab = dir * GH + ju;
+  }
+  int nxt[MI];                     // TAB: the table entry of the step to come
   bool live[MI];
   float hmax[MI];
 #pragma unroll
@@ -67,9 +85,13 @@ __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
     const int idx = j + m * GH;
     const int bg = b0 + idx / H;
     live[m] = idx < NB * H && bg < B;
-    cen[m] = live[m] ? centre[bg] : 0;
-    wlo[m] = live[m] ? lo[bg] : 0;
-    whi[m] = live[m] ? hi[bg] : 0;
+    if constexpr (TAB) {
+      nxt[m] = live[m] ? *(const int32_t *)((const char *)centre + ((size_t)m * G * T + (dir ? T - 1 : 0)) * 4 + tab) : 0;
+    } else {
+      cen[m] = live[m] ? centre[bg] : 0;
+      wlo[m] = live[m] ? lo[bg] : 0;
+      whi[m] = live[m] ? hi[bg] : 0;
+    }
     hmax[m] = 0.f;
   }
   for (int i = j; i < NB * H; i += GH) {
@@ -82,11 +104,18 @@ __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
     const int t = dir ? T - 1 - s : s;
     // this step's input pre-activations of the units the thread finishes below (requested now, used after the barrier)
     float gq[MI][G];
+    const int tn = dir ? max(t - 1, 0) : min(t + 1, T - 1);      // TAB: the step to come (the last step asks for its own again)
 #pragma unroll
     for (int m = 0; m < MI; ++m) {
       if (live[m]) {
         const int u = (j + m * GH) % H;
-        const float *g = gi + window_row(cen[m], wlo[m], whi[m], t, T, stride, rows) * ldgi + dir * GH + u;
+        const float *g;
+        if constexpr (TAB) {
+          g = gi + ((long)min(max(nxt[m], 0), rows - 1) * ldgi + gtab);
+          nxt[m] = *(const int32_t *)((const char *)centre + ((size_t)m * G * T + tn) * 4 + tab);
+        } else {
+          g = gi + window_row(cen[m], wlo[m], whi[m], t, T, stride, rows) * ldgi + dir * GH + u;
+        }
 #pragma unroll
         for (int e = 0; e < G; ++e) gq[m][e] = g[e * H];
       }
@@ -156,7 +185,16 @@ __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
     for (int m = 0; m < MI; ++m) {
       if (!live[m]) continue;
       const int idx = j + m * GH;
-      const int b = idx / H, u = idx - b * H;
+      int b, u;
+      if constexpr (TAB) {
+        // the same (b, u), from the thread's one division; the empty asm keeps the LDS addresses below from being hoisted out of
+        // the step loop into registers of their own (with them the plain GRU form at NB = 6 went over its 128 registers into
+        // scratch): a few integer instructions per step instead
+        b = jb + m * G, u = ju;
+        asm volatile("" : "+v"(b), "+v"(u));
+      } else {
+        b = idx / H, u = idx - b * H;
+      }
       const float *q = gh + b * GH;
       float hn;
       if (G == 3) {
@@ -189,28 +227,34 @@ __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
 
 // F.max / F.mean over the gathered rows of the feature matrix itself (definitions.py:66-69 in feature mode), t ascending as in
 // temporal_pool_kernel (rnn.hip): x (rows, F) -> y (B, F)
+template <bool TAB>
 __global__ void temporal_pool_windows_kernel(const float *__restrict__ x, int rows, int F, const int32_t *__restrict__ centre,
                                              const int32_t *__restrict__ lo, const int32_t *__restrict__ hi, int B, int T,
                                              int stride, int kind, float *__restrict__ y) {
   const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= (long)B * F) return;
   const int b = (int)(id / F), f = (int)(id % F);
-  const int c = centre[b], l = lo[b], h = hi[b];
+  int c = 0, l = 0, h = 0;
+  if constexpr (!TAB) c = centre[b], l = lo[b], h = hi[b];
+  const int32_t *tab = centre + (long)b * T;      // TAB: `centre` is the (B, T) row table
   float acc = kind == TN_POOL_MAX ? -INFINITY : 0.f;
   for (int t = 0; t < T; ++t) {
-    const float v = x[window_row(c, l, h, t, T, stride, rows) * F + f];
+    long row;
+    if constexpr (TAB) row = min(max(tab[t], 0), rows - 1);
+    else row = window_row(c, l, h, t, T, stride, rows);
+    const float v = x[row * F + f];
     acc = kind == TN_POOL_MAX ? fmaxf(acc, v) : acc + v;
   }
   y[id] = kind == TN_POOL_MAX ? acc : acc / (float)T;
 }
 
-template <int G, int NB>
+template <int G, int NB, bool TAB>
 int launch_window_nb(const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *centre,
                      const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, hipStream_t s) {
   const dim3 grid((B + NB - 1) / NB, 2), block(G * H);
   const size_t lds = (size_t)(NB * H * 2 + NB * G * H) * sizeof(float);
 #define TN_WIN_LAUNCH(KR_, DPP_, MT_)                                                                                          \
-  hipLaunchKernelGGL((rnn_window_kernel<G, NB, KR_, DPP_, MT_>), grid, block, lds, s, gi, ldgi, rows, whT, bh, centre, lo, hi, \
+  hipLaunchKernelGGL((rnn_window_kernel<G, NB, KR_, DPP_, MT_, TAB>), grid, block, lds, s, gi, ldgi, rows, whT, bh, centre, lo, hi, \
                      pooled, B, T, stride, H)
   if (H == 128) TN_WIN_LAUNCH(128, true, 512);          // the fast route: CNNRNN's width, the weight column in registers
   else if (H % 16 == 0) TN_WIN_LAUNCH(0, true, 1024);
@@ -224,31 +268,58 @@ int launch_window_nb(const float *gi, int ldgi, int rows, const float *whT, cons
 
 int rnn_window_default_nb(int gates) { return 2 * gates; }
 
-int launch_rnn_window(int gates, const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *centre,
-                      const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, int nb,
-                      hipStream_t s) {
+namespace {
+
+template <bool TAB>
+int launch_window(int gates, const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *centre,
+                  const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, int nb, hipStream_t s) {
   TN_REQUIRE(gates == 3 || gates == 4, "rnn_window: gates must be 3 or 4");
   TN_REQUIRE(gates * H <= 1024 && H % 4 == 0, "rnn_window: the windowed kernel serves gates*hidden <= 1024 and hidden % 4 == 0");
   TN_REQUIRE(rows > 0 && B > 0 && T > 0 && stride > 0, "rnn_window: bad shape");
+  TN_REQUIRE(!TAB || (long)B * T < (1L << 30), "rnn_window: the row table must hold fewer than 2^30 entries");
   if (nb == 0) nb = rnn_window_default_nb(gates);
   if ((size_t)nb * (2 + gates) * H * sizeof(float) > 64 * 1024) nb = 4;      // (the LDS a workgroup may ask for without an attribute)
 #define TN_WIN_ARGS gi, ldgi, rows, whT, bh, centre, lo, hi, pooled, B, T, stride, H, s
   if (gates == 3) {
-    if (nb == 4) return launch_window_nb<3, 4>(TN_WIN_ARGS);
-    if (nb == 6) return launch_window_nb<3, 6>(TN_WIN_ARGS);
+    if (nb == 4) return launch_window_nb<3, 4, TAB>(TN_WIN_ARGS);
+    if (nb == 6) return launch_window_nb<3, 6, TAB>(TN_WIN_ARGS);
   } else {
-    if (nb == 4) return launch_window_nb<4, 4>(TN_WIN_ARGS);
-    if (nb == 8) return launch_window_nb<4, 8>(TN_WIN_ARGS);
+    if (nb == 4) return launch_window_nb<4, 4, TAB>(TN_WIN_ARGS);
+    if (nb == 8) return launch_window_nb<4, 8, TAB>(TN_WIN_ARGS);
   }
 #undef TN_WIN_ARGS
   TN_REQUIRE(false, "rnn_window: rows per workgroup must be 4 or 6 (GRU) / 4 or 8 (LSTM)");
 }
 
-int launch_temporal_pool_windows(const float *x, int rows, int F, const int32_t *centre, const int32_t *lo, const int32_t *hi,
-                                 int B, int T, int stride, int kind, float *y, hipStream_t s) {
+template <bool TAB>
+int launch_pool(const float *x, int rows, int F, const int32_t *centre, const int32_t *lo, const int32_t *hi, int B, int T,
+                int stride, int kind, float *y, hipStream_t s) {
   const long total = (long)B * F;
-  hipLaunchKernelGGL(temporal_pool_windows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, rows, F, centre,
+  hipLaunchKernelGGL(temporal_pool_windows_kernel<TAB>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, rows, F, centre,
                      lo, hi, B, T, stride, kind, y);
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
+}
+
+}  // namespace
+
+int launch_rnn_window(int gates, const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *centre,
+                      const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, int nb,
+                      hipStream_t s) {
+  return launch_window<false>(gates, gi, ldgi, rows, whT, bh, centre, lo, hi, pooled, B, T, stride, H, nb, s);
+}
+
+int launch_rnn_window_rows(int gates, const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *idx,
+                           float *pooled, int B, int T, int H, int nb, hipStream_t s) {
+  return launch_window<true>(gates, gi, ldgi, rows, whT, bh, idx, nullptr, nullptr, pooled, B, T, 1, H, nb, s);
+}
+
+int launch_temporal_pool_windows(const float *x, int rows, int F, const int32_t *centre, const int32_t *lo, const int32_t *hi,
+                                 int B, int T, int stride, int kind, float *y, hipStream_t s) {
+  return launch_pool<false>(x, rows, F, centre, lo, hi, B, T, stride, kind, y, s);
+}
+
+int launch_temporal_pool_rows(const float *x, int rows, int F, const int32_t *idx, int B, int T, int kind, float *y,
+                              hipStream_t s) {
+  return launch_pool<true>(x, rows, F, idx, nullptr, nullptr, B, T, 1, kind, y, s);
 }

@@ -388,6 +388,11 @@ class TennisSet:
             idx[i] = [row[(v, f)] for f in fs]
         return frames, idx
 
+    def frame_view(self, frames=None):
+        """A window-1 view of this dataset over ``frames`` (default: ``window_table()[0]``), for a ``DataLoader``: every distinct
+        frame the windows read, once (``FrameTableView``)."""
+        return FrameTableView(self, self.window_table()[0] if frames is None else frames)
+
     def __getitem__(self, idx):                                                        # dataset.py:184-233
         sample = self._samples[idx]
         label = self.classes.index(sample[2])
@@ -396,6 +401,35 @@ class TennisSet:
         else:
             img = self._load(sample[0], sample[1])
         return img, label, idx
+
+
+class FrameTableView:
+    """A frame-level (window 1) view of a ``TennisSet`` over the ``frames`` list of ``window_table()``: item i is frame ``frames[i]``
+    = (video, frame), loaded by the dataset's own ``_load`` (its transform, or the decoded uint8 frame under a device-batched one)
+    and, under ``DataLoader``, by its host-or-device decode route.  The view shares everything else with the dataset it wraps: it
+    reads no split file and balances nothing.  Frames of the table need not be samples of the split, so they carry no label: items
+    return label 0, which nothing on this route reads."""
+
+    def __init__(self, dataset, frames):
+        self._base = dataset
+        self._samples = [[v, int(f), dataset.classes[0]] for v, f in frames]
+        self._window = 1
+
+    def __getattr__(self, name):          # (only what the view does not define itself)
+        if name == "_base":
+            raise AttributeError(name)
+        return getattr(self._base, name)
+
+    def __len__(self):
+        return len(self._samples)
+
+    def sample_frames(self, idx):
+        s = self._samples[idx]
+        return [(s[0], s[1])]
+
+    def __getitem__(self, idx):
+        s = self._samples[idx]
+        return self._base._load(s[0], s[1]), 0, idx
 
 
 class DataLoader:

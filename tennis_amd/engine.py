@@ -349,6 +349,14 @@ def _index_arrays(dev, *arrays):
     return out
 
 
+def _index_table(dev, idx):
+    """a (samples, window) row table (numpy / torch, any integer type) -> a contiguous int32 tensor on ``dev``"""
+    idx = torch.as_tensor(np.asarray(idx) if not isinstance(idx, torch.Tensor) else idx)
+    if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
+        raise ValueError(f"the row table must be a non-empty (samples, window) array, got {tuple(idx.shape)}")
+    return idx.to(device=dev, dtype=torch.int32).contiguous()
+
+
 class WindowHead(_Handle):
     """Dense windowed evaluation of ``CNNRNN`` in feature mode (reference evaluate.py:274-303 with ``--feats_model M --window W
     --temp_pool gru|lstm``; definitions.py:94-96,106-109): ``project`` runs the i2h projection once per row of a device-resident
@@ -397,6 +405,19 @@ class WindowHead(_Handle):
 
     __call__ = forward
 
+    def forward_rows(self, idx, return_pooled: bool = False):
+        """``forward`` over a row table (``TennisSet.window_table``): ``idx`` (samples, window) integers, step ``t`` of sample ``b``
+        reads row ``clamp(idx[b, t], 0, rows - 1)`` of the projected matrix (a negative entry is row 0).  Any sample layout; a table
+        that spells out a ``(centre, lo, hi, stride)`` window gives ``forward``'s bits."""
+        dev = torch.device("cuda", self.ctx.device)
+        idx = _index_table(dev, idx)
+        n, window = idx.shape
+        logits = torch.empty((n, self.classes), dtype=torch.float32, device=dev)
+        pooled = torch.empty((n, 2 * self.hidden), dtype=torch.float32, device=dev) if return_pooled else None
+        check(self.lib.tn_window_head_forward_rows(self.handle, ptr(idx), n, window, ptr(pooled), ptr(logits)),
+              "tn_window_head_forward_rows")
+        return (logits, pooled) if return_pooled else logits
+
     def _set_rows_per_group(self, nb: int):
         """tuning hook (scripts/bench_window_head.py): samples per workgroup of the recurrent kernel, 0 = the library's choice"""
         check(self.lib.tn_dbg_window_head_rows_per_group(self.handle, int(nb)), "tn_dbg_window_head_rows_per_group")
@@ -418,6 +439,22 @@ def temporal_pool_windows(features: torch.Tensor, centre, lo, hi, window: int, s
     check(ctx.lib.tn_temporal_pool_windows(ctx.handle, ptr(x), x.shape[0], x.shape[1], ptr(centre), ptr(lo), ptr(hi), n, int(window),
                                            int(stride), _lib.POOL_MEAN if kind == "mean" else _lib.POOL_MAX, ptr(y)),
           "tn_temporal_pool_windows")
+    return y
+
+
+def temporal_pool_rows(features: torch.Tensor, idx, kind: str, ctx: _lib.Context | None = None) -> torch.Tensor:
+    """``temporal_pool_windows`` over a row table (``TennisSet.window_table``): sample ``b`` pools the rows
+    ``clamp(idx[b, t], 0, rows - 1)``, t ascending -> (samples, F)."""
+    ctx = ctx or _lib.default_context(features.device.index)
+    _on_ctx_device(ctx, features, "temporal_pool_rows")
+    x = features.contiguous().float()
+    if x.dim() != 2:
+        raise ValueError(f"temporal_pool_rows expects a (rows, F) feature matrix, got {tuple(x.shape)}")
+    idx = _index_table(x.device, idx)
+    n, window = idx.shape
+    y = torch.empty((n, x.shape[1]), dtype=torch.float32, device=x.device)
+    check(ctx.lib.tn_temporal_pool_rows(ctx.handle, ptr(x), x.shape[0], x.shape[1], ptr(idx), n, window,
+                                        _lib.POOL_MEAN if kind == "mean" else _lib.POOL_MAX, ptr(y)), "tn_temporal_pool_rows")
     return y
 
 

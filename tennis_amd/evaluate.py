@@ -109,6 +109,76 @@ def evaluate_windows(net, dataset, metrics, features=None, batch_size=65536):
     return results, ground_truths
 
 
+def encode_table(net_backbone, dataset, frames, batch_size=64, num_workers=0):
+    """The (len(frames), F) float32 DEVICE feature table of ``TennisSet.window_table`` for a model on frames: row r is
+    ``net_backbone`` applied to frame ``frames[r]`` = (video, frame).  Every frame is loaded (the dataset's own decode / transform
+    route, ``TennisSet.frame_view`` under the same ``DataLoader``) and encoded exactly once, in batches of ``batch_size``; the
+    encoder writes a batch's rows straight into the table (its ``out=``) and nothing waits for them, so the loader reads and
+    decodes the next batch behind the encode of this one (as ``save_features_sharded``'s file writes run behind it).  No ``.npy``
+    is read or written."""
+    from .nn import _to_device
+    if not len(frames):
+        raise ValueError("encode_table: no frames")
+    loader = DataLoader(dataset.frame_view(frames), batch_size=batch_size, shuffle=False, num_workers=num_workers)
+    table, r0, shape = None, 0, None
+    for data, _labels, _idxs in loader:
+        x = _to_device(data)
+        n = x.shape[0]
+        eng = getattr(net_backbone, "_engine", None)
+        if table is not None and tuple(x.shape[1:]) == shape and hasattr(eng, "feature_dim") and n <= eng.max_batch:
+            eng(x, out=table[r0:r0 + n])
+        else:                                    # the first batch: the block builds its engine for this frame size
+            feat = net_backbone(x)
+            feat = feat.reshape(n, -1).float()
+            if table is None:
+                table = torch.empty((len(frames), feat.shape[1]), dtype=torch.float32, device=feat.device)
+            table[r0:r0 + n] = feat
+            shape = tuple(x.shape[1:])
+        r0 += n
+    assert r0 == len(frames)
+    return table
+
+
+def evaluate_table(net, dataset, metrics, features=None, frames_idx=None, batch_size=64, num_workers=0, metric_batch=65536):
+    """``evaluate_windows`` through a row table (``TennisSet.window_table`` + ``net.forward_table``): any ``every``, ``stride``,
+    ``padding`` and split layout the loader route accepts, in feature mode and on frames.  ``frames_idx``: ``(frames, idx)`` of
+    ``dataset.window_table()`` if the caller has it.  ``features``: the (len(frames), F) table; None: in feature mode it is loaded
+    with ``load_feature_table`` (every ``.npy`` once), on frames it is built by ``encode_table`` from the model's own backbone
+    (``net.td.model``: every distinct frame decoded and encoded once, in batches of ``batch_size``).  Same return values and metric
+    updates as ``evaluate_windows``."""
+    frames, idx = dataset.window_table() if frames_idx is None else frames_idx
+    if features is None:
+        if getattr(net, "feats", False):
+            features = load_feature_table(dataset, frames)
+        else:
+            features = encode_table(net.td.model, dataset, frames, batch_size, num_workers)
+    if len(features) != len(frames):
+        raise ValueError(f"evaluate_table: {len(features)} feature rows for a table of {len(frames)} frames")
+    outputs = net.forward_table(features, idx, row_videos=[v for v, _ in frames])
+    labels = torch.tensor([dataset.classes.index(s[2]) for s in dataset._samples], dtype=torch.float32, device=outputs.device)
+    for a in range(0, len(dataset), metric_batch):
+        for metric in metrics:
+            metric.update([labels[a:a + metric_batch]], [outputs[a:a + metric_batch]])
+    out = outputs.cpu().numpy()
+    results, ground_truths = dict(), dict()
+    for i, sample in enumerate(dataset._samples):
+        img_path = dataset.get_image_path(dataset._frames_dir, sample[0], sample[1])
+        results[img_path] = out[i]
+        ground_truths[img_path] = dataset.classes.index(sample[2])
+    return results, ground_truths
+
+
+def check_dense_windows(flags):
+    """What ``--dense_windows`` runs for these flags: "windows" (``evaluate_windows`` on stored features, with ``evaluate_table`` where
+    the split has no ``window_rows`` form), "frames" (``evaluate_table`` on frames, each distinct frame encoded once), or None
+    without the flag (and with ``--corpus_frames``, which has a route of its own).  Exits with the reason for what is still refused."""
+    if not flags.dense_windows or flags.corpus_frames > 0:
+        return None
+    if flags.window <= 1 or flags.temp_pool not in ("gru", "lstm", "mean", "max"):
+        raise SystemExit("--dense_windows needs --window W (> 1) and --temp_pool gru|lstm|mean|max")
+    return "frames" if flags.feats_model is None else "windows"
+
+
 def corpus_window_head(full, window, temp_pool, classes, stride=1, hidden=128):
     """``--corpus_frames N --dense_windows``: the temporal head over the gathered (N, F) matrix as ONE sequence (lo = 0,
     hi = N-1), one window per frame -> (logits, seconds of device work)."""
@@ -423,9 +493,11 @@ def build_parser():
     p.add_argument("--gather_block", type=int, default=4, help="batches per rank per all-gather round")
     p.add_argument("--corpus_reuse_frames", action="store_true", help="C4: generate one synthetic batch per rank and re-use it")
     p.add_argument("--dense_windows", action="store_true",
-                   help="dense windowed evaluation (not a reference flag): with --feats_model M --window W --temp_pool gru|lstm|mean|max "
-                        "every frame's features are read once and projected once, the windows are gathered on the GPU "
-                        "(evaluate_windows); with --corpus_frames N the head runs over the gathered matrix as one sequence")
+                   help="dense windowed evaluation (not a reference flag): with --window W --temp_pool gru|lstm|mean|max every frame is "
+                        "read once and projected once, the windows are gathered on the GPU - with --feats_model M from the stored "
+                        "features (evaluate_windows; evaluate_table for splits without an arithmetic window form), without it from "
+                        "frames, each distinct frame decoded and encoded once (evaluate_table); with --corpus_frames N the head "
+                        "runs over the gathered matrix as one sequence")
     return p
 
 
@@ -454,6 +526,7 @@ def _main_rank(flags, rank, world, dev):
     if flags.num_workers < 0:                                               # the reference's -1 = cpu_count() (evaluate.py:80-81)
         flags.num_workers = 3                                               # (files -> features peaks at three decoder threads: scripts/bench_pipeline.py, profiles/r05_c_*)
     every = [int(s) for s in flags.every.split(",")]
+    check_dense_windows(flags)                                              # refusals before anything is built
     if flags.corpus_frames > 0:                                             # BASELINE config C4
         backbone = get_model(flags.backbone, pretrained=True, max_batch=flags.batch_size, conversion=flags.fp16_conversion).features
         full, st = extract_corpus(backbone, flags.corpus_frames, flags.batch_size, flags.data_shape, dev, rank, world,
@@ -535,11 +608,21 @@ def _main_rank(flags, rank, world, dev):
     test_metrics = [PRF1(label_names=test_set.classes)]
     tic = time.time()
     if flags.dense_windows:
-        if flags.feats_model is None or flags.window <= 1 or flags.temp_pool not in ("gru", "lstm", "mean", "max"):
-            raise SystemExit("--dense_windows needs --feats_model M --window W (> 1) --temp_pool gru|lstm|mean|max")
+        route = check_dense_windows(flags)
         if rank != 0:                                                       # one pass over one matrix: nothing to shard
             return 0
-        results, gts = evaluate_windows(model, test_set, test_metrics)
+        if route == "frames":
+            results, gts = evaluate_table(model, test_set, test_metrics, batch_size=flags.batch_size, num_workers=flags.num_workers)
+        else:
+            try:
+                test_set.window_rows()
+            except ValueError as e:
+                print("--dense_windows: this split has no (centre, lo, hi) window form (%s): evaluating through the row table" % e)
+                route = "table"
+            if route == "table":
+                results, gts = evaluate_table(model, test_set, test_metrics)
+            else:
+                results, gts = evaluate_windows(model, test_set, test_metrics)
     elif world > 1:                                                           # each rank tests batches rank::world
         results, gts = evaluate_model(model, _RankBatches(test_data, rank, world), test_set, test_metrics)
         comm = sharding.feature_comm(dev)

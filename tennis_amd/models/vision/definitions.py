@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from ...block import Block
-from ...engine import WindowHead, temporal_pool, temporal_pool_windows
+from ...engine import WindowHead, temporal_pool, temporal_pool_rows, temporal_pool_windows
 from ...nn import GRU, LSTM, Dense, _to_device
 from ...utils.layers import TimeDistributed
 
@@ -43,6 +43,42 @@ def window_chunks(centre, lo, hi, rows, max_rows):
         end = int(b) + 1
     pieces.append((first, end))
     return [(a, b, np.nonzero((lo >= a) & (hi < b))[0]) for a, b in pieces]
+
+
+def table_chunks(idx, row_videos, max_rows):
+    """``window_chunks`` for a row table (``TennisSet.window_table``): cuts a table of ``len(row_videos)`` rows into pieces of at most
+    ``max_rows`` whole videos.  ``idx`` (samples, window): the rows every sample reads; ``row_videos``: the video of every row of the
+    table - a sample's rows never leave its video, and the table is sorted by (video, frame), so a video is one run of rows.
+    -> [(first row, end row, sample ids, idx[sample ids] - first row)]; one piece when the table fits."""
+    idx = _host_index(idx)
+    rows = len(row_videos)
+    if idx.ndim != 2:
+        raise ValueError(f"the row table must be (samples, window), got {idx.shape}")
+    if rows <= max_rows:
+        return [(0, rows, np.arange(len(idx)), idx)]
+    if len(idx) and (idx.min() < 0 or idx.max() >= rows):
+        raise ValueError("a table larger than the row budget is cut at video boundaries: every index must lie inside it")
+    starts = [0] + [r for r in range(1, rows) if row_videos[r] != row_videos[r - 1]]
+    if len({row_videos[a] for a in starts}) != len(starts):
+        raise ValueError("a table larger than the row budget is cut at video boundaries: the rows of a video are not contiguous")
+    ends = starts[1:] + [rows]
+    lo, hi = idx.min(1), idx.max(1)
+    seg = np.searchsorted(np.asarray(starts), lo, side="right") - 1            # the video run each sample's first row lies in
+    if np.any(hi >= np.asarray(ends)[seg]):
+        raise ValueError("a table larger than the row budget is cut at video boundaries: a sample reads rows of two videos")
+    pieces, first = [], 0
+    for a, b in zip(starts, ends):
+        if b - a > max_rows:
+            raise ValueError(f"a video of {b - a} rows does not fit the row budget of {max_rows}")
+        if b - first > max_rows:
+            pieces.append((first, a))
+            first = a
+    pieces.append((first, rows))
+    out = []
+    for a, b in pieces:
+        ids = np.nonzero((lo >= a) & (hi < b))[0]
+        out.append((a, b, ids, idx[ids] - a))
+    return out
 
 
 class FrameModel(Block):
@@ -113,6 +149,30 @@ class TemporalPooling(Block):
             out[torch.from_numpy(ids).to(y.device)] = y
         return out
 
+    def forward_table(self, features, idx, max_rows=WINDOW_MAX_ROWS, row_videos=None):
+        """``forward`` of every window named by a row table (``TennisSet.window_table``): sample ``b`` pools the rows ``idx[b, t]`` of
+        ``features`` (rows, F), t ascending -> logits (samples, classes).  Feature mode: ``features`` are the stored features.
+        Frames mode: the rows ``self.td.model`` produced for the table's frames, each frame encoded once
+        (``evaluate.encode_table``).  Any sample layout; ``row_videos`` (the video of every row) is needed only to cut a table of
+        more than ``max_rows`` rows."""
+        x = _to_device(features).float()
+        if x.dim() != 2:
+            raise ValueError(f"forward_table expects a (rows, F) feature matrix, got {tuple(x.shape)}")
+        kind = "mean" if self.pool == "mean" else "max"
+        if x.shape[0] > max_rows and row_videos is None:
+            raise ValueError(f"forward_table: a table of {x.shape[0]} rows over the budget of {max_rows} needs row_videos to be cut")
+        out, n = None, len(_host_index(idx))
+        for a, b, ids, local in table_chunks(idx, row_videos if row_videos is not None else [0] * x.shape[0], max_rows):
+            if not len(ids):
+                continue
+            y = temporal_pool_rows(x[a:b], local, kind)
+            if self.classes:
+                y = self.classes(y)
+            if out is None:
+                out = torch.empty((n, y.shape[1]), dtype=torch.float32, device=y.device)
+            out[torch.from_numpy(ids).to(y.device)] = y
+        return out
+
 
 class CNNRNN(Block):
     """Reference definitions.py:75-110: [TimeDistributed CNN ->] bi-GRU/LSTM -> max over T -> Dense."""
@@ -157,20 +217,52 @@ class CNNRNN(Block):
         self.rnn._materialize(x.shape[1])
         self.classes._materialize(2 * self.rnn._hidden)
         pieces = window_chunks(centre, lo, hi, x.shape[0], max_rows)
-        need_rows = max(b - a for a, b, _ in pieces)
-        need_samples = max(len(ids) for _, _, ids in pieces)
-        eng = self._engine
-        if eng is None or eng.max_rows < need_rows or eng.max_samples < need_samples or eng.input_size != x.shape[1]:
-            self._engine = eng = None      # release the old workspace first
-            p = {k: v.data for blk in (self.rnn, self.classes) for k, v in blk._own_params.items()}
-            self._engine = eng = WindowHead(self.rnn._mode, x.shape[1], self.rnn._hidden, self.classes._units, p, self.rnn.prefix,
-                                            self.classes.prefix, max_rows=need_rows, max_samples=need_samples)
+        eng = self._window_head(x.shape[1], max(b - a for a, b, _ in pieces), max(len(ids) for _, _, ids in pieces))
         if len(pieces) == 1:
             return eng.project(x).forward(centre, lo, hi, window, stride)
         out = torch.empty((n, self.classes._units), dtype=torch.float32, device=x.device)
         for a, b, ids in pieces:
             c, l, h = (_host_index(v)[ids] - a for v in (centre, lo, hi))
             out[torch.from_numpy(ids).to(x.device)] = eng.project(x[a:b]).forward(c, l, h, window, stride)
+        return out
+
+
+    def _window_head(self, width, need_rows, need_samples):
+        """the ``WindowHead`` of this model's parameters, rebuilt when it is too small for the piece at hand"""
+        eng = self._engine
+        if eng is None or eng.max_rows < need_rows or eng.max_samples < need_samples or eng.input_size != width:
+            self._engine = eng = None      # release the old workspace first
+            p = {k: v.data for blk in (self.rnn, self.classes) for k, v in blk._own_params.items()}
+            self._engine = eng = WindowHead(self.rnn._mode, width, self.rnn._hidden, self.classes._units, p, self.rnn.prefix,
+                                            self.classes.prefix, max_rows=need_rows, max_samples=need_samples)
+        return eng
+
+    def forward_table(self, features, idx, max_rows=WINDOW_MAX_ROWS, row_videos=None):
+        """``forward`` of every window named by a row table (``TennisSet.window_table``) with ONE i2h projection per row: sample ``b``
+        runs over the rows ``idx[b, t]`` of ``features`` (rows, F), t = 0 .. window-1 -> logits (samples, classes).  Feature mode:
+        ``features`` are the stored features.  Frames mode: the rows ``self.td.model`` (the model's own backbone) produced for the
+        table's frames, each frame encoded once (``evaluate.encode_table``); their width must be the recurrent layer's input size.
+        Any sample layout.  A table of more than ``max_rows`` rows is cut into pieces of whole videos, which needs ``row_videos``
+        (the video of every row of the table)."""
+        if not self.classes:
+            raise NotImplementedError("forward_table returns logits: the model needs its Dense (num_classes > 0)")
+        x = _to_device(features).float()
+        if x.dim() != 2:
+            raise ValueError(f"forward_table expects a (rows, F) feature matrix, got {tuple(x.shape)}")
+        self.rnn._materialize(x.shape[1])
+        if self.rnn._input_size != x.shape[1]:
+            raise ValueError(f"forward_table: feature rows of width {x.shape[1]}, the recurrent layer takes {self.rnn._input_size}")
+        self.classes._materialize(2 * self.rnn._hidden)
+        if x.shape[0] > max_rows and row_videos is None:
+            raise ValueError(f"forward_table: a table of {x.shape[0]} rows over the budget of {max_rows} needs row_videos to be cut")
+        pieces = table_chunks(idx, row_videos if row_videos is not None else [0] * x.shape[0], max_rows)
+        eng = self._window_head(x.shape[1], max(b - a for a, b, _, _ in pieces), max(max(len(ids) for _, _, ids, _ in pieces), 1))
+        if len(pieces) == 1:
+            return eng.project(x).forward_rows(pieces[0][3])
+        out = torch.empty((len(_host_index(idx)), self.classes._units), dtype=torch.float32, device=x.device)
+        for a, b, ids, local in pieces:
+            if len(ids):
+                out[torch.from_numpy(ids).to(x.device)] = eng.project(x[a:b]).forward_rows(local)
         return out
 
 
