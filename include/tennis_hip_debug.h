@@ -238,6 +238,34 @@ int tn_dbg_window_head_rows_per_group(struct tn_window_head *h, int nb);
 #define TN_GRAD_SUMSQ_GRID 1024
 int tn_dbg_grad_sumsq(tn_ctx *ctx, const float *dev, int64_t n, const float *dev2, int64_t n2, double *sumsq_host);
 
+/* The captioner's step kernels (csrc/captioner.hip) on their own: each hook launches the production kernel on the ctx stream with
+ * the grid, block and dynamic LDS the decoder / the training step compute for the shape, then synchronises.  All operands DEVICE
+ * fp32 (valid_len / labels / tgt int32), 16-byte aligned; H % 4 == 0.  A null pointer (other than the optional ones), a pitch below
+ * its width or a shape whose LDS passes the step kernels' 152 KiB is refused with TN_ERR_INVALID.
+ * tn_dbg_gnmt_attention_fwd: transpose_bth_kernel on keyproj (B,T,H) row-major, then dec_attention_kernel<1> over R = B * beam rows
+ * (row r belongs to clip r / beam): g0 (R,4H) the first cell's stacked pre-activations (GRU [r, z, n_i2h, n_h2h], LSTM [i, f, g, o]),
+ * hprev (R rows of pitch ldh >= H), cprev (R,H; LSTM only, else NULL), mem (B,T,H), valid_len (B; clamped to [0, T]).  split_cap 0:
+ * the split att_split picks; 16 / 8 / 4 / 2 / 1: min(pick, cap) - the LDS is sized for the split used.  Outputs: hn (R,H), cn (R,H;
+ * LSTM only), x1 (R rows of pitch ldx1 >= 2H, columns [0, 2H) written: [h, context]), ctx_out (R,H), w_out (R,T). */
+int tn_dbg_gnmt_attention_fwd(tn_ctx *ctx, const float *g0, const float *hprev, int ldh, const float *cprev, int lstm, const float *keyproj,
+                              const float *mem, const int32_t *valid_len, int B, int T, int H, int beam, int split_cap, float *hn, float *cn,
+                              float *x1, int ldx1, float *ctx_out, float *w_out);
+/* trn_att_bwd_kernel: aw (B,T) the step's weights, mem / keyproj (B,T,H), d context = c0 + c1 (B rows of pitch lc0 / lc1 >= H; either
+ * may be NULL, not both) -> ds (B,T), dctx (B,H), dh0 (B,H). */
+int tn_dbg_gnmt_attention_bwd(tn_ctx *ctx, const float *aw, const float *mem, const float *keyproj, const float *c0, int lc0, const float *c1,
+                              int lc1, const int32_t *valid_len, int B, int T, int H, float *ds, float *dctx, float *dh0);
+/* trn_att_outer_kernel: aw / ds (steps,B,T), dctx (steps,B,H), h0 (steps * B rows of pitch ldh >= H) -> dmem, dkp (B,T,H). */
+int tn_dbg_gnmt_attention_outer(tn_ctx *ctx, const float *aw, const float *ds, const float *dctx, const float *h0, int ldh, int steps, int B,
+                                int T, int H, float *dmem, float *dkp);
+/* trn_ce_bwd_kernel + the column sum of its loss rows, and masked_ce_kernel on the same operands: logits (B,L,V), labels (B rows of
+ * pitch ld >= L), valid_len (B) -> dlogits (L,B,V), loss_rows (L,B), loss (1: the token-averaged loss), masked_loss (B: the
+ * per-sample mean over L of the masked negative log-probability). */
+int tn_dbg_gnmt_ce(tn_ctx *ctx, const float *logits, const int32_t *labels, int ld, const int32_t *valid_len, int B, int L, int V,
+                   float *dlogits, float *loss_rows, float *loss, float *masked_loss);
+/* trn_emb_grad_kernel: dx0 (L,B,K0) step-major with K0 > E (the first E columns are read), tgt (B rows of pitch ld >= L; an id <= 0
+ * counts as row 0) -> demb (V,E), every row assigned. */
+int tn_dbg_gnmt_emb_grad(tn_ctx *ctx, const float *dx0, int K0, const int32_t *tgt, int ld, int B, int L, int E, int V, float *demb);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,8 +70,12 @@ def _direction(x, w, pref, reverse, vl, cell="gru"):
 
 
 def forward_loss(params: dict, src, src_vl, tgt, tgt_vl, hidden, prefix="gnmt_", dtype=torch.float64, masks=None, cell="gru",
-                 num_layers=2, num_bi_layers=1, use_residual=False):
+                 num_layers=2, num_bi_layers=1, use_residual=False, detach_query=False):
     """-> (loss scalar tensor, logits (B, L-1, V), leaf tensors dict).
+
+    ``detach_query``: a deliberately WRONG backward pass - the attention query is cut out of the graph, so no gradient flows from the
+    scores into the first decoder cell (the forward values are unchanged).  Tests use it to show that their inputs make that path
+    visible: with near-uniform attention it is three orders of magnitude below the other addends of d h.
 
     ``num_layers`` / ``num_bi_layers`` / ``use_residual``: GNMTEncoder.forward (gnmt.py:136-160: dropout on every layer's output,
     ``outputs + inputs`` for layers ``i > num_bi_layers``, the backward direction's states of a bidirectional layer) and
@@ -122,7 +126,7 @@ def forward_loss(params: dict, src, src_vl, tgt, tgt_vl, hidden, prefix="gnmt_",
     for i in range(L):
         emb = w[prefix + "tgt_embed_weight"][tg[:, i].clamp(min=0)]
         hs[0], cs[0] = _cell(cell, torch.cat([emb, att], dim=1), hs[0], cs[0], *cw(0))
-        q = hs[0] / np.sqrt(H)
+        q = (hs[0].detach() if detach_query else hs[0]) / np.sqrt(H)
         score = torch.einsum("bh,bth->bt", q, keyproj)
         score = torch.where(mask, score, torch.full_like(score, -1e18))
         wts = torch.softmax(score, dim=1) * mask.to(dtype)
@@ -147,9 +151,9 @@ def forward_loss(params: dict, src, src_vl, tgt, tgt_vl, hidden, prefix="gnmt_",
 
 
 def loss_and_grads(params, src, src_vl, tgt, tgt_vl, hidden, prefix="gnmt_", masks=None, cell="gru", num_layers=2, num_bi_layers=1,
-                   use_residual=False):
+                   use_residual=False, detach_query=False):
     loss, logits, w = forward_loss(params, src, src_vl, tgt, tgt_vl, hidden, prefix, masks=masks, cell=cell, num_layers=num_layers,
-                                   num_bi_layers=num_bi_layers, use_residual=use_residual)
+                                   num_bi_layers=num_bi_layers, use_residual=use_residual, detach_query=detach_query)
     loss.backward()
     return float(loss.detach()), logits.detach().numpy(), {k: (v.grad.numpy() if v.grad is not None else np.zeros(v.shape)) for k, v in w.items()}
 

@@ -153,6 +153,12 @@ _SIGS = {
     "tn_dbg_grad_sumsq": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_double)]),
     "tn_dbg_rows_pad_skip": (C.c_int, [C.c_int]),
     "tn_dbg_gnmt_trainer_src_grad": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int]),
+    "tn_dbg_gnmt_attention_fwd": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            _P, _P, _P, C.c_int, _P, _P]),
+    "tn_dbg_gnmt_attention_bwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "tn_dbg_gnmt_attention_outer": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tn_dbg_gnmt_ce": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "tn_dbg_gnmt_emb_grad": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "tn_gnmt_trainer_create": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tn_gnmt_trainer_create_ex": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -87,6 +87,8 @@ static size_t att_lds_bytes(int T, int H, int split) {      // q[H] | w[Tp] | pa
   const size_t a = (size_t)hg * Tp, b = (size_t)sg * H;
   return ((size_t)H + Tp + (a > b ? a : b)) * sizeof(float);
 }
+// dynamic LDS of trn_att_bwd_kernel: dctx[H] | ds[T] | part[16][H] | red[16]
+static size_t att_bwd_lds_bytes(int T, int H) { return (size_t)(17 * H + T + 16) * sizeof(float); }
 // the largest split whose attention kernel fits the step kernels' LDS (0: not even one partial row does)
 static int att_split(int T, int H, size_t limit) {
   for (int sp = 16; sp >= 1; sp >>= 1)
@@ -1911,7 +1913,7 @@ static int trainer_step(tn_gnmt_trainer *t, const float *src, const SrcRows *row
   const int BT = B * T, LB = L * B;
   const bool lstm = G == 4;
   const int asplit = att_split(T, H, kStepLdsMax);
-  const size_t attb_lds = (size_t)(17 * H + T + 16) * sizeof(float);
+  const size_t attb_lds = att_bwd_lds_bytes(T, H);
   TN_REQUIRE(asplit > 0 && attb_lds <= kStepLdsMax, "tn_gnmt_trainer: 3 * max(hidden, source length) floats exceed 152 KiB of LDS");
   const size_t att_lds = att_lds_bytes(T, H, asplit);
   if (int rc = allow_lds(dec_attention_kernel<1>, att_lds)) return rc;
@@ -2213,5 +2215,95 @@ extern "C" int tn_gnmt_destroy(tn_gnmt *g) {
   for (tn_birnn *e : g->enc) tn_birnn_destroy(e);
   g->pool.release();
   delete g;
+  return TN_OK;
+}
+
+// ---- test hooks (include/tennis_hip_debug.h): the step kernels above on caller operands, launched as the decoder / the training step
+// launch them.  They sit here because the kernels are in this file's anonymous namespace. ----
+extern "C" int tn_dbg_gnmt_attention_fwd(tn_ctx *ctx, const float *g0, const float *hprev, int ldh, const float *cprev, int lstm,
+                                         const float *keyproj, const float *mem, const int32_t *valid_len, int B, int T, int H, int beam,
+                                         int split_cap, float *hn, float *cn, float *x1, int ldx1, float *ctx_out, float *w_out) {
+  TN_REQUIRE(ctx && g0 && hprev && keyproj && mem && valid_len && hn && x1 && ctx_out && w_out, "tn_dbg_gnmt_attention_fwd: null argument");
+  TN_REQUIRE(!lstm || (cprev && cn), "tn_dbg_gnmt_attention_fwd: the LSTM form needs cprev and cn");
+  TN_REQUIRE(B >= 1 && T >= 1 && beam >= 1 && H >= 4 && H % 4 == 0 && (long)B * beam <= 65535,
+             "tn_dbg_gnmt_attention_fwd: needs B, T, beam >= 1 and H a positive multiple of 4");
+  TN_REQUIRE(ldh >= H && ldx1 >= 2 * H, "tn_dbg_gnmt_attention_fwd: ldh below H or ldx1 below 2 H");
+  TN_REQUIRE(split_cap == 0 || split_cap == 16 || split_cap == 8 || split_cap == 4 || split_cap == 2 || split_cap == 1,
+             "tn_dbg_gnmt_attention_fwd: split_cap must be 0, 16, 8, 4, 2 or 1");
+  int asplit = att_split(T, H, kStepLdsMax);
+  TN_REQUIRE(asplit > 0, "tn_dbg_gnmt_attention_fwd: 3 * max(hidden, source length) floats exceed the step kernel's 152 KiB of LDS");
+  if (split_cap && split_cap < asplit) asplit = split_cap;
+  const size_t att_lds = att_lds_bytes(T, H, asplit);
+  TN_REQUIRE(att_lds <= kStepLdsMax, "tn_dbg_gnmt_attention_fwd: the capped split exceeds the step kernel's 152 KiB of LDS");
+  TN_ON_DEVICE(ctx->device);
+  hipStream_t s = ctx->stream;
+  if (int rc = allow_lds(dec_attention_kernel<1>, att_lds)) return rc;
+  const int R = B * beam, Tp = (T + 3) & ~3;
+  float *kpT = nullptr;
+  TN_HIP_CHECK(hipMalloc((void **)&kpT, sizeof(float) * (size_t)B * H * Tp));
+  hipLaunchKernelGGL(transpose_bth_kernel, dim3((H + 31) / 32, (T + 31) / 32, B), dim3(256), 0, s, keyproj, kpT, T, H);
+  hipLaunchKernelGGL(dec_attention_kernel<1>, dim3(R), dim3(kBeamThreads), att_lds, s, g0, hprev, ldh, cprev, lstm ? 1 : 0, hn, lstm ? cn : (float *)nullptr,
+                     x1, ldx1, (const float *)kpT, mem, valid_len, ctx_out, beam, 1, T, H, w_out, (const int32_t *)nullptr, (const int32_t *)nullptr,
+                     (const float *)nullptr, (const float *)nullptr, asplit, (long)T);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(kpT);
+  TN_HIP_CHECK(e);
+  return TN_OK;
+}
+
+extern "C" int tn_dbg_gnmt_attention_bwd(tn_ctx *ctx, const float *aw, const float *mem, const float *keyproj, const float *c0, int lc0,
+                                         const float *c1, int lc1, const int32_t *valid_len, int B, int T, int H, float *ds, float *dctx,
+                                         float *dh0) {
+  TN_REQUIRE(ctx && aw && mem && keyproj && (c0 || c1) && valid_len && ds && dctx && dh0, "tn_dbg_gnmt_attention_bwd: null argument");
+  TN_REQUIRE(B >= 1 && B <= 65535 && T >= 1 && H >= 4 && H % 4 == 0, "tn_dbg_gnmt_attention_bwd: needs B, T >= 1 and H a positive multiple of 4");
+  TN_REQUIRE((!c0 || lc0 >= H) && (!c1 || lc1 >= H), "tn_dbg_gnmt_attention_bwd: an addend's pitch is below H");
+  const size_t attb_lds = att_bwd_lds_bytes(T, H);
+  TN_REQUIRE(attb_lds <= kStepLdsMax, "tn_dbg_gnmt_attention_bwd: 17 hidden + source length floats exceed the step kernel's 152 KiB of LDS");
+  TN_ON_DEVICE(ctx->device);
+  if (int rc = allow_lds(trn_att_bwd_kernel, attb_lds)) return rc;
+  hipLaunchKernelGGL(trn_att_bwd_kernel, dim3(B), dim3(kBeamThreads), attb_lds, ctx->stream, aw, mem, keyproj, c0, lc0, c1, lc1, valid_len, ds, dctx,
+                     dh0, T, H);
+  TN_HIP_CHECK(hipGetLastError());
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+
+extern "C" int tn_dbg_gnmt_attention_outer(tn_ctx *ctx, const float *aw, const float *ds, const float *dctx, const float *h0, int ldh, int steps,
+                                           int B, int T, int H, float *dmem, float *dkp) {
+  TN_REQUIRE(ctx && aw && ds && dctx && h0 && dmem && dkp, "tn_dbg_gnmt_attention_outer: null argument");
+  TN_REQUIRE(steps >= 1 && B >= 1 && B <= 65535 && T >= 1 && H >= 4 && H % 4 == 0,
+             "tn_dbg_gnmt_attention_outer: needs steps, B, T >= 1 and H a positive multiple of 4");
+  TN_REQUIRE(ldh >= H, "tn_dbg_gnmt_attention_outer: ldh below H");
+  TN_ON_DEVICE(ctx->device);
+  hipLaunchKernelGGL(trn_att_outer_kernel, dim3((T + 3) / 4, B), dim3(256), 0, ctx->stream, aw, ds, dctx, h0, ldh, dmem, dkp, steps, B, T, H);
+  TN_HIP_CHECK(hipGetLastError());
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return TN_OK;
+}
+
+extern "C" int tn_dbg_gnmt_ce(tn_ctx *ctx, const float *logits, const int32_t *labels, int ld, const int32_t *valid_len, int B, int L, int V,
+                              float *dlogits, float *loss_rows, float *loss, float *masked_loss) {
+  TN_REQUIRE(ctx && logits && labels && valid_len && dlogits && loss_rows && loss && masked_loss, "tn_dbg_gnmt_ce: null argument");
+  TN_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && V >= 1, "tn_dbg_gnmt_ce: needs B, L, V >= 1");
+  TN_REQUIRE(ld >= L, "tn_dbg_gnmt_ce: the labels' pitch is below L");
+  TN_ON_DEVICE(ctx->device);
+  hipStream_t s = ctx->stream;
+  hipLaunchKernelGGL(trn_ce_bwd_kernel, dim3(L, B), dim3(256), 0, s, logits, labels, ld, valid_len, B, L, V, dlogits, loss_rows);
+  if (int rc = launch_colsum_f32(loss_rows, 1, L * B, 1, loss, s)) return rc;
+  hipLaunchKernelGGL(masked_ce_kernel, dim3(B), dim3(256), 0, s, logits, labels, ld, valid_len, masked_loss, L, V);
+  TN_HIP_CHECK(hipGetLastError());
+  TN_HIP_CHECK(hipStreamSynchronize(s));
+  return TN_OK;
+}
+
+extern "C" int tn_dbg_gnmt_emb_grad(tn_ctx *ctx, const float *dx0, int K0, const int32_t *tgt, int ld, int B, int L, int E, int V, float *demb) {
+  TN_REQUIRE(ctx && dx0 && tgt && demb, "tn_dbg_gnmt_emb_grad: null argument");
+  TN_REQUIRE(B >= 1 && L >= 1 && E >= 1 && V >= 1, "tn_dbg_gnmt_emb_grad: needs B, L, E, V >= 1");
+  TN_REQUIRE(K0 > E && ld >= L, "tn_dbg_gnmt_emb_grad: K0 must exceed E and the tokens' pitch must reach L");
+  TN_ON_DEVICE(ctx->device);
+  hipLaunchKernelGGL(trn_emb_grad_kernel, dim3(V), dim3(64), 0, ctx->stream, dx0, K0, tgt, ld, B, L, E, V, demb);
+  TN_HIP_CHECK(hipGetLastError());
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return TN_OK;
 }

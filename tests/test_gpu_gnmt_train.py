@@ -9,12 +9,14 @@ from oracle import gnmt_train_torch as gt
 pytestmark = pytest.mark.gpu
 
 
-def _case(seed, B, T, F, H, E, V, L, cell="gru", nl=2, nbi=1, res=False):
+def _case(seed, B, T, F, H, E, V, L, cell="gru", nl=2, nbi=1, res=False, key_scale=1.0, src_scale=0.5):
     from tennis_amd import weights as W
     p = W.make_gnmt_weights(seed, cell, F, H, E, V, num_layers=nl, num_bi_layers=nbi)
     rng = np.random.default_rng(seed)
     p["gnmt_tgt_embed_weight"] = rng.normal(0, 0.5, (V, E)).astype(np.float32)      # every row trainable, none zeroed
-    src = (np.abs(rng.normal(0, 1, (B, T, F))) * 0.5).astype(np.float32)
+    if key_scale != 1.0:                                                            # non-uniform attention (the long-source cases)
+        p["gnmt_dec_attention_key_weight"] = (p["gnmt_dec_attention_key_weight"] * key_scale).astype(np.float32)
+    src = (np.abs(rng.normal(0, 1, (B, T, F))) * src_scale).astype(np.float32)
     svl = rng.integers(max(1, T // 2), T + 1, B).astype(np.int32)
     svl[0] = T
     tgt = rng.integers(4, V, (B, L)).astype(np.int32)
@@ -54,6 +56,44 @@ def test_loss_and_gradients_match_autograd(cfg, report):
         worst = max(worst, err)
         assert err < 2e-3, (k, err, np.abs(g).max())
     report[f"gnmt_train_{cell}_grad_rel_err_H{cfg['H']}_T{cfg['T']}"] = float(worst)
+
+
+# Long sources (config C5 trains at T = 214).  With the weights of make_gnmt_weights the attention is near-uniform: the gradient through
+# the scores is then 1e-3 of the other addends of d h0 and the key projection's gradient falls below the 1e-7 floor of the metric, so a
+# long-source case compares nothing there.  The key weight (x key_scale) and the source magnitude are therefore chosen so that, on the
+# oracle alone, (1) every gradient tensor has max |g| >= 1e-6 and (2) cutting the query out of the oracle's graph (detach_query) moves
+# some tensor by >= 10 x the 2e-3 bar.  Measured on the oracle: T 214: 8.6e-6 / 0.67; T 300: 1.8e-6 / 0.11; T 1030: 2.3e-6 / 0.39.
+# T 300 runs at H 32: at H 16 (key_scale 1000, source x 24) the two figures were 1.09e-6 / 0.10, too close to (1) to keep.
+LONG_SOURCE = [dict(seed=21, B=3, T=214, F=32, H=64, E=20, V=254, L=12, key_scale=1000.0, src_scale=2.0),
+               dict(seed=22, B=3, T=300, F=24, H=32, E=12, V=300, L=5, cell="lstm", key_scale=500.0, src_scale=12.0),
+               dict(seed=23, B=2, T=1030, F=16, H=8, E=6, V=14, L=4, key_scale=1000.0, src_scale=8.0)]
+
+
+@pytest.mark.parametrize("cfg", LONG_SOURCE, ids=[f"T{c['T']}_H{c['H']}" for c in LONG_SOURCE])
+def test_long_source_gradients_match_autograd(cfg, report):
+    from tennis_amd.engine import GNMTTrainer
+    p, src, svl, tgt, tvl = _case(**cfg)
+    cell = cfg.get("cell", "gru")
+    rl, rlog, rg = gt.loss_and_grads(p, src, svl, tgt, tvl, cfg["H"], cell=cell)
+    # the two conditions on the oracle alone, before any comparison
+    for k, g in rg.items():
+        assert np.abs(g).max() >= 1e-6, (k, np.abs(g).max(), "below 10 x the metric's floor: the comparison would be empty")
+    _, _, cut = gt.loss_and_grads(p, src, svl, tgt, tvl, cfg["H"], cell=cell, detach_query=True)
+    moved = max(np.abs(cut[k] - g).max() / max(1e-7, np.abs(g).max()) for k, g in rg.items())
+    assert moved >= 10 * 2e-3, (moved, "a backward pass without the query's gradient would pass")
+    tr = GNMTTrainer(p, cfg["F"], cfg["H"], cfg["E"], cfg["V"], max_batch=cfg["B"], max_src_len=cfg["T"], max_tgt_len=cfg["L"],
+                     cell_type=cell)
+    loss, logits = tr.forward_backward(torch.from_numpy(src).cuda(), torch.from_numpy(svl).cuda(), torch.from_numpy(tgt).cuda(),
+                                       torch.from_numpy(tvl).cuda(), return_logits=True)
+    worst = {k: float(np.abs(tr.get(k, gradient=True) - g).max() / max(1e-7, np.abs(g).max())) for k, g in rg.items()}
+    report[f"gnmt_train_long_{cell}_grad_rel_err_H{cfg['H']}_T{cfg['T']}"] = max(worst.values())
+    report[f"gnmt_train_long_{cell}_logits_err_H{cfg['H']}_T{cfg['T']}"] = float(np.abs(logits.cpu().numpy() - rlog).max())
+    print(f"long source T{cfg['T']} H{cfg['H']}: loss {float(loss):.6f} vs {rl:.6f}, logits err {np.abs(logits.cpu().numpy() - rlog).max():.2e}, "
+          f"detach_query moves {moved:.3f}, worst gradient errors {sorted(worst.items(), key=lambda kv: -kv[1])[:3]}")
+    assert abs(float(loss) - rl) < 1e-4 * max(1.0, abs(rl)), (float(loss), rl)
+    assert np.abs(logits.cpu().numpy() - rlog).max() < 1e-4
+    for k, err in worst.items():
+        assert err < 2e-3, (k, err, np.abs(rg[k]).max())
 
 
 @pytest.mark.parametrize("cfg", [dict(seed=11, B=3, T=9, F=16, H=8, E=6, V=14, L=6, nl=3, nbi=1),
