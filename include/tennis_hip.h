@@ -115,6 +115,19 @@ int tn_densenet121_feature_dim(const tn_encoder *enc);
 size_t tn_densenet121_workspace_bytes(const tn_encoder *enc);
 /* x: `batch` frames in `layout`; feat: (batch, feature_dim) fp32, NCHW-flatten order. */
 int tn_densenet121_forward(tn_encoder *enc, const void *x, tn_layout layout, int batch, float *feat);
+/* The same forward, and the class activation maps of a Dense(feature_dim -> units) behind it.  The network ends in
+ * BN -> ReLU -> AvgPool2D(7) -> Flatten -> Dense, so a logit is a sum over the cells of the last map and the maps need no backward
+ * pass: with A = relu(bn(map)) as the head averages it,
+ *   maps[b,c,y,x] = (1/49) sum_k W[c, k PH PW + (y/7) PW + (x/7)] A[b,k,y,x],    logit[b,c] = bias[c] + sum_{y,x} maps[b,c,y,x].
+ * Same contract as tn_densenet121_forward (layouts, max_batch, pipelining and join: the maps are ordered exactly as the
+ * features are); features are bit-identical to that call's.  maps: (batch, units, h, w) fp32 on the DEVICE, h x w from
+ * tn_densenet121_class_map_dims (7 x 7 at 224^2, 14 x 14 at 512^2: the 16 x 16 map's rows / columns 14 and 15 are dropped by
+ * the pool and belong to no cell).  The maps are computed from the map the head reads in that forward, in every mode, in a
+ * fixed order: bit-reproducible, and independent of how the batch was split.  classes->in_units must be the feature width,
+ * units <= 64, and the Dense must belong to the encoder's context; refused otherwise (tn_last_error names the argument). */
+int tn_densenet121_forward_class_maps(tn_encoder *enc, const void *x, tn_layout layout, int batch, float *feat,
+                                      const tn_dense *classes, float *maps);
+int tn_densenet121_class_map_dims(const tn_encoder *enc, int *h, int *w);        /* 7 PH, 7 PW */
 /* Pipelined forwards.  A large batch runs as two half batches on two library-owned streams; by default forward makes
  * the ctx's stream wait for both before it returns, so the call is stream-ordered like every other one.  With
  * set_pipelined(enc, 1) forward does NOT: consecutive forwards then overlap (the first half of call i+1 starts beside

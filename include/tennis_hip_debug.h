@@ -25,6 +25,18 @@ typedef struct {
 int tn_densenet121_profile(tn_encoder *enc, const void *x, tn_layout layout, int batch, float *feat,
                            tn_kernel_stat *stats, int max_stats, int *n_stats);
 
+/* tn_densenet121_forward_class_maps under the same event timer (one stream): the family "class_maps" stands beside
+ * "head_bnrelu_avgpool7", which reads the same map once. */
+int tn_dbg_profile_class_maps(tn_encoder *enc, const void *x, tn_layout layout, int batch, float *feat, const tn_dense *classes,
+                              float *maps, tn_kernel_stat *stats, int max_stats, int *n_stats);
+/* class_maps_kernel (csrc/class_maps.hip) alone on a caller's DEVICE map (B,H,W,C) NHWC: fp16 x_f16, or - x32 non-NULL - fp32 (x_f16
+ * is then not read).  scale / shift (C) and wd (classes, C PH PW) device fp32, maps (B, classes, 7 PH, 7 PW) device fp32.  Any
+ * B, H >= 7 PH, W >= 7 PW, C % 8 == 0, classes in [1, 64]; everything else is refused.  n_seq / depth (either may be NULL): the longest
+ * sequential fp32 accumulation of a lane at this C and the levels of the cross-lane reduction, the two constants of the error
+ * bound (n_seq + depth + 4) 2^-24 S.  Synchronous. */
+int tn_dbg_class_maps(tn_ctx *ctx, const void *x_f16, const float *x32, int B, int H, int W, int C, const float *scale, const float *shift,
+                      const float *wd, int PH, int PW, int classes, float *maps, int *n_seq, int *depth);
+
 /* Test hook: copy an internal NHWC fp16 activation of the LAST forward to a host
  * fp32 buffer.  tap in {"stem","pool0","stage1".."stage4","trans1".."trans3",
  * "stage<k>_l0_bottleneck"}; returns the element count through *numel. */

@@ -64,6 +64,11 @@ _SIGS = {
     "tn_densenet121_feature_dim": (C.c_int, [_P]),
     "tn_densenet121_workspace_bytes": (C.c_size_t, [_P]),
     "tn_densenet121_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "tn_densenet121_forward_class_maps": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "tn_densenet121_class_map_dims": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tn_dbg_profile_class_maps": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(TnKernelStat), C.c_int, C.POINTER(C.c_int)]),
+    "tn_dbg_class_maps": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tn_densenet121_set_pipelined": (C.c_int, [_P, C.c_int]),
     "tn_densenet121_join": (C.c_int, [_P, C.c_int]),
     "tn_densenet121_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(TnKernelStat), C.c_int,

@@ -54,13 +54,7 @@ extern "C" int tn_ctx_destroy(tn_ctx *ctx) {
   return TN_OK;
 }
 
-// ---- Dense -----------------------------------------------------------------------
-struct tn_dense {
-  tn_ctx *ctx;
-  DevPool pool;
-  float *w, *b;
-  int units, in_units;
-};
+// ---- Dense (struct tn_dense: api_internal.h) --------------------------------------
 
 extern "C" int tn_dense_create(tn_ctx *ctx, const float *weight_host, const float *bias_host, int units,
                                int in_units, tn_dense **out) {

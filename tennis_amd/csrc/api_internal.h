@@ -41,6 +41,14 @@ struct DevPool {  // owns device allocations of one handle
   }
 };
 
+// The Dense handle (api.hip); encoder.hip reads its weights for the class activation maps.
+struct tn_dense {
+  tn_ctx *ctx;
+  DevPool pool;
+  float *w, *b;      // (units, in_units), (units) or nullptr: fp32 on the device
+  int units, in_units;
+};
+
 // tn_birnn_forward (api.hip) with its input never materialised: row b * steps + t of x is row row_idx[b * steps + t] of table (n_rows,
 // input_size; row stride ld, DEVICE), a row of zeros where the index is negative; what tn_gnmt_encode_rows runs for encoder layer 0.
 int birnn_forward_rows(tn_birnn *r, const float *table, int n_rows, int ld, const int32_t *row_idx, int batch, int steps,

@@ -370,6 +370,13 @@ int launch_channel_mean(const f16 *x, int ld, int K, const float *scale, const f
                         float *out, hipStream_t s, int clamp = 0 /* scale / shift are lo / hi of the clamp form */);
 int launch_head(const f16 *x, int B, int H, int W, int C, const float *scale, const float *shift,
                 float *feat, int PH, int PW, hipStream_t s, const float *x32 = nullptr /* the same map un-rounded: read instead of x */);
+// class_maps.hip: the class activation maps of a Dense behind the head, from the map the head reads - x (fp16 NHWC) or, non-null,
+// x32 (the same un-rounded) - with the head's BatchNorm + ReLU applied on load; wd (classes, C PH PW) fp32 in the head's flatten
+// order, out (B, classes, 7 PH, 7 PW) fp32.  classes in [1, 64], C % 8 == 0.
+int launch_class_maps(const f16 *x, const float *x32, int B, int H, int W, int C, const float *scale, const float *shift, const float *wd,
+                      int PH, int PW, int classes, float *out, hipStream_t s);
+int class_maps_seq(int C);     // the longest sequential fp32 accumulation of a lane
+int class_maps_depth();        // levels of the cross-lane reduction
 
 // ---- the fp32 encoder mode (TN_ENC_FP32, dense_fp32.hip): fp32 activations, fp32 weights, f32-input MFMA ----
 enum { FP32_STEM = 0, FP32_1X1 = 1, FP32_3X3 = 2, FP32_TRANS = 3 };

@@ -275,6 +275,20 @@ extern "C" int tn_dbg_head(tn_ctx *ctx, const void *x_f16, const float *x32, int
   return TN_OK;
 }
 
+// class_maps_kernel alone (tennis_hip_debug.h): launch_class_maps on the fp16 map x_f16 or - x32 non-NULL - on the fp32 one.  Synchronous.
+extern "C" int tn_dbg_class_maps(tn_ctx *ctx, const void *x_f16, const float *x32, int B, int H, int W, int C, const float *scale,
+                                 const float *shift, const float *wd, int PH, int PW, int classes, float *maps, int *n_seq, int *depth) {
+  TN_REQUIRE(ctx && (x_f16 || x32) && scale && shift && wd && maps, "tn_dbg_class_maps: null argument");
+  TN_REQUIRE((((uintptr_t)x_f16 | (uintptr_t)x32 | (uintptr_t)wd) & 15) == 0, "tn_dbg_class_maps: the map and the weights must be 16-byte aligned");
+  TN_ON_DEVICE(ctx->device);
+  const int rc = launch_class_maps((const f16 *)x_f16, x32, B, H, W, C, scale, shift, wd, PH, PW, classes, maps, ctx->stream);
+  if (rc) return rc;
+  TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (n_seq) *n_seq = class_maps_seq(C);
+  if (depth) *depth = class_maps_depth();
+  return TN_OK;
+}
+
 // fp32 linear: y = x W^T + b
 extern "C" int tn_dbg_linear(tn_ctx *ctx, const float *x, const float *w, const float *bias, float *y, int M, int N,
                              int K) {

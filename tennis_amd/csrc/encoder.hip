@@ -219,6 +219,11 @@ struct tn_encoder {
   float *zeros128 = nullptr;   // a BatchNorm shift of zeros (un-fused dense layers: the shift was added by the 1x1)
   f16 *stem_out, *bott, *blockbuf[4];
   float *head32 = nullptr;     // the last block's map once more in fp32 (what the head reads): written by the last transition and the 7x7 block kernel
+  // tn_densenet121_forward_class_maps: set for the duration of that call only.  Every range of the call launches class_maps_kernel
+  // behind its head, on the map that head read, and writes the maps of its frames at their offset in cam_out.
+  const float *cam_w = nullptr;   // the Dense weight (cam_units, feat_dim), nullptr: no maps (every other entry point)
+  float *cam_out = nullptr;       // (batch, cam_units, 7 PH, 7 PW)
+  int cam_units = 0;
   size_t workspace_bytes;
   int last_batch;
   bool split;
@@ -342,7 +347,7 @@ static int create_fp32(tn_encoder *e, const ParamMap &pm, const std::string &pre
 // transitions (BN + ReLU + 2x2 average on load), and the head on the last concat buffer.  An fp32x3 encoder runs the same
 // sequence with launch_conv_fp32x3 on the three-term weight images (families "fp32x3_*").
 static int encoder_run_range_fp32(tn_encoder *e, const void *x, tn_layout layout, int B, float *feat, hipStream_t s, EventTimer &tm,
-                                  int w0) {
+                                  int w0, float *cam) {
   auto &F = e->f32;
   int rc;
   const bool x3 = e->fp32x3;
@@ -403,6 +408,12 @@ static int encoder_run_range_fp32(tn_encoder *e, const void *x, tn_layout layout
   }
   tm.begin("head_bnrelu_avgpool7", 0.0, fB * e->geom.Hb[3] * e->geom.Wb[3] * e->geom.Cb[3] * 4 + fB * e->geom.feat_dim * 4);
   rc = launch_head(nullptr, B, e->geom.Hb[3], e->geom.Wb[3], e->geom.Cb[3], F.head_s, F.head_t, feat, e->geom.PH, e->geom.PW, s, buf[3]);
+  tm.end();
+  if (rc || !cam) return rc;
+  tm.begin("class_maps", 2.0 * fB * 49 * e->geom.feat_dim * e->cam_units,
+           fB * e->geom.Hb[3] * e->geom.Wb[3] * e->geom.Cb[3] * 4 + fB * e->cam_units * 49 * e->geom.PH * e->geom.PW * 4);
+  rc = launch_class_maps(nullptr, buf[3], B, e->geom.Hb[3], e->geom.Wb[3], e->geom.Cb[3], F.head_s, F.head_t, e->cam_w, e->geom.PH, e->geom.PW,
+                         e->cam_units, cam, s);
   tm.end();
   return rc;
 }
@@ -679,7 +690,9 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
   const void *x = (const unsigned char *)x0 + (size_t)b0 * frame_bytes;
   float *feat = feat0 + (size_t)b0 * g.feat_dim;
   const int w0 = ws0 >= 0 ? ws0 : b0;        // first frame slot of the workspace (the second workspace set starts at maxB)
-  if (e->fp32) return encoder_run_range_fp32(e, x, layout, B, feat, s, tm, w0);
+  // the class activation maps of frames [b0, b0 + B), nullptr outside tn_densenet121_forward_class_maps
+  float *cam = e->cam_w ? e->cam_out + (size_t)b0 * e->cam_units * 49 * g.PH * g.PW : nullptr;
+  if (e->fp32) return encoder_run_range_fp32(e, x, layout, B, feat, s, tm, w0, cam);
   f16 *stem_out = e->stem_out + (size_t)w0 * g.Hs * g.Ws * 64;
   f16 *bott = e->bott + (size_t)w0 * g.Hb[0] * g.Wb[0] * 128;
   f16 *bbuf[4];
@@ -804,6 +817,11 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
   begin("head_bnrelu_avgpool7", head_cost(g, fB));
   rc = launch_head(bbuf[3], B, g.Hb[3], g.Wb[3], g.Cb[3], e->head_s, e->head_t, feat, g.PH, g.PW, s, h32);
   tm.end();
+  if (rc || !cam) return rc;
+  // the same source the head just read (h32 where this forward wrote it), the same BatchNorm + ReLU on load, this range's stream
+  tm.begin("class_maps", 2.0 * fB * 49 * g.feat_dim * e->cam_units, fB * g.Hb[3] * g.Wb[3] * g.Cb[3] * (h32 ? 4 : 2) + fB * e->cam_units * 49 * g.PH * g.PW * 4);
+  rc = launch_class_maps(bbuf[3], h32, B, g.Hb[3], g.Wb[3], g.Cb[3], e->head_s, e->head_t, e->cam_w, g.PH, g.PW, e->cam_units, cam, s);
+  tm.end();
   return rc;
 }
 
@@ -907,6 +925,58 @@ extern "C" int tn_densenet121_join(tn_encoder *enc, int lag) {
 extern "C" int tn_densenet121_forward(tn_encoder *enc, const void *x, tn_layout layout, int batch, float *feat) {
   EventTimer tm;
   return encoder_run(enc, x, layout, batch, feat, tm);
+}
+
+extern "C" int tn_densenet121_class_map_dims(const tn_encoder *enc, int *h, int *w) {
+  TN_REQUIRE(enc && h && w, "tn_densenet121_class_map_dims: null argument");
+  *h = 7 * enc->geom.PH;
+  *w = 7 * enc->geom.PW;
+  return TN_OK;
+}
+
+// forward with `cam_*` set for the duration of the call: every range launches the maps behind its head (encoder_run_range)
+static int class_maps_check(const char *fn, tn_encoder *enc, const void *x, float *feat, const tn_dense *classes, float *maps) {
+  const std::string f(fn);
+  TN_REQUIRE(enc, f + ": null encoder");
+  TN_REQUIRE(x, f + ": x is null");
+  TN_REQUIRE(feat, f + ": features is null");
+  TN_REQUIRE(classes, f + ": classes is null");
+  TN_REQUIRE(maps, f + ": maps is null");
+  TN_REQUIRE(classes->ctx == enc->ctx, f + ": classes belongs to another context than the encoder");
+  TN_REQUIRE(classes->in_units == enc->geom.feat_dim, f + ": classes has in_units " + std::to_string(classes->in_units) + ", the encoder's feature width is " +
+                                                          std::to_string(enc->geom.feat_dim));
+  TN_REQUIRE(classes->units <= 64, f + ": classes has " + std::to_string(classes->units) + " units, the maps take at most 64");
+  TN_REQUIRE(enc->calib_dev == nullptr, f + ": a calibration pass is in progress");
+  return TN_OK;
+}
+
+extern "C" int tn_densenet121_forward_class_maps(tn_encoder *enc, const void *x, tn_layout layout, int batch, float *feat,
+                                                 const tn_dense *classes, float *maps) {
+  if (int rc = class_maps_check("tn_densenet121_forward_class_maps", enc, x, feat, classes, maps)) return rc;
+  enc->cam_w = classes->w; enc->cam_out = maps; enc->cam_units = classes->units;
+  EventTimer tm;
+  const int rc = encoder_run(enc, x, layout, batch, feat, tm);
+  enc->cam_w = nullptr; enc->cam_out = nullptr; enc->cam_units = 0;
+  return rc;
+}
+
+// the same under the event timer (one stream, as tn_densenet121_profile): the family "class_maps" beside "head_bnrelu_avgpool7"
+extern "C" int tn_dbg_profile_class_maps(tn_encoder *enc, const void *x, tn_layout layout, int batch, float *feat,
+                                                 const tn_dense *classes, float *maps, tn_kernel_stat *stats, int max_stats, int *n_stats) {
+  TN_REQUIRE(stats && n_stats, "tn_dbg_profile_class_maps: null argument");
+  if (int rc = class_maps_check("tn_dbg_profile_class_maps", enc, x, feat, classes, maps)) return rc;
+  enc->cam_w = classes->w; enc->cam_out = maps; enc->cam_units = classes->units;
+  EventTimer tm;
+  tm.on = true;
+  tm.s = enc->ctx->stream;
+  const int rc = encoder_run(enc, x, layout, batch, feat, tm);
+  tm.finish();
+  enc->cam_w = nullptr; enc->cam_out = nullptr; enc->cam_units = 0;
+  if (rc) return rc;
+  const int n = (int)tm.fams.size() < max_stats ? (int)tm.fams.size() : max_stats;
+  for (int i = 0; i < n; ++i) stats[i] = tm.fams[i];
+  *n_stats = n;
+  return TN_OK;
 }
 
 extern "C" int tn_densenet121_profile(tn_encoder *enc, const void *x, tn_layout layout, int batch, float *feat,

@@ -197,15 +197,47 @@ class DenseNet121Features(_Handle):
         self.feature_dim = self.lib.tn_densenet121_feature_dim(h)
         self.workspace_bytes = self.lib.tn_densenet121_workspace_bytes(h)
 
-    def __call__(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    def __call__(self, x: torch.Tensor, out: torch.Tensor | None = None, class_maps: "Dense | None" = None):
+        """Features ``(B, F)``.  ``class_maps=<engine.Dense>`` (``F`` inputs, at most 64 units, same context): returns
+        ``(features, maps)`` with ``maps`` ``(B, units, *class_map_dims)`` the class activation maps of that Dense
+        (``tn_densenet121_forward_class_maps``): ``bias[c] + maps[b, c].sum()`` is logit ``c`` of frame ``b``.  The features are
+        bit-identical to a call without maps; a pipelined call orders the maps with ``join`` as it orders the features."""
         _on_ctx_device(self.ctx, x, "DenseNet121Features")
         x = x.contiguous()
         layout = _layout_of(x, self.size)
         b = x.shape[0]
         if out is None:
             out = torch.empty((b, self.feature_dim), dtype=torch.float32, device=x.device)
-        check(self.lib.tn_densenet121_forward(self.handle, ptr(x), layout, b, ptr(out)), "tn_densenet121_forward")
-        return out
+        if class_maps is None:
+            check(self.lib.tn_densenet121_forward(self.handle, ptr(x), layout, b, ptr(out)), "tn_densenet121_forward")
+            return out
+        if not isinstance(class_maps, Dense):
+            raise TypeError(f"class_maps must be an engine.Dense, got {type(class_maps).__name__}")
+        maps = torch.empty((b, class_maps.units) + self.class_map_dims, dtype=torch.float32, device=x.device)
+        check(self.lib.tn_densenet121_forward_class_maps(self.handle, ptr(x), layout, b, ptr(out), class_maps.handle, ptr(maps)),
+              "tn_densenet121_forward_class_maps")
+        return out, maps
+
+    @property
+    def class_map_dims(self) -> tuple:
+        """``(h, w)`` of a class activation map: 7 cells per pool window each way (7 x 7 at 224^2, 14 x 14 at 512^2)."""
+        h, w = C.c_int(), C.c_int()
+        check(self.lib.tn_densenet121_class_map_dims(self.handle, C.byref(h), C.byref(w)), "tn_densenet121_class_map_dims")
+        return h.value, w.value
+
+    def profile_class_maps(self, x: torch.Tensor, class_maps: "Dense"):
+        """``profile`` of a forward with maps: the family ``class_maps`` beside ``head_bnrelu_avgpool7`` -> (list of dicts, features, maps)."""
+        x = x.contiguous()
+        layout = _layout_of(x, self.size)
+        b = x.shape[0]
+        out = torch.empty((b, self.feature_dim), dtype=torch.float32, device=x.device)
+        maps = torch.empty((b, class_maps.units) + self.class_map_dims, dtype=torch.float32, device=x.device)
+        stats = (_lib.TnKernelStat * 24)()
+        n = C.c_int(0)
+        check(self.lib.tn_dbg_profile_class_maps(self.handle, ptr(x), layout, b, ptr(out), class_maps.handle, ptr(maps), stats, 24, C.byref(n)),
+              "tn_dbg_profile_class_maps")
+        return [dict(name=stats[i].name.decode(), launches=stats[i].launches, ms=stats[i].ms,
+                     flops=stats[i].flops, bytes=stats[i].bytes) for i in range(n.value)], out, maps
 
     def set_pipelined(self, on: bool = True):
         """Consecutive calls overlap on the library's side streams; the caller orders the results with ``join`` (see

@@ -50,6 +50,83 @@ def evaluate_model(net, loader, dataset, metrics, ctx=None):
     return results, ground_truths
 
 
+def check_save_cams(flags, world=1):
+    """``--save_cams`` is for a frame model on one rank: exits with the reason otherwise.  Touches no device."""
+    if not getattr(flags, "save_cams", False):
+        return
+    if flags.window != 1:
+        raise SystemExit("--save_cams needs a frame model: --window %d evaluates a temporal model, and past a recurrent layer or a pool "
+                         "over windows a logit is no longer a sum over the cells of one frame's map" % flags.window)
+    if flags.feats_model is not None:
+        raise SystemExit("--save_cams needs the frames: --feats_model evaluates stored features, the last feature map is not there")
+    if flags.temp_pool is not None:
+        raise SystemExit("--save_cams needs a frame model: --temp_pool %s pools over frames" % flags.temp_pool)
+    if flags.save_feats:
+        raise SystemExit("--save_cams writes the maps of a test run: not together with --save_feats")
+    if flags.dense_windows or flags.corpus_frames > 0:
+        raise SystemExit("--save_cams needs a frame model: not together with --dense_windows / --corpus_frames")
+    if flags.num_gpus > 1 or world > 1:
+        raise SystemExit("--save_cams writes one file from one rank: run it with --num_gpus 1")
+
+
+def evaluate_model_cams(net, loader, dataset, metrics):
+    """``evaluate_model`` of a ``FrameModel`` through ``forward(x, return_cam=True)``: the same logits (bit for bit), the same
+    metric updates and return values, and as a third value the columns of ``save_cams`` in loader order - per frame the map of
+    its arg-max class ``cam (N, h, w)``, ``pred``, ``label``, that class's ``logit``, ``video`` and ``frame``."""
+    results, ground_truths = dict(), dict()
+    cols = {k: [] for k in ("cam", "pred", "label", "logit", "video", "frame")}
+    for data, labels, idxs in loader:
+        outputs, cam = net(data, return_cam=True)
+        lab = torch.from_numpy(labels).to(outputs.device)
+        for metric in metrics:
+            metric.update([lab], [outputs])
+        pred = outputs.argmax(1)
+        rows = torch.arange(outputs.shape[0], device=outputs.device)
+        cols["cam"].append(cam[rows, pred].cpu().numpy())
+        cols["pred"].append(pred.cpu().numpy())
+        out = outputs.cpu().numpy()
+        cols["logit"].append(out[np.arange(len(out)), cols["pred"][-1]])
+        for i, idx in enumerate(int(j) for j in idxs):
+            sample = dataset._samples[idx]
+            img_path = dataset.get_image_path(dataset._frames_dir, sample[0], sample[1])
+            results[img_path] = out[i]
+            ground_truths[img_path] = dataset.classes.index(sample[2])
+            cols["label"].append(ground_truths[img_path])
+            cols["video"].append(sample[0])
+            cols["frame"].append(int(sample[1]))
+    for k in ("cam", "pred", "logit"):
+        cols[k] = np.concatenate(cols[k])
+    return results, ground_truths, cols
+
+
+def save_cams(file_path, cam, pred, label, logit, video, frame):
+    """One ``.npz`` of flat arrays (``np.load(..., allow_pickle=False)`` reads it): ``cam (N, h, w)`` float32 the class activation
+    map of each frame's arg-max class, ``pred (N,)`` that class, ``label (N,)``, ``logit (N,)`` its logit
+    (= the Dense bias of ``pred`` + ``cam.sum((1, 2))``), ``video (N,)`` unicode and ``frame (N,)`` the frame number."""
+    cam = np.ascontiguousarray(cam, np.float32)
+    n = len(cam)
+    if cam.ndim != 3:
+        raise ValueError(f"save_cams: cam must be (N, h, w), got {cam.shape}")
+    cols = dict(cam=cam, pred=np.asarray(pred, np.int64).reshape(-1), label=np.asarray(label, np.int64).reshape(-1),
+                logit=np.asarray(logit, np.float32).reshape(-1), video=np.asarray(list(video), dtype=np.str_).reshape(-1),
+                frame=np.asarray(frame, np.int64).reshape(-1))
+    for k, v in cols.items():
+        if len(v) != n:
+            raise ValueError(f"save_cams: {k} has {len(v)} entries for {n} maps")
+    os.makedirs(os.path.dirname(os.path.abspath(file_path)), exist_ok=True)
+    np.savez(file_path, **cols)
+
+
+def load_cams(file_path):
+    """-> dict of ``save_cams``' arrays: ``cam``, ``pred``, ``label``, ``logit``, ``video``, ``frame``."""
+    with np.load(file_path, allow_pickle=False) as z:
+        d = {k: z[k] for k in z.files}
+    missing = [k for k in ("cam", "pred", "label", "logit", "video", "frame") if k not in d]
+    if missing:
+        raise ValueError(f"{file_path}: not a file of save_cams (no {', '.join(missing)})")
+    return d
+
+
 def load_feature_matrix(dataset):
     """The dataset-order (len(dataset), F) feature matrix from the ``.npy`` files of ``dataset.feat_dir``: every frame's file is
     read once (the loader path reads it once per window that contains it)."""
@@ -498,11 +575,17 @@ def build_parser():
                         "features (evaluate_windows; evaluate_table for splits without an arithmetic window form), without it from "
                         "frames, each distinct frame decoded and encoded once (evaluate_table); with --corpus_frames N the head "
                         "runs over the gathered matrix as one sequence")
+    p.add_argument("--save_cams", action="store_true",
+                   help="frame model only (--window 1, no --feats_model, no --temp_pool; not a reference flag): also write "
+                        "<split>_cams.npz into the experiment's directory - per frame the class activation map of its arg-max class "
+                        "(7 x 7 cells at 224, 14 x 14 at 512), the class, the label, that class's logit, the video and the frame "
+                        "number (evaluate.load_cams reads it); the maps come out of the same forward, the metrics do not change")
     return p
 
 
 def main(argv=None):
     flags = build_parser().parse_args(argv)
+    check_save_cams(flags)                                                  # refusals before any device work
     if flags.num_gpus > 1 and not sharding.under_launcher():
         # evaluate.py:101-102 builds ctx = [gpu(0) .. gpu(N-1)] in one process; here: one process per GPU
         if torch.cuda.is_available() and flags.num_gpus > torch.cuda.device_count():
@@ -527,6 +610,7 @@ def _main_rank(flags, rank, world, dev):
         flags.num_workers = 3                                               # (files -> features peaks at three decoder threads: scripts/bench_pipeline.py, profiles/r05_c_*)
     every = [int(s) for s in flags.every.split(",")]
     check_dense_windows(flags)                                              # refusals before anything is built
+    check_save_cams(flags, world)
     if flags.corpus_frames > 0:                                             # BASELINE config C4
         backbone = get_model(flags.backbone, pretrained=True, max_batch=flags.batch_size, conversion=flags.fp16_conversion).features
         full, st = extract_corpus(backbone, flags.corpus_frames, flags.batch_size, flags.data_shape, dev, rank, world,
@@ -637,6 +721,11 @@ def _main_rank(flags, rank, world, dev):
             m.scores = packed[m.mat.size:].reshape(m.scores.shape)
         if rank != 0:
             return 0
+    elif flags.save_cams:
+        results, gts, cols = evaluate_model_cams(model, test_data, test_set, test_metrics)
+        cams_file = os.path.join(flags.exp_root, flags.model_id, flags.split + "_cams.npz")
+        save_cams(cams_file, **cols)
+        print("Saved %d class activation maps %s: %s" % (len(cols["cam"]), tuple(cols["cam"].shape[1:]), cams_file))
     else:
         results, gts = evaluate_model(model, test_data, test_set, test_metrics)
     str_ = "Test set:"                                                       # evaluate.py:250-255

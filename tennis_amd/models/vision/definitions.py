@@ -94,7 +94,16 @@ class FrameModel(Block):
         if num_classes > 0:
             self.classes = Dense(num_classes, flatten=True, prefix=self.prefix + "dense0_")
 
-    def forward(self, x):
+    def forward(self, x, return_cam=False):
+        """``return_cam=True``: ``(logits, cam)`` with ``cam`` ``(B, classes, h, w)`` the class activation maps of the same
+        forward (7 x 7 cells per pool window: 7 x 7 at 224^2, 14 x 14 at 512^2) - ``classes.bias[c] + cam[b, c].sum()`` is
+        ``logits[b, c]``, exactly in real arithmetic (the network ends in BN, ReLU, average pool, Dense: CAM, no backward pass).
+        The logits are those of ``forward(x)``, bit for bit.  Needs a model with ``classes``."""
+        if return_cam:
+            if not self.classes:
+                raise ValueError("return_cam=True needs a FrameModel with classes (num_classes > 0): the maps are those of its Dense")
+            feat, cam = self.backbone(x, class_maps=self.classes.engine_for)
+            return self.classes(feat), cam
         x = self.backbone(x)            # definitions.py:30
         if self.classes:
             x = self.classes(x)         # definitions.py:31-32

@@ -32,14 +32,18 @@ class Dense(Block):
             self._adopt(p)
         self._in_units = w.data.shape[1]
 
-    def forward(self, x):
-        x = _to_device(x)
-        x = x.reshape(x.shape[0], -1)
-        self._materialize(x.shape[1])
+    def engine_for(self, in_units):
+        """The ``engine.Dense`` that ``forward`` runs for inputs of that width (materialised on first use)."""
+        self._materialize(in_units)
         if self._engine is None:
             self._engine = engine.Dense(self._own_params[self.prefix + "weight"].data,
                                         self._own_params[self.prefix + "bias"].data)
-        return self._engine(x)
+        return self._engine
+
+    def forward(self, x):
+        x = _to_device(x)
+        x = x.reshape(x.shape[0], -1)
+        return self.engine_for(x.shape[1])(x)
 
 
 class _RNNLayer(Block):
@@ -175,7 +179,9 @@ class DenseNet121Backbone(Block):
         p = {k: v.data for k, v in self._own_params.items()}
         self._converted = calibrated_fp16_model(p, frames, size, prefix=self.prefix)
 
-    def forward(self, x):
+    def forward(self, x, class_maps=None):
+        """``class_maps``: an ``engine.Dense`` over the features, or a callable ``feature_dim -> engine.Dense`` (the Dense may only
+        know its input width once the frames' size is known) -> ``(features, maps)`` (engine.DenseNet121Features.__call__)."""
         x = _to_device(x)
         if next(iter(self._own_params.values())).data is None:
             self.initialize()
@@ -191,4 +197,8 @@ class DenseNet121Backbone(Block):
             self._engine = engine.DenseNet121Features(p, size, max_batch=max(b, min(self._max_batch, 64)),
                                                       prefix=self.prefix, exact_weights=self._exact, fp32=self._fp32, fp32x3=self._fp32x3)
             self._size = size
-        return self._engine(x)
+        if class_maps is None:
+            return self._engine(x)
+        if callable(class_maps) and not isinstance(class_maps, engine.Dense):
+            class_maps = class_maps(self._engine.feature_dim)
+        return self._engine(x, class_maps=class_maps)
