@@ -16,7 +16,7 @@ $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/tennis_hip.h include/
 # Its units are compiled with -save-temps so that the ISA that IS in the object (not a second compile) can be audited:
 # the kernel keeps a window of bottleneck rows in literal accumulator registers behind hipcc's back
 # (scripts/audit_strip_isa.py; `make audit`, run by __graft_entry__.build() and tests/test_cpu_build.py).
-STRIP_UNITS := dense_strip_w56 dense_strip_w28 dense_strip_w128 dense_strip_w64 dense_strip_chain_w56 dense_strip_chain_w28
+STRIP_UNITS := dense_strip_w56 dense_strip_w28 dense_strip_w128 dense_strip_w64 dense_strip_chain_w56 dense_strip_chain_w28 dense_strip_pair_w28
 STRIP_OBJS  := $(STRIP_UNITS:%=$(CSRC)/%.o)
 ISA_DIR     := $(CSRC)/isa
 # (grouped target: one recipe makes the object AND its ISA listing)

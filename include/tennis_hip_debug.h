@@ -118,6 +118,19 @@ int tn_dbg_pack_strip(const float *w1_host, int K, const float *s2_host, const f
 int tn_dbg_dense_strip_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K, const float *s1, const float *t1,
                            const void *w1s_f16, const void *w3s_f16, int B, int H, int W,
                            unsigned long long *ts /* NULL or 128 s_memtime stamps per frame */);
+/* The same layer in the paired launch geometry of the 28x28 maps (csrc/dense_strip_pair_w28.hip): two frames per workgroup, each
+ * wave walks half a frame; bit-identical to tn_dbg_dense_strip_dev on the same input.  28x28 and K = 128 ... 320 only; an odd B is
+ * refused without a launch.  ts: NULL or 128 stamps per workgroup (B / 2 of them).  The chained form runs nl = 6 layers from
+ * K0 = 128 in one launch, as six calls of tn_dbg_dense_strip_dev in order would; its operand arrays hold one device pointer per
+ * layer, and it is synchronous. */
+int tn_dbg_dense_strip_pair_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K, const float *s1, const float *t1,
+                                const void *w1s_f16, const void *w3s_f16, int B, int H, int W, unsigned long long *ts);
+int tn_dbg_dense_strip_pair_chain_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K0, int nl, const float *const *s1,
+                                      const float *const *t1, const void *const *w1s_f16, const void *const *w3s_f16, int B, int H,
+                                      int W);
+/* *count: how many launches of the process took the paired 28x28 strip kernels so far.  The instrumented pass never takes that
+ * route (it does not share the chip with a neighbouring call), so this count is how a test sees it. */
+int tn_dbg_strip_pair_launches(int64_t *count);
 
 /* The LDS-resident 7x7 dense block (csrc/dense_block7.hip): nl layers from K0 input channels in ONE launch on a device
  * concat buffer (B,7,7,ldc) fp16.  w1_all: the (128, K_l) 1x1 weights one after the other (K_l = K0 + 32 l); s1_all / t1_all
@@ -204,6 +217,11 @@ int tn_dbg_rnn_wide_launches(int64_t *count);
  * first-seen order, ms 0 - from the routing plan create and forward both follow (csrc/encoder_plan.h).  Refuses what create refuses
  * for the size and the flags, and TN_ENC_FP32 / TN_ENC_FP32X3, which are not planned.  Host arithmetic only: touches no device. */
 int tn_dbg_encoder_plan(int height, int width, int flags, int batch, int calibrate, tn_kernel_stat *stats, int max_stats, int *n_stats);
+/* The same plan for a forward that shares the chip with a neighbouring stream's call (a pipelined whole-batch call; never the
+ * calibration pass): the same families, launches, flops and bytes, and *paired_out: how many of its steps take the paired launch
+ * geometry of the 28x28 strip kernels (TN_NO_STRIP_PAIR, TN_STRIP_PAIR_MIN_BATCH; an even batch only). */
+int tn_dbg_encoder_plan_shared(int height, int width, int flags, int batch, tn_kernel_stat *stats, int max_stats, int *n_stats,
+                               int *paired_out);
 
 /* The parameter table of a training handle, built by the function its create calls (csrc/param_table.h): one row per readable name,
  * in the order of the flat buffers.  where: 0 the flat parameter / gradient buffers (tn_*_buffers) at `offset` floats, 1 the

@@ -1,9 +1,9 @@
-"""Audit of the strip kernel's ISA (dense_strip_impl.h, instantiated in dense_strip_w*.hip) (no GPU needed): the kernel keeps its bottleneck window in literal accumulator registers
+"""Audit of the strip kernel's ISA (dense_strip_impl.h, instantiated in dense_strip_w*.hip, dense_strip_chain_w*.hip and dense_strip_pair_w28.hip) (no GPU needed): the kernel keeps its bottleneck window in literal accumulator registers
 a[160:255], which hipcc does not know are live.  This script fails if the compiler's own code touches them.
 
   python scripts/audit_strip_isa.py <dense_strip_w56 ... gfx950.s> [more .s files]   (scripts/isa_build.sh tennis_amd/csrc/dense_strip_w56.hip -fno-slp-vectorize)
 
-For every dense_strip kernel it checks that
+For every dense_strip kernel (dense_strip_kernel*, dense_strip_pair_kernel*) it checks that
   1. no instruction OUTSIDE an inline-asm region (;;#ASMSTART .. ;;#ASMEND) names an accumulator register >= 160;
   2. nothing was spilled to scratch (.private_segment_fixed_size 0, .vgpr_spill_count 0);
   3. no compiler v_accvgpr_* instruction sits directly in front of an asm MFMA block whose accumulator operands it writes
@@ -39,7 +39,7 @@ def main():
     text = "\n".join(open(p).read() for p in sys.argv[1:])
     bad = 0
     kernels = 0
-    for m in re.finditer(r"^(\S*dense_strip_kernel\S*):", text, re.M):
+    for m in re.finditer(r"^(\S*dense_strip_(?:pair_)?kernel\S*):", text, re.M):
         name = m.group(1)
         end = text.find(".end_amdhsa_kernel", m.end())
         body = text[m.end():text.rfind("s_endpgm", m.end(), end) + 8]

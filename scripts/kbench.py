@@ -18,6 +18,7 @@ ap.add_argument("--blocks", default="0,1,2,3")
 ap.add_argument("--lib", default="")
 ap.add_argument("--allk", action="store_true")
 ap.add_argument("--stamps", action="store_true")
+ap.add_argument("--pair", action="store_true", help="ds: the 28x28 layers in the paired launch geometry (two frames per workgroup, dense_strip_pair_w28.hip)")
 ap.add_argument("--ws", action="store_true", help="tr: the last transition on trans_ws.hip")
 ap.add_argument("--b7stamps", type=int, default=5)
 args = ap.parse_args()
@@ -155,16 +156,19 @@ for v in [int(s) for s in args.variants.split(",")]:
                 lib.tn_dbg_pack_strip(w1.ctypes.data_as(C.c_void_p), K, s2.ctypes.data_as(C.c_void_p), t2.ctypes.data_as(C.c_void_p), w1s.ctypes.data_as(C.c_void_p), None, None)
                 w1d = torch.from_numpy(w1s.view(np.int16)).cuda()
                 s1 = torch.rand(K, device="cuda") + 0.5; t1 = torch.randn(K, device="cuda") * 0.3
-                fn = lambda: _lib.check(lib.tn_dbg_dense_strip_dev(ctx.handle, _lib.ptr(buf), ctot, K, _lib.ptr(s1), _lib.ptr(t1),
-                                                                   _lib.ptr(w1d), _lib.ptr(w3d), B, hw, hw, None))
+                pair = args.pair and hw == 28
+                hook = lib.tn_dbg_dense_strip_pair_dev if pair else lib.tn_dbg_dense_strip_dev
+                nwg = B // 2 if pair else B       # workgroups = rows of stamps
+                fn = lambda: _lib.check(hook(ctx.handle, _lib.ptr(buf), ctot, K, _lib.ptr(s1), _lib.ptr(t1),
+                                             _lib.ptr(w1d), _lib.ptr(w3d), B, hw, hw, None))
                 us = timed(fn, args.iters)
                 tot += us
                 if args.stamps:
                     ts = torch.zeros((B * 128,), dtype=torch.int64, device="cuda")
-                    _lib.check(lib.tn_dbg_dense_strip_dev(ctx.handle, _lib.ptr(buf), ctot, K, _lib.ptr(s1), _lib.ptr(t1), _lib.ptr(w1d),
-                                                          _lib.ptr(w3d), B, hw, hw, _lib.ptr(ts)))
+                    _lib.check(hook(ctx.handle, _lib.ptr(buf), ctot, K, _lib.ptr(s1), _lib.ptr(t1), _lib.ptr(w1d),
+                                    _lib.ptr(w3d), B, hw, hw, _lib.ptr(ts)))
                     torch.cuda.synchronize()
-                    t = ts.cpu().numpy().astype(np.float64).reshape(B, 128)
+                    t = ts.cpu().numpy().astype(np.float64).reshape(B, 128)[:nwg]
                     n = int((t[0, :125] > 0).sum())
                     real_us = (t[:, 125] - t[:, 126]) / 100.0
                     print("   wave 0: %.1f us of wall clock (median; min %.1f max %.1f; launch span %.1f us), shader clock %.2f GHz"
@@ -178,7 +182,7 @@ for v in [int(s) for s in args.variants.split(",")]:
                     print("      mean A %.0f  mean B %.0f  (A slots %d, B slots 72)" % (med[2:-2:2].mean(), med[3:-2:2].mean(), K // 4), flush=True)
                 fl = 2.0 * M * (128 * K + 32 * 1152)
                 by = M * (K + 32) * 2
-                res.append(dict(k="ds", hw=hw, K=K, us=round(us, 1), tf=round(fl / us / 1e6, 1), tbs=round(by / us / 1e6, 2)))
+                res.append(dict(k="ds_pair" if pair else "ds", hw=hw, K=K, us=round(us, 1), tf=round(fl / us / 1e6, 1), tbs=round(by / us / 1e6, 2)))
                 print(res[-1], flush=True)
             print("   ds block %d: sum %.1f us" % (hw, tot), flush=True)
             del buf

@@ -220,6 +220,8 @@ _SIGS = {
     "tn_dbg_rnn_wide_launches": (C.c_int, [C.POINTER(C.c_int64)]),
     "tn_dbg_rnn_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tn_dbg_encoder_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TnKernelStat), C.c_int, C.POINTER(C.c_int)]),
+    "tn_dbg_encoder_plan_shared": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TnKernelStat), C.c_int, C.POINTER(C.c_int),
+                                             C.POINTER(C.c_int)]),
     "tn_dbg_trainer_params": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p, C.c_char_p, C.POINTER(TnParamRow), C.c_int,
                                         C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tn_dbg_linear_bnrelu": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -238,6 +240,9 @@ _SIGS = {
     "tn_comm_destroy": (C.c_int, [_P]),
     "tn_dbg_pack_strip": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "tn_dbg_dense_strip_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "tn_dbg_dense_strip_pair_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "tn_dbg_dense_strip_pair_chain_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "tn_dbg_strip_pair_launches": (C.c_int, [C.POINTER(C.c_int64)]),
     "tn_densenet121_input_means": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "tn_npy_writer_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "tn_npy_writer_submit": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_int]),

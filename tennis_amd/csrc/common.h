@@ -228,6 +228,13 @@ struct DenseStripChainArgs {
 bool dense_strip_chain_supported(int H, int W, int K0, int nl);
 int dense_strip_chain_layers(int H, int W, int K0);    // how many layers from K0 on the chained kernel of that map runs (0: none)
 int launch_dense_strip_chain(const DenseStripChainArgs &a, hipStream_t s);
+// The paired form of the 28 x 28 strip launches (dense_strip_pair_w28.hip): two frames per workgroup, B / 2 workgroups, each wave
+// walks half a frame.  The same arithmetic in the same order per output as the one-frame launches (bit-identical results); for
+// the step whose kernels share the chip with a neighbouring stream's (encoder_plan.h::EncPolicy::strip_pair_min_batch).
+// Refuses an odd B and every map but 28 x 28.
+int launch_dense_strip_pair(const DenseStripArgs &a, hipStream_t s);
+int launch_dense_strip_pair_chain(const DenseStripChainArgs &a, hipStream_t s);
+long strip_pair_launches();      // paired launches of the process so far (what tn_dbg_strip_pair_launches reports)
 std::vector<f16> pack_w1_strip(const float *w /*[128][K], BN2 scale folded in*/, int K, const float *shift /*[128] BN2 shift*/);
 std::vector<f16> pack_w3_strip(const float *w /*(32,128,3,3)*/);
 

@@ -327,6 +327,49 @@ extern "C" int tn_dbg_dense_strip_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K
   return launch_dense_strip(a, ctx->stream);
 }
 
+// The same layer in the paired launch geometry (dense_strip_pair_w28.hip: 28 x 28 only, two frames per workgroup, an even B);
+// ts: 128 stamps per WORKGROUP (B / 2 of them), wave 0's = the upper half of the workgroup's first frame
+extern "C" int tn_dbg_dense_strip_pair_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K, const float *s1, const float *t1,
+                                           const void *w1s_f16, const void *w3s_f16, int B, int H, int W, unsigned long long *ts) {
+  TN_REQUIRE(ctx && buf_f16 && s1 && t1 && w1s_f16 && w3s_f16, "tn_dbg_dense_strip_pair_dev: null argument");
+  DenseStripArgs a{(f16 *)buf_f16, ldc, K, s1, t1, (const f16 *)w1s_f16, (const f16 *)w3s_f16, B, H, W};
+  a.ts = ts;
+  return launch_dense_strip_pair(a, ctx->stream);
+}
+
+// nl layers K0, K0 + 32, ... in one paired launch (dense_strip_pair_kernel_chain: K0 = 128, nl = 6); per-layer operand arrays of
+// DEVICE pointers, host-resident.  Synchronous: the layer table is uploaded for the call and freed behind it.
+extern "C" int tn_dbg_dense_strip_pair_chain_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K0, int nl, const float *const *s1,
+                                                 const float *const *t1, const void *const *w1s_f16, const void *const *w3s_f16, int B,
+                                                 int H, int W) {
+  TN_REQUIRE(ctx && buf_f16 && s1 && t1 && w1s_f16 && w3s_f16, "tn_dbg_dense_strip_pair_chain_dev: null argument");
+  TN_REQUIRE(nl > 0 && nl <= 16, "tn_dbg_dense_strip_pair_chain_dev: bad layer count");
+  TN_ON_DEVICE(ctx->device);
+  std::vector<DenseStripLayerDev> tab(nl);
+  for (int l = 0; l < nl; ++l) {
+    TN_REQUIRE(s1[l] && t1[l] && w1s_f16[l] && w3s_f16[l], "tn_dbg_dense_strip_pair_chain_dev: null operand");
+    tab[l] = DenseStripLayerDev{s1[l], t1[l], (const f16 *)w1s_f16[l], (const f16 *)w3s_f16[l]};
+  }
+  DenseStripLayerDev *dev = nullptr;
+  TN_HIP_CHECK(hipMalloc((void **)&dev, sizeof(DenseStripLayerDev) * nl));
+  int rc = TN_OK;
+  if (hipMemcpy(dev, tab.data(), sizeof(DenseStripLayerDev) * nl, hipMemcpyHostToDevice) != hipSuccess) {
+    tn_set_error("tn_dbg_dense_strip_pair_chain_dev: upload failed");
+    rc = TN_ERR_HIP;
+  }
+  if (rc == TN_OK) {
+    const DenseStripChainArgs c{(f16 *)buf_f16, ldc, K0, nl, dev, B, H, W};
+    rc = launch_dense_strip_pair_chain(c, ctx->stream);
+  }
+  const hipError_t he = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(dev);
+  if (rc == TN_OK && he != hipSuccess) {
+    tn_set_error("tn_dbg_dense_strip_pair_chain_dev: the launch failed");
+    rc = TN_ERR_HIP;
+  }
+  return rc;
+}
+
 
 // ---- the LDS-resident 7x7 dense block (dense_block7.hip) ----
 // nl layers from K0 input channels: w1_all = the (128, K_l) 1x1 weights one after the other, s1_all / t1_all the folded BN1
@@ -604,8 +647,8 @@ extern "C" int tn_dbg_trainer_params(int which, const int *dims, int n_dims, con
 // tn_densenet121_profile would report them: families in first-seen order with launches, flops and bytes (ms 0).  Built from
 // what create and encoder_run_range follow (encoder_plan.h: enc_policy, enc_geom, enc_block_plan); host arithmetic only, no device
 // is touched.  Refuses what create refuses for the size and the flags, and the fp32 / fp32x3 modes, which are not planned.
-extern "C" int tn_dbg_encoder_plan(int height, int width, int flags, int batch, int calibrate, tn_kernel_stat *stats, int max_stats,
-                                   int *n_stats) {
+static int encoder_plan_stats(int height, int width, int flags, int batch, int calibrate, bool shared_chip, tn_kernel_stat *stats, int max_stats,
+                              int *n_stats, int *paired_out) {
   TN_REQUIRE(stats && n_stats && max_stats > 0, "tn_dbg_encoder_plan: null argument");
   TN_REQUIRE((flags & ~TN_ENC_EXACT_WEIGHTS) == 0, "tn_dbg_encoder_plan: unknown flag, or a mode that is not planned (TN_ENC_FP32, TN_ENC_FP32X3)");
   TN_REQUIRE(batch > 0, "tn_dbg_encoder_plan: batch must be positive");
@@ -628,6 +671,7 @@ extern "C" int tn_dbg_encoder_plan(int height, int width, int flags, int batch, 
     fams[i].bytes += c.bytes;
   };
   const double fB = (double)batch;
+  int paired = 0;
   if (p.fuse) {
     add("stem_conv_bn_relu_maxpool", stem_pool_cost(g, fB));
   } else {
@@ -636,7 +680,8 @@ extern "C" int tn_dbg_encoder_plan(int height, int width, int flags, int batch, 
   }
   for (int b = 0; b < 4; ++b) {
     const int M = batch * g.Hb[b] * g.Wb[b];
-    for (const EncStep &st : enc_block_plan(p, g, b, batch, calibrate != 0)) {
+    for (const EncStep &st : enc_block_plan(p, g, b, batch, calibrate != 0, shared_chip)) {
+      if (st.paired) ++paired;
       if (st.route == ENC_LAYERWISE) {
         add(family_name(st, g, b), conv1x1_cost(M, enc_layer_cin(g, b, st.l0)));
         add("conv3x3_bnrelu", conv3x3_cost(M));
@@ -650,6 +695,27 @@ extern "C" int tn_dbg_encoder_plan(int height, int width, int flags, int batch, 
   const int n = (int)fams.size() < max_stats ? (int)fams.size() : max_stats;
   for (int i = 0; i < n; ++i) stats[i] = fams[i];
   *n_stats = n;
+  if (paired_out) *paired_out = paired;
+  return TN_OK;
+}
+
+extern "C" int tn_dbg_encoder_plan(int height, int width, int flags, int batch, int calibrate, tn_kernel_stat *stats, int max_stats,
+                                   int *n_stats) {
+  return encoder_plan_stats(height, width, flags, batch, calibrate, false, stats, max_stats, n_stats, nullptr);
+}
+
+// The plan of a forward whose kernels share the chip with a neighbouring stream's call (the interleaved whole-batch branch of
+// encoder_run; never the calibration pass): the same families, launches, flops and bytes, and *paired_out: how many of its steps take
+// the paired launch geometry of the 28x28 strip kernels (encoder_plan.h::enc_strip_pair)
+extern "C" int tn_dbg_encoder_plan_shared(int height, int width, int flags, int batch, tn_kernel_stat *stats, int max_stats, int *n_stats,
+                                          int *paired_out) {
+  TN_REQUIRE(paired_out, "tn_dbg_encoder_plan_shared: null argument");
+  return encoder_plan_stats(height, width, flags, batch, 0, true, stats, max_stats, n_stats, paired_out);
+}
+
+extern "C" int tn_dbg_strip_pair_launches(int64_t *count) {
+  TN_REQUIRE(count, "tn_dbg_strip_pair_launches: null argument");
+  *count = (int64_t)strip_pair_launches();
   return TN_OK;
 }
 

@@ -1,6 +1,7 @@
 // Fused DenseNet dense layer, strip-streaming form: dispatch and host-side packing (the kernel is dense_strip_impl.h,
 // instantiated per map width in dense_strip_w*.hip).
 #include <array>
+#include <atomic>
 #include <vector>
 
 #include "common.h"
@@ -11,6 +12,8 @@ int launch_dense_strip_w128(const DenseStripArgs &a, hipStream_t s);
 int launch_dense_strip_w64(const DenseStripArgs &a, hipStream_t s);
 int launch_dense_strip_chain_w56(const DenseStripChainArgs &a, hipStream_t s);
 int launch_dense_strip_chain_w28(const DenseStripChainArgs &a, hipStream_t s);
+int launch_dense_strip_pair_w28(const DenseStripArgs &a, hipStream_t s);
+int launch_dense_strip_pair_chain_w28(const DenseStripChainArgs &a, hipStream_t s);
 
 bool dense_strip_supported(int H, int W, int K) {
   // (128 x 128: K <= 288 - the K = 320 instantiation of that width spills one register; a 512 x 512 input needs K <= 224 there)
@@ -44,6 +47,31 @@ int launch_dense_strip_chain(const DenseStripChainArgs &a, hipStream_t s) {
   TN_REQUIRE(a.buf && a.layers && a.B > 0, "dense_strip_chain: null operand");
   TN_REQUIRE(a.ldc % 64 == 0 && a.K0 + 32 * a.nl <= a.ldc, "dense_strip_chain: bad channel geometry");
   return a.W == 56 ? launch_dense_strip_chain_w56(a, s) : launch_dense_strip_chain_w28(a, s);
+}
+
+// ---- the paired form of the 28 x 28 launches: two frames per workgroup (dense_strip_pair_w28.hip) ----
+static std::atomic<long> g_strip_pair_launches{0};
+long strip_pair_launches() { return g_strip_pair_launches.load(std::memory_order_relaxed); }
+
+int launch_dense_strip_pair(const DenseStripArgs &a, hipStream_t s) {
+  TN_REQUIRE(a.H == 28 && a.W == 28 && dense_strip_supported(a.H, a.W, a.K), "dense_strip_pair: unsupported geometry (28 x 28, K = 128 ... 320)");
+  TN_REQUIRE(a.K >= 128, "dense_strip_pair: unsupported geometry (28 x 28, K = 128 ... 320)");
+  TN_REQUIRE(a.buf && a.s1 && a.t1 && a.w1s && a.w3s, "dense_strip_pair: null operand");
+  TN_REQUIRE(a.ldc % 64 == 0 && a.K + 32 <= a.ldc, "dense_strip_pair: bad channel geometry");
+  TN_REQUIRE(a.B > 0 && a.B % 2 == 0, "dense_strip_pair: odd batch (a workgroup takes two frames)");
+  const int rc = launch_dense_strip_pair_w28(a, s);
+  if (rc == TN_OK) g_strip_pair_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+
+int launch_dense_strip_pair_chain(const DenseStripChainArgs &a, hipStream_t s) {
+  TN_REQUIRE(a.H == 28 && a.W == 28 && dense_strip_chain_supported(a.H, a.W, a.K0, a.nl), "dense_strip_pair_chain: unsupported geometry");
+  TN_REQUIRE(a.buf && a.layers, "dense_strip_pair_chain: null operand");
+  TN_REQUIRE(a.ldc % 64 == 0 && a.K0 + 32 * a.nl <= a.ldc, "dense_strip_pair_chain: bad channel geometry");
+  TN_REQUIRE(a.B > 0 && a.B % 2 == 0, "dense_strip_pair_chain: odd batch (a workgroup takes two frames)");
+  const int rc = launch_dense_strip_pair_chain_w28(a, s);
+  if (rc == TN_OK) g_strip_pair_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
 }
 
 // ---- host-side packing (encoder.hip, dbg.hip) ----

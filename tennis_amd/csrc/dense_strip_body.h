@@ -3,8 +3,9 @@
 // once as the whole body of the per-layer kernel and once as the device function the chained kernel calls per layer).  Text
 // inclusion instead of a call from the kernel: an inlined call gives hipcc a different instruction order to allocate registers
 // for, and the per-layer kernels - two of them at 256 VGPRs with nothing to spare - are to keep the listings they have.
-// TN_STRIP_TID: the expression for the thread index (threadIdx.x in the kernel).  No include guard on purpose.
-  using G = DSGeom<W, KS>;
+// TN_STRIP_TID: the expression for the thread index (threadIdx.x in the kernel).  TN_STRIP_GEOM: the geometry type, DSGeom<W, KS> or
+// (dense_strip_pair_w28.hip) DSGeomPair<KS>: two 28 x 28 frames per workgroup, 14 rows per wave.  No include guard on purpose.
+  using G = TN_STRIP_GEOM;
   constexpr int H = W, NSU = G::NSU, K = KS * 32, KQ = G::KQ, ROWS = G::ROWS;
   constexpr bool ODD = (KS & 1) != 0;
   constexpr int XN = kXN, NPL = pl_len<KS>(), PLB = NPL < kPLB ? NPL : kPLB;
@@ -41,14 +42,16 @@
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n = lane & 31, h = lane >> 5;
   const int item = (int)(blockIdx.x % G::WGS) * 4 + wid;
-  const int pair = item % G::NPAIR, part = item / G::NPAIR;
+  // (two frames per workgroup: waves 0 / 1 take the halves of the first frame, 2 / 3 of the second; wid is wave-uniform, and so
+  // is the frame pointer below)
+  const int pair = item % G::NPAIR, part = G::FPW == 2 ? (wid & 1) : item / G::NPAIR;
   const int r_lo = part * ROWS, r_hi = r_lo + ROWS;
   const int x = 14 * (2 * pair + (n >> 4)) - 1 + (n & 15);
   const bool xvalid = x >= 0 && x < W;
   const int xc = x < 0 ? 0 : (x >= W ? W - 1 : x);
   const int ldc = a.ldc;
   const unsigned rowpitch = (unsigned)W * ldc * 2;
-  unsigned char *fb = (unsigned char *)(a.buf + (size_t)(blockIdx.x / G::WGS) * H * W * ldc);
+  unsigned char *fb = (unsigned char *)(a.buf + (size_t)(G::FPW == 2 ? 2 * blockIdx.x + (wid >> 1) : blockIdx.x / G::WGS) * H * W * ldc);
   const unsigned colb = (unsigned)xc * ldc * 2 + 64 * h;     // full super-steps: 64 B per lane
   const unsigned colh = (unsigned)xc * ldc * 2 + 32 * h;     // the trailing half super-step: 32 B per lane
   const bool store_ok = (n & 15) >= 1 && (n & 15) <= 14 && xvalid;
@@ -58,6 +61,18 @@
   const unsigned char *w1l = smem + G::W1OFF + lane * 16;
   const unsigned char *w3l = smem + lane * 16;
   const f16 *tab1 = (const f16 *)(smem + G::T1OFF);
+  // The paired geometry reads its weight fragments through three opaque base registers, 64 KiB apart (a ds_read's offset field
+  // holds 16 bits).  From w1l / w3l hipcc forms a base register of its own per fragment past 64 KiB and keeps them all live across
+  // the row loop: with the extra row event behind a 14-row loop (NREM = 1) that is five / six VGPRs too many at K = 288 / 320,
+  // which went to scratch.  Same reads in the same slots; the one-frame instantiations keep the addresses they have.
+  typedef __attribute__((address_space(3))) const unsigned char *lcp_t;
+  unsigned lb0 = (unsigned)(size_t)(lcp_t)smem + lane * 16, lb1 = lb0 + 65536, lb2 = lb0 + 131072;
+  if constexpr (G::FPW == 2) asm volatile("" : "+v"(lb0), "+v"(lb1), "+v"(lb2));
+  auto lds_frag = [&](auto off_tag) TN_INL {      // the lane's 16 bytes of the 1 KiB fragment at byte OFF of the LDS image
+    constexpr int OFF = decltype(off_tag)::value;
+    const lcp_t b = (lcp_t)(size_t)(OFF < 65536 ? lb0 : OFF < 131072 ? lb1 : lb2);     // (pointer arithmetic: the offset folds into the read)
+    return *(const __attribute__((address_space(3))) u32x4 *)(b + (OFF & 65535));
+  };
   // the pixel fragment of the shift k-step: (1, 1, mask, 0, 0, 0, 0, 0) in the lanes that hold k = 0 .. 7
   const u32x4 xb_shift = {h == 0 ? 0x3c003c00u : 0u, (h == 0 && !xvalid) ? 0x0000fb53u : 0u, 0u, 0u};   // fp16 1.0 = 0x3c00, -60000 = 0xfb53
 
@@ -118,7 +133,8 @@
   auto wa_item = [&](auto q_tag, auto mb_tag) TN_INL {
     constexpr int Q = decltype(q_tag)::value, MB = decltype(mb_tag)::value;
     if ((TN_DS_EXP & 16) && Q >= 2) return;     // (timing experiment: the 1x1 phase keeps reusing its first eight weight fragments)
-    wa[Q & 1][MB] = *(const u32x4 *)(w1l + (Q * 4 + MB) * 1024);
+    if constexpr (G::FPW == 2) wa[Q & 1][MB] = lds_frag(ic<G::W1OFF + (Q * 4 + MB) * 1024>{});
+    else wa[Q & 1][MB] = *(const u32x4 *)(w1l + (Q * 4 + MB) * 1024);
   };
   auto wa_group = [&](auto q_tag) TN_INL { static_for<4>([&](auto mb_tag) TN_INL { wa_item(q_tag, mb_tag); }); };
   // what the 3x3 phase of the previous row would have done for this row (first rows of a wave)
@@ -185,7 +201,8 @@
   auto w3_item = [&](auto s_tag, auto dx_tag) TN_INL {
     constexpr int S = decltype(s_tag)::value, DX = decltype(dx_tag)::value;
     if ((TN_DS_EXP & 8) && S >= 2) return;      // (timing experiment: the 3x3 phase keeps reusing its first six weight fragments)
-    w3f[S & 1][DX] = *(const u32x4 *)(w3l + (S * 3 + DX) * 1024);
+    if constexpr (G::FPW == 2) w3f[S & 1][DX] = lds_frag(ic<(S * 3 + DX) * 1024>{});
+    else w3f[S & 1][DX] = *(const u32x4 *)(w3l + (S * 3 + DX) * 1024);
   };
 
   // ================= 1x1 phase of bottleneck row yb (its first PLB pipeline items have run) =================

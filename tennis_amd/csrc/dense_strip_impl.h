@@ -63,6 +63,7 @@ struct DSGeom {
   static constexpr int ROWS = W == 56 ? 28 : W == 28 ? 7 : W / 4;     // output rows per wave
   static constexpr int NCHUNK = W / ROWS;
   static constexpr int NITEM = NPAIR * NCHUNK, WGS = NITEM / 4;       // workgroups per frame
+  static constexpr int FPW = 1;                  // frames per workgroup (2: DSGeomPair)
   static constexpr int KQ = 2 * KS;              // 16-channel k-steps
   static constexpr int NSU = (KS + 1) / 2;       // 64-channel super-steps (the last one is half when KS is odd)
   static constexpr int W1OFF = kW3Bytes;                   // KQ + 1 k-steps of 4 fragments: the last one carries BN2's shift
@@ -71,6 +72,15 @@ struct DSGeom {
   static_assert(W % ROWS == 0 && NITEM % 4 == 0 && ROWS >= 4, "strip geometry");
   static_assert(NSU <= 5, "the activation ring holds five super-steps");
   static_assert(LDS_BYTES <= 160 * 1024, "weights do not fit LDS");
+};
+
+// The 28 x 28 frame in the paired form (dense_strip_pair_w28.hip): TWO frames per workgroup, each wave walks half a frame - 14 output
+// rows, twice as many as a quarter to spread the per-wave fill (weight prologue, cold first row, window warm-up, exposed last
+// epilogue) over, and 15 or 16 bottleneck rows for them where two quarters compute 17 or 18.  Wave w: frame 2 blockIdx.x + (w >> 1),
+// rows [14 (w & 1), + 14).  LDS map, slot schedules and window registers are DSGeom<28, KS>'s; the layer's weights serve both frames.
+template <int KS>
+struct DSGeomPair : DSGeom<28, KS> {
+  static constexpr int ROWS = 14, NCHUNK = 2, NITEM = 2, WGS = 1, FPW = 2;
 };
 
 // The bottleneck window lives in LITERAL accumulator registers a[160:255] (three rows x eight 16-channel k-steps x one
@@ -234,7 +244,9 @@ constexpr bool a_sched_complete() {        // every epilogue B item and every pi
 template <int W, int KS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void dense_strip_kernel(DenseStripArgs a) {
 #define TN_STRIP_TID threadIdx.x
+#define TN_STRIP_GEOM DSGeom<W, KS>
 #include "dense_strip_body.h"
+#undef TN_STRIP_GEOM
 #undef TN_STRIP_TID
 }
 
@@ -244,7 +256,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 template <int W, int KS>
 __device__ __forceinline__ void dense_strip_layer(const DenseStripArgs &a, const int tid_in) {
 #define TN_STRIP_TID tid_in
+#define TN_STRIP_GEOM DSGeom<W, KS>
 #include "dense_strip_body.h"
+#undef TN_STRIP_GEOM
 #undef TN_STRIP_TID
 }
 

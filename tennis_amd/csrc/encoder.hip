@@ -681,7 +681,7 @@ extern "C" size_t tn_densenet121_workspace_bytes(const tn_encoder *enc) { return
 // sub-batch is just a pointer offset; weights are shared read-only.  Which kernel runs which dense layers is the plan's
 // decision (encoder_plan.h::enc_block_plan); this function fills the launch arguments of the steps it is given.
 static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, int b0, int B, float *feat0,
-                             hipStream_t s, EventTimer &tm, int ws0 = -1) {
+                             hipStream_t s, EventTimer &tm, int ws0 = -1, bool shared_chip = false) {
   int rc;
   const EncGeom &g = e->geom;
   const EncPolicy &p = e->policy;
@@ -707,7 +707,7 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
     return rc2;
   };
   std::vector<EncStep> plan[4];
-  for (int b = 0; b < 4; ++b) plan[b] = enc_block_plan(p, g, b, B, cal);
+  for (int b = 0; b < 4; ++b) plan[b] = enc_block_plan(p, g, b, B, cal, shared_chip);
   // the head reads the last block un-rounded when the kernels that produce it write the fp32 side copy: the LDS-resident 7x7
   // block kernel and the transition in front of it
   float *h32 = plan[3][0].route == ENC_BLOCK7 ? e->head32 + (size_t)w0 * g.Hb[3] * g.Wb[3] * g.Cb[3] : nullptr;
@@ -770,12 +770,12 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
         }
         case ENC_STRIP_CHAIN: {
           DenseStripChainArgs ac{bbuf[b], g.Cb[b], g.Cin[b], st.nl, e->strip_chain_dev[b], B, Hh, Ww};
-          rc = launch_dense_strip_chain(ac, s);
+          rc = st.paired ? launch_dense_strip_pair_chain(ac, s) : launch_dense_strip_chain(ac, s);
           break;
         }
         case ENC_STRIP: {
           DenseStripArgs as{bbuf[b], g.Cb[b], L.cin, L.s1, L.t1, L.w1s, L.w3s, B, Hh, Ww};
-          rc = launch_dense_strip(as, s);
+          rc = st.paired ? launch_dense_strip_pair(as, s) : launch_dense_strip(as, s);
           break;
         }
         default: {      // ENC_LAYERWISE
@@ -859,7 +859,8 @@ static int encoder_run(tn_encoder *e, const void *x, tn_layout layout, int B, fl
         for (int g = 0; g < e->split_of[p2]; ++g) TN_HIP_CHECK(hipStreamWaitEvent(e->side[par], e->ev_done[p2][g], 0));
     e->last_interleaved = true;
     e->last_ws0 = par * e->maxB;
-    const int r = encoder_run_range(e, x, layout, 0, B, feat, e->side[par], tm, par * e->maxB);
+    // (the one place whose kernels share the chip with the other stream's call: the paired 28x28 strip launches, encoder_plan.h)
+    const int r = encoder_run_range(e, x, layout, 0, B, feat, e->side[par], tm, par * e->maxB, true);
     TN_HIP_CHECK(hipEventRecord(e->ev_done[par][0], e->side[par]));
     e->split_of[par] = 1;
     e->split_batch = 0;

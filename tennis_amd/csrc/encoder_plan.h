@@ -7,6 +7,8 @@
 //   streamed 14x14 / 28x28 block > LDS-resident 7x7 block > chained tile-kernel block >
 //   (chained strip launch for the leading layers, then per layer: strip > fused tile kernel > layer-wise 1x1 + 3x3;
 //    28x28 at 128 frames or more: the tile-kernel layers behind the strip layers as one chained tile-kernel launch)
+// A 28x28 strip step (chained or per layer) of a call that shares the chip with the neighbouring stream's call takes the paired launch
+// geometry (EncStep::paired): the same route, family, flops and bytes - the same arithmetic, two frames per workgroup.
 #pragma once
 #include <cstdlib>
 #include <string>
@@ -27,6 +29,10 @@ struct EncPolicy {
   bool strip = true;           // 56x56 / 28x28 layers with K <= 320 run on the strip-streaming kernel (TN_NO_STRIP disables)
   bool strip_chain = true;     // the leading strip layers of a 56x56 / 28x28 block run in one launch (TN_NO_STRIP_CHAIN: one launch per layer)
   int strip_min_batch = 64;    // ... from this many frames per launch on (one workgroup per frame: small batches leave CUs idle)
+  bool strip_pair = true;      // the 28x28 strip launches of a call that shares the chip with the neighbouring stream's take two frames per
+                               // workgroup, 14 rows per wave (dense_strip_pair_w28.hip; TN_NO_STRIP_PAIR disables)
+  int strip_pair_min_batch = 256;  // ... from this many frames per call on (B / 2 workgroups: the neighbour's launch has to take the other half
+                                   // of the CUs) and for an even batch (TN_STRIP_PAIR_MIN_BATCH)
   bool block7 = true;          // a 7x7 block runs on the LDS-resident kernel of dense_block7.hip (TN_NO_BLOCK7 disables)
   // the streamed block kernels (kDenseStreamKernels, common.h): [0] a 14x14 block on dense_block14.hip (TN_NO_BLOCK14 disables),
   // [1] a 28x28 block on dense_block28.hip (TN_BLOCK28=1 enables: measured, not the default)
@@ -48,6 +54,8 @@ inline EncPolicy enc_policy(int flags) {
   p.chain28 = p.chain && getenv("TN_NO_CHAIN28") == nullptr;
   if (getenv("TN_CHAIN28_MIN_BATCH")) p.chain28_min_batch = atoi(getenv("TN_CHAIN28_MIN_BATCH"));
   if (getenv("TN_STRIP_MIN_BATCH")) p.strip_min_batch = atoi(getenv("TN_STRIP_MIN_BATCH"));
+  p.strip_pair = getenv("TN_NO_STRIP_PAIR") == nullptr;
+  if (getenv("TN_STRIP_PAIR_MIN_BATCH")) p.strip_pair_min_batch = atoi(getenv("TN_STRIP_PAIR_MIN_BATCH"));
   p.block7 = getenv("TN_NO_BLOCK7") == nullptr;
   p.block_stream[0] = getenv("TN_NO_BLOCK14") == nullptr;
   p.block_stream[1] = getenv("TN_BLOCK28") != nullptr && atoi(getenv("TN_BLOCK28")) != 0;
@@ -151,16 +159,28 @@ inline constexpr EncRouteName kEncRouteNames[] = {
 static_assert(sizeof(kEncRouteNames) / sizeof(kEncRouteNames[0]) == ENC_NROUTES && ENC_STREAM14 == 0 && ENC_STREAM28 == 1,
               "kEncRouteNames is indexed by EncRoute, whose first two values index kDenseStreamKernels");
 
-struct EncStep { EncRoute route; int l0, nl; };      // layers [l0, l0 + nl) of the block in one launch (layer-wise: two)
+// layers [l0, l0 + nl) of the block in one launch (layer-wise: two).  paired: a 28x28 strip step in the two-frames-per-workgroup
+// launch geometry (enc_strip_pair)
+struct EncStep { EncRoute route; int l0, nl; bool paired = false; };
 
 inline std::string family_name(const EncStep &st, const EncGeom &g, int b) {
   const EncRouteName &n = kEncRouteNames[st.route];
   return n.geo ? n.name + std::to_string(g.Hb[b]) + "x" + std::to_string(g.Wb[b]) : std::string(n.name);
 }
 
+// The 28x28 strip steps of the block take the paired launch: only where the call's kernels share the chip with a neighbouring
+// stream's (shared_chip: a launch of B / 2 workgroups fills half of the CUs and the neighbour's takes the rest; anywhere else those
+// CUs would stand idle), from strip_pair_min_batch frames on, for an even batch (a workgroup takes two frames), and under the
+// conditions the strip routes carry themselves: the default fp16 kernels, no tuning variant, not calibrating.
+inline bool enc_strip_pair(const EncPolicy &p, const EncGeom &g, int b, int B, bool cal, bool shared_chip) {
+  return shared_chip && p.strip_pair && p.strip && !p.exact && p.dl_variant == 0 && !cal && g.Hb[b] == 28 && g.Wb[b] == 28 &&
+         B >= p.strip_pair_min_batch && B % 2 == 0;
+}
+
 // The launches of block b for a batch of B frames, in order.  cal: the calibration pass (tn_densenet121_input_means), layer-wise
-// whatever the switches.  A tuning variant (TN_DL_VARIANT) keeps the block on the tile kernels it tunes.
-inline std::vector<EncStep> enc_block_plan(const EncPolicy &p, const EncGeom &g, int b, int B, bool cal) {
+// whatever the switches.  A tuning variant (TN_DL_VARIANT) keeps the block on the tile kernels it tunes.  shared_chip: the call runs
+// beside the neighbouring stream's call (encoder_run's interleaved whole-batch branch and nowhere else).
+inline std::vector<EncStep> enc_block_plan(const EncPolicy &p, const EncGeom &g, int b, int B, bool cal, bool shared_chip) {
   const int n = kBlockCfg[b], Hh = g.Hb[b];
   std::vector<EncStep> plan;
   if (cal) {
@@ -168,13 +188,14 @@ inline std::vector<EncStep> enc_block_plan(const EncPolicy &p, const EncGeom &g,
     return plan;
   }
   const bool tuned = p.dl_variant != 0;
+  const bool paired = enc_strip_pair(p, g, b, B, cal, shared_chip);
   if (const DenseStreamKernel *sk = tuned ? nullptr : enc_stream_kernel(p, g, b)) return {{(EncRoute)(sk - kDenseStreamKernels), 0, n}};
   if (!tuned && enc_block7(p, g, b)) return {{ENC_BLOCK7, 0, n}};
   if (enc_block_chained_tile(p, g, b)) return {{ENC_CHAIN_TILE, 0, n}};
   // where the per-layer strip route would be taken for the block's leading layers: those layers in one launch (one workgroup
   // per frame walks them; no drain of the chip, no dispatch and no cold start per layer).  The rest follows layer by layer.
   int l = !tuned && B >= p.strip_min_batch ? enc_strip_chain_layers(p, g, b) : 0;
-  if (l > 0) plan.push_back({ENC_STRIP_CHAIN, 0, l});
+  if (l > 0) plan.push_back({ENC_STRIP_CHAIN, 0, l, paired});
   // (one workgroup per 56 x 56 / 28 x 28 frame, 5 / 3 per 128 x 128 / 64 x 64 frame: enough of them to fill the chip?)
   const bool strip_fills = B * (Hh == 128 ? 5 : Hh == 64 ? 3 : 1) >= p.strip_min_batch;
   for (; l < n; ++l) {
@@ -185,7 +206,7 @@ inline std::vector<EncStep> enc_block_plan(const EncPolicy &p, const EncGeom &g,
       plan.push_back({ENC_CHAIN_TILE, l, n - l});
       break;
     }
-    plan.push_back({r, l, 1});
+    plan.push_back({r, l, 1, r == ENC_STRIP && paired});
   }
   return plan;
 }
