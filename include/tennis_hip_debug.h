@@ -74,6 +74,14 @@ int tn_dbg_conv3x3_dev(tn_ctx *ctx, const void *x_f16, const float *scale, const
 int tn_dbg_conv1x1_ex(tn_ctx *ctx, const void *x_f16, int ldx, int K, const float *scale, const float *shift, const void *w_f16, int N,
                       void *y_f16, int ldy, int yoff, int M, int pool, int H, int W, int variant, const float *bias, int clamp,
                       float *y32, int ld32, const void *wfrag);
+/* The warp-specialised transition with the head folded into its epilogue (csrc/trans_ws.hip): tn_dbg_conv1x1_ex's pooling form with
+ * wfrag, plus feat (device fp32, row pitch ldfeat >= N) and head_s / head_t (device fp32 [N], 16-byte aligned).  Frame f's row of feat
+ * receives in columns [0, N) the mean over the frame's 49 pooled pixels of relu(head_s[n] * result + head_t[n]), the un-rounded
+ * results summed in pixel order as the head kernel sums them; y32 is not written.  Refused before any launch: N other than 512, a
+ * map other than 14 x 14 (the frame has to be one tile).  Asynchronous. */
+int tn_dbg_conv1x1_head(tn_ctx *ctx, const void *x_f16, int ldx, int K, const float *scale, const float *shift, const void *w_f16, int N,
+                        void *y_f16, int ldy, int yoff, int M, int pool, int H, int W, float *y32, int ld32, const void *wfrag,
+                        float *feat, const float *head_s, const float *head_t, int ldfeat);
 /* w [N][K] fp16 -> the fragment image the warp-specialised transition reads, [K / 16][N / 32][64 lanes][8] (lane l: row l & 31,
  * k offset 8 (l >> 5)): the host function tn_densenet121_create packs with (touches no device), and the device kernel. */
 int tn_dbg_pack_trans_frags(const uint16_t *w_f16_host, int N, int K, uint16_t *out_host);
@@ -131,6 +139,13 @@ int tn_dbg_dense_strip_pair_chain_dev(tn_ctx *ctx, void *buf_f16, int ldc, int K
 /* *count: how many launches of the process took the paired 28x28 strip kernels so far.  The instrumented pass never takes that
  * route (it does not share the chip with a neighbouring call), so this count is how a test sees it. */
 int tn_dbg_strip_pair_launches(int64_t *count);
+/* *count: how many launches of the process ran with the head folded in so far (the last transition and the 7x7 block kernel: two
+ * per frame range of a forward on that route).  A profile cannot show the route; this count does. */
+int tn_dbg_head_fused_launches(int64_t *count);
+/* *fused: 1 where a forward of that input size, create flags (and TN_* environment), batch and pass folds the head into the last
+ * transition and the 7x7 block kernel (csrc/encoder_plan.h::enc_head_fused), 0 where it keeps the fp32 side copy and the head launch.
+ * class_maps: the call is tn_densenet121_forward_class_maps.  Touches no device. */
+int tn_dbg_head_fused(int height, int width, int flags, int batch, int calibrate, int class_maps, int *fused);
 
 /* The LDS-resident 7x7 dense block (csrc/dense_block7.hip): nl layers from K0 input channels in ONE launch on a device
  * concat buffer (B,7,7,ldc) fp16.  w1_all: the (128, K_l) 1x1 weights one after the other (K_l = K0 + 32 l); s1_all / t1_all
@@ -140,6 +155,12 @@ int tn_dbg_block7_create(tn_ctx *ctx, int K0, int nl, const float *w1_all, const
 int tn_dbg_block7_run(void *handle, void *buf_f16, int ldc, int B);
 int tn_dbg_block7_run_ts(void *handle, void *buf_f16, int ldc, int B,
                          unsigned long long *ts /* NULL or 128 per frame: s_memtime stamps of wave 0 (start, then 5 per layer) */);
+/* ... with the un-rounded fp32 side copy of the appended channels (side: device fp32 (B,7,7,ldc), or NULL), or with the head folded
+ * into the append (feat: device fp32, row pitch ldfeat >= K0 + 32 nl; head_s / head_t: device fp32 indexed by the concat buffer's
+ * channel, 16-byte aligned): frame f's row of feat receives in columns [K0, K0 + 32 nl) the mean over the 49 pixels of
+ * relu(head_s[c] * result + head_t[c]); side is then not written. */
+int tn_dbg_block7_run_head(void *handle, void *buf_f16, int ldc, int B, float *side, float *feat, const float *head_s, const float *head_t,
+                           int ldfeat, unsigned long long *ts);
 void tn_dbg_block7_destroy(void *handle);
 
 /* The streamed 14x14 dense block (csrc/dense_block14.hip; reference call site models/vision/definitions.py:30, the third dense

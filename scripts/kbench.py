@@ -21,6 +21,8 @@ ap.add_argument("--stamps", action="store_true")
 ap.add_argument("--pair", action="store_true", help="ds: the 28x28 layers in the paired launch geometry (two frames per workgroup, dense_strip_pair_w28.hip)")
 ap.add_argument("--ws", action="store_true", help="tr: the last transition on trans_ws.hip")
 ap.add_argument("--b7stamps", type=int, default=5)
+ap.add_argument("--head", default="", choices=["", "side", "fused"], help="tr --ws (the last transition only) and b7 as the forward runs them: "
+                "'side' with the fp32 side copy for the head kernel, 'fused' with the head folded in (the features written by the kernel)")
 args = ap.parse_args()
 if args.lib: _lib.LIB_PATH = os.path.abspath(args.lib)
 ctx = _lib.default_context(0)
@@ -89,9 +91,22 @@ for v in [int(s) for s in args.variants.split(",")]:
             sc = torch.rand(K, device="cuda") + 0.5; sh = torch.randn(K, device="cuda") * 0.3
             fn = lambda: _lib.check(lib.tn_dbg_conv1x1_dev(ctx.handle, _lib.ptr(x), K, K, _lib.ptr(sc), _lib.ptr(sh),
                                                            _lib.ptr(wd), N, _lib.ptr(y), N, 0, Mo, 1, hw, hw, v | ((1 << 18) if (args.ws and N in (256, 512)) else 0)))
+            if args.head and args.ws and N == 512 and hw == 14:      # as the forward launches it: ldy = 1024, and the side copy or the features
+                y = torch.zeros((Mo, 1024), device="cuda", dtype=torch.float16)
+                frag = torch.empty((N * K,), device="cuda", dtype=torch.float16)
+                _lib.check(lib.tn_dbg_pack_trans_frags_dev(ctx.handle, _lib.ptr(wd), N, K, _lib.ptr(frag)))
+                y32 = torch.zeros((Mo, 1024), device="cuda", dtype=torch.float32)
+                feat = torch.zeros((B, 1024), device="cuda", dtype=torch.float32)
+                hs = torch.rand(1024, device="cuda") + 0.5; ht = torch.randn(1024, device="cuda") * 0.3
+                if args.head == "side":
+                    fn = lambda: _lib.check(lib.tn_dbg_conv1x1_ex(ctx.handle, _lib.ptr(x), K, K, _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(wd), N, _lib.ptr(y), 1024, 0,
+                                                                  Mo, 1, hw, hw, 0, None, 0, _lib.ptr(y32), 1024, _lib.ptr(frag)))
+                else:
+                    fn = lambda: _lib.check(lib.tn_dbg_conv1x1_head(ctx.handle, _lib.ptr(x), K, K, _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(wd), N, _lib.ptr(y), 1024, 0,
+                                                                    Mo, 1, hw, hw, None, 0, _lib.ptr(frag), _lib.ptr(feat), _lib.ptr(hs), _lib.ptr(ht), 1024))
             us = timed(fn, args.iters)
             by = M * K * 2 + Mo * N * 2
-            res.append(dict(k="tr", v=v, hw=hw, K=K, us=round(us, 1), tf=round(2.0 * M * N * K / us / 1e6, 1), tbs=round(by / us / 1e6, 2)))
+            res.append(dict(k="tr", v=v, hw=hw, K=K, head=args.head if (args.head and args.ws and N == 512 and hw == 14) else "", us=round(us, 1), tf=round(2.0 * M * N * K / us / 1e6, 1), tbs=round(by / us / 1e6, 2)))
             print(res[-1], flush=True)
             del x, y
     if "dl" in args.kernels:
@@ -199,11 +214,19 @@ for v in [int(s) for s in args.variants.split(",")]:
         _lib.check(lib.tn_dbg_block7_create(ctx.handle, K0, nl, vp(w1), vp(s1), vp(t1), vp(s2), vp(t2), vp(w3), C.byref(h)))
         buf = torch.randn((B * 49, 1024), device="cuda", dtype=torch.float16)
         fn = lambda: _lib.check(lib.tn_dbg_block7_run(h, _lib.ptr(buf), 1024, B))
+        run_ts = lambda ts_: lib.tn_dbg_block7_run_ts(h, _lib.ptr(buf), 1024, B, _lib.ptr(ts_))
+        if args.head:
+            side = torch.zeros((B * 49, 1024), device="cuda", dtype=torch.float32) if args.head == "side" else None
+            feat = torch.zeros((B, 1024), device="cuda", dtype=torch.float32) if args.head == "fused" else None
+            hs = torch.rand(1024, device="cuda") + 0.5; ht = torch.randn(1024, device="cuda") * 0.3
+            hp = (_lib.ptr(hs), _lib.ptr(ht)) if feat is not None else (None, None)
+            run_ts = lambda ts_: lib.tn_dbg_block7_run_head(h, _lib.ptr(buf), 1024, B, _lib.ptr(side), _lib.ptr(feat), hp[0], hp[1], 1024, _lib.ptr(ts_))
+            fn = lambda: _lib.check(run_ts(None))
         us = timed(fn, args.iters)
         fl = sum(2.0 * B * 49 * (128 * K + 32 * 1152) for K in Ks)
         if args.stamps:
             ts = torch.zeros((B * 128,), dtype=torch.int64, device="cuda")
-            _lib.check(lib.tn_dbg_block7_run_ts(h, _lib.ptr(buf), 1024, B, _lib.ptr(ts)))
+            _lib.check(run_ts(ts))
             torch.cuda.synchronize()
             t = ts.cpu().numpy().astype(np.float64).reshape(B, 128)
             real_us = (t[:, 126] - t[:, 127]) / 100.0
@@ -215,7 +238,7 @@ for v in [int(s) for s in args.variants.split(",")]:
             print("   per layer (ticks): 1x1 | reduce | epilogue | 3x3 | append")
             for l in range(nl): print("   l%2d K=%4d  %s  sum %d" % (l, Ks[l], np.round(med[l]).astype(int), med[l].sum()))
             print("   totals %s = %d" % (np.round(med.sum(axis=0)).astype(int), med.sum()), flush=True)
-        res.append(dict(k="b7", us=round(us, 1), tf=round(fl / us / 1e6, 1)))
+        res.append(dict(k="b7", head=args.head, us=round(us, 1), tf=round(fl / us / 1e6, 1)))
         print(res[-1], flush=True)
         lib.tn_dbg_block7_destroy(h)
     if "b14" in args.kernels:     # the streamed 14x14 dense block (dense_block14.hip) next to the chained tile kernel (dl14)

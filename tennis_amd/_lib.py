@@ -200,6 +200,8 @@ _SIGS = {
     "tn_dbg_conv3x3_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_conv1x1_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P]),
+    "tn_dbg_conv1x1_head": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int]),
     "tn_dbg_pack_trans_frags": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "tn_dbg_pack_trans_frags_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "tn_dbg_dense_layer_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int,
@@ -243,6 +245,8 @@ _SIGS = {
     "tn_dbg_dense_strip_pair_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "tn_dbg_dense_strip_pair_chain_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_strip_pair_launches": (C.c_int, [C.POINTER(C.c_int64)]),
+    "tn_dbg_head_fused_launches": (C.c_int, [C.POINTER(C.c_int64)]),
+    "tn_dbg_head_fused": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "tn_densenet121_input_means": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "tn_npy_writer_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "tn_npy_writer_submit": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_int]),
@@ -254,6 +258,7 @@ _SIGS = {
     "tn_dbg_block7_create": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_void_p)]),
     "tn_dbg_block7_run": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "tn_dbg_block7_run_ts": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "tn_dbg_block7_run_head": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "tn_dbg_block7_destroy": (None, [_P]),
     "tn_dbg_block14_create": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_void_p)]),
     "tn_dbg_block14_run": (C.c_int, [_P, _P, C.c_int, C.c_int]),

@@ -155,6 +155,12 @@ struct Conv1x1Args {
   float *y32 = nullptr;   // [M][ld32] fp32: the result once more, un-rounded (the last transition: what the head reads), columns [0, N)
   int ld32 = 0;
   const f16 *wfrag = nullptr;   // w once more in MFMA operand order (pack_trans_frags): enables the warp-specialised kernel of trans_ws.hip
+  // The head folded into the last transition (trans_ws.hip, the 64 x 512 tile of a 14 x 14 -> 7 x 7 frame only): with feat set the
+  // workgroup writes feat[frame * ldfeat + n] = mean over the frame's 49 pooled pixels of relu(head_s[n] * result + head_t[n]),
+  // n in [0, N), summed in pixel order as head_kernel sums them, and leaves y32 alone
+  float *feat = nullptr;
+  const float *head_s = nullptr, *head_t = nullptr;   // [N] the head's folded BatchNorm, channels [0, N) of the last block
+  int ldfeat = 0;
 };
 int launch_conv1x1(const Conv1x1Args &a, hipStream_t s);
 // trans_ws.hip: the last transition (N = 512, one frame of <= 64 pooled pixels per workgroup)
@@ -235,6 +241,8 @@ int launch_dense_strip_chain(const DenseStripChainArgs &a, hipStream_t s);
 int launch_dense_strip_pair(const DenseStripArgs &a, hipStream_t s);
 int launch_dense_strip_pair_chain(const DenseStripChainArgs &a, hipStream_t s);
 long strip_pair_launches();      // paired launches of the process so far (what tn_dbg_strip_pair_launches reports)
+long head_fused_launches();      // launches with the head folded in (trans_ws.hip, dense_block7.hip) so far (tn_dbg_head_fused_launches)
+void head_fused_launched();
 std::vector<f16> pack_w1_strip(const float *w /*[128][K], BN2 scale folded in*/, int K, const float *shift /*[128] BN2 shift*/);
 std::vector<f16> pack_w3_strip(const float *w /*(32,128,3,3)*/);
 
@@ -247,6 +255,11 @@ struct DenseBlock7Args {
   unsigned a_off[4], b_off[4];   // start of each wave's streams, in 16-byte units
   unsigned long long *ts = nullptr;
   float *side = nullptr;         // [B][49][ldc] fp32: the appended channels once more, un-rounded, for the head
+  // The head folded into the append (side is then not written): feat[frame * ldfeat + c] = mean over the 49 pixels of
+  // relu(head_s[c] * result + head_t[c]) for the appended channels c in [K0, K0 + 32 nl), summed in pixel order as head_kernel does
+  float *feat = nullptr;
+  const float *head_s = nullptr, *head_t = nullptr;   // indexed by the channel of the concat buffer
+  int ldfeat = 0;
 };
 struct Block7Layer { const float *w1f /*[128][K], BN2 scale folded in*/, *w3 /*(32,128,3,3)*/, *s1, *t1 /*[K]*/, *t2 /*[128]*/; };
 struct Block7Image {

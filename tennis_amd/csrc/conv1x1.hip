@@ -261,6 +261,7 @@ int launch_conv1x1(const Conv1x1Args &a, hipStream_t s) {
   const dim3 block(256);
   static const bool no_ws = getenv("TN_NO_TRANS_WS") != nullptr;      // A/B runs
   if (a.wfrag && !no_ws && trans_ws_supported(a)) return launch_trans_ws(a, s);
+  TN_REQUIRE(!a.feat, "conv1x1: the head epilogue (feat) exists in the warp-specialised transition kernel only (wfrag, a geometry trans_ws supports, no TN_NO_TRANS_WS)");
   if (a.pool) {
     static const bool narrow = getenv("TN_TRANS_NARROW") != nullptr;   // A/B runs: 128-channel tiles everywhere
     const bool wide = a.N % 256 == 0 && !narrow;

@@ -86,6 +86,27 @@ extern "C" int tn_dbg_conv1x1_ex(tn_ctx *ctx, const void *x_f16, int ldx, int K,
   return launch_conv1x1(a, ctx->stream);
 }
 
+// tn_dbg_conv1x1_ex with the head epilogue of the warp-specialised transition (trans_ws.hip, round 10): feat (device fp32, row pitch
+// ldfeat) receives, per frame, the mean over the frame's pooled pixels of relu(head_s[n] * result + head_t[n]) for n in [0, N);
+// head_s / head_t device fp32 [N].  y32 has to be NULL or is left untouched.  The launcher refuses what the epilogue does not
+// cover (anything but wfrag, N = 512 and a 14 x 14 map), before any launch.  Asynchronous.
+extern "C" int tn_dbg_conv1x1_head(tn_ctx *ctx, const void *x_f16, int ldx, int K, const float *scale, const float *shift, const void *w_f16,
+                                   int N, void *y_f16, int ldy, int yoff, int M, int pool, int H, int W, float *y32, int ld32, const void *wfrag,
+                                   float *feat, const float *head_s, const float *head_t, int ldfeat) {
+  TN_REQUIRE(ctx && x_f16 && y_f16 && scale && shift && w_f16 && wfrag && feat && head_s && head_t, "tn_dbg_conv1x1_head: null argument");
+  TN_REQUIRE(M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= yoff + N && yoff >= 0 && ldfeat >= N, "tn_dbg_conv1x1_head: bad shape (M, K, N positive, ldx >= K, ldy >= yoff + N, ldfeat >= N)");
+  TN_REQUIRE(pool && H >= 2 && W >= 2 && M % ((H / 2) * (W / 2)) == 0, "tn_dbg_conv1x1_head: a pooling transition with M = B (H / 2) (W / 2)");
+  TN_REQUIRE(!y32 || (ld32 >= N && ld32 % 4 == 0 && ((uintptr_t)y32 & 15) == 0), "tn_dbg_conv1x1_head: y32 needs ld32 >= N, a multiple of 4, and 16-byte alignment");
+  Conv1x1Args a{(const f16 *)x_f16, ldx, K, scale, shift, (const f16 *)w_f16, N, (f16 *)y_f16, ldy, yoff, M, pool, H, W};
+  a.y32 = y32;
+  a.ld32 = ld32;
+  a.wfrag = (const f16 *)wfrag;
+  a.feat = feat; a.head_s = head_s; a.head_t = head_t; a.ldfeat = ldfeat;
+  TN_REQUIRE(trans_ws_supported(a), "tn_dbg_conv1x1_head: a geometry trans_ws does not support (N = 512 | 256, K % 128 == 0, even H and W)");
+  TN_ON_DEVICE(ctx->device);
+  return launch_conv1x1(a, ctx->stream);
+}
+
 // The two forms of the warp-specialised transition's weight packer: the host function tn_densenet121_create calls (no device is
 // touched) and the device kernel; w [N][K] fp16 -> [K / 16][N / 32][64 lanes][8], N K halves
 extern "C" int tn_dbg_pack_trans_frags(const uint16_t *w_f16_host, int N, int K, uint16_t *out_host) {
@@ -427,6 +448,22 @@ extern "C" int tn_dbg_block7_run_ts(void *handle, void *buf_f16, int ldc, int B,
   return launch_dense_block7(a, b->ctx->stream);
 }
 
+// tn_dbg_block7_run with the fp32 side copy (side: device fp32 [B][49][ldc], or NULL) or with the head folded into the append (round
+// 10; feat: device fp32 with row pitch ldfeat, head_s / head_t: device fp32 indexed by the concat buffer's channel; or all NULL).
+// ts as tn_dbg_block7_run_ts.  Asynchronous.
+extern "C" int tn_dbg_block7_run_head(void *handle, void *buf_f16, int ldc, int B, float *side, float *feat, const float *head_s,
+                                      const float *head_t, int ldfeat, unsigned long long *ts) {
+  tn_dbg_block7 *b = (tn_dbg_block7 *)handle;
+  TN_REQUIRE(b && buf_f16, "tn_dbg_block7_run_head: null argument");
+  TN_REQUIRE(((uintptr_t)side & 15) == 0, "tn_dbg_block7_run_head: side must be 16-byte aligned");
+  TN_ON_DEVICE(b->ctx->device);
+  DenseBlock7Args a = b->args;
+  a.buf = (f16 *)buf_f16; a.ldc = ldc; a.B = B; a.ts = ts;
+  a.side = side;
+  a.feat = feat; a.head_s = head_s; a.head_t = head_t; a.ldfeat = ldfeat;
+  return launch_dense_block7(a, b->ctx->stream);
+}
+
 extern "C" void tn_dbg_block7_destroy(void *handle) {
   tn_dbg_block7 *b = (tn_dbg_block7 *)handle;
   if (!b) return;
@@ -716,6 +753,29 @@ extern "C" int tn_dbg_encoder_plan_shared(int height, int width, int flags, int 
 extern "C" int tn_dbg_strip_pair_launches(int64_t *count) {
   TN_REQUIRE(count, "tn_dbg_strip_pair_launches: null argument");
   *count = (int64_t)strip_pair_launches();
+  return TN_OK;
+}
+
+// launches with the head folded in so far in this process: one per frame range from the last transition, one from the 7x7 block
+extern "C" int tn_dbg_head_fused_launches(int64_t *count) {
+  TN_REQUIRE(count, "tn_dbg_head_fused_launches: null argument");
+  *count = (int64_t)head_fused_launches();
+  return TN_OK;
+}
+
+// encoder_plan.h::enc_head_fused for an input size, create flags (and the TN_* environment of the call), batch, pass and entry point:
+// *fused = 1 where a forward takes the route, 0 where it keeps the side copy and the head launch (the fp32 / fp32x3 modes: always 0).
+// Host arithmetic only; the instrumented pass never takes the route and is not asked about.
+extern "C" int tn_dbg_head_fused(int height, int width, int flags, int batch, int calibrate, int class_maps, int *fused) {
+  TN_REQUIRE(fused, "tn_dbg_head_fused: null argument");
+  TN_REQUIRE((flags & ~(TN_ENC_EXACT_WEIGHTS | TN_ENC_FP32 | TN_ENC_FP32X3)) == 0, "tn_dbg_head_fused: unknown flag");
+  TN_REQUIRE(batch > 0, "tn_dbg_head_fused: batch must be positive");
+  TN_REQUIRE(height >= 224 && width >= 224 && height <= 1024 && width <= 1024, "tn_dbg_head_fused: input size must be in [224,1024]");
+  const EncPolicy p = enc_policy(flags);
+  const EncGeom g = enc_geom(height, width);
+  if (const char *why = enc_refusal(p, g)) { tn_set_error(why); return TN_ERR_INVALID; }
+  const bool fp32 = (flags & (TN_ENC_FP32 | TN_ENC_FP32X3)) != 0;
+  *fused = !fp32 && enc_head_fused(p, g, calibrate != 0, class_maps != 0, false) ? 1 : 0;
   return TN_OK;
 }
 

@@ -27,7 +27,12 @@
 //   padding).  The 3x3 convolution splits its K = 9 x 128 over the waves by bottleneck channel: wave w convolves exactly
 //   the 32 channels it produced - no barrier between the two GEMMs - and the four 32 x 64 partial outputs are reduced through
 //   the same LDS buffer.
+// * the head (BatchNorm + ReLU + 7 x 7 average of the block's output, pool.hip::head_kernel) wants the appended channels UN-rounded.
+//   Either the append stores them once more in fp32 to a side buffer for head_kernel (DenseBlock7Args::side, round 5), or - HEAD,
+//   round 10, DenseBlock7Args::feat - the kernel applies the head itself, layer by layer, and writes the features.  See the kernel.
+#include <cstdint>
 #include <cstring>
+#include <string>
 #include <type_traits>
 #include <utility>
 
@@ -61,6 +66,10 @@ constexpr int kTabOff = kRedOff + kRedBytes;
 constexpr int kTabFloats = 512 + 512 + 128;          // lo1[1024] | hi1[1024] as fp16 (BN1 + ReLU as a clamp: calib_host.hip) | t2[128] fp32 of one layer
 constexpr int kLdsBytes = kTabOff + kTabFloats * 4;
 static_assert(kLdsBytes <= 160 * 1024, "LDS");
+// HEAD: the head's terms of a layer's 32 new channels, [channel][pixel] fp32 (a row = 49 pixels + 3 of padding: 16-byte reads)
+constexpr int kHeadOff = kLdsBytes, kHeadPitch = 52 * 4;
+constexpr int kLdsBytesHead = kHeadOff + 32 * kHeadPitch;
+static_assert(kHeadOff % 16 == 0 && kLdsBytesHead <= 160 * 1024, "LDS");
 constexpr int kStepUnits = 256;                      // a k-step of the 1x1 stream: 4 fragments x 64 lanes, in 16-byte units
 constexpr int kW3Units = 18 * 64;                    // a wave's 3x3 fragments of one layer
 
@@ -68,7 +77,12 @@ __device__ __forceinline__ f32x16 mfma32(const f16x8 a, const f16x8 b, const f32
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
-template <int D>
+// HEAD (round 10): the head's BatchNorm + ReLU + 7 x 7 average of the appended channels folded into the append, instead of the fp32
+// side copy for head_kernel.  The lane that holds eight un-rounded channels of a pixel puts relu(head_s * v + head_t) of them into
+// a [32 channels][49 pixels] fp32 scratch; behind the layer's closing barrier lane c of wave 3 (the wave with the fewest k-steps
+// whenever the waves' shares differ) adds channel c's 49 terms in pixel order into one fp32 accumulator and scales by 1 / 49:
+// head_kernel's operations in head_kernel's order, the same bits.  The scratch is next written six barriers later.
+template <int D, bool HEAD = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) dense_block7_kernel(DenseBlock7Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
@@ -291,6 +305,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
 
     stamp();
+    f32x4 hsc[2], hsh[2];      // HEAD: the head's scale / shift of the eight channels this lane appends (requested here, they land during the 3x3)
+    if constexpr (HEAD) {
+      const int c0 = K + 16 * (w >> 1) + 8 * h;
+      hsc[0] = *(const f32x4 *)(a.head_s + c0); hsc[1] = *(const f32x4 *)(a.head_s + c0 + 4);
+      hsh[0] = *(const f32x4 *)(a.head_t + c0); hsh[1] = *(const f32x4 *)(a.head_t + c0 + 4);
+    }
     // ======================= 3x3 over this wave's 32 bottleneck channels (all nine taps) =======================
     f32x16 q[2];
     f16x8 bq[2][2];
@@ -342,7 +362,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         // the head (BN + ReLU + 7x7 average -> the features) reads the block's output UN-rounded from a side buffer: a feature
         // of magnitude 8 otherwise carries the fp16 rounding of its 49 stored values directly (round 5; the later layers of the
         // block go on consuming the fp16 copy: that is their MFMA operand)
-        if (a.side) {
+        if constexpr (HEAD) {
+          float *hp = (float *)(smem + kHeadOff + (unsigned)(16 * sf + 8 * h) * kHeadPitch) + p;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            hp[j * (kHeadPitch / 4)] = fmaxf(fmaf(o0[j], hsc[0][j], hsh[0][j]), 0.f);
+            hp[(4 + j) * (kHeadPitch / 4)] = fmaxf(fmaf(o1[j], hsc[1][j], hsh[1][j]), 0.f);
+          }
+        } else if (a.side) {
           float *sp = a.side + ((size_t)blockIdx.x * kPix + p) * a.ldc + K + 16 * sf + 8 * h;
           *(f32x4 *)sp = o0;
           *(f32x4 *)(sp + 4) = o1;
@@ -355,6 +382,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
       }
     }
     __syncthreads();
+    if constexpr (HEAD) {
+      if (w == 3 && lane < 32) {      // channel K + lane: one sequential chain over the pixels p = 0 .. 48
+        const unsigned row = kHeadOff + (unsigned)lane * kHeadPitch;
+        float sum = 0.f;
+#pragma unroll
+        for (int q = 0; q < 12; ++q) {
+          const f32x4 v = lds_f4(row + q * 16);
+          sum += v[0]; sum += v[1]; sum += v[2]; sum += v[3];
+        }
+        sum += *(const float *)(smem + row + 48 * 4);
+        a.feat[(size_t)blockIdx.x * a.ldfeat + K + lane] = sum * (1.0f / 49.0f);
+      }
+    }
     stamp();
   }
   if (a.ts && w == 0 && lane == 0) a.ts[(size_t)blockIdx.x * 128 + 126] = __builtin_amdgcn_s_memrealtime();
@@ -427,6 +467,15 @@ int launch_dense_block7(const DenseBlock7Args &a, hipStream_t s) {
   TN_REQUIRE(a.ldc % 8 == 0, "dense_block7: the row pitch must be a multiple of 8: " + geom);
   TN_REQUIRE(a.K0 + 32 * a.nl <= a.ldc, "dense_block7: the row pitch does not hold the last layer's output: " + geom);
   TN_REQUIRE(a.B > 0, "dense_block7: the batch must be positive: " + geom);
+  if (a.feat) {      // the head folded into the append (side is then not written)
+    TN_REQUIRE(a.head_s && a.head_t && a.ldfeat >= a.K0 + 32 * a.nl, "dense_block7: the head epilogue needs head_s, head_t and ldfeat >= K0 + 32 nl: " + geom);
+    TN_REQUIRE((((uintptr_t)a.head_s | (uintptr_t)a.head_t) & 15) == 0, "dense_block7: head_s and head_t must be 16-byte aligned: " + geom);
+    TN_SET_ATTR_ONCE_PER_DEVICE(TN_HIP_CHECK(hipFuncSetAttribute((const void *)dense_block7_kernel<kRingDepth, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesHead)));
+    hipLaunchKernelGGL((dense_block7_kernel<kRingDepth, true>), dim3(a.B), dim3(256), kLdsBytesHead, s, a);
+    TN_HIP_CHECK(hipGetLastError());
+    head_fused_launched();
+    return TN_OK;
+  }
   TN_SET_ATTR_ONCE_PER_DEVICE(TN_HIP_CHECK(hipFuncSetAttribute((const void *)dense_block7_kernel<kRingDepth>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes)));
   hipLaunchKernelGGL((dense_block7_kernel<kRingDepth>), dim3(a.B), dim3(256), kLdsBytes, s, a);
   TN_HIP_CHECK(hipGetLastError());

@@ -218,7 +218,10 @@ struct tn_encoder {
   float *head_s, *head_t;
   float *zeros128 = nullptr;   // a BatchNorm shift of zeros (un-fused dense layers: the shift was added by the 1x1)
   f16 *stem_out, *bott, *blockbuf[4];
-  float *head32 = nullptr;     // the last block's map once more in fp32 (what the head reads): written by the last transition and the 7x7 block kernel
+  // the last block's map once more in fp32, written by the last transition and the 7x7 block kernel: what the head and the class
+  // activation maps read where those two kernels do not apply the head themselves (encoder_plan.h::enc_head_fused - then nothing
+  // writes or reads it: the instrumented pass, tn_densenet121_forward_class_maps and TN_NO_HEAD_FUSE are its users)
+  float *head32 = nullptr;
   // tn_densenet121_forward_class_maps: set for the duration of that call only.  Every range of the call launches class_maps_kernel
   // behind its head, on the map that head read, and writes the maps of its frames at their offset in cam_out.
   const float *cam_w = nullptr;   // the Dense weight (cam_units, feat_dim), nullptr: no maps (every other entry point)
@@ -710,7 +713,9 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
   for (int b = 0; b < 4; ++b) plan[b] = enc_block_plan(p, g, b, B, cal, shared_chip);
   // the head reads the last block un-rounded when the kernels that produce it write the fp32 side copy: the LDS-resident 7x7
   // block kernel and the transition in front of it
-  float *h32 = plan[3][0].route == ENC_BLOCK7 ? e->head32 + (size_t)w0 * g.Hb[3] * g.Wb[3] * g.Cb[3] : nullptr;
+  // ... unless they apply the head themselves and write this range's features (round 10): no side copy, no head launch
+  const bool head_fused = enc_head_fused(p, g, cal, e->cam_w != nullptr, tm.on) && plan[3][0].route == ENC_BLOCK7;
+  float *h32 = !head_fused && plan[3][0].route == ENC_BLOCK7 ? e->head32 + (size_t)w0 * g.Hb[3] * g.Wb[3] * g.Cb[3] : nullptr;
   auto begin = [&](const std::string &family, const EncCost &c) { tm.begin(family.c_str(), c.flops, c.bytes); };
   {
     StemArgs a{x, (int)layout, B, g.H, g.W, e->stem_wp, e->stem_wp_zf, e->stem_scale, e->stem_shift, stem_out, g.Hs, g.Ws};
@@ -756,6 +761,7 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
           DenseBlock7Args a7 = e->b7[b];
           a7.buf = bbuf[b]; a7.B = B;
           a7.side = b == 3 ? h32 : nullptr;
+          if (b == 3 && head_fused) { a7.feat = feat; a7.head_s = e->head_s; a7.head_t = e->head_t; a7.ldfeat = g.feat_dim; }
           rc = launch_dense_block7(a7, s);
           break;
         }
@@ -808,12 +814,14 @@ static int encoder_run_range(tn_encoder *e, const void *x0, tn_layout layout, in
       at.exact = p.exact;
       at.wfrag = cal ? nullptr : T.wfrag;
       if (b == 2 && h32) { at.y32 = h32; at.ld32 = g.Cb[3]; }
+      if (b == 2 && head_fused) { at.feat = feat; at.head_s = e->head_s; at.head_t = e->head_t; at.ldfeat = g.feat_dim; }
       begin("transition_conv1x1_avgpool", transition_cost(M, Mo, T.cin, T.cout));
       rc = launch_conv1x1(at, s);
       tm.end();
       if (rc) return rc;
     }
   }
+  if (head_fused) return TN_OK;      // (the features are written; no class maps on this route)
   begin("head_bnrelu_avgpool7", head_cost(g, fB));
   rc = launch_head(bbuf[3], B, g.Hb[3], g.Wb[3], g.Cb[3], e->head_s, e->head_t, feat, g.PH, g.PW, s, h32);
   tm.end();

@@ -34,6 +34,10 @@ struct EncPolicy {
   int strip_pair_min_batch = 256;  // ... from this many frames per call on (B / 2 workgroups: the neighbour's launch has to take the other half
                                    // of the CUs) and for an even batch (TN_STRIP_PAIR_MIN_BATCH)
   bool block7 = true;          // a 7x7 block runs on the LDS-resident kernel of dense_block7.hip (TN_NO_BLOCK7 disables)
+  bool trans_ws = true;        // the last two transitions run on the warp-specialised kernel of trans_ws.hip (TN_NO_TRANS_WS disables; read
+                               // by conv1x1.hip's launcher too, which makes the choice)
+  bool head_fuse = true;       // the last transition and the 7x7 block kernel apply the head themselves and write the features: no fp32
+                               // side copy, no head launch (enc_head_fused; TN_NO_HEAD_FUSE disables)
   // the streamed block kernels (kDenseStreamKernels, common.h): [0] a 14x14 block on dense_block14.hip (TN_NO_BLOCK14 disables),
   // [1] a 28x28 block on dense_block28.hip (TN_BLOCK28=1 enables: measured, not the default)
   bool block_stream[2] = {true, false};
@@ -57,6 +61,8 @@ inline EncPolicy enc_policy(int flags) {
   p.strip_pair = getenv("TN_NO_STRIP_PAIR") == nullptr;
   if (getenv("TN_STRIP_PAIR_MIN_BATCH")) p.strip_pair_min_batch = atoi(getenv("TN_STRIP_PAIR_MIN_BATCH"));
   p.block7 = getenv("TN_NO_BLOCK7") == nullptr;
+  p.trans_ws = getenv("TN_NO_TRANS_WS") == nullptr;
+  p.head_fuse = getenv("TN_NO_HEAD_FUSE") == nullptr;
   p.block_stream[0] = getenv("TN_NO_BLOCK14") == nullptr;
   p.block_stream[1] = getenv("TN_BLOCK28") != nullptr && atoi(getenv("TN_BLOCK28")) != 0;
   p.dl_variant = getenv("TN_DL_VARIANT") ? atoi(getenv("TN_DL_VARIANT")) : 0;
@@ -175,6 +181,20 @@ inline std::string family_name(const EncStep &st, const EncGeom &g, int b) {
 inline bool enc_strip_pair(const EncPolicy &p, const EncGeom &g, int b, int B, bool cal, bool shared_chip) {
   return shared_chip && p.strip_pair && p.strip && !p.exact && p.dl_variant == 0 && !cal && g.Hb[b] == 28 && g.Wb[b] == 28 &&
          B >= p.strip_pair_min_batch && B % 2 == 0;
+}
+
+// The head folded into its two producers (round 10): the last transition (trans_ws.hip, the 64 x 512 tile whose 49 rows are the whole
+// 7 x 7 frame) writes features 0 .. 511 and the LDS-resident 7x7 block kernel features 512 .. 1023, each from the un-rounded values
+// it holds; the fp32 side copy and the head launch fall away.  Only where both producers are those kernels: block 3 on ENC_BLOCK7, the
+// transition in the warp-specialised form with N = 512 on a 14 x 14 map, one 7 x 7 pooling window; not when calibrating (layer-wise
+// kernels), not for tn_densenet121_forward_class_maps (class_maps: the maps are made from the side copy) and not in the instrumented
+// pass (timed: it reports the head family from a launch of its own).  Independent of the batch, of shared_chip and of pipelining.
+inline bool enc_head_fused(const EncPolicy &p, const EncGeom &g, bool cal, bool class_maps, bool timed) {
+  if (!p.head_fuse || cal || class_maps || timed) return false;
+  if (p.dl_variant != 0 || !enc_block7(p, g, 3)) return false;                       // (enc_block_plan: block 3 is {ENC_BLOCK7})
+  if (g.Hb[3] != 7 || g.Wb[3] != 7 || g.PH != 1 || g.PW != 1) return false;
+  // the transition: what create packs wfrag for and trans_ws_supported accepts, at N = 512 with the frame as one tile
+  return p.trans_ws && !p.exact && g.Cb[2] / 2 == 512 && g.Cb[2] % 128 == 0 && g.Hb[2] == 14 && g.Wb[2] == 14;
 }
 
 // The launches of block b for a batch of B frames, in order.  cal: the calibration pass (tn_densenet121_input_means), layer-wise

@@ -23,6 +23,13 @@
 // alone; knock-out builds of the last transition: 29 us with neither staging arithmetic nor MFMAs - the kernel's memory time, at
 // the boxes' practical read rate - so the two kinds of wave still add more than they hide.  Inside the pipelined step the gain is
 // not visible (139.8 k against 139.7 k frames/s): there a kernel costs the CU-time it occupies, and this one holds a CU alone.
+//
+// Round 10: the 64 x 512 tile of the last transition has a HEAD form (template flag; Conv1x1Args::feat).  A 7 x 7 frame is one tile, so
+// the workgroup holds everything the head (BatchNorm + ReLU + 7 x 7 average, pool.hip::head_kernel) needs of channels 0 .. 511: it
+// writes those features itself instead of the fp32 copy of its result (y32) that head_kernel would read back.  See the kernel.
+#include <atomic>
+#include <cstdint>
+#include <string>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -48,6 +55,13 @@ struct TG {
   static constexpr int NCT = NB / 4 / 32, NPT = BM / 32;      // 32-channel x 32-pixel accumulator tiles of a multiplier wave
   static_assert(NCT * NPT == 8, "128 accumulator registers");
 };
+// The head epilogue of the 64 x 512 tile (HEAD below): the fp16 output tile bounded to the frame's 49 rows, and behind it the head's terms
+// relu(head_s * result + head_t) of the same 49 rows x 512 channels in fp32 (rows 16 bytes apart in the banks, as the fp16 rows are)
+constexpr int kHeadRows = 49;
+constexpr int kHeadTermOff = kHeadRows * TG<64, 512>::CPITCH;      // 50 960
+constexpr int kHeadTermPitch = 512 * 4 + 16;
+constexpr int kHeadLdsBytes = kHeadTermOff + kHeadRows * kHeadTermPitch;      // 152 096
+static_assert(kHeadTermOff % 16 == 0 && kHeadLdsBytes <= 160 * 1024, "LDS");
 
 // workgroup barrier that orders LDS traffic only (__syncthreads() also drains the global loads in flight)
 __device__ __forceinline__ void lds_barrier() {
@@ -62,9 +76,16 @@ using ic = std::integral_constant<int, V>;
 // NK: k-tiles known at compile time (K = 1024: 16; 0 = run-time count).  hipcc's wait-count pass puts an s_waitcnt vmcnt(0) at the head
 // of a LOOP whose body carries loads across the back edge (seen in the ISA: the stagers then wait for the tile they requested a
 // moment ago, once per trip) - fully unrolled, every wait is counted exactly and the newest tile stays in flight.
-template <int NK, int BM, int NB>
+//
+// HEAD (round 10; BM = 64, NB = 512, the frame is the tile: TPF = 1, P = 49): the head's BatchNorm + ReLU + 7 x 7 average folded into the
+// epilogue.  The multipliers hold the frame's 49 x 512 un-rounded results in their accumulators; instead of storing them to y32 for
+// head_kernel they put the head's terms into LDS, and thread t of the workgroup adds channel t's 49 terms in pixel order into one fp32
+// accumulator and scales by 1 / 49 - head_kernel's operations in head_kernel's order, the same bits.  Rows nrow .. 63 of the tile
+// (repeats of the last pixel) reach neither LDS tile.
+template <int NK, int BM, int NB, bool HEAD = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void trans_ws_kernel(Conv1x1Args a, int TPF, int PT) {
   using G = TG<BM, NB>;
+  static_assert(!HEAD || (BM == 64 && NB == 512), "the head epilogue belongs to the 64 x 512 tile");
   constexpr int XT = G::XT, CPITCH = G::CPITCH, SR = G::SR, NCT = G::NCT, NPT = G::NPT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int t = threadIdx.x, lane = t & 63;
@@ -215,13 +236,31 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           f16x4 h;
 #pragma unroll
           for (int r = 0; r < 4; ++r) h[r] = (f16)acc[ct][pt][4 * g + r];
-          *(f16x4 *)(smem + m * CPITCH + n * 2) = h;
-          if (a.y32 && m < nrow)      // the un-rounded result for the head, 16 B per lane
-            *(float4 *)(a.y32 + ((long)frame * P + p0 + m) * a.ld32 + n) =
-                make_float4(acc[ct][pt][4 * g], acc[ct][pt][4 * g + 1], acc[ct][pt][4 * g + 2], acc[ct][pt][4 * g + 3]);
+          if constexpr (HEAD) {
+            if (m < kHeadRows) {
+              const float4 hs = *(const float4 *)(a.head_s + n), ht = *(const float4 *)(a.head_t + n);
+              *(f16x4 *)(smem + m * CPITCH + n * 2) = h;
+              *(float4 *)(smem + kHeadTermOff + m * kHeadTermPitch + n * 4) =
+                  make_float4(fmaxf(fmaf(acc[ct][pt][4 * g], hs.x, ht.x), 0.f), fmaxf(fmaf(acc[ct][pt][4 * g + 1], hs.y, ht.y), 0.f),
+                              fmaxf(fmaf(acc[ct][pt][4 * g + 2], hs.z, ht.z), 0.f), fmaxf(fmaf(acc[ct][pt][4 * g + 3], hs.w, ht.w), 0.f));
+            }
+          } else {
+            *(f16x4 *)(smem + m * CPITCH + n * 2) = h;
+            if (a.y32 && m < nrow)      // the un-rounded result for the head, 16 B per lane
+              *(float4 *)(a.y32 + ((long)frame * P + p0 + m) * a.ld32 + n) =
+                  make_float4(acc[ct][pt][4 * g], acc[ct][pt][4 * g + 1], acc[ct][pt][4 * g + 2], acc[ct][pt][4 * g + 3]);
+          }
         }
   }
   __syncthreads();
+  if constexpr (HEAD) {
+    // channel t: one sequential chain over the pixels p = 0 .. 48, the channels side by side across the workgroup
+    const unsigned char *col = smem + kHeadTermOff + t * 4;
+    float sum = 0.f;
+#pragma unroll
+    for (int p = 0; p < kHeadRows; ++p) sum += *(const float *)(col + p * kHeadTermPitch);
+    a.feat[(long)frame * a.ldfeat + t] = sum * (1.0f / 49.0f);
+  }
   // coalesced rows: 64 threads x 16 B per pixel
   for (int id = t; id < nrow * (NB / 8); id += 512) {
     const int row = id / (NB / 8), ch = id % (NB / 8);
@@ -276,8 +315,30 @@ static int launch_tws(const Conv1x1Args &a, hipStream_t s) {
   return TN_OK;
 }
 
+static std::atomic<long> g_head_fused_launches{0};
+long head_fused_launches() { return g_head_fused_launches.load(std::memory_order_relaxed); }
+void head_fused_launched() { g_head_fused_launches.fetch_add(1, std::memory_order_relaxed); }
+
+// the 64 x 512 tile with the head epilogue: the frame has to be the tile
+template <int NK>
+static int launch_tws_head(const Conv1x1Args &a, hipStream_t s) {
+  TN_SET_ATTR_ONCE_PER_DEVICE(TN_HIP_CHECK(hipFuncSetAttribute((const void *)trans_ws_kernel<NK, 64, 512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kHeadLdsBytes)));
+  hipLaunchKernelGGL((trans_ws_kernel<NK, 64, 512, true>), dim3(a.M / kHeadRows), dim3(512), kHeadLdsBytes, s, a, 1, kHeadRows);
+  TN_HIP_CHECK(hipGetLastError());
+  head_fused_launched();
+  return TN_OK;
+}
+
 int launch_trans_ws(const Conv1x1Args &a, hipStream_t s) {
   TN_REQUIRE(trans_ws_supported(a) && a.wfrag, "trans_ws: unsupported geometry");
+  if (a.feat) {
+    const int P = (a.H / 2) * (a.W / 2);
+    TN_REQUIRE(a.N == 512 && P == kHeadRows, "trans_ws: the head epilogue needs N = 512 and a frame of one 49-pixel tile (a 14 x 14 map): N = " +
+                                                 std::to_string(a.N) + ", " + std::to_string(a.H) + " x " + std::to_string(a.W));
+    TN_REQUIRE(a.head_s && a.head_t && a.ldfeat >= a.N, "trans_ws: the head epilogue needs head_s, head_t and ldfeat >= N");
+    TN_REQUIRE((((uintptr_t)a.head_s | (uintptr_t)a.head_t) & 15) == 0, "trans_ws: head_s and head_t must be 16-byte aligned");
+    return a.K == 16 * BK ? launch_tws_head<16>(a, s) : launch_tws_head<0>(a, s);
+  }
   if (a.N == 512) return a.K == 16 * BK ? launch_tws<16, 64, 512>(a, s) : launch_tws<0, 64, 512>(a, s);
   return a.K == 8 * BK ? launch_tws<8, 128, 256>(a, s) : launch_tws<0, 128, 256>(a, s);
 }
