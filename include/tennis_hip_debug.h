@@ -316,6 +316,33 @@ int tn_dbg_gnmt_ce(tn_ctx *ctx, const float *logits, const int32_t *labels, int 
 /* trn_emb_grad_kernel: dx0 (L,B,K0) step-major with K0 > E (the first E columns are read), tgt (B rows of pitch ld >= L; an id <= 0
  * counts as row 0) -> demb (V,E), every row assigned. */
 int tn_dbg_gnmt_emb_grad(tn_ctx *ctx, const float *dx0, int K0, const int32_t *tgt, int ld, int B, int L, int E, int V, float *demb);
+/* One launch of dec_beam_kernel<NBM> (the last launch of a beam-search step) over B clips of `beam` rows, R = B * beam, with the
+ * instantiation, dynamic LDS, projection split and extra workgroups tn_gnmt_beam_search computes for the shape.  split_cap as in
+ * tn_dbg_gnmt_attention_fwd.  Refused: a null pointer that is not optional, H % 4 != 0, a pitch below its width, beam outside
+ * 1..16, V < beam, LDS past 152 KiB, misaligned operands of the p0 tiles.
+ *   g1 (R,4H) the last cell's stacked pre-activations; x1 the cell's step input [input (2H) | h_prev (H)]: row-major with pitch
+ *   ldx1 >= 3H, or (ldx1 < 0) k-group-major with -ldx1 >= R rows, element (r, k) at ((k / 4) * (-ldx1) + r) * 4 + k % 4; c1cur (R,H; LSTM,
+ *   else NULL); wp_host (V,H) / bp_host (V; NULL: no bias) HOST, packed as tn_gnmt_create packs tgt_proj; scores / alive / vlen (R) in
+ *   and out; bp_par / bp_word (step,R): row step - 1 is written; any_alive (1): or-ed with 1 when a row stays alive; hstate (R,H) or
+ *   NULL: the residual form (the projection sees h + x1[:, 0:H]); parent_out (R) or NULL.
+ *   Token form (tok_out (R) != NULL): the words go to tok_out; with p0 (R,4H) != NULL, extra workgroups compute
+ *   p0 = x1[:, 0:2H] . w1x[:, 0:2H]^T + b1x (w1x (4H rows of pitch K1p), b1x (4H)) beside the clips; p0 = w1x = b1x = NULL: none.
+ *   x0 form (tok_out NULL): x0 (R, E + 2H) = [emb[word] (emb (V,E)), ctxv[parent], h0n[parent]] (both (R,H)), c0cur = c0n[parent] (LSTM).
+ *   Always: x1[:, 2H:3H] = h[parent] (hstate's rows in the residual form), c1cur = c[parent] (LSTM). */
+int tn_dbg_gnmt_beam_step(tn_ctx *ctx, const float *g1, float *x1, int ldx1, int lstm, float *c1cur, const float *wp_host,
+                          const float *bp_host, int B, int H, int E, int V, int beam, int step, float lp, float prev_lp, int eos,
+                          int split_cap, float *scores, int32_t *alive, int32_t *vlen, int32_t *bp_par, int32_t *bp_word,
+                          int32_t *any_alive, float *hstate, int32_t *parent_out, int32_t *tok_out, const float *w1x, const float *b1x,
+                          int K1p, float *p0, const float *emb, const float *ctxv, const float *h0n, const float *c0n, float *x0,
+                          float *c0cur);
+/* The latency GEMM (csrc/linear.h lat_tile_f32) through its launchers: Y (M rows of pitch ldy >= N) = X W^T + bias, W (N rows of
+ * pitch ldw >= K) row-major, bias (N) or NULL, all DEVICE.  form 0: launch_linear_f32_lat2 - X row-major (pitch ldx >= K); the
+ * columns from nsplit (a multiple of 16; >= N: none) contract only k < K2.  form 1: launch_linear_f32_lat_wk4 on the k-group-major
+ * copy of W built here; X row-major, or (ldx < 0) k-group-major with -ldx >= M rows, element (m, k) at ((k / 4) * (-ldx) + m) * 4 + k % 4;
+ * needs K % 4 == 0, ldx % 4 == 0 and a 16-byte aligned X.  *route (optional): 0 the latency kernel, 1 its k-group-major form, 2 the
+ * launch_linear_f32 fallback (form 0 with K < 128, operands off float4 alignment or more than 4096 tiles).  Synchronous. */
+int tn_dbg_linear_lat(tn_ctx *ctx, int form, const float *X, int ldx, const float *W, int ldw, const float *bias, float *Y, int ldy, int M,
+                      int N, int K, int nsplit, int K2, int *route);
 
 #ifdef __cplusplus
 }

@@ -164,6 +164,9 @@ _SIGS = {
     "tn_dbg_gnmt_attention_outer": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "tn_dbg_gnmt_ce": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "tn_dbg_gnmt_emb_grad": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "tn_dbg_gnmt_beam_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_int, C.c_int]
+                              + [_P] * 11 + [C.c_int] + [_P] * 7),
+    "tn_dbg_linear_lat": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P] + [C.c_int] * 6 + [C.POINTER(C.c_int)]),
     "tn_gnmt_trainer_create": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "tn_gnmt_trainer_create_ex": (C.c_int, [_P, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -95,6 +95,33 @@ static int att_split(int T, int H, size_t limit) {
     if (att_lds_bytes(T, H, sp) <= limit) return sp;
   return 0;
 }
+// dec_beam_kernel's launch parameters: the instantiation (beam rows a projection thread carries), the dynamic LDS
+// h1n[H][NP] | c1n[H][NP] | logits[beam * Vp] | part[KQ * beam * Vp] (+ 16) for a projection split, and the largest split that
+// fits `limit` (1 where none does: the caller compares beam_lds_bytes with its limit)
+static int beam_nbm(int beam) { return beam <= 4 ? 4 : beam == 5 ? 5 : beam <= 8 ? 8 : 16; }   // beam 5: the reference's flag default
+static size_t beam_lds_bytes(int H, int V, int beam, int split) {
+  const int nbm = beam_nbm(beam), Vp = (V + 3) & ~3;
+  return ((size_t)2 * ((nbm + 3) & ~3) * H + (size_t)(1 + kBeamThreads / step_groups(Vp / 4, split)) * beam * Vp + 16) * sizeof(float);
+}
+static int beam_split(int H, int V, int beam, size_t limit) {
+  int sp = 16;
+  while (sp > 1 && beam_lds_bytes(H, V, beam, sp) > limit) sp >>= 1;
+  return sp;
+}
+// the p0 tiles beside the clips (dec_beam_kernel, `tok_out`): workgroups of four 16 x 16 tiles over (R, 4H), and the LDS their
+// partial sums need
+static int beam_gemm_wgs(int R, int H) { return (((R + 15) / 16) * (4 * H / 16) + 3) / 4; }
+constexpr size_t kBeamTileLds = 4 * 4 * 64 * 4 * sizeof(float);
+// the vocabulary projection as dec_beam_kernel reads it: wt = Wp^T (H, Vp) and bpad (Vp), Vp = V rounded up to 4 (the kernel loads
+// four columns at a time), the pad columns zero; wp (V,H) row-major, bp (V) or NULL (no bias)
+static void pack_proj(const float *wp, const float *bp, int V, int H, std::vector<float> &wt, std::vector<float> &bpad) {
+  const int vp = (V + 3) & ~3;
+  wt.assign((size_t)H * vp, 0.f);
+  for (int v = 0; v < V; ++v)
+    for (int k = 0; k < H; ++k) wt[(size_t)k * vp + v] = wp[(size_t)v * H + k];
+  bpad.assign(vp, 0.f);
+  if (bp) memcpy(bpad.data(), bp, sizeof(float) * V);
+}
 // Beam-search step, first launch, one workgroup (16 waves) per decoder row (the step is latency-bound - few workgroups,
 // dependent L2 round trips - so it pays to spread the rows over CUs even though the beams of a clip each re-read the clip's key
 // projection and memory from L2):
@@ -1311,14 +1338,10 @@ extern "C" int tn_gnmt_create_ex(tn_ctx *ctx, const tn_param *params, int n_para
     for (int i = 1; i + 1 < num_layers; ++i)
       if (!stack("dec_rnn" + std::to_string(i) + "_", 2 * H, &g->mid[i - 1].w, &g->mid[i - 1].b)) return fail(TN_ERR_MISSING);
     const float *wp = pm.get(pre + "tgt_proj_weight", (int64_t)vocab * H);
-    const int vp = (vocab + 3) & ~3;        // rows of Wp^T padded to 16 bytes (dec_beam_kernel loads four columns at a time)
-    std::vector<float> wt((size_t)H * vp, 0.f);
-    for (int v = 0; v < vocab; ++v)
-      for (int k = 0; k < H; ++k) wt[(size_t)k * vp + v] = wp[(size_t)v * H + k];
-    g->wpT = g->pool.upload(wt.data(), wt.size());
     const float *bpv = pm.get(pre + "tgt_proj_bias", vocab);
-    std::vector<float> bpad(vp, 0.f);
-    if (bpv) memcpy(bpad.data(), bpv, sizeof(float) * vocab);
+    std::vector<float> wt, bpad;
+    pack_proj(wp, bpv, vocab, H, wt, bpad);
+    g->wpT = g->pool.upload(wt.data(), wt.size());
     g->bpp = g->pool.upload(bpad.data(), bpad.size());
   }
   const size_t BT = (size_t)max_batch * max_src_len, R = (size_t)max_batch * beam;
@@ -1427,13 +1450,10 @@ static int gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, float K, 
   const int B = g->B, T = g->T, H = g->H, E = g->E, V = g->V, beam = g->beam, R = B * beam, L = g->maxL;
   const int K0 = E + 2 * H, K1 = 3 * H;
   const bool lstm = g->G == 4;
-  const int nbm = beam <= 4 ? 4 : beam == 5 ? 5 : beam <= 8 ? 8 : 16;   // beam 5: the reference's flag default
+  const int nbm = beam_nbm(beam);
   const int asplit = att_split(T, H, kStepLdsMax);
-  const int Vp = (V + 3) & ~3;
-  auto beam_lds_of = [&](int sp) { return ((size_t)2 * ((nbm + 3) & ~3) * H + (size_t)(1 + kBeamThreads / step_groups(Vp / 4, sp)) * beam * Vp + 16) * sizeof(float); };
-  int bsplit = 16;
-  while (bsplit > 1 && beam_lds_of(bsplit) > kStepLdsMax) bsplit >>= 1;
-  const size_t beam_lds = beam_lds_of(bsplit);
+  const int bsplit = beam_split(H, V, beam, kStepLdsMax);
+  const size_t beam_lds = beam_lds_bytes(H, V, beam, bsplit);
   TN_REQUIRE(beam_lds <= kStepLdsMax && asplit > 0,
              "tn_gnmt_beam_search: beam * (2*hidden + 2*vocab) or 3 * max(hidden, source length) floats exceed the step kernels' 152 KiB of LDS");
   const size_t att_lds = att_lds_bytes(T, H, asplit);
@@ -1482,8 +1502,8 @@ static int gnmt_beam_search(tn_gnmt *g, int bos, int eos, float alpha, float K, 
       g->ew_ready = true;
     }
     gm = LatGemmArgs{sx1, g->w1x, g->b1x, g->p0, ld1, g->K1p, 4 * H, R, 4 * H, 2 * H};
-    gemm_wgs = (((R + 15) / 16) * (4 * H / 16) + 3) / 4;
-    if (beam_lds_launch < 4 * 4 * 64 * 4 * sizeof(float)) beam_lds_launch = 4 * 4 * 64 * 4 * sizeof(float);   // the tiles' partial sums
+    gemm_wgs = beam_gemm_wgs(R, H);
+    if (beam_lds_launch < kBeamTileLds) beam_lds_launch = kBeamTileLds;   // the tiles' partial sums
   }
   float *h0buf[2] = {g->h0n, fused0 ? g->h0n2 : g->h0n}, *c0buf[2] = {g->c0n, fused0 ? g->c0n2 : g->c0n};
   int steps_done = 0, all_dead = 0;
@@ -2306,4 +2326,112 @@ extern "C" int tn_dbg_gnmt_emb_grad(tn_ctx *ctx, const float *dx0, int K0, const
   TN_HIP_CHECK(hipGetLastError());
   TN_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return TN_OK;
+}
+
+// One launch of dec_beam_kernel<NBM> on caller operands, with the instantiation, LDS, projection split and extra workgroups
+// gnmt_beam_search computes for the shape.  wp / bp HOST (packed by pack_proj as tn_gnmt_create packs them), everything else DEVICE.
+extern "C" int tn_dbg_gnmt_beam_step(tn_ctx *ctx, const float *g1, float *x1, int ldx1, int lstm, float *c1cur, const float *wp_host,
+                                     const float *bp_host, int B, int H, int E, int V, int beam, int step, float lp, float prev_lp, int eos,
+                                     int split_cap, float *scores, int32_t *alive, int32_t *vlen, int32_t *bp_par, int32_t *bp_word,
+                                     int32_t *any_alive, float *hstate, int32_t *parent_out, int32_t *tok_out, const float *w1x,
+                                     const float *b1x, int K1p, float *p0, const float *emb, const float *ctxv, const float *h0n,
+                                     const float *c0n, float *x0, float *c0cur) {
+  TN_REQUIRE(ctx && g1 && x1 && wp_host && scores && alive && vlen && bp_par && bp_word && any_alive, "tn_dbg_gnmt_beam_step: null argument");
+  TN_REQUIRE(!lstm || c1cur, "tn_dbg_gnmt_beam_step: the LSTM form needs c1cur");
+  TN_REQUIRE(beam >= 1 && beam <= 16, "tn_dbg_gnmt_beam_step: beam must be 1 to 16");
+  TN_REQUIRE(B >= 1 && B <= 4096 && H >= 4 && H % 4 == 0 && H <= 4096 && E >= 1 && V >= beam && V <= 65536 && step >= 1 && lp > 0.f,
+             "tn_dbg_gnmt_beam_step: needs 1 <= B <= 4096, H a positive multiple of 4, E >= 1, beam <= V <= 65536, step >= 1, lp > 0");
+  const int R = B * beam;
+  TN_REQUIRE(ldx1 >= 3 * H || -ldx1 >= R, "tn_dbg_gnmt_beam_step: x1's pitch is below 3 H (row-major) or its rows below B * beam (k-group-major)");
+  TN_REQUIRE(split_cap == 0 || split_cap == 16 || split_cap == 8 || split_cap == 4 || split_cap == 2 || split_cap == 1,
+             "tn_dbg_gnmt_beam_step: split_cap must be 0, 16, 8, 4, 2 or 1");
+  int gemm_wgs = 0;
+  LatGemmArgs gm{};
+  if (tok_out) {       // the token form; p0 == NULL: without the extra workgroups
+    TN_REQUIRE(!emb && !ctxv && !h0n && !c0n && !x0 && !c0cur, "tn_dbg_gnmt_beam_step: the token form takes no x0 operands");
+    TN_REQUIRE(p0 ? (w1x && b1x) : (!w1x && !b1x), "tn_dbg_gnmt_beam_step: p0, w1x and b1x come together");
+    if (p0) {
+      TN_REQUIRE(K1p >= 2 * H && K1p % 4 == 0 && (ldx1 < 0 || ldx1 % 4 == 0) && (((uintptr_t)x1 | (uintptr_t)w1x) & 15) == 0,
+                 "tn_dbg_gnmt_beam_step: the p0 tiles need K1p >= 2 H and float4-aligned x1, w1x and pitches");
+      gm = LatGemmArgs{x1, w1x, b1x, p0, ldx1, K1p, 4 * H, R, 4 * H, 2 * H};
+      gemm_wgs = beam_gemm_wgs(R, H);
+    }
+  } else {
+    TN_REQUIRE(!w1x && !b1x && !p0, "tn_dbg_gnmt_beam_step: the x0 form takes no p0 operands");
+    TN_REQUIRE(emb && ctxv && h0n && x0 && (!lstm || (c0n && c0cur)), "tn_dbg_gnmt_beam_step: the x0 form needs emb, ctx, h0n, x0 (LSTM: c0n, c0cur)");
+  }
+  int bsplit = beam_split(H, V, beam, kStepLdsMax);
+  if (split_cap && split_cap < bsplit) bsplit = split_cap;
+  const size_t beam_lds = beam_lds_bytes(H, V, beam, bsplit);
+  TN_REQUIRE(beam_lds <= kStepLdsMax, "tn_dbg_gnmt_beam_step: beam * (2*hidden + 2*vocab) floats exceed the step kernel's 152 KiB of LDS");
+  const size_t beam_lds_launch = gemm_wgs && beam_lds < kBeamTileLds ? kBeamTileLds : beam_lds;
+  TN_ON_DEVICE(ctx->device);
+  hipStream_t s = ctx->stream;
+  const int nbm = beam_nbm(beam);
+  if (int rc = nbm == 4 ? allow_lds(dec_beam_kernel<4>, beam_lds) : nbm == 5 ? allow_lds(dec_beam_kernel<5>, beam_lds)
+               : nbm == 8 ? allow_lds(dec_beam_kernel<8>, beam_lds) : allow_lds(dec_beam_kernel<16>, beam_lds)) return rc;
+  std::vector<float> wt, bpad;
+  pack_proj(wp_host, bp_host, V, H, wt, bpad);
+  float *wpT = nullptr, *bpp = nullptr;
+  hipError_t e = hipMalloc((void **)&wpT, sizeof(float) * wt.size());
+  if (e == hipSuccess) e = hipMalloc((void **)&bpp, sizeof(float) * bpad.size());
+  if (e == hipSuccess) e = hipMemcpyAsync(wpT, wt.data(), sizeof(float) * wt.size(), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(bpp, bpad.data(), sizeof(float) * bpad.size(), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+#define TN_BEAM_LAUNCH(NBM)                                                                                                          \
+  hipLaunchKernelGGL(dec_beam_kernel<NBM>, dim3(B + gemm_wgs), dim3(kBeamThreads), beam_lds_launch, s, g1, 4 * H, x1, ldx1,          \
+                     lstm ? 1 : 0, c1cur, (const float *)wpT, (const float *)bpp, h0n, ctxv, c0n, x0, c0cur, emb, H, E, V, beam,     \
+                     step, lp, prev_lp, eos, scores, alive, vlen, bp_par, bp_word, R, any_alive, hstate, parent_out, tok_out, B, gm, \
+                     bsplit)
+    if (nbm == 4) TN_BEAM_LAUNCH(4);
+    else if (nbm == 5) TN_BEAM_LAUNCH(5);
+    else if (nbm == 8) TN_BEAM_LAUNCH(8);
+    else TN_BEAM_LAUNCH(16);
+#undef TN_BEAM_LAUNCH
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  else (void)hipStreamSynchronize(s);
+  (void)hipFree(wpT);
+  (void)hipFree(bpp);
+  TN_HIP_CHECK(e);
+  return TN_OK;
+}
+
+// The latency GEMM's launchers on caller operands.  form 0: launch_linear_f32_lat2 (row-major X and W); 1: launch_linear_f32_lat_wk4
+// on the k-group-major copy of W built here, X row-major (ldx > 0) or k-group-major with -ldx >= M rows.
+extern "C" int tn_dbg_linear_lat(tn_ctx *ctx, int form, const float *X, int ldx, const float *W, int ldw, const float *bias, float *Y, int ldy,
+                                 int M, int N, int K, int nsplit, int K2, int *route) {
+  TN_REQUIRE(ctx && X && W && Y, "tn_dbg_linear_lat: null argument");
+  TN_REQUIRE(form == 0 || form == 1, "tn_dbg_linear_lat: form must be 0 (lat / lat2) or 1 (lat_wk4)");
+  TN_REQUIRE(M >= 1 && N >= 1 && K >= 1 && M <= 65535 * 16 && N <= (1 << 20) && K <= (1 << 20), "tn_dbg_linear_lat: needs M, N, K >= 1");
+  TN_REQUIRE(ldw >= K && ldy >= N, "tn_dbg_linear_lat: ldw below K or ldy below N");
+  TN_REQUIRE(form == 0 ? ldx >= K : (ldx >= K || -ldx >= M), "tn_dbg_linear_lat: ldx below K (row-major) or X's rows below M (k-group-major)");
+  TN_ON_DEVICE(ctx->device);
+  hipStream_t s = ctx->stream;
+  if (form == 0) {
+    TN_REQUIRE(nsplit >= N || (nsplit >= 16 && nsplit % 16 == 0 && K2 > 0 && K2 <= K && K2 % 4 == 0), "tn_dbg_linear_lat: bad column split");
+    if (route) *route = linear_f32_lat_takes(X, ldx, W, ldw, M, N, K) ? 0 : 2;
+    if (int rc = launch_linear_f32_lat2(X, ldx, W, ldw, bias, Y, ldy, M, N, K, nsplit, K2, s)) return rc;
+    TN_HIP_CHECK(hipStreamSynchronize(s));
+    return TN_OK;
+  }
+  TN_REQUIRE(nsplit >= N, "tn_dbg_linear_lat: the k-group-major form has no column split");
+  TN_REQUIRE((ldx < 0 || (ldx & 3) == 0) && (K & 3) == 0 && ((uintptr_t)X & 15) == 0, "tn_dbg_linear_lat: the k-group-major form needs float4-aligned operands");
+  std::vector<float> w((size_t)N * K), wk((size_t)K * N);
+  TN_HIP_CHECK(hipMemcpy2DAsync(w.data(), sizeof(float) * K, W, sizeof(float) * ldw, sizeof(float) * K, N, hipMemcpyDeviceToHost, s));
+  TN_HIP_CHECK(hipStreamSynchronize(s));
+  for (int row = 0; row < N; ++row)
+    for (int k = 0; k < K; ++k) wk[((size_t)(k >> 2) * N + row) * 4 + (k & 3)] = w[(size_t)row * K + k];
+  float *wk4 = nullptr;
+  TN_HIP_CHECK(hipMalloc((void **)&wk4, sizeof(float) * wk.size()));
+  hipError_t e = hipMemcpyAsync(wk4, wk.data(), sizeof(float) * wk.size(), hipMemcpyHostToDevice, s);
+  int rc = TN_OK;
+  if (e == hipSuccess) rc = launch_linear_f32_lat_wk4(X, ldx, wk4, bias, Y, ldy, M, N, K, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  (void)hipFree(wk4);
+  TN_HIP_CHECK(e);
+  TN_HIP_CHECK(e2);
+  if (route) *route = 1;
+  return rc;
 }

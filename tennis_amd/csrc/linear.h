@@ -76,6 +76,8 @@ void linear_rows_set_pad_skip(bool on);
 // otherwise): 16 x 16 output tiles, K split over the four waves of a workgroup, every operand requested up front.
 int launch_linear_f32_lat(const float *X, int ldx, const float *Wt, int ldw, const float *bias, float *Y, int ldy, int M, int N, int K,
                           hipStream_t s);
+// whether launch_linear_f32_lat / _lat2 run the latency kernel on these operands (false: the launch_linear_f32 fallback)
+bool linear_f32_lat_takes(const float *X, int ldx, const float *Wt, int ldw, int M, int N, int K);
 // the weights k-group-major (see lat_tile_f32<true>): Wk4[(k / 4) * 4 N + n * 4 + k % 4], K % 4 == 0, X float4-aligned
 int launch_linear_f32_lat_wk4(const float *X, int ldx, const float *Wk4, const float *bias, float *Y, int ldy, int M, int N, int K, hipStream_t s);
 // (ldx < 0: X k-group-major too, with -ldx rows: X[(k / 4) * 4 (-ldx) + m * 4 + k % 4])

@@ -289,6 +289,11 @@ int launch_linear_f32_lat_wk4(const float *X, int ldx, const float *Wk4, const f
   return TN_OK;
 }
 
+bool linear_f32_lat_takes(const float *X, int ldx, const float *Wt, int ldw, int M, int N, int K) {
+  const bool vec = ((ldx | ldw | K) & 3) == 0 && (((uintptr_t)X | (uintptr_t)Wt) & 15) == 0;
+  return vec && K >= 128 && (long)((N + 15) / 16) * ((M + 15) / 16) <= 4096;
+}
+
 int launch_linear_f32_lat(const float *X, int ldx, const float *Wt, int ldw, const float *bias, float *Y, int ldy, int M, int N, int K,
                           hipStream_t s) {
   return launch_linear_f32_lat2(X, ldx, Wt, ldw, bias, Y, ldy, M, N, K, N, K, s);
@@ -301,8 +306,7 @@ int launch_linear_f32_lat2(const float *X, int ldx, const float *Wt, int ldw, co
                            int nsplit, int K2, hipStream_t s) {
   if (M <= 0 || N <= 0) return TN_OK;
   TN_REQUIRE(nsplit >= N || (nsplit % 16 == 0 && K2 > 0 && K2 <= K && K2 % 4 == 0), "linear_f32_lat2: bad column split");
-  const bool vec = ((ldx | ldw | K) & 3) == 0 && (((uintptr_t)X | (uintptr_t)Wt) & 15) == 0;
-  if (!vec || K < 128 || (long)((N + 15) / 16) * ((M + 15) / 16) > 4096) {
+  if (!linear_f32_lat_takes(X, ldx, Wt, ldw, M, N, K)) {
     if (nsplit >= N) return launch_linear_f32(X, ldx, Wt, ldw, bias, Y, ldy, M, N, K, 0, s);
     if (int rc = launch_linear_f32(X, ldx, Wt, ldw, bias, Y, ldy, M, nsplit, K, 0, s)) return rc;
     return launch_linear_f32(X, ldx, Wt + (long)nsplit * ldw, ldw, bias ? bias + nsplit : nullptr, Y + nsplit, ldy, M, N - nsplit, K2, 0, s);
