@@ -289,7 +289,7 @@ int tn_dbg_window_head_rows_per_group(struct tn_window_head *h, int nb);
 #define TN_GRAD_SUMSQ_GRID 1024
 int tn_dbg_grad_sumsq(tn_ctx *ctx, const float *dev, int64_t n, const float *dev2, int64_t n2, double *sumsq_host);
 
-/* The captioner's step kernels (csrc/captioner.hip) on their own: each hook launches the production kernel on the ctx stream with
+/* The captioner's step kernels (csrc/gnmt_kernels.hip) on their own: each hook launches the production kernel on the ctx stream with
  * the grid, block and dynamic LDS the decoder / the training step compute for the shape, then synchronises.  All operands DEVICE
  * fp32 (valid_len / labels / tgt int32), 16-byte aligned; H % 4 == 0.  A null pointer (other than the optional ones), a pitch below
  * its width or a shape whose LDS passes the step kernels' 152 KiB is refused with TN_ERR_INVALID.

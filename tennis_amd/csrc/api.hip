@@ -622,7 +622,7 @@ extern "C" int tn_cnnrnn_trainer_destroy(tn_cnnrnn_trainer *t) {
 // reference train_gnmt.py:148-203 without --feats_model: src_embed = TimeDistributed(FrameModel(DenseNet121.features).backbone)
 // inside the NMTModel, trained (or frozen, :164-166) by the same loss.backward() / trainer.step(1) (:334-337).  The fine-tuning
 // step's backbone (finetune.hip, no classifier) over the batch * steps frames of the padded clips, the captioner's step
-// (captioner.hip) on its features.
+// (captioner_train.hip) on its features.
 struct tn_gnmt_frames_trainer {
   tn_ctx *ctx;
   tn_finetune *bb;

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "encoder_plan.h"
 #include "gemm_fp32x3.h"
+#include "gnmt_kernels.h"
 #include "linear.h"
 #include "param_table.h"
 #include "rnn.h"
@@ -883,4 +884,41 @@ extern "C" int tn_dbg_conv_fp32x3(tn_ctx *ctx, int which, int kind, int tile, in
   if (rc) return rc;
   TN_HIP_CHECK(e);
   return TN_OK;
+}
+
+// The latency GEMM's launchers on caller operands.  form 0: launch_linear_f32_lat2 (row-major X and W); 1: launch_linear_f32_lat_wk4
+// on the k-group-major copy of W built here, X row-major (ldx > 0) or k-group-major with -ldx >= M rows.
+extern "C" int tn_dbg_linear_lat(tn_ctx *ctx, int form, const float *X, int ldx, const float *W, int ldw, const float *bias, float *Y, int ldy,
+                                 int M, int N, int K, int nsplit, int K2, int *route) {
+  TN_REQUIRE(ctx && X && W && Y, "tn_dbg_linear_lat: null argument");
+  TN_REQUIRE(form == 0 || form == 1, "tn_dbg_linear_lat: form must be 0 (lat / lat2) or 1 (lat_wk4)");
+  TN_REQUIRE(M >= 1 && N >= 1 && K >= 1 && M <= 65535 * 16 && N <= (1 << 20) && K <= (1 << 20), "tn_dbg_linear_lat: needs M, N, K >= 1");
+  TN_REQUIRE(ldw >= K && ldy >= N, "tn_dbg_linear_lat: ldw below K or ldy below N");
+  TN_REQUIRE(form == 0 ? ldx >= K : (ldx >= K || -ldx >= M), "tn_dbg_linear_lat: ldx below K (row-major) or X's rows below M (k-group-major)");
+  TN_ON_DEVICE(ctx->device);
+  hipStream_t s = ctx->stream;
+  if (form == 0) {
+    TN_REQUIRE(nsplit >= N || (nsplit >= 16 && nsplit % 16 == 0 && K2 > 0 && K2 <= K && K2 % 4 == 0), "tn_dbg_linear_lat: bad column split");
+    if (route) *route = linear_f32_lat_takes(X, ldx, W, ldw, M, N, K) ? 0 : 2;
+    if (int rc = launch_linear_f32_lat2(X, ldx, W, ldw, bias, Y, ldy, M, N, K, nsplit, K2, s)) return rc;
+    TN_HIP_CHECK(hipStreamSynchronize(s));
+    return TN_OK;
+  }
+  TN_REQUIRE(nsplit >= N, "tn_dbg_linear_lat: the k-group-major form has no column split");
+  TN_REQUIRE((ldx < 0 || (ldx & 3) == 0) && (K & 3) == 0 && ((uintptr_t)X & 15) == 0, "tn_dbg_linear_lat: the k-group-major form needs float4-aligned operands");
+  std::vector<float> w((size_t)N * K);
+  TN_HIP_CHECK(hipMemcpy2DAsync(w.data(), sizeof(float) * K, W, sizeof(float) * ldw, sizeof(float) * K, N, hipMemcpyDeviceToHost, s));
+  TN_HIP_CHECK(hipStreamSynchronize(s));
+  const std::vector<float> wk = pack_wk4(w.data(), N, K);
+  float *wk4 = nullptr;
+  TN_HIP_CHECK(hipMalloc((void **)&wk4, sizeof(float) * wk.size()));
+  hipError_t e = hipMemcpyAsync(wk4, wk.data(), sizeof(float) * wk.size(), hipMemcpyHostToDevice, s);
+  int rc = TN_OK;
+  if (e == hipSuccess) rc = launch_linear_f32_lat_wk4(X, ldx, wk4, bias, Y, ldy, M, N, K, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  (void)hipFree(wk4);
+  TN_HIP_CHECK(e);
+  TN_HIP_CHECK(e2);
+  if (route) *route = 1;
+  return rc;
 }

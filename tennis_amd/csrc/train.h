@@ -39,7 +39,7 @@ int launch_colsum_f32(const float *A, int lda, int rows, int cols, float *out, h
 int launch_sgd_momentum(float *w, const float *g, float *mom, long n, float lr, float momentum, float wd,
                         float rescale, hipStream_t s, const float *scale = nullptr);
 // MXNet Adam (gluon.Trainer 'adam', reference train_gnmt.py:310,337): step = the 1-based update count, its bias correction folded
-// into the rate; no weight decay, rescale_grad 1.  Shared by the captioner's parameters (captioner.hip) and the backbone's (finetune.hip).
+// into the rate; no weight decay, rescale_grad 1.  Shared by the captioner's parameters (captioner_train.hip) and the backbone's (finetune.hip).
 int launch_adam(float *w, const float *g, float *m, float *v, long n, float lr, float beta1, float beta2, float epsilon, long step,
                 hipStream_t s, const float *scale = nullptr);
 // The device record of a handle's clipping: what grad_sumsq_finalize_kernel writes and the clipped update kernels read (scale)
@@ -89,7 +89,7 @@ void ft_update_running(tn_finetune *f);
 float *ft_features(tn_finetune *f);
 float *ft_feature_grad(tn_finetune *f);
 int ft_feature_dim(tn_finetune *f);
-// The captioner's training step (captioner.hip), what tn_gnmt_trainer_forward_backward runs.  dsrc non-null: also the gradient of
+// The captioner's training step (captioner_train.hip), what tn_gnmt_trainer_forward_backward runs.  dsrc non-null: also the gradient of
 // the loss with respect to src, (batch * steps, input_size) of row stride ldd, assigned; rows at or past src_valid_len[b] are 0.
 int gnmt_trainer_step(tn_gnmt_trainer *t, const float *src, const int32_t *src_valid_len, const int32_t *tgt, int ld,
                       const int32_t *tgt_valid_len, int batch, int steps, int tgt_len, float *loss, float *logits_out, float *dsrc, int ldd);

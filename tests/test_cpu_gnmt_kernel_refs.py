@@ -4,7 +4,7 @@
     cross-entropy gradient against log_softmax, the embedding gradient against an index_add;
   * the input recipe: every attention case's scores spread by 1 to 2 over the valid steps (clearly non-uniform, not saturated);
   * the mutant condition: every deliberate defect moves the output it damages by at least 10 bars, so the GPU test can fail;
-  * the five hooks are declared in the debug header, bound in tennis_amd/_lib.py and defined in csrc/captioner.hip."""
+  * the five hooks are declared in the debug header, bound in tennis_amd/_lib.py and defined in csrc/gnmt_dbg.hip."""
 import os
 import re
 
@@ -190,7 +190,7 @@ def test_bars_come_from_the_reference_alone():
 def test_hooks_are_declared_bound_and_defined():
     from tennis_amd import _lib
     header = open(os.path.join(ROOT, "include", "tennis_hip_debug.h")).read()
-    source = open(os.path.join(ROOT, "tennis_amd", "csrc", "captioner.hip")).read()
+    source = open(os.path.join(ROOT, "tennis_amd", "csrc", "gnmt_dbg.hip")).read()
     for name in HOOKS:
         assert re.search(r"\bint\s+" + name + r"\s*\(", header), name
         assert re.search(r'extern "C" int ' + name + r"\s*\(", source), name

@@ -8,7 +8,7 @@
     case it applies to, so the GPU tests can fail;
   * the launchers' slice arithmetic restated (step_groups, KQ, kn, NLD, nch, kbeg): the shape lists reach every named path, and a
     list with a row deleted misses one;
-  * the two hooks are declared in the debug header, bound in tennis_amd/_lib.py and defined in csrc/captioner.hip."""
+  * the two hooks are declared in the debug header, bound in tennis_amd/_lib.py and defined in csrc/gnmt_dbg.hip / csrc/dbg.hip."""
 import os
 import re
 
@@ -248,8 +248,8 @@ def test_beam_shapes_reach_every_path():
 
 def test_restated_arithmetic_matches_the_source():
     """the constants restated in tools/gnmt_step_refs.py are the ones the kernels are built with"""
-    cap = open(os.path.join(ROOT, "tennis_amd", "csrc", "captioner.hip")).read()
-    lin = open(os.path.join(ROOT, "tennis_amd", "csrc", "linear.h")).read()
+    cap = "".join(open(os.path.join(ROOT, "tennis_amd", "csrc", f)).read() for f in ("gnmt_kernels.h", "gnmt_kernels.hip"))
+    lin =open(os.path.join(ROOT, "tennis_amd", "csrc", "linear.h")).read()
     assert "constexpr int NLD = NBM <= 5 ? 16 : NBM <= 8 ? 8 : 2;" in cap
     assert "constexpr size_t kStepLdsMax = 152 * 1024;" in cap and "constexpr float kNeg = -1e18f;" in cap
     assert "const int g = n4 <= 64 ? 64 : n4 <= 128 ? 128 : 256, floor_g = 1024 / split;" in cap
@@ -262,7 +262,7 @@ def test_restated_arithmetic_matches_the_source():
 def test_hooks_are_declared_bound_and_defined():
     from tennis_amd import _lib
     header = open(os.path.join(ROOT, "include", "tennis_hip_debug.h")).read()
-    source = open(os.path.join(ROOT, "tennis_amd", "csrc", "captioner.hip")).read()
+    source = "".join(open(os.path.join(ROOT, "tennis_amd", "csrc", f)).read() for f in ("gnmt_dbg.hip", "dbg.hip"))
     for name in HOOKS:
         assert re.search(r"\bint\s+" + name + r"\s*\(", header), name
         assert re.search(r'extern "C" int ' + name + r"\s*\(", source), name

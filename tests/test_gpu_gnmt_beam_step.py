@@ -1,4 +1,4 @@
-"""-m gpu: the beam-search step kernel dec_beam_kernel<NBM> (tennis_amd/csrc/captioner.hip) on its own, against NumPy float64.
+"""-m gpu: the beam-search step kernel dec_beam_kernel<NBM> (tennis_amd/csrc/gnmt_kernels.hip) on its own, against NumPy float64.
 
 Through tn_dbg_gnmt_beam_step (include/tennis_hip_debug.h): one launch with the instantiation, LDS, projection split and extra
 workgroups tn_gnmt_beam_search computes for the shape.  Cases, input recipes, the reference, metrics and bars are

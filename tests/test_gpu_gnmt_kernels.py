@@ -1,4 +1,4 @@
-"""-m gpu: the captioner's attention and loss kernels (tennis_amd/csrc/captioner.hip) on their own, against NumPy float64.
+"""-m gpu: the captioner's attention and loss kernels (tennis_amd/csrc/gnmt_kernels.hip) on their own, against NumPy float64.
 
 Through the tn_dbg_gnmt_* hooks of include/tennis_hip_debug.h, which launch the production kernels with the production grid, block
 and LDS: dec_attention_kernel<1> behind transpose_bth_kernel, trn_att_bwd_kernel, trn_att_outer_kernel, trn_ce_bwd_kernel +

@@ -1,7 +1,7 @@
 """Shapes, input recipes and plain NumPy references for the captioner's step kernels on their own (tests only): what
 tests/test_cpu_gnmt_kernel_refs.py checks on the CPU and tests/test_gpu_gnmt_kernels.py runs through the tn_dbg_gnmt_* hooks.
 
-Five operations of tennis_amd/csrc/captioner.hip, each written once and evaluated in float64 (the reference) and in float32 (the
+Five operations of tennis_amd/csrc/gnmt_kernels.hip, each written once and evaluated in float64 (the reference) and in float32 (the
 same formula, whose distance from the float64 result sets the bar, see ``bar``):
   attention_fwd    first decoder cell on stacked pre-activations + scaled-Luong attention (dec_attention_kernel<1>)
   attention_bwd    ds, dctx, dh0 of one decoder step's attention                            (trn_att_bwd_kernel)

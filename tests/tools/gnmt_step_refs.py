@@ -4,7 +4,7 @@ tests/test_gpu_gnmt_beam_step.py run through tn_dbg_linear_lat / tn_dbg_gnmt_bea
 
   lat_gemm     Y = X W^T + b, optionally with two K ranges      (csrc/linear.h lat_tile_f32 behind launch_linear_f32_lat2 / _lat_wk4)
   beam_step    last decoder cell, residual, projection, log-softmax, length-penalised candidates, finished beams, stable top-`beam`,
-               the sampler's bookkeeping and the re-gather by parent     (csrc/captioner.hip dec_beam_kernel<NBM>)
+               the sampler's bookkeeping and the re-gather by parent     (csrc/gnmt_kernels.hip dec_beam_kernel<NBM>)
 
 Each formula is written once and evaluated in float64 (the reference) and in float32 (whose distance n from float64 sets the bar,
 max(GEMM_TOL, MARGIN * n) of the magnitude of an element's terms).  Both take ``mutant``: a deliberate defect of the kind the
@@ -20,7 +20,7 @@ import numpy as np
 
 from tools.gnmt_kernel_refs import GEMM_TOL, MARGIN, MUTANT_FACTOR, TINY, cell0     # noqa: F401  (re-exported)
 
-K_NEG = np.float32(-1e18)          # captioner.hip kNeg
+K_NEG = np.float32(-1e18)          # gnmt_kernels.hip kNeg
 
 # ---- the latency GEMM ---------------------------------------------------------------------------------------------------------------
 LAT_GROUP = 6                      # linear.h kLatGroup: 16-wide k chunks a wave requests per round
