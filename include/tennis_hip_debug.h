@@ -213,7 +213,7 @@ int tn_dbg_gnmt_trainer_src_grad(tn_gnmt_trainer *t, const float *src, const int
 int tn_dbg_rows_pad_skip(int on);
 
 /* Which instantiation the recurrent kernels run for a shape (csrc/rnn.h rnn_route, the one policy of launch_rnn_recurrent and of the
- * BPTT launchers of csrc/train.hip): gates 3 GRU / 4 LSTM, B batch rows, H hidden, dirs 1 | 2.  *nb rows per workgroup (1 | 4), *kr the
+ * BPTT launcher of csrc/rnn_bptt.hip): gates 3 GRU / 4 LSTM, B batch rows, H hidden, dirs 1 | 2.  *nb rows per workgroup (1 | 4), *kr the
  * register-resident prefix of a W_hh column (0 | 64 | 96 | 128; 0 at nb = 4; not read when *big), *big 1 for the registers + LDS +
  * stream form (H = 256 at nb = 1).  Host arithmetic only: touches no device. */
 int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int *kr, int *big);

@@ -1,4 +1,4 @@
-"""The wide recurrent kernels (csrc/rnn.hip rnn_recurrent_wide_kernel, csrc/train.hip *_train_bwd_wide_kernel: two gate rows per thread,
+"""The wide recurrent kernels (csrc/rnn.hip rnn_recurrent_wide_kernel, csrc/rnn_bptt.hip rnn_bptt_wide_kernel: two gate rows per thread,
 1024 < gates*H <= 2048) at config C5's shapes (32 clips x 214 steps x 1024 features, E = 100, V = 254, 20-token captions, beam 5),
 H = 512 beside H = 256, which runs the kernels it always ran.  Same box, the widths alternating, --reps runs each; medians and every
 run are kept.  No parent-commit number exists for H = 512: the parent refuses the shape.
@@ -118,7 +118,7 @@ def kernel_stats(d):
         if "wide_kernel<" not in name:
             continue
         kern = name.split("::")[-1].split("(")[0]
-        g = 3 if ("gru" in kern or kern.startswith("rnn_recurrent_wide_kernel<3")) else 4
+        g = int(kern.split("<")[1].split(",")[0])              # rnn_recurrent_wide_kernel<G, NB> / rnn_bptt_wide_kernel<G, NB>
         avg_us = float(row["AverageNs"]) / 1e3
         per_step_us = avg_us / T
         out.append({"kernel": kern, "hidden": 512, "launches": int(row["Calls"]), "average_us_per_launch": round(avg_us, 1),

@@ -391,8 +391,7 @@ static int head_step(tn_head *h, const float *x, const int32_t *rows, const int3
   // backward
   TN_TRY(launch_dense_bwd(h->dlog, h->pooled, w + h->o_wd, B, C, 2 * H, g + h->o_wd, g + h->o_bd, h->dpool, s));
   TN_TRY(launch_scatter_pool_grad(h->dpool, h->arg, B, T, 2 * H, h->dseq, s));
-  if (lstm) TN_TRY(launch_lstm_train_bwd(h->seq, h->gates, h->dseq, w + h->o_wh, h->dgi, h->hprev, B, T, H, s));
-  else TN_TRY(launch_gru_train_bwd(h->seq, h->gates, h->dseq, w + h->o_wh, h->dgi, h->dgh, h->hprev, B, T, H, s));
+  TN_TRY(launch_rnn_bptt(h->G, h->seq, h->gates, h->dseq, w + h->o_wh, h->dgi, h->dgh, h->hprev, B, T, H, s));
   const float *dgh = lstm ? h->dgi : h->dgh;   // LSTM: one pre-activation gradient feeds both branches
   if (rows) TN_TRY(launch_gemm_tn_f32_rows(h->dgi, 2 * GH, h->feats, h->feat_ld, rows, h->feat_rows, g + h->o_wi, F, 2 * GH, F, M, s));
   else TN_TRY(launch_gemm_tn_f32(h->dgi, 2 * GH, x, F, g + h->o_wi, F, 2 * GH, F, M, s));      // dW_ih = dGI^T X

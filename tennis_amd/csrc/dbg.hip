@@ -610,7 +610,7 @@ extern "C" int tn_dbg_grad_sumsq(tn_ctx *ctx, const float *dev, int64_t n, const
   return TN_OK;
 }
 
-// The recurrent kernels' dispatch policy (rnn.h rnn_route: what launch_rnn_recurrent and train.hip's BPTT launchers both follow) for a
+// The recurrent kernels' dispatch policy (rnn.h rnn_route: what launch_rnn_recurrent and rnn_bptt.hip's launch_rnn_bptt both follow) for a
 // shape; host arithmetic only, no device is touched
 extern "C" int tn_dbg_rnn_route(int gates, int B, int H, int dirs, int *nb, int *kr, int *big) {
   TN_REQUIRE(nb && kr && big, "tn_dbg_rnn_route: null argument");

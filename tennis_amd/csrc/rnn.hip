@@ -24,6 +24,40 @@ namespace {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// The cell phase of one step for one (batch row, unit u): from the unit's G input pre-activations gq (i2h + b_i2h) and the row's h2h
+// pre-activations q [G*H] (LDS) to the new state in *h (LSTM: and *c), the emitted *out, and - save non-null - the record BPTT reads,
+// row srow of [dirs][B*T][(G+1)*H]: GRU r | z | n | (W_hn h + b_hn), LSTM i | f | g | o | c_t.
+template <int G>
+__device__ __forceinline__ void rnn_cell_forward(const float (&gq)[G], const float *q, int H, int u, float *h, float *c,
+                                                 float *__restrict__ save, long srow, float *__restrict__ out) {
+#pragma clang fp contract(off)   // the roundings below are the contract: a product is fused where fmaf says so and nowhere else
+  float hn;
+  if constexpr (G == 3) {
+    const float r = sigmoidf_(gq[0] + q[u]);
+    const float z = sigmoidf_(gq[1] + q[H + u]);
+    const float n = tanhf(fmaf(r, q[2 * H + u], gq[2]));
+    hn = fmaf(1.f - z, n, z * *h);
+    if (save) {
+      float *sv = save + srow * (4 * H);
+      sv[u] = r; sv[H + u] = z; sv[2 * H + u] = n; sv[3 * H + u] = q[2 * H + u];
+    }
+  } else {
+    const float ig = sigmoidf_(gq[0] + q[u]);
+    const float fg = sigmoidf_(gq[1] + q[H + u]);
+    const float gg = tanhf(gq[2] + q[2 * H + u]);
+    const float og = sigmoidf_(gq[3] + q[3 * H + u]);
+    const float c2 = fmaf(ig, gg, fg * *c);
+    *c = c2;
+    hn = og * tanhf(c2);
+    if (save) {
+      float *sv = save + srow * (5 * H);
+      sv[u] = ig; sv[H + u] = fg; sv[2 * H + u] = gg; sv[3 * H + u] = og; sv[4 * H + u] = c2;
+    }
+  }
+  *h = hn;
+  *out = hn;
+}
+
 // One workgroup = one direction x NB batch rows, all T steps; thread j owns gate row j of W_hh.
 //   * Per step a CU needs 4*G*H*H bytes of W_hh: at 64 B/clk of L1 fill that stream alone costs as much as the
 //     arithmetic, so the first KR k-values of the thread's weight column live in REGISTERS for the whole sequence
@@ -40,7 +74,7 @@ __global__ __launch_bounds__(MAXT) void rnn_recurrent_kernel(
     const int32_t *__restrict__ valid_len,   // [B] or null
     float *__restrict__ seq, int ldo,        // [B*T][dirs*H]
     float *__restrict__ h_last, float *__restrict__ c_last,  // [dirs][B][H]
-    float *__restrict__ save,                // [dirs][B*T][(G+1)*H] or null: what BPTT needs (train.hip)
+    float *__restrict__ save,                // [dirs][B*T][(G+1)*H] or null: what BPTT needs (rnn_bptt.hip)
     int B, int T, int H) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int GH = G * H;
@@ -66,46 +100,7 @@ __global__ __launch_bounds__(MAXT) void rnn_recurrent_kernel(
     float acc[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) acc[b] = bj;
-#pragma unroll
-    for (int k = 0; k < KR; k += 4) {
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const float4 hv = *(const float4 *)(hs + b * H + k);
-        acc[b] = fmaf(wr[k + 0], hv.x, acc[b]);
-        acc[b] = fmaf(wr[k + 1], hv.y, acc[b]);
-        acc[b] = fmaf(wr[k + 2], hv.z, acc[b]);
-        acc[b] = fmaf(wr[k + 3], hv.w, acc[b]);
-      }
-    }
-    int k = KR;
-    for (; k + 16 <= H; k += 16) {
-      float w[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) w[i] = wcol[(long)(k + i) * GH];
-#pragma unroll
-      for (int i = 0; i < 16; i += 4) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const float4 hv = *(const float4 *)(hs + b * H + k + i);
-          acc[b] = fmaf(w[i + 0], hv.x, acc[b]);
-          acc[b] = fmaf(w[i + 1], hv.y, acc[b]);
-          acc[b] = fmaf(w[i + 2], hv.z, acc[b]);
-          acc[b] = fmaf(w[i + 3], hv.w, acc[b]);
-        }
-      }
-    }
-    for (; k < H; k += 4) {
-      const float w0 = wcol[(long)(k + 0) * GH], w1 = wcol[(long)(k + 1) * GH];
-      const float w2 = wcol[(long)(k + 2) * GH], w3 = wcol[(long)(k + 3) * GH];
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const float4 hv = *(const float4 *)(hs + b * H + k);
-        acc[b] = fmaf(w0, hv.x, acc[b]);
-        acc[b] = fmaf(w1, hv.y, acc[b]);
-        acc[b] = fmaf(w2, hv.z, acc[b]);
-        acc[b] = fmaf(w3, hv.w, acc[b]);
-      }
-    }
+    rnn_dot_stream<NB, KR>(acc, wr, wcol, GH, hs, H, H);
 #pragma unroll
     for (int b = 0; b < NB; ++b) gh[b * GH + j] = acc[b];
     __syncthreads();
@@ -117,32 +112,11 @@ __global__ __launch_bounds__(MAXT) void rnn_recurrent_kernel(
       if (s >= vlen) continue;
       const int ti = dir ? (vlen - 1 - s) : s;
       const float *g = gi + ((long)bg * T + ti) * ldgi + dir * GH;
-      const float *q = gh + b * GH;
-      float hn;
-      if (G == 3) {
-        const float r = sigmoidf_(g[u] + q[u]);
-        const float z = sigmoidf_(g[H + u] + q[H + u]);
-        const float n = tanhf(g[2 * H + u] + r * q[2 * H + u]);
-        hn = (1.f - z) * n + z * hs[idx];
-        if (save) {
-          float *sv = save + ((long)dir * B * T + (long)bg * T + ti) * (4 * H);
-          sv[u] = r; sv[H + u] = z; sv[2 * H + u] = n; sv[3 * H + u] = q[2 * H + u];
-        }
-      } else {
-        const float ig = sigmoidf_(g[u] + q[u]);
-        const float fg = sigmoidf_(g[H + u] + q[H + u]);
-        const float gg = tanhf(g[2 * H + u] + q[2 * H + u]);
-        const float og = sigmoidf_(g[3 * H + u] + q[3 * H + u]);
-        const float c2 = fg * cs[idx] + ig * gg;
-        cs[idx] = c2;
-        hn = og * tanhf(c2);
-        if (save) {
-          float *sv = save + ((long)dir * B * T + (long)bg * T + ti) * (5 * H);
-          sv[u] = ig; sv[H + u] = fg; sv[2 * H + u] = gg; sv[3 * H + u] = og; sv[4 * H + u] = c2;
-        }
-      }
-      hs[idx] = hn;
-      seq[((long)bg * T + ti) * ldo + dir * H + u] = hn;
+      float gq[G];
+#pragma unroll
+      for (int e = 0; e < G; ++e) gq[e] = g[e * H + u];
+      rnn_cell_forward<G>(gq, gh + b * GH, H, u, hs + idx, cs + idx, save, (long)dir * B * T + (long)bg * T + ti,
+                          seq + ((long)bg * T + ti) * ldo + dir * H + u);
     }
     __syncthreads();
   }
@@ -205,34 +179,9 @@ __global__ __launch_bounds__(MAXT) void rnn_recurrent_big_kernel(
     const float acc = rnn_dot_big<KR, KL>(bj, wr, wl, GH, j, wcol, GH, hs, H, lane4);
     gh[j] = acc;
     __syncthreads();
-    if (live) {
-      const int u = j;
-      float hn;
-      if (G == 3) {
-        const float r = sigmoidf_(gq[0] + gh[u]);
-        const float z = sigmoidf_(gq[1] + gh[H + u]);
-        const float n = tanhf(gq[2] + r * gh[2 * H + u]);
-        hn = (1.f - z) * n + z * hs[u];
-        if (save) {
-          float *sv = save + ((long)dir * B * T + (long)bg * T + ti) * (4 * H);
-          sv[u] = r; sv[H + u] = z; sv[2 * H + u] = n; sv[3 * H + u] = gh[2 * H + u];
-        }
-      } else {
-        const float ig = sigmoidf_(gq[0] + gh[u]);
-        const float fg = sigmoidf_(gq[1] + gh[H + u]);
-        const float gg = tanhf(gq[2] + gh[2 * H + u]);
-        const float og = sigmoidf_(gq[G - 1] + gh[3 * H + u]);
-        const float c2 = fg * cs[u] + ig * gg;
-        cs[u] = c2;
-        hn = og * tanhf(c2);
-        if (save) {
-          float *sv = save + ((long)dir * B * T + (long)bg * T + ti) * (5 * H);
-          sv[u] = ig; sv[H + u] = fg; sv[2 * H + u] = gg; sv[3 * H + u] = og; sv[4 * H + u] = c2;
-        }
-      }
-      hs[u] = hn;
-      seq[((long)bg * T + ti) * ldo + dir * H + u] = hn;
-    }
+    if (live)
+      rnn_cell_forward<G>(gq, gh, H, j, hs + j, cs + j, save, (long)dir * B * T + (long)bg * T + ti,
+                          seq + ((long)bg * T + ti) * ldo + dir * H + j);
     __syncthreads();
   }
   if (j < H) {
@@ -284,46 +233,7 @@ __global__ __launch_bounds__(1024) void rnn_recurrent_wide_kernel(
     for (int r = 0; r < 2; ++r)
 #pragma unroll
       for (int b = 0; b < NB; ++b) acc[r][b] = bj[r];
-    int k = 0;
-    for (; k + 16 <= H; k += 16) {
-      float w[2][16];
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) w[r][i] = wcol[r][(long)(k + i) * GH];
-#pragma unroll
-      for (int i = 0; i < 16; i += 4) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const float4 hv = *(const float4 *)(hs + b * H + k + i);
-#pragma unroll
-          for (int r = 0; r < 2; ++r) {
-            acc[r][b] = fmaf(w[r][i + 0], hv.x, acc[r][b]);
-            acc[r][b] = fmaf(w[r][i + 1], hv.y, acc[r][b]);
-            acc[r][b] = fmaf(w[r][i + 2], hv.z, acc[r][b]);
-            acc[r][b] = fmaf(w[r][i + 3], hv.w, acc[r][b]);
-          }
-        }
-      }
-    }
-    for (; k < H; k += 4) {
-      float w[2][4];
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[r][i] = wcol[r][(long)(k + i) * GH];
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const float4 hv = *(const float4 *)(hs + b * H + k);
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          acc[r][b] = fmaf(w[r][0], hv.x, acc[r][b]);
-          acc[r][b] = fmaf(w[r][1], hv.y, acc[r][b]);
-          acc[r][b] = fmaf(w[r][2], hv.z, acc[r][b]);
-          acc[r][b] = fmaf(w[r][3], hv.w, acc[r][b]);
-        }
-      }
-    }
+    rnn_dot_stream2_shared<NB>(acc, wcol, GH, hs, H, H);
 #pragma unroll
     for (int r = 0; r < 2; ++r)
       if (own[r]) {
@@ -339,32 +249,11 @@ __global__ __launch_bounds__(1024) void rnn_recurrent_wide_kernel(
       if (s >= vlen) continue;
       const int ti = dir ? (vlen - 1 - s) : s;
       const float *g = gi + ((long)bg * T + ti) * ldgi + dir * GH;
-      const float *q = gh + b * GH;
-      float hn;
-      if (G == 3) {
-        const float r = sigmoidf_(g[u] + q[u]);
-        const float z = sigmoidf_(g[H + u] + q[H + u]);
-        const float n = tanhf(g[2 * H + u] + r * q[2 * H + u]);
-        hn = (1.f - z) * n + z * hs[idx];
-        if (save) {
-          float *sv = save + ((long)dir * B * T + (long)bg * T + ti) * (4 * H);
-          sv[u] = r; sv[H + u] = z; sv[2 * H + u] = n; sv[3 * H + u] = q[2 * H + u];
-        }
-      } else {
-        const float ig = sigmoidf_(g[u] + q[u]);
-        const float fg = sigmoidf_(g[H + u] + q[H + u]);
-        const float gg = tanhf(g[2 * H + u] + q[2 * H + u]);
-        const float og = sigmoidf_(g[3 * H + u] + q[3 * H + u]);
-        const float c2 = fg * cs[idx] + ig * gg;
-        cs[idx] = c2;
-        hn = og * tanhf(c2);
-        if (save) {
-          float *sv = save + ((long)dir * B * T + (long)bg * T + ti) * (5 * H);
-          sv[u] = ig; sv[H + u] = fg; sv[2 * H + u] = gg; sv[3 * H + u] = og; sv[4 * H + u] = c2;
-        }
-      }
-      hs[idx] = hn;
-      seq[((long)bg * T + ti) * ldo + dir * H + u] = hn;
+      float gq[G];
+#pragma unroll
+      for (int e = 0; e < G; ++e) gq[e] = g[e * H + u];
+      rnn_cell_forward<G>(gq, gh + b * GH, H, u, hs + idx, cs + idx, save, (long)dir * B * T + (long)bg * T + ti,
+                          seq + ((long)bg * T + ti) * ldo + dir * H + u);
     }
     __syncthreads();
   }
@@ -413,66 +302,47 @@ static std::atomic<long> g_rnn_wide_launches{0};
 void rnn_count_wide_launch() { g_rnn_wide_launches.fetch_add(1, std::memory_order_relaxed); }
 long rnn_wide_launches() { return g_rnn_wide_launches.load(std::memory_order_relaxed); }
 
+template <int G>
+static int rnn_recurrent_launch(const float *gi, int ldgi, const float *whT, const float *bh, const int32_t *valid_len, float *seq,
+                                int ldo, float *h_last, float *c_last, int B, int T, int H, int dirs, hipStream_t s, float *save) {
+#define TN_RNN_LAUNCH(KERNEL, GRID, BLOCK, LDS) \
+  hipLaunchKernelGGL((KERNEL), GRID, BLOCK, LDS, s, gi, ldgi, whT, bh, valid_len, seq, ldo, h_last, c_last, save, B, T, H)
+  if (rnn_takes_wide(G, H)) {   // two gate rows per thread (rnn.h rnn_wide_route)
+    const tn_rnn_wide_route wr = rnn_wide_route(G, B, H, dirs);
+    const dim3 wgrid((B + wr.nb - 1) / wr.nb, dirs), wblock(wr.threads);
+    // (the forward kernel's LDS stays below the 64 KiB a launch may ask for unraised: 54 KiB at GRU H = 680, four rows)
+    if (wr.nb == 4) TN_RNN_LAUNCH((rnn_recurrent_wide_kernel<G, 4>), wgrid, wblock, wr.lds_fwd);
+    else TN_RNN_LAUNCH((rnn_recurrent_wide_kernel<G, 1>), wgrid, wblock, wr.lds_fwd);
+    rnn_count_wide_launch();
+    TN_HIP_CHECK(hipGetLastError());
+    return TN_OK;
+  }
+  const tn_rnn_route route = rnn_route(G, B, H, dirs);   // rows per workgroup / register-resident prefix / big form (rnn.h)
+  const dim3 grid((B + route.nb - 1) / route.nb, dirs), block(G * H);
+  if (route.big) {   // one row per workgroup and a column that does not fit the registers (H = 256): registers + LDS + stream, h through DPP
+    constexpr tn_rnn_big_split sp = rnn_big_split(G);
+    TN_SET_ATTR_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void *)rnn_recurrent_big_kernel<G, sp.kr, sp.kl, sp.threads>,
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    TN_RNN_LAUNCH((rnn_recurrent_big_kernel<G, sp.kr, sp.kl, sp.threads>), grid, block, route.lds_fwd);
+  }
+  // (register-resident weights only with one row per workgroup: with four the unrolled prefix spills)
+  else if (route.nb == 4) TN_RNN_LAUNCH((rnn_recurrent_kernel<G, 4, 0, 1024>), grid, block, route.lds_fwd);
+  else if (route.kr == 128) TN_RNN_LAUNCH((rnn_recurrent_kernel<G, 1, 128, 512>), grid, block, route.lds_fwd);
+  else if (route.kr == 96) TN_RNN_LAUNCH((rnn_recurrent_kernel<G, 1, 96, 768>), grid, block, route.lds_fwd);
+  else if (route.kr == 64) TN_RNN_LAUNCH((rnn_recurrent_kernel<G, 1, 64, 1024>), grid, block, route.lds_fwd);
+  else TN_RNN_LAUNCH((rnn_recurrent_kernel<G, 1, 0, 1024>), grid, block, route.lds_fwd);
+#undef TN_RNN_LAUNCH
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+
 int launch_rnn_recurrent(int gates, const float *gi, int ldgi, const float *whT, const float *bh,
                          const int32_t *valid_len, float *seq, int ldo, float *h_last, float *c_last, int B, int T,
                          int H, int dirs, hipStream_t s, float *save) {
   TN_REQUIRE(gates == 3 || gates == 4, "rnn: gates must be 3 or 4");
   TN_REQUIRE(H > 0 && gates * H <= 2048 && H % 4 == 0, "rnn: gates*hidden must be <= 2048 and hidden % 4 == 0");
-  if (rnn_takes_wide(gates, H)) {   // two gate rows per thread (rnn.h rnn_wide_route)
-    const tn_rnn_wide_route wr = rnn_wide_route(gates, B, H, dirs);
-    const dim3 wgrid((B + wr.nb - 1) / wr.nb, dirs), wblock(wr.threads);
-    // (the forward kernel's LDS stays below the 64 KiB a launch may ask for unraised: 54 KiB at GRU H = 680, four rows)
-#define TN_RNN_WIDE(G_, NB_)                                                                                              \
-  hipLaunchKernelGGL((rnn_recurrent_wide_kernel<G_, NB_>), wgrid, wblock, wr.lds_fwd, s, gi, ldgi, whT, bh, valid_len, seq, \
-                     ldo, h_last, c_last, save, B, T, H)
-    if (gates == 3) { if (wr.nb == 4) TN_RNN_WIDE(3, 4); else TN_RNN_WIDE(3, 1); }
-    else { if (wr.nb == 4) TN_RNN_WIDE(4, 4); else TN_RNN_WIDE(4, 1); }
-#undef TN_RNN_WIDE
-    rnn_count_wide_launch();
-    TN_HIP_CHECK(hipGetLastError());
-    return TN_OK;
-  }
-  const int threads = gates * H;
-  const tn_rnn_route route = rnn_route(gates, B, H, dirs);   // rows per workgroup / register-resident prefix / big form (rnn.h)
-  const int nb = route.nb, kr = route.kr;
-  const dim3 grid((B + nb - 1) / nb, dirs), block(threads);
-  const size_t lds = (size_t)(nb * H * 2 + nb * gates * H) * sizeof(float);
-#define TN_RNN_LAUNCH(G_, NB_, KR_, MT_)                                                                               \
-  hipLaunchKernelGGL((rnn_recurrent_kernel<G_, NB_, KR_, MT_>), grid, block, lds, s, gi, ldgi, whT, bh, valid_len, seq, \
-                     ldo, h_last, c_last, save, B, T, H)
-#define TN_RNN_PICK(G_, NB_)                                   \
-  do {                                                         \
-    if (kr == 128) TN_RNN_LAUNCH(G_, NB_, 128, 512);           \
-    else if (kr == 96) TN_RNN_LAUNCH(G_, NB_, 96, 768);        \
-    else if (kr == 64) TN_RNN_LAUNCH(G_, NB_, 64, 1024);       \
-    else TN_RNN_LAUNCH(G_, NB_, 0, 1024);                      \
-  } while (0)
-  // one row per workgroup and a column that does not fit the registers (H = 256): registers + LDS + stream, h through DPP
-  if (route.big) {
-    constexpr int KR3 = 112, KL3 = 48, KR4 = 64, KL4 = 32;
-    const int kl = gates == 3 ? KL3 : KL4;
-    const size_t lds2 = (size_t)(2 * H + gates * H + kl * gates * H) * sizeof(float);
-    if (gates == 3) {
-      TN_SET_ATTR_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void *)rnn_recurrent_big_kernel<3, KR3, KL3, 768>,
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      hipLaunchKernelGGL((rnn_recurrent_big_kernel<3, KR3, KL3, 768>), grid, block, lds2, s, gi, ldgi, whT, bh, valid_len, seq, ldo, h_last,
-                         c_last, save, B, T, H);
-    } else {
-      TN_SET_ATTR_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void *)rnn_recurrent_big_kernel<4, KR4, KL4, 1024>,
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      hipLaunchKernelGGL((rnn_recurrent_big_kernel<4, KR4, KL4, 1024>), grid, block, lds2, s, gi, ldgi, whT, bh, valid_len, seq, ldo, h_last,
-                         c_last, save, B, T, H);
-    }
-    TN_HIP_CHECK(hipGetLastError());
-    return TN_OK;
-  }
-  // (register-resident weights only with one row per workgroup: with four the unrolled prefix spills)
-  if (gates == 3) { if (nb == 4) TN_RNN_LAUNCH(3, 4, 0, 1024); else TN_RNN_PICK(3, 1); }
-  else { if (nb == 4) TN_RNN_LAUNCH(4, 4, 0, 1024); else TN_RNN_PICK(4, 1); }
-#undef TN_RNN_PICK
-#undef TN_RNN_LAUNCH
-  TN_HIP_CHECK(hipGetLastError());
-  return TN_OK;
+  return gates == 3 ? rnn_recurrent_launch<3>(gi, ldgi, whT, bh, valid_len, seq, ldo, h_last, c_last, B, T, H, dirs, s, save)
+                    : rnn_recurrent_launch<4>(gi, ldgi, whT, bh, valid_len, seq, ldo, h_last, c_last, B, T, H, dirs, s, save);
 }
 
 int launch_temporal_pool(const float *x, int B, int T, int F, int kind, float *y, hipStream_t s) {

@@ -11,12 +11,12 @@ int launch_softmax_ce(const float *logits, const int32_t *labels, int B, int C, 
 int launch_dense_bwd(const float *dlogits, const float *pooled, const float *wd, int B, int C, int K, float *dwd,
                      float *dbd, float *dpooled, hipStream_t s);
 int launch_scatter_pool_grad(const float *dpooled, const int32_t *arg, int B, int T, int F, float *dseq, hipStream_t s);
-int launch_gru_train_bwd(const float *seq, const float *gates, const float *dseq, const float *wh, float *dgi,
-                         float *dgh, float *hprev, int B, int T, int H, hipStream_t s, int dirs = 2,
-                         const int32_t *valid_len = nullptr, const float *dh_last = nullptr);
-int launch_lstm_train_bwd(const float *seq, const float *gates, const float *dseq, const float *wh, float *dgi,
-                          float *hprev, int B, int T, int H, hipStream_t s, int dirs = 2,
-                          const int32_t *valid_len = nullptr, const float *dh_last = nullptr, const float *dc_last = nullptr);
+// BPTT of launch_rnn_recurrent's recurrence from its seq and save (rnn_bptt.hip): dgi [B*T][dirs*gates*H], hprev [dirs][B*T][H]; GRU
+// also dgh (its candidate block differs from dgi's), LSTM ignores dgh - one pre-activation gradient feeds both branches.  valid_len
+// [B] or null: steps >= valid_len never ran; dh_last / dc_last [dirs][B][H] or null: d loss / d final state (GRU ignores dc_last).
+int launch_rnn_bptt(int gates, const float *seq, const float *save, const float *dseq, const float *wh, float *dgi, float *dgh,
+                    float *hprev, int B, int T, int H, hipStream_t s, int dirs = 2, const int32_t *valid_len = nullptr,
+                    const float *dh_last = nullptr, const float *dc_last = nullptr);
 int launch_gemm_tn_f32(const float *A, int lda, const float *Bm, int ldb, float *Cm, int ldc, int M, int N, int K,
                        hipStream_t s, float *workspace = nullptr, long workspace_floats = 0);   // workspace: enables split-K
 // ... with B -> relu(B * bsc[n] + bsh[n]) applied while the operand is staged

@@ -4,18 +4,13 @@
 // trainer.step(batch_size)) with models/vision/definitions.py:94-110 as the model.  fp32 throughout.
 //
 // The forward recurrence is rnn.hip's persistent kernel with its `save` output (r, z, n and the h2h candidate term per
-// step; LSTM: i, f, g, o, c); backward walks the steps in the
-// reverse of each direction's own order inside one persistent workgroup per (direction, 4 batch rows), the
-// weight gradients are three transposed GEMMs over all B*T rows afterwards.
+// step; LSTM: i, f, g, o, c); its BPTT is rnn_bptt.hip; the weight gradients are three transposed GEMMs over all
+// B*T rows afterwards.  This unit holds the rest of the step: pooling, cross-entropy, the dense backward, the GEMMs, the
+// optimisers and clipping.
 #include "common.h"
 #include "train.h"
-#include "rnn.h"
-#include "rnn_dot.h"
 
 namespace {
-
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 __global__ void pool_max_arg_kernel(const float *__restrict__ x, int B, int T, int F, float *__restrict__ y,
                                     int32_t *__restrict__ arg) {
@@ -81,443 +76,6 @@ __global__ void scatter_pool_grad_kernel(const float *__restrict__ dpooled, cons
   const long bt = id / F;
   const int t = (int)(bt % T), b = (int)(bt / T);
   dseq[id] = arg[(long)b * F + f] == t ? dpooled[(long)b * F + f] : 0.f;
-}
-
-// BPTT of one direction for NB batch rows: thread j = (gate block g, unit u).  As in rnn.hip's forward kernel the
-// first KR values of the thread's W_hh column (loop-invariant over the steps) stay in registers, the rest is streamed
-// 16 loads at a time, and small batches run one row per workgroup.
-template <int NB, int KR, int MAXT, int KL = 0>   // KL > 0 (NB = 1, H % 16 == 0): KL more weights in LDS, x through DPP (rnn_dot.h)
-__global__ __launch_bounds__(MAXT) void gru_train_bwd_kernel(const float *__restrict__ seq, const float *__restrict__ gates,
-                                     const float *__restrict__ dseq, const float *__restrict__ wh,   // [dirs][3H][H]
-                                     float *__restrict__ dgi, float *__restrict__ dgh,               // [B*T][dirs*3H]
-                                     float *__restrict__ hprev,                                      // [dirs][B*T][H]
-                                     int B, int T, int H, int dirs,
-                                     const int32_t *__restrict__ valid_len,    // [B] or null: steps >= valid_len never ran
-                                     const float *__restrict__ dh_last) {      // [dirs][B][H] or null: d loss / d final state
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int GH = 3 * H;
-  float *dh = lds;                  // [NB][H]   gradient flowing into h_t from the later step
-  float *dgs = dh + NB * H;         // [NB][3H]  this step's h2h pre-activation gradients
-  float *part = dgs + NB * GH;      // [NB][3][H]
-  float *wl = part + NB * GH;       // [KL/4][3H][4] (KL > 0)
-  const int j = threadIdx.x, dir = blockIdx.y, b0 = blockIdx.x * NB;
-  const int g = j / H, u = j - g * H;
-  const float *wrow = wh + (long)dir * GH * H + (long)g * H * H + u;   // W_hh[g*H + jj][u], jj = 0..H-1
-  float wr[KR > 0 ? KR : 1];
-#pragma unroll
-  for (int k = 0; k < KR; ++k) wr[k] = wrow[(long)k * H];
-  if constexpr (KL > 0) rnn_dot_fill_lds<KR, KL>(wl, GH, j, wrow, H);
-  for (int i = j; i < NB * H; i += GH) dh[i] = 0.f;
-  __syncthreads();
-  for (int s = T - 1; s >= 0; --s) {          // reverse of the direction's own walking order
-    for (int idx = j; idx < NB * H; idx += GH) {
-      const int b = idx / H, uu = idx - b * H, bg = b0 + b;
-      float d_r = 0.f, d_z = 0.f, d_n = 0.f, d_nr = 0.f, dhp = 0.f, hp = 0.f;
-      const int vlen = bg < B ? (valid_len ? valid_len[bg] : T) : 0;
-      if (s < vlen) {
-        const int t = dir ? vlen - 1 - s : s;       // the reverse direction starts at the row's last valid step
-        const int tp = dir ? t + 1 : t - 1;         // where h_prev of this step was emitted
-        const long row = (long)bg * T + t;
-        const float *sv = gates + ((long)dir * B * T + row) * (4 * H);
-        const float r = sv[uu], z = sv[H + uu], n = sv[2 * H + uu], ghn = sv[3 * H + uu];
-        hp = s > 0 ? seq[((long)bg * T + tp) * (dirs * H) + dir * H + uu] : 0.f;
-        const float carry = (s == vlen - 1 && dh_last) ? dh_last[((long)dir * B + bg) * H + uu] : dh[idx];
-        const float dht = carry + dseq[row * (dirs * H) + dir * H + uu];
-        const float dn = dht * (1.f - z), dz = dht * (hp - n);
-        dhp = dht * z;
-        d_n = dn * (1.f - n * n);
-        d_z = dz * z * (1.f - z);
-        d_r = d_n * ghn * r * (1.f - r);
-        d_nr = d_n * r;
-        float *o1 = dgi + row * (dirs * GH) + dir * GH, *o2 = dgh + row * (dirs * GH) + dir * GH;
-        o1[uu] = d_r; o1[H + uu] = d_z; o1[2 * H + uu] = d_n;
-        o2[uu] = d_r; o2[H + uu] = d_z; o2[2 * H + uu] = d_nr;
-        hprev[((long)dir * B * T + row) * H + uu] = hp;
-      }
-      dgs[b * GH + uu] = d_r; dgs[b * GH + H + uu] = d_z; dgs[b * GH + 2 * H + uu] = d_nr;
-      dh[idx] = dhp;
-    }
-    __syncthreads();
-    float acc[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) acc[b] = 0.f;
-    if constexpr (KL > 0) {
-      static_assert(KL == 0 || NB == 1, "the LDS share is built for one row per workgroup");
-      acc[0] = rnn_dot_big<KR, KL>(0.f, wr, wl, GH, j, wrow, H, dgs + g * H, H, (j & 3) * 4);
-    } else {
-#pragma unroll
-    for (int jj = 0; jj < KR; jj += 4) {
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const float4 dv = *(const float4 *)(dgs + b * GH + g * H + jj);
-        acc[b] = fmaf(wr[jj + 0], dv.x, acc[b]);
-        acc[b] = fmaf(wr[jj + 1], dv.y, acc[b]);
-        acc[b] = fmaf(wr[jj + 2], dv.z, acc[b]);
-        acc[b] = fmaf(wr[jj + 3], dv.w, acc[b]);
-      }
-    }
-    int jj = KR;
-    for (; jj + 16 <= H; jj += 16) {
-      float w[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) w[i] = wrow[(long)(jj + i) * H];
-#pragma unroll
-      for (int i = 0; i < 16; i += 4) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const float4 dv = *(const float4 *)(dgs + b * GH + g * H + jj + i);
-          acc[b] = fmaf(w[i + 0], dv.x, acc[b]);
-          acc[b] = fmaf(w[i + 1], dv.y, acc[b]);
-          acc[b] = fmaf(w[i + 2], dv.z, acc[b]);
-          acc[b] = fmaf(w[i + 3], dv.w, acc[b]);
-        }
-      }
-    }
-    for (; jj < H; jj += 4) {
-      const float w0 = wrow[(long)(jj + 0) * H], w1 = wrow[(long)(jj + 1) * H];
-      const float w2 = wrow[(long)(jj + 2) * H], w3 = wrow[(long)(jj + 3) * H];
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const float4 dv = *(const float4 *)(dgs + b * GH + g * H + jj);
-        acc[b] = fmaf(w0, dv.x, acc[b]);
-        acc[b] = fmaf(w1, dv.y, acc[b]);
-        acc[b] = fmaf(w2, dv.z, acc[b]);
-        acc[b] = fmaf(w3, dv.w, acc[b]);
-      }
-    }
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) part[(b * 3 + g) * H + u] = acc[b];
-    __syncthreads();
-    for (int idx = j; idx < NB * H; idx += GH) {
-      const int b = idx / H, uu = idx - b * H;
-      dh[idx] += part[(b * 3 + 0) * H + uu] + part[(b * 3 + 1) * H + uu] + part[(b * 3 + 2) * H + uu];
-    }
-    __syncthreads();
-  }
-}
-
-// ---- LSTM (gate order [i, f, g, o], mx.gluon.rnn.LSTM); saved per step: i | f | g | o | c_t ----
-// BPTT of one LSTM direction for NB batch rows: thread j = (gate block g of 4, unit u).  The pre-activation
-// gradient is the same for the i2h and the h2h branch, so only dgi is written (the caller uses it for both).
-template <int NB, int KR, int MAXT, int KL = 0>   // KL > 0 (NB = 1, H % 16 == 0): KL more weights in LDS, x through DPP (rnn_dot.h)
-__global__ __launch_bounds__(MAXT) void lstm_train_bwd_kernel(const float *__restrict__ seq, const float *__restrict__ gates,
-                                      const float *__restrict__ dseq, const float *__restrict__ wh,   // [dirs][4H][H]
-                                      float *__restrict__ dgi,                                        // [B*T][dirs*4H]
-                                      float *__restrict__ hprev,                                      // [dirs][B*T][H]
-                                      int B, int T, int H, int dirs,
-                                      const int32_t *__restrict__ valid_len,     // [B] or null: steps >= valid_len never ran
-                                      const float *__restrict__ dh_last,         // [dirs][B][H] or null: d loss / d final h
-                                      const float *__restrict__ dc_last) {       // ... / d final c
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int GH = 4 * H;
-  float *dh = lds;                  // [NB][H]   gradient flowing into h_t from the later step
-  float *dc = dh + NB * H;          // [NB][H]   ... into c_t
-  float *dgs = dc + NB * H;         // [NB][4H]  this step's pre-activation gradients
-  float *part = dgs + NB * GH;      // [NB][4][H]
-  float *wl = part + NB * GH;       // [KL/4][4H][4] (KL > 0)
-  const int j = threadIdx.x, dir = blockIdx.y, b0 = blockIdx.x * NB;
-  const int g = j / H, u = j - g * H;
-  const float *wrow = wh + (long)dir * GH * H + (long)g * H * H + u;   // W_hh[g*H + jj][u], jj = 0..H-1
-  float wr[KR > 0 ? KR : 1];
-#pragma unroll
-  for (int k = 0; k < KR; ++k) wr[k] = wrow[(long)k * H];
-  if constexpr (KL > 0) rnn_dot_fill_lds<KR, KL>(wl, GH, j, wrow, H);
-  for (int i = j; i < NB * H; i += GH) { dh[i] = 0.f; dc[i] = 0.f; }
-  __syncthreads();
-  for (int s = T - 1; s >= 0; --s) {
-    for (int idx = j; idx < NB * H; idx += GH) {
-      const int b = idx / H, uu = idx - b * H, bg = b0 + b;
-      float d_i = 0.f, d_f = 0.f, d_g = 0.f, d_o = 0.f, dcp = 0.f;
-      const int vlen = bg < B ? (valid_len ? valid_len[bg] : T) : 0;
-      if (s < vlen) {
-        const int t = dir ? vlen - 1 - s : s;
-        const int tp = dir ? t + 1 : t - 1;
-        const long row = (long)bg * T + t;
-        const float *sv = gates + ((long)dir * B * T + row) * (5 * H);
-        const float ig = sv[uu], fg = sv[H + uu], gg = sv[2 * H + uu], og = sv[3 * H + uu], c2 = sv[4 * H + uu];
-        float hp = 0.f, cp = 0.f;
-        if (s > 0) {
-          const long rp = (long)bg * T + tp;
-          hp = seq[rp * (dirs * H) + dir * H + uu];
-          cp = gates[((long)dir * B * T + rp) * (5 * H) + 4 * H + uu];
-        }
-        const bool lastp = s == vlen - 1;
-        const float tc = tanhf(c2);
-        const float dht = ((lastp && dh_last) ? dh_last[((long)dir * B + bg) * H + uu] : dh[idx]) + dseq[row * (dirs * H) + dir * H + uu];
-        const float dct = ((lastp && dc_last) ? dc_last[((long)dir * B + bg) * H + uu] : dc[idx]) + dht * og * (1.f - tc * tc);
-        d_o = dht * tc * og * (1.f - og);
-        d_i = dct * gg * ig * (1.f - ig);
-        d_f = dct * cp * fg * (1.f - fg);
-        d_g = dct * ig * (1.f - gg * gg);
-        dcp = dct * fg;
-        float *o1 = dgi + row * (dirs * GH) + dir * GH;
-        o1[uu] = d_i; o1[H + uu] = d_f; o1[2 * H + uu] = d_g; o1[3 * H + uu] = d_o;
-        hprev[((long)dir * B * T + row) * H + uu] = hp;
-      }
-      dgs[b * GH + uu] = d_i; dgs[b * GH + H + uu] = d_f; dgs[b * GH + 2 * H + uu] = d_g; dgs[b * GH + 3 * H + uu] = d_o;
-      dc[idx] = dcp;
-    }
-    __syncthreads();
-    float acc[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) acc[b] = 0.f;
-    if constexpr (KL > 0) {
-      static_assert(KL == 0 || NB == 1, "the LDS share is built for one row per workgroup");
-      acc[0] = rnn_dot_big<KR, KL>(0.f, wr, wl, GH, j, wrow, H, dgs + g * H, H, (j & 3) * 4);
-    } else {
-#pragma unroll
-    for (int jj = 0; jj < KR; jj += 4) {
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const float4 dv = *(const float4 *)(dgs + b * GH + g * H + jj);
-        acc[b] = fmaf(wr[jj + 0], dv.x, acc[b]);
-        acc[b] = fmaf(wr[jj + 1], dv.y, acc[b]);
-        acc[b] = fmaf(wr[jj + 2], dv.z, acc[b]);
-        acc[b] = fmaf(wr[jj + 3], dv.w, acc[b]);
-      }
-    }
-    int jj = KR;
-    for (; jj + 16 <= H; jj += 16) {
-      float w[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) w[i] = wrow[(long)(jj + i) * H];
-#pragma unroll
-      for (int i = 0; i < 16; i += 4) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const float4 dv = *(const float4 *)(dgs + b * GH + g * H + jj + i);
-          acc[b] = fmaf(w[i + 0], dv.x, acc[b]);
-          acc[b] = fmaf(w[i + 1], dv.y, acc[b]);
-          acc[b] = fmaf(w[i + 2], dv.z, acc[b]);
-          acc[b] = fmaf(w[i + 3], dv.w, acc[b]);
-        }
-      }
-    }
-    for (; jj < H; jj += 4) {
-      const float w0 = wrow[(long)(jj + 0) * H], w1 = wrow[(long)(jj + 1) * H];
-      const float w2 = wrow[(long)(jj + 2) * H], w3 = wrow[(long)(jj + 3) * H];
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const float4 dv = *(const float4 *)(dgs + b * GH + g * H + jj);
-        acc[b] = fmaf(w0, dv.x, acc[b]);
-        acc[b] = fmaf(w1, dv.y, acc[b]);
-        acc[b] = fmaf(w2, dv.z, acc[b]);
-        acc[b] = fmaf(w3, dv.w, acc[b]);
-      }
-    }
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) part[(b * 4 + g) * H + u] = acc[b];
-    __syncthreads();
-    for (int idx = j; idx < NB * H; idx += GH) {
-      const int b = idx / H, uu = idx - b * H;
-      dh[idx] = part[(b * 4 + 0) * H + uu] + part[(b * 4 + 1) * H + uu] + part[(b * 4 + 2) * H + uu] +
-                part[(b * 4 + 3) * H + uu];
-    }
-    __syncthreads();
-  }
-}
-
-// ---- BPTT for 1024 < gates*H <= 2048: two gate rows per thread (rnn.h rnn_wide_route), as rnn.hip's wide forward kernel ----
-// Thread j owns the rows j and j + blockDim.x of W_hh^T's product; a row past gates*H works on the last row and stores nothing.
-// Both W_hh columns are streamed with 16 values in flight each.  Per row: one accumulator from 0, jj ascending - the sums of the
-// kernels above, bit for bit.
-template <int NB>
-__device__ __forceinline__ void bptt_dot_two_rows(float (&acc)[2][NB], const float *const (&wrow)[2], const int (&gofs)[2],
-                                                  const float *dgs, int GH, int H) {
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) acc[r][b] = 0.f;
-  int jj = 0;
-  for (; jj + 16 <= H; jj += 16) {
-    float w[2][16];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) w[r][i] = wrow[r][(long)(jj + i) * H];
-#pragma unroll
-    for (int i = 0; i < 16; i += 4) {
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const float4 dv = *(const float4 *)(dgs + b * GH + gofs[r] + jj + i);
-          acc[r][b] = fmaf(w[r][i + 0], dv.x, acc[r][b]);
-          acc[r][b] = fmaf(w[r][i + 1], dv.y, acc[r][b]);
-          acc[r][b] = fmaf(w[r][i + 2], dv.z, acc[r][b]);
-          acc[r][b] = fmaf(w[r][i + 3], dv.w, acc[r][b]);
-        }
-      }
-    }
-  }
-  for (; jj < H; jj += 4) {
-    float w[2][4];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[r][i] = wrow[r][(long)(jj + i) * H];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const float4 dv = *(const float4 *)(dgs + b * GH + gofs[r] + jj);
-        acc[r][b] = fmaf(w[r][0], dv.x, acc[r][b]);
-        acc[r][b] = fmaf(w[r][1], dv.y, acc[r][b]);
-        acc[r][b] = fmaf(w[r][2], dv.z, acc[r][b]);
-        acc[r][b] = fmaf(w[r][3], dv.w, acc[r][b]);
-      }
-    }
-  }
-}
-
-// gru_train_bwd_kernel's contract and LDS layout; the element-wise phases are its loops with the block size as stride
-template <int NB>
-__global__ __launch_bounds__(1024) void gru_train_bwd_wide_kernel(const float *__restrict__ seq, const float *__restrict__ gates,
-                                     const float *__restrict__ dseq, const float *__restrict__ wh, float *__restrict__ dgi,
-                                     float *__restrict__ dgh, float *__restrict__ hprev, int B, int T, int H, int dirs,
-                                     const int32_t *__restrict__ valid_len, const float *__restrict__ dh_last) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int GH = 3 * H, nt = blockDim.x;
-  float *dh = lds;                  // [NB][H]
-  float *dgs = dh + NB * H;         // [NB][3H]
-  float *part = dgs + NB * GH;      // [NB][3][H]
-  const int j = threadIdx.x, dir = blockIdx.y, b0 = blockIdx.x * NB;
-  const bool own[2] = {j < GH, j + nt < GH};
-  int gofs[2], pofs[2];             // where the row's gate block starts in dgs; where its sum goes in a batch row's part
-  const float *wrow[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int rr = min(j + r * nt, GH - 1), g = rr / H, u = rr - g * H;
-    gofs[r] = g * H;
-    pofs[r] = rr;                   // (b * 3 + g) * H + u = b * GH + rr
-    wrow[r] = wh + (long)dir * GH * H + (long)g * H * H + u;   // W_hh[g*H + jj][u], jj = 0..H-1
-  }
-  for (int i = j; i < NB * H; i += nt) dh[i] = 0.f;
-  __syncthreads();
-  for (int s = T - 1; s >= 0; --s) {          // reverse of the direction's own walking order
-    for (int idx = j; idx < NB * H; idx += nt) {
-      const int b = idx / H, uu = idx - b * H, bg = b0 + b;
-      float d_r = 0.f, d_z = 0.f, d_n = 0.f, d_nr = 0.f, dhp = 0.f, hp = 0.f;
-      const int vlen = bg < B ? (valid_len ? valid_len[bg] : T) : 0;
-      if (s < vlen) {
-        const int t = dir ? vlen - 1 - s : s;       // the reverse direction starts at the row's last valid step
-        const int tp = dir ? t + 1 : t - 1;         // where h_prev of this step was emitted
-        const long row = (long)bg * T + t;
-        const float *sv = gates + ((long)dir * B * T + row) * (4 * H);
-        const float r = sv[uu], z = sv[H + uu], n = sv[2 * H + uu], ghn = sv[3 * H + uu];
-        hp = s > 0 ? seq[((long)bg * T + tp) * (dirs * H) + dir * H + uu] : 0.f;
-        const float carry = (s == vlen - 1 && dh_last) ? dh_last[((long)dir * B + bg) * H + uu] : dh[idx];
-        const float dht = carry + dseq[row * (dirs * H) + dir * H + uu];
-        const float dn = dht * (1.f - z), dz = dht * (hp - n);
-        dhp = dht * z;
-        d_n = dn * (1.f - n * n);
-        d_z = dz * z * (1.f - z);
-        d_r = d_n * ghn * r * (1.f - r);
-        d_nr = d_n * r;
-        float *o1 = dgi + row * (dirs * GH) + dir * GH, *o2 = dgh + row * (dirs * GH) + dir * GH;
-        o1[uu] = d_r; o1[H + uu] = d_z; o1[2 * H + uu] = d_n;
-        o2[uu] = d_r; o2[H + uu] = d_z; o2[2 * H + uu] = d_nr;
-        hprev[((long)dir * B * T + row) * H + uu] = hp;
-      }
-      dgs[b * GH + uu] = d_r; dgs[b * GH + H + uu] = d_z; dgs[b * GH + 2 * H + uu] = d_nr;
-      dh[idx] = dhp;
-    }
-    __syncthreads();
-    float acc[2][NB];
-    bptt_dot_two_rows<NB>(acc, wrow, gofs, dgs, GH, H);
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-      if (own[r]) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) part[b * GH + pofs[r]] = acc[r][b];
-      }
-    __syncthreads();
-    for (int idx = j; idx < NB * H; idx += nt) {
-      const int b = idx / H, uu = idx - b * H;
-      dh[idx] += part[(b * 3 + 0) * H + uu] + part[(b * 3 + 1) * H + uu] + part[(b * 3 + 2) * H + uu];
-    }
-    __syncthreads();
-  }
-}
-
-// lstm_train_bwd_kernel's contract and LDS layout, two gate rows per thread
-template <int NB>
-__global__ __launch_bounds__(1024) void lstm_train_bwd_wide_kernel(const float *__restrict__ seq, const float *__restrict__ gates,
-                                      const float *__restrict__ dseq, const float *__restrict__ wh, float *__restrict__ dgi,
-                                      float *__restrict__ hprev, int B, int T, int H, int dirs,
-                                      const int32_t *__restrict__ valid_len, const float *__restrict__ dh_last,
-                                      const float *__restrict__ dc_last) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int GH = 4 * H, nt = blockDim.x;
-  float *dh = lds;                  // [NB][H]
-  float *dc = dh + NB * H;          // [NB][H]
-  float *dgs = dc + NB * H;         // [NB][4H]
-  float *part = dgs + NB * GH;      // [NB][4][H]
-  const int j = threadIdx.x, dir = blockIdx.y, b0 = blockIdx.x * NB;
-  const bool own[2] = {j < GH, j + nt < GH};
-  int gofs[2], pofs[2];
-  const float *wrow[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int rr = min(j + r * nt, GH - 1), g = rr / H, u = rr - g * H;
-    gofs[r] = g * H;
-    pofs[r] = rr;                   // (b * 4 + g) * H + u = b * GH + rr
-    wrow[r] = wh + (long)dir * GH * H + (long)g * H * H + u;
-  }
-  for (int i = j; i < NB * H; i += nt) { dh[i] = 0.f; dc[i] = 0.f; }
-  __syncthreads();
-  for (int s = T - 1; s >= 0; --s) {
-    for (int idx = j; idx < NB * H; idx += nt) {
-      const int b = idx / H, uu = idx - b * H, bg = b0 + b;
-      float d_i = 0.f, d_f = 0.f, d_g = 0.f, d_o = 0.f, dcp = 0.f;
-      const int vlen = bg < B ? (valid_len ? valid_len[bg] : T) : 0;
-      if (s < vlen) {
-        const int t = dir ? vlen - 1 - s : s;
-        const int tp = dir ? t + 1 : t - 1;
-        const long row = (long)bg * T + t;
-        const float *sv = gates + ((long)dir * B * T + row) * (5 * H);
-        const float ig = sv[uu], fg = sv[H + uu], gg = sv[2 * H + uu], og = sv[3 * H + uu], c2 = sv[4 * H + uu];
-        float hp = 0.f, cp = 0.f;
-        if (s > 0) {
-          const long rp = (long)bg * T + tp;
-          hp = seq[rp * (dirs * H) + dir * H + uu];
-          cp = gates[((long)dir * B * T + rp) * (5 * H) + 4 * H + uu];
-        }
-        const bool lastp = s == vlen - 1;
-        const float tc = tanhf(c2);
-        const float dht = ((lastp && dh_last) ? dh_last[((long)dir * B + bg) * H + uu] : dh[idx]) + dseq[row * (dirs * H) + dir * H + uu];
-        const float dct = ((lastp && dc_last) ? dc_last[((long)dir * B + bg) * H + uu] : dc[idx]) + dht * og * (1.f - tc * tc);
-        d_o = dht * tc * og * (1.f - og);
-        d_i = dct * gg * ig * (1.f - ig);
-        d_f = dct * cp * fg * (1.f - fg);
-        d_g = dct * ig * (1.f - gg * gg);
-        dcp = dct * fg;
-        float *o1 = dgi + row * (dirs * GH) + dir * GH;
-        o1[uu] = d_i; o1[H + uu] = d_f; o1[2 * H + uu] = d_g; o1[3 * H + uu] = d_o;
-        hprev[((long)dir * B * T + row) * H + uu] = hp;
-      }
-      dgs[b * GH + uu] = d_i; dgs[b * GH + H + uu] = d_f; dgs[b * GH + 2 * H + uu] = d_g; dgs[b * GH + 3 * H + uu] = d_o;
-      dc[idx] = dcp;
-    }
-    __syncthreads();
-    float acc[2][NB];
-    bptt_dot_two_rows<NB>(acc, wrow, gofs, dgs, GH, H);
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-      if (own[r]) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) part[b * GH + pofs[r]] = acc[r][b];
-      }
-    __syncthreads();
-    for (int idx = j; idx < NB * H; idx += nt) {
-      const int b = idx / H, uu = idx - b * H;
-      dh[idx] = part[(b * 4 + 0) * H + uu] + part[(b * 4 + 1) * H + uu] + part[(b * 4 + 2) * H + uu] +
-                part[(b * 4 + 3) * H + uu];
-    }
-    __syncthreads();
-  }
 }
 
 // C[M][N] = A^T B, A [K][lda] (M columns), B [K][ldb] (N columns): the weight gradients dW = dG^T X over all B*T rows.
@@ -845,54 +403,6 @@ int launch_dense_bwd(const float *dlogits, const float *pooled, const float *wd,
 int launch_scatter_pool_grad(const float *dpooled, const int32_t *arg, int B, int T, int F, float *dseq, hipStream_t s) {
   hipLaunchKernelGGL(scatter_pool_grad_kernel, dim3(((long)B * T * F + 255) / 256), dim3(256), 0, s, dpooled, arg, B, T,
                      F, dseq);
-  TN_LAUNCH_CHECK();
-}
-// rows per workgroup / register-resident prefix: rnn_route (rnn.h), the policy of launch_rnn_recurrent, whose `save` these kernels read
-// ... and past gates*hidden = 1024 (or under tn_dbg_rnn_force_wide) rnn_wide_route: two gate rows per thread, WIDE<nb>
-#define TN_BPTT_DISPATCH(KERNEL, WIDE, GATES, DIRS, ...)                                                                \
-  do {                                                                                                            \
-    const int threads = GATES * H;                                                                                \
-    TN_REQUIRE(H > 0 && threads <= 2048 && H % 4 == 0, "train: gates*hidden must be <= 2048 and hidden % 4 == 0"); \
-    if (rnn_takes_wide(GATES, H)) {                                                                               \
-      const tn_rnn_wide_route wr = rnn_wide_route(GATES, B, H, DIRS);                                             \
-      const dim3 wgrid((B + wr.nb - 1) / wr.nb, DIRS), wblock(wr.threads);                                        \
-      if (wr.nb == 4) {          /* 80 KiB at LSTM H = 512: above what a launch may ask for unraised */           \
-        TN_SET_ATTR_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void *)WIDE<4>,                              \
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((WIDE<4>), wgrid, wblock, wr.lds_bwd, s, __VA_ARGS__);                                 \
-      } else {                                                                                                    \
-        hipLaunchKernelGGL((WIDE<1>), wgrid, wblock, wr.lds_bwd, s, __VA_ARGS__);                                 \
-      }                                                                                                           \
-      rnn_count_wide_launch();                                                                                    \
-      break;                                                                                                      \
-    }                                                                                                             \
-    const tn_rnn_route route = rnn_route(GATES, B, H, DIRS);                                                      \
-    const int nb = route.nb, kr = route.kr;                                                                       \
-    const dim3 grid((B + nb - 1) / nb, DIRS), block(threads);                                                     \
-    const size_t lds = (size_t)(nb * H * (GATES == 4 ? 2 : 1) + 2 * nb * GATES * H) * sizeof(float);              \
-    if (route.big) {             /* the column does not fit the registers: registers + LDS + stream (rnn_dot.h) */       \
-      constexpr int KRb = GATES == 3 ? 112 : 64, KLb = GATES == 3 ? 48 : 32, MTb = GATES == 3 ? 768 : 1024;              \
-      const size_t lds2 = lds + (size_t)KLb * GATES * H * sizeof(float);                                                 \
-      TN_SET_ATTR_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void *)KERNEL<1, KRb, MTb, KLb>,                      \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));    \
-      hipLaunchKernelGGL((KERNEL<1, KRb, MTb, KLb>), grid, block, lds2, s, __VA_ARGS__);                                 \
-    } else                                                                                                              \
-    if (nb == 4) hipLaunchKernelGGL((KERNEL<4, 0, 1024>), grid, block, lds, s, __VA_ARGS__);                      \
-    else if (kr == 128) hipLaunchKernelGGL((KERNEL<1, 128, 512>), grid, block, lds, s, __VA_ARGS__);              \
-    else if (kr == 96) hipLaunchKernelGGL((KERNEL<1, 96, 768>), grid, block, lds, s, __VA_ARGS__);                \
-    else if (kr == 64) hipLaunchKernelGGL((KERNEL<1, 64, 1024>), grid, block, lds, s, __VA_ARGS__);               \
-    else hipLaunchKernelGGL((KERNEL<1, 0, 1024>), grid, block, lds, s, __VA_ARGS__);                              \
-  } while (0)
-int launch_gru_train_bwd(const float *seq, const float *gates, const float *dseq, const float *wh, float *dgi,
-                         float *dgh, float *hprev, int B, int T, int H, hipStream_t s, int dirs, const int32_t *valid_len,
-                         const float *dh_last) {
-  TN_BPTT_DISPATCH(gru_train_bwd_kernel, gru_train_bwd_wide_kernel, 3, dirs, seq, gates, dseq, wh, dgi, dgh, hprev, B, T, H, dirs, valid_len, dh_last);
-  TN_LAUNCH_CHECK();
-}
-int launch_lstm_train_bwd(const float *seq, const float *gates, const float *dseq, const float *wh, float *dgi,
-                          float *hprev, int B, int T, int H, hipStream_t s, int dirs, const int32_t *valid_len,
-                          const float *dh_last, const float *dc_last) {
-  TN_BPTT_DISPATCH(lstm_train_bwd_kernel, lstm_train_bwd_wide_kernel, 4, dirs, seq, gates, dseq, wh, dgi, hprev, B, T, H, dirs, valid_len, dh_last, dc_last);
   TN_LAUNCH_CHECK();
 }
 // C (M,N) = A^T B over K rows; bsc / bsh non-null: B -> relu(B * bsc[n] + bsh[n]) on the way in (a BatchNorm + ReLU that is never stored)

@@ -1,5 +1,5 @@
-"""The dispatch policy of the recurrent kernels (csrc/rnn.h rnn_route, followed by launch_rnn_recurrent and by train.hip's BPTT
-launchers) asked through tn_dbg_rnn_route, which touches no device: the training shape tables of tests/tools/rnn_train_shapes.py
+"""The dispatch policy of the recurrent kernels (csrc/rnn.h rnn_route, followed by launch_rnn_recurrent and by rnn_bptt.hip's
+launch_rnn_bptt) asked through tn_dbg_rnn_route, which touches no device: the training shape tables of tests/tools/rnn_train_shapes.py
 reach every instantiation for both cells, and the policy's edges lie where the kernels' launch bounds need them.  No GPU needed."""
 import ctypes as C
 

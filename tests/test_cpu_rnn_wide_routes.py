@@ -1,5 +1,5 @@
-"""The dispatch policy of the wide recurrent kernels (csrc/rnn.h rnn_wide_route, followed by launch_rnn_recurrent and by train.hip's BPTT
-launchers for 1024 < gates*H <= 2048) asked through tn_dbg_rnn_wide_route, which touches no device: what the hook refuses, the launch
+"""The dispatch policy of the wide recurrent kernels (csrc/rnn.h rnn_wide_route, followed by launch_rnn_recurrent and by rnn_bptt.hip's
+launch_rnn_bptt for 1024 < gates*H <= 2048) asked through tn_dbg_rnn_wide_route, which touches no device: what the hook refuses, the launch
 bounds every legal shape keeps, the rows-per-workgroup edges, and that the shape table of tests/tools/rnn_wide_shapes.py reaches every
 code path of the kernels for both cells.  No GPU needed."""
 import ctypes as C

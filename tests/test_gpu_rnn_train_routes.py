@@ -1,5 +1,5 @@
-"""-m gpu: every instantiation of the recurrent training kernels - rnn.hip's forward kernel writing `save`, train.hip's
-gru_train_bwd_kernel / lstm_train_bwd_kernel reading it - against float64, for both cells.  The shapes come from
+"""-m gpu: every instantiation of the recurrent training kernels - rnn.hip's forward kernel writing `save`, rnn_bptt.hip's
+rnn_bptt_kernel reading it - against float64, for both cells.  The shapes come from
 tests/tools/rnn_train_shapes.py, which tests/test_cpu_rnn_routes.py proves to reach every route of the dispatch policy
 (csrc/rnn.h rnn_route): the three prefixes, no prefix, registers + LDS + stream, four rows per workgroup, with the 4-wide tail and the
 16-wide streamed loop behind a prefix, near-full blocks and the padded rows of a last 4-row workgroup.

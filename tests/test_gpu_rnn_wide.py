@@ -1,4 +1,4 @@
-"""-m gpu: the wide recurrent kernels - rnn.hip's rnn_recurrent_wide_kernel, train.hip's gru_ / lstm_train_bwd_wide_kernel: two gate rows per
+"""-m gpu: the wide recurrent kernels - rnn.hip's rnn_recurrent_wide_kernel, rnn_bptt.hip's rnn_bptt_wide_kernel: two gate rows per
 thread, 1024 < gates*H <= 2048 (LSTM up to H = 512, GRU up to H = 680) - against float64, for both cells.  The shapes come from
 tests/tools/rnn_wide_shapes.py, which tests/test_cpu_rnn_wide_routes.py proves to reach every path of the kernels (rows per workgroup
 1 | 4, a full or a ragged second row, with and without the 4-wide tail).

@@ -1,4 +1,4 @@
-"""The training shapes that pin every instantiation of the recurrent kernels (csrc/rnn.hip with `save`, csrc/train.hip's BPTT kernels)
+"""The training shapes that pin every instantiation of the recurrent kernels (csrc/rnn.hip with `save`, csrc/rnn_bptt.hip's BPTT kernels)
 against float64, and the names of the routes they are chosen to reach.  Shared by tests/test_cpu_rnn_routes.py (the tables reach
 every route, asked of the library's own dispatch policy through tn_dbg_rnn_route: no GPU) and tests/test_gpu_rnn_train_routes.py
 (the steps themselves).

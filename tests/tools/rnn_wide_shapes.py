@@ -1,4 +1,4 @@
-"""The shapes that pin the wide recurrent kernels (csrc/rnn.hip rnn_recurrent_wide_kernel, csrc/train.hip gru_ / lstm_train_bwd_wide_kernel:
+"""The shapes that pin the wide recurrent kernels (csrc/rnn.hip rnn_recurrent_wide_kernel, csrc/rnn_bptt.hip rnn_bptt_wide_kernel:
 1024 < gates*H <= 2048, two gate rows per thread) against float64, and the names of the code paths they are chosen to reach.  Shared by
 tests/test_cpu_rnn_wide_routes.py (the table reaches every path, asked of the library's own policy through tn_dbg_rnn_wide_route: no
 GPU) and tests/test_gpu_rnn_wide.py (the kernels themselves).
