@@ -183,6 +183,17 @@ int tn_densenet121_destroy(tn_encoder *enc);
 int tn_dense_create(tn_ctx *ctx, const float *weight_host, const float *bias_host, int units,
                     int in_units, tn_dense **out);
 int tn_dense_forward(tn_dense *d, const float *x, int rows, float *y);
+/* Temporal activation maps of a head that ends in max over T -> this Dense (CNNRNN, TemporalPooling(pool="max"): reference
+ * models/vision/definitions.py:66-69,106-109; the maps themselves have no counterpart there).  pooled (batch, in_units) fp32 is what
+ * the Dense saw, steps (batch, in_units) int32 the window position in [0, window) each unit's maximum was read from
+ * (tn_temporal_pool_arg and the *_arg / *_tam calls below), tam (batch, units, window) fp32:
+ *   tam[b][c][t] = sum over { k : steps[b][k] == t }, k ascending, of weight[c][k] * pooled[b][k],
+ * so bias[c] + sum_t tam[b][c][t] is the logit of tn_dense_forward in real arithmetic.  Every entry is written, a step no unit names
+ * is 0.0f, a steps entry outside [0, window) contributes nothing and is never used as an address.  No atomics: a sample's maps do
+ * not depend on the batch it is in.  All DEVICE buffers.  A recurrent state at step t has seen the steps before it (after it, in the
+ * reverse direction): the maps say which step's STATE a logit was read from, not which single frame caused it.
+ * Nulls, batch < 1 and window < 1 are TN_ERR_INVALID.  Does not allocate. */
+int tn_dense_step_maps(tn_dense *d, const float *pooled, const int32_t *steps, int batch, int window, float *tam);
 int tn_dense_destroy(tn_dense *d);
 
 /* ---- gluon.rnn.GRU/LSTM(hidden, layout='NTC', bidirectional=True) ------- */
@@ -253,6 +264,9 @@ int tn_jpeg_destroy(tn_jpeg *j);
 /* Replaces reference models/vision/definitions.py:66-69,107.  x (B,T,F) -> y (B,F). */
 int tn_temporal_pool(tn_ctx *ctx, const float *x, int batch, int steps, int feat, tn_pool_kind kind,
                      float *y);
+/* F.max over axis 1 (definitions.py:66-69,107) with the position of every maximum: y (B,F) as TN_POOL_MAX above, arg (B,F) int32 the
+ * smallest t that holds it (the position the training step routes the gradient to). */
+int tn_temporal_pool_arg(tn_ctx *ctx, const float *x, int batch, int steps, int feat, float *y, int32_t *arg);
 
 /* ---- dense windowed evaluation of the temporal heads ------------------------ */
 /* Replaces the evaluation loop of reference evaluate.py:274-303 for `--feats_model M --window W --temp_pool gru|lstm`
@@ -285,6 +299,18 @@ int tn_window_head_forward(tn_window_head *h, const int32_t *centre, const int32
  * 2^30 table entries); a table that spells out a (centre, lo, hi, stride) window gives that call's bits.  Does not allocate. */
 int tn_window_head_forward_rows(tn_window_head *h, const int32_t *idx, int samples, int window, float *pooled /* may be NULL */,
                                 float *logits);
+/* tn_window_head_forward / tn_window_head_forward_rows (the evaluation loop of reference evaluate.py:274-303 over
+ * definitions.py:106-109) that also say where each logit was read from: steps (samples, 2H) int32 or NULL, the window position t in
+ * [0, window) of every pooled unit's maximum - the smallest such t, in both directions - and tam (samples, classes, window) fp32, the
+ * maps of tn_dense_step_maps for the handle's own Dense.  pooled and logits are the bits of the calls without maps; a table that
+ * spells out a (centre, lo, hi, stride) window gives the arithmetic form's steps and tam.  The limits and errors of the calls they
+ * extend, tam NULL included.  With steps == NULL the handle allocates a (max_samples, 2H) int32 buffer at the first such call and
+ * nothing afterwards; a handle that never asks allocates nothing. */
+int tn_window_head_forward_tam(tn_window_head *h, const int32_t *centre, const int32_t *lo, const int32_t *hi, int samples,
+                               int window, int stride, float *pooled /* may be NULL */, float *logits,
+                               int32_t *steps /* may be NULL */, float *tam);
+int tn_window_head_forward_rows_tam(tn_window_head *h, const int32_t *idx, int samples, int window, float *pooled /* may be NULL */,
+                                    float *logits, int32_t *steps /* may be NULL */, float *tam);
 int tn_window_head_destroy(tn_window_head *h);
 /* TemporalPooling.forward in feature mode over the same windows (definitions.py:66-69 on the (B, W, F) batch of
  * dataset.py:190-213): feats (rows, feat) -> y (samples, feat), max or mean over the window's gathered rows. */
@@ -295,6 +321,12 @@ int tn_temporal_pool_windows(tn_ctx *ctx, const float *feats, int rows, int feat
  * rows-1); idx (samples, window) int32 DEVICE.  The bits of tn_temporal_pool_windows on a table that spells out its windows. */
 int tn_temporal_pool_rows(tn_ctx *ctx, const float *feats, int rows, int feat, const int32_t *idx, int samples, int window,
                           tn_pool_kind kind, float *y);
+/* The max pool of the two calls above (definitions.py:66-67 on the same windows) with arg (samples, feat) int32: the smallest window
+ * position whose row holds the maximum.  y is TN_POOL_MAX's, bit for bit. */
+int tn_temporal_pool_windows_arg(tn_ctx *ctx, const float *feats, int rows, int feat, const int32_t *centre, const int32_t *lo,
+                                 const int32_t *hi, int samples, int window, int stride, float *y, int32_t *arg);
+int tn_temporal_pool_rows_arg(tn_ctx *ctx, const float *feats, int rows, int feat, const int32_t *idx, int samples, int window,
+                              float *y, int32_t *arg);
 
 /* ---- temporal-head training step ------------------------------ */
 /* bi-GRU / bi-LSTM(hidden) (`kind`; CNNRNN type='gru'|'lstm', definitions.py:93-96; LSTM gates [i,f,g,o]) over

@@ -77,6 +77,7 @@ _SIGS = {
     "tn_densenet121_destroy": (C.c_int, [_P]),
     "tn_dense_create": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     "tn_dense_forward": (C.c_int, [_P, _P, C.c_int, _P]),
+    "tn_dense_step_maps": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "tn_dense_destroy": (C.c_int, [_P]),
     "tn_birnn_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_int,
                                   C.c_int, C.POINTER(_P)]),
@@ -99,7 +100,12 @@ _SIGS = {
     "tn_window_head_project": (C.c_int, [_P, _P, C.c_int]),
     "tn_window_head_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "tn_window_head_forward_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "tn_window_head_forward_tam": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "tn_window_head_forward_rows_tam": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "tn_window_head_destroy": (C.c_int, [_P]),
+    "tn_temporal_pool_arg": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tn_temporal_pool_windows_arg": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tn_temporal_pool_rows_arg": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
     "tn_temporal_pool_windows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "tn_temporal_pool_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "tn_dbg_window_head_rows_per_group": (C.c_int, [_P, C.c_int]),

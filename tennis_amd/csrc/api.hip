@@ -10,6 +10,7 @@
 #include "linear.h"
 #include "rnn.h"
 #include "rnn_window.h"
+#include "step_maps.h"
 #include "train.h"
 
 // ---------------------------------------------------------------------------
@@ -75,6 +76,12 @@ extern "C" int tn_dense_forward(tn_dense *d, const float *x, int rows, float *y)
   TN_ON_DEVICE(d->ctx->device);
   return launch_linear_f32(x, d->in_units, d->w, d->in_units, d->b, y, d->units, rows, d->units, d->in_units, 0,
                            d->ctx->stream);
+}
+extern "C" int tn_dense_step_maps(tn_dense *d, const float *pooled, const int32_t *steps, int batch, int window, float *tam) {
+  TN_REQUIRE(d && pooled && steps && tam, "tn_dense_step_maps: null argument");
+  TN_REQUIRE(batch > 0 && window >= 1, "tn_dense_step_maps: batch must be > 0 and window >= 1");
+  TN_ON_DEVICE(d->ctx->device);
+  return launch_step_maps(pooled, steps, d->w, batch, d->in_units, d->units, window, tam, d->ctx->stream);
 }
 extern "C" int tn_dense_destroy(tn_dense *d) {
   if (!d) return TN_OK;
@@ -185,6 +192,7 @@ struct tn_window_head {
   float *bd;   // [C]
   float *gi;      // [max_rows][2*G*H]: the projection of every row of the matrix
   float *pooled;  // [max_samples][2H]
+  int32_t *steps = nullptr;   // [max_samples][2H], allocated by the first *_tam call that brings no buffer of its own
 };
 
 extern "C" int tn_window_head_create(tn_ctx *ctx, tn_rnn_kind kind, int input_size, int hidden, int classes,
@@ -271,6 +279,57 @@ extern "C" int tn_window_head_forward_rows(tn_window_head *h, const int32_t *idx
   return launch_linear_f32(p, 2 * H, h->wd, 2 * H, h->bd, logits, h->C, samples, h->C, 2 * H, 0, s);
 }
 
+// the steps buffer of a *_tam call: the caller's, or the handle's own (allocated at first use: a handle that never asks has none)
+static int window_head_steps(tn_window_head *h, int32_t *steps, int32_t **out) {
+  if (!steps && !h->steps) {
+    h->steps = (int32_t *)h->pool.alloc((size_t)h->max_samples * 2 * h->H * sizeof(int32_t));
+    if (!h->steps) { tn_set_error("device allocation failed"); return TN_ERR_NOMEM; }
+  }
+  *out = steps ? steps : h->steps;
+  return TN_OK;
+}
+
+extern "C" int tn_window_head_forward_tam(tn_window_head *h, const int32_t *centre, const int32_t *lo, const int32_t *hi, int samples,
+                                          int window, int stride, float *pooled, float *logits, int32_t *steps, float *tam) {
+  TN_REQUIRE(h && centre && lo && hi && logits && tam, "tn_window_head_forward_tam: null argument");
+  TN_REQUIRE(h->rows > 0, "tn_window_head_forward_tam: no projected matrix (call tn_window_head_project first)");
+  TN_REQUIRE(samples > 0 && samples <= h->max_samples, "tn_window_head_forward_tam: samples must be in [1, max_samples]");
+  TN_REQUIRE(window >= 1 && stride >= 1, "tn_window_head_forward_tam: window and stride must be >= 1");
+  TN_ON_DEVICE(h->ctx->device);
+  hipStream_t s = h->ctx->stream;
+  const int H = h->H;
+  float *p = pooled ? pooled : h->pooled;
+  int32_t *st = nullptr;
+  int rc = window_head_steps(h, steps, &st);
+  if (rc) return rc;
+  rc = launch_rnn_window(h->gates, h->gi, 2 * h->gates * H, h->rows, h->whT, h->bh, centre, lo, hi, p, samples, window, stride, H,
+                         h->nb, s, st);
+  if (rc) return rc;
+  rc = launch_linear_f32(p, 2 * H, h->wd, 2 * H, h->bd, logits, h->C, samples, h->C, 2 * H, 0, s);
+  if (rc) return rc;
+  return launch_step_maps(p, st, h->wd, samples, 2 * H, h->C, window, tam, s);
+}
+
+extern "C" int tn_window_head_forward_rows_tam(tn_window_head *h, const int32_t *idx, int samples, int window, float *pooled,
+                                               float *logits, int32_t *steps, float *tam) {
+  TN_REQUIRE(h && idx && logits && tam, "tn_window_head_forward_rows_tam: null argument");
+  TN_REQUIRE(h->rows > 0, "tn_window_head_forward_rows_tam: no projected matrix (call tn_window_head_project first)");
+  TN_REQUIRE(samples > 0 && samples <= h->max_samples, "tn_window_head_forward_rows_tam: samples must be in [1, max_samples]");
+  TN_REQUIRE(window >= 1, "tn_window_head_forward_rows_tam: window must be >= 1");
+  TN_ON_DEVICE(h->ctx->device);
+  hipStream_t s = h->ctx->stream;
+  const int H = h->H;
+  float *p = pooled ? pooled : h->pooled;
+  int32_t *st = nullptr;
+  int rc = window_head_steps(h, steps, &st);
+  if (rc) return rc;
+  rc = launch_rnn_window_rows(h->gates, h->gi, 2 * h->gates * H, h->rows, h->whT, h->bh, idx, p, samples, window, H, h->nb, s, st);
+  if (rc) return rc;
+  rc = launch_linear_f32(p, 2 * H, h->wd, 2 * H, h->bd, logits, h->C, samples, h->C, 2 * H, 0, s);
+  if (rc) return rc;
+  return launch_step_maps(p, st, h->wd, samples, 2 * H, h->C, window, tam, s);
+}
+
 extern "C" int tn_dbg_window_head_rows_per_group(tn_window_head *h, int nb) {
   TN_REQUIRE(h, "tn_dbg_window_head_rows_per_group: null argument");
   TN_REQUIRE(nb == 0 || nb == 4 || nb == 2 * h->gates, "tn_dbg_window_head_rows_per_group: 0 (default), 4 or twice the gates");
@@ -305,6 +364,26 @@ extern "C" int tn_temporal_pool_rows(tn_ctx *ctx, const float *feats, int rows, 
   TN_REQUIRE(kind == TN_POOL_MAX || kind == TN_POOL_MEAN, "tn_temporal_pool_rows: unknown pool kind");
   TN_ON_DEVICE(ctx->device);
   return launch_temporal_pool_rows(feats, rows, feat, idx, samples, window, (int)kind, y, ctx->stream);
+}
+
+extern "C" int tn_temporal_pool_windows_arg(tn_ctx *ctx, const float *feats, int rows, int feat, const int32_t *centre,
+                                            const int32_t *lo, const int32_t *hi, int samples, int window, int stride, float *y,
+                                            int32_t *arg) {
+  TN_REQUIRE(ctx && feats && centre && lo && hi && y && arg, "tn_temporal_pool_windows_arg: null argument");
+  TN_REQUIRE(rows > 0 && feat > 0 && samples > 0, "tn_temporal_pool_windows_arg: bad shape");
+  TN_REQUIRE(window >= 1 && stride >= 1, "tn_temporal_pool_windows_arg: window and stride must be >= 1");
+  TN_ON_DEVICE(ctx->device);
+  return launch_temporal_pool_windows(feats, rows, feat, centre, lo, hi, samples, window, stride, (int)TN_POOL_MAX, y, ctx->stream,
+                                      arg);
+}
+
+extern "C" int tn_temporal_pool_rows_arg(tn_ctx *ctx, const float *feats, int rows, int feat, const int32_t *idx, int samples,
+                                         int window, float *y, int32_t *arg) {
+  TN_REQUIRE(ctx && feats && idx && y && arg, "tn_temporal_pool_rows_arg: null argument");
+  TN_REQUIRE(rows > 0 && feat > 0 && samples > 0, "tn_temporal_pool_rows_arg: bad shape");
+  TN_REQUIRE(window >= 1, "tn_temporal_pool_rows_arg: window must be >= 1");
+  TN_ON_DEVICE(ctx->device);
+  return launch_temporal_pool_rows(feats, rows, feat, idx, samples, window, (int)TN_POOL_MAX, y, ctx->stream, arg);
 }
 
 // ---- temporal-head training step -----------------------------------------------------
@@ -781,6 +860,12 @@ extern "C" int tn_temporal_pool(tn_ctx *ctx, const float *x, int batch, int step
   TN_REQUIRE(kind == TN_POOL_MAX || kind == TN_POOL_MEAN, "tn_temporal_pool: unknown pool kind");
   TN_ON_DEVICE(ctx->device);
   return launch_temporal_pool(x, batch, steps, feat, (int)kind, y, ctx->stream);
+}
+extern "C" int tn_temporal_pool_arg(tn_ctx *ctx, const float *x, int batch, int steps, int feat, float *y, int32_t *arg) {
+  TN_REQUIRE(ctx && x && y && arg, "tn_temporal_pool_arg: null argument");
+  TN_REQUIRE(batch > 0 && steps > 0 && feat > 0, "tn_temporal_pool_arg: bad shape");
+  TN_ON_DEVICE(ctx->device);
+  return launch_pool_max_arg(x, batch, steps, feat, y, arg, ctx->stream);
 }
 
 extern "C" int tn_prf1_update(tn_ctx *ctx, const float *logits, const int32_t *labels, int rows, int classes,

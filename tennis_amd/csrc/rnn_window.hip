@@ -40,14 +40,20 @@ __device__ __forceinline__ long window_row(int centre, int lo, int hi, int t, in
 // of the gi request, so the indices run one step ahead: step s requests its gi values through the index registers that step s - 1
 // loaded (one register per unit the thread finishes) and then requests the indices of step s + 1; both requests are in flight
 // behind the dot product, and the gi request at the top of a step never waits on an index load.
-template <int G, int NB, int KR, bool DPP, int MAXT, bool TAB>
+// ARG: every unit also keeps the window position t whose state its maximum was read from and writes steps[b][dir*H + u] next to
+// pooled.  pooled is computed by the same expression either way; the position moves by comparison only - forward `hn > old`,
+// reverse (t walks downwards) `hn >= old` - so that in both directions a tie goes to the smallest t, the first-maximum rule of
+// pool_max_arg_kernel (train.hip).  Without ARG the kernel is the code it was: `steps` is the last argument and is never read.
+template <int G, int NB, int KR, bool DPP, int MAXT, bool TAB, bool ARG>
 __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
     const float *__restrict__ gi, int ldgi, int rows,   // [rows][2*G*H] i2h + b_i2h of every row of the feature matrix
     const float *__restrict__ whT,                      // [2][H][G*H]
     const float *__restrict__ bh,                       // [2][G*H]
     const int32_t *__restrict__ centre, const int32_t *__restrict__ lo, const int32_t *__restrict__ hi,   // [B]
     float *__restrict__ pooled,                         // [B][2*H]
-    int B, int T, int stride, int H) {
+    int B, int T, int stride, int H,
+    int32_t *__restrict__ steps) {                      // ARG: [B][2*H] window position of every unit's maximum
+
   static_assert(!DPP || KR % 16 == 0, "whole 16-wide h chunks");
   static_assert(DPP || KR == 0, "the register-resident prefix is part of the DPP form");
   constexpr int MI = (NB + G - 1) / G;     // units a thread finishes per step (NB*H units over G*H threads)
@@ -80,8 +86,10 @@ __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
   int nxt[MI];                     // TAB: the table entry of the step to come
   bool live[MI];
   float hmax[MI];
+  int hstep[ARG ? MI : 1];
 #pragma unroll
   for (int m = 0; m < MI; ++m) {
+    if constexpr (ARG) hstep[m] = 0;
     const int idx = j + m * GH;
     const int bg = b0 + idx / H;
     live[m] = idx < NB * H && bg < B;
@@ -201,7 +209,15 @@ __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
         const float r = sigmoidf_(gq[m][0] + q[u]);
         const float z = sigmoidf_(gq[m][1] + q[H + u]);
         const float n = tanhf(gq[m][2] + r * q[2 * H + u]);
-        hn = (1.f - z) * n + z * hs[idx];
+        if constexpr (ARG) {
+          // the form without ARG compiles this line to one packed multiply of both products and an add - two rounded products,
+          // no fused multiply-add; with the comparisons below the compiler fuses instead, which moves the last bit of h.  The same
+          // bits are the contract (tests/test_gpu_step_maps.py holds pooled to them), so the unfused form is spelt out here.
+#pragma clang fp contract(off)
+          hn = (1.f - z) * n + z * hs[idx];
+        } else {
+          hn = (1.f - z) * n + z * hs[idx];
+        }
       } else {
         const float ig = sigmoidf_(gq[m][0] + q[u]);
         const float fg = sigmoidf_(gq[m][1] + q[H + u]);
@@ -212,6 +228,12 @@ __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
         hn = og * tanhf(c2);
       }
       hs[idx] = hn;
+      if constexpr (ARG) {
+        // one select on integer flags, no branch: as `if (s == 0 || (dir ? hn >= old : hn > old)) hstep = t` the streamed and plain
+        // forms came out with the assignment outside its masked region (steps wrong on the GPU, pooled right)
+        const int moved = (int)(s == 0) | (dir ? (int)(hn >= hmax[m]) : (int)(hn > hmax[m]));
+        hstep[m] = moved ? t : hstep[m];
+      }
       hmax[m] = s == 0 ? hn : fmaxf(hmax[m], hn);
     }
     __syncthreads();
@@ -222,15 +244,17 @@ __global__ __launch_bounds__(MAXT) void rnn_window_kernel(
     const int idx = j + m * GH;
     const int b = idx / H, u = idx - b * H;
     pooled[(long)(b0 + b) * (2 * H) + dir * H + u] = hmax[m];
+    if constexpr (ARG) steps[(long)(b0 + b) * (2 * H) + dir * H + u] = hstep[m];
   }
 }
 
 // F.max / F.mean over the gathered rows of the feature matrix itself (definitions.py:66-69 in feature mode), t ascending as in
-// temporal_pool_kernel (rnn.hip): x (rows, F) -> y (B, F)
-template <bool TAB>
+// temporal_pool_kernel (rnn.hip): x (rows, F) -> y (B, F).  ARG (max only): arg (B, F) the first window position that holds the
+// maximum (`v > old`: a tie stays with the smaller t, as in pool_max_arg_kernel); y is the same fmaxf chain either way.
+template <bool TAB, bool ARG>
 __global__ void temporal_pool_windows_kernel(const float *__restrict__ x, int rows, int F, const int32_t *__restrict__ centre,
                                              const int32_t *__restrict__ lo, const int32_t *__restrict__ hi, int B, int T,
-                                             int stride, int kind, float *__restrict__ y) {
+                                             int stride, int kind, float *__restrict__ y, int32_t *__restrict__ arg) {
   const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= (long)B * F) return;
   const int b = (int)(id / F), f = (int)(id % F);
@@ -238,26 +262,33 @@ __global__ void temporal_pool_windows_kernel(const float *__restrict__ x, int ro
   if constexpr (!TAB) c = centre[b], l = lo[b], h = hi[b];
   const int32_t *tab = centre + (long)b * T;      // TAB: `centre` is the (B, T) row table
   float acc = kind == TN_POOL_MAX ? -INFINITY : 0.f;
+  int at = 0;
   for (int t = 0; t < T; ++t) {
     long row;
     if constexpr (TAB) row = min(max(tab[t], 0), rows - 1);
     else row = window_row(c, l, h, t, T, stride, rows);
     const float v = x[row * F + f];
+    if constexpr (ARG) {
+      if (v > acc) at = t;
+    }
     acc = kind == TN_POOL_MAX ? fmaxf(acc, v) : acc + v;
   }
   y[id] = kind == TN_POOL_MAX ? acc : acc / (float)T;
+  if constexpr (ARG) arg[id] = at;
 }
 
-template <int G, int NB, bool TAB>
+template <int G, int NB, bool TAB, bool ARG>
 int launch_window_nb(const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *centre,
-                     const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, hipStream_t s) {
+                     const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, int32_t *steps,
+                     hipStream_t s) {
   const dim3 grid((B + NB - 1) / NB, 2), block(G * H);
   const size_t lds = (size_t)(NB * H * 2 + NB * G * H) * sizeof(float);
 #define TN_WIN_LAUNCH(KR_, DPP_, MT_)                                                                                          \
-  hipLaunchKernelGGL((rnn_window_kernel<G, NB, KR_, DPP_, MT_, TAB>), grid, block, lds, s, gi, ldgi, rows, whT, bh, centre, lo, hi, \
-                     pooled, B, T, stride, H)
+  hipLaunchKernelGGL((rnn_window_kernel<G, NB, KR_, DPP_, MT_, TAB, ARG>), grid, block, lds, s, gi, ldgi, rows, whT, bh, centre, lo, \
+                     hi, pooled, B, T, stride, H, steps)
   if (H == 128) TN_WIN_LAUNCH(128, true, 512);          // the fast route: CNNRNN's width, the weight column in registers
   else if (H % 16 == 0) TN_WIN_LAUNCH(0, true, 1024);
+  else if constexpr (ARG && G == 4 && NB == 8) TN_REQUIRE(false, "rnn_window: the plain LSTM form keeps steps at 4 rows per workgroup");
   else TN_WIN_LAUNCH(0, false, 1024);
 #undef TN_WIN_LAUNCH
   TN_HIP_CHECK(hipGetLastError());
@@ -272,31 +303,38 @@ namespace {
 
 template <bool TAB>
 int launch_window(int gates, const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *centre,
-                  const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, int nb, hipStream_t s) {
+                  const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, int nb, int32_t *steps,
+                  hipStream_t s) {
   TN_REQUIRE(gates == 3 || gates == 4, "rnn_window: gates must be 3 or 4");
   TN_REQUIRE(gates * H <= 1024 && H % 4 == 0, "rnn_window: the windowed kernel serves gates*hidden <= 1024 and hidden % 4 == 0");
   TN_REQUIRE(rows > 0 && B > 0 && T > 0 && stride > 0, "rnn_window: bad shape");
   TN_REQUIRE(!TAB || (long)B * T < (1L << 30), "rnn_window: the row table must hold fewer than 2^30 entries");
   if (nb == 0) nb = rnn_window_default_nb(gates);
   if ((size_t)nb * (2 + gates) * H * sizeof(float) > 64 * 1024) nb = 4;      // (the LDS a workgroup may ask for without an attribute)
-#define TN_WIN_ARGS gi, ldgi, rows, whT, bh, centre, lo, hi, pooled, B, T, stride, H, s
-  if (gates == 3) {
-    if (nb == 4) return launch_window_nb<3, 4, TAB>(TN_WIN_ARGS);
-    if (nb == 6) return launch_window_nb<3, 6, TAB>(TN_WIN_ARGS);
-  } else {
-    if (nb == 4) return launch_window_nb<4, 4, TAB>(TN_WIN_ARGS);
-    if (nb == 8) return launch_window_nb<4, 8, TAB>(TN_WIN_ARGS);
-  }
+  // the plain LSTM form at 8 rows is at its 128 registers without the steps: with them it would spill, so it runs 4 rows per
+  // workgroup (one unit per thread instead of two); the result does not depend on the rows per workgroup
+  if (steps && gates == 4 && nb == 8 && H % 16 != 0) nb = 4;
+#define TN_WIN_ARGS gi, ldgi, rows, whT, bh, centre, lo, hi, pooled, B, T, stride, H, steps, s
+#define TN_WIN_NB(G_, NB_)                                                                    \
+  if (gates == G_ && nb == NB_)                                                               \
+    return steps ? launch_window_nb<G_, NB_, TAB, true>(TN_WIN_ARGS) : launch_window_nb<G_, NB_, TAB, false>(TN_WIN_ARGS)
+  TN_WIN_NB(3, 4);
+  TN_WIN_NB(3, 6);
+  TN_WIN_NB(4, 4);
+  TN_WIN_NB(4, 8);
+#undef TN_WIN_NB
 #undef TN_WIN_ARGS
   TN_REQUIRE(false, "rnn_window: rows per workgroup must be 4 or 6 (GRU) / 4 or 8 (LSTM)");
 }
 
 template <bool TAB>
 int launch_pool(const float *x, int rows, int F, const int32_t *centre, const int32_t *lo, const int32_t *hi, int B, int T,
-                int stride, int kind, float *y, hipStream_t s) {
+                int stride, int kind, float *y, int32_t *arg, hipStream_t s) {
   const long total = (long)B * F;
-  hipLaunchKernelGGL(temporal_pool_windows_kernel<TAB>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, rows, F, centre,
-                     lo, hi, B, T, stride, kind, y);
+  TN_REQUIRE(!arg || kind == TN_POOL_MAX, "temporal_pool_windows: the step of a maximum exists for the max pool only");
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  if (arg) hipLaunchKernelGGL((temporal_pool_windows_kernel<TAB, true>), grid, block, 0, s, x, rows, F, centre, lo, hi, B, T, stride, kind, y, arg);
+  else hipLaunchKernelGGL((temporal_pool_windows_kernel<TAB, false>), grid, block, 0, s, x, rows, F, centre, lo, hi, B, T, stride, kind, y, arg);
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
 }
@@ -305,21 +343,21 @@ int launch_pool(const float *x, int rows, int F, const int32_t *centre, const in
 
 int launch_rnn_window(int gates, const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *centre,
                       const int32_t *lo, const int32_t *hi, float *pooled, int B, int T, int stride, int H, int nb,
-                      hipStream_t s) {
-  return launch_window<false>(gates, gi, ldgi, rows, whT, bh, centre, lo, hi, pooled, B, T, stride, H, nb, s);
+                      hipStream_t s, int32_t *steps) {
+  return launch_window<false>(gates, gi, ldgi, rows, whT, bh, centre, lo, hi, pooled, B, T, stride, H, nb, steps, s);
 }
 
 int launch_rnn_window_rows(int gates, const float *gi, int ldgi, int rows, const float *whT, const float *bh, const int32_t *idx,
-                           float *pooled, int B, int T, int H, int nb, hipStream_t s) {
-  return launch_window<true>(gates, gi, ldgi, rows, whT, bh, idx, nullptr, nullptr, pooled, B, T, 1, H, nb, s);
+                           float *pooled, int B, int T, int H, int nb, hipStream_t s, int32_t *steps) {
+  return launch_window<true>(gates, gi, ldgi, rows, whT, bh, idx, nullptr, nullptr, pooled, B, T, 1, H, nb, steps, s);
 }
 
 int launch_temporal_pool_windows(const float *x, int rows, int F, const int32_t *centre, const int32_t *lo, const int32_t *hi,
-                                 int B, int T, int stride, int kind, float *y, hipStream_t s) {
-  return launch_pool<false>(x, rows, F, centre, lo, hi, B, T, stride, kind, y, s);
+                                 int B, int T, int stride, int kind, float *y, hipStream_t s, int32_t *arg) {
+  return launch_pool<false>(x, rows, F, centre, lo, hi, B, T, stride, kind, y, arg, s);
 }
 
 int launch_temporal_pool_rows(const float *x, int rows, int F, const int32_t *idx, int B, int T, int kind, float *y,
-                              hipStream_t s) {
-  return launch_pool<true>(x, rows, F, idx, nullptr, nullptr, B, T, 1, kind, y, s);
+                              hipStream_t s, int32_t *arg) {
+  return launch_pool<true>(x, rows, F, idx, nullptr, nullptr, B, T, 1, kind, y, arg, s);
 }

@@ -321,6 +321,22 @@ class Dense(_Handle):
         check(self.lib.tn_dense_forward(self.handle, ptr(x), x.shape[0], ptr(y)), "tn_dense_forward")
         return y
 
+    def step_maps(self, pooled: torch.Tensor, steps: torch.Tensor, window: int) -> torch.Tensor:
+        """Temporal activation maps of a head that ends in ``max over T -> this Dense``: ``pooled`` (B, in_units) what the Dense saw,
+        ``steps`` (B, in_units) the window position each unit's maximum was read from (``temporal_pool(..., return_steps=True)``)
+        -> ``tam`` (B, units, window) with ``tam[b, c, t]`` the sum of ``weight[c, k] * pooled[b, k]`` over the ``k`` with
+        ``steps[b, k] == t``: ``bias[c] + tam[b, c].sum()`` is the logit.  A step outside ``[0, window)`` contributes nothing."""
+        _on_ctx_device(self.ctx, pooled, "Dense.step_maps")
+        pooled = pooled.reshape(pooled.shape[0], -1).contiguous().float()
+        steps = steps.reshape(steps.shape[0], -1).to(device=pooled.device, dtype=torch.int32).contiguous()
+        if pooled.shape[1] != self.in_units or steps.shape != pooled.shape:
+            raise ValueError(f"Dense.step_maps expects pooled and steps of shape (B, {self.in_units}), got {tuple(pooled.shape)} and "
+                             f"{tuple(steps.shape)}")
+        tam = torch.empty((pooled.shape[0], self.units, int(window)), dtype=torch.float32, device=pooled.device)
+        check(self.lib.tn_dense_step_maps(self.handle, ptr(pooled), ptr(steps), pooled.shape[0], int(window), ptr(tam)),
+              "tn_dense_step_maps")
+        return tam
+
 
 
 class BiRNN(_Handle):
@@ -358,13 +374,24 @@ class BiRNN(_Handle):
 
 
 
-def temporal_pool(x: torch.Tensor, kind: str, ctx: _lib.Context | None = None) -> torch.Tensor:
-    """``F.max(x, axis=1)`` / ``F.mean(x, axis=1)`` (definitions.py:66-69,107)."""
+def _max_only(kind: str, what: str):
+    if kind != "max":
+        raise ValueError(f"{what}(..., return_steps=True) is for the max pool: a mean is read from every step alike")
+
+
+def temporal_pool(x: torch.Tensor, kind: str, ctx: _lib.Context | None = None, return_steps: bool = False):
+    """``F.max(x, axis=1)`` / ``F.mean(x, axis=1)`` (definitions.py:66-69,107).  ``return_steps=True`` (max only): ``(y, steps)``,
+    ``steps`` int32 of ``y``'s shape, the first position along axis 1 that holds each maximum."""
     ctx = ctx or _lib.default_context(x.device.index)
     x = x.contiguous().float()
     b, t = x.shape[:2]
     f = int(np.prod(x.shape[2:]))
     y = torch.empty((b,) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+    if return_steps:
+        _max_only(kind, "temporal_pool")
+        arg = torch.empty(y.shape, dtype=torch.int32, device=x.device)
+        check(ctx.lib.tn_temporal_pool_arg(ctx.handle, ptr(x), b, t, f, ptr(y), ptr(arg)), "tn_temporal_pool_arg")
+        return y, arg
     check(ctx.lib.tn_temporal_pool(ctx.handle, ptr(x), b, t, f, _lib.POOL_MEAN if kind == "mean" else _lib.POOL_MAX,
                                    ptr(y)), "tn_temporal_pool")
     return y
@@ -425,27 +452,49 @@ class WindowHead(_Handle):
         self.rows = x.shape[0]
         return self
 
-    def forward(self, centre, lo, hi, window: int, stride: int = 1, return_pooled: bool = False):
+    def forward(self, centre, lo, hi, window: int, stride: int = 1, return_pooled: bool = False, return_tam: bool = False,
+                return_steps: bool = False):
+        """``return_tam=True``: ``(logits, tam)`` - ``(logits, pooled, tam)`` with ``return_pooled`` - with ``tam`` (samples,
+        classes, window) the temporal activation maps (``Dense.step_maps``): ``bias[c] + tam[b, c].sum()`` is ``logits[b, c]``.
+        ``return_steps`` appends ``steps`` (samples, 2H) int32, the window position each pooled unit was read from.  ``logits`` and
+        ``pooled`` are the bits of the call without maps."""
         dev = torch.device("cuda", self.ctx.device)
         centre, lo, hi = _index_arrays(dev, centre, lo, hi)
         n = centre.shape[0]
         logits = torch.empty((n, self.classes), dtype=torch.float32, device=dev)
         pooled = torch.empty((n, 2 * self.hidden), dtype=torch.float32, device=dev) if return_pooled else None
+        if return_tam or return_steps:
+            steps = torch.empty((n, 2 * self.hidden), dtype=torch.int32, device=dev) if return_steps else None
+            tam = torch.empty((n, self.classes, int(window)), dtype=torch.float32, device=dev)
+            check(self.lib.tn_window_head_forward_tam(self.handle, ptr(centre), ptr(lo), ptr(hi), n, int(window), int(stride),
+                                                      ptr(pooled), ptr(logits), ptr(steps), ptr(tam)), "tn_window_head_forward_tam")
+            return self._with_maps(logits, pooled, tam, steps, return_tam)
         check(self.lib.tn_window_head_forward(self.handle, ptr(centre), ptr(lo), ptr(hi), n, int(window), int(stride), ptr(pooled),
                                               ptr(logits)), "tn_window_head_forward")
         return (logits, pooled) if return_pooled else logits
 
     __call__ = forward
 
-    def forward_rows(self, idx, return_pooled: bool = False):
+    @staticmethod
+    def _with_maps(logits, pooled, tam, steps, return_tam):
+        out = (logits,) + (() if pooled is None else (pooled,)) + ((tam,) if return_tam else ()) + (() if steps is None else (steps,))
+        return out
+
+    def forward_rows(self, idx, return_pooled: bool = False, return_tam: bool = False, return_steps: bool = False):
         """``forward`` over a row table (``TennisSet.window_table``): ``idx`` (samples, window) integers, step ``t`` of sample ``b``
         reads row ``clamp(idx[b, t], 0, rows - 1)`` of the projected matrix (a negative entry is row 0).  Any sample layout; a table
-        that spells out a ``(centre, lo, hi, stride)`` window gives ``forward``'s bits."""
+        that spells out a ``(centre, lo, hi, stride)`` window gives ``forward``'s bits, ``return_tam`` / ``return_steps`` included."""
         dev = torch.device("cuda", self.ctx.device)
         idx = _index_table(dev, idx)
         n, window = idx.shape
         logits = torch.empty((n, self.classes), dtype=torch.float32, device=dev)
         pooled = torch.empty((n, 2 * self.hidden), dtype=torch.float32, device=dev) if return_pooled else None
+        if return_tam or return_steps:
+            steps = torch.empty((n, 2 * self.hidden), dtype=torch.int32, device=dev) if return_steps else None
+            tam = torch.empty((n, self.classes, window), dtype=torch.float32, device=dev)
+            check(self.lib.tn_window_head_forward_rows_tam(self.handle, ptr(idx), n, window, ptr(pooled), ptr(logits), ptr(steps),
+                                                           ptr(tam)), "tn_window_head_forward_rows_tam")
+            return self._with_maps(logits, pooled, tam, steps, return_tam)
         check(self.lib.tn_window_head_forward_rows(self.handle, ptr(idx), n, window, ptr(pooled), ptr(logits)),
               "tn_window_head_forward_rows")
         return (logits, pooled) if return_pooled else logits
@@ -457,9 +506,10 @@ class WindowHead(_Handle):
 
 
 def temporal_pool_windows(features: torch.Tensor, centre, lo, hi, window: int, stride: int, kind: str,
-                          ctx: _lib.Context | None = None) -> torch.Tensor:
+                          ctx: _lib.Context | None = None, return_steps: bool = False):
     """``F.max`` / ``F.mean`` over axis 1 of the windows of a (rows, F) feature matrix without materialising them
-    (definitions.py:66-69 on the batch of dataset.py:190-213) -> (samples, F)."""
+    (definitions.py:66-69 on the batch of dataset.py:190-213) -> (samples, F).  ``return_steps=True`` (max only): ``(y, steps)``,
+    ``steps`` (samples, F) int32 the first window position whose row holds the maximum."""
     ctx = ctx or _lib.default_context(features.device.index)
     _on_ctx_device(ctx, features, "temporal_pool_windows")
     x = features.contiguous().float()
@@ -468,15 +518,21 @@ def temporal_pool_windows(features: torch.Tensor, centre, lo, hi, window: int, s
     centre, lo, hi = _index_arrays(x.device, centre, lo, hi)
     n = centre.shape[0]
     y = torch.empty((n, x.shape[1]), dtype=torch.float32, device=x.device)
+    if return_steps:
+        _max_only(kind, "temporal_pool_windows")
+        arg = torch.empty(y.shape, dtype=torch.int32, device=x.device)
+        check(ctx.lib.tn_temporal_pool_windows_arg(ctx.handle, ptr(x), x.shape[0], x.shape[1], ptr(centre), ptr(lo), ptr(hi), n,
+                                                   int(window), int(stride), ptr(y), ptr(arg)), "tn_temporal_pool_windows_arg")
+        return y, arg
     check(ctx.lib.tn_temporal_pool_windows(ctx.handle, ptr(x), x.shape[0], x.shape[1], ptr(centre), ptr(lo), ptr(hi), n, int(window),
                                            int(stride), _lib.POOL_MEAN if kind == "mean" else _lib.POOL_MAX, ptr(y)),
           "tn_temporal_pool_windows")
     return y
 
 
-def temporal_pool_rows(features: torch.Tensor, idx, kind: str, ctx: _lib.Context | None = None) -> torch.Tensor:
+def temporal_pool_rows(features: torch.Tensor, idx, kind: str, ctx: _lib.Context | None = None, return_steps: bool = False):
     """``temporal_pool_windows`` over a row table (``TennisSet.window_table``): sample ``b`` pools the rows
-    ``clamp(idx[b, t], 0, rows - 1)``, t ascending -> (samples, F)."""
+    ``clamp(idx[b, t], 0, rows - 1)``, t ascending -> (samples, F); ``return_steps`` as there."""
     ctx = ctx or _lib.default_context(features.device.index)
     _on_ctx_device(ctx, features, "temporal_pool_rows")
     x = features.contiguous().float()
@@ -485,6 +541,12 @@ def temporal_pool_rows(features: torch.Tensor, idx, kind: str, ctx: _lib.Context
     idx = _index_table(x.device, idx)
     n, window = idx.shape
     y = torch.empty((n, x.shape[1]), dtype=torch.float32, device=x.device)
+    if return_steps:
+        _max_only(kind, "temporal_pool_rows")
+        arg = torch.empty(y.shape, dtype=torch.int32, device=x.device)
+        check(ctx.lib.tn_temporal_pool_rows_arg(ctx.handle, ptr(x), x.shape[0], x.shape[1], ptr(idx), n, window, ptr(y), ptr(arg)),
+              "tn_temporal_pool_rows_arg")
+        return y, arg
     check(ctx.lib.tn_temporal_pool_rows(ctx.handle, ptr(x), x.shape[0], x.shape[1], ptr(idx), n, window,
                                         _lib.POOL_MEAN if kind == "mean" else _lib.POOL_MAX, ptr(y)), "tn_temporal_pool_rows")
     return y

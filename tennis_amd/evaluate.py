@@ -127,6 +127,101 @@ def load_cams(file_path):
     return d
 
 
+def check_save_tams(flags, world=1):
+    """``--save_tams`` is for a windowed model that ends in ``max over the window -> Dense``, on one rank: exits with the reason
+    otherwise.  Touches no device."""
+    if not getattr(flags, "save_tams", False):
+        return
+    if flags.window <= 1:
+        raise SystemExit("--save_tams needs a temporal model: --window %d evaluates single frames, there is no window whose steps a "
+                         "logit could be read from (--save_cams maps a frame model's logits onto the frame)" % flags.window)
+    if flags.temp_pool == "mean":
+        raise SystemExit("--save_tams needs --temp_pool gru|lstm|max: a mean reads every step alike - its maps are the Dense applied to "
+                         "each step's features divided by the window, which needs no run of this driver")
+    if flags.temp_pool not in ("gru", "lstm", "max"):
+        raise SystemExit("--save_tams needs --temp_pool gru|lstm|max, got %r" % flags.temp_pool)
+    if flags.save_feats:
+        raise SystemExit("--save_tams writes the maps of a test run: not together with --save_feats")
+    if flags.corpus_frames > 0:
+        raise SystemExit("--save_tams writes the maps of a split's samples: --corpus_frames runs a synthetic corpus that has none")
+    if flags.num_gpus > 1 or world > 1:
+        raise SystemExit("--save_tams writes one file from one rank: run it with --num_gpus 1")
+
+
+TAM_COLUMNS = ("tam", "pred", "label", "logit", "video", "frame", "frames", "bias")
+
+
+def tam_columns(net, dataset, order, outputs, tam):
+    """The columns of ``save_tams`` for the samples ``order`` (dataset indices) with logits ``outputs`` (N, classes) and maps ``tam``
+    (N, classes, window) in that order: per sample the map of its arg-max class ``tam (N, window)``, ``pred``, ``label``, that class's
+    ``logit`` and Dense ``bias``, ``video``, the centre ``frame`` and ``frames (N, window)``, the frame number every window step read
+    (``TennisSet.window_frames``)."""
+    pred = outputs.argmax(1)
+    rows = torch.arange(outputs.shape[0], device=outputs.device)
+    sel, pred, out = tam[rows, pred].cpu().numpy(), pred.cpu().numpy(), outputs.cpu().numpy()
+    bias = np.asarray(net.classes._own_params[net.classes.prefix + "bias"].data, np.float32).reshape(-1)
+    samples = [dataset._samples[int(i)] for i in order]
+    return dict(tam=sel, pred=pred, label=[dataset.classes.index(s[2]) for s in samples], logit=out[np.arange(len(out)), pred],
+                video=[s[0] for s in samples], frame=[int(s[1]) for s in samples],
+                frames=np.asarray([dataset.window_frames(s) for s in samples], np.int64).reshape(len(samples), -1), bias=bias[pred])
+
+
+def evaluate_model_tams(net, loader, dataset, metrics):
+    """``evaluate_model`` of a windowed ``CNNRNN`` / ``TemporalPooling(max)`` through ``forward(x, return_tam=True)``: the same
+    logits (bit for bit), metric updates and return values, and as a third value the columns of ``save_tams`` in loader order."""
+    results, ground_truths = dict(), dict()
+    outs, tams, order = [], [], []
+    for data, labels, idxs in loader:
+        outputs, tam = net(data, return_tam=True)
+        lab = torch.from_numpy(labels).to(outputs.device)
+        for metric in metrics:
+            metric.update([lab], [outputs])
+        outs.append(outputs)
+        tams.append(tam)
+        out = outputs.cpu().numpy()
+        for i, idx in enumerate(int(j) for j in idxs):
+            sample = dataset._samples[idx]
+            img_path = dataset.get_image_path(dataset._frames_dir, sample[0], sample[1])
+            results[img_path] = out[i]
+            ground_truths[img_path] = dataset.classes.index(sample[2])
+            order.append(idx)
+    return results, ground_truths, tam_columns(net, dataset, order, torch.cat(outs), torch.cat(tams))
+
+
+def save_tams(file_path, tam, pred, label, logit, video, frame, frames, bias):
+    """One ``.npz`` of flat arrays (``np.load(..., allow_pickle=False)`` reads it): ``tam (N, window)`` float32 the temporal activation
+    map of each sample's arg-max class, ``pred (N,)`` that class, ``label (N,)``, ``logit (N,)`` its logit (= ``bias`` +
+    ``tam.sum(1)``), ``bias (N,)`` the Dense bias of ``pred``, ``video (N,)`` unicode, ``frame (N,)`` the centre frame and
+    ``frames (N, window)`` the frame number every window step read.  ``tam[n, t]`` is what the logit read from the model's state at
+    window step ``t``; a recurrent state at step ``t`` has seen the steps before it (after it, in the reverse direction), so this
+    names the step whose state was read, not a single frame that caused the logit."""
+    tam = np.ascontiguousarray(tam, np.float32)
+    n = len(tam)
+    if tam.ndim != 2:
+        raise ValueError(f"save_tams: tam must be (N, window), got {tam.shape}")
+    cols = dict(tam=tam, pred=np.asarray(pred, np.int64).reshape(-1), label=np.asarray(label, np.int64).reshape(-1),
+                logit=np.asarray(logit, np.float32).reshape(-1), video=np.asarray(list(video), dtype=np.str_).reshape(-1),
+                frame=np.asarray(frame, np.int64).reshape(-1), frames=np.asarray(frames, np.int64).reshape(n, -1),
+                bias=np.asarray(bias, np.float32).reshape(-1))
+    for k, v in cols.items():
+        if len(v) != n:
+            raise ValueError(f"save_tams: {k} has {len(v)} entries for {n} maps")
+    if cols["frames"].shape != tam.shape:
+        raise ValueError(f"save_tams: frames must be {tam.shape} like tam, got {cols['frames'].shape}")
+    os.makedirs(os.path.dirname(os.path.abspath(file_path)), exist_ok=True)
+    np.savez(file_path, **cols)
+
+
+def load_tams(file_path):
+    """-> dict of ``save_tams``' arrays: ``tam``, ``pred``, ``label``, ``logit``, ``video``, ``frame``, ``frames``, ``bias``."""
+    with np.load(file_path, allow_pickle=False) as z:
+        d = {k: z[k] for k in z.files}
+    missing = [k for k in TAM_COLUMNS if k not in d]
+    if missing:
+        raise ValueError(f"{file_path}: not a file of save_tams (no {', '.join(missing)})")
+    return d
+
+
 def load_feature_matrix(dataset):
     """The dataset-order (len(dataset), F) feature matrix from the ``.npy`` files of ``dataset.feat_dir``: every frame's file is
     read once (the loader path reads it once per window that contains it)."""
@@ -161,18 +256,21 @@ def load_feature_table(dataset, frames):
     return read_rows(lambda r: np.load(path(frames[r])), len(frames))
 
 
-def evaluate_windows(net, dataset, metrics, features=None, batch_size=65536):
+def evaluate_windows(net, dataset, metrics, features=None, batch_size=65536, return_tams=False):
     """``evaluate_model`` for a windowed feature-mode model (``CNNRNN`` / ``TemporalPooling``) without the loader: the
     dataset-order feature matrix (``features``: (len(dataset), F), e.g. what ``save_features_sharded`` returned; None: loaded from
     the ``.npy`` files, each once) goes to the device once, ``net.forward_windows`` evaluates every sample's window from it
     (``TennisSet.window_rows``), and the metrics are updated in dataset order in pieces of ``batch_size``.  Same return values:
-    results[img_path] = raw logits, ground_truths[img_path] = class index."""
+    results[img_path] = raw logits, ground_truths[img_path] = class index; ``return_tams``: the columns of ``save_tams`` as a third,
+    from ``forward_windows(..., return_tam=True)`` (the same logits)."""
     centre, lo, hi, row_stride = dataset.window_rows()
     if features is None:
         features = load_feature_matrix(dataset)
     if len(features) != len(dataset):
         raise ValueError(f"evaluate_windows: {len(features)} feature rows for {len(dataset)} samples")
-    outputs = net.forward_windows(features, centre, lo, hi, dataset._window, row_stride)
+    outputs = net.forward_windows(features, centre, lo, hi, dataset._window, row_stride, return_tam=return_tams)
+    if return_tams:
+        outputs, tam = outputs
     labels = torch.tensor([dataset.classes.index(s[2]) for s in dataset._samples], dtype=torch.float32, device=outputs.device)
     for a in range(0, len(dataset), batch_size):
         for metric in metrics:
@@ -183,6 +281,8 @@ def evaluate_windows(net, dataset, metrics, features=None, batch_size=65536):
         img_path = dataset.get_image_path(dataset._frames_dir, sample[0], sample[1])
         results[img_path] = out[i]
         ground_truths[img_path] = dataset.classes.index(sample[2])
+    if return_tams:
+        return results, ground_truths, tam_columns(net, dataset, range(len(dataset)), outputs, tam)
     return results, ground_truths
 
 
@@ -216,13 +316,14 @@ def encode_table(net_backbone, dataset, frames, batch_size=64, num_workers=0):
     return table
 
 
-def evaluate_table(net, dataset, metrics, features=None, frames_idx=None, batch_size=64, num_workers=0, metric_batch=65536):
+def evaluate_table(net, dataset, metrics, features=None, frames_idx=None, batch_size=64, num_workers=0, metric_batch=65536,
+                   return_tams=False):
     """``evaluate_windows`` through a row table (``TennisSet.window_table`` + ``net.forward_table``): any ``every``, ``stride``,
     ``padding`` and split layout the loader route accepts, in feature mode and on frames.  ``frames_idx``: ``(frames, idx)`` of
     ``dataset.window_table()`` if the caller has it.  ``features``: the (len(frames), F) table; None: in feature mode it is loaded
     with ``load_feature_table`` (every ``.npy`` once), on frames it is built by ``encode_table`` from the model's own backbone
     (``net.td.model``: every distinct frame decoded and encoded once, in batches of ``batch_size``).  Same return values and metric
-    updates as ``evaluate_windows``."""
+    updates as ``evaluate_windows``, ``return_tams`` included."""
     frames, idx = dataset.window_table() if frames_idx is None else frames_idx
     if features is None:
         if getattr(net, "feats", False):
@@ -231,7 +332,9 @@ def evaluate_table(net, dataset, metrics, features=None, frames_idx=None, batch_
             features = encode_table(net.td.model, dataset, frames, batch_size, num_workers)
     if len(features) != len(frames):
         raise ValueError(f"evaluate_table: {len(features)} feature rows for a table of {len(frames)} frames")
-    outputs = net.forward_table(features, idx, row_videos=[v for v, _ in frames])
+    outputs = net.forward_table(features, idx, row_videos=[v for v, _ in frames], return_tam=return_tams)
+    if return_tams:
+        outputs, tam = outputs
     labels = torch.tensor([dataset.classes.index(s[2]) for s in dataset._samples], dtype=torch.float32, device=outputs.device)
     for a in range(0, len(dataset), metric_batch):
         for metric in metrics:
@@ -242,6 +345,8 @@ def evaluate_table(net, dataset, metrics, features=None, frames_idx=None, batch_
         img_path = dataset.get_image_path(dataset._frames_dir, sample[0], sample[1])
         results[img_path] = out[i]
         ground_truths[img_path] = dataset.classes.index(sample[2])
+    if return_tams:
+        return results, ground_truths, tam_columns(net, dataset, range(len(dataset)), outputs, tam)
     return results, ground_truths
 
 
@@ -580,12 +685,21 @@ def build_parser():
                         "<split>_cams.npz into the experiment's directory - per frame the class activation map of its arg-max class "
                         "(7 x 7 cells at 224, 14 x 14 at 512), the class, the label, that class's logit, the video and the frame "
                         "number (evaluate.load_cams reads it); the maps come out of the same forward, the metrics do not change")
+    p.add_argument("--save_tams", action="store_true",
+                   help="windowed model that ends in max over the window -> Dense (--window W > 1 with --temp_pool gru|lstm|max, with or "
+                        "without --feats_model / --dense_windows, one rank; not a reference flag): also write <split>_tams.npz into the "
+                        "experiment's directory - per sample the temporal activation map of its arg-max class (one number per window "
+                        "step; with that class's Dense bias they sum to its logit), the class, the label, the logit, the bias, the "
+                        "video, the centre frame and the frame number every window step read (evaluate.load_tams reads it).  A map "
+                        "names the step whose state the logit was read from - a recurrent state has seen the steps before it - not "
+                        "a single frame that caused it.  The maps come out of the same forward, the metrics do not change")
     return p
 
 
 def main(argv=None):
     flags = build_parser().parse_args(argv)
     check_save_cams(flags)                                                  # refusals before any device work
+    check_save_tams(flags)
     if flags.num_gpus > 1 and not sharding.under_launcher():
         # evaluate.py:101-102 builds ctx = [gpu(0) .. gpu(N-1)] in one process; here: one process per GPU
         if torch.cuda.is_available() and flags.num_gpus > torch.cuda.device_count():
@@ -611,7 +725,9 @@ def _main_rank(flags, rank, world, dev):
     every = [int(s) for s in flags.every.split(",")]
     check_dense_windows(flags)                                              # refusals before anything is built
     check_save_cams(flags, world)
-    if flags.corpus_frames > 0:                                             # BASELINE config C4
+    check_save_tams(flags, world)
+    flags.save_tams = getattr(flags, "save_tams", False)                    # (flags built by hand, without the newer switches)
+    if flags.corpus_frames > 0:                                            # BASELINE config C4
         backbone = get_model(flags.backbone, pretrained=True, max_batch=flags.batch_size, conversion=flags.fp16_conversion).features
         full, st = extract_corpus(backbone, flags.corpus_frames, flags.batch_size, flags.data_shape, dev, rank, world,
                                   block=flags.gather_block, reuse_frames=flags.corpus_reuse_frames)
@@ -691,12 +807,15 @@ def _main_rank(flags, rank, world, dev):
         model = TemporalPooling(model, pool=flags.temp_pool, num_classes=0, feats=flags.feats_model is not None)
     test_metrics = [PRF1(label_names=test_set.classes)]
     tic = time.time()
+    tams = {"return_tams": True} if flags.save_tams else {}                 # (a call without the flag is the call it was)
+    cols = None
     if flags.dense_windows:
         route = check_dense_windows(flags)
         if rank != 0:                                                       # one pass over one matrix: nothing to shard
             return 0
         if route == "frames":
-            results, gts = evaluate_table(model, test_set, test_metrics, batch_size=flags.batch_size, num_workers=flags.num_workers)
+            results, gts, *cols = evaluate_table(model, test_set, test_metrics, batch_size=flags.batch_size,
+                                                 num_workers=flags.num_workers, **tams)
         else:
             try:
                 test_set.window_rows()
@@ -704,9 +823,9 @@ def _main_rank(flags, rank, world, dev):
                 print("--dense_windows: this split has no (centre, lo, hi) window form (%s): evaluating through the row table" % e)
                 route = "table"
             if route == "table":
-                results, gts = evaluate_table(model, test_set, test_metrics)
+                results, gts, *cols = evaluate_table(model, test_set, test_metrics, **tams)
             else:
-                results, gts = evaluate_windows(model, test_set, test_metrics)
+                results, gts, *cols = evaluate_windows(model, test_set, test_metrics, **tams)
     elif world > 1:                                                           # each rank tests batches rank::world
         results, gts = evaluate_model(model, _RankBatches(test_data, rank, world), test_set, test_metrics)
         comm = sharding.feature_comm(dev)
@@ -726,8 +845,14 @@ def _main_rank(flags, rank, world, dev):
         cams_file = os.path.join(flags.exp_root, flags.model_id, flags.split + "_cams.npz")
         save_cams(cams_file, **cols)
         print("Saved %d class activation maps %s: %s" % (len(cols["cam"]), tuple(cols["cam"].shape[1:]), cams_file))
+    elif flags.save_tams:
+        results, gts, *cols = evaluate_model_tams(model, test_data, test_set, test_metrics)
     else:
         results, gts = evaluate_model(model, test_data, test_set, test_metrics)
+    if flags.save_tams:
+        tams_file = os.path.join(flags.exp_root, flags.model_id, flags.split + "_tams.npz")
+        save_tams(tams_file, **cols[0])
+        print("Saved %d temporal activation maps of %d steps: %s" % (len(cols[0]["tam"]), cols[0]["tam"].shape[1], tams_file))
     str_ = "Test set:"                                                       # evaluate.py:250-255
     for i in range(len(test_set.classes)):
         str_ += "\n"

@@ -81,6 +81,19 @@ def table_chunks(idx, row_videos, max_rows):
     return out
 
 
+def _need_classes(model, what):
+    if not model.classes:
+        raise ValueError(f"{what}(..., return_tam=True) needs a model with classes (num_classes > 0): the maps are those of its Dense")
+
+
+def _scatter(out, ids, y, n):
+    """out[ids] = y for the pieces of a cut matrix; ``out`` (n, ...) is created from the first piece"""
+    if out is None:
+        out = torch.empty((n,) + tuple(y.shape[1:]), dtype=y.dtype, device=y.device)
+    out[torch.from_numpy(ids).to(y.device)] = y
+    return out
+
+
 class FrameModel(Block):
     """Reference definitions.py:10-33: backbone CNN + one Dense to the classes."""
 
@@ -129,50 +142,84 @@ class TemporalPooling(Block):
         else:                                          # definitions.py:60-61
             self.classes = Dense(num_classes, flatten=True, prefix=self.prefix + "dense0_")
 
-    def forward(self, x):
+    def _tam_check(self, what):
+        """``return_tam`` is for the max pool of a model with classes"""
+        if self.pool == "mean":
+            raise ValueError(f"{what}(..., return_tam=True) is for pool='max': a mean reads every step alike - its decomposition is the "
+                             "Dense applied to each step's features and divided by the window, which needs no step bookkeeping and "
+                             "which a caller can already compute; it is out of scope here")
+        _need_classes(self, what)
+
+    def _maps(self, y, steps, window):
+        """the Dense and its maps for pooled features ``y`` and their steps -> (logits, tam)"""
+        y = y.reshape(y.shape[0], -1)
+        return self.classes(y), self.classes.engine_for(y.shape[1]).step_maps(y, steps, window)
+
+    def forward(self, x, return_tam=False):
+        """``return_tam=True``: ``(logits, tam)`` with ``tam`` ``(N, classes, window)`` the temporal activation maps of the same
+        forward: the model ends in ``max over the window -> Dense``, so ``classes.bias[c] + tam[n, c].sum()`` is ``logits[n, c]``
+        exactly in real arithmetic, ``tam[n, c, t]`` being the part of the Dense's sum read from window step ``t`` (no backward
+        pass).  The logits are those of ``forward(x)``, bit for bit.  ``pool="max"`` and a model with ``classes`` only."""
+        if return_tam:
+            self._tam_check("forward")
         if not self.feats:
             x = self.td(x)                             # definitions.py:64-65
+        if return_tam:
+            x = _to_device(x)
+            return self._maps(*temporal_pool(x, "max", return_steps=True), x.shape[1])
         x = temporal_pool(_to_device(x), "mean" if self.pool == "mean" else "max")   # :66-69
         if self.classes:
             x = self.classes(x)
         return x
 
-    def forward_windows(self, features, centre, lo, hi, window, stride=1, max_rows=WINDOW_MAX_ROWS):
+    def forward_windows(self, features, centre, lo, hi, window, stride=1, max_rows=WINDOW_MAX_ROWS, return_tam=False):
         """``forward`` of every window of a (rows, F) feature matrix without materialising the (samples, window, F) batch: sample
         ``b`` pools the rows ``clamp(centre[b] + (t - window // 2) * stride, lo[b], hi[b])``, t = 0 .. window-1
-        (``TennisSet.window_rows``) -> logits (samples, classes).  Feature mode only."""
+        (``TennisSet.window_rows``) -> logits (samples, classes).  Feature mode only.  ``return_tam`` as in ``forward``."""
+        if return_tam:
+            self._tam_check("forward_windows")
         if not self.feats:
             raise NotImplementedError("forward_windows: feature mode only (TemporalPooling(..., feats=True))")
         x = _to_device(features).float()
         if x.dim() != 2:
             raise ValueError(f"forward_windows expects a (rows, F) feature matrix, got {tuple(x.shape)}")
         kind = "mean" if self.pool == "mean" else "max"
-        out = None
+        out, tam, n = None, None, len(_host_index(centre))
         for a, b, ids in window_chunks(centre, lo, hi, x.shape[0], max_rows):
             c, l, h = (_host_index(v)[ids] - a for v in (centre, lo, hi))
+            if return_tam:
+                y, t = self._maps(*temporal_pool_windows(x[a:b], c, l, h, window, stride, "max", return_steps=True), window)
+                out, tam = _scatter(out, ids, y, n), _scatter(tam, ids, t, n)
+                continue
             y = temporal_pool_windows(x[a:b], c, l, h, window, stride, kind)
             if self.classes:
                 y = self.classes(y)
             if out is None:
                 out = torch.empty((len(_host_index(centre)), y.shape[1]), dtype=torch.float32, device=y.device)
             out[torch.from_numpy(ids).to(y.device)] = y
-        return out
+        return (out, tam) if return_tam else out
 
-    def forward_table(self, features, idx, max_rows=WINDOW_MAX_ROWS, row_videos=None):
+    def forward_table(self, features, idx, max_rows=WINDOW_MAX_ROWS, row_videos=None, return_tam=False):
         """``forward`` of every window named by a row table (``TennisSet.window_table``): sample ``b`` pools the rows ``idx[b, t]`` of
         ``features`` (rows, F), t ascending -> logits (samples, classes).  Feature mode: ``features`` are the stored features.
         Frames mode: the rows ``self.td.model`` produced for the table's frames, each frame encoded once
         (``evaluate.encode_table``).  Any sample layout; ``row_videos`` (the video of every row) is needed only to cut a table of
-        more than ``max_rows`` rows."""
+        more than ``max_rows`` rows.  ``return_tam`` as in ``forward``."""
+        if return_tam:
+            self._tam_check("forward_table")
         x = _to_device(features).float()
         if x.dim() != 2:
             raise ValueError(f"forward_table expects a (rows, F) feature matrix, got {tuple(x.shape)}")
         kind = "mean" if self.pool == "mean" else "max"
         if x.shape[0] > max_rows and row_videos is None:
             raise ValueError(f"forward_table: a table of {x.shape[0]} rows over the budget of {max_rows} needs row_videos to be cut")
-        out, n = None, len(_host_index(idx))
+        out, tam, n = None, None, len(_host_index(idx))
         for a, b, ids, local in table_chunks(idx, row_videos if row_videos is not None else [0] * x.shape[0], max_rows):
             if not len(ids):
+                continue
+            if return_tam:
+                y, t = self._maps(*temporal_pool_rows(x[a:b], local, "max", return_steps=True), local.shape[1])
+                out, tam = _scatter(out, ids, y, n), _scatter(tam, ids, t, n)
                 continue
             y = temporal_pool_rows(x[a:b], local, kind)
             if self.classes:
@@ -180,7 +227,7 @@ class TemporalPooling(Block):
             if out is None:
                 out = torch.empty((n, y.shape[1]), dtype=torch.float32, device=y.device)
             out[torch.from_numpy(ids).to(y.device)] = y
-        return out
+        return (out, tam) if return_tam else out
 
 
 class CNNRNN(Block):
@@ -201,20 +248,33 @@ class CNNRNN(Block):
         elif num_classes > 0:
             self.classes = Dense(num_classes, flatten=True, prefix=self.prefix + "dense0_")
 
-    def forward(self, x):
+    def forward(self, x, return_tam=False):
+        """``return_tam=True``: ``(logits, tam)`` with ``tam`` ``(N, classes, window)`` the temporal activation maps of the same
+        forward: the model ends in ``max over the window -> Dense``, so ``classes.bias[c] + tam[n, c].sum()`` is ``logits[n, c]``
+        exactly in real arithmetic, ``tam[n, c, t]`` being the part of the Dense's sum read from the recurrent state of window step
+        ``t`` (no backward pass).  A state at step ``t`` has seen the steps before it (after it, in the reverse direction): the maps
+        say which step's state a logit was read from, not which single frame caused it.  The logits are those of ``forward(x)``, bit
+        for bit.  Needs a model with ``classes``."""
+        if return_tam:
+            _need_classes(self, "forward")
         if not self.feats:
             x = self.td(x)                                             # definitions.py:104-105
         x = self.rnn(x)                                                # :106
+        if return_tam:
+            pooled, steps = temporal_pool(x, "max", return_steps=True)
+            return self.classes(pooled), self.classes.engine_for(pooled.shape[1]).step_maps(pooled, steps, x.shape[1])
         x = temporal_pool(x, "max")                                    # :107
         if self.classes:
             x = self.classes(x)                                        # :108-109
         return x
 
-    def forward_windows(self, features, centre, lo, hi, window, stride=1, max_rows=WINDOW_MAX_ROWS):
+    def forward_windows(self, features, centre, lo, hi, window, stride=1, max_rows=WINDOW_MAX_ROWS, return_tam=False):
         """``forward`` of every window of a (rows, F) feature matrix with ONE i2h projection per row (``engine.WindowHead``): sample
         ``b`` runs over the rows ``clamp(centre[b] + (t - window // 2) * stride, lo[b], hi[b])``, t = 0 .. window-1
         (``TennisSet.window_rows``) -> logits (samples, classes).  Feature mode only.  A matrix of more than ``max_rows`` rows is cut
-        at video boundaries."""
+        at video boundaries.  ``return_tam`` as in ``forward``: the maps come out of the windowed kernel's own pass."""
+        if return_tam:
+            _need_classes(self, "forward_windows")
         if not self.feats:
             raise NotImplementedError("forward_windows: feature mode only (CNNRNN(model=None, ...))")
         if not self.classes:
@@ -228,12 +288,17 @@ class CNNRNN(Block):
         pieces = window_chunks(centre, lo, hi, x.shape[0], max_rows)
         eng = self._window_head(x.shape[1], max(b - a for a, b, _ in pieces), max(len(ids) for _, _, ids in pieces))
         if len(pieces) == 1:
-            return eng.project(x).forward(centre, lo, hi, window, stride)
+            return eng.project(x).forward(centre, lo, hi, window, stride, return_tam=return_tam)
         out = torch.empty((n, self.classes._units), dtype=torch.float32, device=x.device)
+        tam = torch.empty((n, self.classes._units, int(window)), dtype=torch.float32, device=x.device) if return_tam else None
         for a, b, ids in pieces:
             c, l, h = (_host_index(v)[ids] - a for v in (centre, lo, hi))
-            out[torch.from_numpy(ids).to(x.device)] = eng.project(x[a:b]).forward(c, l, h, window, stride)
-        return out
+            at = torch.from_numpy(ids).to(x.device)
+            if return_tam:
+                out[at], tam[at] = eng.project(x[a:b]).forward(c, l, h, window, stride, return_tam=True)
+            else:
+                out[at] = eng.project(x[a:b]).forward(c, l, h, window, stride)
+        return (out, tam) if return_tam else out
 
 
     def _window_head(self, width, need_rows, need_samples):
@@ -246,13 +311,15 @@ class CNNRNN(Block):
                                             self.classes.prefix, max_rows=need_rows, max_samples=need_samples)
         return eng
 
-    def forward_table(self, features, idx, max_rows=WINDOW_MAX_ROWS, row_videos=None):
+    def forward_table(self, features, idx, max_rows=WINDOW_MAX_ROWS, row_videos=None, return_tam=False):
         """``forward`` of every window named by a row table (``TennisSet.window_table``) with ONE i2h projection per row: sample ``b``
         runs over the rows ``idx[b, t]`` of ``features`` (rows, F), t = 0 .. window-1 -> logits (samples, classes).  Feature mode:
         ``features`` are the stored features.  Frames mode: the rows ``self.td.model`` (the model's own backbone) produced for the
         table's frames, each frame encoded once (``evaluate.encode_table``); their width must be the recurrent layer's input size.
         Any sample layout.  A table of more than ``max_rows`` rows is cut into pieces of whole videos, which needs ``row_videos``
-        (the video of every row of the table)."""
+        (the video of every row of the table).  ``return_tam`` as in ``forward``."""
+        if return_tam:
+            _need_classes(self, "forward_table")
         if not self.classes:
             raise NotImplementedError("forward_table returns logits: the model needs its Dense (num_classes > 0)")
         x = _to_device(features).float()
@@ -267,12 +334,19 @@ class CNNRNN(Block):
         pieces = table_chunks(idx, row_videos if row_videos is not None else [0] * x.shape[0], max_rows)
         eng = self._window_head(x.shape[1], max(b - a for a, b, _, _ in pieces), max(max(len(ids) for _, _, ids, _ in pieces), 1))
         if len(pieces) == 1:
-            return eng.project(x).forward_rows(pieces[0][3])
-        out = torch.empty((len(_host_index(idx)), self.classes._units), dtype=torch.float32, device=x.device)
+            return eng.project(x).forward_rows(pieces[0][3], return_tam=return_tam)
+        n, window = _host_index(idx).shape
+        out = torch.empty((n, self.classes._units), dtype=torch.float32, device=x.device)
+        tam = torch.empty((n, self.classes._units, window), dtype=torch.float32, device=x.device) if return_tam else None
         for a, b, ids, local in pieces:
-            if len(ids):
-                out[torch.from_numpy(ids).to(x.device)] = eng.project(x[a:b]).forward_rows(local)
-        return out
+            if not len(ids):
+                continue
+            at = torch.from_numpy(ids).to(x.device)
+            if return_tam:
+                out[at], tam[at] = eng.project(x[a:b]).forward_rows(local, return_tam=True)
+            else:
+                out[at] = eng.project(x[a:b]).forward_rows(local)
+        return (out, tam) if return_tam else out
 
 
 class TwoStreamModel(Block):
