@@ -555,6 +555,36 @@ int tn_gnmt_frames_trainer_clip_stats(tn_gnmt_frames_trainer *t, float *norm, fl
 int tn_prf1_update(tn_ctx *ctx, const float *logits, const int32_t *labels, int rows, int classes,
                    int64_t *mat);
 
+/* ---- events from per-frame logits (csrc/event_runs.hip; docs/kernels.md "Event decoding") ----
+ * Turns the (N, C) fp32 DEVICE logits of an evaluation into events "class c, positions first..last, score".  Has no counterpart in
+ * the reference, whose per-frame results go into visualise_events on the host.
+ *   inputs   rows (M,) int32: position m of the time-ordered list reads logits[clamp(rows[m], 0, N-1)], unconditionally (any
+ *            selection or permutation: a split's samples are not stored in time order); start (M,) int32: non-zero where position m
+ *            begins a new video, position 0 always does; width odd in [1, 63]; C in [1, 64].
+ *   p        p[m] = softmax of that row: maximum subtracted, accurate expf, the sum in ascending c, one division per value.
+ *   score    score[m, c] = (sum_{j = lo..hi} p[j, c]) / (hi - lo + 1), j ascending, lo = max(m - h, first position of m's video),
+ *            hi = min(m + h, last position of m's video), h = (width - 1) / 2: the direct sum of at most 63 terms, no sliding sum, so
+ *            that no score depends on where a tile begins.  A window of one position is p's bits, with no division.
+ *   label    label[m] = the first arg-max of score[m] (a tie goes to the smallest class), conf[m] = score[m, label[m]].
+ *   events   a maximal stretch of positions of one video with one label.  Per event first, last (positions, inclusive), cls,
+ *            peak = the maximum conf and score = the mean conf, summed in an order that depends on the event's own positions only
+ *            (lane l of a wave takes first + l, first + l + 64, ... ascending, then a six-level xor tree 32, 16, ..., 1; one
+ *            division by the length).  Events come out ordered by first; *count = K <= M.
+ * So a video decoded alone gives the bits of its events inside a whole-corpus call, nothing depends on grid or tile size, and there
+ * are no atomics on floats.  A run of the "other" class is an event too; smoothing moves boundaries by up to h positions.
+ * create: workspace for up to max_positions positions (9 bytes each and 8 per 128) - run allocates nothing.
+ * run: label_out (M,) int32 and conf_out (M,) fp32 may be NULL; ev_first, ev_last, ev_cls (int32) and ev_score, ev_peak (fp32) hold
+ * M entries each, of which the first K are written; count is ONE DEVICE int32.  stream: a hipStream_t, NULL = the context's
+ * stream; the call is asynchronous on it.  All pointers DEVICE.  TN_ERR_INVALID with the argument named in tn_last_error for: a
+ * null pointer (label_out / conf_out excepted), N < 1, C outside [1, 64] or past max_classes, an even width, width outside
+ * [1, 63], M < 1, M > max_positions. */
+typedef struct tn_event_decoder tn_event_decoder;
+int tn_event_decoder_create(tn_ctx *ctx, int max_positions, int max_classes, tn_event_decoder **out);
+int tn_event_decoder_run(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows, const int32_t *start, int M,
+                         int width, int32_t *label_out, float *conf_out, int32_t *ev_first, int32_t *ev_last, int32_t *ev_cls,
+                         float *ev_score, float *ev_peak, int32_t *count, void *stream);
+int tn_event_decoder_destroy(tn_event_decoder *d);
+
 /* ---- multi-GPU exchange: RCCL over xGMI, one process per GPU (csrc/comm.hip) ------------
  * The path's one exchange step (BASELINE config C4).  The reference splits every DataLoader batch over its ctx list and
  * exchanges the per-frame feature rows through the file system: evaluate.py:278-281,308-321 writes

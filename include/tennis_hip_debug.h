@@ -147,6 +147,11 @@ int tn_dbg_head_fused_launches(int64_t *count);
  * class_maps: the call is tn_densenet121_forward_class_maps.  Touches no device. */
 int tn_dbg_head_fused(int height, int width, int flags, int batch, int calibrate, int class_maps, int *fused);
 
+/* The event decoder's geometry (csrc/event_runs.hip): *tile = positions per workgroup of its score and scatter kernels, *scan_block =
+ * tile counts its one scan workgroup takes per step (more tiles than that make it loop).  Tests place their edge shapes from these.
+ * Touches no device. */
+int tn_dbg_event_decoder_geometry(int *tile, int *scan_block);
+
 /* The LDS-resident 7x7 dense block (csrc/dense_block7.hip): nl layers from K0 input channels in ONE launch on a device
  * concat buffer (B,7,7,ldc) fp16.  w1_all: the (128, K_l) 1x1 weights one after the other (K_l = K0 + 32 l); s1_all / t1_all
  * folded BN1 scale / shift (K_l each); s2_all / t2_all folded BN2 scale / shift (128 per layer); w3_all nl x (32,128,3,3). */

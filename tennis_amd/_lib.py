@@ -110,6 +110,10 @@ _SIGS = {
     "tn_temporal_pool_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "tn_dbg_window_head_rows_per_group": (C.c_int, [_P, C.c_int]),
     "tn_prf1_update": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "tn_event_decoder_create": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
+    "tn_event_decoder_run": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tn_event_decoder_destroy": (C.c_int, [_P]),
+    "tn_dbg_event_decoder_geometry": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tn_head_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_char_p, C.c_int,
                                  C.c_int, C.POINTER(_P)]),
     "tn_head_forward_backward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),

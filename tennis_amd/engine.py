@@ -338,6 +338,54 @@ class Dense(_Handle):
         return tam
 
 
+def event_decoder_geometry():
+    """``tn_dbg_event_decoder_geometry``: (positions per workgroup of the score kernel, tile counts per step of the one scan
+    workgroup); touches no device."""
+    tile, scan = C.c_int(), C.c_int()
+    check(_lib.load().tn_dbg_event_decoder_geometry(C.byref(tile), C.byref(scan)), "tn_dbg_event_decoder_geometry")
+    return tile.value, scan.value
+
+
+class EventDecoder(_Handle):
+    """Per-frame logits -> events on the device (``tn_event_decoder_*``, docs/kernels.md "Event decoding"): workspace for up to
+    ``max_positions`` positions of up to ``classes`` classes; ``decode`` allocates its outputs only."""
+
+    _ABI = "tn_event_decoder"
+
+    def __init__(self, max_positions: int, classes: int, ctx: _lib.Context | None = None):
+        super().__init__(ctx)
+        self.max_positions, self.classes = int(max_positions), int(classes)
+        h = C.c_void_p()
+        check(self.lib.tn_event_decoder_create(self.ctx.handle, self.max_positions, self.classes, C.byref(h)), "tn_event_decoder_create")
+        self.handle = h
+
+    def decode(self, logits: torch.Tensor, rows, start, smooth: int = 1, return_frames: bool = False):
+        """``logits`` (N, C) fp32 on the GPU; ``rows`` (M,) the logit row of every position of the time-ordered list (clamped into
+        ``[0, N)``), ``start`` (M,) non-zero where a video begins, ``smooth`` the odd window width in [1, 63].  Returns a dict of
+        tensors on the GPU, one entry per event in order of ``first``: ``first``, ``last`` (positions, inclusive), ``cls`` (int32),
+        ``score`` the mean and ``peak`` the maximum of the smoothed score of ``cls`` over the event (float32); with
+        ``return_frames`` also ``label`` (M,) int32 and ``conf`` (M,) float32 of every position.  Synchronises once, for the count."""
+        _on_ctx_device(self.ctx, logits, "EventDecoder.decode")
+        if logits.dim() != 2 or logits.dtype != torch.float32:
+            raise ValueError(f"EventDecoder.decode: logits must be (N, C) float32, got {tuple(logits.shape)} {logits.dtype}")
+        logits = logits.contiguous()
+        rows, start = _index_arrays(logits.device, rows, start)
+        m, dev = rows.shape[0], logits.device
+        ints = torch.empty((3, max(m, 1)), dtype=torch.int32, device=dev)
+        flts = torch.empty((2, max(m, 1)), dtype=torch.float32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        label = torch.empty(m, dtype=torch.int32, device=dev) if return_frames else None
+        conf = torch.empty(m, dtype=torch.float32, device=dev) if return_frames else None
+        check(self.lib.tn_event_decoder_run(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start), m, int(smooth),
+                                            ptr(label), ptr(conf), ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(flts[0]), ptr(flts[1]),
+                                            ptr(count), None), "tn_event_decoder_run")        # (stream NULL: the context's)
+        k = int(count.item())
+        out = dict(first=ints[0, :k], last=ints[1, :k], cls=ints[2, :k], score=flts[0, :k], peak=flts[1, :k])
+        if return_frames:
+            out.update(label=label, conf=conf)
+        return out
+
+
 
 class BiRNN(_Handle):
     """``mx.gluon.rnn.GRU/LSTM(hidden, layout='NTC', bidirectional=...)`` (definitions.py:94-96)."""

@@ -26,18 +26,28 @@ import numpy as np
 import torch
 
 from . import sharding, transforms
+from .events import check_save_events, decode_split, event_table, save_events
 from .dataset import DataLoader, TennisSet
 from .metrics.vision import PRF1
 from .model_zoo import get_model
 from .models.vision.definitions import CNNRNN, FrameModel, TemporalPooling
 
 
-def evaluate_model(net, loader, dataset, metrics, ctx=None):
+def _keep_logits(keep, outputs, idxs):
+    """``keep`` (a dict, or None: nothing happens) collects what ``--save_events`` decodes: the device logits of every batch and the
+    dataset index of every row, in loader order."""
+    if keep is not None:
+        keep.setdefault("logits", []).append(outputs)
+        keep.setdefault("order", []).extend(int(j) for j in idxs)
+
+
+def evaluate_model(net, loader, dataset, metrics, ctx=None, keep=None):
     """Reference evaluate.py:274-303: forward, metric.update, results[img_path] = raw
-    logits, ground_truths[img_path] = class index."""
+    logits, ground_truths[img_path] = class index.  ``keep``: ``_keep_logits``."""
     results, ground_truths = dict(), dict()
     for data, labels, idxs in loader:
         outputs = net(data)
+        _keep_logits(keep, outputs, idxs)
         lab = torch.from_numpy(labels).to(outputs.device)
         for metric in metrics:
             metric.update([lab], [outputs])
@@ -69,7 +79,7 @@ def check_save_cams(flags, world=1):
         raise SystemExit("--save_cams writes one file from one rank: run it with --num_gpus 1")
 
 
-def evaluate_model_cams(net, loader, dataset, metrics):
+def evaluate_model_cams(net, loader, dataset, metrics, keep=None):
     """``evaluate_model`` of a ``FrameModel`` through ``forward(x, return_cam=True)``: the same logits (bit for bit), the same
     metric updates and return values, and as a third value the columns of ``save_cams`` in loader order - per frame the map of
     its arg-max class ``cam (N, h, w)``, ``pred``, ``label``, that class's ``logit``, ``video`` and ``frame``."""
@@ -77,6 +87,7 @@ def evaluate_model_cams(net, loader, dataset, metrics):
     cols = {k: [] for k in ("cam", "pred", "label", "logit", "video", "frame")}
     for data, labels, idxs in loader:
         outputs, cam = net(data, return_cam=True)
+        _keep_logits(keep, outputs, idxs)
         lab = torch.from_numpy(labels).to(outputs.device)
         for metric in metrics:
             metric.update([lab], [outputs])
@@ -166,13 +177,14 @@ def tam_columns(net, dataset, order, outputs, tam):
                 frames=np.asarray([dataset.window_frames(s) for s in samples], np.int64).reshape(len(samples), -1), bias=bias[pred])
 
 
-def evaluate_model_tams(net, loader, dataset, metrics):
+def evaluate_model_tams(net, loader, dataset, metrics, keep=None):
     """``evaluate_model`` of a windowed ``CNNRNN`` / ``TemporalPooling(max)`` through ``forward(x, return_tam=True)``: the same
     logits (bit for bit), metric updates and return values, and as a third value the columns of ``save_tams`` in loader order."""
     results, ground_truths = dict(), dict()
     outs, tams, order = [], [], []
     for data, labels, idxs in loader:
         outputs, tam = net(data, return_tam=True)
+        _keep_logits(keep, outputs, idxs)
         lab = torch.from_numpy(labels).to(outputs.device)
         for metric in metrics:
             metric.update([lab], [outputs])
@@ -256,7 +268,7 @@ def load_feature_table(dataset, frames):
     return read_rows(lambda r: np.load(path(frames[r])), len(frames))
 
 
-def evaluate_windows(net, dataset, metrics, features=None, batch_size=65536, return_tams=False):
+def evaluate_windows(net, dataset, metrics, features=None, batch_size=65536, return_tams=False, keep=None):
     """``evaluate_model`` for a windowed feature-mode model (``CNNRNN`` / ``TemporalPooling``) without the loader: the
     dataset-order feature matrix (``features``: (len(dataset), F), e.g. what ``save_features_sharded`` returned; None: loaded from
     the ``.npy`` files, each once) goes to the device once, ``net.forward_windows`` evaluates every sample's window from it
@@ -271,6 +283,7 @@ def evaluate_windows(net, dataset, metrics, features=None, batch_size=65536, ret
     outputs = net.forward_windows(features, centre, lo, hi, dataset._window, row_stride, return_tam=return_tams)
     if return_tams:
         outputs, tam = outputs
+    _keep_logits(keep, outputs, range(len(dataset)))
     labels = torch.tensor([dataset.classes.index(s[2]) for s in dataset._samples], dtype=torch.float32, device=outputs.device)
     for a in range(0, len(dataset), batch_size):
         for metric in metrics:
@@ -317,7 +330,7 @@ def encode_table(net_backbone, dataset, frames, batch_size=64, num_workers=0):
 
 
 def evaluate_table(net, dataset, metrics, features=None, frames_idx=None, batch_size=64, num_workers=0, metric_batch=65536,
-                   return_tams=False):
+                   return_tams=False, keep=None):
     """``evaluate_windows`` through a row table (``TennisSet.window_table`` + ``net.forward_table``): any ``every``, ``stride``,
     ``padding`` and split layout the loader route accepts, in feature mode and on frames.  ``frames_idx``: ``(frames, idx)`` of
     ``dataset.window_table()`` if the caller has it.  ``features``: the (len(frames), F) table; None: in feature mode it is loaded
@@ -335,6 +348,7 @@ def evaluate_table(net, dataset, metrics, features=None, frames_idx=None, batch_
     outputs = net.forward_table(features, idx, row_videos=[v for v, _ in frames], return_tam=return_tams)
     if return_tams:
         outputs, tam = outputs
+    _keep_logits(keep, outputs, range(len(dataset)))
     labels = torch.tensor([dataset.classes.index(s[2]) for s in dataset._samples], dtype=torch.float32, device=outputs.device)
     for a in range(0, len(dataset), metric_batch):
         for metric in metrics:
@@ -693,6 +707,16 @@ def build_parser():
                         "video, the centre frame and the frame number every window step read (evaluate.load_tams reads it).  A map "
                         "names the step whose state the logit was read from - a recurrent state has seen the steps before it - not "
                         "a single frame that caused it.  The maps come out of the same forward, the metrics do not change")
+    p.add_argument("--save_events", action="store_true",
+                   help="also decode the per-sample logits into events on the GPU (every route that yields them: the frame model, windowed "
+                        "models on the loader route, --dense_windows on stored features and on frames; one rank; not a reference flag) "
+                        "and write <split>_events.npz into the experiment's directory - per predicted event the video, first and last "
+                        "frame, class, mean and peak score, per ground-truth event (runs of one label in time order) the same without "
+                        "scores, and event precision / recall / F1 at tIoU 0.1, 0.3, 0.5 (events.load_events reads it).  A run of the "
+                        "background class is an event too.  The per-frame scores and results do not change")
+    p.add_argument("--event_smooth", type=int, default=None,
+                   help="with --save_events: odd width in [1, 63] of the window the class probabilities are averaged over before the "
+                        "arg-max (cut at video boundaries; default 1, no smoothing).  Moves event boundaries by up to (width - 1) / 2 frames")
     return p
 
 
@@ -700,6 +724,7 @@ def main(argv=None):
     flags = build_parser().parse_args(argv)
     check_save_cams(flags)                                                  # refusals before any device work
     check_save_tams(flags)
+    check_save_events(flags)
     if flags.num_gpus > 1 and not sharding.under_launcher():
         # evaluate.py:101-102 builds ctx = [gpu(0) .. gpu(N-1)] in one process; here: one process per GPU
         if torch.cuda.is_available() and flags.num_gpus > torch.cuda.device_count():
@@ -726,7 +751,9 @@ def _main_rank(flags, rank, world, dev):
     check_dense_windows(flags)                                              # refusals before anything is built
     check_save_cams(flags, world)
     check_save_tams(flags, world)
+    check_save_events(flags, world)
     flags.save_tams = getattr(flags, "save_tams", False)                    # (flags built by hand, without the newer switches)
+    flags.save_events = getattr(flags, "save_events", False)
     if flags.corpus_frames > 0:                                            # BASELINE config C4
         backbone = get_model(flags.backbone, pretrained=True, max_batch=flags.batch_size, conversion=flags.fp16_conversion).features
         full, st = extract_corpus(backbone, flags.corpus_frames, flags.batch_size, flags.data_shape, dev, rank, world,
@@ -809,6 +836,9 @@ def _main_rank(flags, rank, world, dev):
     tic = time.time()
     tams = {"return_tams": True} if flags.save_tams else {}                 # (a call without the flag is the call it was)
     cols = None
+    kept = {} if flags.save_events else None                                # (None: every call below is the call it was)
+    keep = {} if kept is None else {"keep": kept}
+    tams = dict(tams, **keep)
     if flags.dense_windows:
         route = check_dense_windows(flags)
         if rank != 0:                                                       # one pass over one matrix: nothing to shard
@@ -841,18 +871,25 @@ def _main_rank(flags, rank, world, dev):
         if rank != 0:
             return 0
     elif flags.save_cams:
-        results, gts, cols = evaluate_model_cams(model, test_data, test_set, test_metrics)
+        results, gts, cols = evaluate_model_cams(model, test_data, test_set, test_metrics, **keep)
         cams_file = os.path.join(flags.exp_root, flags.model_id, flags.split + "_cams.npz")
         save_cams(cams_file, **cols)
         print("Saved %d class activation maps %s: %s" % (len(cols["cam"]), tuple(cols["cam"].shape[1:]), cams_file))
     elif flags.save_tams:
-        results, gts, *cols = evaluate_model_tams(model, test_data, test_set, test_metrics)
+        results, gts, *cols = evaluate_model_tams(model, test_data, test_set, test_metrics, **keep)
     else:
-        results, gts = evaluate_model(model, test_data, test_set, test_metrics)
+        results, gts = evaluate_model(model, test_data, test_set, test_metrics, **keep)
     if flags.save_tams:
         tams_file = os.path.join(flags.exp_root, flags.model_id, flags.split + "_tams.npz")
         save_tams(tams_file, **cols[0])
         print("Saved %d temporal activation maps of %d steps: %s" % (len(cols[0]["tam"]), cols[0]["tam"].shape[1], tams_file))
+    if kept is not None:                                                     # the logits never left the device: decode them there
+        ev_cols, ev_metric = decode_split(test_set, torch.cat(kept["logits"]), kept["order"], smooth=getattr(flags, "event_smooth", None) or 1)
+        events_file = os.path.join(flags.exp_root, flags.model_id, flags.split + "_events.npz")
+        save_events(events_file, **ev_cols)
+        print(event_table(ev_cols, test_set.classes))
+        print("[Events] " + ", ".join("{}={:.3f}".format(k, v) for k, v in ev_metric.get() if k.startswith("AVG_")))
+        print("Saved %d events (%d ground truth): %s" % (len(ev_cols["video"]), len(ev_cols["gt_video"]), events_file))
     str_ = "Test set:"                                                       # evaluate.py:250-255
     for i in range(len(test_set.classes)):
         str_ += "\n"

@@ -1,0 +1,148 @@
+"""From per-sample logits to events: the host side of ``evaluate --save_events`` (the decoding itself is ``engine.EventDecoder``).
+
+A split's samples are not stored in time order (balancing thins them, splits interleave videos), so ``time_order`` sorts them once
+per split on the host into the position list the decoder walks; ``label_runs`` applies the decoder's run rule to integer labels, which
+is where the ground-truth events come from (not from ``TennisSet._events``, which opens every video with an empty ``OTH`` run and is
+built before balancing); ``save_events`` / ``load_events`` keep one ``.npz`` of flat arrays.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+EVENT_COLUMNS = ("video", "first_frame", "last_frame", "cls", "score", "peak", "first_sample", "last_sample",
+                 "gt_video", "gt_first_frame", "gt_last_frame", "gt_cls", "smooth", "tiou", "precision", "recall", "f1")
+MAX_SMOOTH = 63
+
+
+def check_save_events(flags, world=1):
+    """``--save_events`` is for a test run that yields per-sample logits, on one rank: exits with the reason otherwise.  Touches no
+    device."""
+    smooth = getattr(flags, "event_smooth", None)
+    if not getattr(flags, "save_events", False):
+        if smooth is not None:
+            raise SystemExit("--event_smooth %s sets the smoothing window of --save_events: give --save_events too" % smooth)
+        return
+    if smooth is not None and (smooth < 1 or smooth > MAX_SMOOTH or smooth % 2 == 0):
+        raise SystemExit("--event_smooth %d: the smoothing window is centred on a frame, so it must be odd, and it is summed directly, "
+                         "so it must lie in [1, %d]" % (smooth, MAX_SMOOTH))
+    if flags.save_feats:
+        raise SystemExit("--save_events decodes the logits of a test run: not together with --save_feats")
+    if flags.corpus_frames > 0:
+        raise SystemExit("--save_events writes the events of a split's samples: --corpus_frames runs a synthetic corpus that has none")
+    if flags.num_gpus > 1 or world > 1:
+        raise SystemExit("--save_events decodes one time-ordered list on one rank: run it with --num_gpus 1")
+
+
+def time_order(dataset, order=None):
+    """-> ``(rows, start, video, frame)`` of the time-ordered position list: ``rows (M,)`` int32 the logit row of every position,
+    ``start (M,)`` int32 1 where a video begins, ``video (M,)`` unicode and ``frame (M,)`` int64 of every position.  ``order``: the
+    dataset index whose logits row r holds (None: row r is sample r).  Samples are sorted by (video, frame number) with a stable
+    sort, on the host."""
+    order = np.arange(len(dataset._samples)) if order is None else np.asarray(order, np.int64).reshape(-1)
+    samples = [dataset._samples[int(i)] for i in order]
+    video = np.asarray([s[0] for s in samples], dtype=np.str_)
+    frame = np.asarray([int(s[1]) for s in samples], np.int64)
+    rows = np.lexsort((frame, video)) if len(samples) else np.zeros(0, np.int64)      # (lexsort is stable; the last key is the primary)
+    video, frame = video[rows], frame[rows]
+    start = np.ones(len(rows), np.int32)
+    if len(rows) > 1:
+        start[1:] = video[1:] != video[:-1]
+    return rows.astype(np.int32), start, video, frame
+
+
+def label_runs(labels, start):
+    """The decoder's run rule on integer labels: a run begins where ``start`` is non-zero (position 0 always) or the label differs from
+    the one before.  -> ``(first, last, cls)`` int64 arrays, positions inclusive, ordered by ``first``."""
+    labels = np.asarray(labels, np.int64).reshape(-1)
+    start = np.asarray(start).reshape(-1) != 0
+    if len(labels) != len(start):
+        raise ValueError(f"label_runs: {len(labels)} labels for {len(start)} start flags")
+    if not len(labels):
+        z = np.zeros(0, np.int64)
+        return z, z.copy(), z.copy()
+    begins = start.copy()
+    begins[0] = True
+    begins[1:] |= labels[1:] != labels[:-1]
+    first = np.flatnonzero(begins)
+    last = np.append(first[1:], len(labels)) - 1
+    return first, last, labels[first]
+
+
+def save_events(file_path, video, first_frame, last_frame, cls, score, peak, first_sample, last_sample, gt_video, gt_first_frame,
+                gt_last_frame, gt_cls, smooth, tiou, precision, recall, f1):
+    """One ``.npz`` of flat arrays (``np.load(..., allow_pickle=False)`` reads it).  Per predicted event ``video`` (unicode),
+    ``first_frame`` / ``last_frame`` (frame numbers, inclusive), ``cls``, ``score`` the mean and ``peak`` the maximum of the smoothed
+    score of ``cls``, ``first_sample`` / ``last_sample`` (dataset indices of the two end frames); per ground-truth event ``gt_video``,
+    ``gt_first_frame``, ``gt_last_frame``, ``gt_cls``; ``smooth`` the window width, ``tiou (T,)`` the thresholds and ``precision``,
+    ``recall``, ``f1`` (T, classes) of ``metrics.events.EventPRF1``.  A run of the background class is an event too, and smoothing
+    moves boundaries by up to (smooth - 1) / 2 frames."""
+    i64 = lambda a: np.asarray(a, np.int64).reshape(-1)
+    f32 = lambda a: np.asarray(a, np.float32).reshape(-1)
+    txt = lambda a: np.asarray(list(a), dtype=np.str_).reshape(-1)
+    cols = dict(video=txt(video), first_frame=i64(first_frame), last_frame=i64(last_frame), cls=i64(cls), score=f32(score), peak=f32(peak),
+                first_sample=i64(first_sample), last_sample=i64(last_sample), gt_video=txt(gt_video), gt_first_frame=i64(gt_first_frame),
+                gt_last_frame=i64(gt_last_frame), gt_cls=i64(gt_cls), smooth=np.asarray(int(smooth), np.int64),
+                tiou=np.asarray(tiou, np.float64).reshape(-1), precision=np.asarray(precision, np.float64),
+                recall=np.asarray(recall, np.float64), f1=np.asarray(f1, np.float64))
+    n, g, t = len(cols["video"]), len(cols["gt_video"]), len(cols["tiou"])
+    for k in ("first_frame", "last_frame", "cls", "score", "peak", "first_sample", "last_sample"):
+        if len(cols[k]) != n:
+            raise ValueError(f"save_events: {k} has {len(cols[k])} entries for {n} events")
+    for k in ("gt_first_frame", "gt_last_frame", "gt_cls"):
+        if len(cols[k]) != g:
+            raise ValueError(f"save_events: {k} has {len(cols[k])} entries for {g} ground-truth events")
+    for k in ("precision", "recall", "f1"):
+        if cols[k].ndim != 2 or cols[k].shape[0] != t:
+            raise ValueError(f"save_events: {k} must be ({t}, classes), got {cols[k].shape}")
+    os.makedirs(os.path.dirname(os.path.abspath(file_path)), exist_ok=True)
+    np.savez(file_path, **cols)
+
+
+def load_events(file_path):
+    """-> dict of ``save_events``' arrays (``EVENT_COLUMNS``)."""
+    with np.load(file_path, allow_pickle=False) as z:
+        d = {k: z[k] for k in z.files}
+    missing = [k for k in EVENT_COLUMNS if k not in d]
+    if missing:
+        raise ValueError(f"{file_path}: not a file of save_events (no {', '.join(missing)})")
+    return d
+
+
+def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), decoder=None):
+    """The events of one evaluated split: ``logits`` (N, classes) fp32 ON THE GPU, row r the logits of sample ``order[r]`` (None:
+    of sample r).  The positions are time-ordered on the host (``time_order``), decoded on the device (``engine.EventDecoder``; only
+    the events come back), the ground truth is ``label_runs`` of the samples' labels, both are scored with ``EventPRF1``.
+    -> ``(columns of save_events, EventPRF1)``."""
+    from .engine import EventDecoder
+    from .metrics.events import EventPRF1
+    rows, start, video, frame = time_order(dataset, order)
+    order = np.arange(len(dataset._samples)) if order is None else np.asarray(order, np.int64).reshape(-1)
+    decoder = decoder or EventDecoder(len(rows), logits.shape[1])
+    ev = {k: v.cpu().numpy() for k, v in decoder.decode(logits, rows, start, smooth=smooth).items()}
+    first, last = ev["first"].astype(np.int64), ev["last"].astype(np.int64)
+    labels = np.asarray([dataset.classes.index(dataset._samples[int(i)][2]) for i in order[rows]], np.int64)
+    gfirst, glast, gcls = label_runs(labels, start)
+    pred = dict(video=video[first], first_frame=frame[first], last_frame=frame[last], cls=ev["cls"].astype(np.int64), score=ev["score"])
+    gt = dict(video=video[gfirst], first_frame=frame[gfirst], last_frame=frame[glast], cls=gcls)
+    metric = EventPRF1(dataset.classes, tious=tious)
+    metric.update(pred, gt)
+    prec, rec, f1 = metric.arrays()
+    cols = dict(pred, peak=ev["peak"], first_sample=order[rows[first]], last_sample=order[rows[last]], gt_video=gt["video"],
+                gt_first_frame=gt["first_frame"], gt_last_frame=gt["last_frame"], gt_cls=gt["cls"], smooth=int(smooth),
+                tiou=np.asarray(metric.tious), precision=prec, recall=rec, f1=f1)
+    return cols, metric
+
+
+def event_table(cols, classes, limit=40):
+    """The printed form of ``decode_split``'s columns: one line per predicted event (the first ``limit``), then the scores."""
+    n = len(cols["video"])
+    lines = ["Events: %d predicted, %d ground truth (smooth %d)" % (n, len(cols["gt_video"]), int(cols["smooth"]))]
+    for i in range(min(n, limit)):
+        lines.append("  %s\t%s\tframes %d-%d\tscore %.3f\tpeak %.3f" % (cols["video"][i], classes[int(cols["cls"][i])],
+                                                                      cols["first_frame"][i], cols["last_frame"][i],
+                                                                      cols["score"][i], cols["peak"][i]))
+    if n > limit:
+        lines.append("  ... %d more" % (n - limit))
+    return "\n".join(lines)
