@@ -585,6 +585,29 @@ int tn_event_decoder_run(tn_event_decoder *d, const float *logits, int N, int C,
                          float *ev_score, float *ev_peak, int32_t *count, void *stream);
 int tn_event_decoder_destroy(tn_event_decoder *d);
 
+/* The same events from the label path that maximises the sum of the per-position scores minus switch_cost for every change of label
+ * inside a video (a Potts model, decoded with Viterbi; docs/kernels.md "Event decoding with a switch cost").  Arguments as
+ * tn_event_decoder_run, with float switch_cost (finite, >= 0, in logit = natural-log units) in place of the window width.
+ *   e        e[m, c] = q[c] - max_c q[c], q = logits[clamp(rows[m], 0, N-1)], fp32.  The log-sum-exp is not subtracted: it is the
+ *            same for every class of a position and cannot change the path.
+ *   forward  per video, positions t = 0 .. T-1 in order, fp32:  v_0 = e_0;  stay_t[c] = (v_{t-1}[c] >= -switch_cost);
+ *            u_t[c] = e_t[c] + max(v_{t-1}[c], -switch_cost);  v_t[c] = u_t[c] - max_c u_t[c];  a_t = the first arg-max of v_t.
+ *            The best predecessor scores 0 after the normalisation, so switching in is worth exactly -switch_cost, and every value
+ *            stays within [-(switch_cost + max|e|), 0] however long the video is.  A tie between staying and switching stays.
+ *   back     label[T-1] = a_{T-1};  label[t-1] = stay_t[label[t]] ? label[t] : a_{t-1}.
+ *   conf     conf[m] = softmax(q)[label[m]]: maximum subtracted, accurate expf, the sum in ascending c, one division - the bits
+ *            tn_event_decoder_run gives at width 1 for that class.
+ *   events   from label, conf and start exactly as tn_event_decoder_run's.
+ * The order is sequential by definition (fp32 max-plus does not round associatively): one workgroup walks one video, no workgroup
+ * waits on another, there are no atomics on floats, and no value depends on the grid or on the tile, so a video decoded alone gives
+ * the bits it gives inside a whole-corpus call.  switch_cost = 0 gives the first arg-max of every row that has no tied maximum.
+ * The first call allocates the path workspace inside the handle (13 bytes per position of max_positions; TN_ERR_NOMEM with the size
+ * in tn_last_error if that fails); later calls allocate nothing, and tn_event_decoder_run never touches it.  TN_ERR_INVALID as
+ * tn_event_decoder_run, and for a switch_cost that is negative, NaN or infinite. */
+int tn_event_decoder_run_switch(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows, const int32_t *start,
+                                int M, float switch_cost, int32_t *label_out, float *conf_out, int32_t *ev_first, int32_t *ev_last,
+                                int32_t *ev_cls, float *ev_score, float *ev_peak, int32_t *count, void *stream);
+
 /* ---- multi-GPU exchange: RCCL over xGMI, one process per GPU (csrc/comm.hip) ------------
  * The path's one exchange step (BASELINE config C4).  The reference splits every DataLoader batch over its ctx list and
  * exchanges the per-frame feature rows through the file system: evaluate.py:278-281,308-321 writes

@@ -152,6 +152,14 @@ int tn_dbg_head_fused(int height, int width, int flags, int batch, int calibrate
  * Touches no device. */
 int tn_dbg_event_decoder_geometry(int *tile, int *scan_block);
 
+/* The switch-cost path decoder's geometry: *tile = positions of a video its forward and backtrack kernels take per step (the rows
+ * staged into LDS while the walking wave consumes the tile before).  Touches no device. */
+int tn_dbg_event_decoder_switch_geometry(int *tile);
+
+/* Device bytes the handle holds: what tn_event_decoder_create allocated, plus the path workspace once the first
+ * tn_event_decoder_run_switch has allocated it.  Touches no device. */
+int tn_dbg_event_decoder_workspace_bytes(const tn_event_decoder *d, size_t *bytes);
+
 /* The LDS-resident 7x7 dense block (csrc/dense_block7.hip): nl layers from K0 input channels in ONE launch on a device
  * concat buffer (B,7,7,ldc) fp16.  w1_all: the (128, K_l) 1x1 weights one after the other (K_l = K0 + 32 l); s1_all / t1_all
  * folded BN1 scale / shift (K_l each); s2_all / t2_all folded BN2 scale / shift (128 per layer); w3_all nl x (32,128,3,3). */

@@ -112,8 +112,11 @@ _SIGS = {
     "tn_prf1_update": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "tn_event_decoder_create": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     "tn_event_decoder_run": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tn_event_decoder_run_switch": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tn_event_decoder_destroy": (C.c_int, [_P]),
     "tn_dbg_event_decoder_geometry": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tn_dbg_event_decoder_switch_geometry": (C.c_int, [C.POINTER(C.c_int)]),
+    "tn_dbg_event_decoder_workspace_bytes": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     "tn_head_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TnParam), C.c_int, C.c_char_p, C.c_char_p, C.c_int,
                                  C.c_int, C.POINTER(_P)]),
     "tn_head_forward_backward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),

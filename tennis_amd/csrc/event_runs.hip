@@ -14,7 +14,24 @@
 //   4 event_reduce_kernel   one wave per event (grid-stride over K, which only the device knows): lane l takes the positions
 //                           first + l, first + l + 64, ... in ascending order, then a six-level xor tree (32, 16, ..., 1) as
 //                           class_maps_kernel's; score = sum / length.  The order depends on the event's own positions only.
+//
+// With a switch cost (tn_event_decoder_run_switch; docs/kernels.md "Event decoding with a switch cost") label comes from the path that
+// maximises sum_m e[m, label[m]] - cost * (changes of label inside a video), e[m, c] = q[c] - max_c q[c]:
+//   forward   v_0 = e_0;  stay_t[c] = (v_{t-1}[c] >= -cost);  u_t[c] = e_t[c] + max(v_{t-1}[c], -cost);  v_t = u_t - max_c u_t;
+//             a_t = first arg-max of v_t          (fp32, positions in order: the sequential order is the definition)
+//   back      label[T-1] = a_{T-1};  label[t-1] = stay_t[label[t]] ? label[t] : a_{t-1}
+//   conf[m]   = softmax(q)[label[m]], computed as event_score_kernel computes p
+// Nine plain launches: the video bounds are the set flags of `start`, found with the scan and scatter above; then
+//   viterbi_forward_kernel    one workgroup per video (grid-stride over the videos, whose number only the device knows).  Wave 0 walks
+//                             the chain, lane c holding v[c]; the maximum is a DPP all-reduce, stay and the arg-max one ballot each.
+//                             Waves 1..3 gather the next tile of kViterbiTile rows and store e into the other half of the LDS.
+//   viterbi_backtrack_kernel  one wave per video, tiles back to front: lane j holds stay_{t+1} and a_t of its position, the tile in
+//                             front is in flight while the wave walks this one with scalar selects
+//   event_flag_kernel<true>   one thread per position: conf, the run-start flags and the tile counts - what event_score_kernel
+//                             leaves behind, so that scan, scatter and reduce run unchanged
 #include "common.h"
+
+#include <cmath>
 
 namespace {
 
@@ -205,6 +222,231 @@ __global__ __launch_bounds__(256) void event_reduce_kernel(const int32_t *__rest
   }
 }
 
+// ---- the switch-cost path ----
+
+constexpr int kViterbiTile = 64;         // positions of a video per step of the forward and backtrack kernels
+constexpr int kViterbiThreads = 256;     // forward: wave 0 walks, the other waves stage
+constexpr int kViterbiStageWaves = kViterbiThreads / 64 - 1;
+constexpr int kViterbiRowsPerWave = (kViterbiTile + kViterbiStageWaves - 1) / kViterbiStageWaves;
+constexpr int kViterbiChunk = 8;         // positions the walking wave reads ahead of the chain
+constexpr int kViterbiMaxGrid = 1024;    // workgroups of the two chain kernels (any number of videos: they loop)
+constexpr int kEventMaxClasses = 64;     // one lane per class
+
+// static LDS of the forward kernel: two tiles of e, rows kEventMaxClasses wide whatever C is (the lanes past C hold -inf)
+__host__ __device__ constexpr size_t viterbi_lds_bytes() { return (size_t)2 * kViterbiTile * kEventMaxClasses * 4; }
+static_assert(viterbi_lds_bytes() <= 64 * 1024, "the forward kernel stays inside the default LDS limit");
+static_assert(kViterbiTile == 64, "a tile's stay masks and arg-maxima are kept one position per lane");
+static_assert(kViterbiTile % kViterbiChunk == 0, "whole chunks");
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
+}
+
+__device__ __forceinline__ float lane_f32(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
+
+// The maximum over the wave, the same in every lane; call it with all 64 lanes active.  A maximum is exact, so its order is free.
+// ONE_ROW: only lanes 0..15 can hold it (C <= 16, the others hold -inf).
+template <bool ONE_ROW>
+__device__ __forceinline__ float wave_max(float x) {
+  x = fmaxf(x, dpp_f32<0xB1>(x));        // quad_perm [1, 0, 3, 2]
+  x = fmaxf(x, dpp_f32<0x4E>(x));        // quad_perm [2, 3, 0, 1]
+  x = fmaxf(x, dpp_f32<0x141>(x));       // row_half_mirror
+  x = fmaxf(x, dpp_f32<0x140>(x));       // row_mirror: every lane holds the maximum of its row of 16
+  if constexpr (ONE_ROW) return lane_f32(x, 0);
+  return fmaxf(fmaxf(lane_f32(x, 0), lane_f32(x, 16)), fmaxf(lane_f32(x, 32), lane_f32(x, 48)));
+}
+
+// e of the positions t0 + s, s < kViterbiTile, that lie before ve -> buf[s][lane]; wave w (1..3) takes s = w - 1, w + 2, ...  All its
+// loads are issued before the first maximum, so that a tile costs two global round trips, not two per row.
+// The same for values that are all <= 0 (-inf and either zero included), as every u of the recurrence is: e <= 0 and max(v, -cost) <= 0.
+// Such floats are ordered against their bit patterns taken as unsigned integers, so their maximum is the unsigned minimum of the
+// patterns - one v_min_u32 with the DPP operand folded in where fmaxf costs a move and two v_max_f32 (hipcc canonicalises both
+// operands), and scalar minima for the four rows.  +0 and -0 both stand for zero; which of them comes back changes no sum and no
+// comparison below.
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_u32(unsigned x) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
+}
+
+__device__ __forceinline__ unsigned lane_u32(unsigned x, int l) { return (unsigned)__builtin_amdgcn_readlane((int)x, l); }
+
+__device__ __forceinline__ float max_nonpos(float a, float b) { return __uint_as_float(min(__float_as_uint(a), __float_as_uint(b))); }
+
+template <bool ONE_ROW>
+__device__ __forceinline__ float wave_max_nonpos(float v) {
+  unsigned x = __float_as_uint(v);
+  x = min(x, dpp_u32<0xB1>(x));
+  x = min(x, dpp_u32<0x4E>(x));
+  x = min(x, dpp_u32<0x141>(x));
+  x = min(x, dpp_u32<0x140>(x));
+  if constexpr (ONE_ROW) return __uint_as_float(lane_u32(x, 0));
+  return __uint_as_float(min(min(lane_u32(x, 0), lane_u32(x, 16)), min(lane_u32(x, 32), lane_u32(x, 48))));
+}
+
+template <bool ONE_ROW>
+__device__ __forceinline__ void viterbi_stage(float (*buf)[kEventMaxClasses], int t0, int ve, const float *__restrict__ logits, int N, int C,
+                                              const int32_t *__restrict__ rows, int wave, int lane) {
+  // no load sits under a branch: a position past the video reads the video's last one, a lane past C reads class C - 1
+  const int row = min(max(rows[min(t0 + lane, ve - 1)], 0), N - 1);          // lane l: the logit row of position t0 + l
+  const int s0 = __builtin_amdgcn_readfirstlane(wave) - 1, col = min(lane, C - 1);
+  float q[kViterbiRowsPerWave];
+#pragma unroll
+  for (int i = 0; i < kViterbiRowsPerWave; ++i) {
+    const int r = __builtin_amdgcn_readlane(row, min(s0 + i * kViterbiStageWaves, kViterbiTile - 1));
+    q[i] = logits[(size_t)r * C + col];
+  }
+#pragma unroll
+  for (int i = 0; i < kViterbiRowsPerWave; ++i) {
+    const int s = s0 + i * kViterbiStageWaves;
+    if (s < kViterbiTile && t0 + s < ve) {                                    // (wave-uniform)
+      const float x = lane < C ? q[i] : -INFINITY;
+      buf[s][lane] = x - wave_max<ONE_ROW>(x);
+    }
+  }
+}
+
+template <bool ONE_ROW>
+__global__ __launch_bounds__(kViterbiThreads) void viterbi_forward_kernel(const float *__restrict__ logits, int N, int C,
+                                                                          const int32_t *__restrict__ rows, int M,
+                                                                          const int32_t *__restrict__ vid_first,
+                                                                          const int32_t *__restrict__ vid_count, float neg_cost,
+                                                                          unsigned long long *__restrict__ stay, uint8_t *__restrict__ amax) {
+  __shared__ float se[2][kViterbiTile][kEventMaxClasses];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int V = *vid_count;
+  for (int vid = blockIdx.x; vid < V; vid += gridDim.x) {
+    const int vb = vid_first[vid], ve = vid + 1 < V ? vid_first[vid + 1] : M;
+    const int ntiles = (ve - vb + kViterbiTile - 1) / kViterbiTile;
+    if (wave > 0) viterbi_stage<ONE_ROW>(se[0], vb, ve, logits, N, C, rows, wave, lane);
+    __syncthreads();
+    float v = 0.f;                                 // in front of position 0 every class scores 0: u_0 = e_0, whose maximum is 0
+    for (int k = 0; k < ntiles; ++k) {
+      const int t0 = vb + k * kViterbiTile;
+      if (wave == 0) {
+        const int n = min(kViterbiTile, ve - t0);
+        const float(*buf)[kEventMaxClasses] = se[k & 1];
+        unsigned long long my_stay = 0;
+        int my_a = 0;
+        // kViterbiChunk rows of e are read ahead of the chunk that is walked, so that no LDS latency sits on the chain.  The last
+        // chunk of a video may run past position n - 1 on rows nobody staged: those steps reach no store and v is not used after them.
+        float e[kViterbiChunk], e_next[kViterbiChunk];
+#pragma unroll
+        for (int i = 0; i < kViterbiChunk; ++i) e[i] = buf[i][lane];
+        for (int j0 = 0; j0 < n; j0 += kViterbiChunk) {
+#pragma unroll
+          for (int i = 0; i < kViterbiChunk; ++i) e_next[i] = buf[min(j0 + kViterbiChunk + i, kViterbiTile - 1)][lane];
+#pragma unroll
+          for (int i = 0; i < kViterbiChunk; ++i) {
+            const unsigned long long st = __ballot(v >= neg_cost);
+            const float u = e[i] + max_nonpos(v, neg_cost);
+            const float mx = wave_max_nonpos<ONE_ROW>(u);
+            const unsigned long long hit = __ballot(u == mx);
+            v = u - mx;
+            const int a = hit ? min(__ffsll(hit) - 1, C - 1) : 0;             // (no hit: a NaN among the logits)
+            if (lane == j0 + i) {
+              my_stay = st;
+              my_a = a;
+            }
+          }
+#pragma unroll
+          for (int i = 0; i < kViterbiChunk; ++i) e[i] = e_next[i];
+        }
+        if (lane < n) {
+          stay[t0 + lane] = my_stay;
+          amax[t0 + lane] = (uint8_t)my_a;
+        }
+      } else if (k + 1 < ntiles) {
+        viterbi_stage<ONE_ROW>(se[(k + 1) & 1], t0 + kViterbiTile, ve, logits, N, C, rows, wave, lane);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// One wave per video.  Lane j of a tile stands for position t = its first position + j and holds nx = stay_{t+1} and at = a_t, so that
+// label[t] = nx[label[t+1]] ? label[t+1] : at.  nx is 0 at the video's last position (take a_t) and all ones past it (pass through).
+__global__ __launch_bounds__(64) void viterbi_backtrack_kernel(const unsigned long long *__restrict__ stay, const uint8_t *__restrict__ amax, int M,
+                                                               const int32_t *__restrict__ vid_first, const int32_t *__restrict__ vid_count,
+                                                               int32_t *__restrict__ label) {
+  const int lane = threadIdx.x;
+  const int V = *vid_count;
+  for (int vid = blockIdx.x; vid < V; vid += gridDim.x) {
+    const int vb = vid_first[vid], ve = vid + 1 < V ? vid_first[vid + 1] : M;
+    const int ntiles = (ve - vb + kViterbiTile - 1) / kViterbiTile;
+    auto load = [&](int k, unsigned long long &nx, int &at) {
+      const int t = vb + k * kViterbiTile + lane;
+      nx = ~0ull;
+      at = 0;
+      if (t < ve) {
+        nx = t + 1 < ve ? stay[t + 1] : 0ull;
+        at = amax[t];
+      }
+    };
+    unsigned long long nx;
+    int at, cur = 0;
+    load(ntiles - 1, nx, at);
+    for (int k = ntiles - 1; k >= 0; --k) {
+      unsigned long long nx_front = ~0ull;
+      int at_front = 0;
+      if (k > 0) load(k - 1, nx_front, at_front);                              // in flight while this tile is walked
+      const int nlo = (int)(unsigned)nx, nhi = (int)(unsigned)(nx >> 32);
+      int my_label = 0;
+#pragma unroll
+      for (int j = kViterbiTile - 1; j >= 0; --j) {
+        const unsigned long long mask = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(nhi, j) << 32) |
+                                        (unsigned)__builtin_amdgcn_readlane(nlo, j);
+        const int a = __builtin_amdgcn_readlane(at, j);
+        cur = ((mask >> cur) & 1ull) ? cur : a;
+        if (lane == j) my_label = cur;
+      }
+      const int t = vb + k * kViterbiTile + lane;
+      if (t < ve) label[t] = my_label;
+      nx = nx_front;
+      at = at_front;
+    }
+  }
+}
+
+// One thread per position, one workgroup per tile of kEventTile: flags and tile counts for the scan and scatter above.
+//   PATH = false  flags[m] = a video begins at m: scan and scatter then list the videos' first positions
+//   PATH = true   flags[m] = a run of `label` begins at m, and conf[m] = softmax(q)[label[m]] with event_score_kernel's operations
+template <bool PATH>
+__global__ __launch_bounds__(kEventTile) void event_flag_kernel(const float *__restrict__ logits, int N, int C, const int32_t *__restrict__ rows,
+                                                                const int32_t *__restrict__ start, int M, const int32_t *__restrict__ label,
+                                                                float *__restrict__ conf, uint8_t *__restrict__ flags,
+                                                                int32_t *__restrict__ counts) {
+  __shared__ int wcnt[kEventTile / 64];
+  const int tid = threadIdx.x, m = blockIdx.x * kEventTile + tid;
+  int f = 0;
+  if (m < M) {
+    f = (m == 0 || start[m] != 0) ? 1 : 0;
+    if constexpr (PATH) {
+      const int lab = label[m];
+      if (!f) f = label[m - 1] != lab ? 1 : 0;
+      const float *q = logits + (size_t)min(max(rows[m], 0), N - 1) * C;
+      float mx = q[0];
+      for (int c = 1; c < C; ++c) mx = fmaxf(mx, q[c]);
+      float sum = 0.f, el = 0.f;
+      for (int c = 0; c < C; ++c) {
+        const float e = expf(q[c] - mx);
+        sum += e;
+        if (c == lab) el = e;
+      }
+      conf[m] = el / sum;
+    }
+    flags[m] = (uint8_t)f;
+  }
+  const int nw = __popcll(__ballot(f));
+  if ((tid & 63) == 0) wcnt[tid >> 6] = nw;
+  __syncthreads();
+  if (tid == 0) {
+    int total = 0;
+    for (int k = 0; k < kEventTile / 64; ++k) total += wcnt[k];
+    counts[blockIdx.x] = total;
+  }
+}
+
 }  // namespace
 
 struct tn_event_decoder {
@@ -215,6 +457,13 @@ struct tn_event_decoder {
   float *conf;             //   [max_positions]   ... no conf_out
   int32_t *counts, *offsets;   // [max_tiles] each
   uint8_t *flags;          //   [max_positions]
+  size_t ws_bytes;
+  void *path_ws;           // the switch-cost path's, allocated by the first tn_event_decoder_run_switch:
+  unsigned long long *stay;    // [max_positions]   bit c: v_{t-1}[c] >= -cost
+  int32_t *vid_first;      //   [max_positions]   the first position of every video
+  uint8_t *amax;           //   [max_positions]   a_t
+  int32_t *vid_count;      //   [1]
+  size_t path_bytes;
 };
 
 extern "C" int tn_event_decoder_create(tn_ctx *ctx, int max_positions, int max_classes, tn_event_decoder **out) {
@@ -228,7 +477,8 @@ extern "C" int tn_event_decoder_create(tn_ctx *ctx, int max_positions, int max_c
   d->max_classes = max_classes;
   d->max_tiles = (max_positions + kEventTile - 1) / kEventTile;
   const size_t mp = ((size_t)max_positions + 3) & ~(size_t)3, mt = d->max_tiles;
-  if (hipMalloc(&d->ws, mp * 4 * 2 + mt * 4 * 2 + mp) != hipSuccess) {
+  d->ws_bytes = mp * 4 * 2 + mt * 4 * 2 + mp;
+  if (hipMalloc(&d->ws, d->ws_bytes) != hipSuccess) {
     delete d;
     tn_set_error("device allocation failed");
     return TN_ERR_NOMEM;
@@ -247,6 +497,7 @@ extern "C" int tn_event_decoder_destroy(tn_event_decoder *d) {
   TnDeviceGuard tn_dg_(d->ctx->device);
   (void)hipStreamSynchronize(d->ctx->stream);
   (void)hipFree(d->ws);
+  if (d->path_ws) (void)hipFree(d->path_ws);
   delete d;
   return TN_OK;
 }
@@ -295,5 +546,81 @@ extern "C" int tn_dbg_event_decoder_geometry(int *tile, int *scan_block) {
   TN_REQUIRE(tile && scan_block, "tn_dbg_event_decoder_geometry: null argument (tile, scan_block)");
   *tile = kEventTile;
   *scan_block = kEventScanBlock;
+  return TN_OK;
+}
+
+extern "C" int tn_event_decoder_run_switch(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows, const int32_t *start,
+                                           int M, float switch_cost, int32_t *label_out, float *conf_out, int32_t *ev_first, int32_t *ev_last,
+                                           int32_t *ev_cls, float *ev_score, float *ev_peak, int32_t *count, void *stream) {
+  TN_REQUIRE(d, "tn_event_decoder_run_switch: null handle");
+  TN_REQUIRE(logits, "tn_event_decoder_run_switch: logits is null");
+  TN_REQUIRE(rows, "tn_event_decoder_run_switch: rows is null");
+  TN_REQUIRE(start, "tn_event_decoder_run_switch: start is null");
+  TN_REQUIRE(ev_first, "tn_event_decoder_run_switch: ev_first is null");
+  TN_REQUIRE(ev_last, "tn_event_decoder_run_switch: ev_last is null");
+  TN_REQUIRE(ev_cls, "tn_event_decoder_run_switch: ev_cls is null");
+  TN_REQUIRE(ev_score, "tn_event_decoder_run_switch: ev_score is null");
+  TN_REQUIRE(ev_peak, "tn_event_decoder_run_switch: ev_peak is null");
+  TN_REQUIRE(count, "tn_event_decoder_run_switch: count is null");
+  TN_REQUIRE(N >= 1, "tn_event_decoder_run_switch: N must be >= 1");
+  TN_REQUIRE(C >= 1 && C <= kEventMaxClasses, "tn_event_decoder_run_switch: C must be in [1, 64]");
+  TN_REQUIRE(C <= d->max_classes, "tn_event_decoder_run_switch: C exceeds the handle's max_classes");
+  TN_REQUIRE(std::isfinite(switch_cost) && switch_cost >= 0.f, "tn_event_decoder_run_switch: switch_cost must be finite and >= 0");
+  TN_REQUIRE(M >= 1, "tn_event_decoder_run_switch: M must be >= 1");
+  TN_REQUIRE(M <= d->max_positions, "tn_event_decoder_run_switch: M exceeds the handle's max_positions");
+  TN_ON_DEVICE(d->ctx->device);
+  if (!d->path_ws) {
+    const size_t mp = ((size_t)d->max_positions + 3) & ~(size_t)3;
+    const size_t bytes = mp * (8 + 4 + 1) + 4;
+    void *ws = nullptr;
+    if (hipMalloc(&ws, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      tn_set_error("tn_event_decoder_run_switch: device allocation of the path workspace failed (" + std::to_string(bytes) + " bytes)");
+      return TN_ERR_NOMEM;
+    }
+    d->path_ws = ws;
+    d->path_bytes = bytes;
+    d->stay = (unsigned long long *)ws;
+    d->vid_first = (int32_t *)(d->stay + mp);
+    d->amax = (uint8_t *)(d->vid_first + mp);
+    d->vid_count = (int32_t *)(d->amax + mp);
+  }
+  hipStream_t s = stream ? (hipStream_t)stream : d->ctx->stream;
+  const int tiles = (M + kEventTile - 1) / kEventTile;
+  int32_t *label = label_out ? label_out : d->label;
+  float *conf = conf_out ? conf_out : d->conf;
+  // the videos' first positions: the set flags of start through the scan and scatter of the runs
+  hipLaunchKernelGGL(event_flag_kernel<false>, dim3(tiles), dim3(kEventTile), 0, s, logits, N, C, rows, start, M, (const int32_t *)nullptr,
+                     (float *)nullptr, d->flags, d->counts);
+  hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(kEventScanBlock), 0, s, d->counts, tiles, d->offsets, d->vid_count);
+  hipLaunchKernelGGL(event_scatter_kernel, dim3(tiles), dim3(kEventTile), 0, s, d->flags, M, d->offsets, d->vid_first);
+  const int chains = std::min(M, kViterbiMaxGrid);
+  const float neg_cost = -switch_cost;
+  if (C <= 16)
+    hipLaunchKernelGGL(viterbi_forward_kernel<true>, dim3(chains), dim3(kViterbiThreads), 0, s, logits, N, C, rows, M, d->vid_first,
+                       d->vid_count, neg_cost, d->stay, d->amax);
+  else
+    hipLaunchKernelGGL(viterbi_forward_kernel<false>, dim3(chains), dim3(kViterbiThreads), 0, s, logits, N, C, rows, M, d->vid_first,
+                       d->vid_count, neg_cost, d->stay, d->amax);
+  hipLaunchKernelGGL(viterbi_backtrack_kernel, dim3(chains), dim3(64), 0, s, d->stay, d->amax, M, d->vid_first, d->vid_count, label);
+  hipLaunchKernelGGL(event_flag_kernel<true>, dim3(tiles), dim3(kEventTile), 0, s, logits, N, C, rows, start, M, label, conf, d->flags,
+                     d->counts);
+  hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(kEventScanBlock), 0, s, d->counts, tiles, d->offsets, count);
+  hipLaunchKernelGGL(event_scatter_kernel, dim3(tiles), dim3(kEventTile), 0, s, d->flags, M, d->offsets, ev_first);
+  const int blocks = std::min((M + 3) / 4, 2048);
+  hipLaunchKernelGGL(event_reduce_kernel, dim3(blocks), dim3(256), 0, s, label, conf, M, count, ev_first, ev_last, ev_cls, ev_score, ev_peak);
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+
+extern "C" int tn_dbg_event_decoder_switch_geometry(int *tile) {
+  TN_REQUIRE(tile, "tn_dbg_event_decoder_switch_geometry: null argument (tile)");
+  *tile = kViterbiTile;
+  return TN_OK;
+}
+
+extern "C" int tn_dbg_event_decoder_workspace_bytes(const tn_event_decoder *d, size_t *bytes) {
+  TN_REQUIRE(d && bytes, "tn_dbg_event_decoder_workspace_bytes: null argument (handle, bytes)");
+  *bytes = d->ws_bytes + d->path_bytes;
   return TN_OK;
 }

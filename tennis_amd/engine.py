@@ -346,6 +346,13 @@ def event_decoder_geometry():
     return tile.value, scan.value
 
 
+def event_decoder_switch_geometry():
+    """``tn_dbg_event_decoder_switch_geometry``: positions of a video the switch-cost path kernels take per step; touches no device."""
+    tile = C.c_int()
+    check(_lib.load().tn_dbg_event_decoder_switch_geometry(C.byref(tile)), "tn_dbg_event_decoder_switch_geometry")
+    return tile.value
+
+
 class EventDecoder(_Handle):
     """Per-frame logits -> events on the device (``tn_event_decoder_*``, docs/kernels.md "Event decoding"): workspace for up to
     ``max_positions`` positions of up to ``classes`` classes; ``decode`` allocates its outputs only."""
@@ -359,12 +366,28 @@ class EventDecoder(_Handle):
         check(self.lib.tn_event_decoder_create(self.ctx.handle, self.max_positions, self.classes, C.byref(h)), "tn_event_decoder_create")
         self.handle = h
 
-    def decode(self, logits: torch.Tensor, rows, start, smooth: int = 1, return_frames: bool = False):
+    def workspace_bytes(self) -> int:
+        """``tn_dbg_event_decoder_workspace_bytes``: device bytes the handle holds (the path workspace of ``switch_cost`` is allocated
+        by the first call that gives one)."""
+        n = C.c_size_t()
+        check(self.lib.tn_dbg_event_decoder_workspace_bytes(self.handle, C.byref(n)), "tn_dbg_event_decoder_workspace_bytes")
+        return n.value
+
+    def decode(self, logits: torch.Tensor, rows, start, smooth: int = 1, return_frames: bool = False, switch_cost: float | None = None):
         """``logits`` (N, C) fp32 on the GPU; ``rows`` (M,) the logit row of every position of the time-ordered list (clamped into
         ``[0, N)``), ``start`` (M,) non-zero where a video begins, ``smooth`` the odd window width in [1, 63].  Returns a dict of
         tensors on the GPU, one entry per event in order of ``first``: ``first``, ``last`` (positions, inclusive), ``cls`` (int32),
         ``score`` the mean and ``peak`` the maximum of the smoothed score of ``cls`` over the event (float32); with
-        ``return_frames`` also ``label`` (M,) int32 and ``conf`` (M,) float32 of every position.  Synchronises once, for the count."""
+        ``return_frames`` also ``label`` (M,) int32 and ``conf`` (M,) float32 of every position.  Synchronises once, for the count.
+        ``switch_cost`` (finite, >= 0, in logit units; not together with ``smooth`` > 1): the labels are the path that maximises the
+        summed scores minus ``switch_cost`` per change of label inside a video (``tn_event_decoder_run_switch``), ``conf`` the
+        unsmoothed probability of the label; None: the call is what it was."""
+        if switch_cost is not None:                                             # refused before anything is launched
+            if int(smooth) != 1:
+                raise ValueError(f"EventDecoder.decode: switch_cost decodes the unsmoothed scores, not together with smooth={smooth}")
+            switch_cost = float(switch_cost)
+            if not (np.isfinite(switch_cost) and switch_cost >= 0):
+                raise ValueError(f"EventDecoder.decode: switch_cost must be finite and >= 0, got {switch_cost}")
         _on_ctx_device(self.ctx, logits, "EventDecoder.decode")
         if logits.dim() != 2 or logits.dtype != torch.float32:
             raise ValueError(f"EventDecoder.decode: logits must be (N, C) float32, got {tuple(logits.shape)} {logits.dtype}")
@@ -376,9 +399,14 @@ class EventDecoder(_Handle):
         count = torch.zeros(1, dtype=torch.int32, device=dev)
         label = torch.empty(m, dtype=torch.int32, device=dev) if return_frames else None
         conf = torch.empty(m, dtype=torch.float32, device=dev) if return_frames else None
-        check(self.lib.tn_event_decoder_run(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start), m, int(smooth),
-                                            ptr(label), ptr(conf), ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(flts[0]), ptr(flts[1]),
-                                            ptr(count), None), "tn_event_decoder_run")        # (stream NULL: the context's)
+        if switch_cost is None:
+            check(self.lib.tn_event_decoder_run(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start), m, int(smooth),
+                                                ptr(label), ptr(conf), ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(flts[0]), ptr(flts[1]),
+                                                ptr(count), None), "tn_event_decoder_run")    # (stream NULL: the context's)
+        else:
+            check(self.lib.tn_event_decoder_run_switch(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start), m,
+                                                       switch_cost, ptr(label), ptr(conf), ptr(ints[0]), ptr(ints[1]), ptr(ints[2]),
+                                                       ptr(flts[0]), ptr(flts[1]), ptr(count), None), "tn_event_decoder_run_switch")
         k = int(count.item())
         out = dict(first=ints[0, :k], last=ints[1, :k], cls=ints[2, :k], score=flts[0, :k], peak=flts[1, :k])
         if return_frames:

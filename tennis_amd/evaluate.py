@@ -717,6 +717,12 @@ def build_parser():
     p.add_argument("--event_smooth", type=int, default=None,
                    help="with --save_events: odd width in [1, 63] of the window the class probabilities are averaged over before the "
                         "arg-max (cut at video boundaries; default 1, no smoothing).  Moves event boundaries by up to (width - 1) / 2 frames")
+    p.add_argument("--event_switch_cost", type=float, default=None,
+                   help="with --save_events, instead of smoothing: decode every video as one label path that maximises the summed "
+                        "per-frame scores (logit minus the frame's largest logit) minus this penalty for every change of label "
+                        "(Viterbi on the GPU; finite, >= 0, in logit units; 0 is the per-frame arg-max).  A one-frame glitch that leads "
+                        "by less than twice the penalty is absorbed, boundaries stay where the scores put them.  For a stay "
+                        "probability s over C classes: ln(s (C - 1) / (1 - s)).  Not together with --event_smooth above 1")
     return p
 
 
@@ -884,7 +890,10 @@ def _main_rank(flags, rank, world, dev):
         save_tams(tams_file, **cols[0])
         print("Saved %d temporal activation maps of %d steps: %s" % (len(cols[0]["tam"]), cols[0]["tam"].shape[1], tams_file))
     if kept is not None:                                                     # the logits never left the device: decode them there
-        ev_cols, ev_metric = decode_split(test_set, torch.cat(kept["logits"]), kept["order"], smooth=getattr(flags, "event_smooth", None) or 1)
+        cost = getattr(flags, "event_switch_cost", None)
+        path = {} if cost is None else {"switch_cost": cost}                 # (without the flag the call is the call it was)
+        ev_cols, ev_metric = decode_split(test_set, torch.cat(kept["logits"]), kept["order"], smooth=getattr(flags, "event_smooth", None) or 1,
+                                          **path)
         events_file = os.path.join(flags.exp_root, flags.model_id, flags.split + "_events.npz")
         save_events(events_file, **ev_cols)
         print(event_table(ev_cols, test_set.classes))

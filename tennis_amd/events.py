@@ -20,10 +20,19 @@ def check_save_events(flags, world=1):
     """``--save_events`` is for a test run that yields per-sample logits, on one rank: exits with the reason otherwise.  Touches no
     device."""
     smooth = getattr(flags, "event_smooth", None)
+    cost = getattr(flags, "event_switch_cost", None)
     if not getattr(flags, "save_events", False):
         if smooth is not None:
             raise SystemExit("--event_smooth %s sets the smoothing window of --save_events: give --save_events too" % smooth)
+        if cost is not None:
+            raise SystemExit("--event_switch_cost %s sets the label-switch penalty of --save_events: give --save_events too" % cost)
         return
+    if cost is not None:
+        if not (np.isfinite(cost) and cost >= 0):
+            raise SystemExit("--event_switch_cost %s: the penalty for every change of label is subtracted from a path's summed scores, "
+                             "so it must be finite and >= 0" % cost)
+        if smooth is not None and smooth > 1:
+            raise SystemExit("--event_switch_cost decodes the unsmoothed scores as one path: not together with --event_smooth %d" % smooth)
     if smooth is not None and (smooth < 1 or smooth > MAX_SMOOTH or smooth % 2 == 0):
         raise SystemExit("--event_smooth %d: the smoothing window is centred on a frame, so it must be odd, and it is summed directly, "
                          "so it must lie in [1, %d]" % (smooth, MAX_SMOOTH))
@@ -70,14 +79,63 @@ def label_runs(labels, start):
     return first, last, labels[first]
 
 
+def viterbi_labels(logits, rows, start, switch_cost, dtype=np.float64):
+    """The label path of ``EventDecoder.decode(..., switch_cost=...)`` on the host, in ``dtype`` arithmetic (docs/kernels.md "Event
+    decoding with a switch cost"): per video the path that maximises the sum of ``e[m, label[m]]`` minus ``switch_cost`` for every
+    change of label, ``e[m] = q - max(q)``, ``q = logits[clip(rows[m], 0, N - 1)]``.  Forward ``v_0 = e_0``, ``stay_t = v_{t-1} >=
+    -switch_cost``, ``u_t = e_t + max(v_{t-1}, -switch_cost)``, ``v_t = u_t - max(u_t)``, ``a_t`` the first arg-max of ``v_t``; back
+    ``label[T-1] = a_{T-1}``, ``label[t-1] = label[t] if stay_t[label[t]] else a_{t-1}``.  A Python loop over the positions.
+    -> ``label (M,)`` int64."""
+    dtype = np.dtype(dtype).type
+    cost = float(switch_cost)
+    if not (np.isfinite(cost) and cost >= 0):
+        raise ValueError(f"viterbi_labels: switch_cost must be finite and >= 0, got {switch_cost}")
+    logits = np.asarray(logits)
+    if logits.ndim != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"viterbi_labels: logits must be (N, C), got {logits.shape}")
+    rows = np.clip(np.asarray(rows, np.int64).reshape(-1), 0, logits.shape[0] - 1)
+    begins = np.asarray(start).reshape(-1) != 0
+    if len(rows) != len(begins):
+        raise ValueError(f"viterbi_labels: {len(rows)} rows for {len(begins)} start flags")
+    m = len(rows)
+    label = np.zeros(m, np.int64)
+    if not m:
+        return label
+    q = logits[rows].astype(dtype)
+    e = q - q.max(1, keepdims=True)
+    neg = dtype(-cost)
+    bounds = np.flatnonzero(begins).tolist()
+    if not bounds or bounds[0] != 0:
+        bounds = [0] + bounds
+    bounds.append(m)
+    stay = np.zeros(e.shape, bool)
+    amax = np.zeros(m, np.int64)
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        v = e[a]
+        amax[a] = int(np.argmax(v))                                              # (numpy's argmax is the first maximum)
+        for t in range(a + 1, b):
+            stay[t] = v >= neg
+            u = e[t] + np.maximum(v, neg)
+            v = u - u.max()
+            amax[t] = int(np.argmax(v))
+        lab = amax[b - 1]
+        label[b - 1] = lab
+        for t in range(b - 1, a, -1):
+            if not stay[t, lab]:
+                lab = amax[t - 1]
+            label[t - 1] = lab
+    return label
+
+
 def save_events(file_path, video, first_frame, last_frame, cls, score, peak, first_sample, last_sample, gt_video, gt_first_frame,
-                gt_last_frame, gt_cls, smooth, tiou, precision, recall, f1):
+                gt_last_frame, gt_cls, smooth, tiou, precision, recall, f1, switch_cost=None):
     """One ``.npz`` of flat arrays (``np.load(..., allow_pickle=False)`` reads it).  Per predicted event ``video`` (unicode),
     ``first_frame`` / ``last_frame`` (frame numbers, inclusive), ``cls``, ``score`` the mean and ``peak`` the maximum of the smoothed
     score of ``cls``, ``first_sample`` / ``last_sample`` (dataset indices of the two end frames); per ground-truth event ``gt_video``,
     ``gt_first_frame``, ``gt_last_frame``, ``gt_cls``; ``smooth`` the window width, ``tiou (T,)`` the thresholds and ``precision``,
     ``recall``, ``f1`` (T, classes) of ``metrics.events.EventPRF1``.  A run of the background class is an event too, and smoothing
-    moves boundaries by up to (smooth - 1) / 2 frames."""
+    moves boundaries by up to (smooth - 1) / 2 frames.  ``switch_cost`` (None: the file has no such column): the label-switch penalty the
+    events were decoded with, a float64 scalar; ``score`` and ``peak`` are then of the unsmoothed probability."""
     i64 = lambda a: np.asarray(a, np.int64).reshape(-1)
     f32 = lambda a: np.asarray(a, np.float32).reshape(-1)
     txt = lambda a: np.asarray(list(a), dtype=np.str_).reshape(-1)
@@ -96,6 +154,8 @@ def save_events(file_path, video, first_frame, last_frame, cls, score, peak, fir
     for k in ("precision", "recall", "f1"):
         if cols[k].ndim != 2 or cols[k].shape[0] != t:
             raise ValueError(f"save_events: {k} must be ({t}, classes), got {cols[k].shape}")
+    if switch_cost is not None:
+        cols["switch_cost"] = np.asarray(float(switch_cost), np.float64)
     os.makedirs(os.path.dirname(os.path.abspath(file_path)), exist_ok=True)
     np.savez(file_path, **cols)
 
@@ -110,17 +170,19 @@ def load_events(file_path):
     return d
 
 
-def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), decoder=None):
+def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), decoder=None, switch_cost=None):
     """The events of one evaluated split: ``logits`` (N, classes) fp32 ON THE GPU, row r the logits of sample ``order[r]`` (None:
     of sample r).  The positions are time-ordered on the host (``time_order``), decoded on the device (``engine.EventDecoder``; only
     the events come back), the ground truth is ``label_runs`` of the samples' labels, both are scored with ``EventPRF1``.
+    ``switch_cost`` (None: per-frame arg-max of the smoothed scores) goes to the decoder and into the columns.
     -> ``(columns of save_events, EventPRF1)``."""
     from .engine import EventDecoder
     from .metrics.events import EventPRF1
     rows, start, video, frame = time_order(dataset, order)
     order = np.arange(len(dataset._samples)) if order is None else np.asarray(order, np.int64).reshape(-1)
     decoder = decoder or EventDecoder(len(rows), logits.shape[1])
-    ev = {k: v.cpu().numpy() for k, v in decoder.decode(logits, rows, start, smooth=smooth).items()}
+    path = {} if switch_cost is None else {"switch_cost": float(switch_cost)}    # (without it the call is the call it was)
+    ev = {k: v.cpu().numpy() for k, v in decoder.decode(logits, rows, start, smooth=smooth, **path).items()}
     first, last = ev["first"].astype(np.int64), ev["last"].astype(np.int64)
     labels = np.asarray([dataset.classes.index(dataset._samples[int(i)][2]) for i in order[rows]], np.int64)
     gfirst, glast, gcls = label_runs(labels, start)
@@ -131,14 +193,15 @@ def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), d
     prec, rec, f1 = metric.arrays()
     cols = dict(pred, peak=ev["peak"], first_sample=order[rows[first]], last_sample=order[rows[last]], gt_video=gt["video"],
                 gt_first_frame=gt["first_frame"], gt_last_frame=gt["last_frame"], gt_cls=gt["cls"], smooth=int(smooth),
-                tiou=np.asarray(metric.tious), precision=prec, recall=rec, f1=f1)
+                tiou=np.asarray(metric.tious), precision=prec, recall=rec, f1=f1, **path)
     return cols, metric
 
 
 def event_table(cols, classes, limit=40):
     """The printed form of ``decode_split``'s columns: one line per predicted event (the first ``limit``), then the scores."""
     n = len(cols["video"])
-    lines = ["Events: %d predicted, %d ground truth (smooth %d)" % (n, len(cols["gt_video"]), int(cols["smooth"]))]
+    how = "smooth %d" % int(cols["smooth"]) if cols.get("switch_cost") is None else "switch cost %g" % float(cols["switch_cost"])
+    lines = ["Events: %d predicted, %d ground truth (%s)" % (n, len(cols["gt_video"]), how)]
     for i in range(min(n, limit)):
         lines.append("  %s\t%s\tframes %d-%d\tscore %.3f\tpeak %.3f" % (cols["video"][i], classes[int(cols["cls"][i])],
                                                                       cols["first_frame"][i], cols["last_frame"][i],
