@@ -608,6 +608,32 @@ int tn_event_decoder_run_switch(tn_event_decoder *d, const float *logits, int N,
                                 int M, float switch_cost, int32_t *label_out, float *conf_out, int32_t *ev_first, int32_t *ev_last,
                                 int32_t *ev_cls, float *ev_score, float *ev_peak, int32_t *count, void *stream);
 
+/* The same events from the label path under a class-transition matrix (an HMM on top of the frame classifier, decoded with Viterbi;
+ * docs/kernels.md "Event decoding with a transition matrix").  Arguments as tn_event_decoder_run_switch, with the matrix in place of
+ * the cost: transitions is a HOST pointer to (C, C) floats, row-major, transitions[from * C + to] = T[from][to] the score added when a
+ * position labelled `from` is followed inside the same video by one labelled `to`.  Every entry is finite and <= 0, or -inf (the
+ * transition is forbidden); the diagonal is finite, so staying is always possible and every value below stays finite.  The matrix
+ * is checked on the host, then copied into the handle with hipMemcpyAsync on the call's stream (keep pinned memory unchanged until
+ * the stream has passed the copy).
+ *   e        as above.  The path maximises  sum_m e[m, label[m]] + sum_{m not its video's first} T[label[m-1]][label[m]].
+ *   forward  per video, positions in order, fp32, every sum rounded:  v_0 = e_0;  w_t[c] = max_p (v_{t-1}[p] + T[p][c]);
+ *            b_t[c] = c if v_{t-1}[c] + T[c][c] attains w_t[c] (staying wins a tie), else the smallest p that attains it;
+ *            u_t[c] = e_t[c] + w_t[c];  v_t[c] = u_t[c] - max_c u_t[c];  a_t = the first arg-max of v_t.
+ *   back     label[T-1] = a_{T-1};  label[t-1] = b_t[label[t]].
+ *   conf, events   exactly as tn_event_decoder_run_switch's.
+ * With T = -cost (1 - I) every u and v is the switch-cost recurrence's bit for bit (the best predecessor has v = 0 and the rounded
+ * sums v[p] - cost are monotone in v[p]).  Sequential by definition, one workgroup per video, no workgroup waits on another, no
+ * atomics on floats, nothing depends on grid or tile: a video decoded alone gives the bits of the whole-corpus call.  Every stored
+ * index lies in [0, C) whatever the floats are; with a NaN among the logits the labels are unspecified but in range.
+ * The first call allocates the back-pointer workspace inside the handle: (pitch + 5) bytes per position of max_positions (rounded up
+ * to a multiple of 4), pitch = 16 for max_classes <= 16 and 64 above, plus 4 max_classes^2 + 4 bytes; TN_ERR_NOMEM with the size in
+ * tn_last_error if that fails.  Later calls allocate nothing, and the other two run entries never touch it.  TN_ERR_INVALID as
+ * tn_event_decoder_run_switch, for a null transitions, and - naming the first offending [from][to] - for an entry that is NaN, an
+ * entry that is positive (+inf included), and a diagonal entry that is not finite. */
+int tn_event_decoder_run_transitions(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows, const int32_t *start,
+                                     int M, const float *transitions, int32_t *label_out, float *conf_out, int32_t *ev_first,
+                                     int32_t *ev_last, int32_t *ev_cls, float *ev_score, float *ev_peak, int32_t *count, void *stream);
+
 /* ---- multi-GPU exchange: RCCL over xGMI, one process per GPU (csrc/comm.hip) ------------
  * The path's one exchange step (BASELINE config C4).  The reference splits every DataLoader batch over its ctx list and
  * exchanges the per-frame feature rows through the file system: evaluate.py:278-281,308-321 writes

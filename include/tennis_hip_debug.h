@@ -156,8 +156,13 @@ int tn_dbg_event_decoder_geometry(int *tile, int *scan_block);
  * staged into LDS while the walking wave consumes the tile before).  Touches no device. */
 int tn_dbg_event_decoder_switch_geometry(int *tile);
 
+/* The transition-matrix path decoder's geometry: *tile = positions of a video its forward and backtrack kernels take per step,
+ * *pitch16 / *pitch64 = bytes of a position's row of back-pointers in a handle of max_classes <= 16 / above.  Touches no device. */
+int tn_dbg_event_decoder_transition_geometry(int *tile, int *pitch16, int *pitch64);
+
 /* Device bytes the handle holds: what tn_event_decoder_create allocated, plus the path workspace once the first
- * tn_event_decoder_run_switch has allocated it.  Touches no device. */
+ * tn_event_decoder_run_switch has allocated it, plus the back-pointer workspace once the first tn_event_decoder_run_transitions has.
+ * Touches no device. */
 int tn_dbg_event_decoder_workspace_bytes(const tn_event_decoder *d, size_t *bytes);
 
 /* The LDS-resident 7x7 dense block (csrc/dense_block7.hip): nl layers from K0 input channels in ONE launch on a device

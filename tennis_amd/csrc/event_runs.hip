@@ -29,6 +29,19 @@
 //                             front is in flight while the wave walks this one with scalar selects
 //   event_flag_kernel<true>   one thread per position: conf, the run-start flags and the tile counts - what event_score_kernel
 //                             leaves behind, so that scan, scatter and reduce run unchanged
+//
+// With a transition matrix (tn_event_decoder_run_transitions; docs/kernels.md "Event decoding with a transition matrix") the path
+// maximises sum_m e[m, label[m]] + sum_{m not a video's first} T[label[m-1], label[m]], T (C, C) with entries <= 0 or -inf and a
+// finite diagonal:
+//   forward   v_0 = e_0;  w_t[c] = max_p (v_{t-1}[p] + T[p, c]);  b_t[c] = c if v_{t-1}[c] + T[c, c] attains w_t[c], else the smallest
+//             p that does;  u_t[c] = e_t[c] + w_t[c];  v_t = u_t - max_c u_t;  a_t = first arg-max of v_t
+//   back      label[T-1] = a_{T-1};  label[t-1] = b_t[label[t]]
+// The same nine launches with two other chain kernels:
+//   viterbi_trans_forward_kernel    the staging of viterbi_forward_kernel; on the chain lane c holds v[c] and the column T[:, c] in
+//                                   registers, v[p] comes as a scalar from readlane, the C candidates of a step are independent.
+//                                   The back-pointers of a tile go through LDS and leave as whole rows of a fixed pitch.
+//   viterbi_trans_backtrack_kernel  one wave per video, tiles back to front: the rows of the tile in front are in flight while the
+//                                   wave walks this one, one dependent LDS byte read per position
 #include "common.h"
 
 #include <cmath>
@@ -408,6 +421,150 @@ __global__ __launch_bounds__(64) void viterbi_backtrack_kernel(const unsigned lo
   }
 }
 
+// ---- the transition-matrix path ----
+
+// bytes of a position's row of back-pointers: one row of lanes up to 16 classes, one lane per class above
+template <bool ONE_ROW>
+__host__ __device__ constexpr int trans_pitch() { return ONE_ROW ? 16 : kEventMaxClasses; }
+
+// The staging and the read-ahead are viterbi_forward_kernel's.  On the chain lane c holds v[c], the column T[:, c] (tc, -inf past C:
+// such a predecessor is never chosen) and T[c, c].  A step forms the candidates v[p] + T[p, c] in ascending p from v[p] as a scalar
+// and keeps the first maximum (strict comparison), then lets staying win a tie; every sum is <= 0 or -inf, so the wave maximum is
+// wave_max_nonpos's.  A NaN compares false everywhere, so every stored index is in [0, C) whatever the floats are.
+template <bool ONE_ROW>
+__global__ __launch_bounds__(kViterbiThreads) void viterbi_trans_forward_kernel(const float *__restrict__ logits, int N, int C,
+                                                                                const int32_t *__restrict__ rows, int M,
+                                                                                const int32_t *__restrict__ vid_first,
+                                                                                const int32_t *__restrict__ vid_count,
+                                                                                const float *__restrict__ trans, uint8_t *__restrict__ back,
+                                                                                uint8_t *__restrict__ amax) {
+  constexpr int P = trans_pitch<ONE_ROW>();
+  __shared__ float se[2][kViterbiTile][kEventMaxClasses];
+  __shared__ __attribute__((aligned(16))) uint8_t sb[kViterbiTile][kEventMaxClasses];      // b_t of the tile that is walked
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int V = *vid_count;
+  float tc[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) tc[p] = (wave == 0 && p < C && lane < C) ? trans[p * C + lane] : -INFINITY;
+  const float t_stay = (wave == 0 && lane < C) ? trans[lane * C + lane] : -INFINITY;
+  for (int vid = blockIdx.x; vid < V; vid += gridDim.x) {
+    const int vb = vid_first[vid], ve = vid + 1 < V ? vid_first[vid + 1] : M;
+    const int ntiles = (ve - vb + kViterbiTile - 1) / kViterbiTile;
+    if (wave > 0) viterbi_stage<ONE_ROW>(se[0], vb, ve, logits, N, C, rows, wave, lane);
+    __syncthreads();
+    float v = 0.f;
+    for (int k = 0; k < ntiles; ++k) {
+      const int t0 = vb + k * kViterbiTile;
+      if (wave == 0) {
+        const int n = min(kViterbiTile, ve - t0);
+        const float(*buf)[kEventMaxClasses] = se[k & 1];
+        int my_a = 0;
+        // (the last chunk of a video may run past position n - 1 on rows nobody staged: those steps reach no global store)
+        float e[kViterbiChunk], e_next[kViterbiChunk];
+#pragma unroll
+        for (int i = 0; i < kViterbiChunk; ++i) e[i] = buf[i][lane];
+        for (int j0 = 0; j0 < n; j0 += kViterbiChunk) {
+#pragma unroll
+          for (int i = 0; i < kViterbiChunk; ++i) e_next[i] = buf[min(j0 + kViterbiChunk + i, kViterbiTile - 1)][lane];
+#pragma unroll
+          for (int i = 0; i < kViterbiChunk; ++i) {
+            float best = lane_f32(v, 0) + tc[0];
+            int from = 0;
+#pragma unroll
+            for (int p = 1; p < P; ++p) {
+              const float cand = lane_f32(v, p) + tc[p];
+              if (cand > best) {
+                best = cand;
+                from = p;
+              }
+            }
+            if (v + t_stay >= best) from = lane;                              // (the maximum holds this sum: >= is ==)
+            const float w = (i == 0 && j0 == 0 && k == 0) ? 0.f : best;       // a video's first position has no predecessor: u_0 = e_0
+            const float u = e[i] + w;
+            const float mx = wave_max_nonpos<ONE_ROW>(u);
+            const unsigned long long hit = __ballot(u == mx);
+            v = u - mx;
+            const int a = hit ? min(__ffsll(hit) - 1, C - 1) : 0;             // (no hit: a NaN among the inputs)
+            sb[j0 + i][lane] = (uint8_t)from;
+            if (lane == j0 + i) my_a = a;
+          }
+#pragma unroll
+          for (int i = 0; i < kViterbiChunk; ++i) e[i] = e_next[i];
+        }
+        __builtin_amdgcn_wave_barrier();                                      // the rows above are read below by other lanes of this wave
+        if constexpr (ONE_ROW) {
+          if (lane < n) *(uint4 *)(back + (size_t)(t0 + lane) * P) = *(const uint4 *)&sb[lane][0];
+        } else {
+#pragma unroll
+          for (int i = 0; i < P / 16; ++i) {
+            const int f = i * 64 + lane, row = f / (P / 16), part = f % (P / 16);
+            if (row < n) *(uint4 *)(back + (size_t)(t0 + row) * P + part * 16) = *(const uint4 *)&sb[row][part * 16];
+          }
+        }
+        if (lane < n) amax[t0 + lane] = (uint8_t)my_a;
+      } else if (k + 1 < ntiles) {
+        viterbi_stage<ONE_ROW>(se[(k + 1) & 1], t0 + kViterbiTile, ve, logits, N, C, rows, wave, lane);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// One wave per video, tiles back to front.  Slot j of the LDS holds b_{t+1}, t = the tile's first position + j, so that
+// label[t] = slot j [label[t+1]]: one dependent byte read per position.  The rows of the tile in front are loaded before the walk and
+// stored into the LDS after it.  A byte is masked into the row, so that no read leaves the LDS whatever the workspace holds.
+template <bool ONE_ROW>
+__global__ __launch_bounds__(64) void viterbi_trans_backtrack_kernel(const uint8_t *__restrict__ back, const uint8_t *__restrict__ amax, int M,
+                                                                     const int32_t *__restrict__ vid_first,
+                                                                     const int32_t *__restrict__ vid_count, int32_t *__restrict__ label) {
+  constexpr int P = trans_pitch<ONE_ROW>(), Q = P / 16;                       // Q: 16-byte parts of a row
+  __shared__ __attribute__((aligned(16))) uint8_t sb[kViterbiTile * P];
+  const int lane = threadIdx.x;
+  const int V = *vid_count;
+  for (int vid = blockIdx.x; vid < V; vid += gridDim.x) {
+    const int vb = vid_first[vid], ve = vid + 1 < V ? vid_first[vid + 1] : M;
+    const int ntiles = (ve - vb + kViterbiTile - 1) / kViterbiTile;
+    uint4 part[Q];
+    auto load = [&](int k) {                                                  // the rows of positions first + 1 .. first + kViterbiTile
+      const int t1 = vb + k * kViterbiTile + 1;
+#pragma unroll
+      for (int i = 0; i < Q; ++i) {
+        const int f = i * 64 + lane, t = t1 + f / Q;
+        part[i] = make_uint4(0, 0, 0, 0);
+        if (t < ve) part[i] = ((const uint4 *)(back + (size_t)t * P))[f % Q];
+      }
+    };
+    auto put = [&]() {
+#pragma unroll
+      for (int i = 0; i < Q; ++i) ((uint4 *)sb)[i * 64 + lane] = part[i];
+    };
+    load(ntiles - 1);
+    put();
+    __syncthreads();
+    int cur = amax[ve - 1] & (P - 1);
+    for (int k = ntiles - 1; k >= 0; --k) {
+      if (k > 0) load(k - 1);                                                  // in flight while this tile is walked
+      const int t0 = vb + k * kViterbiTile, n = min(kViterbiTile, ve - t0);
+      int my_label = 0, j = n - 1;
+      if (k == ntiles - 1) {                                                   // the video's last position takes a_t
+        if (lane == j) my_label = cur;
+        --j;
+      }
+#pragma unroll 4
+      for (; j >= 0; --j) {
+        cur = sb[j * P + cur] & (P - 1);
+        if (lane == j) my_label = cur;
+      }
+      if (lane < n) label[t0 + lane] = my_label;
+      __syncthreads();
+      if (k > 0) {
+        put();
+        __syncthreads();
+      }
+    }
+  }
+}
+
 // One thread per position, one workgroup per tile of kEventTile: flags and tile counts for the scan and scatter above.
 //   PATH = false  flags[m] = a video begins at m: scan and scatter then list the videos' first positions
 //   PATH = true   flags[m] = a run of `label` begins at m, and conf[m] = softmax(q)[label[m]] with event_score_kernel's operations
@@ -464,6 +621,13 @@ struct tn_event_decoder {
   uint8_t *amax;           //   [max_positions]   a_t
   int32_t *vid_count;      //   [1]
   size_t path_bytes;
+  void *trans_ws;          // the transition-matrix path's, allocated by the first tn_event_decoder_run_transitions:
+  uint8_t *back;           //   [max_positions][pitch]   b_t, pitch = 16 bytes for max_classes <= 16, else 64
+  float *trans;            //   [max_classes^2]   the call's matrix, (C, C) row-major
+  int32_t *tvid_first;     //   [max_positions]
+  int32_t *tvid_count;     //   [1]
+  uint8_t *tamax;          //   [max_positions]   a_t
+  size_t trans_bytes;
 };
 
 extern "C" int tn_event_decoder_create(tn_ctx *ctx, int max_positions, int max_classes, tn_event_decoder **out) {
@@ -498,6 +662,7 @@ extern "C" int tn_event_decoder_destroy(tn_event_decoder *d) {
   (void)hipStreamSynchronize(d->ctx->stream);
   (void)hipFree(d->ws);
   if (d->path_ws) (void)hipFree(d->path_ws);
+  if (d->trans_ws) (void)hipFree(d->trans_ws);
   delete d;
   return TN_OK;
 }
@@ -619,8 +784,98 @@ extern "C" int tn_dbg_event_decoder_switch_geometry(int *tile) {
   return TN_OK;
 }
 
+extern "C" int tn_event_decoder_run_transitions(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows,
+                                                const int32_t *start, int M, const float *transitions, int32_t *label_out,
+                                                float *conf_out, int32_t *ev_first, int32_t *ev_last, int32_t *ev_cls, float *ev_score,
+                                                float *ev_peak, int32_t *count, void *stream) {
+  TN_REQUIRE(d, "tn_event_decoder_run_transitions: null handle");
+  TN_REQUIRE(logits, "tn_event_decoder_run_transitions: logits is null");
+  TN_REQUIRE(rows, "tn_event_decoder_run_transitions: rows is null");
+  TN_REQUIRE(start, "tn_event_decoder_run_transitions: start is null");
+  TN_REQUIRE(transitions, "tn_event_decoder_run_transitions: transitions is null");
+  TN_REQUIRE(ev_first, "tn_event_decoder_run_transitions: ev_first is null");
+  TN_REQUIRE(ev_last, "tn_event_decoder_run_transitions: ev_last is null");
+  TN_REQUIRE(ev_cls, "tn_event_decoder_run_transitions: ev_cls is null");
+  TN_REQUIRE(ev_score, "tn_event_decoder_run_transitions: ev_score is null");
+  TN_REQUIRE(ev_peak, "tn_event_decoder_run_transitions: ev_peak is null");
+  TN_REQUIRE(count, "tn_event_decoder_run_transitions: count is null");
+  TN_REQUIRE(N >= 1, "tn_event_decoder_run_transitions: N must be >= 1");
+  TN_REQUIRE(C >= 1 && C <= kEventMaxClasses, "tn_event_decoder_run_transitions: C must be in [1, 64]");
+  TN_REQUIRE(C <= d->max_classes, "tn_event_decoder_run_transitions: C exceeds the handle's max_classes");
+  TN_REQUIRE(M >= 1, "tn_event_decoder_run_transitions: M must be >= 1");
+  TN_REQUIRE(M <= d->max_positions, "tn_event_decoder_run_transitions: M exceeds the handle's max_positions");
+  for (int p = 0; p < C; ++p)
+    for (int c = 0; c < C; ++c) {
+      const float x = transitions[p * C + c];
+      const char *why = std::isnan(x) ? "is NaN" : x > 0.f ? "is positive: a transition score must be <= 0 or -inf"
+                        : (p == c && std::isinf(x)) ? "is not finite: staying must always be possible" : nullptr;
+      if (why) {
+        tn_set_error("tn_event_decoder_run_transitions: transitions[" + std::to_string(p) + "][" + std::to_string(c) + "] " + why);
+        return TN_ERR_INVALID;
+      }
+    }
+  TN_ON_DEVICE(d->ctx->device);
+  const bool one_row = d->max_classes <= 16;                // (the pitch of the workspace follows the handle, not the call)
+  const size_t pitch = one_row ? trans_pitch<true>() : trans_pitch<false>();
+  if (!d->trans_ws) {
+    const size_t mp = ((size_t)d->max_positions + 3) & ~(size_t)3, mc = d->max_classes;
+    const size_t bytes = mp * (pitch + 4 + 1) + mc * mc * 4 + 4;
+    void *ws = nullptr;
+    if (hipMalloc(&ws, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      tn_set_error("tn_event_decoder_run_transitions: device allocation of the back-pointer workspace failed (" + std::to_string(bytes) +
+                   " bytes)");
+      return TN_ERR_NOMEM;
+    }
+    d->trans_ws = ws;
+    d->trans_bytes = bytes;
+    d->back = (uint8_t *)ws;
+    d->trans = (float *)(d->back + mp * pitch);
+    d->tvid_first = (int32_t *)(d->trans + mc * mc);
+    d->tvid_count = d->tvid_first + mp;
+    d->tamax = (uint8_t *)(d->tvid_count + 1);
+  }
+  hipStream_t s = stream ? (hipStream_t)stream : d->ctx->stream;
+  TN_HIP_CHECK(hipMemcpyAsync(d->trans, transitions, (size_t)C * C * 4, hipMemcpyHostToDevice, s));
+  const int tiles = (M + kEventTile - 1) / kEventTile;
+  int32_t *label = label_out ? label_out : d->label;
+  float *conf = conf_out ? conf_out : d->conf;
+  hipLaunchKernelGGL(event_flag_kernel<false>, dim3(tiles), dim3(kEventTile), 0, s, logits, N, C, rows, start, M, (const int32_t *)nullptr,
+                     (float *)nullptr, d->flags, d->counts);
+  hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(kEventScanBlock), 0, s, d->counts, tiles, d->offsets, d->tvid_count);
+  hipLaunchKernelGGL(event_scatter_kernel, dim3(tiles), dim3(kEventTile), 0, s, d->flags, M, d->offsets, d->tvid_first);
+  const int chains = std::min(M, kViterbiMaxGrid);
+  if (one_row) {
+    hipLaunchKernelGGL(viterbi_trans_forward_kernel<true>, dim3(chains), dim3(kViterbiThreads), 0, s, logits, N, C, rows, M, d->tvid_first,
+                       d->tvid_count, d->trans, d->back, d->tamax);
+    hipLaunchKernelGGL(viterbi_trans_backtrack_kernel<true>, dim3(chains), dim3(64), 0, s, d->back, d->tamax, M, d->tvid_first,
+                       d->tvid_count, label);
+  } else {
+    hipLaunchKernelGGL(viterbi_trans_forward_kernel<false>, dim3(chains), dim3(kViterbiThreads), 0, s, logits, N, C, rows, M, d->tvid_first,
+                       d->tvid_count, d->trans, d->back, d->tamax);
+    hipLaunchKernelGGL(viterbi_trans_backtrack_kernel<false>, dim3(chains), dim3(64), 0, s, d->back, d->tamax, M, d->tvid_first,
+                       d->tvid_count, label);
+  }
+  hipLaunchKernelGGL(event_flag_kernel<true>, dim3(tiles), dim3(kEventTile), 0, s, logits, N, C, rows, start, M, label, conf, d->flags,
+                     d->counts);
+  hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(kEventScanBlock), 0, s, d->counts, tiles, d->offsets, count);
+  hipLaunchKernelGGL(event_scatter_kernel, dim3(tiles), dim3(kEventTile), 0, s, d->flags, M, d->offsets, ev_first);
+  const int blocks = std::min((M + 3) / 4, 2048);
+  hipLaunchKernelGGL(event_reduce_kernel, dim3(blocks), dim3(256), 0, s, label, conf, M, count, ev_first, ev_last, ev_cls, ev_score, ev_peak);
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+
+extern "C" int tn_dbg_event_decoder_transition_geometry(int *tile, int *pitch16, int *pitch64) {
+  TN_REQUIRE(tile && pitch16 && pitch64, "tn_dbg_event_decoder_transition_geometry: null argument (tile, pitch16, pitch64)");
+  *tile = kViterbiTile;
+  *pitch16 = trans_pitch<true>();
+  *pitch64 = trans_pitch<false>();
+  return TN_OK;
+}
+
 extern "C" int tn_dbg_event_decoder_workspace_bytes(const tn_event_decoder *d, size_t *bytes) {
   TN_REQUIRE(d && bytes, "tn_dbg_event_decoder_workspace_bytes: null argument (handle, bytes)");
-  *bytes = d->ws_bytes + d->path_bytes;
+  *bytes = d->ws_bytes + d->path_bytes + d->trans_bytes;
   return TN_OK;
 }

@@ -353,6 +353,15 @@ def event_decoder_switch_geometry():
     return tile.value
 
 
+def event_decoder_transition_geometry():
+    """``tn_dbg_event_decoder_transition_geometry``: (positions of a video the transition-matrix path kernels take per step, bytes of a
+    position's back-pointer row in a handle of up to 16 classes, the same above 16); touches no device."""
+    tile, p16, p64 = C.c_int(), C.c_int(), C.c_int()
+    check(_lib.load().tn_dbg_event_decoder_transition_geometry(C.byref(tile), C.byref(p16), C.byref(p64)),
+          "tn_dbg_event_decoder_transition_geometry")
+    return tile.value, p16.value, p64.value
+
+
 class EventDecoder(_Handle):
     """Per-frame logits -> events on the device (``tn_event_decoder_*``, docs/kernels.md "Event decoding"): workspace for up to
     ``max_positions`` positions of up to ``classes`` classes; ``decode`` allocates its outputs only."""
@@ -367,13 +376,14 @@ class EventDecoder(_Handle):
         self.handle = h
 
     def workspace_bytes(self) -> int:
-        """``tn_dbg_event_decoder_workspace_bytes``: device bytes the handle holds (the path workspace of ``switch_cost`` is allocated
-        by the first call that gives one)."""
+        """``tn_dbg_event_decoder_workspace_bytes``: device bytes the handle holds (the path workspace of ``switch_cost`` and the back-pointer
+        workspace of ``transitions`` are each allocated by the first call that gives one)."""
         n = C.c_size_t()
         check(self.lib.tn_dbg_event_decoder_workspace_bytes(self.handle, C.byref(n)), "tn_dbg_event_decoder_workspace_bytes")
         return n.value
 
-    def decode(self, logits: torch.Tensor, rows, start, smooth: int = 1, return_frames: bool = False, switch_cost: float | None = None):
+    def decode(self, logits: torch.Tensor, rows, start, smooth: int = 1, return_frames: bool = False, switch_cost: float | None = None,
+               transitions=None):
         """``logits`` (N, C) fp32 on the GPU; ``rows`` (M,) the logit row of every position of the time-ordered list (clamped into
         ``[0, N)``), ``start`` (M,) non-zero where a video begins, ``smooth`` the odd window width in [1, 63].  Returns a dict of
         tensors on the GPU, one entry per event in order of ``first``: ``first``, ``last`` (positions, inclusive), ``cls`` (int32),
@@ -381,7 +391,22 @@ class EventDecoder(_Handle):
         ``return_frames`` also ``label`` (M,) int32 and ``conf`` (M,) float32 of every position.  Synchronises once, for the count.
         ``switch_cost`` (finite, >= 0, in logit units; not together with ``smooth`` > 1): the labels are the path that maximises the
         summed scores minus ``switch_cost`` per change of label inside a video (``tn_event_decoder_run_switch``), ``conf`` the
-        unsmoothed probability of the label; None: the call is what it was."""
+        unsmoothed probability of the label; None: the call is what it was.
+        ``transitions`` (a numpy array or CPU tensor (C, C), ``[from, to]``, every entry <= 0 or -inf, the diagonal finite; not together
+        with ``smooth`` > 1 or ``switch_cost``): the labels are the path that maximises the summed scores plus ``transitions[a, b]`` for
+        every position labelled ``b`` that follows one labelled ``a`` inside a video (``tn_event_decoder_run_transitions``), ``conf`` as
+        with ``switch_cost``; None: the call is what it was."""
+        if transitions is not None:                                             # refused before anything is launched
+            if int(smooth) != 1:
+                raise ValueError(f"EventDecoder.decode: transitions decodes the unsmoothed scores, not together with smooth={smooth}")
+            if switch_cost is not None:
+                raise ValueError(f"EventDecoder.decode: transitions is a matrix of switch costs, not together with switch_cost={switch_cost}")
+            if isinstance(transitions, torch.Tensor):
+                if transitions.device.type != "cpu":
+                    raise ValueError(f"EventDecoder.decode: transitions is read on the host, got a tensor on {transitions.device}")
+                transitions = transitions.detach().numpy()
+            from .events import check_transitions
+            transitions = np.ascontiguousarray(check_transitions(transitions, logits.shape[-1], "EventDecoder.decode"))
         if switch_cost is not None:                                             # refused before anything is launched
             if int(smooth) != 1:
                 raise ValueError(f"EventDecoder.decode: switch_cost decodes the unsmoothed scores, not together with smooth={smooth}")
@@ -399,7 +424,12 @@ class EventDecoder(_Handle):
         count = torch.zeros(1, dtype=torch.int32, device=dev)
         label = torch.empty(m, dtype=torch.int32, device=dev) if return_frames else None
         conf = torch.empty(m, dtype=torch.float32, device=dev) if return_frames else None
-        if switch_cost is None:
+        if transitions is not None:
+            check(self.lib.tn_event_decoder_run_transitions(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start),
+                                                            m, transitions.ctypes.data_as(C.c_void_p), ptr(label), ptr(conf), ptr(ints[0]),
+                                                            ptr(ints[1]), ptr(ints[2]), ptr(flts[0]), ptr(flts[1]), ptr(count), None),
+                  "tn_event_decoder_run_transitions")
+        elif switch_cost is None:
             check(self.lib.tn_event_decoder_run(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start), m, int(smooth),
                                                 ptr(label), ptr(conf), ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(flts[0]), ptr(flts[1]),
                                                 ptr(count), None), "tn_event_decoder_run")    # (stream NULL: the context's)

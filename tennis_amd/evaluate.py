@@ -723,7 +723,38 @@ def build_parser():
                         "(Viterbi on the GPU; finite, >= 0, in logit units; 0 is the per-frame arg-max).  A one-frame glitch that leads "
                         "by less than twice the penalty is absorbed, boundaries stay where the scores put them.  For a stay "
                         "probability s over C classes: ln(s (C - 1) / (1 - s)).  Not together with --event_smooth above 1")
+    p.add_argument("--event_transitions", type=str, default=None, metavar="train|FILE.npy",
+                   help="with --save_events, instead of smoothing or one switch cost: decode every video as one label path under a "
+                        "(classes, classes) matrix of transition scores, entry [from, to] added where a frame labelled `from` is "
+                        "followed by one labelled `to` (an HMM over the frame classifier, Viterbi on the GPU).  train: the log "
+                        "probabilities of the label bigrams of this run's train split, counted in time order with the test split's "
+                        "--every, --window, --stride and --padding, unbalanced (labels only: nothing is encoded).  FILE.npy: a matrix "
+                        "of your own, every entry <= 0, -inf off the diagonal forbids a transition.  Not together with "
+                        "--event_smooth above 1 or --event_switch_cost")
+    p.add_argument("--event_transition_prior", type=float, default=None,
+                   help="with --event_transitions train: the count added to every bigram before the logarithm (> 0; default 1)")
+    p.add_argument("--event_transition_scale", type=float, default=None,
+                   help="with --event_transitions train: the factor on the log probabilities, i.e. how much the grammar weighs "
+                        "against the per-frame scores (> 0; default 1)")
     return p
+
+
+def event_transitions(flags, test_set, every):
+    """The matrix of ``--event_transitions`` -> ``(T (classes, classes) float32, where it came from)``.  ``train``: the bigrams of the
+    run's own train split in time order (``events.transition_scores``); the split is built for its labels only."""
+    from .events import check_transitions, time_order, transition_scores
+    classes = len(test_set.classes)
+    if flags.event_transitions != "train":
+        return check_transitions(np.load(flags.event_transitions, allow_pickle=False), classes, "--event_transitions"), flags.event_transitions
+    train_set = TennisSet(root=flags.root, split="train", every=every, padding=flags.padding, stride=flags.stride, window=flags.window,
+                          model_id=flags.model_id, split_id=flags.split_id, balance=False, data_shape=flags.data_shape,
+                          frames_per_video=flags.frames_per_video, decode=flags.decode)
+    rows, start, _, _ = time_order(train_set)
+    labels = np.asarray([train_set.classes.index(train_set._samples[int(i)][2]) for i in rows], np.int64)
+    prior = 1.0 if getattr(flags, "event_transition_prior", None) is None else flags.event_transition_prior
+    scale = 1.0 if getattr(flags, "event_transition_scale", None) is None else flags.event_transition_scale
+    return (transition_scores(labels, start, classes, prior=prior, scale=scale),
+            "the %d label bigrams of the train split (prior %g, scale %g)" % (int((start == 0).sum()), prior, scale))
 
 
 def main(argv=None):
@@ -892,6 +923,12 @@ def _main_rank(flags, rank, world, dev):
     if kept is not None:                                                     # the logits never left the device: decode them there
         cost = getattr(flags, "event_switch_cost", None)
         path = {} if cost is None else {"switch_cost": cost}                 # (without the flag the call is the call it was)
+        if getattr(flags, "event_transitions", None) is not None:
+            matrix, source = event_transitions(flags, test_set, every[2])
+            off = matrix[~np.eye(len(matrix), dtype=bool)]
+            print("Event transitions (%d x %d) from %s: smallest diagonal entry %.4g, largest off-diagonal entry %.4g" %
+                  (matrix.shape[0], matrix.shape[1], source, np.diagonal(matrix).min(), off.max() if off.size else float("nan")))
+            path["transitions"] = matrix
         ev_cols, ev_metric = decode_split(test_set, torch.cat(kept["logits"]), kept["order"], smooth=getattr(flags, "event_smooth", None) or 1,
                                           **path)
         events_file = os.path.join(flags.exp_root, flags.model_id, flags.split + "_events.npz")

@@ -21,12 +21,33 @@ def check_save_events(flags, world=1):
     device."""
     smooth = getattr(flags, "event_smooth", None)
     cost = getattr(flags, "event_switch_cost", None)
+    trans = getattr(flags, "event_transitions", None)
+    prior = getattr(flags, "event_transition_prior", None)
+    scale = getattr(flags, "event_transition_scale", None)
+    if trans is None:
+        for name, value in (("prior", prior), ("scale", scale)):
+            if value is not None:
+                raise SystemExit("--event_transition_%s %s sets how --event_transitions train turns counts into scores: give "
+                                 "--event_transitions too" % (name, value))
     if not getattr(flags, "save_events", False):
         if smooth is not None:
             raise SystemExit("--event_smooth %s sets the smoothing window of --save_events: give --save_events too" % smooth)
         if cost is not None:
             raise SystemExit("--event_switch_cost %s sets the label-switch penalty of --save_events: give --save_events too" % cost)
+        if trans is not None:
+            raise SystemExit("--event_transitions %s sets the class-transition scores of --save_events: give --save_events too" % trans)
         return
+    if trans is not None:
+        if cost is not None:
+            raise SystemExit("--event_transitions is a matrix of switch costs: not together with --event_switch_cost %s" % cost)
+        if smooth is not None and smooth > 1:
+            raise SystemExit("--event_transitions decodes the unsmoothed scores as one path: not together with --event_smooth %d" % smooth)
+        if trans != "train" and (prior is not None or scale is not None):
+            raise SystemExit("--event_transition_prior and --event_transition_scale shape the matrix that --event_transitions train "
+                             "counts: %s is used as it is" % trans)
+        for name, value in (("prior", prior), ("scale", scale)):
+            if value is not None and not (np.isfinite(value) and value > 0):
+                raise SystemExit("--event_transition_%s %s: it must be finite and > 0, so that every score is finite" % (name, value))
     if cost is not None:
         if not (np.isfinite(cost) and cost >= 0):
             raise SystemExit("--event_switch_cost %s: the penalty for every change of label is subtracted from a path's summed scores, "
@@ -79,13 +100,61 @@ def label_runs(labels, start):
     return first, last, labels[first]
 
 
-def viterbi_labels(logits, rows, start, switch_cost, dtype=np.float64):
+def check_transitions(transitions, classes=None, who="transitions"):
+    """-> the matrix as (C, C) float32, or ValueError naming the first entry ``[from, to]`` that is NaN or positive, or the first
+    diagonal entry that is not finite (the contract of ``tn_event_decoder_run_transitions``)."""
+    t = np.asarray(transitions, np.float32)
+    if t.ndim != 2 or t.shape[0] != t.shape[1] or t.shape[0] < 1 or (classes is not None and t.shape[0] != classes):
+        raise ValueError(f"{who}: the matrix must be (C, C)" + ("" if classes is None else f" = ({classes}, {classes})") + f", got {t.shape}")
+    bad = np.isnan(t) | (t > 0) | (np.eye(len(t), dtype=bool) & ~np.isfinite(t))
+    if bad.any():
+        p, c = (int(i) for i in np.argwhere(bad)[0])
+        why = "is NaN" if np.isnan(t[p, c]) else "is positive" if t[p, c] > 0 else "is not finite (staying must always be possible)"
+        raise ValueError(f"{who}: transitions[{p}][{c}] {why}")
+    return t
+
+
+def transition_scores(labels, start, classes, prior=1.0, scale=1.0):
+    """Transition scores from the label bigrams of a time-ordered list: ``N[p, c]`` counts the positions that are not a video's first
+    (``start`` zero, position 0 never counts) with ``labels[m - 1] = p`` and ``labels[m] = c``;
+    ``T = scale * ln((N + prior) / (N.sum(1, keepdims=True) + prior * classes))`` in float64 -> ``(classes, classes)`` float32, every
+    entry finite and < 0, the rows of ``exp(T / scale)`` summing to 1.  ``prior`` > 0 (additive smoothing) and ``scale`` > 0."""
+    classes = int(classes)
+    if classes < 1:
+        raise ValueError(f"transition_scores: classes must be >= 1, got {classes}")
+    if not (np.isfinite(prior) and prior > 0):
+        raise ValueError(f"transition_scores: prior must be finite and > 0, got {prior}")
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"transition_scores: scale must be finite and > 0, got {scale}")
+    labels = np.asarray(labels, np.int64).reshape(-1)
+    begins = np.asarray(start).reshape(-1) != 0
+    if len(labels) != len(begins):
+        raise ValueError(f"transition_scores: {len(labels)} labels for {len(begins)} start flags")
+    if len(labels) and (labels.min() < 0 or labels.max() >= classes):
+        raise ValueError(f"transition_scores: labels must lie in [0, {classes}), got [{labels.min()}, {labels.max()}]")
+    counts = np.zeros((classes, classes), np.float64)
+    if len(labels) > 1:
+        inside = ~begins[1:]
+        np.add.at(counts, (labels[:-1][inside], labels[1:][inside]), 1.0)
+    t = float(scale) * np.log((counts + float(prior)) / (counts.sum(1, keepdims=True) + float(prior) * classes))
+    return t.astype(np.float32)
+
+
+def viterbi_labels(logits, rows, start, switch_cost=None, dtype=np.float64, transitions=None):
     """The label path of ``EventDecoder.decode(..., switch_cost=...)`` on the host, in ``dtype`` arithmetic (docs/kernels.md "Event
     decoding with a switch cost"): per video the path that maximises the sum of ``e[m, label[m]]`` minus ``switch_cost`` for every
     change of label, ``e[m] = q - max(q)``, ``q = logits[clip(rows[m], 0, N - 1)]``.  Forward ``v_0 = e_0``, ``stay_t = v_{t-1} >=
     -switch_cost``, ``u_t = e_t + max(v_{t-1}, -switch_cost)``, ``v_t = u_t - max(u_t)``, ``a_t`` the first arg-max of ``v_t``; back
     ``label[T-1] = a_{T-1}``, ``label[t-1] = label[t] if stay_t[label[t]] else a_{t-1}``.  A Python loop over the positions.
+    With ``transitions`` (C, C) in place of ``switch_cost`` (exactly one of the two): the path of ``decode(..., transitions=...)``
+    (docs/kernels.md "Event decoding with a transition matrix"), which adds ``transitions[label[m-1], label[m]]`` at every position
+    that is not its video's first: ``w_t[c] = max_p (v_{t-1}[p] + T[p, c])``, ``b_t[c] = c`` if ``v_{t-1}[c] + T[c, c]`` attains it,
+    else the smallest ``p`` that does, ``u_t = e_t + w_t``, ``v_t`` and ``a_t`` as above; back ``label[t-1] = b_t[label[t]]``.
     -> ``label (M,)`` int64."""
+    if (switch_cost is None) == (transitions is None):
+        raise ValueError("viterbi_labels: give exactly one of switch_cost and transitions")
+    if transitions is not None:
+        return _viterbi_labels_transitions(logits, rows, start, transitions, dtype)
     dtype = np.dtype(dtype).type
     cost = float(switch_cost)
     if not (np.isfinite(cost) and cost >= 0):
@@ -127,15 +196,64 @@ def viterbi_labels(logits, rows, start, switch_cost, dtype=np.float64):
     return label
 
 
+def _viterbi_positions(logits, rows, start, who):
+    """the argument checks of ``viterbi_labels`` -> ``(logits (N, C), rows (M,) clipped into [0, N), the videos' bounds [0, ..., M])``"""
+    logits = np.asarray(logits)
+    if logits.ndim != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"{who}: logits must be (N, C), got {logits.shape}")
+    rows = np.clip(np.asarray(rows, np.int64).reshape(-1), 0, logits.shape[0] - 1)
+    begins = np.asarray(start).reshape(-1) != 0
+    if len(rows) != len(begins):
+        raise ValueError(f"{who}: {len(rows)} rows for {len(begins)} start flags")
+    bounds = np.flatnonzero(begins).tolist()
+    if not bounds or bounds[0] != 0:
+        bounds = [0] + bounds
+    bounds.append(len(rows))
+    return logits, rows, bounds
+
+
+def _viterbi_labels_transitions(logits, rows, start, transitions, dtype):
+    dtype = np.dtype(dtype).type
+    logits, rows, bounds = _viterbi_positions(logits, rows, start, "viterbi_labels")
+    trans = check_transitions(transitions, logits.shape[1], "viterbi_labels").astype(dtype)
+    m, c = len(rows), logits.shape[1]
+    label = np.zeros(m, np.int64)
+    if not m:
+        return label
+    q = logits[rows].astype(dtype)
+    e = q - q.max(1, keepdims=True)
+    diag = np.diagonal(trans)
+    cls = np.arange(c)
+    back = np.zeros((m, c), np.int64)
+    amax = np.zeros(m, np.int64)
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        v = e[a]
+        amax[a] = int(np.argmax(v))
+        for t in range(a + 1, b):
+            cand = v[:, None] + trans                                            # [p, c], every sum rounded to dtype
+            w = cand.max(0)
+            back[t] = np.where(v + diag == w, cls, cand.argmax(0))               # staying wins a tie, else the smallest p
+            u = e[t] + w
+            v = u - u.max()
+            amax[t] = int(np.argmax(v))
+        lab = amax[b - 1]
+        label[b - 1] = lab
+        for t in range(b - 1, a, -1):
+            lab = back[t, lab]
+            label[t - 1] = lab
+    return label
+
+
 def save_events(file_path, video, first_frame, last_frame, cls, score, peak, first_sample, last_sample, gt_video, gt_first_frame,
-                gt_last_frame, gt_cls, smooth, tiou, precision, recall, f1, switch_cost=None):
+                gt_last_frame, gt_cls, smooth, tiou, precision, recall, f1, switch_cost=None, transitions=None):
     """One ``.npz`` of flat arrays (``np.load(..., allow_pickle=False)`` reads it).  Per predicted event ``video`` (unicode),
     ``first_frame`` / ``last_frame`` (frame numbers, inclusive), ``cls``, ``score`` the mean and ``peak`` the maximum of the smoothed
     score of ``cls``, ``first_sample`` / ``last_sample`` (dataset indices of the two end frames); per ground-truth event ``gt_video``,
     ``gt_first_frame``, ``gt_last_frame``, ``gt_cls``; ``smooth`` the window width, ``tiou (T,)`` the thresholds and ``precision``,
     ``recall``, ``f1`` (T, classes) of ``metrics.events.EventPRF1``.  A run of the background class is an event too, and smoothing
     moves boundaries by up to (smooth - 1) / 2 frames.  ``switch_cost`` (None: the file has no such column): the label-switch penalty the
-    events were decoded with, a float64 scalar; ``score`` and ``peak`` are then of the unsmoothed probability."""
+    events were decoded with, a float64 scalar; ``score`` and ``peak`` are then of the unsmoothed probability.  ``transitions`` (None:
+    the file has no such column): the (classes, classes) float32 transition scores the events were decoded with, ``[from, to]``."""
     i64 = lambda a: np.asarray(a, np.int64).reshape(-1)
     f32 = lambda a: np.asarray(a, np.float32).reshape(-1)
     txt = lambda a: np.asarray(list(a), dtype=np.str_).reshape(-1)
@@ -156,6 +274,8 @@ def save_events(file_path, video, first_frame, last_frame, cls, score, peak, fir
             raise ValueError(f"save_events: {k} must be ({t}, classes), got {cols[k].shape}")
     if switch_cost is not None:
         cols["switch_cost"] = np.asarray(float(switch_cost), np.float64)
+    if transitions is not None:
+        cols["transitions"] = check_transitions(transitions, cols["f1"].shape[1], "save_events")
     os.makedirs(os.path.dirname(os.path.abspath(file_path)), exist_ok=True)
     np.savez(file_path, **cols)
 
@@ -170,11 +290,12 @@ def load_events(file_path):
     return d
 
 
-def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), decoder=None, switch_cost=None):
+def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), decoder=None, switch_cost=None, transitions=None):
     """The events of one evaluated split: ``logits`` (N, classes) fp32 ON THE GPU, row r the logits of sample ``order[r]`` (None:
     of sample r).  The positions are time-ordered on the host (``time_order``), decoded on the device (``engine.EventDecoder``; only
     the events come back), the ground truth is ``label_runs`` of the samples' labels, both are scored with ``EventPRF1``.
-    ``switch_cost`` (None: per-frame arg-max of the smoothed scores) goes to the decoder and into the columns.
+    ``switch_cost`` (None: per-frame arg-max of the smoothed scores) goes to the decoder and into the columns, and so does
+    ``transitions`` (None: no transition matrix; (classes, classes), see ``EventDecoder.decode``).
     -> ``(columns of save_events, EventPRF1)``."""
     from .engine import EventDecoder
     from .metrics.events import EventPRF1
@@ -182,6 +303,8 @@ def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), d
     order = np.arange(len(dataset._samples)) if order is None else np.asarray(order, np.int64).reshape(-1)
     decoder = decoder or EventDecoder(len(rows), logits.shape[1])
     path = {} if switch_cost is None else {"switch_cost": float(switch_cost)}    # (without it the call is the call it was)
+    if transitions is not None:
+        path["transitions"] = check_transitions(transitions, logits.shape[1], "decode_split")
     ev = {k: v.cpu().numpy() for k, v in decoder.decode(logits, rows, start, smooth=smooth, **path).items()}
     first, last = ev["first"].astype(np.int64), ev["last"].astype(np.int64)
     labels = np.asarray([dataset.classes.index(dataset._samples[int(i)][2]) for i in order[rows]], np.int64)
@@ -201,6 +324,8 @@ def event_table(cols, classes, limit=40):
     """The printed form of ``decode_split``'s columns: one line per predicted event (the first ``limit``), then the scores."""
     n = len(cols["video"])
     how = "smooth %d" % int(cols["smooth"]) if cols.get("switch_cost") is None else "switch cost %g" % float(cols["switch_cost"])
+    if cols.get("transitions") is not None:
+        how = "transition matrix"
     lines = ["Events: %d predicted, %d ground truth (%s)" % (n, len(cols["gt_video"]), how)]
     for i in range(min(n, limit)):
         lines.append("  %s\t%s\tframes %d-%d\tscore %.3f\tpeak %.3f" % (cols["video"][i], classes[int(cols["cls"][i])],
