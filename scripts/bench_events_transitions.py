@@ -12,8 +12,10 @@ Input: that of scripts/bench_events.py - 786 455 x 11 logits (the 5-match corpus
     time.  It is a Python loop with a (C, C) sum per position, so it is timed on the FIRST VIDEO ONLY and scaled by the number of
     positions (the file says so); the runs it finds there must be the device's runs of that video (count, sum of the first
     positions, sum of the classes).
-  * (c) the parent-commit check: ``decode(switch_cost=2)``, ``decode(smooth=1)`` and ``decode(smooth=9)`` on this build against the
-    parent's (``--parent-tree``: a checkout of the parent commit with its library built), device time and wall time as above.
+  * (c) the parent-commit check: ``decode(transitions=T)``, ``decode(switch_cost=2)``, ``decode(smooth=1)`` and ``decode(smooth=9)``
+    on this build against the parent's (``--parent-tree``: a checkout of the parent commit with its library built), device time and
+    wall time as above, and a SHA-256 of the bytes of ``label``, ``conf`` and the five event arrays: the two builds must agree on
+    every one, and this build's median device time is held against the parent's own range over its runs, widened by its width.
   * (d) the per-position time of the two chains: device time over the positions of one video (the videos run side by side).
 
 One box, every run a fresh process (``--worker``), the routes alternating, three runs each; medians and the range.  This process
@@ -21,6 +23,7 @@ never opens the GPU.
 
     python scripts/bench_events_transitions.py --parent-tree /path/to/parent/checkout [--out profiles/events_transitions_bench.json]"""
 import argparse
+import hashlib
 import json
 import os
 import subprocess
@@ -100,6 +103,8 @@ def worker(kind, tree, rows, reps, width, cost):
             out = {k: v.cpu().numpy() for k, v in dec.decode(logits, rows_d, start_d, smooth=width, **how).items()}
             wall.append((time.perf_counter() - t0) * 1e3)
         res.update(device=_stats(devt), wall=_stats(wall), workspace_bytes=dec.workspace_bytes())
+        frames = dec.decode(logits, rows_d, start_d, smooth=width, return_frames=True, **how)
+        res["sha256"] = {k: hashlib.sha256(v.cpu().numpy().tobytes()).hexdigest() for k, v in sorted(frames.items())}
         first, cls = out["first"], out["cls"]
         res["score_sum"] = float(out["score"].astype(np.float64).sum())
         res.update(events_all=int(len(first)), first_sum_all=int(first.astype(np.int64).sum()), cls_sum_all=int(cls.astype(np.int64).sum()))
@@ -122,7 +127,7 @@ def child(kind, tree, a, width=1, reps=None):
     return json.loads(lines[-1][7:])
 
 
-ROUTES = {"cost": ("path", 1), "w1": ("smooth", 1), "w9": ("smooth", 9)}
+ROUTES = {"trans": ("trans", 1), "cost": ("path", 1), "w1": ("smooth", 1), "w9": ("smooth", 9)}
 
 
 def main():
@@ -143,15 +148,14 @@ def main():
         return worker(a.worker, os.path.abspath(a.tree), a.rows, a.reps, a.width, a.switch_cost)
     this = os.path.abspath(os.path.join(HERE, ".."))
     parent = os.path.abspath(a.parent_tree) if a.parent_tree else None
-    runs = {k: [] for k in ["trans", "host"] + [f"{t}_{r}" for t in ("this", "parent") for r in ROUTES]}
+    runs = {k: [] for k in ["host"] + [f"{t}_{r}" for t in ("this", "parent") for r in ROUTES]}
     for _ in range(a.runs):                     # alternating, a fresh process each
-        runs["trans"].append(child("trans", this, a))
         runs["host"].append(child("host", this, a, reps=a.host_reps))
         for r, (kind, w) in ROUTES.items():
             runs[f"this_{r}"].append(child(kind, this, a, w))
             if parent:
                 runs[f"parent_{r}"].append(child(kind, parent, a, w))
-    d, h = runs["trans"], runs["host"]
+    d, h = runs["this_trans"], runs["host"]
     per_video = a.rows // VIDEOS
     doc = {"shape": {"rows": a.rows, "classes": CLASSES, "videos": VIDEOS, "runs_of": "10-200 positions", "rows_order": "permutation"},
            "matrix": {"from": "events.transition_scores of the planted labels, prior 1, scale 1",
@@ -177,7 +181,11 @@ def main():
             doc[f"{r}_device_time_difference_ms"] = round(a_["median_ms"] - b_["median_ms"], 4)
             doc[f"{r}_spread_of_three_runs_ms"] = round(spread, 4)
             doc[f"{r}_same_result"] = all(runs[f"this_{r}"][0][k] == runs[f"parent_{r}"][0][k]
-                                          for k in ("events", "first_sum", "cls_sum", "score_sum"))
+                                          for k in ("events_all", "first_sum_all", "cls_sum_all", "score_sum"))
+            doc[f"{r}_sha256"] = runs[f"parent_{r}"][0]["sha256"]
+            doc[f"{r}_same_sha256"] = all(x["sha256"] == doc[f"{r}_sha256"] for x in runs[f"this_{r}"] + runs[f"parent_{r}"])
+            width = b_["max_ms"] - b_["min_ms"]
+            doc[f"{r}_median_inside_parent_range_widened_by_its_width"] = b_["min_ms"] - width <= a_["median_ms"] <= b_["max_ms"] + width
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)

@@ -21,27 +21,26 @@
 //             a_t = first arg-max of v_t          (fp32, positions in order: the sequential order is the definition)
 //   back      label[T-1] = a_{T-1};  label[t-1] = stay_t[label[t]] ? label[t] : a_{t-1}
 //   conf[m]   = softmax(q)[label[m]], computed as event_score_kernel computes p
-// Nine plain launches: the video bounds are the set flags of `start`, found with the scan and scatter above; then
-//   viterbi_forward_kernel    one workgroup per video (grid-stride over the videos, whose number only the device knows).  Wave 0 walks
-//                             the chain, lane c holding v[c]; the maximum is a DPP all-reduce, stay and the arg-max one ballot each.
-//                             Waves 1..3 gather the next tile of kViterbiTile rows and store e into the other half of the LDS.
-//   viterbi_backtrack_kernel  one wave per video, tiles back to front: lane j holds stay_{t+1} and a_t of its position, the tile in
-//                             front is in flight while the wave walks this one with scalar selects
-//   event_flag_kernel<true>   one thread per position: conf, the run-start flags and the tile counts - what event_score_kernel
-//                             leaves behind, so that scan, scatter and reduce run unchanged
-//
 // With a transition matrix (tn_event_decoder_run_transitions; docs/kernels.md "Event decoding with a transition matrix") the path
 // maximises sum_m e[m, label[m]] + sum_{m not a video's first} T[label[m-1], label[m]], T (C, C) with entries <= 0 or -inf and a
 // finite diagonal:
 //   forward   v_0 = e_0;  w_t[c] = max_p (v_{t-1}[p] + T[p, c]);  b_t[c] = c if v_{t-1}[c] + T[c, c] attains w_t[c], else the smallest
 //             p that does;  u_t[c] = e_t[c] + w_t[c];  v_t = u_t - max_c u_t;  a_t = first arg-max of v_t
 //   back      label[T-1] = a_{T-1};  label[t-1] = b_t[label[t]]
-// The same nine launches with two other chain kernels:
-//   viterbi_trans_forward_kernel    the staging of viterbi_forward_kernel; on the chain lane c holds v[c] and the column T[:, c] in
-//                                   registers, v[p] comes as a scalar from readlane, the C candidates of a step are independent.
-//                                   The back-pointers of a tile go through LDS and leave as whole rows of a fixed pitch.
-//   viterbi_trans_backtrack_kernel  one wave per video, tiles back to front: the rows of the tile in front are in flight while the
-//                                   wave walks this one, one dependent LDS byte read per position
+// Either path is nine plain launches (and the copy of the matrix): the video bounds are the set flags of `start`, found with the
+// scan and scatter above (find_videos); then
+//   viterbi_forward_kernel<ONE_ROW, TRANS>  one workgroup per video (grid-stride over the videos, whose number only the device knows).
+//                             Wave 0 walks the chain, lane c holding v[c]; the maximum is a DPP all-reduce, the arg-max one ballot.
+//                             Waves 1..3 gather the next tile of kViterbiTile rows and store e into the other half of the LDS.
+//                             TRANS selects the step and what a position leaves behind: the stay mask, one ballot, kept in a register;
+//                             or b_t, with the column T[:, c] in registers, v[p] a scalar from readlane and the C candidates of a
+//                             step independent - a tile's back-pointers go through LDS and leave as whole rows of a fixed pitch.
+//   viterbi_backtrack_kernel  one wave per video, tiles back to front: lane j holds stay_{t+1} and a_t of its position, the tile in
+//                             front is in flight while the wave walks this one with scalar selects
+//   viterbi_trans_backtrack_kernel  the same walk over b_t: the rows of the tile in front are in flight while the wave walks this
+//                             one, one dependent LDS byte read per position
+//   event_flag_kernel<true>   one thread per position: conf, the run-start flags and the tile counts - what event_score_kernel
+//                             leaves behind, so that scan, scatter and reduce run unchanged (emit_events)
 #include "common.h"
 
 #include <cmath>
@@ -235,7 +234,7 @@ __global__ __launch_bounds__(256) void event_reduce_kernel(const int32_t *__rest
   }
 }
 
-// ---- the switch-cost path ----
+// ---- the two path decoders ----
 
 constexpr int kViterbiTile = 64;         // positions of a video per step of the forward and backtrack kernels
 constexpr int kViterbiThreads = 256;     // forward: wave 0 walks, the other waves stage
@@ -319,18 +318,50 @@ __device__ __forceinline__ void viterbi_stage(float (*buf)[kEventMaxClasses], in
   }
 }
 
+// bytes of a position's row of back-pointers: one row of lanes up to 16 classes, one lane per class above
 template <bool ONE_ROW>
+__host__ __device__ constexpr int trans_pitch() { return ONE_ROW ? 16 : kEventMaxClasses; }
+
+struct video_span {
+  int vb, ve, ntiles;      // positions [vb, ve) in tiles of kViterbiTile, counted from vb
+};
+
+__device__ __forceinline__ video_span video_of(const int32_t *__restrict__ vid_first, int V, int vid, int M) {
+  const int vb = vid_first[vid], ve = vid + 1 < V ? vid_first[vid + 1] : M;
+  return {vb, ve, (ve - vb + kViterbiTile - 1) / kViterbiTile};
+}
+
+// TRANS = false, the switch cost: a position leaves its stay mask (one ballot, kept in a register) in `stay`.
+// TRANS = true, the matrix: on the chain lane c holds v[c], the column T[:, c] (tc, -inf past C: such a predecessor is never chosen)
+// and T[c, c].  A step forms the candidates v[p] + T[p, c] in ascending p from v[p] as a scalar and keeps the first maximum (strict
+// comparison), then lets staying win a tie; a position leaves its row of b_t in `back`, through sb.  A NaN compares false
+// everywhere, so every stored index is in [0, C) whatever the floats are.
+// Every u is <= 0 or -inf on either path (e <= 0, max(v, -cost) <= 0, T <= 0), so the wave maximum is wave_max_nonpos's.
+// Each branch holds its whole step, the four lines from u to a_t included.  They are the chain, and hipcc's schedule of it follows how
+// they are written: shared behind the branches (a helper, a lambda, or variables declared in front) the same operations came out
+// with the compare results in SGPR pairs instead of vcc and more wait states - 16.36 against 15.72 ms on the 786 455-position corpus
+// at a switch cost, 42.00 against 41.59 ms with a matrix.  Written like this the listings are those of two separate kernels.
+template <bool ONE_ROW, bool TRANS>
 __global__ __launch_bounds__(kViterbiThreads) void viterbi_forward_kernel(const float *__restrict__ logits, int N, int C,
                                                                           const int32_t *__restrict__ rows, int M,
                                                                           const int32_t *__restrict__ vid_first,
                                                                           const int32_t *__restrict__ vid_count, float neg_cost,
-                                                                          unsigned long long *__restrict__ stay, uint8_t *__restrict__ amax) {
+                                                                          const float *__restrict__ trans, unsigned long long *__restrict__ stay,
+                                                                          uint8_t *__restrict__ back, uint8_t *__restrict__ amax) {
+  constexpr int P = TRANS ? trans_pitch<ONE_ROW>() : 1;                       // (without the matrix nothing of it exists: no tc, no sb)
   __shared__ float se[2][kViterbiTile][kEventMaxClasses];
+  __shared__ __attribute__((aligned(16))) uint8_t sb[TRANS ? kViterbiTile : 1][kEventMaxClasses];      // b_t of the tile that is walked
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int V = *vid_count;
+  float tc[P], t_stay = 0.f;
+  if constexpr (TRANS) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) tc[p] = (wave == 0 && p < C && lane < C) ? trans[p * C + lane] : -INFINITY;
+    t_stay = (wave == 0 && lane < C) ? trans[lane * C + lane] : -INFINITY;
+  }
   for (int vid = blockIdx.x; vid < V; vid += gridDim.x) {
-    const int vb = vid_first[vid], ve = vid + 1 < V ? vid_first[vid + 1] : M;
-    const int ntiles = (ve - vb + kViterbiTile - 1) / kViterbiTile;
+    const video_span sp = video_of(vid_first, V, vid, M);
+    const int vb = sp.vb, ve = sp.ve, ntiles = sp.ntiles;
     if (wave > 0) viterbi_stage<ONE_ROW>(se[0], vb, ve, logits, N, C, rows, wave, lane);
     __syncthreads();
     float v = 0.f;                                 // in front of position 0 every class scores 0: u_0 = e_0, whose maximum is 0
@@ -342,7 +373,8 @@ __global__ __launch_bounds__(kViterbiThreads) void viterbi_forward_kernel(const 
         unsigned long long my_stay = 0;
         int my_a = 0;
         // kViterbiChunk rows of e are read ahead of the chunk that is walked, so that no LDS latency sits on the chain.  The last
-        // chunk of a video may run past position n - 1 on rows nobody staged: those steps reach no store and v is not used after them.
+        // chunk of a video may run past position n - 1 on rows nobody staged: those steps reach no global store and v is not used
+        // after them.
         float e[kViterbiChunk], e_next[kViterbiChunk];
 #pragma unroll
         for (int i = 0; i < kViterbiChunk; ++i) e[i] = buf[i][lane];
@@ -351,24 +383,57 @@ __global__ __launch_bounds__(kViterbiThreads) void viterbi_forward_kernel(const 
           for (int i = 0; i < kViterbiChunk; ++i) e_next[i] = buf[min(j0 + kViterbiChunk + i, kViterbiTile - 1)][lane];
 #pragma unroll
           for (int i = 0; i < kViterbiChunk; ++i) {
-            const unsigned long long st = __ballot(v >= neg_cost);
-            const float u = e[i] + max_nonpos(v, neg_cost);
-            const float mx = wave_max_nonpos<ONE_ROW>(u);
-            const unsigned long long hit = __ballot(u == mx);
-            v = u - mx;
-            const int a = hit ? min(__ffsll(hit) - 1, C - 1) : 0;             // (no hit: a NaN among the logits)
-            if (lane == j0 + i) {
-              my_stay = st;
-              my_a = a;
+            if constexpr (TRANS) {
+              float best = lane_f32(v, 0) + tc[0];
+              int from = 0;
+#pragma unroll
+              for (int p = 1; p < P; ++p) {
+                const float cand = lane_f32(v, p) + tc[p];
+                if (cand > best) {
+                  best = cand;
+                  from = p;
+                }
+              }
+              if (v + t_stay >= best) from = lane;                            // (the maximum holds this sum: >= is ==)
+              const float w = (i == 0 && j0 == 0 && k == 0) ? 0.f : best;     // a video's first position has no predecessor: u_0 = e_0
+              const float u = e[i] + w;
+              const float mx = wave_max_nonpos<ONE_ROW>(u);
+              const unsigned long long hit = __ballot(u == mx);
+              v = u - mx;
+              const int a = hit ? min(__ffsll(hit) - 1, C - 1) : 0;           // (no hit: a NaN among the inputs)
+              sb[j0 + i][lane] = (uint8_t)from;
+              if (lane == j0 + i) my_a = a;
+            } else {
+              const unsigned long long st = __ballot(v >= neg_cost);
+              const float u = e[i] + max_nonpos(v, neg_cost);
+              const float mx = wave_max_nonpos<ONE_ROW>(u);
+              const unsigned long long hit = __ballot(u == mx);
+              v = u - mx;
+              const int a = hit ? min(__ffsll(hit) - 1, C - 1) : 0;
+              if (lane == j0 + i) {
+                my_stay = st;
+                my_a = a;
+              }
             }
           }
 #pragma unroll
           for (int i = 0; i < kViterbiChunk; ++i) e[i] = e_next[i];
         }
-        if (lane < n) {
-          stay[t0 + lane] = my_stay;
-          amax[t0 + lane] = (uint8_t)my_a;
+        if constexpr (TRANS) {
+          __builtin_amdgcn_wave_barrier();                                    // the rows above are read below by other lanes of this wave
+          if constexpr (ONE_ROW) {
+            if (lane < n) *(uint4 *)(back + (size_t)(t0 + lane) * P) = *(const uint4 *)&sb[lane][0];
+          } else {
+#pragma unroll
+            for (int i = 0; i < P / 16; ++i) {
+              const int f = i * 64 + lane, row = f / (P / 16), part = f % (P / 16);
+              if (row < n) *(uint4 *)(back + (size_t)(t0 + row) * P + part * 16) = *(const uint4 *)&sb[row][part * 16];
+            }
+          }
+        } else {
+          if (lane < n) stay[t0 + lane] = my_stay;
         }
+        if (lane < n) amax[t0 + lane] = (uint8_t)my_a;
       } else if (k + 1 < ntiles) {
         viterbi_stage<ONE_ROW>(se[(k + 1) & 1], t0 + kViterbiTile, ve, logits, N, C, rows, wave, lane);
       }
@@ -385,8 +450,8 @@ __global__ __launch_bounds__(64) void viterbi_backtrack_kernel(const unsigned lo
   const int lane = threadIdx.x;
   const int V = *vid_count;
   for (int vid = blockIdx.x; vid < V; vid += gridDim.x) {
-    const int vb = vid_first[vid], ve = vid + 1 < V ? vid_first[vid + 1] : M;
-    const int ntiles = (ve - vb + kViterbiTile - 1) / kViterbiTile;
+    const video_span sp = video_of(vid_first, V, vid, M);
+    const int vb = sp.vb, ve = sp.ve, ntiles = sp.ntiles;
     auto load = [&](int k, unsigned long long &nx, int &at) {
       const int t = vb + k * kViterbiTile + lane;
       nx = ~0ull;
@@ -421,95 +486,6 @@ __global__ __launch_bounds__(64) void viterbi_backtrack_kernel(const unsigned lo
   }
 }
 
-// ---- the transition-matrix path ----
-
-// bytes of a position's row of back-pointers: one row of lanes up to 16 classes, one lane per class above
-template <bool ONE_ROW>
-__host__ __device__ constexpr int trans_pitch() { return ONE_ROW ? 16 : kEventMaxClasses; }
-
-// The staging and the read-ahead are viterbi_forward_kernel's.  On the chain lane c holds v[c], the column T[:, c] (tc, -inf past C:
-// such a predecessor is never chosen) and T[c, c].  A step forms the candidates v[p] + T[p, c] in ascending p from v[p] as a scalar
-// and keeps the first maximum (strict comparison), then lets staying win a tie; every sum is <= 0 or -inf, so the wave maximum is
-// wave_max_nonpos's.  A NaN compares false everywhere, so every stored index is in [0, C) whatever the floats are.
-template <bool ONE_ROW>
-__global__ __launch_bounds__(kViterbiThreads) void viterbi_trans_forward_kernel(const float *__restrict__ logits, int N, int C,
-                                                                                const int32_t *__restrict__ rows, int M,
-                                                                                const int32_t *__restrict__ vid_first,
-                                                                                const int32_t *__restrict__ vid_count,
-                                                                                const float *__restrict__ trans, uint8_t *__restrict__ back,
-                                                                                uint8_t *__restrict__ amax) {
-  constexpr int P = trans_pitch<ONE_ROW>();
-  __shared__ float se[2][kViterbiTile][kEventMaxClasses];
-  __shared__ __attribute__((aligned(16))) uint8_t sb[kViterbiTile][kEventMaxClasses];      // b_t of the tile that is walked
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int V = *vid_count;
-  float tc[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) tc[p] = (wave == 0 && p < C && lane < C) ? trans[p * C + lane] : -INFINITY;
-  const float t_stay = (wave == 0 && lane < C) ? trans[lane * C + lane] : -INFINITY;
-  for (int vid = blockIdx.x; vid < V; vid += gridDim.x) {
-    const int vb = vid_first[vid], ve = vid + 1 < V ? vid_first[vid + 1] : M;
-    const int ntiles = (ve - vb + kViterbiTile - 1) / kViterbiTile;
-    if (wave > 0) viterbi_stage<ONE_ROW>(se[0], vb, ve, logits, N, C, rows, wave, lane);
-    __syncthreads();
-    float v = 0.f;
-    for (int k = 0; k < ntiles; ++k) {
-      const int t0 = vb + k * kViterbiTile;
-      if (wave == 0) {
-        const int n = min(kViterbiTile, ve - t0);
-        const float(*buf)[kEventMaxClasses] = se[k & 1];
-        int my_a = 0;
-        // (the last chunk of a video may run past position n - 1 on rows nobody staged: those steps reach no global store)
-        float e[kViterbiChunk], e_next[kViterbiChunk];
-#pragma unroll
-        for (int i = 0; i < kViterbiChunk; ++i) e[i] = buf[i][lane];
-        for (int j0 = 0; j0 < n; j0 += kViterbiChunk) {
-#pragma unroll
-          for (int i = 0; i < kViterbiChunk; ++i) e_next[i] = buf[min(j0 + kViterbiChunk + i, kViterbiTile - 1)][lane];
-#pragma unroll
-          for (int i = 0; i < kViterbiChunk; ++i) {
-            float best = lane_f32(v, 0) + tc[0];
-            int from = 0;
-#pragma unroll
-            for (int p = 1; p < P; ++p) {
-              const float cand = lane_f32(v, p) + tc[p];
-              if (cand > best) {
-                best = cand;
-                from = p;
-              }
-            }
-            if (v + t_stay >= best) from = lane;                              // (the maximum holds this sum: >= is ==)
-            const float w = (i == 0 && j0 == 0 && k == 0) ? 0.f : best;       // a video's first position has no predecessor: u_0 = e_0
-            const float u = e[i] + w;
-            const float mx = wave_max_nonpos<ONE_ROW>(u);
-            const unsigned long long hit = __ballot(u == mx);
-            v = u - mx;
-            const int a = hit ? min(__ffsll(hit) - 1, C - 1) : 0;             // (no hit: a NaN among the inputs)
-            sb[j0 + i][lane] = (uint8_t)from;
-            if (lane == j0 + i) my_a = a;
-          }
-#pragma unroll
-          for (int i = 0; i < kViterbiChunk; ++i) e[i] = e_next[i];
-        }
-        __builtin_amdgcn_wave_barrier();                                      // the rows above are read below by other lanes of this wave
-        if constexpr (ONE_ROW) {
-          if (lane < n) *(uint4 *)(back + (size_t)(t0 + lane) * P) = *(const uint4 *)&sb[lane][0];
-        } else {
-#pragma unroll
-          for (int i = 0; i < P / 16; ++i) {
-            const int f = i * 64 + lane, row = f / (P / 16), part = f % (P / 16);
-            if (row < n) *(uint4 *)(back + (size_t)(t0 + row) * P + part * 16) = *(const uint4 *)&sb[row][part * 16];
-          }
-        }
-        if (lane < n) amax[t0 + lane] = (uint8_t)my_a;
-      } else if (k + 1 < ntiles) {
-        viterbi_stage<ONE_ROW>(se[(k + 1) & 1], t0 + kViterbiTile, ve, logits, N, C, rows, wave, lane);
-      }
-      __syncthreads();
-    }
-  }
-}
-
 // One wave per video, tiles back to front.  Slot j of the LDS holds b_{t+1}, t = the tile's first position + j, so that
 // label[t] = slot j [label[t+1]]: one dependent byte read per position.  The rows of the tile in front are loaded before the walk and
 // stored into the LDS after it.  A byte is masked into the row, so that no read leaves the LDS whatever the workspace holds.
@@ -522,8 +498,8 @@ __global__ __launch_bounds__(64) void viterbi_trans_backtrack_kernel(const uint8
   const int lane = threadIdx.x;
   const int V = *vid_count;
   for (int vid = blockIdx.x; vid < V; vid += gridDim.x) {
-    const int vb = vid_first[vid], ve = vid + 1 < V ? vid_first[vid + 1] : M;
-    const int ntiles = (ve - vb + kViterbiTile - 1) / kViterbiTile;
+    const video_span sp = video_of(vid_first, V, vid, M);
+    const int vb = sp.vb, ve = sp.ve, ntiles = sp.ntiles;
     uint4 part[Q];
     auto load = [&](int k) {                                                  // the rows of positions first + 1 .. first + kViterbiTile
       const int t1 = vb + k * kViterbiTile + 1;
@@ -606,6 +582,15 @@ __global__ __launch_bounds__(kEventTile) void event_flag_kernel(const float *__r
 
 }  // namespace
 
+// what either chain keeps between its launches: the tail of its workspace, behind what the path itself stores per position
+struct event_chain {
+  void *ws;
+  size_t bytes;
+  int32_t *vid_first;      //   [max_positions]   the first position of every video
+  int32_t *vid_count;      //   [1]
+  uint8_t *amax;           //   [max_positions]   a_t
+};
+
 struct tn_event_decoder {
   tn_ctx *ctx;
   int max_positions, max_classes, max_tiles;
@@ -615,20 +600,119 @@ struct tn_event_decoder {
   int32_t *counts, *offsets;   // [max_tiles] each
   uint8_t *flags;          //   [max_positions]
   size_t ws_bytes;
-  void *path_ws;           // the switch-cost path's, allocated by the first tn_event_decoder_run_switch:
+  event_chain path;        // the switch-cost path's, allocated by the first tn_event_decoder_run_switch, in front of the chain's:
   unsigned long long *stay;    // [max_positions]   bit c: v_{t-1}[c] >= -cost
-  int32_t *vid_first;      //   [max_positions]   the first position of every video
-  uint8_t *amax;           //   [max_positions]   a_t
-  int32_t *vid_count;      //   [1]
-  size_t path_bytes;
-  void *trans_ws;          // the transition-matrix path's, allocated by the first tn_event_decoder_run_transitions:
+  event_chain trans;       // the transition-matrix path's, allocated by the first tn_event_decoder_run_transitions, in front:
   uint8_t *back;           //   [max_positions][pitch]   b_t, pitch = 16 bytes for max_classes <= 16, else 64
-  float *trans;            //   [max_classes^2]   the call's matrix, (C, C) row-major
-  int32_t *tvid_first;     //   [max_positions]
-  int32_t *tvid_count;     //   [1]
-  uint8_t *tamax;          //   [max_positions]   a_t
-  size_t trans_bytes;
+  float *matrix;           //   [max_classes^2]   the call's matrix, (C, C) row-major
 };
+
+namespace {
+
+struct event_in {
+  const float *logits;
+  int N, C;
+  const int32_t *rows, *start;
+  int M;
+};
+
+struct event_out {
+  int32_t *label;          // the caller's or the handle's
+  float *conf;
+  int32_t *first, *last, *cls;
+  float *score, *peak;
+  int32_t *count;
+};
+
+size_t padded_positions(const tn_event_decoder *d) { return ((size_t)d->max_positions + 3) & ~(size_t)3; }
+
+// The checks the three entries share, in the one order they are made in.  own_null: the entry's own pointer argument is null (the
+// message, checked behind start); own_bad: the entry's own parameter is refused (the message, checked behind C); nullptr: neither.
+int check_run(const char *entry, const tn_event_decoder *d, const event_in &in, const char *own_null, const char *own_bad, const event_out &out) {
+  const std::string fn = std::string(entry) + ": ";
+  TN_REQUIRE(d, fn + "null handle");
+  TN_REQUIRE(in.logits, fn + "logits is null");
+  TN_REQUIRE(in.rows, fn + "rows is null");
+  TN_REQUIRE(in.start, fn + "start is null");
+  TN_REQUIRE(!own_null, fn + own_null);
+  TN_REQUIRE(out.first, fn + "ev_first is null");
+  TN_REQUIRE(out.last, fn + "ev_last is null");
+  TN_REQUIRE(out.cls, fn + "ev_cls is null");
+  TN_REQUIRE(out.score, fn + "ev_score is null");
+  TN_REQUIRE(out.peak, fn + "ev_peak is null");
+  TN_REQUIRE(out.count, fn + "count is null");
+  TN_REQUIRE(in.N >= 1, fn + "N must be >= 1");
+  TN_REQUIRE(in.C >= 1 && in.C <= kEventMaxClasses, fn + "C must be in [1, 64]");
+  TN_REQUIRE(in.C <= d->max_classes, fn + "C exceeds the handle's max_classes");
+  TN_REQUIRE(!own_bad, fn + own_bad);
+  TN_REQUIRE(in.M >= 1, fn + "M must be >= 1");
+  TN_REQUIRE(in.M <= d->max_positions, fn + "M exceeds the handle's max_positions");
+  return TN_OK;
+}
+
+// label_out / conf_out NULL: the handle's own buffers
+void own_frames(const tn_event_decoder *d, event_out &out) {
+  if (!out.label) out.label = d->label;
+  if (!out.conf) out.conf = d->conf;
+}
+
+int event_tiles(int M) { return (M + kEventTile - 1) / kEventTile; }
+
+// the positions of the set flags, in order -> first; their number -> *count
+void list_flags(tn_event_decoder *d, hipStream_t s, int M, int32_t *count, int32_t *first) {
+  const int tiles = event_tiles(M);
+  hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(kEventScanBlock), 0, s, d->counts, tiles, d->offsets, count);
+  hipLaunchKernelGGL(event_scatter_kernel, dim3(tiles), dim3(kEventTile), 0, s, d->flags, M, d->offsets, first);
+}
+
+// the videos' first positions: the set flags of start through the scan and scatter of the runs
+void find_videos(tn_event_decoder *d, hipStream_t s, const event_in &in, const event_chain &c) {
+  hipLaunchKernelGGL(event_flag_kernel<false>, dim3(event_tiles(in.M)), dim3(kEventTile), 0, s, in.logits, in.N, in.C, in.rows, in.start, in.M,
+                     (const int32_t *)nullptr, (float *)nullptr, d->flags, d->counts);
+  list_flags(d, s, in.M, c.vid_count, c.vid_first);
+}
+
+// label, conf and the run-start flags with their tile counts -> the events
+void reduce_events(tn_event_decoder *d, hipStream_t s, int M, const event_out &out) {
+  list_flags(d, s, M, out.count, out.first);
+  const int blocks = std::min((M + 3) / 4, 2048);
+  hipLaunchKernelGGL(event_reduce_kernel, dim3(blocks), dim3(256), 0, s, out.label, out.conf, M, out.count, out.first, out.last, out.cls,
+                     out.score, out.peak);
+}
+
+// a label path -> conf and the events
+void emit_events(tn_event_decoder *d, hipStream_t s, const event_in &in, const event_out &out) {
+  hipLaunchKernelGGL(event_flag_kernel<true>, dim3(event_tiles(in.M)), dim3(kEventTile), 0, s, in.logits, in.N, in.C, in.rows, in.start, in.M,
+                     out.label, out.conf, d->flags, d->counts);
+  reduce_events(d, s, in.M, out);
+}
+
+// A path's workspace, allocated by the first call that needs it: `own` bytes of the path's (a multiple of 4) and then the chain's.
+int chain_workspace(const tn_event_decoder *d, event_chain &c, size_t own, const char *entry, const char *what) {
+  if (c.ws) return TN_OK;
+  const size_t mp = padded_positions(d), bytes = own + mp * (4 + 1) + 4;
+  void *ws = nullptr;
+  if (hipMalloc(&ws, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    tn_set_error(std::string(entry) + ": device allocation of the " + what + " workspace failed (" + std::to_string(bytes) + " bytes)");
+    return TN_ERR_NOMEM;
+  }
+  c.ws = ws;
+  c.bytes = bytes;
+  c.vid_first = (int32_t *)((char *)ws + own);
+  c.vid_count = c.vid_first + mp;
+  c.amax = (uint8_t *)(c.vid_count + 1);
+  return TN_OK;
+}
+
+template <bool ONE_ROW, bool TRANS>
+void launch_forward(const tn_event_decoder *d, hipStream_t s, const event_in &in, const event_chain &c, int chains, float neg_cost) {
+  hipLaunchKernelGGL((viterbi_forward_kernel<ONE_ROW, TRANS>), dim3(chains), dim3(kViterbiThreads), 0, s, in.logits, in.N, in.C, in.rows, in.M,
+                     c.vid_first, c.vid_count, neg_cost, TRANS ? d->matrix : nullptr, TRANS ? nullptr : d->stay, TRANS ? d->back : nullptr,
+                     c.amax);
+}
+
+}  // namespace
 
 extern "C" int tn_event_decoder_create(tn_ctx *ctx, int max_positions, int max_classes, tn_event_decoder **out) {
   TN_REQUIRE(ctx && out, "tn_event_decoder_create: null argument (ctx, out)");
@@ -639,8 +723,8 @@ extern "C" int tn_event_decoder_create(tn_ctx *ctx, int max_positions, int max_c
   d->ctx = ctx;
   d->max_positions = max_positions;
   d->max_classes = max_classes;
-  d->max_tiles = (max_positions + kEventTile - 1) / kEventTile;
-  const size_t mp = ((size_t)max_positions + 3) & ~(size_t)3, mt = d->max_tiles;
+  d->max_tiles = event_tiles(max_positions);
+  const size_t mp = padded_positions(d), mt = d->max_tiles;
   d->ws_bytes = mp * 4 * 2 + mt * 4 * 2 + mp;
   if (hipMalloc(&d->ws, d->ws_bytes) != hipSuccess) {
     delete d;
@@ -661,8 +745,8 @@ extern "C" int tn_event_decoder_destroy(tn_event_decoder *d) {
   TnDeviceGuard tn_dg_(d->ctx->device);
   (void)hipStreamSynchronize(d->ctx->stream);
   (void)hipFree(d->ws);
-  if (d->path_ws) (void)hipFree(d->path_ws);
-  if (d->trans_ws) (void)hipFree(d->trans_ws);
+  if (d->path.ws) (void)hipFree(d->path.ws);
+  if (d->trans.ws) (void)hipFree(d->trans.ws);
   delete d;
   return TN_OK;
 }
@@ -670,39 +754,22 @@ extern "C" int tn_event_decoder_destroy(tn_event_decoder *d) {
 extern "C" int tn_event_decoder_run(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows, const int32_t *start, int M,
                                     int width, int32_t *label_out, float *conf_out, int32_t *ev_first, int32_t *ev_last, int32_t *ev_cls,
                                     float *ev_score, float *ev_peak, int32_t *count, void *stream) {
-  TN_REQUIRE(d, "tn_event_decoder_run: null handle");
-  TN_REQUIRE(logits, "tn_event_decoder_run: logits is null");
-  TN_REQUIRE(rows, "tn_event_decoder_run: rows is null");
-  TN_REQUIRE(start, "tn_event_decoder_run: start is null");
-  TN_REQUIRE(ev_first, "tn_event_decoder_run: ev_first is null");
-  TN_REQUIRE(ev_last, "tn_event_decoder_run: ev_last is null");
-  TN_REQUIRE(ev_cls, "tn_event_decoder_run: ev_cls is null");
-  TN_REQUIRE(ev_score, "tn_event_decoder_run: ev_score is null");
-  TN_REQUIRE(ev_peak, "tn_event_decoder_run: ev_peak is null");
-  TN_REQUIRE(count, "tn_event_decoder_run: count is null");
-  TN_REQUIRE(N >= 1, "tn_event_decoder_run: N must be >= 1");
-  TN_REQUIRE(C >= 1 && C <= 64, "tn_event_decoder_run: C must be in [1, 64]");
-  TN_REQUIRE(C <= d->max_classes, "tn_event_decoder_run: C exceeds the handle's max_classes");
-  TN_REQUIRE(width >= 1 && width <= 63, "tn_event_decoder_run: width must be in [1, 63]");
-  TN_REQUIRE(width % 2 == 1, "tn_event_decoder_run: width must be odd");
-  TN_REQUIRE(M >= 1, "tn_event_decoder_run: M must be >= 1");
-  TN_REQUIRE(M <= d->max_positions, "tn_event_decoder_run: M exceeds the handle's max_positions");
+  const event_in in{logits, N, C, rows, start, M};
+  event_out out{label_out, conf_out, ev_first, ev_last, ev_cls, ev_score, ev_peak, count};
+  const char *bad = !(width >= 1 && width <= 63) ? "width must be in [1, 63]" : width % 2 != 1 ? "width must be odd" : nullptr;
+  if (const int rc = check_run("tn_event_decoder_run", d, in, nullptr, bad, out)) return rc;
   TN_ON_DEVICE(d->ctx->device);
   hipStream_t s = stream ? (hipStream_t)stream : d->ctx->stream;
-  const int h = (width - 1) / 2, tiles = (M + kEventTile - 1) / kEventTile;
-  int32_t *label = label_out ? label_out : d->label;
-  float *conf = conf_out ? conf_out : d->conf;
+  own_frames(d, out);
+  const int h = (width - 1) / 2, tiles = event_tiles(M);
   const size_t lds = event_lds_bytes(C, h);
   if (C % 4 == 0 && ((uintptr_t)logits & 15) == 0)
-    hipLaunchKernelGGL(event_score_kernel<true>, dim3(tiles), dim3(kEventThreads), lds, s, logits, N, C, rows, start, M, h, label, conf,
+    hipLaunchKernelGGL(event_score_kernel<true>, dim3(tiles), dim3(kEventThreads), lds, s, logits, N, C, rows, start, M, h, out.label, out.conf,
                        d->flags, d->counts);
   else
-    hipLaunchKernelGGL(event_score_kernel<false>, dim3(tiles), dim3(kEventThreads), lds, s, logits, N, C, rows, start, M, h, label, conf,
+    hipLaunchKernelGGL(event_score_kernel<false>, dim3(tiles), dim3(kEventThreads), lds, s, logits, N, C, rows, start, M, h, out.label, out.conf,
                        d->flags, d->counts);
-  hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(kEventScanBlock), 0, s, d->counts, tiles, d->offsets, count);
-  hipLaunchKernelGGL(event_scatter_kernel, dim3(tiles), dim3(kEventTile), 0, s, d->flags, M, d->offsets, ev_first);
-  const int blocks = std::min((M + 3) / 4, 2048);
-  hipLaunchKernelGGL(event_reduce_kernel, dim3(blocks), dim3(256), 0, s, label, conf, M, count, ev_first, ev_last, ev_cls, ev_score, ev_peak);
+  reduce_events(d, s, M, out);
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
 }
@@ -717,63 +784,25 @@ extern "C" int tn_dbg_event_decoder_geometry(int *tile, int *scan_block) {
 extern "C" int tn_event_decoder_run_switch(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows, const int32_t *start,
                                            int M, float switch_cost, int32_t *label_out, float *conf_out, int32_t *ev_first, int32_t *ev_last,
                                            int32_t *ev_cls, float *ev_score, float *ev_peak, int32_t *count, void *stream) {
-  TN_REQUIRE(d, "tn_event_decoder_run_switch: null handle");
-  TN_REQUIRE(logits, "tn_event_decoder_run_switch: logits is null");
-  TN_REQUIRE(rows, "tn_event_decoder_run_switch: rows is null");
-  TN_REQUIRE(start, "tn_event_decoder_run_switch: start is null");
-  TN_REQUIRE(ev_first, "tn_event_decoder_run_switch: ev_first is null");
-  TN_REQUIRE(ev_last, "tn_event_decoder_run_switch: ev_last is null");
-  TN_REQUIRE(ev_cls, "tn_event_decoder_run_switch: ev_cls is null");
-  TN_REQUIRE(ev_score, "tn_event_decoder_run_switch: ev_score is null");
-  TN_REQUIRE(ev_peak, "tn_event_decoder_run_switch: ev_peak is null");
-  TN_REQUIRE(count, "tn_event_decoder_run_switch: count is null");
-  TN_REQUIRE(N >= 1, "tn_event_decoder_run_switch: N must be >= 1");
-  TN_REQUIRE(C >= 1 && C <= kEventMaxClasses, "tn_event_decoder_run_switch: C must be in [1, 64]");
-  TN_REQUIRE(C <= d->max_classes, "tn_event_decoder_run_switch: C exceeds the handle's max_classes");
-  TN_REQUIRE(std::isfinite(switch_cost) && switch_cost >= 0.f, "tn_event_decoder_run_switch: switch_cost must be finite and >= 0");
-  TN_REQUIRE(M >= 1, "tn_event_decoder_run_switch: M must be >= 1");
-  TN_REQUIRE(M <= d->max_positions, "tn_event_decoder_run_switch: M exceeds the handle's max_positions");
+  const char *entry = "tn_event_decoder_run_switch";
+  const event_in in{logits, N, C, rows, start, M};
+  event_out out{label_out, conf_out, ev_first, ev_last, ev_cls, ev_score, ev_peak, count};
+  const char *bad = std::isfinite(switch_cost) && switch_cost >= 0.f ? nullptr : "switch_cost must be finite and >= 0";
+  if (const int rc = check_run(entry, d, in, nullptr, bad, out)) return rc;
   TN_ON_DEVICE(d->ctx->device);
-  if (!d->path_ws) {
-    const size_t mp = ((size_t)d->max_positions + 3) & ~(size_t)3;
-    const size_t bytes = mp * (8 + 4 + 1) + 4;
-    void *ws = nullptr;
-    if (hipMalloc(&ws, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      tn_set_error("tn_event_decoder_run_switch: device allocation of the path workspace failed (" + std::to_string(bytes) + " bytes)");
-      return TN_ERR_NOMEM;
-    }
-    d->path_ws = ws;
-    d->path_bytes = bytes;
-    d->stay = (unsigned long long *)ws;
-    d->vid_first = (int32_t *)(d->stay + mp);
-    d->amax = (uint8_t *)(d->vid_first + mp);
-    d->vid_count = (int32_t *)(d->amax + mp);
-  }
+  if (const int rc = chain_workspace(d, d->path, padded_positions(d) * 8, entry, "path")) return rc;
+  d->stay = (unsigned long long *)d->path.ws;
   hipStream_t s = stream ? (hipStream_t)stream : d->ctx->stream;
-  const int tiles = (M + kEventTile - 1) / kEventTile;
-  int32_t *label = label_out ? label_out : d->label;
-  float *conf = conf_out ? conf_out : d->conf;
-  // the videos' first positions: the set flags of start through the scan and scatter of the runs
-  hipLaunchKernelGGL(event_flag_kernel<false>, dim3(tiles), dim3(kEventTile), 0, s, logits, N, C, rows, start, M, (const int32_t *)nullptr,
-                     (float *)nullptr, d->flags, d->counts);
-  hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(kEventScanBlock), 0, s, d->counts, tiles, d->offsets, d->vid_count);
-  hipLaunchKernelGGL(event_scatter_kernel, dim3(tiles), dim3(kEventTile), 0, s, d->flags, M, d->offsets, d->vid_first);
+  own_frames(d, out);
+  find_videos(d, s, in, d->path);
   const int chains = std::min(M, kViterbiMaxGrid);
-  const float neg_cost = -switch_cost;
   if (C <= 16)
-    hipLaunchKernelGGL(viterbi_forward_kernel<true>, dim3(chains), dim3(kViterbiThreads), 0, s, logits, N, C, rows, M, d->vid_first,
-                       d->vid_count, neg_cost, d->stay, d->amax);
+    launch_forward<true, false>(d, s, in, d->path, chains, -switch_cost);
   else
-    hipLaunchKernelGGL(viterbi_forward_kernel<false>, dim3(chains), dim3(kViterbiThreads), 0, s, logits, N, C, rows, M, d->vid_first,
-                       d->vid_count, neg_cost, d->stay, d->amax);
-  hipLaunchKernelGGL(viterbi_backtrack_kernel, dim3(chains), dim3(64), 0, s, d->stay, d->amax, M, d->vid_first, d->vid_count, label);
-  hipLaunchKernelGGL(event_flag_kernel<true>, dim3(tiles), dim3(kEventTile), 0, s, logits, N, C, rows, start, M, label, conf, d->flags,
-                     d->counts);
-  hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(kEventScanBlock), 0, s, d->counts, tiles, d->offsets, count);
-  hipLaunchKernelGGL(event_scatter_kernel, dim3(tiles), dim3(kEventTile), 0, s, d->flags, M, d->offsets, ev_first);
-  const int blocks = std::min((M + 3) / 4, 2048);
-  hipLaunchKernelGGL(event_reduce_kernel, dim3(blocks), dim3(256), 0, s, label, conf, M, count, ev_first, ev_last, ev_cls, ev_score, ev_peak);
+    launch_forward<false, false>(d, s, in, d->path, chains, -switch_cost);
+  hipLaunchKernelGGL(viterbi_backtrack_kernel, dim3(chains), dim3(64), 0, s, d->stay, d->path.amax, M, d->path.vid_first, d->path.vid_count,
+                     out.label);
+  emit_events(d, s, in, out);
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
 }
@@ -788,22 +817,10 @@ extern "C" int tn_event_decoder_run_transitions(tn_event_decoder *d, const float
                                                 const int32_t *start, int M, const float *transitions, int32_t *label_out,
                                                 float *conf_out, int32_t *ev_first, int32_t *ev_last, int32_t *ev_cls, float *ev_score,
                                                 float *ev_peak, int32_t *count, void *stream) {
-  TN_REQUIRE(d, "tn_event_decoder_run_transitions: null handle");
-  TN_REQUIRE(logits, "tn_event_decoder_run_transitions: logits is null");
-  TN_REQUIRE(rows, "tn_event_decoder_run_transitions: rows is null");
-  TN_REQUIRE(start, "tn_event_decoder_run_transitions: start is null");
-  TN_REQUIRE(transitions, "tn_event_decoder_run_transitions: transitions is null");
-  TN_REQUIRE(ev_first, "tn_event_decoder_run_transitions: ev_first is null");
-  TN_REQUIRE(ev_last, "tn_event_decoder_run_transitions: ev_last is null");
-  TN_REQUIRE(ev_cls, "tn_event_decoder_run_transitions: ev_cls is null");
-  TN_REQUIRE(ev_score, "tn_event_decoder_run_transitions: ev_score is null");
-  TN_REQUIRE(ev_peak, "tn_event_decoder_run_transitions: ev_peak is null");
-  TN_REQUIRE(count, "tn_event_decoder_run_transitions: count is null");
-  TN_REQUIRE(N >= 1, "tn_event_decoder_run_transitions: N must be >= 1");
-  TN_REQUIRE(C >= 1 && C <= kEventMaxClasses, "tn_event_decoder_run_transitions: C must be in [1, 64]");
-  TN_REQUIRE(C <= d->max_classes, "tn_event_decoder_run_transitions: C exceeds the handle's max_classes");
-  TN_REQUIRE(M >= 1, "tn_event_decoder_run_transitions: M must be >= 1");
-  TN_REQUIRE(M <= d->max_positions, "tn_event_decoder_run_transitions: M exceeds the handle's max_positions");
+  const char *entry = "tn_event_decoder_run_transitions";
+  const event_in in{logits, N, C, rows, start, M};
+  event_out out{label_out, conf_out, ev_first, ev_last, ev_cls, ev_score, ev_peak, count};
+  if (const int rc = check_run(entry, d, in, transitions ? nullptr : "transitions is null", nullptr, out)) return rc;
   for (int p = 0; p < C; ++p)
     for (int c = 0; c < C; ++c) {
       const float x = transitions[p * C + c];
@@ -816,52 +833,25 @@ extern "C" int tn_event_decoder_run_transitions(tn_event_decoder *d, const float
     }
   TN_ON_DEVICE(d->ctx->device);
   const bool one_row = d->max_classes <= 16;                // (the pitch of the workspace follows the handle, not the call)
-  const size_t pitch = one_row ? trans_pitch<true>() : trans_pitch<false>();
-  if (!d->trans_ws) {
-    const size_t mp = ((size_t)d->max_positions + 3) & ~(size_t)3, mc = d->max_classes;
-    const size_t bytes = mp * (pitch + 4 + 1) + mc * mc * 4 + 4;
-    void *ws = nullptr;
-    if (hipMalloc(&ws, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      tn_set_error("tn_event_decoder_run_transitions: device allocation of the back-pointer workspace failed (" + std::to_string(bytes) +
-                   " bytes)");
-      return TN_ERR_NOMEM;
-    }
-    d->trans_ws = ws;
-    d->trans_bytes = bytes;
-    d->back = (uint8_t *)ws;
-    d->trans = (float *)(d->back + mp * pitch);
-    d->tvid_first = (int32_t *)(d->trans + mc * mc);
-    d->tvid_count = d->tvid_first + mp;
-    d->tamax = (uint8_t *)(d->tvid_count + 1);
-  }
+  const size_t rows_bytes = padded_positions(d) * (one_row ? trans_pitch<true>() : trans_pitch<false>());
+  if (const int rc = chain_workspace(d, d->trans, rows_bytes + (size_t)d->max_classes * d->max_classes * 4, entry, "back-pointer")) return rc;
+  d->back = (uint8_t *)d->trans.ws;
+  d->matrix = (float *)(d->back + rows_bytes);
   hipStream_t s = stream ? (hipStream_t)stream : d->ctx->stream;
-  TN_HIP_CHECK(hipMemcpyAsync(d->trans, transitions, (size_t)C * C * 4, hipMemcpyHostToDevice, s));
-  const int tiles = (M + kEventTile - 1) / kEventTile;
-  int32_t *label = label_out ? label_out : d->label;
-  float *conf = conf_out ? conf_out : d->conf;
-  hipLaunchKernelGGL(event_flag_kernel<false>, dim3(tiles), dim3(kEventTile), 0, s, logits, N, C, rows, start, M, (const int32_t *)nullptr,
-                     (float *)nullptr, d->flags, d->counts);
-  hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(kEventScanBlock), 0, s, d->counts, tiles, d->offsets, d->tvid_count);
-  hipLaunchKernelGGL(event_scatter_kernel, dim3(tiles), dim3(kEventTile), 0, s, d->flags, M, d->offsets, d->tvid_first);
+  TN_HIP_CHECK(hipMemcpyAsync(d->matrix, transitions, (size_t)C * C * 4, hipMemcpyHostToDevice, s));
+  own_frames(d, out);
+  find_videos(d, s, in, d->trans);
   const int chains = std::min(M, kViterbiMaxGrid);
   if (one_row) {
-    hipLaunchKernelGGL(viterbi_trans_forward_kernel<true>, dim3(chains), dim3(kViterbiThreads), 0, s, logits, N, C, rows, M, d->tvid_first,
-                       d->tvid_count, d->trans, d->back, d->tamax);
-    hipLaunchKernelGGL(viterbi_trans_backtrack_kernel<true>, dim3(chains), dim3(64), 0, s, d->back, d->tamax, M, d->tvid_first,
-                       d->tvid_count, label);
+    launch_forward<true, true>(d, s, in, d->trans, chains, 0.f);
+    hipLaunchKernelGGL(viterbi_trans_backtrack_kernel<true>, dim3(chains), dim3(64), 0, s, d->back, d->trans.amax, M, d->trans.vid_first,
+                       d->trans.vid_count, out.label);
   } else {
-    hipLaunchKernelGGL(viterbi_trans_forward_kernel<false>, dim3(chains), dim3(kViterbiThreads), 0, s, logits, N, C, rows, M, d->tvid_first,
-                       d->tvid_count, d->trans, d->back, d->tamax);
-    hipLaunchKernelGGL(viterbi_trans_backtrack_kernel<false>, dim3(chains), dim3(64), 0, s, d->back, d->tamax, M, d->tvid_first,
-                       d->tvid_count, label);
+    launch_forward<false, true>(d, s, in, d->trans, chains, 0.f);
+    hipLaunchKernelGGL(viterbi_trans_backtrack_kernel<false>, dim3(chains), dim3(64), 0, s, d->back, d->trans.amax, M, d->trans.vid_first,
+                       d->trans.vid_count, out.label);
   }
-  hipLaunchKernelGGL(event_flag_kernel<true>, dim3(tiles), dim3(kEventTile), 0, s, logits, N, C, rows, start, M, label, conf, d->flags,
-                     d->counts);
-  hipLaunchKernelGGL(event_scan_kernel, dim3(1), dim3(kEventScanBlock), 0, s, d->counts, tiles, d->offsets, count);
-  hipLaunchKernelGGL(event_scatter_kernel, dim3(tiles), dim3(kEventTile), 0, s, d->flags, M, d->offsets, ev_first);
-  const int blocks = std::min((M + 3) / 4, 2048);
-  hipLaunchKernelGGL(event_reduce_kernel, dim3(blocks), dim3(256), 0, s, label, conf, M, count, ev_first, ev_last, ev_cls, ev_score, ev_peak);
+  emit_events(d, s, in, out);
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
 }
@@ -876,6 +866,6 @@ extern "C" int tn_dbg_event_decoder_transition_geometry(int *tile, int *pitch16,
 
 extern "C" int tn_dbg_event_decoder_workspace_bytes(const tn_event_decoder *d, size_t *bytes) {
   TN_REQUIRE(d && bytes, "tn_dbg_event_decoder_workspace_bytes: null argument (handle, bytes)");
-  *bytes = d->ws_bytes + d->path_bytes + d->trans_bytes;
+  *bytes = d->ws_bytes + d->path.bytes + d->trans.bytes;
   return TN_OK;
 }

@@ -424,19 +424,16 @@ class EventDecoder(_Handle):
         count = torch.zeros(1, dtype=torch.int32, device=dev)
         label = torch.empty(m, dtype=torch.int32, device=dev) if return_frames else None
         conf = torch.empty(m, dtype=torch.float32, device=dev) if return_frames else None
+        # the three entries differ in one argument, between the positions and the outputs
         if transitions is not None:
-            check(self.lib.tn_event_decoder_run_transitions(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start),
-                                                            m, transitions.ctypes.data_as(C.c_void_p), ptr(label), ptr(conf), ptr(ints[0]),
-                                                            ptr(ints[1]), ptr(ints[2]), ptr(flts[0]), ptr(flts[1]), ptr(count), None),
-                  "tn_event_decoder_run_transitions")
-        elif switch_cost is None:
-            check(self.lib.tn_event_decoder_run(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start), m, int(smooth),
-                                                ptr(label), ptr(conf), ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(flts[0]), ptr(flts[1]),
-                                                ptr(count), None), "tn_event_decoder_run")    # (stream NULL: the context's)
+            entry, how = "tn_event_decoder_run_transitions", transitions.ctypes.data_as(C.c_void_p)
+        elif switch_cost is not None:
+            entry, how = "tn_event_decoder_run_switch", switch_cost
         else:
-            check(self.lib.tn_event_decoder_run_switch(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start), m,
-                                                       switch_cost, ptr(label), ptr(conf), ptr(ints[0]), ptr(ints[1]), ptr(ints[2]),
-                                                       ptr(flts[0]), ptr(flts[1]), ptr(count), None), "tn_event_decoder_run_switch")
+            entry, how = "tn_event_decoder_run", int(smooth)
+        check(getattr(self.lib, entry)(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start), m, how, ptr(label),
+                                       ptr(conf), ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(flts[0]), ptr(flts[1]), ptr(count), None),
+              entry)                                                             # (stream NULL: the context's)
         k = int(count.item())
         out = dict(first=ints[0, :k], last=ints[1, :k], cls=ints[2, :k], score=flts[0, :k], peak=flts[1, :k])
         if return_frames:

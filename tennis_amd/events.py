@@ -153,45 +153,47 @@ def viterbi_labels(logits, rows, start, switch_cost=None, dtype=np.float64, tran
     -> ``label (M,)`` int64."""
     if (switch_cost is None) == (transitions is None):
         raise ValueError("viterbi_labels: give exactly one of switch_cost and transitions")
-    if transitions is not None:
-        return _viterbi_labels_transitions(logits, rows, start, transitions, dtype)
     dtype = np.dtype(dtype).type
-    cost = float(switch_cost)
-    if not (np.isfinite(cost) and cost >= 0):
-        raise ValueError(f"viterbi_labels: switch_cost must be finite and >= 0, got {switch_cost}")
-    logits = np.asarray(logits)
-    if logits.ndim != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
-        raise ValueError(f"viterbi_labels: logits must be (N, C), got {logits.shape}")
-    rows = np.clip(np.asarray(rows, np.int64).reshape(-1), 0, logits.shape[0] - 1)
-    begins = np.asarray(start).reshape(-1) != 0
-    if len(rows) != len(begins):
-        raise ValueError(f"viterbi_labels: {len(rows)} rows for {len(begins)} start flags")
-    m = len(rows)
+    if transitions is None:
+        cost = float(switch_cost)
+        if not (np.isfinite(cost) and cost >= 0):
+            raise ValueError(f"viterbi_labels: switch_cost must be finite and >= 0, got {switch_cost}")
+    logits, rows, bounds = _viterbi_positions(logits, rows, start, "viterbi_labels")
+    m, c = len(rows), logits.shape[1]
+    # step: v_{t-1} -> (w_t, what the way back needs of the step);  back: (that, label[t], a_{t-1}) -> label[t-1]
+    if transitions is None:
+        neg = dtype(-cost)
+        kept = np.zeros((m, c), bool)                                            # stay_t
+        step = lambda v: (np.maximum(v, neg), v >= neg)
+        back = lambda stay, lab, a: lab if stay[lab] else a
+    else:
+        trans = check_transitions(transitions, c, "viterbi_labels").astype(dtype)
+        diag, cls = np.diagonal(trans), np.arange(c)
+        kept = np.zeros((m, c), np.int64)                                        # b_t
+
+        def step(v):
+            cand = v[:, None] + trans                                            # [p, c], every sum rounded to dtype
+            w = cand.max(0)
+            return w, np.where(v + diag == w, cls, cand.argmax(0))               # staying wins a tie, else the smallest p
+        back = lambda b, lab, a: b[lab]
     label = np.zeros(m, np.int64)
     if not m:
         return label
     q = logits[rows].astype(dtype)
     e = q - q.max(1, keepdims=True)
-    neg = dtype(-cost)
-    bounds = np.flatnonzero(begins).tolist()
-    if not bounds or bounds[0] != 0:
-        bounds = [0] + bounds
-    bounds.append(m)
-    stay = np.zeros(e.shape, bool)
     amax = np.zeros(m, np.int64)
-    for a, b in zip(bounds[:-1], bounds[1:]):
-        v = e[a]
-        amax[a] = int(np.argmax(v))                                              # (numpy's argmax is the first maximum)
-        for t in range(a + 1, b):
-            stay[t] = v >= neg
-            u = e[t] + np.maximum(v, neg)
+    for first, end in zip(bounds[:-1], bounds[1:]):
+        v = e[first]
+        amax[first] = int(np.argmax(v))                                          # (numpy's argmax is the first maximum)
+        for t in range(first + 1, end):
+            w, kept[t] = step(v)
+            u = e[t] + w
             v = u - u.max()
             amax[t] = int(np.argmax(v))
-        lab = amax[b - 1]
-        label[b - 1] = lab
-        for t in range(b - 1, a, -1):
-            if not stay[t, lab]:
-                lab = amax[t - 1]
+        lab = amax[end - 1]
+        label[end - 1] = lab
+        for t in range(end - 1, first, -1):
+            lab = back(kept[t], lab, amax[t - 1])
             label[t - 1] = lab
     return label
 
@@ -210,38 +212,6 @@ def _viterbi_positions(logits, rows, start, who):
         bounds = [0] + bounds
     bounds.append(len(rows))
     return logits, rows, bounds
-
-
-def _viterbi_labels_transitions(logits, rows, start, transitions, dtype):
-    dtype = np.dtype(dtype).type
-    logits, rows, bounds = _viterbi_positions(logits, rows, start, "viterbi_labels")
-    trans = check_transitions(transitions, logits.shape[1], "viterbi_labels").astype(dtype)
-    m, c = len(rows), logits.shape[1]
-    label = np.zeros(m, np.int64)
-    if not m:
-        return label
-    q = logits[rows].astype(dtype)
-    e = q - q.max(1, keepdims=True)
-    diag = np.diagonal(trans)
-    cls = np.arange(c)
-    back = np.zeros((m, c), np.int64)
-    amax = np.zeros(m, np.int64)
-    for a, b in zip(bounds[:-1], bounds[1:]):
-        v = e[a]
-        amax[a] = int(np.argmax(v))
-        for t in range(a + 1, b):
-            cand = v[:, None] + trans                                            # [p, c], every sum rounded to dtype
-            w = cand.max(0)
-            back[t] = np.where(v + diag == w, cls, cand.argmax(0))               # staying wins a tie, else the smallest p
-            u = e[t] + w
-            v = u - u.max()
-            amax[t] = int(np.argmax(v))
-        lab = amax[b - 1]
-        label[b - 1] = lab
-        for t in range(b - 1, a, -1):
-            lab = back[t, lab]
-            label[t - 1] = lab
-    return label
 
 
 def save_events(file_path, video, first_frame, last_frame, cls, score, peak, first_sample, last_sample, gt_video, gt_first_frame,

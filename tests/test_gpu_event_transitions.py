@@ -1,4 +1,4 @@
-"""-m gpu: the transition-matrix path decoder (csrc/event_runs.hip: viterbi_trans_forward_kernel, viterbi_trans_backtrack_kernel;
+"""-m gpu: the transition-matrix path decoder (csrc/event_runs.hip: viterbi_forward_kernel<ONE_ROW, true>, viterbi_trans_backtrack_kernel;
 tn_event_decoder_run_transitions, engine.EventDecoder.decode(transitions=...)) against its definition in float64
 (events.viterbi_labels(transitions=...), tests/tools/transitions_ref.py).  Shapes are placed from the decoder's own geometry: G
 positions of a video per step of the chain kernels (tn_dbg_event_decoder_transition_geometry); layouts and row modes are those of
@@ -18,6 +18,11 @@ import torch
 
 from tools import events_ref as ER
 from tools import transitions_ref as TR
+from tools.event_paths import Spy as _Spy
+from tools.event_paths import check_events_of_own_frames as _check_events_of_own_frames
+from tools.event_paths import layout as _layout
+from tools.event_paths import rows_of as _rows
+from tools.event_paths import to_numpy as _np
 
 pytestmark = pytest.mark.gpu
 
@@ -45,35 +50,11 @@ def _handles(decs, c):
     return [decs[k] for k in (16, 64) if c <= k]
 
 
-def _np(d):
-    return {k: v.cpu().numpy() for k, v in d.items()}
-
-
 def _decode(dec, logits, rows, start, trans=None, frames=True, **kw):
     if trans is not None:
         kw["transitions"] = trans
     return _np(dec.decode(torch.tensor(np.asarray(logits, np.float32), device="cuda"), np.array(rows), np.array(start),
                           return_frames=frames, **kw))
-
-
-def _layout(m, kind):
-    """video-start flags: 0 lengths 1, 2 and then exactly G; 1 lengths 1, 2, G - 3 and the rest (G + 3 at m = 2 G + 3: two tiles);
-    2 one video over everything (three tiles at m = 2 G + 3)"""
-    start = np.zeros(m, np.int32)
-    for at in {0: (1, 3, 3 + G), 1: (1, 3, G), 2: ()}[kind]:
-        if at < m:
-            start[at] = 1
-    return start
-
-
-def _rows(rng, m, mode):
-    """the identity, a permutation of a larger N, or that with entries outside [0, N) -> (N, rows)"""
-    n = m if mode == 0 else m + 37
-    rows = np.arange(m) if mode == 0 else rng.permutation(n)[:m]
-    if mode == 2:
-        rows = rows.copy()
-        rows[::5] = rng.choice([-3, -1, n, n + 9, 2 ** 31 - 1, -2 ** 31], len(rows[::5]))
-    return n, rows.astype(np.int64)
 
 
 def _matrix(rng, c, kind):
@@ -113,17 +94,6 @@ def _exact_case(m, c, kind, coarse):
     for arr in (logits, rows, start, trans, label, p):
         arr.setflags(write=False)
     return logits, rows, start, trans, label, p, (int(amax_tie.sum()), int(stay_tie.sum()), int(pred_tie.sum()))
-
-
-def _check_events_of_own_frames(got, start):
-    from tennis_amd.events import label_runs
-    first, last, cls = label_runs(got["label"], start)
-    assert np.array_equal(got["first"], first) and np.array_equal(got["last"], last) and np.array_equal(got["cls"], cls)
-    assert got["first"].dtype == np.int32 and got["score"].dtype == np.float32
-    conf64 = got["conf"].astype(np.float64)
-    for a, b, sc, pk in zip(first, last, got["score"], got["peak"]):
-        assert pk == got["conf"][a:b + 1].max()
-        assert abs(float(sc) - conf64[a:b + 1].mean()) <= ER.mean_bound(b - a + 1)
 
 
 def expected_ties(c, kind):
@@ -291,6 +261,35 @@ def test_nothing_changes_without_the_keyword(classes, pitch):
     assert set(quiet) == {"first", "last", "cls", "score", "peak"} and all(np.array_equal(quiet[k], first[k]) for k in quiet)
 
 
+@pytest.mark.parametrize("classes", [16, 64])
+def test_the_paths_interleaved_on_one_handle_give_the_bits_of_a_fresh_handle(classes):
+    """The two chains keep their bookkeeping (the videos' bounds, a_t) in workspaces of their own inside one handle.  ONE handle runs
+    transitions first, then the switch cost, smooth = 9, transitions and the switch cost again, over every shape; each result must be
+    the bits of the same call on a handle that has run nothing else, and the handle grows exactly twice."""
+    from tennis_amd.engine import EventDecoder
+    dec = EventDecoder(MAXPOS, classes)
+    held = [dec.workspace_bytes()]
+    for m in (1, G, G + 1, 2 * G + 3):
+        for c in (k for k in (3, 16, 17, 64) if k <= classes):
+            rng = np.random.default_rng(m * 67 + c)
+            n, rows = _rows(rng, m, (m + c) % 3)
+            start = np.zeros(m, np.int32)
+            start[m // 3 + 1:m // 3 + 2] = 1                                     # two videos from two positions on
+            logits = (rng.normal(0, 1, (n, c)) * 2).astype(np.float32)
+            trans = (-3.0 * rng.random((c, c))).astype(np.float32)
+            calls = {"transitions": dict(transitions=trans), "switch": dict(switch_cost=1.5), "smooth9": dict(smooth=9)}
+            fresh = {k: _decode(EventDecoder(MAXPOS, classes), logits, rows, start, **kw) for k, kw in calls.items()}
+            for k in ("transitions", "switch", "smooth9", "transitions", "switch"):
+                got = _decode(dec, logits, rows, start, **calls[k])
+                held.append(dec.workspace_bytes())
+                assert set(got) == set(fresh[k]) == {"label", "conf", "first", "last", "cls", "score", "peak"}
+                for key in got:
+                    assert got[key].dtype == fresh[k][key].dtype and np.array_equal(got[key], fresh[k][key]), (m, c, k, key)
+            if m >= 2:
+                assert {0, m // 3 + 1} <= set(fresh["smooth9"]["first"].tolist())
+    assert sum(b != a for a, b in zip(held, held[1:])) == 2 and held[0] < held[1] < held[2] == held[-1]
+
+
 def test_a_nan_among_the_logits_leaves_every_label_in_range(decs):
     rng = np.random.default_rng(8)
     m, c = 2 * G + 3, 11
@@ -368,14 +367,3 @@ def test_refusals(decs):
         small.decode(x, np.arange(8), np.zeros(8), transitions=good)
     assert small.workspace_bytes() == created                                    # and nothing was allocated for it
     torch.cuda.synchronize()
-
-
-class _Spy:
-    """the library with every call recorded"""
-
-    def __init__(self, lib, calls):
-        self._lib, self._calls = lib, calls
-
-    def __getattr__(self, name):
-        self._calls.append(name)
-        return getattr(self._lib, name)

@@ -1,4 +1,4 @@
-"""-m gpu: the switch-cost path decoder (csrc/event_runs.hip: viterbi_forward_kernel, viterbi_backtrack_kernel, event_flag_kernel;
+"""-m gpu: the switch-cost path decoder (csrc/event_runs.hip: viterbi_forward_kernel<ONE_ROW, false>, viterbi_backtrack_kernel, event_flag_kernel;
 tn_event_decoder_run_switch, engine.EventDecoder.decode(switch_cost=...)) against its definition in float64
 (events.viterbi_labels, tests/tools/viterbi_ref.py).  Shapes are placed from the decoder's own geometry: G positions of a video per
 step of the chain kernels (tn_dbg_event_decoder_switch_geometry).  A video's tiles are counted from the video's own first position,
@@ -16,6 +16,11 @@ import torch
 
 from tools import events_ref as ER
 from tools import viterbi_ref as VR
+from tools.event_paths import Spy as _Spy
+from tools.event_paths import check_events_of_own_frames as _check_events_of_own_frames
+from tools.event_paths import layout as _layout
+from tools.event_paths import rows_of as _rows
+from tools.event_paths import to_numpy as _np
 
 pytestmark = pytest.mark.gpu
 
@@ -38,34 +43,10 @@ def dec():
     return EventDecoder(MAXPOS, 64)
 
 
-def _np(d):
-    return {k: v.cpu().numpy() for k, v in d.items()}
-
-
 def _decode(dec, logits, rows, start, cost=None, smooth=1, frames=True):
     kw = {} if cost is None else {"switch_cost": cost}
     return _np(dec.decode(torch.tensor(np.asarray(logits, np.float32), device="cuda"), np.array(rows), np.array(start), smooth=smooth,
                           return_frames=frames, **kw))
-
-
-def _layout(m, kind):
-    """video-start flags: 0 lengths 1, 2 and then exactly G; 1 lengths 1, 2, G - 3 and the rest (G + 3 at m = 2 G + 3: two tiles);
-    2 one video over everything (three tiles at m = 2 G + 3)"""
-    start = np.zeros(m, np.int32)
-    for at in {0: (1, 3, 3 + G), 1: (1, 3, G), 2: ()}[kind]:
-        if at < m:
-            start[at] = 1
-    return start
-
-
-def _rows(rng, m, mode):
-    """the identity, a permutation of a larger N, or that with entries outside [0, N) -> (N, rows)"""
-    n = m if mode == 0 else m + 37
-    rows = np.arange(m) if mode == 0 else rng.permutation(n)[:m]
-    if mode == 2:
-        rows = rows.copy()
-        rows[::5] = rng.choice([-3, -1, n, n + 9, 2 ** 31 - 1, -2 ** 31], len(rows[::5]))
-    return n, rows.astype(np.int64)
 
 
 @functools.lru_cache(maxsize=None)
@@ -103,17 +84,6 @@ def _exact_case(m, c, cost, coarse):
     for arr in (logits, rows, start, label, p):
         arr.setflags(write=False)
     return logits, rows, start, label, p, int(amax_tie.sum()), int(stay_tie.sum())
-
-
-def _check_events_of_own_frames(got, start):
-    from tennis_amd.events import label_runs
-    first, last, cls = label_runs(got["label"], start)
-    assert np.array_equal(got["first"], first) and np.array_equal(got["last"], last) and np.array_equal(got["cls"], cls)
-    assert got["first"].dtype == np.int32 and got["score"].dtype == np.float32
-    conf64 = got["conf"].astype(np.float64)
-    for a, b, sc, pk in zip(first, last, got["score"], got["peak"]):
-        assert pk == got["conf"][a:b + 1].max()
-        assert abs(float(sc) - conf64[a:b + 1].mean()) <= ER.mean_bound(b - a + 1)
 
 
 @pytest.mark.parametrize("cost", COSTS)
@@ -334,14 +304,3 @@ def test_refusals(dec):
     finally:
         assert lib.tn_event_decoder_destroy(small) == 0
     torch.cuda.synchronize()
-
-
-class _Spy:
-    """the library with every call recorded"""
-
-    def __init__(self, lib, calls):
-        self._lib, self._calls = lib, calls
-
-    def __getattr__(self, name):
-        self._calls.append(name)
-        return getattr(self._lib, name)
