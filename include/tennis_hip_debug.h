@@ -219,6 +219,50 @@ int tn_dbg_gemm_tn_fp32x3(tn_ctx *ctx, const float *A, int lda, const float *B, 
 int tn_dbg_gemm_nn(tn_ctx *ctx, const float *A, int lda, const float *B, int ldb, float *Cm, int ldc, int M, int N, int K);
 int tn_dbg_bn_train(tn_ctx *ctx, const float *x, int ld, int64_t M, int C, const float *gamma, const float *beta, float *mean, float *var,
                     float *y, const float *dy, float *dgamma, float *dbeta, float *dx, int ldd, int accumulate);
+/* The training steps' operator kernels, each alone (csrc/finetune.hip, csrc/train.hip), through the launchers the steps call, on the
+ * context's stream, synchronous; all operands device fp32 (labels, valid_len, arg: device int32), NHWC.  Each hook refuses with
+ * TN_ERR_INVALID and a message, before anything is launched: null pointers, counts <= 0, a row stride below its column count, and
+ * what is listed with it.  docs/numerics.md, "The training steps' operator kernels, alone", has the bars they are held to.
+ *   ft_im2col7: x (B, H, W, 3) -> col (B H/2 W/2, 147), 7x7 stride 2 pad 3, columns (ky, kx, c).  H, W even.
+ *   ft_im2col3: a (B, H, W, C) -> col (B H W, 9 C), 3x3 pad 1, columns (ky, kx, c); sc / sh (C each, together or both NULL): the source
+ *     goes through relu(a sc[c] + sh[c]), padding stays 0.  ft_col2im3: its adjoint, dcol -> da (B, H, W, C).  Both: C % 4 == 0 and
+ *     every pointer 16-byte aligned.
+ *   ft_maxpool: 3x3 stride 2 pad 1, a (B, H, W, C) -> y (B H/2 W/2 rows of stride ldy) when y is given; dy (rows of stride ldy) and da
+ *     (B, H, W, C) given together: the gradient, to the first maximum of a window in (ky, kx) order.  H, W even.
+ *   ft_avgpool2: 2x2 stride 2; z with y: the forward, dy with dz: the gradient; layouts of ft_maxpool.  H, W even.
+ *   ft_gap: a (B, P, C) with f (B, C): the mean over P; df (B, C) with da (B, P, C): the gradient df / P.
+ *   ft_bn_fold: sc = gamma / sqrt(var + 1e-5), sh = beta - mean sc.  ft_bn_running: running = 0.9 running + 0.1 batch, in place.
+ *   pool_max_arg: x (B, T, F) -> y (B, F), arg (B, F) the first maximum over T; dpooled (B, F) with dseq (B, T, F): then the scatter of
+ *     dpooled to step arg, zeros elsewhere.
+ *   softmax_ce: loss (B) = -log softmax(logits (B, C))[label], dlogits = softmax - onehot.  labels_host: the host copy of labels; a
+ *     label outside [0, C) is refused (the kernel indexes by it unchecked).
+ *   dense_bwd: dwd (C, K) = dlogits^T pooled, dbd (C) = column sums of dlogits (B, C), dpooled (B, K) = dlogits wd.
+ *   colsum: out (cols) = column sums of A (rows, lda).
+ *   sgd_momentum: mom = momentum mom - lr (rescale g + wd w), w += mom.  adam: m, v, w of MXNet's Adam at the 1-based update count
+ *     step, the bias correction folded into the rate.  scale: a device float that multiplies g first (the clipped instantiation), or
+ *     NULL (the plain one).
+ *   stage_frames: y (B, T, frame_floats) = x with zeros in the slots t >= valid_len[b].  frame_floats % 4 == 0, 16-byte aligned.
+ *   transpose: dst (cols, rows) = src (rows, cols)^T. */
+int tn_dbg_ft_im2col7(tn_ctx *ctx, const float *x, int B, int H, int W, float *col);
+int tn_dbg_ft_im2col3(tn_ctx *ctx, const float *a, int B, int H, int W, int C, const float *sc, const float *sh, float *col);
+int tn_dbg_ft_col2im3(tn_ctx *ctx, const float *dcol, int B, int H, int W, int C, float *da);
+int tn_dbg_ft_maxpool(tn_ctx *ctx, const float *a, int B, int H, int W, int C, float *y, int ldy, const float *dy, float *da);
+int tn_dbg_ft_avgpool2(tn_ctx *ctx, const float *z, int B, int H, int W, int C, float *y, int ldy, const float *dy, float *dz);
+int tn_dbg_ft_gap(tn_ctx *ctx, const float *a, int B, int P, int C, float *f, const float *df, float *da);
+int tn_dbg_ft_bn_fold(tn_ctx *ctx, const float *mean, const float *var, const float *gamma, const float *beta, int C, float *sc, float *sh);
+int tn_dbg_ft_bn_running(tn_ctx *ctx, float *rmean, float *rvar, const float *mean, const float *var, int C);
+int tn_dbg_pool_max_arg(tn_ctx *ctx, const float *x, int B, int T, int F, float *y, int32_t *arg, const float *dpooled, float *dseq);
+int tn_dbg_softmax_ce(tn_ctx *ctx, const float *logits, const int32_t *labels, const int32_t *labels_host, int B, int C, float *loss,
+                      float *dlogits);
+int tn_dbg_dense_bwd(tn_ctx *ctx, const float *dlogits, const float *pooled, const float *wd, int B, int C, int K, float *dwd, float *dbd,
+                     float *dpooled);
+int tn_dbg_colsum(tn_ctx *ctx, const float *A, int lda, int rows, int cols, float *out);
+int tn_dbg_sgd_momentum(tn_ctx *ctx, float *w, const float *g, float *mom, int64_t n, float lr, float momentum, float wd, float rescale,
+                        const float *scale);
+int tn_dbg_adam(tn_ctx *ctx, float *w, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float epsilon,
+                int64_t step, const float *scale);
+int tn_dbg_stage_frames(tn_ctx *ctx, const float *x, const int32_t *valid_len, int B, int T, int64_t frame_floats, float *y);
+int tn_dbg_transpose(tn_ctx *ctx, const float *src, int rows, int cols, float *dst);
 /* tn_gnmt_trainer_forward_backward that also leaves d loss / d src in dsrc (batch * steps, input_size; row stride ldd, DEVICE,
  * assigned): the gradient the frame-mode step (tn_gnmt_frames_trainer_*) hands to the backbone.  Rows at or past src_valid_len[b]
  * come out 0. */

@@ -248,6 +248,22 @@ _SIGS = {
     "tn_dbg_linear_fp32x3": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_gemm_tn_fp32x3": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
     "tn_dbg_bn_train": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int]),
+    "tn_dbg_ft_im2col7": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "tn_dbg_ft_im2col3": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "tn_dbg_ft_col2im3": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "tn_dbg_ft_maxpool": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    "tn_dbg_ft_avgpool2": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    "tn_dbg_ft_gap": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "tn_dbg_ft_bn_fold": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P]),
+    "tn_dbg_ft_bn_running": (C.c_int, [_P, _P, _P, _P, _P, C.c_int]),
+    "tn_dbg_pool_max_arg": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "tn_dbg_softmax_ce": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "tn_dbg_dense_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "tn_dbg_colsum": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "tn_dbg_sgd_momentum": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "tn_dbg_adam": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, _P]),
+    "tn_dbg_stage_frames": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, _P]),
+    "tn_dbg_transpose": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "tn_comm_unique_id": (C.c_int, [_P]),
     "tn_comm_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(_P)]),
     "tn_comm_rank": (C.c_int, [_P]),

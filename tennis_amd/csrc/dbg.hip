@@ -848,6 +848,147 @@ extern "C" int tn_dbg_bn_train(tn_ctx *ctx, const float *x, int ld, int64_t M, i
   return TN_OK;
 }
 
+// ---- the training steps' operator kernels, alone (finetune.hip launch_ft_*, train.hip) ----
+// Each hook checks what its kernel cannot take, runs the operator through the launcher the step calls on the context's stream and
+// synchronises.  Nothing is launched after a refusal.
+namespace {
+inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+inline bool fits_int(long n) { return n > 0 && n <= 0x7fffffffL; }
+int dbg_finish(tn_ctx *ctx, int rc) {
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  TN_HIP_CHECK(e);
+  TN_HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+}  // namespace
+
+extern "C" int tn_dbg_ft_im2col7(tn_ctx *ctx, const float *x, int B, int H, int W, float *col) {
+  TN_REQUIRE(ctx && x && col, "tn_dbg_ft_im2col7: null argument");
+  TN_REQUIRE(B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "tn_dbg_ft_im2col7: B, H, W must be positive, H and W even");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_ft_im2col7(x, B, H, W, col, ctx->stream));
+}
+extern "C" int tn_dbg_ft_im2col3(tn_ctx *ctx, const float *a, int B, int H, int W, int C, const float *sc, const float *sh, float *col) {
+  TN_REQUIRE(ctx && a && col && (sc == nullptr) == (sh == nullptr), "tn_dbg_ft_im2col3: null argument (sc and sh go together)");
+  TN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "tn_dbg_ft_im2col3: B, H, W, C must be positive, C a multiple of 4");
+  TN_REQUIRE(al16(a) && al16(col) && al16(sc) && al16(sh), "tn_dbg_ft_im2col3: the buffers must be 16-byte aligned");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_ft_im2col3(a, B, H, W, C, col, sc, sh, ctx->stream));
+}
+extern "C" int tn_dbg_ft_col2im3(tn_ctx *ctx, const float *dcol, int B, int H, int W, int C, float *da) {
+  TN_REQUIRE(ctx && dcol && da, "tn_dbg_ft_col2im3: null argument");
+  TN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "tn_dbg_ft_col2im3: B, H, W, C must be positive, C a multiple of 4");
+  TN_REQUIRE(al16(dcol) && al16(da), "tn_dbg_ft_col2im3: the buffers must be 16-byte aligned");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_ft_col2im3(dcol, B, H, W, C, da, ctx->stream));
+}
+// y non-null: the forward; dy and da non-null (together): the gradient.  At least one of the two.
+extern "C" int tn_dbg_ft_maxpool(tn_ctx *ctx, const float *a, int B, int H, int W, int C, float *y, int ldy, const float *dy, float *da) {
+  TN_REQUIRE(ctx && a && (y || dy) && (dy == nullptr) == (da == nullptr), "tn_dbg_ft_maxpool: null argument (dy and da go together)");
+  TN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0, "tn_dbg_ft_maxpool: B, H, W, C must be positive, H and W even");
+  TN_REQUIRE(ldy >= C, "tn_dbg_ft_maxpool: ldy below C");
+  TN_ON_DEVICE(ctx->device);
+  int rc = y ? launch_ft_maxpool(a, B, H, W, C, y, ldy, ctx->stream) : TN_OK;
+  if (!rc && dy) rc = launch_ft_maxpool_bwd(a, dy, ldy, B, H, W, C, da, ctx->stream);
+  return dbg_finish(ctx, rc);
+}
+// z and y non-null (together): the forward; dy and dz non-null (together): the gradient.  At least one of the two.
+extern "C" int tn_dbg_ft_avgpool2(tn_ctx *ctx, const float *z, int B, int H, int W, int C, float *y, int ldy, const float *dy, float *dz) {
+  TN_REQUIRE(ctx && (z || dy) && (z == nullptr) == (y == nullptr) && (dy == nullptr) == (dz == nullptr),
+             "tn_dbg_ft_avgpool2: null argument (z with y, dy with dz)");
+  TN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0, "tn_dbg_ft_avgpool2: B, H, W, C must be positive, H and W even");
+  TN_REQUIRE(ldy >= C, "tn_dbg_ft_avgpool2: ldy below C");
+  TN_ON_DEVICE(ctx->device);
+  int rc = z ? launch_ft_avgpool2(z, B, H, W, C, y, ldy, ctx->stream) : TN_OK;
+  if (!rc && dy) rc = launch_ft_avgpool2_bwd(dy, ldy, B, H, W, C, dz, ctx->stream);
+  return dbg_finish(ctx, rc);
+}
+// a and f non-null (together): the forward; df and da non-null (together): the gradient.  At least one of the two.
+extern "C" int tn_dbg_ft_gap(tn_ctx *ctx, const float *a, int B, int P, int C, float *f, const float *df, float *da) {
+  TN_REQUIRE(ctx && (a || df) && (a == nullptr) == (f == nullptr) && (df == nullptr) == (da == nullptr),
+             "tn_dbg_ft_gap: null argument (a with f, df with da)");
+  TN_REQUIRE(B > 0 && P > 0 && C > 0 && fits_int((long)B * C), "tn_dbg_ft_gap: B, P, C must be positive, B C below 2^31");
+  TN_ON_DEVICE(ctx->device);
+  int rc = a ? launch_ft_gap(a, B, P, C, f, ctx->stream) : TN_OK;
+  if (!rc && df) rc = launch_ft_gap_bwd(df, B, P, C, da, ctx->stream);
+  return dbg_finish(ctx, rc);
+}
+extern "C" int tn_dbg_ft_bn_fold(tn_ctx *ctx, const float *mean, const float *var, const float *gamma, const float *beta, int C, float *sc,
+                                 float *sh) {
+  TN_REQUIRE(ctx && mean && var && gamma && beta && sc && sh, "tn_dbg_ft_bn_fold: null argument");
+  TN_REQUIRE(C > 0, "tn_dbg_ft_bn_fold: C must be positive");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_ft_bn_fold(mean, var, gamma, beta, C, sc, sh, ctx->stream));
+}
+extern "C" int tn_dbg_ft_bn_running(tn_ctx *ctx, float *rmean, float *rvar, const float *mean, const float *var, int C) {
+  TN_REQUIRE(ctx && rmean && rvar && mean && var, "tn_dbg_ft_bn_running: null argument");
+  TN_REQUIRE(C > 0, "tn_dbg_ft_bn_running: C must be positive");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_ft_bn_running(rmean, rvar, mean, var, C, ctx->stream));
+}
+// Max over time with the first argmax; dpooled and dseq non-null (together): then the scatter of dpooled through arg.
+extern "C" int tn_dbg_pool_max_arg(tn_ctx *ctx, const float *x, int B, int T, int F, float *y, int32_t *arg, const float *dpooled, float *dseq) {
+  TN_REQUIRE(ctx && x && y && arg && (dpooled == nullptr) == (dseq == nullptr), "tn_dbg_pool_max_arg: null argument (dpooled and dseq go together)");
+  TN_REQUIRE(B > 0 && T > 0 && F > 0, "tn_dbg_pool_max_arg: B, T, F must be positive");
+  TN_ON_DEVICE(ctx->device);
+  int rc = launch_pool_max_arg(x, B, T, F, y, arg, ctx->stream);
+  if (!rc && dpooled) rc = launch_scatter_pool_grad(dpooled, arg, B, T, F, dseq, ctx->stream);
+  return dbg_finish(ctx, rc);
+}
+// labels_host: the host copy of the device labels; the kernel indexes a row by its label unchecked, so the hook checks the copy.
+extern "C" int tn_dbg_softmax_ce(tn_ctx *ctx, const float *logits, const int32_t *labels, const int32_t *labels_host, int B, int C, float *loss,
+                                 float *dlogits) {
+  TN_REQUIRE(ctx && logits && labels && labels_host && loss && dlogits, "tn_dbg_softmax_ce: null argument");
+  TN_REQUIRE(B > 0 && C > 0, "tn_dbg_softmax_ce: B and C must be positive");
+  for (int b = 0; b < B; ++b) TN_REQUIRE(labels_host[b] >= 0 && labels_host[b] < C, "tn_dbg_softmax_ce: a label lies outside [0, C)");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_softmax_ce(logits, labels, B, C, loss, dlogits, ctx->stream));
+}
+extern "C" int tn_dbg_dense_bwd(tn_ctx *ctx, const float *dlogits, const float *pooled, const float *wd, int B, int C, int K, float *dwd,
+                                float *dbd, float *dpooled) {
+  TN_REQUIRE(ctx && dlogits && pooled && wd && dwd && dbd && dpooled, "tn_dbg_dense_bwd: null argument");
+  TN_REQUIRE(B > 0 && C > 0 && K > 0 && fits_int((long)C * K) && fits_int((long)B * K) && fits_int((long)B * C),
+             "tn_dbg_dense_bwd: B, C, K must be positive, their pairwise products below 2^31");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_dense_bwd(dlogits, pooled, wd, B, C, K, dwd, dbd, dpooled, ctx->stream));
+}
+extern "C" int tn_dbg_colsum(tn_ctx *ctx, const float *A, int lda, int rows, int cols, float *out) {
+  TN_REQUIRE(ctx && A && out, "tn_dbg_colsum: null argument");
+  TN_REQUIRE(rows > 0 && cols > 0, "tn_dbg_colsum: rows and cols must be positive");
+  TN_REQUIRE(lda >= cols, "tn_dbg_colsum: lda below cols");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_colsum_f32(A, lda, rows, cols, out, ctx->stream));
+}
+// scale: a device float, or NULL for the un-clipped instantiation
+extern "C" int tn_dbg_sgd_momentum(tn_ctx *ctx, float *w, const float *g, float *mom, int64_t n, float lr, float momentum, float wd,
+                                   float rescale, const float *scale) {
+  TN_REQUIRE(ctx && w && g && mom, "tn_dbg_sgd_momentum: null argument");
+  TN_REQUIRE(n > 0, "tn_dbg_sgd_momentum: n must be positive");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_sgd_momentum(w, g, mom, (long)n, lr, momentum, wd, rescale, ctx->stream, scale));
+}
+extern "C" int tn_dbg_adam(tn_ctx *ctx, float *w, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2,
+                           float epsilon, int64_t step, const float *scale) {
+  TN_REQUIRE(ctx && w && g && m && v, "tn_dbg_adam: null argument");
+  TN_REQUIRE(n > 0 && step > 0, "tn_dbg_adam: n and step must be positive");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_adam(w, g, m, v, (long)n, lr, beta1, beta2, epsilon, (long)step, ctx->stream, scale));
+}
+extern "C" int tn_dbg_stage_frames(tn_ctx *ctx, const float *x, const int32_t *valid_len, int B, int T, int64_t frame_floats, float *y) {
+  TN_REQUIRE(ctx && x && valid_len && y, "tn_dbg_stage_frames: null argument");
+  TN_REQUIRE(B > 0 && T > 0 && frame_floats > 0, "tn_dbg_stage_frames: B, T and frame_floats must be positive");
+  TN_REQUIRE(frame_floats % 4 == 0, "tn_dbg_stage_frames: frame_floats must be a multiple of 4");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_stage_frames(x, valid_len, B, T, (long)frame_floats, y, ctx->stream));
+}
+extern "C" int tn_dbg_transpose(tn_ctx *ctx, const float *src, int rows, int cols, float *dst) {
+  TN_REQUIRE(ctx && src && dst, "tn_dbg_transpose: null argument");
+  TN_REQUIRE(rows > 0 && cols > 0, "tn_dbg_transpose: rows and cols must be positive");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_transpose_f32(src, rows, cols, dst, ctx->stream));
+}
+
 // ---- the fp32x3 encoder mode's kernel (dense_fp32x3.hip) and, on the same operands, the fp32 mode's (dense_fp32.hip) ----
 extern "C" int tn_dbg_conv_fp32x3(tn_ctx *ctx, int which, int kind, int tile, int layout, const void *x, int ldx, int K, const float *s,
                                   const float *t, const float *w_host, int N, const float *es, const float *et, float *y, int ldy, int yoff,

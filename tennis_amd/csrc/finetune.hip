@@ -388,6 +388,54 @@ int launch_ft_bn_backward(const float *dy, const float *x, int ld, long M, int C
   TN_HIP_CHECK(hipPeekAtLastError());
   return TN_OK;
 }
+// The step's other operators (train.h), on raw device pointers: what the step calls and what the tn_dbg_ft_* hooks run, so the
+// grid arithmetic is the step's.  Shapes are the kernels' (above); a launch error is peeked at, not cleared.
+#define FT_LAUNCHED() do { TN_HIP_CHECK(hipPeekAtLastError()); return TN_OK; } while (0)
+int launch_ft_im2col7(const float *x, int B, int H, int W, float *col, hipStream_t s) {
+  hipLaunchKernelGGL(ft_im2col7_kernel, dim3(nblk((long)B * (H / 2) * (W / 2) * 49)), dim3(256), 0, s, x, B, H, W, col);
+  FT_LAUNCHED();
+}
+int launch_ft_im2col3(const float *a, int B, int H, int W, int C, float *col, const float *sc, const float *sh, hipStream_t s) {
+  hipLaunchKernelGGL(ft_im2col3_kernel, dim3(nblk((long)B * H * W * 9 * (C / 4))), dim3(256), 0, s, a, B, H, W, C, col, sc, sh);
+  FT_LAUNCHED();
+}
+int launch_ft_col2im3(const float *dcol, int B, int H, int W, int C, float *da, hipStream_t s) {
+  hipLaunchKernelGGL(ft_col2im3_kernel, dim3(nblk((long)B * H * W * (C / 4))), dim3(256), 0, s, dcol, B, H, W, C, da);
+  FT_LAUNCHED();
+}
+int launch_ft_maxpool(const float *a, int B, int H, int W, int C, float *y, int ldy, hipStream_t s) {
+  hipLaunchKernelGGL(ft_maxpool_kernel, dim3(nblk((long)B * (H / 2) * (W / 2) * C)), dim3(256), 0, s, a, B, H, W, C, y, ldy);
+  FT_LAUNCHED();
+}
+int launch_ft_maxpool_bwd(const float *a, const float *dy, int ldy, int B, int H, int W, int C, float *da, hipStream_t s) {
+  hipLaunchKernelGGL(ft_maxpool_bwd_kernel, dim3(nblk((long)B * H * W * C)), dim3(256), 0, s, a, dy, ldy, B, H, W, C, da);
+  FT_LAUNCHED();
+}
+int launch_ft_avgpool2(const float *z, int B, int H, int W, int C, float *y, int ldy, hipStream_t s) {
+  hipLaunchKernelGGL(ft_avgpool2_kernel, dim3(nblk((long)B * (H / 2) * (W / 2) * C)), dim3(256), 0, s, z, B, H, W, C, y, ldy);
+  FT_LAUNCHED();
+}
+int launch_ft_avgpool2_bwd(const float *dy, int ldy, int B, int H, int W, int C, float *dz, hipStream_t s) {
+  hipLaunchKernelGGL(ft_avgpool2_bwd_kernel, dim3(nblk((long)B * H * W * C)), dim3(256), 0, s, dy, ldy, B, H, W, C, dz);
+  FT_LAUNCHED();
+}
+int launch_ft_gap(const float *a, int B, int P, int C, float *f, hipStream_t s) {
+  hipLaunchKernelGGL(ft_gap_kernel, dim3(nblk((long)B * C)), dim3(256), 0, s, a, B, P, C, f);
+  FT_LAUNCHED();
+}
+int launch_ft_gap_bwd(const float *df, int B, int P, int C, float *da, hipStream_t s) {
+  hipLaunchKernelGGL(ft_gap_bwd_kernel, dim3(nblk((long)B * P * C)), dim3(256), 0, s, df, B, P, C, da);
+  FT_LAUNCHED();
+}
+int launch_ft_bn_fold(const float *mean, const float *var, const float *gamma, const float *beta, int C, float *sc, float *sh, hipStream_t s) {
+  hipLaunchKernelGGL(ft_bn_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, s, mean, var, gamma, beta, C, sc, sh);
+  FT_LAUNCHED();
+}
+int launch_ft_bn_running(float *rmean, float *rvar, const float *mean, const float *var, int C, hipStream_t s) {
+  hipLaunchKernelGGL(ft_bn_running_kernel, dim3((C + 255) / 256), dim3(256), 0, s, rmean, rvar, mean, var, C);
+  FT_LAUNCHED();
+}
+#undef FT_LAUNCHED
 static void ft_bn_forward(tn_finetune *f, const FtBn &bn, const float *x, int ld, long M, float *y, hipStream_t s) {
   (void)launch_ft_bn_stats(x, ld, M, bn.C, f->ws, bn.mean, bn.var, s);
   (void)launch_ft_bn_relu(x, ld, M, bn.C, bn.mean, bn.var, f->w + bn.o_gamma, f->w + bn.o_beta, y, s);
@@ -398,8 +446,7 @@ static void ft_stats(tn_finetune *f, const float *x, int ld, long M, int C, floa
 }
 // relu(x * sc + sh) of a BatchNorm whose batch statistics are known (bn.mean / bn.var)
 static void ft_bn_fold(tn_finetune *f, const FtBn &bn, hipStream_t s) {
-  hipLaunchKernelGGL(ft_bn_fold_kernel, dim3((bn.C + 255) / 256), dim3(256), 0, s, (const float *)bn.mean, (const float *)bn.var,
-                     (const float *)(f->w + bn.o_gamma), (const float *)(f->w + bn.o_beta), bn.C, bn.sc, bn.sh);
+  (void)launch_ft_bn_fold(bn.mean, bn.var, f->w + bn.o_gamma, f->w + bn.o_beta, bn.C, bn.sc, bn.sh, s);
 }
 static void ft_bn_recompute(tn_finetune *f, const FtBn &bn, const float *x, int ld, long M, float *y, hipStream_t s) {
   (void)launch_ft_bn_relu(x, ld, M, bn.C, bn.mean, bn.var, f->w + bn.o_gamma, f->w + bn.o_beta, y, s);
@@ -541,11 +588,10 @@ int ft_forward_features(tn_finetune *f, const float *x, int n) {
   float *w = f->w;
   int rc;
 #define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
-  hipLaunchKernelGGL(ft_im2col7_kernel, dim3(nblk(M0 * 49)), dim3(256), 0, s, x, B, H, W, f->col7);
+  TN_TRY(launch_ft_im2col7(x, B, H, W, f->col7, s));
   TN_TRY(ft_linear(f, f->col7, 147, nullptr, nullptr, w + f->o_w0, 147, f->z0, 64, (int)M0, 64, 147, s));
   ft_bn_forward(f, f->bn0, f->z0, 64, M0, f->a0, s);
-  hipLaunchKernelGGL(ft_maxpool_kernel, dim3(nblk((long)B * f->Hb[0] * f->Hb[0] * 64)), dim3(256), 0, s, (const float *)f->a0, B, H / 2, W / 2, 64,
-                     f->X[0], f->Ctot[0]);
+  TN_TRY(launch_ft_maxpool(f->a0, B, H / 2, W / 2, 64, f->X[0], f->Ctot[0], s));
   // Round 4: (a) a channel's batch statistics are computed once, when it is produced (64 / 32 / Cout new columns at a time) - every
   // BatchNorm of the block that normalises it reads them; (b) BatchNorm + ReLU in front of a convolution is never stored: the 1x1
   // GEMMs transform their X operand while staging it (launch_linear_f32_bnrelu), im2col transforms the bottleneck on the way
@@ -558,8 +604,7 @@ int ft_forward_features(tn_finetune *f, const float *x, int n) {
       TN_TRY(ft_linear(f, f->X[b], Ct, L.bn1.sc, L.bn1.sh, w + L.o_w1, L.K, L.z1, 128, (int)M, 128, L.K, s));
       ft_stats(f, L.z1, 128, M, 128, L.bn2.mean, L.bn2.var, s);
       ft_bn_fold(f, L.bn2, s);
-      hipLaunchKernelGGL(ft_im2col3_kernel, dim3(nblk(M * 9 * 32)), dim3(256), 0, s, (const float *)L.z1, B, Hh, Hh, 128, f->col,
-                         (const float *)L.bn2.sc, (const float *)L.bn2.sh);
+      TN_TRY(launch_ft_im2col3(L.z1, B, Hh, Hh, 128, f->col, L.bn2.sc, L.bn2.sh, s));
       TN_TRY(ft_linear(f, f->col, 1152, nullptr, nullptr, w + L.o_w3, 1152, f->X[b] + L.K, Ct, (int)M, 32, 1152, s));
       ft_stats(f, f->X[b] + L.K, Ct, M, 32, f->Xmean[b] + L.K, f->Xvar[b] + L.K, s);
     }
@@ -567,15 +612,14 @@ int ft_forward_features(tn_finetune *f, const float *x, int n) {
       FtTrans &T = f->trans[b];
       ft_bn_fold(f, T.bn, s);
       TN_TRY(ft_linear(f, f->X[b], Ct, T.bn.sc, T.bn.sh, w + T.o_w, T.Cin, T.z, T.Cout, (int)M, T.Cout, T.Cin, s));
-      hipLaunchKernelGGL(ft_avgpool2_kernel, dim3(nblk(M / 4 * T.Cout)), dim3(256), 0, s, (const float *)T.z, B, Hh, Hh, T.Cout, f->X[b + 1],
-                         f->Ctot[b + 1]);
+      TN_TRY(launch_ft_avgpool2(T.z, B, Hh, Hh, T.Cout, f->X[b + 1], f->Ctot[b + 1], s));
       ft_stats(f, f->X[b + 1], f->Ctot[b + 1], M / 4, T.Cout, f->Xmean[b + 1], f->Xvar[b + 1], s);
     }
   }
   const int CF = f->Ctot[3], P3 = f->Hb[3] * f->Hb[3];
   const long M3 = (long)B * P3;
   ft_bn_recompute(f, f->bnF, f->X[3], CF, M3, f->ta, s);
-  hipLaunchKernelGGL(ft_gap_kernel, dim3(nblk((long)B * CF)), dim3(256), 0, s, (const float *)f->ta, B, P3, CF, f->feat);
+  TN_TRY(launch_ft_gap(f->ta, B, P3, CF, f->feat, s));
   return TN_OK;
 }
 
@@ -589,7 +633,7 @@ int ft_backward_features(tn_finetune *f, int n) {
   const int CF = f->Ctot[3], P3 = f->Hb[3] * f->Hb[3];
   const long M3 = (long)B * P3;
   int rc;
-  hipLaunchKernelGGL(ft_gap_bwd_kernel, dim3(nblk(M3 * CF)), dim3(256), 0, s, (const float *)f->dfeat, B, P3, CF, f->tg);
+  TN_TRY(launch_ft_gap_bwd(f->dfeat, B, P3, CF, f->tg, s));
   ft_bn_backward(f, f->bnF, f->tg, f->X[3], CF, M3, f->dX[3], CF, 0, s);
   for (int b = 3; b >= 0; --b) {
     const int Hh = f->Hb[b], Ct = f->Ctot[b];
@@ -598,12 +642,11 @@ int ft_backward_features(tn_finetune *f, int n) {
       FtLayer &L = f->layers[b][l];
       const float *dy = f->dX[b] + L.K;                      // (M, 32) view, row stride Ct
       // 3x3: dW3 = dy^T col ; dcol = dy W3 ; col2im
-      hipLaunchKernelGGL(ft_im2col3_kernel, dim3(nblk(M * 9 * 32)), dim3(256), 0, s, (const float *)L.z1, B, Hh, Hh, 128, f->col,
-                         (const float *)L.bn2.sc, (const float *)L.bn2.sh);
+      TN_TRY(launch_ft_im2col3(L.z1, B, Hh, Hh, 128, f->col, L.bn2.sc, L.bn2.sh, s));
       TN_TRY(ft_gemm_tn(f, dy, Ct, f->col, 1152, nullptr, nullptr, g + L.o_w3, 1152, 32, 1152, (int)M, s));
       TN_TRY(launch_transpose_f32(w + L.o_w3, 32, 1152, f->tw, s));                      // (1152, 32)
       TN_TRY(ft_linear(f, dy, Ct, nullptr, nullptr, f->tw, 32, f->dcol, 1152, (int)M, 1152, 32, s));
-      hipLaunchKernelGGL(ft_col2im3_kernel, dim3(nblk(M * 32)), dim3(256), 0, s, (const float *)f->dcol, B, Hh, Hh, 128, f->tg);
+      TN_TRY(launch_ft_col2im3(f->dcol, B, Hh, Hh, 128, f->tg, s));
       ft_bn_backward(f, L.bn2, f->tg, L.z1, 128, M, f->tb, 128, 0, s);                  // tb = d z1
       // 1x1: dW1 = dz1^T a ; da = dz1 W1
       TN_TRY(ft_gemm_tn(f, f->tb, 128, f->X[b], Ct, L.bn1.sc, L.bn1.sh, g + L.o_w1, L.K, 128, L.K, (int)M, s));
@@ -615,7 +658,7 @@ int ft_backward_features(tn_finetune *f, int n) {
       FtTrans &T = f->trans[b - 1];
       const int Hp = f->Hb[b - 1], Cp = f->Ctot[b - 1];
       const long Mp = (long)B * Hp * Hp;
-      hipLaunchKernelGGL(ft_avgpool2_bwd_kernel, dim3(nblk(Mp * T.Cout)), dim3(256), 0, s, (const float *)f->dX[b], Ct, B, Hp, Hp, T.Cout, f->tb);
+      TN_TRY(launch_ft_avgpool2_bwd(f->dX[b], Ct, B, Hp, Hp, T.Cout, f->tb, s));
       TN_TRY(ft_gemm_tn(f, f->tb, T.Cout, f->X[b - 1], Cp, T.bn.sc, T.bn.sh, g + T.o_w, T.Cin, T.Cout, T.Cin, (int)Mp, s));
       TN_TRY(launch_transpose_f32(w + T.o_w, T.Cout, T.Cin, f->tw, s));                  // (Cin, Cout)
       TN_TRY(ft_linear(f, f->tb, T.Cout, nullptr, nullptr, f->tw, T.Cout, f->tg, T.Cin, (int)Mp, T.Cin, T.Cout, s));
@@ -623,8 +666,7 @@ int ft_backward_features(tn_finetune *f, int n) {
     } else {
       // stem: maxpool -> BN+ReLU -> conv 7x7 (its input gradient is not needed)
       ft_bn_recompute(f, f->bn0, f->z0, 64, M0, f->a0, s);
-      hipLaunchKernelGGL(ft_maxpool_bwd_kernel, dim3(nblk(M0 * 64)), dim3(256), 0, s, (const float *)f->a0, (const float *)f->dX[0], Ct, B, H / 2,
-                         W / 2, 64, f->tg);
+      TN_TRY(launch_ft_maxpool_bwd(f->a0, f->dX[0], Ct, B, H / 2, W / 2, 64, f->tg, s));
       ft_bn_backward(f, f->bn0, f->tg, f->z0, 64, M0, f->tb, 64, 0, s);
       TN_TRY(ft_gemm_tn(f, f->tb, 64, f->col7, 147, nullptr, nullptr, g + f->o_w0, 147, 64, 147, (int)M0, s));
     }
@@ -636,8 +678,7 @@ int ft_backward_features(tn_finetune *f, int n) {
 void ft_update_running(tn_finetune *f) {
   hipStream_t s = f->ctx->stream;
   f->each_bn([&](const FtBn &b) {
-    hipLaunchKernelGGL(ft_bn_running_kernel, dim3((b.C + 255) / 256), dim3(256), 0, s, f->state + b.o_rm, f->state + b.o_rv,
-                       (const float *)b.mean, (const float *)b.var, b.C);
+    (void)launch_ft_bn_running(f->state + b.o_rm, f->state + b.o_rv, b.mean, b.var, b.C, s);
   });
 }
 #undef TN_TRY

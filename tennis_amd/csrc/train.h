@@ -65,6 +65,25 @@ int launch_ft_bn_relu(const float *x, int ld, long M, int C, const float *mean, 
                       float *y, hipStream_t s);
 int launch_ft_bn_backward(const float *dy, const float *x, int ld, long M, int C, const float *mean, const float *var, const float *gamma,
                           const float *beta, float *ws, float *dgamma, float *dbeta, float *dx, int ldd, int accumulate, hipStream_t s);
+// The step's other operators (finetune.hip), NHWC fp32; what the step calls and what the tn_dbg_ft_* hooks run.
+// im2col7: 7x7 stride 2 pad 3 of x (B, H, W, 3), H and W even -> col (B H/2 W/2, 147), columns (ky, kx, c).
+// im2col3: 3x3 pad 1 of a (B, H, W, C), C % 4 == 0, 16-byte aligned -> col (B H W, 9 C), columns (ky, kx, c); sc / sh non-null: the
+// source goes through relu(a sc[c] + sh[c]) first (the padding stays 0).  col2im3: its adjoint, dcol (B H W, 9 C) -> da (B, H, W, C).
+// maxpool: 3x3 stride 2 pad 1 (padding never wins) of a (B, H, W, C), H and W even -> y (B H/2 W/2 rows of stride ldy); its gradient
+// from dy (rows of stride ldy) goes to the first maximum of a window in (ky, kx) order -> da contiguous.  avgpool2: 2x2 stride 2, the
+// same layouts.  gap: mean over the P pixels of a frame, a (B, P, C) -> f (B, C); gradient da = df / P.
+// bn_fold: sc = gamma / sqrt(var + 1e-5), sh = beta - mean sc.  bn_running: running = 0.9 running + 0.1 batch, in place.
+int launch_ft_im2col7(const float *x, int B, int H, int W, float *col, hipStream_t s);
+int launch_ft_im2col3(const float *a, int B, int H, int W, int C, float *col, const float *sc, const float *sh, hipStream_t s);
+int launch_ft_col2im3(const float *dcol, int B, int H, int W, int C, float *da, hipStream_t s);
+int launch_ft_maxpool(const float *a, int B, int H, int W, int C, float *y, int ldy, hipStream_t s);
+int launch_ft_maxpool_bwd(const float *a, const float *dy, int ldy, int B, int H, int W, int C, float *da, hipStream_t s);
+int launch_ft_avgpool2(const float *z, int B, int H, int W, int C, float *y, int ldy, hipStream_t s);
+int launch_ft_avgpool2_bwd(const float *dy, int ldy, int B, int H, int W, int C, float *dz, hipStream_t s);
+int launch_ft_gap(const float *a, int B, int P, int C, float *f, hipStream_t s);
+int launch_ft_gap_bwd(const float *df, int B, int P, int C, float *da, hipStream_t s);
+int launch_ft_bn_fold(const float *mean, const float *var, const float *gamma, const float *beta, int C, float *sc, float *sh, hipStream_t s);
+int launch_ft_bn_running(float *rmean, float *rvar, const float *mean, const float *var, int C, hipStream_t s);
 // The fine-tuning step in parts (finetune.hip), what tn_finetune_forward_backward chains and the CNN-RNN step (api.hip) drives.
 // ft_create: the table of param_table.h::ft_param_table, loaded, uploaded, then the workspaces; dense_prefix NULL builds the backbone
 // alone (no classifier; classes ignored); fit_frames non-NULL: first compare the
