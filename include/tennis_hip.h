@@ -634,6 +634,31 @@ int tn_event_decoder_run_transitions(tn_event_decoder *d, const float *logits, i
                                      int M, const float *transitions, int32_t *label_out, float *conf_out, int32_t *ev_first,
                                      int32_t *ev_last, int32_t *ev_cls, float *ev_score, float *ev_peak, int32_t *count, void *stream);
 
+/* The events of tn_event_decoder_run_transitions, scored with the HMM's own posteriors (forward-backward; docs/kernels.md "Event scores
+ * from posteriors").  Arguments as tn_event_decoder_run_transitions, plus float *posterior: DEVICE memory for (M, C) floats, row-major,
+ * may be NULL.
+ *   label    the Viterbi path under the matrix: the bits of tn_event_decoder_run_transitions.
+ *   gamma    gamma_t[c] = P(label_t = c | every position of the video) under the HMM with emissions e and transitions T, per video in
+ *            the log domain, fp32, LSE(x) = mx + ln sum_i exp(x_i - mx) with mx = max x, the sum in ascending i, a -inf term adding 0:
+ *            forward   a_0 = e_0;  a_t[c] = e_t[c] + LSE_p(ah_{t-1}[p] + T[p][c]);  ah_t = a_t - max_c a_t;
+ *            backward  b_{L-1} = 0;  b_t[p] = LSE_c(T[p][c] + (e_{t+1}[c] + bh_{t+1}[c]));  bh_t = b_t - max_p b_t;
+ *            gamma_t = softmax_c(ah_t + bh_t): maximum subtracted, expf, the sum in ascending c, one division per value.
+ *            The finite diagonal keeps every b_t[p] and at least one a_t[c] finite, so no value is NaN however far the logits
+ *            lie apart and whatever the matrix forbids; a class that cannot be reached has gamma = 0.
+ *   posterior  gamma, if not NULL.
+ *   conf     conf[m] = gamma_m[label[m]], the bits stored in posterior.  score and peak of an event are the mean and maximum of that.
+ *   events   from label, conf and start exactly as tn_event_decoder_run's.
+ * Each direction of each video is one workgroup's sequential walk, both directions of all videos in one launch; no workgroup waits
+ * on another, there are no atomics on floats and nothing depends on grid or tile: a video decoded alone gives the bits of the
+ * whole-corpus call.  The first call allocates the posterior workspace inside the handle, 2 * max_positions * pitch * 4 bytes for ah
+ * and bh, pitch = 16 for max_classes <= 16 and 64 above (and the back-pointer workspace, if no tn_event_decoder_run_transitions has);
+ * TN_ERR_NOMEM with the size in tn_last_error if that fails.  Later calls allocate nothing, and the other run entries never touch it.
+ * TN_ERR_INVALID exactly as tn_event_decoder_run_transitions. */
+int tn_event_decoder_run_posteriors(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows, const int32_t *start,
+                                    int M, const float *transitions, int32_t *label_out, float *conf_out, float *posterior,
+                                    int32_t *ev_first, int32_t *ev_last, int32_t *ev_cls, float *ev_score, float *ev_peak, int32_t *count,
+                                    void *stream);
+
 /* ---- multi-GPU exchange: RCCL over xGMI, one process per GPU (csrc/comm.hip) ------------
  * The path's one exchange step (BASELINE config C4).  The reference splits every DataLoader batch over its ctx list and
  * exchanges the per-frame feature rows through the file system: evaluate.py:278-281,308-321 writes

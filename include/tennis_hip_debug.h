@@ -161,7 +161,8 @@ int tn_dbg_event_decoder_switch_geometry(int *tile);
 int tn_dbg_event_decoder_transition_geometry(int *tile, int *pitch16, int *pitch64);
 
 /* Device bytes the handle holds: what tn_event_decoder_create allocated, plus the path workspace once the first
- * tn_event_decoder_run_switch has allocated it, plus the back-pointer workspace once the first tn_event_decoder_run_transitions has.
+ * tn_event_decoder_run_switch has allocated it, plus the back-pointer workspace once the first tn_event_decoder_run_transitions has,
+ * plus the posterior workspace (2 * max_positions * pitch * 4 bytes) once the first tn_event_decoder_run_posteriors has.
  * Touches no device. */
 int tn_dbg_event_decoder_workspace_bytes(const tn_event_decoder *d, size_t *bytes);
 

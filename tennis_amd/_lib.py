@@ -114,6 +114,7 @@ _SIGS = {
     "tn_event_decoder_run": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tn_event_decoder_run_switch": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tn_event_decoder_run_transitions": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tn_event_decoder_run_posteriors": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tn_event_decoder_destroy": (C.c_int, [_P]),
     "tn_dbg_event_decoder_transition_geometry": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tn_dbg_event_decoder_geometry": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),

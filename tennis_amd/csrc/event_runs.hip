@@ -41,6 +41,18 @@
 //                             one, one dependent LDS byte read per position
 //   event_flag_kernel<true>   one thread per position: conf, the run-start flags and the tile counts - what event_score_kernel
 //                             leaves behind, so that scan, scatter and reduce run unchanged (emit_events)
+// With posteriors (tn_event_decoder_run_posteriors; docs/kernels.md "Event scores from posteriors") label is the path under the
+// matrix as above and conf[m] = gamma_m[label[m]], gamma_t[c] = P(label_t = c | every position of the video) under the same HMM, from
+// the forward-backward recurrences in the log domain, LSE(x) = mx + ln sum_i exp(x_i - mx) in ascending i:
+//   forward   a_0 = e_0;  a_t[c] = e_t[c] + LSE_p(ah_{t-1}[p] + T[p, c]);  ah_t = a_t - max_c a_t
+//   backward  b_{L-1} = 0;  b_t[p] = LSE_c(T[p, c] + (e_{t+1}[c] + bh_{t+1}[c]));  bh_t = b_t - max_p b_t
+//   gamma_t   = softmax_c(ah_t + bh_t)
+// Two more launches between the backtrack and the flags:
+//   hmm_chain_kernel<ONE_ROW>  one workgroup per chain, two chains per video (even workgroups walk forward, odd ones backward, so
+//                             that both directions of a video run at once); wave 0 walks, waves 1..3 stage e as for the Viterbi
+//                             kernel, backward in descending tiles.  Every position leaves ah_t or bh_t as a row of the workspace.
+//   hmm_posterior_kernel<ONE_ROW>  one thread per position: gamma, and conf = gamma[label].  event_flag_kernel<true> runs in front
+//                             of it unchanged (its conf is overwritten), scan, scatter and reduce behind it.
 #include "common.h"
 
 #include <cmath>
@@ -580,6 +592,129 @@ __global__ __launch_bounds__(kEventTile) void event_flag_kernel(const float *__r
   }
 }
 
+// ---- posteriors under the transition matrix: forward-backward in the log domain ----
+
+constexpr float kLog2e = 1.44269504088896340736f, kLn2 = 0.69314718055994530942f;
+
+// One direction of the recurrence over every chain this workgroup takes.  Lane l holds element l of the running vector and tm, its slice
+// of the matrix: the column T[:, l] forward (the sum runs over the predecessors p), the row T[l, :] backward (over the successors c);
+// -inf past C, so that a lane or a term past C is -inf throughout.  x is the vector a step reads through readlane:
+//   forward   x = ah_{t-1};           r[c] = LSE_p(x[p] + T[p, c]);  a_t = e_t + r;  ah_t = a_t - max a_t          -> out[t]
+//   backward  x = e_{t+1} + bh_{t+1};  r[p] = LSE_c(T[p, c] + x[c]);  bh_t = r - max r                              -> out[t]
+// Every candidate is <= 0 or -inf (ah, bh, e, T <= 0), so their maximum is max_nonpos's; r itself may pass 0 (by at most ln C).  A
+// column whose candidates are all -inf gives -inf: its maximum is replaced by 0, the sum is 0 and its logarithm -inf.  The finite
+// diagonal keeps every b_t[p] and at least one a_t[c] finite, so the wave maximum is finite and no value is NaN.
+// The C exponentials of a step are v_exp_f32 on (x - mx) log2(e) and the logarithm v_log_f32 times ln 2: each is within an ulp or two
+// of its argument's rounding, and the terms that count have |x - mx| < 17, where that rounding is below the sum's own.
+// A step past the chain's last position (the read-ahead works in whole chunks) is skipped as a whole: backward the short tile is
+// walked first, so x must not move there.
+template <bool ONE_ROW, bool BACKWARD>
+__device__ __forceinline__ void hmm_chain(float (*se)[kViterbiTile][kEventMaxClasses], const float *__restrict__ logits, int N, int C,
+                                          const int32_t *__restrict__ rows, int M, const int32_t *__restrict__ vid_first, int V,
+                                          const float *__restrict__ trans, float *__restrict__ out) {
+  constexpr int P = trans_pitch<ONE_ROW>();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float tm[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) tm[i] = (wave == 0 && i < C && lane < C) ? trans[BACKWARD ? lane * C + i : i * C + lane] : -INFINITY;
+  const float open = lane < C ? 0.f : -INFINITY;   // r of a chain's first step: no predecessor forward (a_0 = e_0), b_{L-1} = 0 backward
+  for (int ch = blockIdx.x; ch < 2 * V; ch += gridDim.x) {                    // (the grid is even: a workgroup keeps its direction)
+    const video_span sp = video_of(vid_first, V, ch >> 1, M);
+    const int vb = sp.vb, ve = sp.ve, ntiles = sp.ntiles;
+    if (wave > 0) viterbi_stage<ONE_ROW>(se[0], vb + (BACKWARD ? ntiles - 1 : 0) * kViterbiTile, ve, logits, N, C, rows, wave, lane);
+    __syncthreads();
+    float x = open;
+    for (int k = 0; k < ntiles; ++k) {
+      const int t0 = vb + (BACKWARD ? ntiles - 1 - k : k) * kViterbiTile;
+      if (wave == 0) {
+        const int n = min(kViterbiTile, ve - t0);
+        const float(*buf)[kEventMaxClasses] = se[k & 1];
+        // step s of a tile takes its row s forward and n - 1 - s backward; kViterbiChunk rows are read ahead of the chain
+        float e[kViterbiChunk], e_next[kViterbiChunk];
+#pragma unroll
+        for (int i = 0; i < kViterbiChunk; ++i) e[i] = buf[BACKWARD ? max(n - 1 - i, 0) : i][lane];
+        for (int j0 = 0; j0 < n; j0 += kViterbiChunk) {
+#pragma unroll
+          for (int i = 0; i < kViterbiChunk; ++i) {
+            const int s = j0 + kViterbiChunk + i;
+            e_next[i] = buf[BACKWARD ? max(n - 1 - s, 0) : min(s, kViterbiTile - 1)][lane];
+          }
+#pragma unroll
+          for (int i = 0; i < kViterbiChunk; ++i) {
+            const int s = j0 + i;
+            if (s < n) {                                                      // (wave-uniform)
+              float cand[P];
+#pragma unroll
+              for (int p = 0; p < P; ++p) cand[p] = lane_f32(x, p) + tm[p];
+              float mx = cand[0];
+#pragma unroll
+              for (int p = 1; p < P; ++p) mx = max_nonpos(mx, cand[p]);
+              if (mx == -INFINITY) mx = 0.f;
+              float sum = 0.f;
+#pragma unroll
+              for (int p = 0; p < P; ++p) sum += __builtin_amdgcn_exp2f((cand[p] - mx) * kLog2e);
+              const float r = (s == 0 && k == 0) ? open : mx + __builtin_amdgcn_logf(sum) * kLn2;
+              float keep;
+              if constexpr (BACKWARD) {
+                keep = r - wave_max<ONE_ROW>(r);
+                x = e[i] + keep;
+              } else {
+                const float a = e[i] + r;
+                keep = a - wave_max<ONE_ROW>(a);
+                x = keep;
+              }
+              if (lane < P) out[(size_t)(t0 + (BACKWARD ? n - 1 - s : s)) * P + lane] = keep;
+            }
+          }
+#pragma unroll
+          for (int i = 0; i < kViterbiChunk; ++i) e[i] = e_next[i];
+        }
+      } else if (k + 1 < ntiles) {
+        viterbi_stage<ONE_ROW>(se[(k + 1) & 1], BACKWARD ? t0 - kViterbiTile : t0 + kViterbiTile, ve, logits, N, C, rows, wave, lane);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// chain 2 v walks video v forward into fwd, chain 2 v + 1 walks it backward into bwd: rows of trans_pitch floats per position
+template <bool ONE_ROW>
+__global__ __launch_bounds__(kViterbiThreads) void hmm_chain_kernel(const float *__restrict__ logits, int N, int C, const int32_t *__restrict__ rows,
+                                                                    int M, const int32_t *__restrict__ vid_first,
+                                                                    const int32_t *__restrict__ vid_count, const float *__restrict__ trans,
+                                                                    float *__restrict__ fwd, float *__restrict__ bwd) {
+  __shared__ float se[2][kViterbiTile][kEventMaxClasses];
+  const int V = *vid_count;
+  if (blockIdx.x & 1)
+    hmm_chain<ONE_ROW, true>(se, logits, N, C, rows, M, vid_first, V, trans, bwd);
+  else
+    hmm_chain<ONE_ROW, false>(se, logits, N, C, rows, M, vid_first, V, trans, fwd);
+}
+
+// One thread per position: gamma = softmax(ah + bh) - maximum subtracted, accurate expf, the sum in ascending c, one division per
+// value - into posterior (M, C) if there is one, and conf[m] = gamma[label[m]], the value that is stored.
+template <bool ONE_ROW>
+__global__ __launch_bounds__(kEventThreads) void hmm_posterior_kernel(const float *__restrict__ fwd, const float *__restrict__ bwd, int C, int M,
+                                                                      const int32_t *__restrict__ label, float *__restrict__ posterior,
+                                                                      float *__restrict__ conf) {
+  constexpr int P = trans_pitch<ONE_ROW>();
+  const int m = blockIdx.x * kEventThreads + threadIdx.x;
+  if (m >= M) return;
+  const float *a = fwd + (size_t)m * P, *b = bwd + (size_t)m * P;
+  float mx = a[0] + b[0];
+  for (int c = 1; c < C; ++c) mx = fmaxf(mx, a[c] + b[c]);
+  float sum = 0.f;
+  for (int c = 0; c < C; ++c) sum += expf(a[c] + b[c] - mx);
+  const int lab = label[m];
+  float mine = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float g = expf(a[c] + b[c] - mx) / sum;
+    if (posterior) posterior[(size_t)m * C + c] = g;
+    if (c == lab) mine = g;
+  }
+  conf[m] = mine;
+}
+
 }  // namespace
 
 // what either chain keeps between its launches: the tail of its workspace, behind what the path itself stores per position
@@ -605,6 +740,8 @@ struct tn_event_decoder {
   event_chain trans;       // the transition-matrix path's, allocated by the first tn_event_decoder_run_transitions, in front:
   uint8_t *back;           //   [max_positions][pitch]   b_t, pitch = 16 bytes for max_classes <= 16, else 64
   float *matrix;           //   [max_classes^2]   the call's matrix, (C, C) row-major
+  float *post;             // allocated by the first tn_event_decoder_run_posteriors: [2][max_positions][pitch] fp32, ah_t and then bh_t,
+  size_t post_bytes;       //   pitch = 16 floats for max_classes <= 16, else 64
 };
 
 namespace {
@@ -747,6 +884,7 @@ extern "C" int tn_event_decoder_destroy(tn_event_decoder *d) {
   (void)hipFree(d->ws);
   if (d->path.ws) (void)hipFree(d->path.ws);
   if (d->trans.ws) (void)hipFree(d->trans.ws);
+  if (d->post) (void)hipFree(d->post);
   delete d;
   return TN_OK;
 }
@@ -813,13 +951,12 @@ extern "C" int tn_dbg_event_decoder_switch_geometry(int *tile) {
   return TN_OK;
 }
 
-extern "C" int tn_event_decoder_run_transitions(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows,
-                                                const int32_t *start, int M, const float *transitions, int32_t *label_out,
-                                                float *conf_out, int32_t *ev_first, int32_t *ev_last, int32_t *ev_cls, float *ev_score,
-                                                float *ev_peak, int32_t *count, void *stream) {
-  const char *entry = "tn_event_decoder_run_transitions";
-  const event_in in{logits, N, C, rows, start, M};
-  event_out out{label_out, conf_out, ev_first, ev_last, ev_cls, ev_score, ev_peak, count};
+namespace {
+
+// The path under the matrix, and with `posteriors` the marginals under it: conf is then gamma's and `posterior` (may be null) takes gamma.
+int run_matrix(const char *entry, tn_event_decoder *d, const event_in &in, const float *transitions, event_out out, bool posteriors,
+               float *posterior, void *stream) {
+  const int C = in.C, M = in.M;
   if (const int rc = check_run(entry, d, in, transitions ? nullptr : "transitions is null", nullptr, out)) return rc;
   for (int p = 0; p < C; ++p)
     for (int c = 0; c < C; ++c) {
@@ -827,16 +964,28 @@ extern "C" int tn_event_decoder_run_transitions(tn_event_decoder *d, const float
       const char *why = std::isnan(x) ? "is NaN" : x > 0.f ? "is positive: a transition score must be <= 0 or -inf"
                         : (p == c && std::isinf(x)) ? "is not finite: staying must always be possible" : nullptr;
       if (why) {
-        tn_set_error("tn_event_decoder_run_transitions: transitions[" + std::to_string(p) + "][" + std::to_string(c) + "] " + why);
+        tn_set_error(std::string(entry) + ": transitions[" + std::to_string(p) + "][" + std::to_string(c) + "] " + why);
         return TN_ERR_INVALID;
       }
     }
   TN_ON_DEVICE(d->ctx->device);
   const bool one_row = d->max_classes <= 16;                // (the pitch of the workspace follows the handle, not the call)
-  const size_t rows_bytes = padded_positions(d) * (one_row ? trans_pitch<true>() : trans_pitch<false>());
+  const size_t pitch = one_row ? trans_pitch<true>() : trans_pitch<false>(), rows_bytes = padded_positions(d) * pitch;
   if (const int rc = chain_workspace(d, d->trans, rows_bytes + (size_t)d->max_classes * d->max_classes * 4, entry, "back-pointer")) return rc;
   d->back = (uint8_t *)d->trans.ws;
   d->matrix = (float *)(d->back + rows_bytes);
+  const size_t post_half = (size_t)d->max_positions * pitch;                 // floats of ah, and of bh behind it
+  if (posteriors && !d->post) {
+    const size_t bytes = 2 * post_half * 4;
+    void *ws = nullptr;
+    if (hipMalloc(&ws, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      tn_set_error(std::string(entry) + ": device allocation of the posterior workspace failed (" + std::to_string(bytes) + " bytes)");
+      return TN_ERR_NOMEM;
+    }
+    d->post = (float *)ws;
+    d->post_bytes = bytes;
+  }
   hipStream_t s = stream ? (hipStream_t)stream : d->ctx->stream;
   TN_HIP_CHECK(hipMemcpyAsync(d->matrix, transitions, (size_t)C * C * 4, hipMemcpyHostToDevice, s));
   own_frames(d, out);
@@ -851,9 +1000,45 @@ extern "C" int tn_event_decoder_run_transitions(tn_event_decoder *d, const float
     hipLaunchKernelGGL(viterbi_trans_backtrack_kernel<false>, dim3(chains), dim3(64), 0, s, d->back, d->trans.amax, M, d->trans.vid_first,
                        d->trans.vid_count, out.label);
   }
-  emit_events(d, s, in, out);
+  if (!posteriors) {
+    emit_events(d, s, in, out);
+  } else {
+    static_assert(kViterbiMaxGrid % 2 == 0, "a workgroup of the chain kernel keeps its direction");
+    const int both = (int)std::min<long long>(2ll * M, kViterbiMaxGrid), blocks = (M + kEventThreads - 1) / kEventThreads;
+    float *fwd = d->post, *bwd = d->post + post_half;
+    hipLaunchKernelGGL(event_flag_kernel<true>, dim3(event_tiles(M)), dim3(kEventTile), 0, s, in.logits, in.N, C, in.rows, in.start, M,
+                       out.label, out.conf, d->flags, d->counts);
+    if (one_row) {
+      hipLaunchKernelGGL(hmm_chain_kernel<true>, dim3(both), dim3(kViterbiThreads), 0, s, in.logits, in.N, C, in.rows, M, d->trans.vid_first,
+                         d->trans.vid_count, d->matrix, fwd, bwd);
+      hipLaunchKernelGGL(hmm_posterior_kernel<true>, dim3(blocks), dim3(kEventThreads), 0, s, fwd, bwd, C, M, out.label, posterior, out.conf);
+    } else {
+      hipLaunchKernelGGL(hmm_chain_kernel<false>, dim3(both), dim3(kViterbiThreads), 0, s, in.logits, in.N, C, in.rows, M, d->trans.vid_first,
+                         d->trans.vid_count, d->matrix, fwd, bwd);
+      hipLaunchKernelGGL(hmm_posterior_kernel<false>, dim3(blocks), dim3(kEventThreads), 0, s, fwd, bwd, C, M, out.label, posterior, out.conf);
+    }
+    reduce_events(d, s, M, out);
+  }
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
+}
+
+}  // namespace
+
+extern "C" int tn_event_decoder_run_transitions(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows,
+                                                const int32_t *start, int M, const float *transitions, int32_t *label_out,
+                                                float *conf_out, int32_t *ev_first, int32_t *ev_last, int32_t *ev_cls, float *ev_score,
+                                                float *ev_peak, int32_t *count, void *stream) {
+  return run_matrix("tn_event_decoder_run_transitions", d, {logits, N, C, rows, start, M}, transitions,
+                    {label_out, conf_out, ev_first, ev_last, ev_cls, ev_score, ev_peak, count}, false, nullptr, stream);
+}
+
+extern "C" int tn_event_decoder_run_posteriors(tn_event_decoder *d, const float *logits, int N, int C, const int32_t *rows,
+                                               const int32_t *start, int M, const float *transitions, int32_t *label_out, float *conf_out,
+                                               float *posterior, int32_t *ev_first, int32_t *ev_last, int32_t *ev_cls, float *ev_score,
+                                               float *ev_peak, int32_t *count, void *stream) {
+  return run_matrix("tn_event_decoder_run_posteriors", d, {logits, N, C, rows, start, M}, transitions,
+                    {label_out, conf_out, ev_first, ev_last, ev_cls, ev_score, ev_peak, count}, true, posterior, stream);
 }
 
 extern "C" int tn_dbg_event_decoder_transition_geometry(int *tile, int *pitch16, int *pitch64) {
@@ -866,6 +1051,6 @@ extern "C" int tn_dbg_event_decoder_transition_geometry(int *tile, int *pitch16,
 
 extern "C" int tn_dbg_event_decoder_workspace_bytes(const tn_event_decoder *d, size_t *bytes) {
   TN_REQUIRE(d && bytes, "tn_dbg_event_decoder_workspace_bytes: null argument (handle, bytes)");
-  *bytes = d->ws_bytes + d->path.bytes + d->trans.bytes;
+  *bytes = d->ws_bytes + d->path.bytes + d->trans.bytes + d->post_bytes;
   return TN_OK;
 }

@@ -376,14 +376,14 @@ class EventDecoder(_Handle):
         self.handle = h
 
     def workspace_bytes(self) -> int:
-        """``tn_dbg_event_decoder_workspace_bytes``: device bytes the handle holds (the path workspace of ``switch_cost`` and the back-pointer
-        workspace of ``transitions`` are each allocated by the first call that gives one)."""
+        """``tn_dbg_event_decoder_workspace_bytes``: device bytes the handle holds (the path workspace of ``switch_cost``, the back-pointer
+        workspace of ``transitions`` and the workspace of ``posteriors`` are each allocated by the first call that gives one)."""
         n = C.c_size_t()
         check(self.lib.tn_dbg_event_decoder_workspace_bytes(self.handle, C.byref(n)), "tn_dbg_event_decoder_workspace_bytes")
         return n.value
 
     def decode(self, logits: torch.Tensor, rows, start, smooth: int = 1, return_frames: bool = False, switch_cost: float | None = None,
-               transitions=None):
+               transitions=None, posteriors: bool = False, return_posteriors: bool = False):
         """``logits`` (N, C) fp32 on the GPU; ``rows`` (M,) the logit row of every position of the time-ordered list (clamped into
         ``[0, N)``), ``start`` (M,) non-zero where a video begins, ``smooth`` the odd window width in [1, 63].  Returns a dict of
         tensors on the GPU, one entry per event in order of ``first``: ``first``, ``last`` (positions, inclusive), ``cls`` (int32),
@@ -395,7 +395,18 @@ class EventDecoder(_Handle):
         ``transitions`` (a numpy array or CPU tensor (C, C), ``[from, to]``, every entry <= 0 or -inf, the diagonal finite; not together
         with ``smooth`` > 1 or ``switch_cost``): the labels are the path that maximises the summed scores plus ``transitions[a, b]`` for
         every position labelled ``b`` that follows one labelled ``a`` inside a video (``tn_event_decoder_run_transitions``), ``conf`` as
-        with ``switch_cost``; None: the call is what it was."""
+        with ``switch_cost``; None: the call is what it was.
+        ``posteriors`` (with ``transitions`` or ``switch_cost``, which then stands for the matrix ``-switch_cost (1 - I)``; ``smooth``
+        1): the labels stay the path's, and ``conf`` - so ``score`` and ``peak`` - is the posterior probability of the label given
+        every position of its video under the same HMM (forward-backward, ``tn_event_decoder_run_posteriors``; on the host
+        ``events.hmm_posteriors``).  ``return_posteriors`` implies it and adds ``posterior`` (M, C) float32.  False: the call is what
+        it was."""
+        posteriors = bool(posteriors or return_posteriors)
+        if posteriors:                                                          # refused before anything is launched
+            if int(smooth) != 1:
+                raise ValueError(f"EventDecoder.decode: posteriors score a path of the unsmoothed scores, not together with smooth={smooth}")
+            if transitions is None and switch_cost is None:
+                raise ValueError("EventDecoder.decode: posteriors are those of the path's HMM, give transitions or switch_cost")
         if transitions is not None:                                             # refused before anything is launched
             if int(smooth) != 1:
                 raise ValueError(f"EventDecoder.decode: transitions decodes the unsmoothed scores, not together with smooth={smooth}")
@@ -413,6 +424,9 @@ class EventDecoder(_Handle):
             switch_cost = float(switch_cost)
             if not (np.isfinite(switch_cost) and switch_cost >= 0):
                 raise ValueError(f"EventDecoder.decode: switch_cost must be finite and >= 0, got {switch_cost}")
+            if posteriors and transitions is None:
+                c = int(logits.shape[-1])
+                transitions = np.ascontiguousarray(-np.float32(switch_cost) * (1 - np.eye(c, dtype=np.float32)))
         _on_ctx_device(self.ctx, logits, "EventDecoder.decode")
         if logits.dim() != 2 or logits.dtype != torch.float32:
             raise ValueError(f"EventDecoder.decode: logits must be (N, C) float32, got {tuple(logits.shape)} {logits.dtype}")
@@ -424,20 +438,26 @@ class EventDecoder(_Handle):
         count = torch.zeros(1, dtype=torch.int32, device=dev)
         label = torch.empty(m, dtype=torch.int32, device=dev) if return_frames else None
         conf = torch.empty(m, dtype=torch.float32, device=dev) if return_frames else None
-        # the three entries differ in one argument, between the positions and the outputs
-        if transitions is not None:
+        post = torch.empty((m, logits.shape[1]), dtype=torch.float32, device=dev) if return_posteriors else None
+        # the entries differ in one argument, between the positions and the outputs (and the posteriors' in one output more)
+        more = ()
+        if posteriors:
+            entry, how, more = "tn_event_decoder_run_posteriors", transitions.ctypes.data_as(C.c_void_p), (ptr(post),)
+        elif transitions is not None:
             entry, how = "tn_event_decoder_run_transitions", transitions.ctypes.data_as(C.c_void_p)
         elif switch_cost is not None:
             entry, how = "tn_event_decoder_run_switch", switch_cost
         else:
             entry, how = "tn_event_decoder_run", int(smooth)
         check(getattr(self.lib, entry)(self.handle, ptr(logits), logits.shape[0], logits.shape[1], ptr(rows), ptr(start), m, how, ptr(label),
-                                       ptr(conf), ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(flts[0]), ptr(flts[1]), ptr(count), None),
+                                       ptr(conf), *more, ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(flts[0]), ptr(flts[1]), ptr(count), None),
               entry)                                                             # (stream NULL: the context's)
         k = int(count.item())
         out = dict(first=ints[0, :k], last=ints[1, :k], cls=ints[2, :k], score=flts[0, :k], peak=flts[1, :k])
         if return_frames:
             out.update(label=label, conf=conf)
+        if return_posteriors:
+            out["posterior"] = post
         return out
 
 

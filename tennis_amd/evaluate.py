@@ -736,6 +736,11 @@ def build_parser():
     p.add_argument("--event_transition_scale", type=float, default=None,
                    help="with --event_transitions train: the factor on the log probabilities, i.e. how much the grammar weighs "
                         "against the per-frame scores (> 0; default 1)")
+    p.add_argument("--event_posteriors", action="store_true",
+                   help="with --save_events and --event_transitions or --event_switch_cost: score every event with the posterior "
+                        "probability of its class under the same model (forward-backward on the GPU) - per frame the probability of "
+                        "the path's label given ALL frames of the video, its mean and maximum over the event - in place of the "
+                        "frame's own softmax probability.  The events themselves do not change")
     return p
 
 
@@ -929,6 +934,8 @@ def _main_rank(flags, rank, world, dev):
             print("Event transitions (%d x %d) from %s: smallest diagonal entry %.4g, largest off-diagonal entry %.4g" %
                   (matrix.shape[0], matrix.shape[1], source, np.diagonal(matrix).min(), off.max() if off.size else float("nan")))
             path["transitions"] = matrix
+        if getattr(flags, "event_posteriors", False):
+            path["posteriors"] = True
         ev_cols, ev_metric = decode_split(test_set, torch.cat(kept["logits"]), kept["order"], smooth=getattr(flags, "event_smooth", None) or 1,
                                           **path)
         events_file = os.path.join(flags.exp_root, flags.model_id, flags.split + "_events.npz")

@@ -24,6 +24,7 @@ def check_save_events(flags, world=1):
     trans = getattr(flags, "event_transitions", None)
     prior = getattr(flags, "event_transition_prior", None)
     scale = getattr(flags, "event_transition_scale", None)
+    post = getattr(flags, "event_posteriors", False)
     if trans is None:
         for name, value in (("prior", prior), ("scale", scale)):
             if value is not None:
@@ -36,7 +37,12 @@ def check_save_events(flags, world=1):
             raise SystemExit("--event_switch_cost %s sets the label-switch penalty of --save_events: give --save_events too" % cost)
         if trans is not None:
             raise SystemExit("--event_transitions %s sets the class-transition scores of --save_events: give --save_events too" % trans)
+        if post:
+            raise SystemExit("--event_posteriors sets how the events of --save_events are scored: give --save_events too")
         return
+    if post and trans is None and cost is None:
+        raise SystemExit("--event_posteriors scores events with the posteriors of the path's model: give --event_transitions or "
+                         "--event_switch_cost too")
     if trans is not None:
         if cost is not None:
             raise SystemExit("--event_transitions is a matrix of switch costs: not together with --event_switch_cost %s" % cost)
@@ -198,6 +204,47 @@ def viterbi_labels(logits, rows, start, switch_cost=None, dtype=np.float64, tran
     return label
 
 
+def hmm_posteriors(logits, rows, start, transitions, dtype=np.float64):
+    """The posterior marginals behind ``EventDecoder.decode(..., transitions=..., posteriors=True)`` on the host, in ``dtype`` arithmetic
+    (docs/kernels.md "Event scores from posteriors"): ``gamma[t, c] = P(label_t = c | every position of the video)`` under the HMM with
+    emissions ``e_t = q_t - max(q_t)``, ``q_t = logits[clip(rows[t], 0, N - 1)]``, and transition scores ``T`` (``check_transitions``),
+    per video, in the log domain.  ``LSE(x) = mx + ln(sum_i exp(x_i - mx))``, ``mx = max(x)``, the sum in ascending ``i``, a ``-inf`` term
+    adding 0 and all ``-inf`` giving ``-inf``.  Forward ``a_0 = e_0``, ``a_t[c] = e_t[c] + LSE_p(ah_{t-1}[p] + T[p, c])``, ``ah_t = a_t -
+    max(a_t)``; backward ``b_{L-1} = 0``, ``b_t[p] = LSE_c(T[p, c] + (e_{t+1}[c] + bh_{t+1}[c]))``, ``bh_t = b_t - max(b_t)``;
+    ``gamma_t = softmax(ah_t + bh_t)``: maximum subtracted, ``exp``, the sum in ascending ``c``, one division per value.  The finite
+    diagonal keeps every ``b_t[p]`` and at least one ``a_t[c]`` finite, so nothing is clamped.  A Python loop over the positions.
+    -> ``gamma (M, C)`` of ``dtype``."""
+    dtype = np.dtype(dtype).type
+    logits, rows, bounds = _viterbi_positions(logits, rows, start, "hmm_posteriors")
+    m, c = len(rows), logits.shape[1]
+    trans = check_transitions(transitions, c, "hmm_posteriors").astype(dtype)
+    gamma = np.zeros((m, c), dtype)
+    if not m:
+        return gamma
+    zero = dtype(0)
+
+    def lse(x):                                                                  # over axis 0, whose slices numpy adds in ascending order
+        mx = x.max(0)
+        mx = np.where(np.isneginf(mx), zero, mx)
+        return mx + np.log(np.exp(x - mx).sum(0))
+    q = logits[rows].astype(dtype)
+    e = q - q.max(1, keepdims=True)
+    trans_t = np.ascontiguousarray(trans.T)                                      # [c, p]: the backward sum runs over axis 0 as well
+    ah, bh = np.zeros((m, c), dtype), np.zeros((m, c), dtype)
+    with np.errstate(divide="ignore"):                                           # (ln 0 = -inf is the definition's)
+        for first, end in zip(bounds[:-1], bounds[1:]):
+            ah[first] = e[first]                                                 # (its maximum is 0)
+            for t in range(first + 1, end):
+                a = e[t] + lse(ah[t - 1][:, None] + trans)
+                ah[t] = a - a.max()
+            for t in range(end - 2, first - 1, -1):
+                b = lse(trans_t + (e[t + 1] + bh[t + 1])[:, None])
+                bh[t] = b - b.max()
+    g = np.ascontiguousarray((ah + bh).T)                                        # (C, M): sums over axis 0 run in ascending c
+    x = np.exp(g - g.max(0))
+    return np.ascontiguousarray((x / x.sum(0)).T)
+
+
 def _viterbi_positions(logits, rows, start, who):
     """the argument checks of ``viterbi_labels`` -> ``(logits (N, C), rows (M,) clipped into [0, N), the videos' bounds [0, ..., M])``"""
     logits = np.asarray(logits)
@@ -215,7 +262,7 @@ def _viterbi_positions(logits, rows, start, who):
 
 
 def save_events(file_path, video, first_frame, last_frame, cls, score, peak, first_sample, last_sample, gt_video, gt_first_frame,
-                gt_last_frame, gt_cls, smooth, tiou, precision, recall, f1, switch_cost=None, transitions=None):
+                gt_last_frame, gt_cls, smooth, tiou, precision, recall, f1, switch_cost=None, transitions=None, posteriors=None):
     """One ``.npz`` of flat arrays (``np.load(..., allow_pickle=False)`` reads it).  Per predicted event ``video`` (unicode),
     ``first_frame`` / ``last_frame`` (frame numbers, inclusive), ``cls``, ``score`` the mean and ``peak`` the maximum of the smoothed
     score of ``cls``, ``first_sample`` / ``last_sample`` (dataset indices of the two end frames); per ground-truth event ``gt_video``,
@@ -223,7 +270,9 @@ def save_events(file_path, video, first_frame, last_frame, cls, score, peak, fir
     ``recall``, ``f1`` (T, classes) of ``metrics.events.EventPRF1``.  A run of the background class is an event too, and smoothing
     moves boundaries by up to (smooth - 1) / 2 frames.  ``switch_cost`` (None: the file has no such column): the label-switch penalty the
     events were decoded with, a float64 scalar; ``score`` and ``peak`` are then of the unsmoothed probability.  ``transitions`` (None:
-    the file has no such column): the (classes, classes) float32 transition scores the events were decoded with, ``[from, to]``."""
+    the file has no such column): the (classes, classes) float32 transition scores the events were decoded with, ``[from, to]``.
+    ``posteriors`` (None: the file has no such column; needs ``switch_cost`` or ``transitions``): a bool scalar, true where ``score`` and
+    ``peak`` are of the posterior probability of ``cls`` under the path's HMM (``hmm_posteriors``)."""
     i64 = lambda a: np.asarray(a, np.int64).reshape(-1)
     f32 = lambda a: np.asarray(a, np.float32).reshape(-1)
     txt = lambda a: np.asarray(list(a), dtype=np.str_).reshape(-1)
@@ -246,6 +295,10 @@ def save_events(file_path, video, first_frame, last_frame, cls, score, peak, fir
         cols["switch_cost"] = np.asarray(float(switch_cost), np.float64)
     if transitions is not None:
         cols["transitions"] = check_transitions(transitions, cols["f1"].shape[1], "save_events")
+    if posteriors is not None:
+        if switch_cost is None and transitions is None:
+            raise ValueError("save_events: posteriors are those of a path's HMM, give switch_cost or transitions")
+        cols["posteriors"] = np.asarray(bool(posteriors), np.bool_)
     os.makedirs(os.path.dirname(os.path.abspath(file_path)), exist_ok=True)
     np.savez(file_path, **cols)
 
@@ -260,13 +313,19 @@ def load_events(file_path):
     return d
 
 
-def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), decoder=None, switch_cost=None, transitions=None):
+def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), decoder=None, switch_cost=None, transitions=None,
+                 posteriors=False):
     """The events of one evaluated split: ``logits`` (N, classes) fp32 ON THE GPU, row r the logits of sample ``order[r]`` (None:
     of sample r).  The positions are time-ordered on the host (``time_order``), decoded on the device (``engine.EventDecoder``; only
     the events come back), the ground truth is ``label_runs`` of the samples' labels, both are scored with ``EventPRF1``.
     ``switch_cost`` (None: per-frame arg-max of the smoothed scores) goes to the decoder and into the columns, and so does
-    ``transitions`` (None: no transition matrix; (classes, classes), see ``EventDecoder.decode``).
+    ``transitions`` (None: no transition matrix; (classes, classes), see ``EventDecoder.decode``).  ``posteriors`` (with one of the
+    two, ``smooth`` 1): ``score`` and ``peak`` are of the posterior probability under the path's HMM, and the columns say so.
     -> ``(columns of save_events, EventPRF1)``."""
+    if posteriors and switch_cost is None and transitions is None:
+        raise ValueError("decode_split: posteriors are those of a path's HMM, give switch_cost or transitions")
+    if posteriors and int(smooth) != 1:
+        raise ValueError(f"decode_split: posteriors score a path of the unsmoothed scores, not together with smooth={smooth}")
     from .engine import EventDecoder
     from .metrics.events import EventPRF1
     rows, start, video, frame = time_order(dataset, order)
@@ -275,7 +334,8 @@ def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), d
     path = {} if switch_cost is None else {"switch_cost": float(switch_cost)}    # (without it the call is the call it was)
     if transitions is not None:
         path["transitions"] = check_transitions(transitions, logits.shape[1], "decode_split")
-    ev = {k: v.cpu().numpy() for k, v in decoder.decode(logits, rows, start, smooth=smooth, **path).items()}
+    how = {"posteriors": True} if posteriors else {}                             # (without it the call is the call it was)
+    ev = {k: v.cpu().numpy() for k, v in decoder.decode(logits, rows, start, smooth=smooth, **path, **how).items()}
     first, last = ev["first"].astype(np.int64), ev["last"].astype(np.int64)
     labels = np.asarray([dataset.classes.index(dataset._samples[int(i)][2]) for i in order[rows]], np.int64)
     gfirst, glast, gcls = label_runs(labels, start)
@@ -286,7 +346,7 @@ def decode_split(dataset, logits, order=None, smooth=1, tious=(0.1, 0.3, 0.5), d
     prec, rec, f1 = metric.arrays()
     cols = dict(pred, peak=ev["peak"], first_sample=order[rows[first]], last_sample=order[rows[last]], gt_video=gt["video"],
                 gt_first_frame=gt["first_frame"], gt_last_frame=gt["last_frame"], gt_cls=gt["cls"], smooth=int(smooth),
-                tiou=np.asarray(metric.tious), precision=prec, recall=rec, f1=f1, **path)
+                tiou=np.asarray(metric.tious), precision=prec, recall=rec, f1=f1, **path, **how)
     return cols, metric
 
 
@@ -296,6 +356,8 @@ def event_table(cols, classes, limit=40):
     how = "smooth %d" % int(cols["smooth"]) if cols.get("switch_cost") is None else "switch cost %g" % float(cols["switch_cost"])
     if cols.get("transitions") is not None:
         how = "transition matrix"
+    if cols.get("posteriors") is not None and bool(cols["posteriors"]):
+        how += ", posterior scores"
     lines = ["Events: %d predicted, %d ground truth (%s)" % (n, len(cols["gt_video"]), how)]
     for i in range(min(n, limit)):
         lines.append("  %s\t%s\tframes %d-%d\tscore %.3f\tpeak %.3f" % (cols["video"][i], classes[int(cols["cls"][i])],
