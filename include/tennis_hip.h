@@ -239,7 +239,10 @@ int tn_augment_forward(tn_ctx *ctx, const uint8_t *src, int batch, int src_h, in
                        const tn_aug_frame *frames_host, int size, uint8_t *tmp, float *gray_tmp, uint8_t *dst);
 /* ToTensor + Normalize (reference evaluate.py:96-97, train.py:138-139) for consumers of fp32 frames (the fine-tuning
  * step; the inference encoder fuses it into its stem load): dst[p][c] = (src[p][c] / 255 - mean[c]) / std[c],
- * src (pixels, 3) uint8 NHWC, dst (pixels, 3) float NHWC, both DEVICE; mean3 / std3 HOST arrays of 3 floats. */
+ * in float32 with two divisions, each operation rounded once (dataset.default_transform's formula bit for bit).
+ * src (pixels, 3) uint8 NHWC, dst (pixels, 3) float NHWC, both DEVICE; mean3 / std3 HOST arrays of 3 floats, no std zero.
+ * src may start at any byte and dst at any float: the 12-bytes-in / three-float4-out path is taken when src is 4-byte
+ * and dst 16-byte aligned, a byte-wise loop otherwise, with the same values. */
 int tn_to_tensor_normalize(tn_ctx *ctx, const uint8_t *src, long pixels, const float *mean3, const float *std3, float *dst);
 
 /* ---- JPEG decode on the device ------------------------------------------------ */
@@ -551,7 +554,9 @@ int tn_gnmt_frames_trainer_clip_stats(tn_gnmt_frames_trainer *t, float *norm, fl
 /* ---- device PRF1 confusion histogram -------------------------------------- */
 /* Replaces the argmax + per-sample python loop of PRF1.update (reference
  * metrics/vision.py:41-49).  logits (rows,classes) fp32, labels (rows,) int32;
- * adds into mat (classes*classes) int64, row = label, col = argmax (first max). */
+ * adds into mat (classes*classes) int64, row = label, col = argmax (first max).
+ * Rows whose label lies outside 0..classes-1 are dropped, and mat.sum() grows by
+ * the number of in-range labels. */
 int tn_prf1_update(tn_ctx *ctx, const float *logits, const int32_t *labels, int rows, int classes,
                    int64_t *mat);
 

@@ -109,28 +109,33 @@ extern "C" int tn_preproc_forward(tn_preproc *p, const uint8_t *src, int batch, 
 }
 
 // ToTensor + Normalize of the transform (evaluate.py:96-97, train.py:138) for consumers that want fp32 frames (the
-// fine-tuning step): y = (x / 255 - mean[c]) / std[c], NHWC in, NHWC out.  4 pixels (12 bytes) per thread.
+// fine-tuning step): y = (x / 255 - mean[c]) / std[c], NHWC in, NHWC out: two float32 divisions and one subtraction, each rounded
+// once, the formula of dataset.default_transform bit for bit (a multiplication by 1 / std differs in the last bit for 230 of the
+// 768 (byte, channel) pairs).  4 pixels (12 bytes) per thread; `vec`: src is 4-byte and dst 16-byte aligned, so that a whole group is
+// read as three words and written as three float4; otherwise, and in the last group of a pixel count that is no multiple of 4,
+// byte by byte.
 __global__ __launch_bounds__(256) void to_tensor_normalize_kernel(const uint8_t *__restrict__ src, long npix, float m0, float m1, float m2,
-                                                                   float i0, float i1, float i2, float *__restrict__ dst) {
+                                                                   float s0, float s1, float s2, int vec, float *__restrict__ dst) {
   const long q = (long)blockIdx.x * 256 + threadIdx.x;     // group of 4 pixels
   const long p0 = q * 4;
   if (p0 >= npix) return;
-  const float mean[3] = {m0, m1, m2}, inv[3] = {i0, i1, i2};
-  if (p0 + 4 <= npix) {
+  const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+  if (vec && p0 + 4 <= npix) {
     const uint32_t *s32 = (const uint32_t *)(src + p0 * 3);
     const uint32_t a = s32[0], b = s32[1], c = s32[2];
     const uint8_t v[12] = {(uint8_t)a, (uint8_t)(a >> 8), (uint8_t)(a >> 16), (uint8_t)(a >> 24), (uint8_t)b, (uint8_t)(b >> 8),
                            (uint8_t)(b >> 16), (uint8_t)(b >> 24), (uint8_t)c, (uint8_t)(c >> 8), (uint8_t)(c >> 16), (uint8_t)(c >> 24)};
     float o[12];
 #pragma unroll
-    for (int j = 0; j < 12; ++j) o[j] = ((float)v[j] / 255.0f - mean[j % 3]) * inv[j % 3];
+    for (int j = 0; j < 12; ++j) o[j] = ((float)v[j] / 255.0f - mean[j % 3]) / sd[j % 3];
     float4 *d4 = (float4 *)(dst + p0 * 3);
     d4[0] = make_float4(o[0], o[1], o[2], o[3]);
     d4[1] = make_float4(o[4], o[5], o[6], o[7]);
     d4[2] = make_float4(o[8], o[9], o[10], o[11]);
   } else {
-    for (long p = p0; p < npix; ++p)
-      for (int c = 0; c < 3; ++c) dst[p * 3 + c] = ((float)src[p * 3 + c] / 255.0f - mean[c]) * inv[c];
+    const long p1 = p0 + 4 < npix ? p0 + 4 : npix;
+    for (long p = p0; p < p1; ++p)
+      for (int c = 0; c < 3; ++c) dst[p * 3 + c] = ((float)src[p * 3 + c] / 255.0f - mean[c]) / sd[c];
   }
 }
 
@@ -140,8 +145,9 @@ extern "C" int tn_to_tensor_normalize(tn_ctx *ctx, const uint8_t *src, long pixe
   TN_REQUIRE(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "tn_to_tensor_normalize: zero std");
   TN_ON_DEVICE(ctx->device);
   const long groups = (pixels + 3) / 4;
+  const int vec = ((uintptr_t)src & 3) == 0 && ((uintptr_t)dst & 15) == 0;      // a group starts 12 q bytes into src, 48 q into dst
   hipLaunchKernelGGL(to_tensor_normalize_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, ctx->stream, src, pixels, mean3[0],
-                     mean3[1], mean3[2], 1.0f / std3[0], 1.0f / std3[1], 1.0f / std3[2], dst);
+                     mean3[1], mean3[2], std3[0], std3[1], std3[2], vec, dst);
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
 }
