@@ -1,4 +1,4 @@
-// What the handles of api.hip, encoder.hip, finetune.hip, captioner.hip and captioner_train.hip share on the host: the device allocations of a handle
+// What the handles of api.hip, train_steps.hip, encoder.hip, finetune.hip, captioner.hip and captioner_train.hip share on the host: the device allocations of a handle
 // (DevPool), the lookup of its parameters by name and the table of where each lives (param_table.h), and - for the training
 // handles - the flat buffers with the one read-back and the one buffers query that go through that table (TrainParams).
 #pragma once

@@ -33,6 +33,8 @@ void tn_set_error(const std::string &msg);
       return TN_ERR_INVALID;                                                           \
     }                                                                                  \
   } while (0)
+// a call that returns a TN_ code and has set the error text itself: a failure is handed on as it is
+#define TN_TRY(e) do { if (int tn_rc_ = (e)) return tn_rc_; } while (0)
 
 // Makes `dev` the calling thread's current HIP device for the rest of the scope and puts the previous one back
 // on exit: the library never leaves the caller's (torch's) current device changed behind its back.

@@ -586,8 +586,6 @@ int ft_forward_features(tn_finetune *f, const float *x, int n) {
   const int B = n, H = f->H, W = f->W;
   const long M0 = (long)B * (H / 2) * (W / 2);
   float *w = f->w;
-  int rc;
-#define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
   TN_TRY(launch_ft_im2col7(x, B, H, W, f->col7, s));
   TN_TRY(ft_linear(f, f->col7, 147, nullptr, nullptr, w + f->o_w0, 147, f->z0, 64, (int)M0, 64, 147, s));
   ft_bn_forward(f, f->bn0, f->z0, 64, M0, f->a0, s);
@@ -632,7 +630,6 @@ int ft_backward_features(tn_finetune *f, int n) {
   float *w = f->w, *g = f->g;
   const int CF = f->Ctot[3], P3 = f->Hb[3] * f->Hb[3];
   const long M3 = (long)B * P3;
-  int rc;
   TN_TRY(launch_ft_gap_bwd(f->dfeat, B, P3, CF, f->tg, s));
   ft_bn_backward(f, f->bnF, f->tg, f->X[3], CF, M3, f->dX[3], CF, 0, s);
   for (int b = 3; b >= 0; --b) {
@@ -681,7 +678,6 @@ void ft_update_running(tn_finetune *f) {
     (void)launch_ft_bn_running(f->state + b.o_rm, f->state + b.o_rv, b.mean, b.var, b.C, s);
   });
 }
-#undef TN_TRY
 
 float *ft_features(tn_finetune *f) { return f->feat; }
 float *ft_feature_grad(tn_finetune *f) { return f->dfeat; }
@@ -715,8 +711,6 @@ extern "C" int tn_finetune_forward_backward(tn_finetune *f, const float *x, cons
   hipStream_t s = f->ctx->stream;
   const int B = f->B, NC = f->classes, CF = f->Ctot[3];
   float *w = f->w, *g = f->g;
-  int rc;
-#define TN_TRY(e) do { rc = (e); if (rc) return rc; } while (0)
   TN_TRY(ft_forward_features(f, x, B));
   TN_TRY(launch_linear_f32(f->feat, CF, w + f->o_wd, CF, w + f->o_bd, f->logits, NC, B, NC, CF, 0, s));
   TN_HIP_CHECK(hipMemcpyAsync(f->labels, labels, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
@@ -726,7 +720,6 @@ extern "C" int tn_finetune_forward_backward(tn_finetune *f, const float *x, cons
   TN_TRY(launch_dense_bwd(f->dlog, f->feat, w + f->o_wd, B, NC, CF, g + f->o_wd, g + f->o_bd, f->dfeat, s));
   TN_TRY(ft_backward_features(f, B));
   ft_update_running(f);
-#undef TN_TRY
   TN_HIP_CHECK(hipGetLastError());
   return TN_OK;
 }

@@ -8,8 +8,6 @@
 
 #include "common.h"
 
-#define TN_TRY(e) do { if (int tn_rc_ = (e)) return tn_rc_; } while (0)
-
 // ---- the step kernels' launch parameters: 1024 threads = 16 waves ----
 constexpr int kBeamThreads = 1024;
 // dynamic LDS the step kernels may ask for: a launch above 64 KiB needs the kernel's limit raised first (160 KiB per CU on

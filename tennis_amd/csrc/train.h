@@ -84,7 +84,7 @@ int launch_ft_gap(const float *a, int B, int P, int C, float *f, hipStream_t s);
 int launch_ft_gap_bwd(const float *df, int B, int P, int C, float *da, hipStream_t s);
 int launch_ft_bn_fold(const float *mean, const float *var, const float *gamma, const float *beta, int C, float *sc, float *sh, hipStream_t s);
 int launch_ft_bn_running(float *rmean, float *rvar, const float *mean, const float *var, int C, hipStream_t s);
-// The fine-tuning step in parts (finetune.hip), what tn_finetune_forward_backward chains and the CNN-RNN step (api.hip) drives.
+// The fine-tuning step in parts (finetune.hip), what tn_finetune_forward_backward chains and the two frame-trained steps (train_steps.hip) drive.
 // ft_create: the table of param_table.h::ft_param_table, loaded, uploaded, then the workspaces; dense_prefix NULL builds the backbone
 // alone (no classifier; classes ignored); fit_frames non-NULL: first compare the
 // memory batch frames need with what the device has free, and on a shortfall return TN_ERR_NOMEM with *fit_frames = the frames

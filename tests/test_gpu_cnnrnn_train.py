@@ -240,33 +240,58 @@ def test_abi_refusals():
     def create(c=ctx.handle, params=arr, size=224, classes=11, batch=2, steps=3, out=C.byref(h)):
         return lib.tn_cnnrnn_trainer_create(c, L.RNN_GRU, params, len(arr), b"densenet0_", b"cnnrnn0_gru0_", b"cnnrnn0_dense0_",
                                             size, size, classes, batch, steps, 0, out)
+    last = lambda: lib.tn_last_error().decode()                  # the whole message a refusal leaves, entry name included
+    INV, FB = "invalid argument: ", "invalid argument: tn_cnnrnn_trainer_forward_backward: "
     assert create(c=None) == -1                                  # TN_ERR_INVALID
+    assert last() == INV + "tn_cnnrnn_trainer_create: null argument"
     assert create(params=None) != 0
+    assert last() == INV + "tn_cnnrnn_trainer_create: null argument"
     assert create(out=None) != 0
-    assert create(size=100) != 0 and create(size=0) != 0
-    assert create(classes=0) != 0 and create(classes=-1) != 0
-    assert create(batch=0) != 0 and create(steps=0) != 0
+    assert last() == INV + "tn_cnnrnn_trainer_create: null argument"
+    for size in (100, 0):
+        assert create(size=size) != 0
+        assert last() == INV + "tn_cnnrnn_trainer_create: frames must be square with a side divisible by 32"
+    for classes in (0, -1):
+        assert create(classes=classes) != 0
+        assert last() == INV + "tn_cnnrnn_trainer_create: classes must be positive"
+    assert create(batch=0) != 0
+    assert last() == INV + "tn_cnnrnn_trainer_create: bad batch / steps"
+    assert create(steps=0) != 0
+    assert last() == INV + "tn_cnnrnn_trainer_create: bad batch / steps"
     assert create() == 0 and h.value
     xd = torch.from_numpy(x).cuda().permute(0, 2, 3, 1).contiguous()
     yd = torch.from_numpy(y).cuda()
     loss = torch.empty(2, device="cuda")
     try:
         assert lib.tn_cnnrnn_trainer_forward_backward(h, None, L.ptr(yd), 2, 3, 224, 224, L.ptr(loss), None) != 0
+        assert last() == FB + "null argument"
         assert lib.tn_cnnrnn_trainer_forward_backward(h, L.ptr(xd), None, 2, 3, 224, 224, L.ptr(loss), None) != 0
+        assert last() == FB + "null argument"
         assert lib.tn_cnnrnn_trainer_forward_backward(None, L.ptr(xd), L.ptr(yd), 2, 3, 224, 224, None, None) != 0
+        assert last() == FB + "null argument"
         # frame counts that are not the handle's batch x steps (6 = 2 x 3)
+        counts = FB + "batch and steps must equal the handle's (batch x steps frames, BatchNorm statistics over all)"
         assert lib.tn_cnnrnn_trainer_forward_backward(h, L.ptr(xd), L.ptr(yd), 1, 6, 224, 224, None, None) != 0
+        assert last() == counts
         assert lib.tn_cnnrnn_trainer_forward_backward(h, L.ptr(xd), L.ptr(yd), 2, 2, 224, 224, None, None) != 0
         assert "batch and steps" in lib.tn_last_error().decode()
+        assert last() == counts
         assert lib.tn_cnnrnn_trainer_forward_backward(h, L.ptr(xd), L.ptr(yd), 2, 3, 192, 192, None, None) != 0
         assert "frame size" in lib.tn_last_error().decode()
+        assert last() == FB + "the frame size must equal the handle's"
         assert lib.tn_cnnrnn_trainer_buffers(None, None, None, None, None, None, None) != 0
+        assert last() == INV + "tn_cnnrnn_trainer_buffers: null handle"
         assert lib.tn_cnnrnn_trainer_sgd_step(None, 0.1, 0.9, 0.0, 0.5) != 0
+        assert last() == INV + "tn_cnnrnn_trainer_sgd_step: null handle"
         buf = (C.c_float * 4)()
         n = C.c_int64()
+        # (a name with a part's prefix is that part's to refuse, under its own name)
         assert lib.tn_cnnrnn_trainer_read_param(h, b"densenet0_no_such", 0, buf, 4, C.byref(n)) != 0
+        assert last() == INV + "tn_finetune_read_param: unknown parameter name"
         assert lib.tn_cnnrnn_trainer_read_param(h, b"cnnrnn0_dense0_bias", 0, buf, 4, C.byref(n)) != 0     # buffer too small
+        assert last() == INV + "tn_head_read_param: host buffer too small"
         assert lib.tn_cnnrnn_trainer_read_param(h, b"cnnrnn0_dense0_bias", 0, None, 4, C.byref(n)) != 0
+        assert last() == INV + "tn_cnnrnn_trainer_read_param: null argument"
         # a step after the refusals still runs
         assert lib.tn_cnnrnn_trainer_forward_backward(h, L.ptr(xd), L.ptr(yd), 2, 3, 224, 224, L.ptr(loss), None) == 0
         assert bool(torch.isfinite(loss).all())
@@ -279,4 +304,5 @@ def test_abi_refusals():
     h2 = C.c_void_p()
     assert lib.tn_cnnrnn_trainer_create(ctx.handle, L.RNN_GRU, arr2, len(arr2), b"densenet0_", b"cnnrnn0_gru0_", b"cnnrnn0_dense0_",
                                         224, 224, 11, 2, 3, 0, C.byref(h2)) != 0
+    assert last() == "missing parameter: cnnrnn0_gru0_r0_h2h_bias"
     del keep, keep2

@@ -388,11 +388,20 @@ def test_abi_refusals():
                out=C.byref(h)):
         return lib.tn_gnmt_frames_trainer_create(c, params, n, bb, pre, Lb.RNN_GRU, 8, E, V, 2, 1, 0, side, max_batch, max_src_len, L,
                                                  max_frames, 0, out)
+    last = lambda: lib.tn_last_error().decode()                  # the whole message a refusal leaves, entry name included
+    INV, CR, FB = ("invalid argument: " + s for s in ("", "tn_gnmt_frames_trainer_create: ", "tn_gnmt_frames_trainer_forward_backward: "))
     assert create(c=None) == -1                                  # TN_ERR_INVALID
-    assert create(params=None) != 0 and create(bb=None) != 0 and create(pre=None) != 0 and create(out=None) != 0
-    assert create(side=100) != 0 and create(side=0) != 0
-    assert "divisible by 32" in lib.tn_last_error().decode()
-    assert create(max_batch=0) != 0 and create(max_src_len=0) != 0 and create(max_frames=0) != 0
+    assert last() == CR + "null argument"
+    for null in ("params", "bb", "pre", "out"):
+        assert create(**{null: None}) != 0
+        assert last() == CR + "null argument"
+    for side in (100, 0):
+        assert create(side=side) != 0
+        assert "divisible by 32" in lib.tn_last_error().decode()
+        assert last() == CR + "frames must be square with a side divisible by 32"
+    for zero in ("max_batch", "max_src_len", "max_frames"):
+        assert create(**{zero: 0}) != 0
+        assert last() == CR + "bad max_batch / max_src_len / max_frames"
     assert create() == 0 and h.value
     xd = torch.from_numpy(x).cuda().permute(0, 1, 3, 4, 2).contiguous()
     sd, td, ld = (torch.from_numpy(a).cuda() for a in (svl, tgt, tvl))
@@ -401,19 +410,36 @@ def test_abi_refusals():
     def fb(t=h, frames=Lb.ptr(xd), s=Lb.ptr(sd), tg=Lb.ptr(td), tv=Lb.ptr(ld), batch=2, steps=3, lo=Lb.ptr(loss)):
         return lib.tn_gnmt_frames_trainer_forward_backward(t, frames, s, tg, L, tv, batch, steps, L, lo, None)
     try:
-        assert fb(t=None) != 0 and fb(frames=None) != 0 and fb(s=None) != 0 and fb(tg=None) != 0 and fb(tv=None) != 0 and fb(lo=None) != 0
+        for null in ("t", "frames", "s", "tg", "tv", "lo"):
+            assert fb(**{null: None}) != 0
+            assert last() == FB + "null argument"
         assert fb(batch=3, steps=2) != 0 and "max_batch" in lib.tn_last_error().decode()
+        assert last() == FB + "batch exceeds max_batch"
         assert fb(batch=1, steps=4) != 0 and "max_src_len" in lib.tn_last_error().decode()
-        assert fb(batch=0) != 0 and fb(steps=0) != 0
+        assert last() == FB + "steps exceed max_src_len"
+        assert fb(batch=0) != 0
+        assert last() == FB + "batch exceeds max_batch"
+        assert fb(steps=0) != 0
+        assert last() == FB + "steps exceed max_src_len"
         assert lib.tn_gnmt_frames_trainer_buffers(None, None, None, None, None, None, None) != 0
+        assert last() == INV + "tn_gnmt_frames_trainer_buffers: null handle"
         assert lib.tn_gnmt_frames_trainer_adam_step(None, 1e-3, 0.9, 0.999, 1e-8) != 0
-        assert lib.tn_gnmt_frames_trainer_set_dropout(None, 0.1, 0) != 0 and lib.tn_gnmt_frames_trainer_set_dropout(h, 1.0, 0) != 0
+        assert last() == INV + "tn_gnmt_frames_trainer_adam_step: null handle"
+        # (what a part refuses, it refuses under its own name)
+        assert lib.tn_gnmt_frames_trainer_set_dropout(None, 0.1, 0) != 0
+        assert last() == INV + "tn_gnmt_frames_trainer_set_dropout: null handle"
+        assert lib.tn_gnmt_frames_trainer_set_dropout(h, 1.0, 0) != 0
+        assert last() == INV + "tn_gnmt_trainer_set_dropout: rate must be in [0, 1)"
         buf = (C.c_float * 4)()
         n = C.c_int64()
         assert lib.tn_gnmt_frames_trainer_read_param(h, b"densenet0_no_such", 0, buf, 4, C.byref(n)) != 0
+        assert last() == INV + "tn_finetune_read_param: unknown parameter name"
         assert lib.tn_gnmt_frames_trainer_read_param(h, b"other_name", 0, buf, 4, C.byref(n)) != 0
+        assert last() == INV + "tn_gnmt_frames_trainer_read_param: unknown parameter name"
         assert lib.tn_gnmt_frames_trainer_read_param(h, b"gnmt_tgt_proj_bias", 0, buf, 4, C.byref(n)) != 0     # buffer too small
+        assert last() == INV + "tn_gnmt_trainer_read_param: host buffer too small"
         assert lib.tn_gnmt_frames_trainer_read_param(h, b"gnmt_tgt_proj_bias", 0, None, 4, C.byref(n)) != 0
+        assert last() == INV + "tn_gnmt_frames_trainer_read_param: null argument"
         # a step after the refusals still runs
         assert fb() == 0 and bool(torch.isfinite(loss).all())
     finally:
@@ -426,6 +452,7 @@ def test_abi_refusals():
         assert lib.tn_gnmt_frames_trainer_forward_backward(h3, Lb.ptr(xd), Lb.ptr(sd), Lb.ptr(td), L, Lb.ptr(ld), 2, 3, L, Lb.ptr(loss),
                                                            None) != 0
         assert "max_frames" in lib.tn_last_error().decode()
+        assert last() == FB + "batch * steps exceeds max_frames"
         assert lib.tn_gnmt_frames_trainer_forward_backward(h3, Lb.ptr(xd), Lb.ptr(sd), Lb.ptr(td), L, Lb.ptr(ld), 2, 2, L, Lb.ptr(loss),
                                                            None) == 0
     finally:
@@ -437,10 +464,12 @@ def test_abi_refusals():
     h2 = C.c_void_p()
     assert create(params=arr2, n=len(arr2), out=C.byref(h2)) != 0
     assert "feature width" in lib.tn_last_error().decode()
+    assert last() == "tn_gnmt_frames_trainer_create: gnmt_enc_rnn0_l_i2h_weight is not (gates * hidden, 1024), the backbone's feature width"
     # a missing parameter, of either part
     for gone in ("gnmt_dec_rnn1_h2h_bias", "densenet0_stage2_conv3_weight"):
         q = {k: v for k, v in p.items() if k != gone}
         arr3, keep3 = Lb.make_params(q)
         assert create(params=arr3, n=len(arr3), out=C.byref(h2)) != 0
         assert gone in lib.tn_last_error().decode()
+        assert last() == "missing parameter: " + gone
     del keep, keep2, keep3

@@ -339,7 +339,9 @@ def test_abi_refusals_and_switching_off():
     f, i64 = C.c_float(), C.c_int64()
     for h in ("tn_head", "tn_finetune", "tn_cnnrnn_trainer", "tn_gnmt_trainer", "tn_gnmt_frames_trainer"):
         assert getattr(lib, h + "_set_clip")(None, 1.0) != 0 and b"null handle" in lib.tn_last_error()
+        assert lib.tn_last_error().decode() == f"invalid argument: {h}_set_clip: null handle"      # (the two-part handles too: their own name)
         assert getattr(lib, h + "_clip_stats")(None, C.byref(f), C.byref(f), C.byref(i64)) != 0 and b"null handle" in lib.tn_last_error()
+        assert lib.tn_last_error().decode() == f"invalid argument: {h}_clip_stats: null handle"
     cfg, p, batches = _gnmt_case(1, "gru")
     make = lambda: GNMTTrainer(p, cfg["F"], cfg["H"], cfg["E"], cfg["V"], max_batch=cfg["B"], max_src_len=cfg["T"], max_tgt_len=cfg["L"])
     tr, twin = make(), make()
