@@ -331,10 +331,16 @@ int tn_dbg_trainer_params(int which, const int *dims, int n_dims, const char *pr
  * the BatchNorm applied on load (K values; 3x3: 128), es / et NULL except for the stem, y (M, ldy) fp32 written in columns
  * [yoff, yoff + N), M = B Ho Wo output pixels: all DEVICE, 16-byte aligned.  w_host: the GEMM's B operand (K, N) fp32, k-major
  * (stem k = c 49 + ky 7 + kx, 3x3 k = tap 128 + c), HOST; padded and - which = 0 - split and packed as tn_densenet121_create_ex
- * does.  tile (which = 0): 0 the launcher's choice, 1 the small tile, 2 the large one.  Synchronous. */
+ * does.  tile, for either kernel: 0 the launcher's choice, 1 the small tile (1x1 / transition 128 x 64, 3x3 128 x 32), 2 the large one
+ * (128 x 128, 3x3 256 x 32); the stem has one tile (128 x 64).  The selector's range, K a multiple of 32 (other than the stem's 147)
+ * and the output window are the launchers' own refusals ("conv_fp32x3: ..." / "conv_fp32: ...").  Synchronous. */
 int tn_dbg_conv_fp32x3(tn_ctx *ctx, int which, int kind, int tile, int layout, const void *x, int ldx, int K, const float *s, const float *t,
                        const float *w_host, int N, const float *es, const float *et, float *y, int ldy, int yoff, int64_t M, int H, int W,
                        int Ho, int Wo);
+
+/* The fp32 mode's 3x3 stride-2 pad-1 max pool (csrc/dense_fp32.hip) on caller buffers: x (B, H, W, 64) fp32, y (B Ho Wo, ldy) fp32
+ * written in columns [0, 64), Ho = (H - 1) / 2 + 1, Wo likewise, ldy >= 64 a multiple of 4: DEVICE, 16-byte aligned.  Synchronous. */
+int tn_dbg_maxpool_fp32(tn_ctx *ctx, const float *x, int B, int H, int W, float *y, int ldy, int Ho, int Wo);
 
 /* Tuning hook of the windowed recurrent kernel (csrc/rnn_window.hip): the samples one workgroup walks - 0 the library's choice,
  * 4, or twice the gates (6 GRU / 8 LSTM).  The results do not depend on it (scripts/bench_window_head.py measures both). */

@@ -233,6 +233,7 @@ _SIGS = {
     "tn_dbg_head": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int]),
     "tn_dbg_conv_fp32x3": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int,
                                      C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tn_dbg_maxpool_fp32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_gemm_tn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
     "tn_dbg_gemm_nn": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tn_dbg_rnn_wide_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -419,7 +419,11 @@ struct Fp32ConvArgs {
   int H, W;              // input map (stem: frame) size
   int Ho, Wo;            // output map size
 };
-int launch_conv_fp32(const Fp32ConvArgs &a, hipStream_t s);
+// tile: 0 = the launcher's rule (the large tile where it still gives >= 512 workgroups), 1 = the small one (<1X1,1,2>, <3X3,1,1>,
+// <TRANS,1,2>), 2 = the large one (<1X1,1,4>, <3X3,2,1>, <TRANS,1,4>); the stem is <1,2> always.  Refuses (messages "conv_fp32: ...")
+// a non-stem K that is no multiple of 32 - the k loop reads s, t, the activation and the weight rows up to K rounded up to 32 - and
+// operands that are not 16-byte aligned.
+int launch_conv_fp32(const Fp32ConvArgs &a, hipStream_t s, int tile = 0);
 // ---- the fp32x3 encoder mode (TN_ENC_FP32X3, dense_fp32x3.hip): the same network, every fp32 operand as three bf16 terms, six
 // products per k-step on the bf16 MFMA.  tile: 0 = the tile launch_conv_fp32 would take, 1 = the small one, 2 = the large one.
 int launch_conv_fp32x3(const Fp32ConvArgs &a, hipStream_t s, int tile = 0);

@@ -995,7 +995,6 @@ extern "C" int tn_dbg_conv_fp32x3(tn_ctx *ctx, int which, int kind, int tile, in
                                   int64_t M, int H, int W, int Ho, int Wo) {
   TN_REQUIRE(ctx && x && w_host && y, "tn_dbg_conv_fp32x3: null argument");
   TN_REQUIRE(which == 0 || which == 1, "tn_dbg_conv_fp32x3: which must be 0 (fp32x3) or 1 (fp32)");
-  TN_REQUIRE(which == 0 || tile == 0, "tn_dbg_conv_fp32x3: the fp32 kernel takes its launcher's tile");
   TN_REQUIRE(kind >= FP32_STEM && kind <= FP32_TRANS, "tn_dbg_conv_fp32x3: unknown kind");
   TN_REQUIRE(layout >= 0 && layout <= 2, "tn_dbg_conv_fp32x3: unknown input layout");
   TN_REQUIRE(M > 0 && K > 0 && N > 0 && N % 32 == 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && M % ((int64_t)Ho * Wo) == 0,
@@ -1003,7 +1002,8 @@ extern "C" int tn_dbg_conv_fp32x3(tn_ctx *ctx, int which, int kind, int tile, in
   if (kind == FP32_STEM) {
     TN_REQUIRE(K == 147 && es && et && Ho == (H - 1) / 2 + 1 && Wo == (W - 1) / 2 + 1, "tn_dbg_conv_fp32x3: the stem has K = 147, an epilogue and a ((H - 1) / 2 + 1) x ((W - 1) / 2 + 1) output");
   } else {
-    TN_REQUIRE(s && t && !es && !et && K % 32 == 0 && ldx % 4 == 0, "tn_dbg_conv_fp32x3: s / t, no epilogue, K a multiple of 32");
+    // (K a multiple of 32 and the tile selector's range are the launchers' own refusals: "conv_fp32: ..." / "conv_fp32x3: ...")
+    TN_REQUIRE(s && t && !es && !et && ldx % 4 == 0, "tn_dbg_conv_fp32x3: s / t, no epilogue, ldx a multiple of 4");
     TN_REQUIRE(kind == FP32_3X3 ? (K == 1152 && ldx == 128) : ldx >= K, "tn_dbg_conv_fp32x3: K beyond the channel stride (3x3: K = 1152, ldx = 128)");
     TN_REQUIRE(kind == FP32_TRANS ? (2 * Ho <= H && 2 * Wo <= W) : (Ho == H && Wo == W), "tn_dbg_conv_fp32x3: output map size does not fit the input's");
   }
@@ -1019,12 +1019,22 @@ extern "C" int tn_dbg_conv_fp32x3(tn_ctx *ctx, int which, int kind, int tile, in
   Fp32ConvArgs a{};
   a.kind = kind; a.x = x; a.layout = layout; a.ldx = ldx; a.K = K; a.s = s; a.t = t; a.w = wd; a.wx = wx; a.N = N; a.es = es; a.et = et;
   a.y = y; a.ldy = ldy; a.yoff = yoff; a.M = (long)M; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
-  const int rc = which == 0 ? launch_conv_fp32x3(a, ctx->stream, tile) : launch_conv_fp32(a, ctx->stream);
+  const int rc = which == 0 ? launch_conv_fp32x3(a, ctx->stream, tile) : launch_conv_fp32(a, ctx->stream, tile);
   const hipError_t e = hipStreamSynchronize(ctx->stream);
   (void)hipFree(wd); (void)hipFree(wx);
   if (rc) return rc;
   TN_HIP_CHECK(e);
   return TN_OK;
+}
+
+// The fp32 mode's max pool (dense_fp32.hip) on caller buffers
+extern "C" int tn_dbg_maxpool_fp32(tn_ctx *ctx, const float *x, int B, int H, int W, float *y, int ldy, int Ho, int Wo) {
+  TN_REQUIRE(ctx && x && y, "tn_dbg_maxpool_fp32: null argument");
+  TN_REQUIRE(B > 0 && H > 0 && W > 0, "tn_dbg_maxpool_fp32: B, H and W must be positive");
+  TN_REQUIRE(Ho == (H - 1) / 2 + 1 && Wo == (W - 1) / 2 + 1, "tn_dbg_maxpool_fp32: the output is ((H - 1) / 2 + 1) x ((W - 1) / 2 + 1)");
+  TN_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "tn_dbg_maxpool_fp32: buffers must be 16-byte aligned");
+  TN_ON_DEVICE(ctx->device);
+  return dbg_finish(ctx, launch_maxpool_fp32(x, B, H, W, y, ldy, Ho, Wo, ctx->stream));
 }
 
 // The latency GEMM's launchers on caller operands.  form 0: launch_linear_f32_lat2 (row-major X and W); 1: launch_linear_f32_lat_wk4

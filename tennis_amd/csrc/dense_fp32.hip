@@ -206,21 +206,30 @@ int launch_kind(const Fp32ConvArgs &a, hipStream_t s) {
 
 }  // namespace
 
-int launch_conv_fp32(const Fp32ConvArgs &a, hipStream_t s) {
+int launch_conv_fp32(const Fp32ConvArgs &a, hipStream_t s, int tile) {
   TN_REQUIRE(a.M > 0 && a.K > 0 && a.x && a.w && a.y, "conv_fp32: empty or null operand");
-  TN_REQUIRE(a.kind == FP32_STEM || (a.ldx % 4 == 0 && a.K % 4 == 0), "conv_fp32: channel strides must be multiples of 4");
-  TN_REQUIRE(a.ldy % 4 == 0 && a.yoff % 4 == 0 && a.yoff + a.N <= a.ldy, "conv_fp32: output columns out of range");
+  TN_REQUIRE(tile >= 0 && tile <= 2, "conv_fp32: tile selector must be 0 (the launcher's choice), 1 (small) or 2 (large)");
+  // The k loop runs to K rounded up to the k-stage and reads s, t, the activation's channels and the weight rows that far: only the
+  // stem's loader stops at K (its weight array carries the zero rows), every other kind needs K to be a whole number of stages.
+  TN_REQUIRE(a.kind == FP32_STEM || (a.ldx % 4 == 0 && a.K % kBK == 0 && a.s && a.t),
+             "conv_fp32: channel strides must be multiples of 4 and K a multiple of the k-stage (32)");
+  TN_REQUIRE(a.kind == FP32_STEM || (((uintptr_t)a.x | (uintptr_t)a.s | (uintptr_t)a.t) & 15) == 0, "conv_fp32: operands must be 16-byte aligned");
+  TN_REQUIRE(((uintptr_t)a.w & 15) == 0, "conv_fp32: the weight array must be 16-byte aligned");
+  TN_REQUIRE(a.N % 32 == 0 && a.ldy % 4 == 0 && a.yoff % 4 == 0 && a.yoff + a.N <= a.ldy, "conv_fp32: output columns out of range");
   // Where the large tile leaves fewer than two workgroups per CU (the 28 x 28 and smaller maps of a 224 x 224 input), half the tile:
   // every output value is the same k-ordered chain whatever the tile, so the choice changes no bit of the result.
   auto tiles = [&](int bm, int bn) { return ((long)a.M + bm - 1) / bm * (a.N / bn); };
-  const bool big = tiles(128, 128) >= 512;
+  const bool big = tile ? tile == 2 : tiles(128, 128) >= 512;
   switch (a.kind) {
     case FP32_STEM: return launch_kind<FP32_STEM, 1, 2>(a, s);
-    case FP32_1X1: return big ? launch_kind<FP32_1X1, 1, 4>(a, s) : launch_kind<FP32_1X1, 1, 2>(a, s);
+    case FP32_1X1:
+      TN_REQUIRE(a.ldx >= a.K, "conv_fp32: K beyond the channel stride");
+      return big ? launch_kind<FP32_1X1, 1, 4>(a, s) : launch_kind<FP32_1X1, 1, 2>(a, s);
     case FP32_3X3:
       TN_REQUIRE(a.K == 9 * 128 && a.ldx == 128, "conv_fp32: the 3x3 reads a dense 128-channel bottleneck");
-      return tiles(256, 32) >= 512 ? launch_kind<FP32_3X3, 2, 1>(a, s) : launch_kind<FP32_3X3, 1, 1>(a, s);
+      return (tile ? tile == 2 : tiles(256, 32) >= 512) ? launch_kind<FP32_3X3, 2, 1>(a, s) : launch_kind<FP32_3X3, 1, 1>(a, s);
     case FP32_TRANS:
+      TN_REQUIRE(a.ldx >= a.K, "conv_fp32: K beyond the channel stride");
       TN_REQUIRE(2 * a.Ho <= a.H && 2 * a.Wo <= a.W, "conv_fp32: transition output larger than half its input");
       return big ? launch_kind<FP32_TRANS, 1, 4>(a, s) : launch_kind<FP32_TRANS, 1, 2>(a, s);
   }
